@@ -6,7 +6,7 @@ murmur hashes, tf / tf-idf weights, weighted MinHash, ordered bottom-S sketch), 
 candidate count, second-stage overlap scoring, accepted records delivered to the host.  The packed reads are
 resident in HBM before the timed region starts (mhap_stage_reads); record text formatting is outside it.
 
-  python bench.py --gpus 1 --steps K --warmup W [--config c1|c2|c3|c4|c4slice|c5slice]
+  python bench.py --gpus 1 --steps K --warmup W [--config c1|c2|c3|c4|c4slice|c5slice] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 N > 1 (strong scaling, same data set): rank r sketches reads r, r+N, ... and indexes them — only them; the exchange is inside
@@ -107,7 +107,13 @@ def main():
                          "per rank through the library's transport, check every rank's block and peer access, print one JSON line with "
                          "every rank's view (ncclCommCount / ncclCommUserRank / device PCI id) and exit: a fabric or rendezvous problem "
                          "shows here, not as a hang of the compute step.  Launch like the timed run (torch.distributed.run for N > 1)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the records of the last timed step as DIR/<field>.npy (float64, one file per record field, canonical "
+                         "order; a fixed hash-selected sample when they exceed 64 MB) so that two builds can be compared output for "
+                         "output.  N > 1: every rank writes its own records to DIR/rank<r>/")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (ms_per_step is the time of one timed step)")
     if args.preflight:
         raise SystemExit(preflight(args.gpus))
     if args.dry_collective:
@@ -286,6 +292,10 @@ def main():
         csum = 0
         for ln in lines:
             csum = (csum + int.from_bytes(hashlib.sha256(ln.encode()).digest()[:8], "little")) & ((1 << 64) - 1)
+    dump = None
+    if args.dump_outputs:
+        dump = dump_outputs(recs, args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}"),
+                            DUMP_MAX_BYTES // world)
 
     rdev = dev if backend == "nccl" else torch.device("cpu")
     tmax = torch.tensor([elapsed], dtype=torch.float64, device=rdev)
@@ -464,6 +474,7 @@ def main():
             "value_incl_host_pack_and_pcie": round(total_records / (sec_per_step + t_stage), 2),
             "c3": "C3 skipped: MHAP_C3_FASTA is not set" if (args.config != "c3" and W.c3_fasta_path() is None) else
                   ("this run" if args.config == "c3" else "available: run --config c3"),
+            "dump_outputs": dump,
         }
         if not args.no_cpu_baseline and world == 1 and not force_dist:
             # the N > 1 code path (collective add + sharded search through a ONE-rank RCCL communicator) timed on the same staged reads,
@@ -478,6 +489,31 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 64_000_000
+DUMP_FIELDS = [f for f in mhap_amd.api.RECORD_DTYPE.names if f != "pad"]   # what a caller of find_matches() receives, field by field
+
+
+def dump_outputs(recs, out_dir, max_bytes):
+    """The records of one step as out_dir/<field>.npy (float64: the ids, coordinates and flags are exact in it), sorted on every field
+    so that the files do not depend on the order the library delivered the records in.  Beyond max_bytes a fixed sample is kept: the
+    records with the smallest seeded hash of all their fields, a choice that depends on the set of records alone."""
+    n = len(recs)
+    cap = max(1, (max_bytes - 128 * len(DUMP_FIELDS)) // (8 * len(DUMP_FIELDS)))   # (128: the header of a .npy file)
+    if n > cap:
+        h = np.full(n, 0x5EED0D0A5EED0D0A, dtype=np.uint64)
+        with np.errstate(over="ignore"):
+            for f in DUMP_FIELDS:
+                v = np.ascontiguousarray(recs[f], dtype=np.float64 if recs.dtype[f].kind == "f" else np.int64).view(np.uint64)
+                h = (h ^ v) * np.uint64(0x9E3779B97F4A7C15) + np.uint64(0x632BE59BD9B4E019)
+                h ^= h >> np.uint64(29)
+        recs = recs[np.argpartition(h, cap - 1)[:cap]]
+    recs = recs[np.lexsort([recs[f] for f in reversed(DUMP_FIELDS)])]
+    os.makedirs(out_dir, exist_ok=True)
+    for f in DUMP_FIELDS:
+        np.save(os.path.join(out_dir, f + ".npy"), recs[f].astype(np.float64))
+    return {"dir": out_dir, "records": n, "dumped": len(recs), "sampled": n > cap, "fields": DUMP_FIELDS, "dtype": "float64"}
 
 
 def emit(obj):

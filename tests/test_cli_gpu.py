@@ -262,6 +262,32 @@ def test_bench_distributed_path_through_the_library_one_rccl_rank():
     assert r2["ranks"]["consistent"] and r2["ranks"]["world"] == 1 and r2["ranks"]["per_rank"][0]["comm_count"] == 1 and r1["ranks"] is None
 
 
+def test_bench_dump_outputs_are_the_records_of_the_timed_step(tmp_path):
+    """bench.py --dump-outputs DIR: the files hold exactly the records the line's fingerprint is taken over (its sorted record lines,
+    rebuilt from the float64 files, hash to records_sha256_sorted_lines), --steps is the number of timed steps the line reports, and a
+    run with other step counts writes the same files."""
+    import hashlib
+    import sys
+    base = ["--reads", "3000", "--length", "3000", "--error-rate", "0.05", "--no-cpu-baseline"]
+    for steps, warmup in ((1, 0), (3, 1)):
+        out = tmp_path / f"s{steps}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(out)]
+                           + base, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads(r.stdout.strip().split("\n")[-1])
+        assert d["steps"] == steps and d["ms_per_step"] > 0 and d["records_per_step"] > 1000
+        assert d["dump_outputs"]["records"] == d["records_per_step"] == d["dump_outputs"]["dumped"] and not d["dump_outputs"]["sampled"]
+        cols = {f: np.load(out / f"{f}.npy") for f in d["dump_outputs"]["fields"]}
+        assert all(c.dtype == np.float64 and len(c) == d["records_per_step"] for c in cols.values())
+        assert sum(p.stat().st_size for p in out.iterdir()) <= 64_000_000
+        recs = np.zeros(d["records_per_step"], dtype=mhap_amd.api.RECORD_DTYPE)
+        for f, c in cols.items():
+            recs[f] = c
+        lines = sorted(mhap_amd.records_to_lines(recs))
+        assert hashlib.sha256("\n".join(lines).encode()).hexdigest() == d["records_sha256_sorted_lines"]
+        assert all(np.array_equal(c, np.load(tmp_path / "s1" / f"{f}.npy")) for f, c in cols.items())
+
+
 def test_bench_preflight_says_what_an_n_gpu_run_needs():
     """bench.py --preflight: one GPU is ready (devices, the library's RCCL entry points, the IPC mode); eight on this one-GPU box are
     not, and the report names the missing devices instead of a collective hanging."""

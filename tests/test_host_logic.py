@@ -445,6 +445,35 @@ def test_bench_preflight_without_a_gpu_reports_instead_of_hanging():
     assert set(rep["checks"]) >= {"devices", "torch_rccl_backend", "library_rccl_entry_points", "peer_access", "ipc_mode"}
 
 
+def test_bench_dump_outputs_is_canonical_and_capped(tmp_path):
+    """bench.py --dump-outputs: one float64 file per record field, the same files whatever order the records arrive in, and past the
+    size cap a sample that depends on the set of records alone (a subset of them, values exact)."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(7)
+    n = 20000
+    recs = np.zeros(n, dtype=api.RECORD_DTYPE)
+    for f in bench.DUMP_FIELDS:
+        recs[f] = rng.random(n) if recs.dtype[f].kind == "f" else rng.integers(0, 1 << 20, n)
+    recs["from_id"] = rng.integers(1, 1 << 40, n)
+    shuffled = recs[rng.permutation(n)]
+
+    def load(d):
+        return {f: np.load(os.path.join(d, f + ".npy")) for f in bench.DUMP_FIELDS}
+    for max_bytes, want in ((bench.DUMP_MAX_BYTES, n), (8 * len(bench.DUMP_FIELDS) * 5000 + 128 * len(bench.DUMP_FIELDS), 5000)):
+        a = bench.dump_outputs(recs, str(tmp_path / f"a{want}"), max_bytes)
+        b = bench.dump_outputs(shuffled, str(tmp_path / f"b{want}"), max_bytes)
+        assert a["records"] == n and a["dumped"] == want and a["sampled"] == (want < n)
+        A, B = load(a["dir"]), load(b["dir"])
+        assert set(os.listdir(a["dir"])) == {f + ".npy" for f in bench.DUMP_FIELDS} and "pad" not in A
+        assert all(A[f].dtype == np.float64 and len(A[f]) == want and np.array_equal(A[f], B[f]) for f in A)
+        assert sum(os.path.getsize(os.path.join(a["dir"], x)) for x in os.listdir(a["dir"])) <= max_bytes
+        got = set(zip(*(A[f].tolist() for f in bench.DUMP_FIELDS)))
+        assert got <= set(zip(*(recs[f].astype(np.float64).tolist() for f in bench.DUMP_FIELDS))) and len(got) == want
+
+
 def test_early_reject_table_of_the_second_stage_is_exact():
     """The join kernel ends a pair early when its joined k-mers inside both windows (an upper bound of the intersection) are fewer than
     pass_min[lower bound of its k]: pass_min[k] must be the smallest intersection that reaches --threshold for ANY k' >= k, read off the
