@@ -178,6 +178,26 @@ int mhap_index_add_scan(mhap_handle* h, const mhap_fasta_scan* s);
 /* the reads of the scan as query reads against the index (-q mode, mhap_find_matches_reads), in groups */
 int mhap_find_matches_scan(mhap_handle* h, const mhap_fasta_scan* s, mhap_record_sink sink, void* user);
 
+/* Exact k-mer counting (k = 1..16) on the GPU and the `-f` repeat filter file made from it (the file FrequencyCounts reads,
+ * J/sketch/FrequencyCounts.java:63-200; MHAP itself never writes it).  A window [i, i+k) of a read counts when its k bytes are all
+ * A, C, G or T (a scanned FASTA file is upper-cased by the ingest; mhap_kmer_count_add_reads takes its bytes as they are); its value
+ * has 2 bits per base (A=0 C=1 G=2 T=3, first base most significant); canonical: min(value, value of its reverse complement).  Only
+ * the forward strand is read, and reads shorter than --min-olap-length count too.  One count per handle at a time, between _begin and
+ * _finish; index calls in between close it (MHAP_E_STATE), as does any failed add.  A k-mer seen more than 2^32 - 1 times is an error. */
+typedef struct mhap_kmer_counts mhap_kmer_counts;
+int mhap_kmer_count_begin(mhap_handle* h, int32_t k, int32_t canonical);
+int mhap_kmer_count_add_reads(mhap_handle* h, const char* bases, const int64_t* offsets, const int32_t* lengths, int64_t n);
+/* the reads of a scanned file through the ingest's pipeline (host threads pack group g + 1 while the GPU counts group g) */
+int mhap_kmer_count_add_scan(mhap_handle* h, const mhap_fasta_scan* s);
+/* ends the count: the lines are the k-mers with (double)count / total >= min_fraction, by descending count, then ascending value */
+int mhap_kmer_count_finish(mhap_handle* h, double min_fraction, mhap_kmer_counts** out);
+/* windows counted, distinct values, lines, k */
+int mhap_kmer_counts_info(const mhap_kmer_counts* c, int64_t* total, int64_t* distinct, int64_t* lines, int32_t* k);
+int mhap_kmer_counts_lines(const mhap_kmer_counts* c, uint64_t* kmers, uint64_t* counts);   /* `lines` entries each, in file order */
+/* the `-f` file: "<distinct> <lines>", then "<kmer>\t<count / total as %.10e>" per line; MHAP_E_IO when it cannot be written */
+int mhap_kmer_counts_write(const mhap_kmer_counts* c, const char* path);
+void mhap_kmer_counts_free(mhap_kmer_counts* c);
+
 /* Sketch only (no index change); outputs to caller-allocated HOST arrays, any may be NULL:
  * minhash[2n][max(1,H)], ordered[2n][S][2] (hash,pos), ordered_size[2n], status[2n].
  * Strand order: 2*i = forward, 2*i+1 = reverse complement.  Used by parity tests and the
@@ -378,6 +398,8 @@ int mhap_selftest_transpose32(uint32_t* a32);
 int mhap_selftest_pass_min(int32_t S, int32_t k2, double threshold, double* scores, int32_t* pass_min);
 int mhap_selftest_xorshift_jump(uint64_t key, int32_t nsteps, uint64_t* out);
 int mhap_selftest_xorshift_unjump(uint64_t x, int32_t nsteps, uint64_t* out);   /* the key nsteps steps before chain value x */
+/* the k-mer counter's window values of one read's bytes: out[i] / valid[i] for the window starting at i (len - k + 1 of each) */
+int mhap_selftest_kmer_windows(const char* seq, int32_t len, int32_t k, int32_t canonical, uint64_t* out, uint8_t* valid);
 /* out8 = {empty, valid(rawScore), a1, a2, b1, b2, inter, k} */
 int mhap_selftest_overlap_lane(const int32_t* A, int32_t nA, int32_t lenA, const int32_t* B, int32_t nB, int32_t lenB,
                                double max_shift, int32_t stride, int32_t* out8);

@@ -13,6 +13,8 @@ from .api import (  # noqa: F401
     FastaData,
     FastaScan,
     FrequencyCounts,
+    KmerCounts,
+    count_kmers,
     MatchResult,
     format_record,
     synth_reads,

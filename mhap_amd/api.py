@@ -66,6 +66,8 @@ EXPORTED_SYMBOLS = [
     "mhap_group_find_matches_self", "mhap_group_find_matches_reads", "mhap_group_get_stats", "mhap_abi_version", "mhap_abi_sizes",
     "mhap_index_reserve", "mhap_fasta_scan_open", "mhap_fasta_scan_free", "mhap_fasta_scan_reads", "mhap_fasta_scan_bases", "mhap_fasta_scan_info",
     "mhap_index_add_scan", "mhap_find_matches_scan", "mhap_group_add_scan",
+    "mhap_kmer_count_begin", "mhap_kmer_count_add_reads", "mhap_kmer_count_add_scan", "mhap_kmer_count_finish", "mhap_kmer_counts_info",
+    "mhap_kmer_counts_lines", "mhap_kmer_counts_write", "mhap_kmer_counts_free", "mhap_selftest_kmer_windows",
 ]
 ABI_VERSION = 3   # MHAP_ABI_VERSION of include/mhap_hip.h this binding was written against
 
@@ -109,6 +111,10 @@ def load_library(build_if_missing=True):
     lib.mhap_fasta_scan_reads.argtypes = [C.c_void_p]
     lib.mhap_fasta_scan_bases.restype = C.c_int64
     lib.mhap_fasta_scan_bases.argtypes = [C.c_void_p]
+    lib.mhap_kmer_counts_free.restype = None
+    lib.mhap_kmer_counts_free.argtypes = [C.c_void_p]
+    for name in ("mhap_kmer_counts_info", "mhap_kmer_counts_lines", "mhap_kmer_counts_write"):
+        getattr(lib, name).argtypes = [C.c_void_p] + [C.c_void_p] * {"mhap_kmer_counts_info": 4, "mhap_kmer_counts_lines": 2, "mhap_kmer_counts_write": 1}[name]
     for name in EXPORTED_SYMBOLS:
         getattr(lib, name)  # AttributeError here = header/library mismatch
     # a stale library next to newer host code (or the reverse) must not get as far as a struct copy
@@ -298,6 +304,23 @@ class FrequencyCounts:
                    repeat_idf_scale, no_tf, supress_noise, np.array(allh, dtype=np.int64), size_bloom)
 
 
+    @classmethod
+    def from_counts(cls, kc, filter_cutoff=1.0e-5, repeat_weight=0.9, repeat_idf_scale=3.0, no_tf=False, do_rc=True, supress_noise=0):
+        """The filter that from_file gives on the file kc.write() writes, without the file: the same hashes, the fractions as the
+        file's `%.10e` text parses back, the whitelist and size_bloom = kc.distinct (the header's first number)."""
+        lib = load_library()
+        offset = repeat_weight if 0.0 <= repeat_weight < 1.0 else 0.0   # MhapMain.java:346-350
+        out = C.c_int64()
+        hs = np.zeros(len(kc.kmers), dtype=np.int64)
+        for i, s in enumerate(kc.kmer_strings()):
+            b = s.encode("latin-1")
+            if lib.mhap_hash_kmer(b, C.c_int32(len(b)), C.c_int32(1 if do_rc else 0), C.byref(out)) != 0:
+                raise MhapError(f"mhap_hash_kmer failed on {s}")
+            hs[i] = out.value
+        fr = np.array([float(f"{x:.10e}") for x in kc.fractions.tolist()], dtype=np.float64)
+        return cls(hs, fr, filter_cutoff, offset, repeat_idf_scale, no_tf, supress_noise, hs.copy(), kc.distinct)
+
+
 class FastaScan:
     """A FASTA file mapped and scanned, not copied (mhap_fasta_scan_*): ids, lengths and names of its records; the index is fed from
     the mapped text in groups, host threads packing one group while the GPU sketches the previous one (MinHashSearch.add_scan)."""
@@ -346,6 +369,66 @@ class FastaScan:
             self.close()
         except Exception:
             pass
+
+
+class KmerCounts:
+    """Exact k-mer counts made on the GPU (mhap_kmer_count_*): the lines of the `-f` repeat filter file — k-mers (2 bits per base,
+    A=0 C=1 G=2 T=3, first base most significant) whose share of all counted windows is at least the min_fraction they were made
+    with, by descending count, then ascending value — and the totals of its header."""
+
+    def __init__(self, lib, ptr):
+        self._lib, self._c = lib, ptr
+        total, distinct, lines, k = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int32()
+        lib.mhap_kmer_counts_info(ptr, C.byref(total), C.byref(distinct), C.byref(lines), C.byref(k))
+        self.total, self.distinct, self.k = total.value, distinct.value, k.value
+        self.kmers = np.zeros(lines.value, dtype=np.uint64)
+        self.counts = np.zeros(lines.value, dtype=np.uint64)
+        if lines.value:
+            lib.mhap_kmer_counts_lines(ptr, _ptr(self.kmers), _ptr(self.counts))
+        self.fractions = self.counts.astype(np.float64) / float(max(self.total, 1))
+
+    def __len__(self):
+        return int(self.kmers.shape[0])
+
+    def kmer_strings(self):
+        if len(self) == 0:
+            return []
+        shifts = np.uint64(2) * np.arange(self.k - 1, -1, -1, dtype=np.uint64)
+        codes = ((self.kmers[:, None] >> shifts[None, :]) & np.uint64(3)).astype(np.uint8)
+        chars = np.frombuffer(b"ACGT", dtype=np.uint8)[codes]
+        return [r.tobytes().decode("latin-1") for r in chars]
+
+    def write(self, path):
+        """The `-f` file: "<distinct> <lines>", then "<kmer>\t<fraction %.10e>" per line (mhap_kmer_counts_write)."""
+        if not self._c:
+            raise MhapError("KmerCounts already freed")
+        if self._lib.mhap_kmer_counts_write(self._c, os.fspath(path).encode()) != 0:
+            raise MhapError(f"cannot write the k-mer filter file {path}")
+
+    def close(self):
+        if getattr(self, "_c", None):
+            self._lib.mhap_kmer_counts_free(self._c)
+            self._c = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def count_kmers(source, k=16, canonical=True, min_fraction=2.5e-6, device=0):
+    """Count the k-mers (k = 1..16) of a FastaData or a FASTA file (plain, gz or bz2; a path goes through the streamed ingest) on the GPU
+    and return the KmerCounts of the `-f` repeat filter file.  Windows with a byte other than A/C/G/T are skipped; only the forward
+    strand is read; canonical counts a k-mer together with its reverse complement under the smaller value."""
+    with MinHashSearch(MhapParams(num_hashes=1, ordered_sketch_size=1, device=device)) as ms:
+        ms.kmer_count_begin(k, canonical)
+        if isinstance(source, FastaData):
+            ms.kmer_count_add(source)
+        else:
+            with FastaScan(os.fspath(source)) as scan:
+                ms.kmer_count_add_scan(scan)
+        return ms.kmer_count_finish(min_fraction)
 
 
 class MatchResult:
@@ -469,6 +552,22 @@ class MinHashSearch:
 
     def set_stream(self, hip_stream_ptr):
         self._chk(self._lib.mhap_set_stream(self._h, C.c_void_p(hip_stream_ptr)))
+
+    # -- k-mer counting (the -f filter file) -----------------------------------------------------
+    def kmer_count_begin(self, k=16, canonical=True):
+        self._chk(self._lib.mhap_kmer_count_begin(self._h, C.c_int32(k), C.c_int32(1 if canonical else 0)))
+
+    def kmer_count_add(self, fasta):
+        self._chk(self._lib.mhap_kmer_count_add_reads(self._h, _ptr(fasta.bases), _ptr(fasta.offsets), _ptr(fasta.lengths),
+                                                      C.c_int64(len(fasta))))
+
+    def kmer_count_add_scan(self, scan):
+        self._chk(self._lib.mhap_kmer_count_add_scan(self._h, scan._s))
+
+    def kmer_count_finish(self, min_fraction=2.5e-6):
+        out = C.c_void_p()
+        self._chk(self._lib.mhap_kmer_count_finish(self._h, C.c_double(min_fraction), C.byref(out)))
+        return KmerCounts(self._lib, out)
 
     # -- index ----------------------------------------------------------------------------------
     def add_data(self, fasta):

@@ -1,6 +1,6 @@
-"""Build libmhaphip.so (gfx950) and the mhap-hip CLI in-tree with hipcc.
+"""Build libmhaphip.so (gfx950) and the mhap-hip / mhap-hip-kmers CLIs in-tree with hipcc.
 
-No CMake: six translation units, each compiled to an object of its own (side by side) and linked with one hipcc command.  The built
+No CMake: the translation units of SOURCES, each compiled to an object of its own (side by side) and linked with one hipcc command.  The built
 artefacts live under mhap_amd/lib/ (git-ignored, but shipped to the GPU box by gpurun).  An object is rebuilt whenever the SHA-256
 of its source + the headers + its command differs from the stamp written next to it, the library whenever an object changed.
 """
@@ -15,7 +15,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libmhaphip.so")
 CLI = os.path.join(LIBDIR, "mhap-hip")
-SOURCES = ["sketch_kernels.hip", "search_kernels.hip", "search_kernels_wide.hip", "search_kernels_wide2.hip", "mhap_capi.hip", "mhap_dist.hip", "mhap_ingest.hip", "host_util.cpp"]
+KMERS_CLI = os.path.join(LIBDIR, "mhap-hip-kmers")   # the -f filter file from the reads (mhap_kmers_cli.cpp)
+SOURCES = ["sketch_kernels.hip", "search_kernels.hip", "search_kernels_wide.hip", "search_kernels_wide2.hip", "mhap_capi.hip", "mhap_dist.hip", "mhap_ingest.hip", "kmer_kernels.hip", "host_util.cpp"]
 HEADERS = ["device_common.hpp", "kernels.hpp", "mhap_internal.hpp", "overlap_lane.hpp", os.path.join("..", "..", "include", "mhap_hip.h")]
 ARCH = "gfx950"
 EXTRA_DEPS = {"search_kernels_wide.hip": ["search_kernels.hip"], "search_kernels_wide2.hip": ["search_kernels.hip"]}   # (a translation unit that includes another one)
@@ -138,7 +139,7 @@ def _link(hipcc, objs, target, force, verbose):
 
 
 def build(force=False, verbose=False, variants=()):
-    """libmhaphip.so + mhap-hip; `variants`: names from VARIANTS to build as mhap_amd/lib/variants/libmhaphip_NAME.so as well."""
+    """libmhaphip.so + mhap-hip + mhap-hip-kmers; `variants`: names from VARIANTS to build as mhap_amd/lib/variants/libmhaphip_NAME.so as well."""
     os.makedirs(LIBDIR, exist_ok=True)
     try:
         hipcc = _hipcc()
@@ -152,16 +153,16 @@ def build(force=False, verbose=False, variants=()):
         raise
     objs, _ = _compile_objects(hipcc, [], [], "", force, verbose)
     dg = _link(hipcc, objs, LIB, force, verbose)
-    cli_src = os.path.join(CSRC, "mhap_cli.cpp")
-    if os.path.exists(cli_src):
-        cmd = [hipcc, "-O2", "-std=c++17", "-pthread", cli_src, "-o", CLI, f"-L{LIBDIR}", "-lmhaphip",
+    for src, exe in (("mhap_cli.cpp", CLI), ("mhap_kmers_cli.cpp", KMERS_CLI)):
+        cli_src = os.path.join(CSRC, src)
+        cmd = [hipcc, "-O2", "-std=c++17", "-pthread", cli_src, "-o", exe, f"-L{LIBDIR}", "-lmhaphip",
                "-Wl,-rpath,$ORIGIN"]
         dg_cli = _digest([cli_src, os.path.join(CSRC, HEADERS[-1])], cmd[1:] + [dg])
-        if force or _stale(CLI, dg_cli):
+        if force or _stale(exe, dg_cli):
             if verbose:
                 print(" ".join(cmd), file=sys.stderr)
             subprocess.run(cmd, check=True, cwd=CSRC)
-            _stamp(CLI, dg_cli)
+            _stamp(exe, dg_cli)
     for name in variants:
         flags, only = VARIANTS[name]
         vobjs, _ = _compile_objects(hipcc, flags, only, name, force, verbose)

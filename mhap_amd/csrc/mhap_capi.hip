@@ -150,6 +150,7 @@ struct mhap_handle {
   InvIndex inv{};   // device view of the inverted index in inv_ends / inv_items
   mhap_stage_gate gate = nullptr; void* gate_user = nullptr;   // mhap_set_second_stage_gate
   void* dist = nullptr;   // multi-GPU state (mhap_dist.hip)
+  void* kmer = nullptr;   // open k-mer count (kmer_kernels.hip)
   std::vector<mhap_record> out_recs;
 
   // timing
@@ -1151,7 +1152,7 @@ HandleView handle_view(mhap_handle* h) {
   v.device = h->device; v.stream = h->stream; v.Hrow = h->Hrow; v.S = h->P.ordered_sketch_size; v.k = h->P.kmer_size; v.min_olap_length = h->P.min_olap_length;
   v.n_entries = h->n_entries; v.index_gen = h->index_gen;
   v.d_minhash = h->d_minhash; v.d_ordered = h->d_ordered; v.d_meta = h->d_meta;
-  v.h_ids = h->ids.data(); v.h_fwd = h->fwd.data(); v.err = &h->err; v.dist = &h->dist;
+  v.h_ids = h->ids.data(); v.h_fwd = h->fwd.data(); v.err = &h->err; v.dist = &h->dist; v.kmer = &h->kmer;
   return v;
 }
 int internal_stage_packed(mhap_handle* h, const ReadDesc* descs, const int64_t* ids, int64_t n, const void* packed, size_t bytes) {
@@ -1268,6 +1269,7 @@ void mhap_destroy(mhap_handle* h) {
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   if (h->dist) { mhap_dist_release(h->dist); h->dist = nullptr; }
+  if (h->kmer) { kmer_count_release((KmerCountState*)h->kmer); h->kmer = nullptr; }
   for (auto& t : h->pending) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
   for (auto& p : h->free_events) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
   DevBuf* bufs[] = {&h->f_keys, &h->f_vals, &h->f_bloom, &h->score_tbl, &h->jump_tbl, &h->hash_luts, &h->own_minhash, &h->own_ordered, &h->own_meta, &h->d_ids, &h->store, &h->descs,

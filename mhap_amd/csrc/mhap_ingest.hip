@@ -419,3 +419,174 @@ int mhap_find_matches_scan(mhap_handle* h, const mhap_fasta_scan* s, mhap_record
 }
 
 }  // extern "C"
+
+// ---- exact k-mer counting: the C ABI (kernels and their driver: kmer_kernels.hip) ---------------------------------------------
+struct mhap_kmer_counts {
+  int32_t k = 0;
+  int64_t total = 0, distinct = 0;
+  std::vector<uint32_t> values, counts;   // the lines, in file order
+};
+
+namespace {
+
+// the open count of h, or null with the reason in h's error (a count that an index call interrupted is closed here)
+KmerCountState* kc_state(const HandleView& v, const char* what, int& rc) {
+  KmerCountState* S = (KmerCountState*)*v.kmer;
+  rc = MHAP_OK;
+  if (!S) { *v.err = std::string(what) + ": no k-mer count is open on this handle (mhap_kmer_count_begin starts one)"; rc = MHAP_E_STATE; return nullptr; }
+  if (kmer_count_index_gen(*S) != v.index_gen) {
+    *v.err = std::string(what) + ": the index changed while a k-mer count was open; the count is closed (begin it again)";
+    kmer_count_release(S); *v.kmer = nullptr; rc = MHAP_E_STATE; return nullptr;
+  }
+  return S;
+}
+// a failed add or finish closes the count: its state is partial
+int kc_close_on_error(const HandleView& v, int rc) {
+  if (rc != MHAP_OK && *v.kmer) { kmer_count_release((KmerCountState*)*v.kmer); *v.kmer = nullptr; }
+  return rc;
+}
+inline bool is_upper_base(uint8_t c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T'; }
+
+}  // namespace
+
+extern "C" {
+
+int mhap_kmer_count_begin(mhap_handle* h, int32_t k, int32_t canonical) {
+  if (!h) return MHAP_E_INVALID;
+  HandleView v = handle_view(h);
+  if (k < 1 || k > 16) { *v.err = "k-mer counting supports k from 1 to 16 (got " + std::to_string(k) + ")"; return MHAP_E_INVALID; }
+  if (*v.kmer) { *v.err = "mhap_kmer_count_begin: a k-mer count is already open on this handle (mhap_kmer_count_finish ends it)"; return MHAP_E_STATE; }
+  KmerCountState* S = nullptr;
+  const int rc = kmer_count_begin(S, v, k, canonical);
+  if (rc == MHAP_OK) *v.kmer = S;
+  return rc;
+}
+
+int mhap_kmer_count_add_reads(mhap_handle* h, const char* bases, const int64_t* offsets, const int32_t* lengths, int64_t n) {
+  if (!h) return MHAP_E_INVALID;
+  HandleView v = handle_view(h);
+  int rc;
+  KmerCountState* S = kc_state(v, "mhap_kmer_count_add_reads", rc);
+  if (!S) return rc;
+  if (n < 0 || (n > 0 && (!bases || !offsets || !lengths))) { *v.err = "mhap_kmer_count_add_reads: null argument"; return MHAP_E_INVALID; }
+  for (int64_t i = 0; i < n; i++) if (lengths[i] < 0 || offsets[i] < 0) { *v.err = "mhap_kmer_count_add_reads: negative read length or offset"; return MHAP_E_INVALID; }
+  // groups of <= 256 Mbase (and <= 2^21 reads), packed like the ingest packs them: 2 bits per base when every byte is A/C/G/T, else the bytes
+  const int nthreads = host_threads();
+  std::vector<ReadDesc> descs;
+  std::vector<uint8_t> packed;
+  for (int64_t lo = 0; lo < n;) {
+    int64_t hi = lo, tot = 0;
+    while (hi < n && (hi == lo || tot + lengths[hi] <= (256LL << 20)) && hi - lo < (1 << 21)) { tot += lengths[hi]; hi++; }
+    descs.assign((size_t)(hi - lo), ReadDesc{});
+    std::vector<uint8_t> raw((size_t)(hi - lo));
+    parallel_chunks(hi - lo, nthreads, [&](int64_t a, int64_t b, int) {
+      for (int64_t i = a; i < b; i++) {
+        const uint8_t* s = (const uint8_t*)bases + offsets[lo + i];
+        bool pure = true;
+        for (int j = 0; j < lengths[lo + i] && pure; j++) pure = is_upper_base(s[j]);
+        raw[(size_t)i] = pure ? 0 : 1;
+      }
+    });
+    int64_t store = 0;
+    for (int64_t i = 0; i < hi - lo; i++) {
+      ReadDesc& d = descs[(size_t)i];
+      d.length = lengths[lo + i];
+      d.flags = raw[(size_t)i] ? MHAP_RD_RAW : 0;
+      d.base_off = store;
+      store += raw[(size_t)i] ? align4(d.length) : align4((d.length + 3) / 4);
+    }
+    packed.assign((size_t)std::max<int64_t>(store, 4), 0);
+    parallel_chunks(hi - lo, nthreads, [&](int64_t a, int64_t b, int) {
+      for (int64_t i = a; i < b; i++) {
+        const ReadDesc& d = descs[(size_t)i];
+        const uint8_t* s = (const uint8_t*)bases + offsets[lo + i];
+        if (d.flags & MHAP_RD_RAW) memcpy(packed.data() + d.base_off, s, (size_t)d.length);
+        else pack_bases(s, d.length, packed.data() + d.base_off);
+      }
+    });
+    rc = kmer_count_add_group(*S, v, descs.data(), hi - lo, packed.data(), (size_t)store);
+    if (rc != MHAP_OK) return kc_close_on_error(v, rc);
+    lo = hi;
+  }
+  return MHAP_OK;
+}
+
+int mhap_kmer_count_add_scan(mhap_handle* h, const mhap_fasta_scan* s) {
+  if (!h) return MHAP_E_INVALID;
+  HandleView v = handle_view(h);
+  int rc;
+  KmerCountState* S = kc_state(v, "mhap_kmer_count_add_scan", rc);
+  if (!S) return rc;
+  if (!s) { *v.err = "mhap_kmer_count_add_scan: null scan"; return MHAP_E_INVALID; }
+  (void)hipSetDevice(v.device);
+  const FastaScanImpl& sc = s->impl;
+  uint64_t windows = 0;
+  for (int32_t L : sc.len) windows += (uint64_t)std::max(0, L - kmer_count_k(*S) + 1);
+  rc = kmer_count_reserve(*S, v, std::min(windows, kmer_count_budget(*S)));   // the staging arena at its size for this file (up to the flush budget) at once
+  if (rc != MHAP_OK) return kc_close_on_error(v, rc);
+  std::string err;
+  // min_olap 0: reads below --min-olap-length are counted too (the counter never skips a read)
+  rc = ingest_pipeline(sc, 0, 1, 0, false, [&](Slot& sl) {
+    return kmer_count_add_group(*S, v, sl.descs.data(), (int64_t)sl.descs.size(), sl.pin, sl.bytes);
+  }, err);
+  if (rc != MHAP_OK && !err.empty()) *v.err = err;
+  return kc_close_on_error(v, rc);
+}
+
+int mhap_kmer_count_finish(mhap_handle* h, double min_fraction, mhap_kmer_counts** out) {
+  if (!h) return MHAP_E_INVALID;
+  HandleView v = handle_view(h);
+  int rc;
+  KmerCountState* S = kc_state(v, "mhap_kmer_count_finish", rc);
+  if (!S) return rc;
+  if (!out) { *v.err = "mhap_kmer_count_finish: null output"; return MHAP_E_INVALID; }
+  if (!(min_fraction == min_fraction)) { *v.err = "mhap_kmer_count_finish: min_fraction is NaN"; return MHAP_E_INVALID; }
+  mhap_kmer_counts* c = new mhap_kmer_counts();
+  rc = kmer_count_finish(*S, v, min_fraction, c->values, c->counts, c->distinct);
+  c->k = kmer_count_k(*S);
+  c->total = kmer_count_total(*S);
+  kmer_count_release(S); *v.kmer = nullptr;
+  if (rc != MHAP_OK) { delete c; return rc; }
+  *out = c;
+  return MHAP_OK;
+}
+
+int mhap_kmer_counts_info(const mhap_kmer_counts* c, int64_t* total, int64_t* distinct, int64_t* lines, int32_t* k) {
+  if (!c) return MHAP_E_INVALID;
+  if (total) *total = c->total;
+  if (distinct) *distinct = c->distinct;
+  if (lines) *lines = (int64_t)c->values.size();
+  if (k) *k = c->k;
+  return MHAP_OK;
+}
+
+int mhap_kmer_counts_lines(const mhap_kmer_counts* c, uint64_t* kmers, uint64_t* counts) {
+  if (!c) return MHAP_E_INVALID;
+  for (size_t i = 0; i < c->values.size(); i++) {
+    if (kmers) kmers[i] = c->values[i];
+    if (counts) counts[i] = c->counts[i];
+  }
+  return MHAP_OK;
+}
+
+int mhap_kmer_counts_write(const mhap_kmer_counts* c, const char* path) {
+  if (!c || !path) return MHAP_E_INVALID;
+  FILE* f = fopen(path, "w");
+  if (!f) return MHAP_E_IO;
+  std::vector<char> buf(1 << 20);
+  setvbuf(f, buf.data(), _IOFBF, buf.size());
+  bool ok = fprintf(f, "%lld %lld\n", (long long)c->distinct, (long long)c->values.size()) > 0;
+  char km[17];
+  const double T = (double)c->total;
+  for (size_t i = 0; i < c->values.size() && ok; i++) {
+    for (int j = 0; j < c->k; j++) km[j] = "ACGT"[(c->values[i] >> (2 * (c->k - 1 - j))) & 3u];
+    km[c->k] = 0;
+    ok = fprintf(f, "%s\t%.10e\n", km, (double)c->counts[i] / T) > 0;
+  }
+  ok = (fclose(f) == 0) && ok;
+  return ok ? MHAP_OK : MHAP_E_IO;
+}
+
+void mhap_kmer_counts_free(mhap_kmer_counts* c) { delete c; }
+
+}  // extern "C"

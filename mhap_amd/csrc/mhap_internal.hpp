@@ -10,6 +10,7 @@
 #include <cstring>
 #include <string>
 #include <thread>
+#include <vector>
 
 #include "../../include/mhap_hip.h"
 
@@ -67,6 +68,7 @@ struct HandleView {
   const int64_t* h_ids; const uint8_t* h_fwd;
   std::string* err;
   void** dist;
+  void** kmer;             // the open k-mer count (kmer_kernels.hip), or null
 };
 HandleView handle_view(mhap_handle* h);
 void mhap_dist_release(void* dist_state);
@@ -97,6 +99,18 @@ int ingest_add_subset(mhap_handle* h, const FastaScanImpl* scan, int64_t start, 
 const FastaScanImpl* scan_impl(const mhap_fasta_scan* s);
 int internal_find_matches_device(mhap_handle* h, const void* d_q_minhash, const void* d_q_ordered, const void* d_q_meta, const int64_t* ids,
                                  const int64_t* d_ids_dev, int64_t m, int to_self, mhap_record_sink sink, void* user);
+// Exact k-mer counting (kmer_kernels.hip): one count per handle between mhap_kmer_count_begin and _finish
+struct KmerCountState;
+int kmer_count_begin(KmerCountState*& out, const HandleView& v, int k, int canonical);
+int kmer_count_add_group(KmerCountState& S, const HandleView& v, const ReadDesc* descs, int64_t n, const void* packed, size_t bytes);
+int kmer_count_reserve(KmerCountState& S, const HandleView& v, uint64_t windows);
+int kmer_count_finish(KmerCountState& S, const HandleView& v, double min_fraction, std::vector<uint32_t>& values, std::vector<uint32_t>& counts,
+                      int64_t& distinct);
+int64_t kmer_count_total(const KmerCountState& S);
+int kmer_count_k(const KmerCountState& S);
+uint64_t kmer_count_index_gen(const KmerCountState& S);
+uint64_t kmer_count_budget(const KmerCountState& S);   // windows staged before a flush
+void kmer_count_release(KmerCountState* S);
 int internal_sketch_queries(mhap_handle* h, const char* bases, const int64_t* offsets, const int32_t* lengths, int64_t n, void* d_mh, void* d_od, void* d_mt);
 
 }  // namespace mhap

@@ -1,0 +1,112 @@
+// mhap_kmers_cli.cpp — `mhap-hip-kmers`: counts the k-mers of FASTA files on the GPU and writes the `-f` repeat filter file that
+// `mhap-hip -f` (and MHAP's FrequencyCounts, J/sketch/FrequencyCounts.java:63-200) reads.  MHAP has no such tool; its users bring the
+// file from a k-mer counter.  Inputs are plain, gz or bz2 FASTA files or directories of them, read by the streamed ingest.
+#include <dirent.h>
+#include <sys/stat.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/mhap_hip.h"
+
+namespace {
+
+const char* USAGE =
+    "Usage: mhap-hip-kmers -o <output file> [-k 16] [--no-rc] [--min-fraction 2.5e-6] [--device 0] <FASTA file or directory> ...\n"
+    "  -o               the k-mer filter file to write (the -f file of mhap-hip)\n"
+    "  -k               k-mer size, 1 to 16 (default 16)\n"
+    "  --no-rc          count k-mers as they are read instead of canonical (the smaller of a k-mer and its reverse complement)\n"
+    "  --min-fraction   write the k-mers whose share of all counted k-mers is at least this (default 2.5e-6)\n"
+    "  --device         HIP device ordinal (default 0)\n";
+
+[[noreturn]] void die(const std::string& m) {
+  fprintf(stderr, "mhap-hip-kmers: %s\n%s", m.c_str(), USAGE);
+  exit(1);
+}
+
+double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+bool is_dir(const std::string& p) { struct stat st; return stat(p.c_str(), &st) == 0 && S_ISDIR(st.st_mode); }
+
+std::vector<std::string> list_files(const std::string& path) {   // non-hidden entries, sorted
+  std::vector<std::string> out;
+  if (!is_dir(path)) { out.push_back(path); return out; }
+  DIR* d = opendir(path.c_str());
+  if (!d) return out;
+  while (dirent* e = readdir(d)) { std::string n = e->d_name; if (n.empty() || n[0] == '.') continue; out.push_back(path + "/" + n); }
+  closedir(d);
+  std::sort(out.begin(), out.end());
+  return out;
+}
+
+bool parse_int(const char* s, long& v) { char* e = nullptr; v = strtol(s, &e, 10); return *s && e && *e == 0; }
+bool parse_double(const char* s, double& v) { char* e = nullptr; v = strtod(s, &e); return *s && e && *e == 0 && v == v; }
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  std::string out;
+  long k = 16, device = 0;
+  double min_fraction = 2.5e-6;
+  bool rc = true;
+  std::vector<std::string> inputs;
+  for (int a = 1; a < argc; a++) {
+    const std::string s = argv[a];
+    auto value = [&]() -> const char* { if (a + 1 >= argc) die("option " + s + " requires a value"); return argv[++a]; };
+    if (s == "-h" || s == "--help") { fputs(USAGE, stdout); return 0; }
+    else if (s == "-o") out = value();
+    else if (s == "-k") { if (!parse_int(value(), k)) die("-k takes an integer"); }
+    else if (s == "--no-rc") rc = false;
+    else if (s == "--min-fraction") { if (!parse_double(value(), min_fraction)) die("--min-fraction takes a number"); }
+    else if (s == "--device") { if (!parse_int(value(), device) || device < 0) die("--device takes a device ordinal"); }
+    else if (!s.empty() && s[0] == '-') die("unknown option " + s);
+    else inputs.push_back(s);
+  }
+  if (out.empty()) die("no output file (-o)");
+  if (inputs.empty()) die("no input file");
+  if (k < 1 || k > 16) die("k-mer size must be from 1 to 16 (got " + std::to_string(k) + ")");
+  const double t0 = now();
+  mhap_params p;
+  mhap_default_params(&p);
+  p.num_hashes = 1; p.ordered_sketch_size = 1;   // (no sketching here: the smallest per-handle tables)
+  p.device = (int32_t)device;
+  mhap_handle* h = nullptr;
+  char err[512] = {0};
+  if (mhap_create(&p, &h, err, sizeof err) != MHAP_OK) { fprintf(stderr, "mhap-hip-kmers: %s\n", err); return 1; }
+  auto chk = [&](int r) { if (r != MHAP_OK) { fprintf(stderr, "mhap-hip-kmers: %s (code %d)\n", mhap_last_error(h), r); mhap_destroy(h); exit(1); } };
+  chk(mhap_kmer_count_begin(h, (int32_t)k, rc ? 1 : 0));
+  int64_t reads = 0, bases = 0;
+  double t_scan = 0.0, t_count = 0.0;
+  for (const std::string& in : inputs) {
+    for (const std::string& f : list_files(in)) {
+      const double a = now();
+      mhap_fasta_scan* s = nullptr;
+      if (mhap_fasta_scan_open(f.c_str(), 0, &s, err, sizeof err) != MHAP_OK) { fprintf(stderr, "mhap-hip-kmers: %s\n", err); mhap_destroy(h); return 1; }
+      const double b = now();
+      reads += mhap_fasta_scan_reads(s); bases += mhap_fasta_scan_bases(s);
+      const int r = mhap_kmer_count_add_scan(h, s);
+      mhap_fasta_scan_free(s);
+      chk(r);
+      t_scan += b - a; t_count += now() - b;
+    }
+  }
+  mhap_kmer_counts* c = nullptr;
+  chk(mhap_kmer_count_finish(h, min_fraction, &c));
+  int64_t total = 0, distinct = 0, lines = 0;
+  int32_t kk = 0;
+  mhap_kmer_counts_info(c, &total, &distinct, &lines, &kk);
+  const double tw = now();
+  const int w = mhap_kmer_counts_write(c, out.c_str());
+  mhap_kmer_counts_free(c);
+  mhap_destroy(h);
+  if (w != MHAP_OK) { fprintf(stderr, "mhap-hip-kmers: cannot write %s\n", out.c_str()); return 1; }
+  fprintf(stderr, "Counted %lld %d-mers (%lld distinct) in %lld reads, %.1f Mbase; wrote %lld lines to %s; total %.3f s (scan %.3f s, count %.3f s, write %.3f s)\n",
+          (long long)total, (int)kk, (long long)distinct, (long long)reads, bases / 1e6, (long long)lines, out.c_str(), now() - t0, t_scan, t_count, now() - tw);
+  return 0;
+}
