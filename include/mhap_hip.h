@@ -365,6 +365,23 @@ typedef struct mhap_fasta {
 int mhap_fasta_read(const char* path, int64_t id_offset, mhap_fasta* out, char* err, size_t errcap);
 void mhap_fasta_free(mhap_fasta* f);
 
+/* Batched local alignment on the GPU: the Smith-Waterman check of EstimateROC's computeDP (J/main/EstimateROC.java:746-800), SSW's
+ * scoring as EstimateROC calls it (Aligner.align(s1, s2, MATCH_MATRIX, 2, 1, true), matrix :302-308).  bases: the reads' bytes as
+ * mhap_fasta holds them (upper-cased); pairs: n rows of 5 int64 {a_off, a_len, b_off, b_len, b_rc}.  s1 = bases[a_off, a_off + a_len),
+ * s2 = bases[b_off, b_off + b_len), reverse-complemented through Utils.rc's table (J/utils/Utils.java:496-507) when b_rc != 0.
+ *   substitution +2 when the two bytes are equal (N against N too), -2 otherwise; a gap of length L costs 2 + (L - 1):
+ *   E(i,j) = max(H(i,j-1) - 2, E(i,j-1) - 1)   deletion, consumes s2        H(i,j) = max(0, H(i-1,j-1) + sub, E(i,j), F(i,j))
+ *   F(i,j) = max(H(i-1,j) - 2, F(i-1,j) - 1)   insertion, consumes s1
+ * The path rules are this project's (SSW's cigar comes from a second banded pass; parity with it is not pinned):
+ *   end cell: the maximum H; on ties the smallest j (position in s2), then the smallest i;
+ *   predecessors: H prefers the diagonal, then E, then F; E and F prefer extension over opening on ties;
+ *   a cell with H = 0 ends every path through it; an alignment begins at a diagonal step out of an H = 0 cell.
+ * results: n rows of 7 int32 {score, read_begin, read_end, ref_begin, ref_end, columns, errors}; read_* are 0-based inclusive rows of s1,
+ * ref_* columns of s2 (as SSW reports read_begin1 ... ref_end1); columns = M + I + D of the path, errors = mismatched M columns + I + D.
+ * A pair without a positive cell (an empty segment included) gives {0, -1, -1, -1, -1, 0, 0}.  MHAP_E_INVALID for a segment outside
+ * the n_bases bases. */
+int mhap_align_pairs(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const int64_t* pairs, int64_t n, int32_t* results);
+
 /* Deterministic synthetic PacBio-style reads: xoshiro256** seeded by
  * splitmix64(seed), random genome of n*len/coverage bp, reads at uniform positions/strands with
  * i.i.d. errors (ins:del:sub = 0.1188:0.0183:0.0129 scaled to error_rate), exactly `len` bases each.
@@ -382,6 +399,17 @@ int mhap_synth_reads_repeats(uint64_t seed, int64_t n, int32_t len, double cover
  * bases[offsets[r] .. offsets[r] + lengths[r]).  Test / bench tooling (the E. coli-shaped stand-in of BASELINE configs[2]). */
 int mhap_synth_reads_genome(uint64_t seed, const uint8_t* genome, int64_t G, int64_t n, const int32_t* lengths, const int64_t* offsets,
                             double error_rate, char* bases);
+
+/* Where the synthetic reads came from (the truth EstimateROC measures overlaps against), replayed from the same per-read generators
+ * without generating a base.  lengths == NULL: the reads of mhap_synth_reads_repeats / _shard / mhap_synth_reads (n reads of `len`
+ * bases, genome of n*len/coverage bases; G is ignored; entry q is read shard + q*nshards).  lengths != NULL: the reads of
+ * mhap_synth_reads_genome from a genome of G bases (len, coverage, shard and nshards ignored; entry r is read r).  Per read: the genome
+ * position of its first consumed base, the genome bases consumed (span; the read may wrap past G on the circular genome), the strand
+ * (1 = the read is the reverse complement of genome[start, start + span)), and its inserted, deleted and substituted bases
+ * (length = span + ins - del).  A read of length <= 0 gets start -1 and zeros. */
+int mhap_synth_truth(uint64_t seed, int64_t n, int32_t len, double coverage, int64_t G, const int32_t* lengths, double error_rate,
+                     int64_t shard, int64_t nshards, int64_t* start, int64_t* span, int8_t* strand, int32_t* n_ins, int32_t* n_del,
+                     int32_t* n_sub);
 
 /* murmur3_x64_128(seed 0).h1 of one k-mer line of a `-f` filter file, canonicalised when do_rc != 0
  * (HashUtils.computeSequenceHashesLong(str, len, 0, doRC)[0], J/sketch/FrequencyCounts.java:169). */

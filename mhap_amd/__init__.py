@@ -18,6 +18,9 @@ from .api import (  # noqa: F401
     MatchResult,
     format_record,
     synth_reads,
+    synth_reads_from_genome,
+    synth_truth,
+    align_pairs,
     records_to_lines,
     load_library,
     KERNEL_NAMES,

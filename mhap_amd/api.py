@@ -68,6 +68,7 @@ EXPORTED_SYMBOLS = [
     "mhap_index_add_scan", "mhap_find_matches_scan", "mhap_group_add_scan",
     "mhap_kmer_count_begin", "mhap_kmer_count_add_reads", "mhap_kmer_count_add_scan", "mhap_kmer_count_finish", "mhap_kmer_counts_info",
     "mhap_kmer_counts_lines", "mhap_kmer_counts_write", "mhap_kmer_counts_free", "mhap_selftest_kmer_windows",
+    "mhap_synth_truth", "mhap_align_pairs",
 ]
 ABI_VERSION = 3   # MHAP_ABI_VERSION of include/mhap_hip.h this binding was written against
 
@@ -248,6 +249,60 @@ def synth_reads_from_genome(genome, lengths, seed=0x4D484150, error_rate=0.15):
     if rc != 0:
         raise MhapError(f"mhap_synth_reads_genome failed ({rc})")
     return FastaData(bases, offsets, lengths, np.arange(1, n + 1, dtype=np.int64))
+
+
+SYNTH_TRUTH_DTYPE = np.dtype([("start", "<i8"), ("span", "<i8"), ("strand", "i1"), ("ins", "<i4"), ("dels", "<i4"), ("subs", "<i4"),
+                              ("length", "<i4")])
+
+
+def synth_truth(n, length=None, seed=0x4D484150, coverage=30.0, error_rate=0.15, shard=0, nshards=1, lengths=None, genome_len=None):
+    """Where the reads of synth_reads (length=..., coverage=..., shard/nshards) or of synth_reads_from_genome (lengths=..., genome_len=...)
+    came from: mhap_synth_truth.  One SYNTH_TRUTH_DTYPE row per read: genome start, genome bases consumed (span; may wrap past the end
+    of the circular genome), strand (1 = reverse complement), inserted / deleted / substituted bases, and the read's length.
+    Returns (rows, genome length)."""
+    lib = load_library()
+    if lengths is not None:
+        lengths = np.ascontiguousarray(lengths, dtype=np.int32)
+        if genome_len is None or len(lengths) != n:
+            raise MhapError("synth_truth: the genome form needs genome_len and n == len(lengths)")
+        m, G = n, int(genome_len)
+    else:
+        if length is None:
+            raise MhapError("synth_truth: give length (synth_reads) or lengths + genome_len (synth_reads_from_genome)")
+        m = len(range(shard, n, nshards))
+        G = max(int(float(n) * float(length) / coverage), length + 1)   # mhap_synth_reads_repeats' genome length
+    start, span = np.zeros(max(m, 1), np.int64), np.zeros(max(m, 1), np.int64)
+    strand = np.zeros(max(m, 1), np.int8)
+    ins, dels, subs = (np.zeros(max(m, 1), np.int32) for _ in range(3))
+    rc = lib.mhap_synth_truth(C.c_uint64(seed), C.c_int64(n), C.c_int32(length or 0), C.c_double(coverage), C.c_int64(G if lengths is not None else 0),
+                              _ptr(lengths), C.c_double(error_rate), C.c_int64(shard), C.c_int64(nshards), _ptr(start), _ptr(span),
+                              _ptr(strand), _ptr(ins), _ptr(dels), _ptr(subs))
+    if rc != 0:
+        raise MhapError(f"mhap_synth_truth failed ({rc})")
+    out = np.zeros(m, SYNTH_TRUTH_DTYPE)
+    out["start"], out["span"], out["strand"] = start[:m], span[:m], strand[:m]
+    out["ins"], out["dels"], out["subs"] = ins[:m], dels[:m], subs[:m]
+    out["length"] = lengths if lengths is not None else length
+    return out, G
+
+
+def align_pairs(bases, pairs, device=0, handle=None):
+    """Local alignments of many segment pairs on the GPU (mhap_align_pairs; its header comment is the contract).  bases: uint8 array
+    (FastaData.bases); pairs: int64 array (n, 5) of (a_off, a_len, b_off, b_len, b_rc).  Returns an int32 array (n, 7) of
+    (score, read_begin, read_end, ref_begin, ref_end, columns, errors).  handle: a MinHashSearch whose device to use (else one is made)."""
+    bases = np.ascontiguousarray(bases, dtype=np.uint8)
+    pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 5))
+    out = np.zeros((len(pairs), 7), dtype=np.int32)
+    if len(pairs) == 0:
+        return out
+    own = handle is None
+    ms = MinHashSearch(MhapParams(num_hashes=1, ordered_sketch_size=1, device=device)) if own else handle
+    try:
+        ms._chk(ms._lib.mhap_align_pairs(ms._h, _ptr(bases), C.c_int64(len(bases)), _ptr(pairs), C.c_int64(len(pairs)), _ptr(out)))
+    finally:
+        if own:
+            ms.close()
+    return out
 
 
 class FrequencyCounts:

@@ -394,6 +394,52 @@ int mhap_synth_reads_genome(uint64_t seed, const uint8_t* genome, int64_t G, int
   return MHAP_OK;
 }
 
+// Where each synthetic read came from: the per-read generator of mhap_synth_reads_repeats (lengths == NULL: n reads of `len` bases from
+// the genome of n*len/coverage bases, reads shard, shard+nshards, ...) or of mhap_synth_reads_genome (lengths != NULL: G given, len,
+// coverage and the shard ignored), replayed draw for draw without writing a base.  The genome's bases never steer a draw, so neither
+// the genome nor the repeat family is needed.
+int mhap_synth_truth(uint64_t seed, int64_t n, int32_t len, double coverage, int64_t G, const int32_t* lengths, double error_rate,
+                     int64_t shard, int64_t nshards, int64_t* start, int64_t* span, int8_t* strand, int32_t* n_ins, int32_t* n_del,
+                     int32_t* n_sub) {
+  if (n < 0 || error_rate < 0.0 || error_rate >= 1.0 || !start || !span || !strand || !n_ins || !n_del || !n_sub) return MHAP_E_INVALID;
+  if (!lengths) {
+    if (len <= 0 || coverage <= 0.0 || nshards < 1 || shard < 0 || shard >= nshards) return MHAP_E_INVALID;
+    G = std::max<int64_t>((int64_t)((double)n * (double)len / coverage), (int64_t)len + 1);   // as mhap_synth_reads_repeats sizes it
+  } else {
+    if (G < 1) return MHAP_E_INVALID;
+    shard = 0; nshards = 1;
+  }
+  if (n == 0) return MHAP_OK;
+  const double p_ins = error_rate * (0.1188 / 0.15), p_del = error_rate * (0.0183 / 0.15), p_sub = error_rate * (0.0129 / 0.15);
+  const int nthreads = (int)std::max<int64_t>(1, std::min<int64_t>(mhap::usable_host_threads(32), n));
+  std::vector<std::thread> th;
+  for (int t = 0; t < nthreads; t++) {
+    th.emplace_back([&, t]() {
+      for (int64_t q = t; shard + q * nshards < n; q += nthreads) {
+        const int64_t r = shard + q * nshards;
+        const int rl = lengths ? lengths[r] : len;
+        if (rl <= 0) { start[q] = -1; span[q] = 0; strand[q] = 0; n_ins[q] = n_del[q] = n_sub[q] = 0; continue; }   // no generator drawn
+        Xoshiro256ss g(SplitMix64{seed ^ (0x9e3779b97f4a7c15ULL * (uint64_t)(r + 1))}.next());
+        start[q] = (int64_t)g.below((uint64_t)G);
+        strand[q] = (int8_t)((g.next() >> 63) != 0);
+        int w = 0, ni = 0, nd = 0, ns = 0;
+        int64_t used = 0;
+        while (w < rl) {
+          const double u = g.unit();
+          if (u < p_ins) { (void)g.next(); w++; ni++; continue; }
+          used++;
+          if (u < p_ins + p_del) { nd++; continue; }
+          if (u < p_ins + p_del + p_sub) { (void)g.next(); w++; ns++; continue; }
+          w++;
+        }
+        span[q] = used; n_ins[q] = ni; n_del[q] = nd; n_sub[q] = ns;
+      }
+    });
+  }
+  for (auto& x : th) x.join();
+  return MHAP_OK;
+}
+
 // new FrequencyCounts(reader, filterCutoff, offset, removeUnique, noTf, numThreads, range, doRC) (J/sketch/FrequencyCounts.java:63-229)
 int mhap_set_filter_file(mhap_handle* h, const char* path, double filter_cutoff, double offset, int32_t remove_unique, int32_t no_tf,
                          double range, int32_t do_rc, char* kmer_sizes, size_t kmer_sizes_cap) {

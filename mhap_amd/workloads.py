@@ -130,6 +130,33 @@ def write_fasta(fasta, path, prefix="r"):
             fh.write(b"\n")
 
 
+def write_truth_m4(path, truth, genome_len, chrom="synth", ids=None):
+    """The reads' true positions (mhap_amd.synth_truth rows) as the BLASR M4 file EstimateROC's processReference reads
+    (J/main/EstimateROC.java:548-627), one line per read:
+        qname chrom score idy 0 0 len len tstrand tstart tend genome_len
+    qname is the read's 1-based ordinal (ids[q], default q + 1: what mhap-hip prints without --store-full-id); the read is the query,
+    forward, whole; tstrand 1 marks a reverse read, its tstart / tend on the reverse strand (genome_len - end, genome_len - start), so that
+    processReference's flip gives back the forward [start, start + span); idy = 100 (1 - (ins + del + sub) / (len + del)); score
+    = -(len - ins - sub), the read's aligned bases, negative as BLASR's (lower is better).  Reads that wrap past the end of the circular
+    genome (start + span > genome_len) have no single interval and are left out; so are reads of length 0.  Returns how many wrapped."""
+    G = int(genome_len)
+    wrapped = 0
+    with open(path, "w") as fh:
+        for q, r in enumerate(truth):
+            start, span, ln = int(r["start"]), int(r["span"]), int(r["length"])
+            if start < 0 or ln <= 0:
+                continue
+            if start + span > G:
+                wrapped += 1
+                continue
+            ins, dl, sb = int(r["ins"]), int(r["dels"]), int(r["subs"])
+            idy = 100.0 * (1.0 - (ins + dl + sb) / float(ln + dl))
+            ts, te = (G - start - span, G - start) if r["strand"] else (start, start + span)
+            qname = int(ids[q]) if ids is not None else q + 1
+            fh.write(f"{qname} {chrom} {-(ln - ins - sb)} {idy:.4f} 0 0 {ln} {ln} {int(r['strand'])} {ts} {te} {G}\n")
+    return wrapped
+
+
 _CODE = np.full(256, 255, dtype=np.uint8)
 for _i, _c in enumerate(b"ACGT"):
     _CODE[_c] = _i
