@@ -382,6 +382,71 @@ void mhap_fasta_free(mhap_fasta* f);
  * the n_bases bases. */
 int mhap_align_pairs(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const int64_t* pairs, int64_t n, int32_t* results);
 
+/* KmerStatSimulator's pair statistics on the GPU (J/main/KmerStatSimulator.java:163-196).  pairs: n rows of 4 int64 {a_off, a_len,
+ * b_off, b_len}; a = bases[a_off, a_off + a_len) is the first read, b the second.  skip: n_skip k-mers of k bytes each, back to back, in
+ * any order (the skip set of loadSkipMers; entries of another length never match and are left out by the caller).  For each pair,
+ * out[3 q ..] = {shared, total, intersect}:
+ *   shared    = the distinct k-mers of b that are among the distinct k-mers of a not in the skip set (compareKmers' `shared`);
+ *   total     = the distinct k-mers of a and b together (compareKmers' `totalSeqs`);
+ *   intersect = BottomSketch.jaccard's intersectCount: the bottom sketch of a read is the min(bottom_k, windows) smallest signed
+ *               murmur3_x86_32(seed 0) values of its canonical k-mers (String.compareTo of the k-mer against Utils.rc of it), duplicates
+ *               kept, and the count comes from Java's merge loop run for min(sketch sizes) steps.
+ * Exact for any bytes and any k >= 1 (k-mers are compared byte for byte); a read shorter than k has no windows.  MHAP_E_INVALID for a
+ * segment outside the n_bases bases.  The environment variable MHAP_KSIM_HASH_BITS=b (1..64, tests only) narrows the kernel's internal
+ * 64-bit window key to b bits, so that different k-mers share keys and the byte comparison decides. */
+int mhap_pair_kmer_stats(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const int64_t* pairs, int64_t n, int32_t k,
+                         int32_t bottom_k, const uint8_t* skip, int64_t n_skip, int32_t* out, int32_t* paths);
+/* paths (may be NULL): n int32, the scratch each pair took: 1 = LDS (the pair's keys fit min(device LDS per workgroup, 160 KiB)), 2 = a
+ * per-workgroup slice of HBM.  The kernel is chosen by segment length and key kind, never by an option.  The smallest bottom_k hashes of
+ * each read come from a full sort of its hashes in that scratch (a radix select of them would do less work; not built).
+ * mhap_ksim_dev_create / _destroy: the same statistics with device buffers kept (grow-only) across calls, for a simulation's chunks;
+ * mhap_ksim_dev_pair_stats takes mhap_pair_kmer_stats's arguments after the session. */
+void* mhap_ksim_dev_create(mhap_handle* h);
+void mhap_ksim_dev_destroy(void* dev);
+int mhap_ksim_dev_pair_stats(void* dev, const uint8_t* bases, int64_t n_bases, const int64_t* pairs, int64_t n, int32_t k, int32_t bottom_k,
+                             const uint8_t* skip, int64_t n_skip, int32_t* out, int32_t* paths);
+/* KmerStatSimulator's trials generated on the device (--rng device): trials trial0 .. trial0 + n - 1 of the stream `seed`, with
+ * mhap_ksim_create's meaning of length, offset, the rates, flags and the reference records.  Java's rules, not its stream:
+ *   - every draw is splitmix64 of a counter keyed by (seed, trial, role, index, slot) — seed -> splitmix64; ^ trial -> splitmix64;
+ *     ^ (role << 32 | slot) -> splitmix64; ^ index -> splitmix64 — so a trial's reads do not depend on the launch shape or the chunk;
+ *   - roles 0 / 1 / 2: the walks of the first read / shared partner / random partner over their 2L source bases (index = source base;
+ *     slot 3v, 3v + 1, 3v + 2 = the error test, the error type and the new base of visit v); role 3: base i of a trial's random 4L sequence
+ *     (no reference; "ACGT"[r >> 62]); role 4: base i of the random partner without a reference; role 5: the picks (index = draw count);
+ *   - per visit: the error test (u < errorRate, u = top 53 bits * 2^-53), then the type in Java's order: substitution (one of the other
+ *     three of ACGT; a non-ACGT base: one of all four), insertion (a uniform base, the same source base visited again), deletion;
+ *   - per-base emission counts are prefix-summed into positions; the first read keeps the last L bases, the partners the first L;
+ *   - picks: a record is redrawn until it has 4L (first read) or 2L (random partner) bases, the random partner's position while it
+ *     overlaps the first read on the same record (Utils.getRangeOverlap > 0); without a reference firstPos = 0 and the random partner
+ *     is L uniform bases without errors.
+ * stats: n x 2 x 3 int32, mhap_pair_kmer_stats of (first, shared partner) and (first, random partner) on the reads where the generator
+ * wrote them (not with MHAP_KSIM_SIM_ONLY).  Test hooks (each may be NULL): reads n x roles x L bytes, meta n x 5 as mhap_ksim_next's,
+ * events n x roles x 4 int32 = {insertions, deletions, substitutions, visits} of each walk.  A read shorter than L after its errors
+ * (Java's StringIndexOutOfBoundsException) gives MHAP_E_INVALID and *failed_trial = the first such trial. */
+int mhap_ksim_dev_trials(void* dev, uint64_t seed, int64_t trial0, int64_t n, int32_t length, int32_t offset, double error_rate,
+                         double ins_pct, double del_pct, double sub_pct, int32_t flags, const uint8_t* ref_bases,
+                         const int64_t* ref_offsets, const int32_t* ref_lengths, int64_t n_ref, int32_t k, int32_t bottom_k,
+                         const uint8_t* skip, int64_t n_skip, int32_t* stats, uint8_t* reads, int32_t* meta, int32_t* events,
+                         int64_t* failed_trial);
+/* Which scratch each pair of mhap_pair_kmer_stats would take with lds_bytes of LDS per workgroup: path[q] = 1 (LDS) or 2 (HBM).
+ * hashed != 0: the pair has a non-ACGT byte or k > 31 (its keys carry a position word).  Tests only. */
+int mhap_pair_kmer_stats_paths(const int64_t* pairs, int64_t n, int32_t k, int64_t lds_bytes, int32_t hashed, int32_t* path);
+
+/* KmerStatSimulator's trials with its own java.util.Random stream (host only; the stream is sequential).  mhap_ksim_create(seed, L,
+ * offset = (int) (2 * requestedLength - overlap), errorRate and the three error percentages, flags, reference records): the records are
+ * upper-cased with N removed by the caller; n_ref = 0 simulates without a reference (buildRandomSequence(4L), firstPos = 0).
+ * mhap_ksim_next writes the next n_trials trials: reads[t][role][L] with role 0 = first read, 1 = shared partner, 2 = random partner
+ * (role 0 only with MHAP_KSIM_SIM_ONLY), and meta[t][5] = {seqID, firstPos, secondPos, random seqID, random pos}.  It returns the
+ * number of trials completed; fewer than n_trials means Java threw in the next one: mhap_ksim_error gives the exception text and the
+ * role whose getSequence threw ("" when none).  The caller checks that a reference has a record of at least 4L bases first (Java
+ * would loop forever) and that the error mix terminates. */
+#define MHAP_KSIM_ONE_SIDED 1     /* the second reads are walked at error rate 0 */
+#define MHAP_KSIM_SIM_ONLY 2      /* only the first read of each trial (Usage 2, or k < 0) */
+void* mhap_ksim_create(int64_t seed, int32_t length, int32_t offset, double error_rate, double ins_pct, double del_pct, double sub_pct,
+                       int32_t flags, const uint8_t* ref_bases, const int64_t* ref_offsets, const int32_t* ref_lengths, int64_t n_ref);
+int64_t mhap_ksim_next(void* state, int64_t n_trials, uint8_t* reads, int32_t* meta);
+const char* mhap_ksim_error(void* state, int32_t* role);
+void mhap_ksim_destroy(void* state);
+
 /* Deterministic synthetic PacBio-style reads: xoshiro256** seeded by
  * splitmix64(seed), random genome of n*len/coverage bp, reads at uniform positions/strands with
  * i.i.d. errors (ins:del:sub = 0.1188:0.0183:0.0129 scaled to error_rate), exactly `len` bases each.

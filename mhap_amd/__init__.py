@@ -21,7 +21,16 @@ from .api import (  # noqa: F401
     synth_reads_from_genome,
     synth_truth,
     align_pairs,
+    pair_kmer_stats,
     records_to_lines,
     load_library,
     KERNEL_NAMES,
 )
+
+
+def __getattr__(name):
+    # KmerStatSimulator's API, imported on first use so that `python -m mhap_amd.kmer_sim` runs a module not yet imported
+    if name in ("simulate_pairs", "simulate_reads"):
+        from . import kmer_sim
+        return getattr(kmer_sim, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

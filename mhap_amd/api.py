@@ -69,6 +69,8 @@ EXPORTED_SYMBOLS = [
     "mhap_kmer_count_begin", "mhap_kmer_count_add_reads", "mhap_kmer_count_add_scan", "mhap_kmer_count_finish", "mhap_kmer_counts_info",
     "mhap_kmer_counts_lines", "mhap_kmer_counts_write", "mhap_kmer_counts_free", "mhap_selftest_kmer_windows",
     "mhap_synth_truth", "mhap_align_pairs",
+    "mhap_pair_kmer_stats", "mhap_pair_kmer_stats_paths", "mhap_ksim_create", "mhap_ksim_next", "mhap_ksim_error", "mhap_ksim_destroy",
+    "mhap_ksim_dev_create", "mhap_ksim_dev_destroy", "mhap_ksim_dev_pair_stats", "mhap_ksim_dev_trials",
 ]
 ABI_VERSION = 3   # MHAP_ABI_VERSION of include/mhap_hip.h this binding was written against
 
@@ -116,6 +118,24 @@ def load_library(build_if_missing=True):
     lib.mhap_kmer_counts_free.argtypes = [C.c_void_p]
     for name in ("mhap_kmer_counts_info", "mhap_kmer_counts_lines", "mhap_kmer_counts_write"):
         getattr(lib, name).argtypes = [C.c_void_p] + [C.c_void_p] * {"mhap_kmer_counts_info": 4, "mhap_kmer_counts_lines": 2, "mhap_kmer_counts_write": 1}[name]
+    lib.mhap_ksim_create.restype = C.c_void_p
+    lib.mhap_ksim_create.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    lib.mhap_ksim_next.restype = C.c_int64
+    lib.mhap_ksim_next.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.mhap_ksim_error.restype = C.c_char_p
+    lib.mhap_ksim_error.argtypes = [C.c_void_p, C.c_void_p]
+    lib.mhap_ksim_destroy.restype = None
+    lib.mhap_ksim_destroy.argtypes = [C.c_void_p]
+    lib.mhap_ksim_dev_create.restype = C.c_void_p
+    lib.mhap_ksim_dev_create.argtypes = [C.c_void_p]
+    lib.mhap_ksim_dev_destroy.restype = None
+    lib.mhap_ksim_dev_destroy.argtypes = [C.c_void_p]
+    lib.mhap_ksim_dev_pair_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                             C.c_int64, C.c_void_p, C.c_void_p]
+    lib.mhap_ksim_dev_trials.argtypes = [C.c_void_p, C.c_uint64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                         C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                         C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     for name in EXPORTED_SYMBOLS:
         getattr(lib, name)  # AttributeError here = header/library mismatch
     # a stale library next to newer host code (or the reverse) must not get as far as a struct copy
@@ -303,6 +323,81 @@ def align_pairs(bases, pairs, device=0, handle=None):
         if own:
             ms.close()
     return out
+
+
+def _skip_bytes(skip, k):
+    """skip k-mers (str or bytes) -> (uint8 array of the length-k ones back to back or None, their count)."""
+    sk = [x.encode("latin-1") if isinstance(x, str) else bytes(x) for x in skip]
+    sk = b"".join(x for x in sk if len(x) == k)
+    return (np.frombuffer(sk, dtype=np.uint8) if sk else None), len(sk) // k
+
+
+class KsimDevice:
+    """A KmerStatSimulator session on one device (mhap_ksim_dev_*): device buffers kept across its calls."""
+
+    def __init__(self, device=0, handle=None):
+        self._own = handle is None
+        self.ms = MinHashSearch(MhapParams(num_hashes=1, ordered_sketch_size=1, device=device)) if self._own else handle
+        self._lib = self.ms._lib
+        self.d = self._lib.mhap_ksim_dev_create(self.ms._h)
+        if not self.d:
+            err = self.ms._lib.mhap_last_error(self.ms._h)
+            self.close()
+            raise MhapError(err.decode() if err else "mhap_ksim_dev_create failed")
+
+    def pair_stats(self, bases, pairs, k, bottom_k=1256, skip=(), paths=False):
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 4))
+        out = np.zeros((len(pairs), 3), dtype=np.int32)
+        pth = np.zeros(len(pairs), dtype=np.int32)
+        if len(pairs):
+            skb, ns = _skip_bytes(skip, k)
+            self.ms._chk(self._lib.mhap_ksim_dev_pair_stats(self.d, _ptr(bases), len(bases), _ptr(pairs), len(pairs), k, bottom_k, _ptr(skb),
+                                                            ns, _ptr(out), _ptr(pth)))
+        return (out, pth) if paths else out
+
+    def trials(self, seed, trial0, n, L, offset, err, pi, pd, ps, flags, ref, k, bottom_k, skip, want_reads=False):
+        """mhap_ksim_dev_trials: (stats (n, 2, 3) or None, reads (n, roles, L) or None, meta (n, 5), events (n, roles, 4))."""
+        roles = 1 if flags & 2 else 3
+        stats = None if flags & 2 else np.zeros((n, 2, 3), dtype=np.int32)
+        reads = np.zeros((n, roles, L), dtype=np.uint8) if want_reads else None
+        meta = np.zeros((n, 5), dtype=np.int32)
+        events = np.zeros((n, roles, 4), dtype=np.int32)
+        b, off, ln = ref
+        skb, ns = _skip_bytes(skip, k) if k >= 1 else (None, 0)
+        failed = C.c_int64(-1)
+        rc = self._lib.mhap_ksim_dev_trials(self.d, seed, trial0, n, L, offset, err, pi, pd, ps, flags, _ptr(b), _ptr(off), _ptr(ln),
+                                            0 if off is None else len(off), max(k, 1), bottom_k, _ptr(skb), ns, _ptr(stats), _ptr(reads),
+                                            _ptr(meta), _ptr(events), C.byref(failed))
+        if rc != 0:
+            msg = self._lib.mhap_last_error(self.ms._h)
+            raise MhapError((msg.decode() if msg else f"mhap_ksim_dev_trials failed ({rc})"), failed.value)
+        return stats, reads, meta, events
+
+    def close(self):
+        if getattr(self, "d", None):
+            self._lib.mhap_ksim_dev_destroy(self.d)
+            self.d = None
+        if self._own and self.ms is not None:
+            self.ms.close()
+            self.ms = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def pair_kmer_stats(bases, pairs, k, bottom_k=1256, skip=(), device=0, handle=None, paths=False):
+    """KmerStatSimulator's compareKmers / compareMinHash counts of many segment pairs on the GPU (mhap_pair_kmer_stats; its header comment
+    is the contract).  bases: uint8 array; pairs: int64 array (n, 4) of (a_off, a_len, b_off, b_len); skip: k-mers (str or bytes) left
+    out of `shared` (entries whose length is not k never match).  Returns an int32 array (n, 3) of (shared, total, intersect), and with
+    paths=True also the scratch each pair took on the device (1 = LDS, 2 = HBM).  handle: a MinHashSearch or a KsimDevice to use."""
+    if isinstance(handle, KsimDevice):
+        return handle.pair_stats(bases, pairs, k, bottom_k, skip, paths)
+    with KsimDevice(device, handle) as d:
+        return d.pair_stats(bases, pairs, k, bottom_k, skip, paths)
 
 
 class FrequencyCounts:

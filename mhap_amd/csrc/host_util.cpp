@@ -494,3 +494,156 @@ int mhap_set_filter_file(mhap_handle* h, const char* path, double filter_cutoff,
 }
 
 }  // extern "C"
+
+// ---- KmerStatSimulator's trials, replayed draw for draw (J/main/KmerStatSimulator.java) -----------------------------------------------
+namespace {
+
+// java.util.Random: the 48-bit LCG, next(bits), nextDouble and nextInt(bound)
+struct JavaRandom {
+  uint64_t s;
+  explicit JavaRandom(int64_t seed) : s(((uint64_t)seed ^ 0x5DEECE66DULL) & ((1ULL << 48) - 1)) {}
+  int32_t next(int bits) {
+    s = (s * 0x5DEECE66DULL + 0xBULL) & ((1ULL << 48) - 1);
+    return (int32_t)(uint32_t)(s >> (48 - bits));
+  }
+  double next_double() { return (double)(((int64_t)next(26) << 27) + next(27)) * 0x1.0p-53; }
+  int32_t next_int(int32_t bound) {   // bound > 0 (checked by the caller)
+    int32_t r = next(31);
+    const int32_t m = bound - 1;
+    if ((bound & m) == 0) return (int32_t)(((int64_t)bound * (int64_t)r) >> 31);
+    for (int32_t u = r; (int32_t)((uint32_t)u - (uint32_t)(r = u % bound) + (uint32_t)m) < 0; u = next(31)) {}
+    return r;
+  }
+};
+
+struct KsimState {
+  JavaRandom g;
+  int32_t L, offset, one_sided, sim_only;
+  double err, ins, del, sub;
+  std::vector<std::string> recs;   // upper-cased, N removed (the caller's job)
+  std::string error;
+  int32_t error_role = -1;
+  explicit KsimState(int64_t seed) : g(seed) {}
+
+  char random_base(int exclude) {   // getRandomBase (:185-206): redraw while the base equals the excluded char
+    for (;;) {
+      const double b = g.next_double();
+      const char r = b < 0.25 ? 'A' : b < 0.5 ? 'C' : b < 0.75 ? 'G' : 'T';
+      if (exclude < 0 || exclude != r) return r;
+    }
+  }
+  // getSequence (:215-276): the 2L window from pos (wrapped from the start of `seq`), mutated by the ListIterator walk, trimmed to L
+  bool get_sequence(const std::string& seq, int32_t pos, double e, double pi, double pd, double ps, bool trim_right, char* out) {
+    (void)pd;
+    const int64_t n = (int64_t)seq.size(), two = 2 * (int64_t)L;
+    std::string w = seq.substr((size_t)pos, (size_t)(std::min<int64_t>(n, pos + two) - pos));
+    if ((int64_t)w.size() < two) w += seq.substr(0, (size_t)std::min<int64_t>(n, two - (int64_t)w.size()));
+    std::string m;
+    m.reserve(w.size() + w.size() / 4 + 16);
+    size_t i = 0;
+    while (i < w.size()) {
+      const char c = w[i];
+      if (g.next_double() < e) {
+        const double t = g.next_double();
+        if (t < ps) { m.push_back(random_base((unsigned char)c)); i++; }
+        else if (t < pi + ps) m.push_back(random_base(-1));          // previous(); add(x): the same base is visited again
+        else i++;                                                       // remove()
+      } else {
+        m.push_back(c);
+        i++;
+      }
+    }
+    const int64_t len = (int64_t)m.size();
+    if (len < L) {   // String.substring's StringIndexOutOfBoundsException
+      const int64_t b = trim_right ? 0 : len - L, en = trim_right ? L : len;
+      error = "java.lang.StringIndexOutOfBoundsException: begin " + std::to_string(b) + ", end " + std::to_string(en) + ", length " +
+              std::to_string(len);
+      return false;
+    }
+    memcpy(out, m.data() + (trim_right ? 0 : len - L), (size_t)L);
+    return true;
+  }
+  std::string random_sequence(int64_t n) {   // buildRandomSequence (:154-161)
+    std::string s((size_t)n, 'A');
+    for (int64_t i = 0; i < n; i++) s[(size_t)i] = random_base(-1);
+    return s;
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+void* mhap_ksim_create(int64_t seed, int32_t length, int32_t offset, double error_rate, double ins_pct, double del_pct, double sub_pct,
+                       int32_t flags, const uint8_t* ref_bases, const int64_t* ref_offsets, const int32_t* ref_lengths, int64_t n_ref) {
+  if (length < 0 || n_ref < 0 || (n_ref > 0 && (!ref_offsets || !ref_lengths)) || n_ref > INT32_MAX) return nullptr;
+  KsimState* s = new KsimState(seed);
+  s->L = length; s->offset = offset;
+  s->err = error_rate; s->ins = ins_pct; s->del = del_pct; s->sub = sub_pct;
+  s->one_sided = (flags & MHAP_KSIM_ONE_SIDED) != 0;
+  s->sim_only = (flags & MHAP_KSIM_SIM_ONLY) != 0;
+  for (int64_t r = 0; r < n_ref; r++) s->recs.emplace_back((const char*)ref_bases + ref_offsets[r], (size_t)ref_lengths[r]);
+  return s;
+}
+
+void mhap_ksim_destroy(void* state) { delete (KsimState*)state; }
+
+const char* mhap_ksim_error(void* state, int32_t* role) {
+  KsimState* s = (KsimState*)state;
+  if (role) *role = s->error_role;
+  return s->error.c_str();
+}
+
+int64_t mhap_ksim_next(void* state, int64_t n_trials, uint8_t* reads, int32_t* meta) {
+  KsimState* s = (KsimState*)state;
+  if (!s || n_trials < 0 || (n_trials > 0 && (!reads || !meta))) return MHAP_E_INVALID;
+  if (!s->error.empty()) return 0;
+  const int64_t L = s->L, nroles = s->sim_only ? 1 : 3;
+  const bool ref = !s->recs.empty();
+  const double e2 = s->one_sided ? 0.0 : s->err, i2 = s->one_sided ? 0.0 : s->ins, d2 = s->one_sided ? 0.0 : s->del,
+               p2 = s->one_sided ? 0.0 : s->sub;
+  for (int64_t t = 0; t < n_trials; t++) {
+    char* out = (char*)reads + t * nroles * L;
+    int32_t* mt = meta + 5 * t;
+    int32_t first_pos = 0, seq_id = 0;
+    std::string gen;
+    const std::string* seq;
+    if (ref) {
+      const int32_t nrec = (int32_t)s->recs.size();
+      do { seq_id = s->g.next_int(nrec); seq = &s->recs[(size_t)seq_id]; } while ((int64_t)seq->size() < 4 * L);
+      first_pos = s->g.next_int((int32_t)seq->size());
+    } else {
+      gen = s->random_sequence(4 * L);
+      seq = &gen;
+    }
+    mt[0] = seq_id; mt[1] = first_pos; mt[2] = mt[3] = mt[4] = 0;
+    s->error_role = 0;
+    if (!s->get_sequence(*seq, first_pos, s->err, s->ins, s->del, s->sub, false, out)) return t;
+    if (s->sim_only) continue;
+    if (seq->empty()) { s->error_role = 1; s->error = "java.lang.ArithmeticException: / by zero"; return t; }
+    const int32_t second_pos = (int32_t)(((int64_t)first_pos + s->offset) % (int64_t)seq->size());
+    mt[2] = second_pos;
+    s->error_role = 1;
+    if (!s->get_sequence(*seq, second_pos, e2, i2, d2, p2, true, out + L)) return t;
+    s->error_role = 2;
+    if (ref) {
+      const int32_t nrec = (int32_t)s->recs.size();
+      int32_t sid;
+      const std::string* sq;
+      do { sid = s->g.next_int(nrec); sq = &s->recs[(size_t)sid]; } while ((int64_t)sq->size() < 2 * L);
+      int32_t pos = s->g.next_int((int32_t)sq->size());
+      // Utils.getRangeOverlap(firstPos, firstPos + L, pos, pos + L) > 0 on the same record: redraw
+      while (seq_id == sid && std::min<int64_t>(first_pos + L, pos + L) - std::max<int64_t>(first_pos, pos) + 1 > 0)
+        pos = s->g.next_int((int32_t)sq->size());
+      mt[3] = sid; mt[4] = pos;
+      if (!s->get_sequence(*sq, pos, e2, i2, d2, p2, true, out + 2 * L)) return t;
+    } else {
+      const std::string r = s->random_sequence(L);
+      memcpy(out + 2 * L, r.data(), (size_t)L);
+    }
+    s->error_role = -1;
+  }
+  return n_trials;
+}
+
+}  // extern "C"

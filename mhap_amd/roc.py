@@ -33,7 +33,7 @@ class RocError(RuntimeError):
 
 # ---- java.util.Random ------------------------------------------------------------------------------------------------------
 class JavaRandom:
-    """java.util.Random: the 48-bit LCG, next(bits), nextInt() and nextInt(bound) with its power-of-two and rejection branches."""
+    """java.util.Random: the 48-bit LCG, next(bits), nextDouble(), nextInt() and nextInt(bound) with its power-of-two and rejection branches."""
     MULT, ADD, MASK = 0x5DEECE66D, 0xB, (1 << 48) - 1
 
     def __init__(self, seed=0):
@@ -43,6 +43,9 @@ class JavaRandom:
         self.seed = (self.seed * self.MULT + self.ADD) & self.MASK
         r = self.seed >> (48 - bits)
         return r - (1 << 32) if r >= 1 << 31 else r     # (int) of the top `bits` bits
+
+    def next_double(self):
+        return ((self.next(26) << 27) + self.next(27)) * 2.0 ** -53
 
     def next_int(self, bound=None):
         if bound is None:
