@@ -216,10 +216,8 @@ extern "C" int mhap_align_pairs(mhap_handle* h, const uint8_t* bases, int64_t n_
   // HBM rows between passes: 10 words per column of s2, one set per workgroup of the big kernel
   int64_t n_max_multi = 0;
   for (int32_t q : big) if (pairs[5 * (int64_t)q + 1] > (int64_t)NWB * 64 * AL_R) n_max_multi = std::max(n_max_multi, pairs[5 * (int64_t)q + 3]);
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, v.device) != hipSuccess) { *v.err = "mhap_align_pairs: hipGetDeviceProperties failed"; return MHAP_E_HIP; }
-  int grid_big = (int)std::min<int64_t>((int64_t)big.size(), 2LL * prop.multiProcessorCount);
-  const int grid_small = (int)std::min<int64_t>((int64_t)small.size(), 8LL * prop.multiProcessorCount);
+  int grid_big = (int)std::min<int64_t>((int64_t)big.size(), 2LL * v.num_cus);   // (the handle's compute units: MHAP_NUM_CUS caps them)
+  const int grid_small = (int)std::min<int64_t>((int64_t)small.size(), 8LL * v.num_cus);
   const int64_t stride = 10 * n_max_multi;
   if (stride > 0) {
     const int64_t budget = (int64_t)2 << 30;   // at most 2 GiB of pass boundaries: fewer big workgroups in flight beyond that

@@ -474,7 +474,7 @@ extern "C" void* mhap_ksim_dev_create(mhap_handle* h) {
   KsDev* d = new KsDev;
   d->h = h;
   d->lds_cap = std::min<int64_t>((int64_t)prop.sharedMemPerBlock, 160 * 1024) - 64;
-  d->cus = prop.multiProcessorCount;
+  d->cus = v.num_cus;   // (the handle's compute units: MHAP_NUM_CUS caps them)
   return d;
 }
 

@@ -1149,7 +1149,7 @@ int search_core(mhap_handle* h, QuerySide& qs, const std::vector<int32_t>& ql_in
 namespace mhap {
 HandleView handle_view(mhap_handle* h) {
   HandleView v;
-  v.device = h->device; v.stream = h->stream; v.Hrow = h->Hrow; v.S = h->P.ordered_sketch_size; v.k = h->P.kmer_size; v.min_olap_length = h->P.min_olap_length;
+  v.device = h->device; v.stream = h->stream; v.num_cus = h->num_cus; v.Hrow = h->Hrow; v.S = h->P.ordered_sketch_size; v.k = h->P.kmer_size; v.min_olap_length = h->P.min_olap_length;
   v.n_entries = h->n_entries; v.index_gen = h->index_gen;
   v.d_minhash = h->d_minhash; v.d_ordered = h->d_ordered; v.d_meta = h->d_meta;
   v.h_ids = h->ids.data(); v.h_fwd = h->fwd.data(); v.err = &h->err; v.dist = &h->dist; v.kmer = &h->kmer;
@@ -1233,7 +1233,7 @@ int mhap_create(const mhap_params* params, mhap_handle** out, char* err, size_t 
   h->device = dev;
   if ((e = hipSetDevice(dev)) != hipSuccess) { seterr(hipGetErrorString(e)); delete h; return MHAP_E_HIP; }
   hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, dev) == hipSuccess) h->num_cus = std::max(1, prop.multiProcessorCount);
+  h->num_cus = capped_num_cus(hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : h->num_cus);   // (MHAP_NUM_CUS)
   if ((e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking)) != hipSuccess) { seterr(hipGetErrorString(e)); delete h; return MHAP_E_HIP; }
   h->stream = h->own_stream;
   if (hipStreamCreateWithFlags(&h->mh_stream, hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking) != hipSuccess ||

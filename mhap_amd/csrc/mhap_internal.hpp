@@ -33,6 +33,19 @@ inline int usable_host_threads(int hard_cap = 64) {
   return (int)std::max(1u, std::min(hc, (unsigned)hard_cap));
 }
 
+// Compute units the persistent grids are sized for: the device's count, lowered by MHAP_NUM_CUS=n (tests: small grids, so that every
+// persistent worker takes several items and its per-item resets are exercised).  Never raised; unset, not a number or n < 1: ignored.
+// Read at every call: tests switch it between handles inside one process.
+inline int capped_num_cus(int device_cus) {
+  int n = std::max(1, device_cus);
+  if (const char* e = getenv("MHAP_NUM_CUS")) {
+    char* end = nullptr;
+    const long v = strtol(e, &end, 10);
+    if (end != e && *end == '\0' && v >= 1 && v < n) n = (int)v;
+  }
+  return n;
+}
+
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
@@ -61,6 +74,7 @@ struct DevBuf {
 // through mhap_dist_release).
 struct HandleView {
   int device; hipStream_t stream;
+  int num_cus;             // compute units the handle's persistent grids are sized for (capped_num_cus)
   int Hrow, S, k, min_olap_length;
   int64_t n_entries;
   uint64_t index_gen;      // bumped by every change of the entry set
