@@ -191,11 +191,23 @@ int mhap_kmer_count_add_reads(mhap_handle* h, const char* bases, const int64_t* 
 int mhap_kmer_count_add_scan(mhap_handle* h, const mhap_fasta_scan* s);
 /* ends the count: the lines are the k-mers with (double)count / total >= min_fraction, by descending count, then ascending value */
 int mhap_kmer_count_finish(mhap_handle* h, double min_fraction, mhap_kmer_counts** out);
+/* the same with flags (0: exactly mhap_kmer_count_finish; unknown bits: MHAP_E_INVALID, the count stays open).  MHAP_KMER_HISTOGRAM
+ * also keeps the histogram of the final counts, made on the device in the same pass: for every count c >= 1, the number of distinct
+ * values counted c times (the lines and the `-f` file are the same with it as without it). */
+#define MHAP_KMER_HISTOGRAM 1
+int mhap_kmer_count_finish_flags(mhap_handle* h, double min_fraction, uint32_t flags, mhap_kmer_counts** out);
 /* windows counted, distinct values, lines, k */
 int mhap_kmer_counts_info(const mhap_kmer_counts* c, int64_t* total, int64_t* distinct, int64_t* lines, int32_t* k);
 int mhap_kmer_counts_lines(const mhap_kmer_counts* c, uint64_t* kmers, uint64_t* counts);   /* `lines` entries each, in file order */
 /* the `-f` file: "<distinct> <lines>", then "<kmer>\t<count / total as %.10e>" per line; MHAP_E_IO when it cannot be written */
 int mhap_kmer_counts_write(const mhap_kmer_counts* c, const char* path);
+/* The histogram (counts made with MHAP_KMER_HISTOGRAM; else MHAP_E_STATE and *n = 0): n entries in ascending count, nonzero ones only;
+ * the numbers sum to `distinct` and count x number sums to `total`.  _write_histogram writes "<count>\t<number>\n" per entry, the
+ * k-mer count histogram GetHistogramStats reads (J/main/GetHistogramStats.java:50-55: Integer.parseInt of column 0, Long.parseLong of
+ * column 1; a count above 2^31 - 1 ends its reading there); MHAP_E_IO when the file cannot be written. */
+int mhap_kmer_counts_histogram_size(const mhap_kmer_counts* c, int64_t* n);
+int mhap_kmer_counts_histogram(const mhap_kmer_counts* c, uint32_t* counts, uint64_t* numbers);
+int mhap_kmer_counts_write_histogram(const mhap_kmer_counts* c, const char* path);
 void mhap_kmer_counts_free(mhap_kmer_counts* c);
 
 /* Sketch only (no index change); outputs to caller-allocated HOST arrays, any may be NULL:
@@ -475,6 +487,13 @@ int mhap_synth_reads_genome(uint64_t seed, const uint8_t* genome, int64_t G, int
 int mhap_synth_truth(uint64_t seed, int64_t n, int32_t len, double coverage, int64_t G, const int32_t* lengths, double error_rate,
                      int64_t shard, int64_t nshards, int64_t* start, int64_t* span, int8_t* strand, int32_t* n_ins, int32_t* n_del,
                      int32_t* n_sub);
+
+/* GetHistogramStats.process() (J/main/GetHistogramStats.java:63-90) on a histogram already read: n rows (count vals[r], number
+ * numbers[r]) in the TreeMap's order (ascending, distinct vals).  One Welford step per k-mer, numbers[r] steps per row (a number <= 0
+ * steps none), in double with Java's rounding (no contraction): mean, stdev = sqrt(variance / k-mers) (NaN when there are none), and
+ * cut = the first count whose running share of all occurrences, sum of (double)val * number over sum of val per k-mer, is above
+ * percent (:81-89; 0 when none is). */
+int mhap_histogram_stats(const int32_t* vals, const int64_t* numbers, int64_t n, double percent, double* mean, double* stdev, int64_t* cut);
 
 /* murmur3_x64_128(seed 0).h1 of one k-mer line of a `-f` filter file, canonicalised when do_rc != 0
  * (HashUtils.computeSequenceHashesLong(str, len, 0, doRC)[0], J/sketch/FrequencyCounts.java:169). */

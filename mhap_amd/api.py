@@ -68,10 +68,13 @@ EXPORTED_SYMBOLS = [
     "mhap_index_add_scan", "mhap_find_matches_scan", "mhap_group_add_scan",
     "mhap_kmer_count_begin", "mhap_kmer_count_add_reads", "mhap_kmer_count_add_scan", "mhap_kmer_count_finish", "mhap_kmer_counts_info",
     "mhap_kmer_counts_lines", "mhap_kmer_counts_write", "mhap_kmer_counts_free", "mhap_selftest_kmer_windows",
+    "mhap_kmer_count_finish_flags", "mhap_kmer_counts_histogram_size", "mhap_kmer_counts_histogram", "mhap_kmer_counts_write_histogram",
+    "mhap_histogram_stats",
     "mhap_synth_truth", "mhap_align_pairs",
     "mhap_pair_kmer_stats", "mhap_pair_kmer_stats_paths", "mhap_ksim_create", "mhap_ksim_next", "mhap_ksim_error", "mhap_ksim_destroy",
     "mhap_ksim_dev_create", "mhap_ksim_dev_destroy", "mhap_ksim_dev_pair_stats", "mhap_ksim_dev_trials",
 ]
+MHAP_KMER_HISTOGRAM = 1   # mhap_kmer_count_finish_flags
 ABI_VERSION = 3   # MHAP_ABI_VERSION of include/mhap_hip.h this binding was written against
 
 
@@ -116,8 +119,10 @@ def load_library(build_if_missing=True):
     lib.mhap_fasta_scan_bases.argtypes = [C.c_void_p]
     lib.mhap_kmer_counts_free.restype = None
     lib.mhap_kmer_counts_free.argtypes = [C.c_void_p]
-    for name in ("mhap_kmer_counts_info", "mhap_kmer_counts_lines", "mhap_kmer_counts_write"):
-        getattr(lib, name).argtypes = [C.c_void_p] + [C.c_void_p] * {"mhap_kmer_counts_info": 4, "mhap_kmer_counts_lines": 2, "mhap_kmer_counts_write": 1}[name]
+    for name, nargs in (("mhap_kmer_counts_info", 4), ("mhap_kmer_counts_lines", 2), ("mhap_kmer_counts_write", 1),
+                        ("mhap_kmer_counts_histogram_size", 1), ("mhap_kmer_counts_histogram", 2), ("mhap_kmer_counts_write_histogram", 1)):
+        getattr(lib, name).argtypes = [C.c_void_p] + [C.c_void_p] * nargs
+    lib.mhap_histogram_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mhap_ksim_create.restype = C.c_void_p
     lib.mhap_ksim_create.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
@@ -524,7 +529,9 @@ class FastaScan:
 class KmerCounts:
     """Exact k-mer counts made on the GPU (mhap_kmer_count_*): the lines of the `-f` repeat filter file — k-mers (2 bits per base,
     A=0 C=1 G=2 T=3, first base most significant) whose share of all counted windows is at least the min_fraction they were made
-    with, by descending count, then ascending value — and the totals of its header."""
+    with, by descending count, then ascending value — and the totals of its header.  `histogram` (when asked for at finish, else
+    None): (counts uint32, numbers uint64), for every count that occurs, in ascending order, the number of distinct k-mers counted
+    that many times."""
 
     def __init__(self, lib, ptr):
         self._lib, self._c = lib, ptr
@@ -536,6 +543,13 @@ class KmerCounts:
         if lines.value:
             lib.mhap_kmer_counts_lines(ptr, _ptr(self.kmers), _ptr(self.counts))
         self.fractions = self.counts.astype(np.float64) / float(max(self.total, 1))
+        self.histogram = None
+        nh = C.c_int64()
+        if lib.mhap_kmer_counts_histogram_size(ptr, C.byref(nh)) == 0:
+            hc, hn = np.zeros(nh.value, dtype=np.uint32), np.zeros(nh.value, dtype=np.uint64)
+            if nh.value:
+                lib.mhap_kmer_counts_histogram(ptr, _ptr(hc), _ptr(hn))
+            self.histogram = (hc, hn)
 
     def __len__(self):
         return int(self.kmers.shape[0])
@@ -555,6 +569,16 @@ class KmerCounts:
         if self._lib.mhap_kmer_counts_write(self._c, os.fspath(path).encode()) != 0:
             raise MhapError(f"cannot write the k-mer filter file {path}")
 
+    def write_histogram(self, path):
+        """The k-mer count histogram: "<count>\t<number>" per line in ascending count (mhap_kmer_counts_write_histogram), the file
+        `python -m mhap_amd.histogram_stats` reads."""
+        if not self._c:
+            raise MhapError("KmerCounts already freed")
+        if self.histogram is None:
+            raise MhapError("these counts were made without the histogram (kmer_count_finish(..., histogram=True))")
+        if self._lib.mhap_kmer_counts_write_histogram(self._c, os.fspath(path).encode()) != 0:
+            raise MhapError(f"cannot write the k-mer count histogram {path}")
+
     def close(self):
         if getattr(self, "_c", None):
             self._lib.mhap_kmer_counts_free(self._c)
@@ -567,10 +591,11 @@ class KmerCounts:
             pass
 
 
-def count_kmers(source, k=16, canonical=True, min_fraction=2.5e-6, device=0):
+def count_kmers(source, k=16, canonical=True, min_fraction=2.5e-6, device=0, histogram=False):
     """Count the k-mers (k = 1..16) of a FastaData or a FASTA file (plain, gz or bz2; a path goes through the streamed ingest) on the GPU
     and return the KmerCounts of the `-f` repeat filter file.  Windows with a byte other than A/C/G/T are skipped; only the forward
-    strand is read; canonical counts a k-mer together with its reverse complement under the smaller value."""
+    strand is read; canonical counts a k-mer together with its reverse complement under the smaller value.  histogram=True also
+    keeps the k-mer count histogram (KmerCounts.histogram), made on the GPU in the same pass."""
     with MinHashSearch(MhapParams(num_hashes=1, ordered_sketch_size=1, device=device)) as ms:
         ms.kmer_count_begin(k, canonical)
         if isinstance(source, FastaData):
@@ -578,7 +603,7 @@ def count_kmers(source, k=16, canonical=True, min_fraction=2.5e-6, device=0):
         else:
             with FastaScan(os.fspath(source)) as scan:
                 ms.kmer_count_add_scan(scan)
-        return ms.kmer_count_finish(min_fraction)
+        return ms.kmer_count_finish(min_fraction, histogram=histogram)
 
 
 class MatchResult:
@@ -714,9 +739,12 @@ class MinHashSearch:
     def kmer_count_add_scan(self, scan):
         self._chk(self._lib.mhap_kmer_count_add_scan(self._h, scan._s))
 
-    def kmer_count_finish(self, min_fraction=2.5e-6):
+    def kmer_count_finish(self, min_fraction=2.5e-6, histogram=False):
         out = C.c_void_p()
-        self._chk(self._lib.mhap_kmer_count_finish(self._h, C.c_double(min_fraction), C.byref(out)))
+        if histogram:
+            self._chk(self._lib.mhap_kmer_count_finish_flags(self._h, C.c_double(min_fraction), C.c_uint32(MHAP_KMER_HISTOGRAM), C.byref(out)))
+        else:
+            self._chk(self._lib.mhap_kmer_count_finish(self._h, C.c_double(min_fraction), C.byref(out)))
         return KmerCounts(self._lib, out)
 
     # -- index ----------------------------------------------------------------------------------

@@ -588,6 +588,37 @@ void* mhap_ksim_create(int64_t seed, int32_t length, int32_t offset, double erro
 
 void mhap_ksim_destroy(void* state) { delete (KsimState*)state; }
 
+// GetHistogramStats.process() (J/main/GetHistogramStats.java:63-90), literally: the Welford loop is one dependent step per k-mer, so it
+// is run here rather than in Python; without contraction, as Java evaluates it (variance += delta * (val - mean) is no FMA).
+int mhap_histogram_stats(const int32_t* vals, const int64_t* numbers, int64_t n, double percent, double* mean_out, double* stdev_out,
+                         int64_t* cut_out) {
+#pragma clang fp contract(off)
+  if (n < 0 || (n > 0 && (!vals || !numbers)) || !mean_out || !stdev_out || !cut_out) return MHAP_E_INVALID;
+  double variance = 0, sum = 0, mean = 0;
+  int64_t total = 0;
+  for (int64_t r = 0; r < n; r++) {                  // :68-77
+    const int32_t val = vals[r];
+    const int64_t count = numbers[r];
+    for (int64_t i = 0; i < count; i++) {
+      total++;
+      const double delta = (double)val - mean;
+      mean += delta / (double)total;
+      variance += delta * ((double)val - mean);
+      sum += (double)val;
+    }
+  }
+  variance /= (double)total;                         // :78-79 (0 / 0: NaN)
+  const double stdev = std::sqrt(variance);
+  int64_t cut = 0;
+  double running = 0;
+  for (int64_t r = 0; r < n; r++) {                  // :81-89
+    running += (double)vals[r] * (double)numbers[r];
+    if (running / sum > percent) { cut = vals[r]; break; }
+  }
+  *mean_out = mean; *stdev_out = stdev; *cut_out = cut;
+  return MHAP_OK;
+}
+
 const char* mhap_ksim_error(void* state, int32_t* role) {
   KsimState* s = (KsimState*)state;
   if (role) *role = s->error_role;

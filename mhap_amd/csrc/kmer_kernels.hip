@@ -10,7 +10,9 @@
 //   4. kmer_count_kernel    one workgroup per bucket: the bucket's 2^L counters in LDS (128 KiB at L = 15), the counts kept from earlier
 //                           flushes and the bucket's segments of every staged group folded in with LDS atomics; then either the kept
 //                           counts are written back (sparse: (low bits, count) of the values seen), or, at finish, the bucket's distinct
-//                           values are counted and the (value, count) pairs at or above the line threshold are emitted
+//                           values are counted and the (value, count) pairs at or above the line threshold are emitted; the
+//                           histogram finish (kmer_count_kernel<2>) also bins every final count: counts 1..4096 in LDS, merged into
+//                           a global histogram by nonzero bin, larger counts to a tail list (one entry per value)
 // Each bucket is owned by one workgroup, so the counts need no global atomics.  Staging is 2 bytes per window; it is flushed into the
 // kept counts when the next group would pass a budget (a quarter of the free HBM), so every allocation is sized by the input.
 #include <hip/hip_runtime.h>
@@ -55,6 +57,7 @@ constexpr int KC_THREADS = 256;     // hist / scatter workgroups: 4 waves, one r
 constexpr int KC_COUNT_THREADS = 1024;
 constexpr int KC_SCAN_THREADS = 1024;
 constexpr int KC_LDS = 1 << 15;
+constexpr int KC_HIST_DENSE = 4096;  // histogram finish: counts 1..4096 binned in LDS (16 KiB beside cnt[]'s 128 KiB: one workgroup per CU either way)
 
 // The windows [s, e) of the lane's share of read rd, each passed to emit(value).
 template <class F>
@@ -154,16 +157,23 @@ struct KcCountArgs {
   uint2* kept_out; const uint64_t* kept_out_off; uint32_t* kept_out_n;      // FINISH = 0: the counts to keep
   uint32_t* distinct; uint2* sel; unsigned long long* nsel; uint64_t sel_cap; uint32_t thr;   // FINISH = 1: (value, count >= thr)
   int* overflow;
+  // FINISH = 2, the histogram: dense[c - 1] += distinct values with count c (c <= KC_HIST_DENSE, merged by nonzero bin); every count
+  // above that goes to tail[] (at most total / (KC_HIST_DENSE + 1) entries: each such value holds more than KC_HIST_DENSE windows)
+  unsigned long long* dense; uint32_t* tail; unsigned long long* ntail; uint64_t tail_cap;
 };
 
-// Step 4: one workgroup per bucket.
+// Step 4: one workgroup per bucket.  FINISH = 0: a flush, 1: the finish, 2: the finish with the histogram.
 template <int FINISH>
 __global__ __launch_bounds__(KC_COUNT_THREADS) void kmer_count_kernel(KcCountArgs a) {
   __shared__ uint32_t cnt[KC_LDS];
   __shared__ uint32_t cursor;
+  __shared__ uint32_t bins[FINISH == 2 ? KC_HIST_DENSE : 1];   // (unused below FINISH = 2, so not allocated there)
   const int b = blockIdx.x, t = threadIdx.x, lane = t & (MHAP_WAVE - 1);
   const int nv = 1 << a.L;
   for (int i = t; i < nv; i += KC_COUNT_THREADS) cnt[i] = 0u;
+  if constexpr (FINISH == 2) {
+    for (int i = t; i < KC_HIST_DENSE; i += KC_COUNT_THREADS) bins[i] = 0u;
+  }
   if (t == 0) cursor = 0u;
   __syncthreads();
   const uint64_t k0 = a.kept_off[b];
@@ -187,6 +197,18 @@ __global__ __launch_bounds__(KC_COUNT_THREADS) void kmer_count_kernel(KcCountArg
       const unsigned long long nz = __ballot(c > 0u);
       if (lane == 0 && nz) atomicAdd(&cursor, (uint32_t)__popcll(nz));
     }
+    if constexpr (FINISH == 2) {
+      // count 1, the most common one, once per wave; the other dense counts one LDS atomic per value; the rest to the tail
+      const unsigned long long ones = __ballot(c == 1u), big = __ballot(c > (uint32_t)KC_HIST_DENSE);
+      if (lane == 0 && ones) atomicAdd(&bins[0], (uint32_t)__popcll(ones));
+      if (c > 1u && c <= (uint32_t)KC_HIST_DENSE) atomicAdd(&bins[c - 1u], 1u);
+      if (big) {
+        unsigned long long at = 0;
+        if (lane == 0) at = atomicAdd(a.ntail, (unsigned long long)__popcll(big));
+        at = __shfl(at, 0) + (unsigned long long)__popcll(big & ((1ULL << lane) - 1ULL));
+        if (c > (uint32_t)KC_HIST_DENSE && at < a.tail_cap) a.tail[at] = c;
+      }
+    }
     if (!m) continue;
     const uint32_t before = (uint32_t)__popcll(m & ((1ULL << lane) - 1ULL));
     if (FINISH) {
@@ -202,6 +224,12 @@ __global__ __launch_bounds__(KC_COUNT_THREADS) void kmer_count_kernel(KcCountArg
     }
   }
   __syncthreads();
+  if constexpr (FINISH == 2) {
+    for (int i = t; i < KC_HIST_DENSE; i += KC_COUNT_THREADS) {
+      const uint32_t n = bins[i];
+      if (n) atomicAdd(a.dense + i, (unsigned long long)n);
+    }
+  }
   if (t == 0) {
     if (FINISH) a.distinct[b] = cursor;
     else a.kept_out_n[b] = cursor;
@@ -217,9 +245,10 @@ struct KmerCountState {
   uint64_t arena_used = 0;      // windows staged since the last flush
   uint64_t budget = 0;          // windows staged before a flush
   int flushes = 0;
-  DevBuf store, descs, hist, segs, flush_n, arena, kept, kept_off, kept_n, kept2, kept2_off, kept2_n, scalars, distinct, sel;
+  DevBuf store, descs, hist, segs, flush_n, arena, kept, kept_off, kept_n, kept2, kept2_off, kept2_n, scalars, distinct, sel, hdense, htail;
   ~KmerCountState() {
-    DevBuf* bufs[] = {&store, &descs, &hist, &segs, &flush_n, &arena, &kept, &kept_off, &kept_n, &kept2, &kept2_off, &kept2_n, &scalars, &distinct, &sel};
+    DevBuf* bufs[] = {&store, &descs, &hist, &segs, &flush_n, &arena, &kept, &kept_off, &kept_n, &kept2, &kept2_off, &kept2_n, &scalars, &distinct, &sel,
+                      &hdense, &htail};
     for (DevBuf* b : bufs) b->release();
   }
 };
@@ -237,7 +266,7 @@ namespace {
 
 bool kc_prof() { return getenv("MHAP_HOST_PROF") != nullptr; }
 
-// scalars: [0] group total, [1] kept room total, [2] selected pairs, [3] overflow flag (as int)
+// scalars: [0] group total, [1] kept room total, [2] selected pairs, [3] overflow flag (as int), [4] histogram tail entries
 int kc_flush(KmerCountState& S, const HandleView& v) {
   if (S.ngroups == 0) return MHAP_OK;
   hipStream_t st = v.stream;
@@ -353,7 +382,7 @@ uint64_t kmer_line_threshold(uint64_t total, double mf) {
 }
 
 int kmer_count_finish(KmerCountState& S, const HandleView& v, double min_fraction, std::vector<uint32_t>& values, std::vector<uint32_t>& counts,
-                      int64_t& distinct) {
+                      int64_t& distinct, KmerHistogram* histogram) {
   (void)hipSetDevice(v.device);
   hipStream_t st = v.stream;
   const uint64_t total = (uint64_t)S.total;
@@ -371,15 +400,34 @@ int kmer_count_finish(KmerCountState& S, const HandleView& v, double min_fractio
   a.distinct = S.distinct.as<uint32_t>(); a.sel = S.sel.as<uint2>(); a.nsel = sc + 2; a.sel_cap = cap;
   a.thr = (uint32_t)std::min<uint64_t>(thr, 0xFFFFFFFFull);
   a.overflow = (int*)(sc + 3);
-  kmer_count_kernel<1><<<S.NB, KC_COUNT_THREADS, 0, st>>>(a);
+  // the histogram: a count above the dense range holds more than KC_HIST_DENSE windows, so at most total / (KC_HIST_DENSE + 1) values have one
+  const uint64_t tail_cap = std::min<uint64_t>(total / (KC_HIST_DENSE + 1), space);
+  std::vector<unsigned long long> dense;
+  unsigned long long ntail = 0;
+  if (histogram) {
+    KCHK(v, S.hdense.ensure((size_t)KC_HIST_DENSE * 8));
+    KCHK(v, S.htail.ensure(std::max<uint64_t>(tail_cap, 1) * 4));
+    KCHK(v, hipMemsetAsync(S.hdense.p, 0, (size_t)KC_HIST_DENSE * 8, st));
+    KCHK(v, hipMemsetAsync(sc + 4, 0, 8, st));
+    a.dense = S.hdense.as<unsigned long long>(); a.tail = S.htail.as<uint32_t>(); a.ntail = sc + 4; a.tail_cap = tail_cap;
+    kmer_count_kernel<2><<<S.NB, KC_COUNT_THREADS, 0, st>>>(a);
+    dense.resize(KC_HIST_DENSE);
+  } else {
+    kmer_count_kernel<1><<<S.NB, KC_COUNT_THREADS, 0, st>>>(a);
+  }
   KCHK(v, hipGetLastError());
   unsigned long long tail[2] = {0, 0};
   KCHK(v, hipMemcpyAsync(tail, sc + 2, 16, hipMemcpyDeviceToHost, st));
   std::vector<uint32_t> dist((size_t)S.NB);
   KCHK(v, hipMemcpyAsync(dist.data(), S.distinct.p, (size_t)S.NB * 4, hipMemcpyDeviceToHost, st));
+  if (histogram) {
+    KCHK(v, hipMemcpyAsync(dense.data(), S.hdense.p, (size_t)KC_HIST_DENSE * 8, hipMemcpyDeviceToHost, st));
+    KCHK(v, hipMemcpyAsync(&ntail, sc + 4, 8, hipMemcpyDeviceToHost, st));
+  }
   KCHK(v, hipStreamSynchronize(st));
   if ((int)tail[1]) { *v.err = "a k-mer occurs more than 4294967295 times: its count would overflow the counter"; return MHAP_E_INVALID; }
   if (tail[0] > cap) { *v.err = "k-mer counter: more selected k-mers than the bound (internal error)"; return MHAP_E_HIP; }
+  if (ntail > tail_cap) { *v.err = "k-mer counter: more histogram tail entries than the bound (internal error)"; return MHAP_E_HIP; }
   distinct = 0;
   for (uint32_t d : dist) distinct += d;
   std::vector<uint2> sel((size_t)tail[0]);
@@ -388,8 +436,23 @@ int kmer_count_finish(KmerCountState& S, const HandleView& v, double min_fractio
   std::sort(sel.begin(), sel.end(), [](const uint2& x, const uint2& y) { return x.y != y.y ? x.y > y.y : x.x < y.x; });
   values.resize(sel.size()); counts.resize(sel.size());
   for (size_t i = 0; i < sel.size(); i++) { values[i] = sel[i].x; counts[i] = sel[i].y; }
+  if (histogram) {
+    // ascending count, nonzero entries only: the dense range, then the tail's counts (sorted) with their multiplicities
+    std::vector<uint32_t> big((size_t)ntail);
+    if (!big.empty()) KCHK(v, hipMemcpy(big.data(), S.htail.p, big.size() * 4, hipMemcpyDeviceToHost));
+    std::sort(big.begin(), big.end());
+    histogram->counts.clear(); histogram->numbers.clear();
+    for (int c = 1; c <= KC_HIST_DENSE; c++)
+      if (dense[(size_t)c - 1]) { histogram->counts.push_back((uint32_t)c); histogram->numbers.push_back(dense[(size_t)c - 1]); }
+    for (size_t i = 0; i < big.size(); i++) {
+      if (i == 0 || big[i] != big[i - 1]) { histogram->counts.push_back(big[i]); histogram->numbers.push_back(0); }
+      histogram->numbers.back()++;
+    }
+  }
   if (kc_prof()) fprintf(stderr, "[kmer] finish: %llu windows, %lld distinct, %zu lines (count >= %llu), %d flushes before\n", (unsigned long long)total,
                          (long long)distinct, sel.size(), (unsigned long long)thr, S.flushes);
+  if (kc_prof() && histogram)
+    fprintf(stderr, "[kmer] histogram: %zu counts, %llu tail entries (bound %llu)\n", histogram->counts.size(), ntail, (unsigned long long)tail_cap);
   return MHAP_OK;
 }
 

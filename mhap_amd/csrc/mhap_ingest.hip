@@ -425,6 +425,8 @@ struct mhap_kmer_counts {
   int32_t k = 0;
   int64_t total = 0, distinct = 0;
   std::vector<uint32_t> values, counts;   // the lines, in file order
+  bool has_histogram = false;
+  KmerHistogram histogram;                // (when asked for at finish)
 };
 
 namespace {
@@ -534,6 +536,10 @@ int mhap_kmer_count_add_scan(mhap_handle* h, const mhap_fasta_scan* s) {
 }
 
 int mhap_kmer_count_finish(mhap_handle* h, double min_fraction, mhap_kmer_counts** out) {
+  return mhap_kmer_count_finish_flags(h, min_fraction, 0, out);
+}
+
+int mhap_kmer_count_finish_flags(mhap_handle* h, double min_fraction, uint32_t flags, mhap_kmer_counts** out) {
   if (!h) return MHAP_E_INVALID;
   HandleView v = handle_view(h);
   int rc;
@@ -541,8 +547,10 @@ int mhap_kmer_count_finish(mhap_handle* h, double min_fraction, mhap_kmer_counts
   if (!S) return rc;
   if (!out) { *v.err = "mhap_kmer_count_finish: null output"; return MHAP_E_INVALID; }
   if (!(min_fraction == min_fraction)) { *v.err = "mhap_kmer_count_finish: min_fraction is NaN"; return MHAP_E_INVALID; }
+  if (flags & ~(uint32_t)MHAP_KMER_HISTOGRAM) { *v.err = "mhap_kmer_count_finish_flags: unknown flags " + std::to_string(flags); return MHAP_E_INVALID; }
   mhap_kmer_counts* c = new mhap_kmer_counts();
-  rc = kmer_count_finish(*S, v, min_fraction, c->values, c->counts, c->distinct);
+  c->has_histogram = (flags & MHAP_KMER_HISTOGRAM) != 0;
+  rc = kmer_count_finish(*S, v, min_fraction, c->values, c->counts, c->distinct, c->has_histogram ? &c->histogram : nullptr);
   c->k = kmer_count_k(*S);
   c->total = kmer_count_total(*S);
   kmer_count_release(S); *v.kmer = nullptr;
@@ -583,6 +591,36 @@ int mhap_kmer_counts_write(const mhap_kmer_counts* c, const char* path) {
     km[c->k] = 0;
     ok = fprintf(f, "%s\t%.10e\n", km, (double)c->counts[i] / T) > 0;
   }
+  ok = (fclose(f) == 0) && ok;
+  return ok ? MHAP_OK : MHAP_E_IO;
+}
+
+int mhap_kmer_counts_histogram_size(const mhap_kmer_counts* c, int64_t* n) {
+  if (!c || !n) return MHAP_E_INVALID;
+  *n = c->has_histogram ? (int64_t)c->histogram.counts.size() : 0;
+  return c->has_histogram ? MHAP_OK : MHAP_E_STATE;
+}
+
+int mhap_kmer_counts_histogram(const mhap_kmer_counts* c, uint32_t* counts, uint64_t* numbers) {
+  if (!c) return MHAP_E_INVALID;
+  if (!c->has_histogram) return MHAP_E_STATE;
+  for (size_t i = 0; i < c->histogram.counts.size(); i++) {
+    if (counts) counts[i] = c->histogram.counts[i];
+    if (numbers) numbers[i] = c->histogram.numbers[i];
+  }
+  return MHAP_OK;
+}
+
+int mhap_kmer_counts_write_histogram(const mhap_kmer_counts* c, const char* path) {
+  if (!c || !path) return MHAP_E_INVALID;
+  if (!c->has_histogram) return MHAP_E_STATE;
+  FILE* f = fopen(path, "w");
+  if (!f) return MHAP_E_IO;
+  std::vector<char> buf(1 << 20);
+  setvbuf(f, buf.data(), _IOFBF, buf.size());
+  bool ok = true;
+  for (size_t i = 0; i < c->histogram.counts.size() && ok; i++)
+    ok = fprintf(f, "%u\t%llu\n", (unsigned)c->histogram.counts[i], (unsigned long long)c->histogram.numbers[i]) > 0;
   ok = (fclose(f) == 0) && ok;
   return ok ? MHAP_OK : MHAP_E_IO;
 }

@@ -115,11 +115,16 @@ int internal_find_matches_device(mhap_handle* h, const void* d_q_minhash, const 
                                  const int64_t* d_ids_dev, int64_t m, int to_self, mhap_record_sink sink, void* user);
 // Exact k-mer counting (kmer_kernels.hip): one count per handle between mhap_kmer_count_begin and _finish
 struct KmerCountState;
+// the histogram of the final counts (when asked for at finish): counts[i] ascending, numbers[i] = distinct values with that count (> 0)
+struct KmerHistogram {
+  std::vector<uint32_t> counts;
+  std::vector<uint64_t> numbers;
+};
 int kmer_count_begin(KmerCountState*& out, const HandleView& v, int k, int canonical);
 int kmer_count_add_group(KmerCountState& S, const HandleView& v, const ReadDesc* descs, int64_t n, const void* packed, size_t bytes);
 int kmer_count_reserve(KmerCountState& S, const HandleView& v, uint64_t windows);
 int kmer_count_finish(KmerCountState& S, const HandleView& v, double min_fraction, std::vector<uint32_t>& values, std::vector<uint32_t>& counts,
-                      int64_t& distinct);
+                      int64_t& distinct, KmerHistogram* histogram = nullptr);
 int64_t kmer_count_total(const KmerCountState& S);
 int kmer_count_k(const KmerCountState& S);
 uint64_t kmer_count_index_gen(const KmerCountState& S);

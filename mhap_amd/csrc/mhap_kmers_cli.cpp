@@ -19,11 +19,13 @@
 namespace {
 
 const char* USAGE =
-    "Usage: mhap-hip-kmers -o <output file> [-k 16] [--no-rc] [--min-fraction 2.5e-6] [--device 0] <FASTA file or directory> ...\n"
+    "Usage: mhap-hip-kmers -o <output file> [-k 16] [--no-rc] [--min-fraction 2.5e-6] [--histogram <file>] [--device 0] <FASTA file or directory> ...\n"
     "  -o               the k-mer filter file to write (the -f file of mhap-hip)\n"
     "  -k               k-mer size, 1 to 16 (default 16)\n"
     "  --no-rc          count k-mers as they are read instead of canonical (the smaller of a k-mer and its reverse complement)\n"
     "  --min-fraction   write the k-mers whose share of all counted k-mers is at least this (default 2.5e-6)\n"
+    "  --histogram      also write the k-mer count histogram, \"<count>\\t<number of k-mers>\" per line in ascending count\n"
+    "                   (what `python -m mhap_amd.histogram_stats <file> <percent>` reads to help choose --min-fraction)\n"
     "  --device         HIP device ordinal (default 0)\n";
 
 [[noreturn]] void die(const std::string& m) {
@@ -51,7 +53,7 @@ bool parse_double(const char* s, double& v) { char* e = nullptr; v = strtod(s, &
 }  // namespace
 
 int main(int argc, char** argv) {
-  std::string out;
+  std::string out, histogram;
   long k = 16, device = 0;
   double min_fraction = 2.5e-6;
   bool rc = true;
@@ -63,6 +65,7 @@ int main(int argc, char** argv) {
     else if (s == "-o") out = value();
     else if (s == "-k") { if (!parse_int(value(), k)) die("-k takes an integer"); }
     else if (s == "--no-rc") rc = false;
+    else if (s == "--histogram") histogram = value();
     else if (s == "--min-fraction") { if (!parse_double(value(), min_fraction)) die("--min-fraction takes a number"); }
     else if (s == "--device") { if (!parse_int(value(), device) || device < 0) die("--device takes a device ordinal"); }
     else if (!s.empty() && s[0] == '-') die("unknown option " + s);
@@ -97,15 +100,17 @@ int main(int argc, char** argv) {
     }
   }
   mhap_kmer_counts* c = nullptr;
-  chk(mhap_kmer_count_finish(h, min_fraction, &c));
+  chk(mhap_kmer_count_finish_flags(h, min_fraction, histogram.empty() ? 0u : (uint32_t)MHAP_KMER_HISTOGRAM, &c));
   int64_t total = 0, distinct = 0, lines = 0;
   int32_t kk = 0;
   mhap_kmer_counts_info(c, &total, &distinct, &lines, &kk);
   const double tw = now();
   const int w = mhap_kmer_counts_write(c, out.c_str());
+  const int wh = w != MHAP_OK || histogram.empty() ? MHAP_OK : mhap_kmer_counts_write_histogram(c, histogram.c_str());
   mhap_kmer_counts_free(c);
   mhap_destroy(h);
   if (w != MHAP_OK) { fprintf(stderr, "mhap-hip-kmers: cannot write %s\n", out.c_str()); return 1; }
+  if (wh != MHAP_OK) { fprintf(stderr, "mhap-hip-kmers: cannot write %s\n", histogram.c_str()); return 1; }
   fprintf(stderr, "Counted %lld %d-mers (%lld distinct) in %lld reads, %.1f Mbase; wrote %lld lines to %s; total %.3f s (scan %.3f s, count %.3f s, write %.3f s)\n",
           (long long)total, (int)kk, (long long)distinct, (long long)reads, bases / 1e6, (long long)lines, out.c_str(), now() - t0, t_scan, t_count, now() - tw);
   return 0;

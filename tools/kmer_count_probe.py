@@ -1,8 +1,10 @@
 """The GPU k-mer counter (mhap_kmer_count_*) measured at size, on the GPU box; prints one JSON line.
-  python tools/kmer_count_probe.py [--workdir DIR] [--reads 625000]
+  python tools/kmer_count_probe.py [--workdir DIR] [--reads 625000] [--histogram]
 Steps, each a child process under its own `timeout` (the probe stops at the first that fails):
   c5rank   c5rank-shaped reads (625 000 x 12 kb, mhap_synth_reads_repeats) counted through the API (add_reads): wall time
+           (--histogram: finished with the k-mer count histogram, then GetHistogramStats' loop, mhap_histogram_stats, timed on it)
   profile  the same step under `rocprofv3 --kernel-trace --stats`: device time of the counter's kernels per Gbase
+           (--histogram: once with the histogram on, then once with it off)
   c2       C2 written as a FASTA file: mhap-hip-kmers file -> filter, then `mhap-hip -s file -f filter` end to end
   cpu      the numpy counter (workloads.count_kmers) on a 4 000-read sample: the CPU figure"""
 import argparse
@@ -29,10 +31,19 @@ def step_c5rank(a):
     gen = time.time() - t
     bases = int(fa.lengths.astype("int64").sum())
     t = time.perf_counter()
-    kc = mhap_amd.count_kmers(fa, k=16, canonical=True, min_fraction=2.5e-6)
+    kc = mhap_amd.count_kmers(fa, k=16, canonical=True, min_fraction=2.5e-6, histogram=a.histogram)
     dt = time.perf_counter() - t
-    return {"reads": len(fa), "gbase": round(bases / 1e9, 3), "gen_s": round(gen, 1), "count_s": round(dt, 3),
-            "gbase_per_s": round(bases / 1e9 / dt, 2), "total": kc.total, "distinct": kc.distinct, "lines": len(kc)}
+    out = {"reads": len(fa), "gbase": round(bases / 1e9, 3), "gen_s": round(gen, 1), "count_s": round(dt, 3),
+           "gbase_per_s": round(bases / 1e9 / dt, 2), "total": kc.total, "distinct": kc.distinct, "lines": len(kc)}
+    if a.histogram and a.stats:
+        from mhap_amd import histogram_stats as H
+        hc, hn = kc.histogram
+        keep = hc <= 0x7FFFFFFF                        # (GetHistogramStats reads counts as int)
+        t = time.perf_counter()
+        mean, stdev, cut = H.histogram_stats(hc[keep].astype("int32"), hn[keep].astype("int64"), 0.99)
+        out["stats"] = {"rows": int(keep.sum()), "kmers": int(hn[keep].sum()), "s": round(time.perf_counter() - t, 2),
+                        "line": H.format_line(mean, stdev, cut)}
+    return out
 
 
 def step_c2(a):
@@ -72,9 +83,9 @@ def step_cpu(a):
     return {"reads": 4000, "windows": total, "s": round(dt, 3), "mbase_per_s": round(int(fa.lengths.sum()) / 1e6 / dt, 2)}
 
 
-def child(step, a, limit, prefix=()):
+def child(step, a, limit, prefix=(), extra=()):
     cmd = ["timeout", "-k", "10", str(limit)] + list(prefix) + [sys.executable, os.path.abspath(__file__), "--step", step,
-                                                                "--workdir", a.workdir, "--reads", str(a.reads)]
+                                                                "--workdir", a.workdir, "--reads", str(a.reads)] + list(extra)
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         return None, {"step": step, "exit": r.returncode, "stderr": r.stderr[-1500:]}
@@ -102,6 +113,8 @@ def main():
     ap.add_argument("--workdir")
     ap.add_argument("--reads", type=int, default=625000)
     ap.add_argument("--profile-dir", help="where rocprofv3 writes its CSV files (default: WORKDIR/rocprof)")
+    ap.add_argument("--histogram", action="store_true", help="finish with the k-mer count histogram; profile it on and off")
+    ap.add_argument("--stats", action="store_true", help=argparse.SUPPRESS)   # (the c5rank child: time the stats loop too)
     a = ap.parse_args()
     if a.step:
         print(json.dumps({"c5rank": step_c5rank, "c2": step_c2, "cpu": step_cpu}[a.step](a)))
@@ -110,22 +123,27 @@ def main():
     os.makedirs(a.workdir, exist_ok=True)
     a.profile_dir = a.profile_dir or os.path.join(a.workdir, "rocprof")
     res = {"tool": "kmer_count_probe"}
-    got, err = child("c5rank", a, 900)
+    got, err = child("c5rank", a, 900, extra=["--histogram", "--stats"] if a.histogram else [])
     res["c5rank"] = got
     if err:
         res["error"] = err
         print(json.dumps(res))
         return 1
-    os.makedirs(a.profile_dir, exist_ok=True)
-    got, err = child("c5rank", a, 900, ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", a.profile_dir, "-o", "kt", "--"])
-    if err:
-        res["error"] = err
+    for name, extra in ((("profile_histogram", ["--histogram"]), ("profile", [])) if a.histogram else (("profile", []),)):
+        pdir = os.path.join(a.profile_dir, name)
+        os.makedirs(pdir, exist_ok=True)
+        got, err = child("c5rank", a, 900, ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", pdir, "-o", "kt", "--"], extra)
+        if err:
+            res["error"] = err
+            print(json.dumps(res))
+            return 1
+        ks = kernel_stats(pdir)
+        dev_ms = sum(v["ms"] for v in ks.values())
+        res[name] = {"kernels": {k: {"calls": v["calls"], "ms": round(v["ms"], 2)} for k, v in ks.items()}, "device_ms": round(dev_ms, 2),
+                     "device_ms_per_gbase": round(dev_ms / got["gbase"], 2) if got and got.get("gbase") else None}
+    if a.histogram:   # (the c2 and cpu steps do not change with the histogram)
         print(json.dumps(res))
-        return 1
-    ks = kernel_stats(a.profile_dir)
-    dev_ms = sum(v["ms"] for v in ks.values())
-    res["profile"] = {"kernels": {k: {"calls": v["calls"], "ms": round(v["ms"], 2)} for k, v in ks.items()}, "device_ms": round(dev_ms, 2),
-                      "device_ms_per_gbase": round(dev_ms / got["gbase"], 2) if got and got.get("gbase") else None}
+        return 0
     got, err = child("c2", a, 900)
     res["c2"] = got
     if err:
