@@ -125,13 +125,14 @@ struct InvIndex {
   uint32_t* lines;       // [H][nl][16] or nullptr: line l of slot s packs the postings of buckets [l << lb, (l + 1) << lb)
   uint32_t nl_log, line_lb, line_ebits;   // nl = 1 << nl_log lines per slot, lb = log2(buckets per line), entry bits of a packed posting
   // scratch of the build
+  uint32_t tile_entries, tiles;   // entries per tile of the build and tiles of the index: decided once, where tile_counts is sized (inv_alloc)
   uint2* staged;         // [H][slot_stride]: the postings grouped by coarse bin
   uint32_t* tile_counts; // [H][tiles][coarse bins]
   uint32_t* bin_start;   // [H][coarse bins + 1]
   uint32_t* bin_long;    // [H][coarse bins]: the bin holds a bucket longer than group_t (written by step 4 for step 5)
 };
 void launch_query_iota(hipStream_t st, int32_t* qlist, int first, int n);
-int index_tiles(int ne);
+int index_tile_entries(int ne);   // entries per tile of an index of ne entries (MHAP_INDEX_TILE, read at every call)
 void index_group_params(int64_t entries, InvIndex& ix);   // sets grouped / group_t / class_log for an index of this many entries
 int index_coarse_bins();
 bool index_line_params(int64_t entries, uint32_t nb, uint32_t& nl_log, uint32_t& lb, uint32_t& ebits);   // false: no line table for this index
@@ -139,7 +140,7 @@ size_t index_line_bytes(int H, uint32_t nl_log);
 int index_max_buckets_log();
 void launch_index_verify(hipStream_t st, const int32_t* minhash, int64_t row_stride, const int32_t* meta, int ne, int H, const InvIndex& ix,
                          unsigned long long* missing);   // self-check: postings that are not where a lookup would find them
-void launch_index_build(hipStream_t st, const int32_t* minhash, int64_t row_stride, const int32_t* meta, int ne, int H, const InvIndex& ix);
+bool launch_index_build(hipStream_t st, const int32_t* minhash, int64_t row_stride, const int32_t* meta, int ne, int H, const InvIndex& ix);   // false: ix.tiles do not cover ne
 void launch_index_query(hipStream_t st, const InvIndex& ix, const int32_t* qminhash, int64_t qrow_stride,
                         const int32_t* qlist, int nq, const int64_t* ids, const int64_t* qids, const int32_t* meta, const int32_t* qmeta,
                         const SearchParams& sp, Candidate* cand, unsigned long long* cand_count, unsigned long long cand_cap,

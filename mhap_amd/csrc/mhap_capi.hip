@@ -334,7 +334,9 @@ static int inv_alloc(mhap_handle* h, int64_t ne) {
 #define MH_INV_BUCKETS_PER_ENTRY 1
 #endif
   while (lg < (uint32_t)index_max_buckets_log() && (1ULL << lg) < (uint64_t)MH_INV_BUCKETS_PER_ENTRY * (uint64_t)ne) lg++;
-  const size_t nb = (size_t)1 << lg, stride = (size_t)std::max<int64_t>(ne, 1), tiles = (size_t)index_tiles((int)ne), cb = (size_t)index_coarse_bins();
+  // the tile size is decided here, once: tile_counts is sized for these tiles and launch_index_build launches with them
+  const int te = index_tile_entries((int)ne);
+  const size_t nb = (size_t)1 << lg, stride = (size_t)std::max<int64_t>(ne, 1), tiles = (size_t)((ne + te - 1) / te), cb = (size_t)index_coarse_bins();
   HIPCHK(h, h->inv_ends.ensure((size_t)H * (nb + 1) * 4));
   HIPCHK(h, h->inv_items.ensure((size_t)H * stride * 8));
   HIPCHK(h, h->inv_staged.ensure((size_t)H * stride * 8));
@@ -345,6 +347,7 @@ static int inv_alloc(mhap_handle* h, int64_t ne) {
   h->inv.nb = (uint32_t)nb; h->inv.shift = 32 - lg;
   h->inv.slot_stride = (uint64_t)stride;
   h->inv.ne = (uint32_t)std::min<int64_t>(ne, 0xFFFFFFFFLL);
+  h->inv.tile_entries = (uint32_t)te; h->inv.tiles = (uint32_t)tiles;
   index_group_params(ne, h->inv);
   // the line table of the first query tier (round 6); an index it does not cover, or no memory for it: the tier reads ends / items
   h->inv.lines = nullptr; h->inv.nl_log = 0; h->inv.line_lb = 0; h->inv.line_ebits = 0;
@@ -587,7 +590,7 @@ int sketch_staged(mhap_handle* h, int32_t* d_minhash, int64_t mh_stride, int32_t
     }
     {   // experiments (round 6, EXPERIMENTS.md "the MinHash launch's clock"): MHAP_ORDERED_FIRST=2 = an idle gap between the ordered kernel and the
         // MinHash launch; MHAP_W1_PREFILL=n = n fills of the queue buffer in front of the MinHash launch (it is enqueued behind running work)
-      static const int prefill = []() { const char* e = getenv("MHAP_W1_PREFILL"); return e ? atoi(e) : 0; }();
+      const int prefill = []() { const char* e = getenv("MHAP_W1_PREFILL"); return e ? atoi(e) : 0; }();   // (read at every launch group)
       if (ord_first_env == 2) (void)hipStreamSynchronize(h->stream);
       for (int i = 0; i < prefill; i++) (void)hipMemsetAsync(h->mhq.p, 0, h->mhq.cap, h->stream);
     }
@@ -699,8 +702,9 @@ int ensure_inverted_index(mhap_handle* h, hipStream_t st, int64_t ne_override) {
   { const int rr = inv_alloc(h, ne); if (rr != MHAP_OK) return rr; }
   HPROF("index build launch");
   time_begin(h, MHAP_K_INDEX_BUILD, st);
-  launch_index_build(st, h->d_minhash, h->Hrow, h->d_meta, ne, H, h->inv);
+  const bool built = launch_index_build(st, h->d_minhash, h->Hrow, h->d_meta, ne, H, h->inv);
   time_end(h, st);
+  if (!built) return fail(h, MHAP_E_STATE, "inverted index: its tiles do not cover the entries it was sized for");
   HIPCHK(h, hipGetLastError());
   if (getenv("MHAP_DEBUG_INDEX")) {   // self-check: every stored (entry, slot) must find its own posting
     HIPCHK(h, h->counters.ensure(256));

@@ -547,35 +547,46 @@ void launch_index_verify(hipStream_t st, const int32_t* minhash, int64_t row_str
 // (Round 6: a small index — one rank's shard of an 8-GPU job at C2: 25 000 entries — had 7 tiles x 64 slot groups = 448 workgroups for 256 CUs;
 //  tiles of 1 024 entries give it four times as many.  Their shares of a bin are 64 bytes: the scatter's half-written lines — what made 512
 //  coarse bins slow at C2 — meet in the caches while the whole staging area is a few hundred MB.)
-static int index_tile_entries(int ne) {
-  static const int force = []() { const char* e = getenv("MHAP_INDEX_TILE"); const int v = e ? atoi(e) : 0; return v >= 256 && v <= IB_TE ? v : 0; }();
-  return force ? force : (ne <= 65536 ? 1024 : IB_TE);
+// (read at every call: tests switch MHAP_INDEX_TILE inside one process; inv_alloc calls this once per index and keeps the answer in
+//  InvIndex::tile_entries / tiles, which size tile_counts and which launch_index_build launches with)
+int index_tile_entries(int ne) {
+  const char* e = getenv("MHAP_INDEX_TILE");
+  const int force = e ? atoi(e) : 0;
+  if (force >= 256 && force <= IB_TE) return force;
+  return ne <= 65536 ? 1024 : IB_TE;
 }
-int index_tiles(int ne) { const int te = index_tile_entries(ne); return (ne + te - 1) / te; }
 int index_coarse_bins() { return IB_BINS; }
 int index_max_buckets_log() { return IB_BINS_LOG + 13; }   // IB_SUB_MAX buckets per coarse bin
-// (re)build the index for entries [0, ne): ix.ends / items / staged / tile_counts / bin_start sized by the caller (index_tiles)
-void launch_index_build(hipStream_t st, const int32_t* minhash, int64_t row_stride, const int32_t* meta, int ne, int H, const InvIndex& ix) {
-  if ((int64_t)ne * H <= 0) return;
-  const int tiles = index_tiles(ne), te = index_tile_entries(ne);
+// (re)build the index for entries [0, ne): ix.ends / items / staged / tile_counts / bin_start, and ix.tile_entries / tiles, set by the caller
+// (inv_alloc) for these ne entries.  False: the tiles do not cover ne entries (nothing launched).
+bool launch_index_build(hipStream_t st, const int32_t* minhash, int64_t row_stride, const int32_t* meta, int ne, int H, const InvIndex& ix) {
+  if ((int64_t)ne * H <= 0) return true;
+  const int tiles = (int)ix.tiles, te = (int)ix.tile_entries;
+  if (te <= 0 || (int64_t)tiles * te < (int64_t)ne) return false;
   const unsigned grid = (unsigned)tiles * (unsigned)((H + IB_S - 1) / IB_S);
   hipLaunchKernelGGL(index_tile_kernel<false>, dim3(grid), dim3(IB_THREADS), 0, st, minhash, row_stride, meta, ne, H, tiles, te, ix);
   hipLaunchKernelGGL(index_offsets_kernel, dim3((unsigned)H), dim3(IB_BINS), 0, st, ix, tiles);
   hipLaunchKernelGGL(index_tile_kernel<true>, dim3(grid), dim3(IB_THREADS), 0, st, minhash, row_stride, meta, ne, H, tiles, te, ix);
+  const int sub = (int)(ix.nb >> IB_BINS_LOG);
+  int launched;
   {
-    const int sub = (int)(ix.nb >> IB_BINS_LOG);
     const dim3 g((unsigned)H << IB_BINS_LOG);
-    static const int force = []() { const char* e = getenv("MHAP_INDEX_BINS_SHAPE"); return e ? atoi(e) : -1; }();   // 0 / 1 / 2: pin a shape that fits (A/B)
+    const char* e = getenv("MHAP_INDEX_BINS_SHAPE");   // 0 / 1 / 2: pin a shape that fits (A/B; read at every build: tests switch it inside one process)
+    const int force = e ? atoi(e) : -1;
     const int shape = force >= 0 ? force : (sub <= 512 ? 0 : (sub <= 2048 ? 1 : 2));
-    if (shape == 0 && sub <= 512) hipLaunchKernelGGL((index_bins_kernel<512, 64>), g, dim3(64), 0, st, ix);
-    else if (shape <= 1 && sub <= 2048) hipLaunchKernelGGL((index_bins_kernel<2048, 256>), g, dim3(256), 0, st, ix);
-    else hipLaunchKernelGGL((index_bins_kernel<IB_SUB_MAX, 256>), g, dim3(256), 0, st, ix);
+    if (shape == 0 && sub <= 512) { hipLaunchKernelGGL((index_bins_kernel<512, 64>), g, dim3(64), 0, st, ix); launched = 0; }
+    else if (shape <= 1 && sub <= 2048) { hipLaunchKernelGGL((index_bins_kernel<2048, 256>), g, dim3(256), 0, st, ix); launched = 1; }
+    else { hipLaunchKernelGGL((index_bins_kernel<IB_SUB_MAX, 256>), g, dim3(256), 0, st, ix); launched = 2; }
   }
   if (ix.grouped) hipLaunchKernelGGL(index_group_kernel, dim3((unsigned)H << IB_BINS_LOG), dim3(IB_GRP_THREADS), 0, st, ix);
   if (ix.lines) {
     const size_t threads = (size_t)H << ix.nl_log;
     hipLaunchKernelGGL(index_lines_kernel, dim3((unsigned)((threads + IL_THREADS - 1) / IL_THREADS)), dim3(IL_THREADS), 0, st, ix, H);
   }
+  if (getenv("MHAP_HOST_PROF"))   // which build ran (tests assert it)
+    fprintf(stderr, "[index build] entries %d tile_entries %d tiles %d sub %d bins_shape %d grouped %u lines %d\n", ne, te, tiles, sub, launched,
+            ix.grouped, ix.lines ? 1 : 0);
+  return true;
 }
 // (called when the index is sized: an index the compact dense tier covers in one pass gains nothing from the order, and the class
 //  counters bound the size from above.  MHAP_INDEX_GROUP=0|1 never / always, MHAP_INDEX_GROUP_T, MHAP_INDEX_CLASS_LOG: tests, which

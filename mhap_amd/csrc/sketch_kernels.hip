@@ -2039,14 +2039,18 @@ int minhash_waves_per_workgroup(int H) {
 // Strands of a weight-1 launch that are cut into row items (the others are taken whole): one strand's worth of rows per resident
 // wave at the end of the list evens the waves' finish times out to one row; a list shorter than that is all rows.
 int64_t minhash_tail_strands(int nblocks, int64_t n_unweighted) {
-  static int div = 0;   // MHAP_W1_TAIL_DIV: 1 / 2 / 4 ... = a strand's worth of rows for every / every second / fourth resident wave (experiments)
-  if (div == 0) { const char* e = getenv("MHAP_W1_TAIL_DIV"); div = e && atoi(e) > 0 ? atoi(e) : 1; }
+  // MHAP_W1_TAIL_DIV: 1 / 2 / 4 ... = a strand's worth of rows for every / every second / fourth resident wave (experiments; read at every
+  // launch: tests switch it inside one process)
+  const char* e = getenv("MHAP_W1_TAIL_DIV");
+  const int div = e && atoi(e) > 0 ? atoi(e) : 1;
   const int64_t waves = (int64_t)nblocks * 4 / div;
   return n_unweighted < waves ? n_unweighted : waves;
 }
 size_t minhash_merge_bytes(int nblocks, int H) { return (size_t)nblocks * 4 * (size_t)H * 8; }
 
-// MHAP_MINHASH=perchain selects the kernel without bit-sliced rows, MHAP_MINHASH=classic round 2's kernel for the weight-1 strands too (A/B measurements)
+// MHAP_MINHASH=perchain selects the kernel without bit-sliced rows, MHAP_MINHASH=classic round 2's kernel for the weight-1 strands too (A/B measurements;
+// read at every launch, like MHAP_W1_TAIL_DIV and MHAP_W1_STAGGER: tests switch them inside one process).  MHAP_HOST_PROF: one stderr line per
+// launch says which kernels ran ("[minhash] ..."; tests assert it)
 bool launch_minhash(hipStream_t st, hipStream_t st_weighted, int nblocks, int64_t n_unweighted, int64_t n_weighted, const ReadDesc* descs, int64_t nstrands, const int64_t* keys, const uint32_t* wts,
                     const uint32_t* perm, const StrandInfo* info, const uint8_t* store, const uint64_t* luts, int k, int k2, int H,
                     unsigned long long* counter, int32_t* out_rows, int64_t out_stride, int32_t* out_status, int64_t status_stride,
@@ -2056,8 +2060,9 @@ bool launch_minhash(hipStream_t st, hipStream_t st_weighted, int nblocks, int64_
   // merge: minhash_merge_bytes(nblocks, H); max_nk: k-mers of the launch's longest strand.  Returns whether anything was put on st_weighted
   // (the caller joins that stream only then)
   if (nstrands <= 0) return false;
-  static int perchain = -1, classic = 0;
-  if (perchain < 0) { const char* e = getenv("MHAP_MINHASH"); perchain = (e && strcmp(e, "perchain") == 0) ? 1 : 0; classic = (e && strcmp(e, "classic") == 0) ? 1 : 0; }
+  const char* mode_env = getenv("MHAP_MINHASH");
+  const int perchain = (mode_env && strcmp(mode_env, "perchain") == 0) ? 1 : 0, classic = (mode_env && strcmp(mode_env, "classic") == 0) ? 1 : 0;
+  const bool witness = getenv("MHAP_HOST_PROF") != nullptr;
   size_t per_wave = (((size_t)H * 12 + 8) + 15) & ~(size_t)15;
   const size_t lut_bytes = (size_t)MH_LUT_WORDS * 8;
   const int waves = minhash_waves_per_workgroup(H);   // waves (= strands in flight) per workgroup; fewer when --num-hashes is huge
@@ -2098,6 +2103,9 @@ bool launch_minhash(hipStream_t st, hipStream_t st_weighted, int nblocks, int64_
                        counter_w, out_rows, out_stride, out_status, status_stride, jump, jump_na, slist_w, counter + 5, qbuf_w, qcap);
     hipLaunchKernelGGL((minhash_kernel<MH_U, false, false>), dim3(nblocks), block, lds, st, descs, nstrands, keys, wts, perm, info, store, luts, k, k2, H,
                        counter_u, out_rows, out_stride, out_status, status_stride, jump, jump_na, slist, counter + 4, qbuf, qcap);
+    if (witness)
+      fprintf(stderr, "[minhash] strands %lld weight-1 %lld weighted %lld nblocks %d: perchain\n", (long long)nstrands, (long long)n_unweighted,
+              (long long)n_weighted, nblocks);
     return true;
   } else {
     // n_unweighted / n_weighted >= 0: the lengths of the two work lists (the caller read them back): each launch gets only the
@@ -2113,9 +2121,11 @@ bool launch_minhash(hipStream_t st, hipStream_t st_weighted, int nblocks, int64_
     if (nb_w > 0)
       hipLaunchKernelGGL((minhash_kernel<MH_U, true, true>), dim3(nb_w), block, lds + 16, st_weighted, descs, nstrands, keys, wts, perm, info, store, luts, k, k2, H,
                          counter_w, out_rows, out_stride, out_status, status_stride, jump, jump_na, slist_w, counter + 5, qbuf_w, qcap, nullptr, split ? 1 : 0);
+    char w1_path[160] = "none";
     if (nb_u > 0 && (classic || n_unweighted < 0 || waves_wg != 4)) {
       hipLaunchKernelGGL((minhash_kernel<MH_U, true, false>), dim3(nb_u), block, lds, st, descs, nstrands, keys, wts, perm, info, store, luts, k, k2, H,
                          counter_u, out_rows, out_stride, out_status, status_stride, jump, jump_na, slist, counter + 4, qbuf, qcap);
+      if (witness) snprintf(w1_path, sizeof(w1_path), "classic");
     } else if (nb_u > 0) {
       // the weight-1 strands: whole strands first, the last minhash_tail_strands() of the list row by row (see minhash_w1_kernel)
       W1Args a;
@@ -2126,8 +2136,8 @@ bool launch_minhash(hipStream_t st, hipStream_t st_weighted, int nblocks, int64_
       a.out_rows = out_rows; a.out_stride = out_stride; a.out_status = out_status; a.status_stride = status_stride;
       a.jump = jump_w1; a.unjump = unjump; a.jump_na = W1_JUMP_NA; a.qbuf = qbuf; a.qcap = qcap; a.merge = merge;   // (its own two-level table set)
       {   // a quarter of a row's ~1 300 clocks per slot (MHAP_W1_STAGGER: clocks per SIMD slot number; 0 = all waves start together)
-        static int stag = -2;
-        if (stag == -2) { const char* e = getenv("MHAP_W1_STAGGER"); stag = e ? atoi(e) : -1; }
+        const char* e = getenv("MHAP_W1_STAGGER");
+        const int stag = e ? atoi(e) : -1;
         a.stagger = stag >= 0 ? stag : 0;   // (default off: measured without effect on a rank's launch — 10.83 / 10.70 ms with, 10.83 / 10.69 without: EXPERIMENTS round 6)
       }
       const long long items = a.n_whole + a.n_tail * (long long)a.rmax;
@@ -2163,7 +2173,11 @@ bool launch_minhash(hipStream_t st, hipStream_t st_weighted, int nblocks, int64_
         else hipLaunchKernelGGL((minhash_w1_kernel<false, false>), dim3(nb), dim3(256), lds1, st, a);
       if (a.n_tail > 0)
         hipLaunchKernelGGL(minhash_w1_finish_kernel, dim3((unsigned)((a.n_tail * (long long)H + 255) / 256)), dim3(256), 0, st, a);
+      if (witness) snprintf(w1_path, sizeof(w1_path), "w1 n_whole %lld n_tail %lld rmax %d stagger %d", (long long)a.n_whole, (long long)a.n_tail, a.rmax, a.stagger);
     }
+    if (witness)
+      fprintf(stderr, "[minhash] strands %lld weight-1 %lld weighted %lld nblocks %d: weight-1 launch %s; weighted launch %s\n", (long long)nstrands,
+              (long long)n_unweighted, (long long)n_weighted, nblocks, w1_path, nb_w > 0 ? (split ? "split" : "wave") : "none");
     return nb_w > 0;
   }
 }

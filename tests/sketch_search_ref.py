@@ -24,16 +24,21 @@ def _candidates(q_mh, e_mh, num_min_matches):
     return np.concatenate(out) if out else np.zeros((0, 2), dtype=np.int64)
 
 
-def expected_pairs(entries, queries=None, *, num_min_matches, min_store_length):
+def expected_pairs(entries, queries=None, *, num_min_matches, min_store_length, pairs=None):
     """The (query, entry) pairs MinHashSearch.findMatches compares.  queries=None: self mode (toSelf, orc_run_self's loop, every
-    forward entry is a query); else -q mode (toSelf false: only "never short to short", MinHashSearch.java:197-229)."""
+    forward entry is a query); else -q mode (toSelf false: only "never short to short", MinHashSearch.java:197-229).
+    pairs: the (query row, entry row) pairs whose MinHash rows share at least num_min_matches slots, where the caller built the tables
+    so that it knows them all (in self mode every query row a forward entry): the all-pairs scan is skipped, the filters still apply."""
     to_self = queries is None
     q = entries if to_self else queries
-    qsel = np.nonzero(np.asarray(entries["is_fwd"]) != 0)[0] if to_self else np.arange(len(q["ids"]))
-    cand = _candidates(np.asarray(q["minhash"])[qsel], np.asarray(entries["minhash"]), num_min_matches)
+    if pairs is None:
+        qsel = np.nonzero(np.asarray(entries["is_fwd"]) != 0)[0] if to_self else np.arange(len(q["ids"]))
+        cand = [(int(qsel[qi_]), int(m)) for qi_, m in _candidates(np.asarray(q["minhash"])[qsel], np.asarray(entries["minhash"]), num_min_matches)]
+    else:
+        cand = sorted((int(qi), int(m)) for qi, m in pairs)
+        assert not to_self or all(entries["is_fwd"][qi] for qi, _ in cand), "a query row of self mode that is no forward entry"
     pairs = []
-    for qi_, m in cand:
-        qi = int(qsel[qi_])
+    for qi, m in cand:
         qid, mid = int(q["ids"][qi]), int(entries["ids"][m])
         ql, ml = int(q["seq_length"][qi]), int(entries["seq_length"][m])
         if to_self and mid == qid:
@@ -53,13 +58,14 @@ def _row(t, i):
 
 
 def expected_records(entries, queries=None, *, H, k2, num_min_matches, min_store_length, threshold, max_shift, nthreads=16,
-                     return_compared=False):
+                     return_compared=False, pairs=None):
     """MinHashSearch.findMatches over the tables: sorted record lines (O.format_record), as orc_run_self builds its records —
     alen / blen the read lengths, the b1 / b2 flip of a reverse-strand entry (MatchResult.java:56-57), and at threshold 0 an EMPTY
-    overlap is a record too.  return_compared: also the number of pairs given to getOverlapInfo (stats' candidates_compared)."""
+    overlap is a record too.  return_compared: also the number of pairs given to getOverlapInfo (stats' candidates_compared).
+    pairs: the candidate pairs, where the caller knows them (expected_pairs)."""
     assert np.asarray(entries["minhash"]).shape[1] == max(1, H)
     q = entries if queries is None else queries
-    pairs = expected_pairs(entries, queries, num_min_matches=num_min_matches, min_store_length=min_store_length)
+    pairs = expected_pairs(entries, queries, num_min_matches=num_min_matches, min_store_length=min_store_length, pairs=pairs)
 
     def one(p):
         qi, m = p

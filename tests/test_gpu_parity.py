@@ -962,20 +962,28 @@ def test_fused_and_separate_kmer_hashing_agree(monkeypatch):
         assert np.array_equal(a[key], b[key]), key
 
 
-def test_perchain_minhash_switch_agrees(monkeypatch):
+def test_perchain_minhash_switch_agrees(monkeypatch, capfd):
     """MHAP_MINHASH=perchain (every row in 64-bit registers, both launches) gives the bit-sliced rows' sketches — weight-1 strands
-    and strands with repeated k-mers (second launch, own stream) alike."""
+    and strands with repeated k-mers (second launch, own stream) alike — and the oracle's.  The switch is read at every launch: the
+    witness lines (MHAP_HOST_PROF) show which kernels made each set of sketches."""
     rnd = random.Random(123)
     unit = _rand_seq(rnd, 150)
     seqs = [_rand_seq(rnd, rnd.randrange(300, 7000)) for _ in range(40)] + [unit * 12 + _rand_seq(rnd, 2500) for _ in range(6)]
     fa = FastaData.from_strings(seqs)
     p = MhapParams(num_hashes=128, ordered_sketch_size=256)
+    monkeypatch.delenv("MHAP_MINHASH", raising=False)
+    monkeypatch.setenv("MHAP_HOST_PROF", "1")
     _assert_sketch_parity(fa, p)
     with MinHashSearch(p) as ms:
         a = ms.sketch(fa)
+    wit = [x for x in capfd.readouterr()[1].splitlines() if x.startswith("[minhash] ")]
+    assert len(wit) == 2 and all(": weight-1 launch w1 " in x for x in wit), wit
     monkeypatch.setenv("MHAP_MINHASH", "perchain")
+    _assert_sketch_parity(fa, p)
     with MinHashSearch(p) as ms:
         b = ms.sketch(fa)
+    wit = [x for x in capfd.readouterr()[1].splitlines() if x.startswith("[minhash] ")]
+    assert len(wit) == 2 and all(x.endswith(": perchain") for x in wit), wit
     for key in ("minhash", "ordered", "ordered_size", "status"):
         assert np.array_equal(a[key], b[key]), key
 

@@ -89,6 +89,28 @@ def test_expected_records_query_mode():
     assert len(lines) == len(pairs)                # threshold 0: every compared pair is a record
 
 
+def test_known_candidate_pairs_give_the_scan_s_records():
+    """expected_records(pairs=...): the candidate pairs given by a caller who built the tables (every ordered pair of rows that share
+    num_min_matches slots, self pairs and both directions included) pass the same filters and give the same records and count as the
+    all-pairs scan, in self mode and in -q mode."""
+    fa = _reads(120, seed=13)
+    H, S = 64, 256
+    kw = dict(H=H, k2=K2, num_min_matches=3, min_store_length=2000, threshold=0.0, max_shift=0.2)
+    t = _tables(fa, H, S)
+    mh = t["minhash"]
+    shared = (mh[:, None, :] == mh[None, :, :]).sum(axis=2) >= 3
+    fw = np.nonzero(t["is_fwd"])[0]
+    self_cand = [(int(a), int(b)) for a, b in zip(*np.nonzero(shared)) if t["is_fwd"][a]]
+    want, compared = R.expected_records(t, return_compared=True, **kw)
+    got, got_compared = R.expected_records(t, return_compared=True, pairs=self_cand, **kw)
+    assert got == want and got_compared == compared and compared > 50
+    q = {k: v[fw] for k, v in t.items()}
+    q_cand = [(int(a), int(b)) for a, b in zip(*np.nonzero(shared[fw]))]
+    assert R.expected_records(t, q, pairs=q_cand, **kw) == R.expected_records(t, q, **kw)
+    with pytest.raises(AssertionError):
+        R.expected_records(t, pairs=[(int(np.nonzero(t["is_fwd"] == 0)[0][0]), 0)], **kw)
+
+
 def test_row_builder_refuses_rows_a_dat_cannot_hold():
     b = R.TableBuilder(S=8, H=4)
     mh = [1, 2, 3, 4]
