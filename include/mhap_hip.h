@@ -394,6 +394,42 @@ void mhap_fasta_free(mhap_fasta* f);
  * the n_bases bases. */
 int mhap_align_pairs(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const int64_t* pairs, int64_t n, int32_t* results);
 
+/* ---- the realignment stage: aligned ends and a counted identity for reported overlaps -------- */
+
+/* mhap_align_pairs inside a band.  pairs: n rows of 7 int64 {a_off, a_len, b_off, b_len, b_rc, diag, band}; the first five as above.
+ * With i the 0-based position in s1 and j the 0-based position in s2 (after the reverse complement when b_rc), cell (i, j) is in the
+ * band iff |j - i - diag| <= band.  The contract is mhap_align_pairs' with one sentence added:
+ *   a cell outside the band has H = 0 and E = F = -infinity and carries nothing.
+ * (A diagonal step never leaves the band, and an E or F that opens from an out-of-band H = 0 is negative, so the band's edge needs no
+ * rule of its own.)  When every cell of the matrix is in the band the seven result fields equal mhap_align_pairs' on the same pair; a
+ * band that misses the matrix, or an empty segment, gives {0, -1, -1, -1, -1, 0, 0}.  MHAP_E_INVALID, with the pair's index in the
+ * message, for band < 0 or a segment outside the n_bases bases.  Work and memory follow the band clipped to the matrix, not the
+ * matrix (realign_kernels.hip). */
+int mhap_align_pairs_banded(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const int64_t* pairs /* n x 7 */, int64_t n,
+                            int32_t* results /* n x 7 */);
+
+/* Overlap records -> banded pairs (no GPU).  The reads are (read_ids[r], offsets[r], lengths[r]) into one array of bases; a record's
+ * reads are found by id through a host map.  Per record: s1 = the whole `from` read, s2 = the whole `to` read, b_rc = to_rc.
+ * MatchResult's flip (J/impl/MatchResult.java:56-57) is undone when to_rc: b1' = blen - b2 - 1, b2' = blen - b1 - 1, else b1' = b1,
+ * b2' = b2.  diag = floor(((b1' + b2') - (a1 + a2)) / 2), floor toward -infinity.  band > 0: that value; band = 0 (automatic):
+ * max(1, (int)(max(a2 - a1, b2' - b1') * max_shift)), the tolerance the second stage applies around its median shift
+ * (J/sketch/BottomOverlapSketch.java:205).  MHAP_E_INVALID for a record whose id is not among read_ids or whose alen / blen disagree
+ * with the read's length; the message, which names the record, is mhap_realign_plan_error() of the calling thread. */
+int mhap_realign_plan(const mhap_record* recs, int64_t n, const int64_t* read_ids, const int64_t* offsets, const int32_t* lengths,
+                      int64_t n_reads, double max_shift, int32_t band /* 0 = auto */, int64_t* pairs /* n x 7 */);
+const char* mhap_realign_plan_error(void);
+
+/* Plan, align in the band and convert back.  The automatic band (band = 0) uses the max_shift of the handle's parameters.  out[q]:
+ * ids, alen, blen, to_rc and raw copied from recs[q]; a1 = read_begin, a2 = read_end; b1, b2 = ref_begin, ref_end, flipped back when
+ * to_rc; score = 1.0 - (double)errors / columns.  detail (may be NULL): n rows of 3 int32 {score, columns, errors} of the alignment.
+ * A record without an alignment comes back with score 0, the four positions 0 and a detail row of zeros: the caller decides what to do
+ * with it.  The bases are uploaded once; records go through the kernel 65 536 at a time, so device memory besides the bases is 88
+ * bytes per record of a batch plus at most 1 GiB of pass boundaries, whatever n is.  Errors as mhap_realign_plan (message:
+ * mhap_last_error) and mhap_align_pairs_banded. */
+int mhap_realign_records(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const int64_t* read_ids, const int64_t* offsets,
+                         const int32_t* lengths, int64_t n_reads, const mhap_record* recs, int64_t n, int32_t band,
+                         mhap_record* out, int32_t* detail /* n x 3: score, columns, errors; may be NULL */);
+
 /* KmerStatSimulator's pair statistics on the GPU (J/main/KmerStatSimulator.java:163-196).  pairs: n rows of 4 int64 {a_off, a_len,
  * b_off, b_len}; a = bases[a_off, a_off + a_len) is the first read, b the second.  skip: n_skip k-mers of k bytes each, back to back, in
  * any order (the skip set of loadSkipMers; entries of another length never match and are left out by the caller).  For each pair,

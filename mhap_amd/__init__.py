@@ -21,6 +21,9 @@ from .api import (  # noqa: F401
     synth_reads_from_genome,
     synth_truth,
     align_pairs,
+    align_pairs_banded,
+    realign_plan,
+    realign_records,
     pair_kmer_stats,
     records_to_lines,
     load_library,

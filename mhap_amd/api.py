@@ -71,6 +71,7 @@ EXPORTED_SYMBOLS = [
     "mhap_kmer_count_finish_flags", "mhap_kmer_counts_histogram_size", "mhap_kmer_counts_histogram", "mhap_kmer_counts_write_histogram",
     "mhap_histogram_stats",
     "mhap_synth_truth", "mhap_align_pairs",
+    "mhap_align_pairs_banded", "mhap_realign_plan", "mhap_realign_plan_error", "mhap_realign_records",
     "mhap_pair_kmer_stats", "mhap_pair_kmer_stats_paths", "mhap_ksim_create", "mhap_ksim_next", "mhap_ksim_error", "mhap_ksim_destroy",
     "mhap_ksim_dev_create", "mhap_ksim_dev_destroy", "mhap_ksim_dev_pair_stats", "mhap_ksim_dev_trials",
 ]
@@ -141,6 +142,11 @@ def load_library(build_if_missing=True):
     lib.mhap_ksim_dev_trials.argtypes = [C.c_void_p, C.c_uint64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                          C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                          C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mhap_realign_plan_error.restype = C.c_char_p
+    lib.mhap_realign_plan_error.argtypes = []
+    lib.mhap_realign_plan.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int32, C.c_void_p]
+    lib.mhap_realign_records.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                         C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
     for name in EXPORTED_SYMBOLS:
         getattr(lib, name)  # AttributeError here = header/library mismatch
     # a stale library next to newer host code (or the reverse) must not get as far as a struct copy
@@ -328,6 +334,77 @@ def align_pairs(bases, pairs, device=0, handle=None):
         if own:
             ms.close()
     return out
+
+
+def align_pairs_banded(bases, pairs7, device=0, handle=None):
+    """align_pairs inside a band (mhap_align_pairs_banded; its header comment is the contract).  pairs7: int64 array (n, 7) of
+    (a_off, a_len, b_off, b_len, b_rc, diag, band): cell (i, j) is in the band iff |j - i - diag| <= band.  Returns the (n, 7) int32
+    rows of align_pairs."""
+    bases = np.ascontiguousarray(bases, dtype=np.uint8)
+    pairs7 = np.ascontiguousarray(np.asarray(pairs7, dtype=np.int64).reshape(-1, 7))
+    out = np.zeros((len(pairs7), 7), dtype=np.int32)
+    if len(pairs7) == 0:
+        return out
+    own = handle is None
+    ms = MinHashSearch(MhapParams(num_hashes=1, ordered_sketch_size=1, device=device)) if own else handle
+    try:
+        ms._chk(ms._lib.mhap_align_pairs_banded(ms._h, _ptr(bases), C.c_int64(len(bases)), _ptr(pairs7), C.c_int64(len(pairs7)), _ptr(out)))
+    finally:
+        if own:
+            ms.close()
+    return out
+
+
+def _all_reads(fasta, query_fasta):
+    """(bases, ids, offsets, lengths) of the indexed reads followed by the -q reads, as one array of bases."""
+    if query_fasta is None or len(query_fasta) == 0:
+        return fasta.bases, fasta.ids, fasta.offsets, fasta.lengths
+    return (np.concatenate([fasta.bases, query_fasta.bases]), np.concatenate([fasta.ids, query_fasta.ids]),
+            np.concatenate([fasta.offsets, query_fasta.offsets + len(fasta.bases)]), np.concatenate([fasta.lengths, query_fasta.lengths]))
+
+
+def realign_plan(records, fasta, band=0, max_shift=0.2, query_fasta=None):
+    """The banded pairs of overlap records (mhap_realign_plan, no GPU): an int64 array (n, 7) for align_pairs_banded over the bases of
+    `fasta` followed by those of `query_fasta`."""
+    lib = load_library()
+    records = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
+    bases, ids, offsets, lengths = _all_reads(fasta, query_fasta)
+    ids, offsets = np.ascontiguousarray(ids, np.int64), np.ascontiguousarray(offsets, np.int64)
+    lengths = np.ascontiguousarray(lengths, np.int32)
+    pairs = np.zeros((len(records), 7), np.int64)
+    rc = lib.mhap_realign_plan(_ptr(records), C.c_int64(len(records)), _ptr(ids), _ptr(offsets), _ptr(lengths), C.c_int64(len(ids)),
+                               C.c_double(max_shift), C.c_int32(band), _ptr(pairs))
+    if rc != 0:
+        raise MhapError(f"{lib.mhap_realign_plan_error().decode()} (code {rc})")
+    return pairs
+
+
+def realign_records(records, fasta, band=0, max_shift=0.2, device=0, handle=None, query_fasta=None):
+    """Realign overlap records on the GPU (mhap_realign_records): every record's interval and identity are replaced by those of the
+    banded local alignment of its two reads around the diagonal the record implies.  records: RECORD_DTYPE array (a search's
+    output); fasta: the FastaData the ids refer to (query_fasta: the -q reads, whose ids follow).  band = 0: the automatic band,
+    max(1, int(max(a2 - a1, b2 - b1) * max_shift)) — with a `handle`, the max_shift of that handle's parameters is the one used.
+    Returns (records, detail): detail is an int32 array (n, 3) of (score, columns, errors); a record without an alignment has score 0,
+    positions 0 and a zero detail row."""
+    records = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
+    out = np.zeros(len(records), dtype=RECORD_DTYPE)
+    detail = np.zeros((len(records), 3), dtype=np.int32)
+    if len(records) == 0:
+        return out, detail
+    bases, ids, offsets, lengths = _all_reads(fasta, query_fasta)
+    bases = np.ascontiguousarray(bases, np.uint8)
+    ids, offsets = np.ascontiguousarray(ids, np.int64), np.ascontiguousarray(offsets, np.int64)
+    lengths = np.ascontiguousarray(lengths, np.int32)
+    own = handle is None
+    ms = MinHashSearch(MhapParams(num_hashes=1, ordered_sketch_size=1, max_shift=max_shift, device=device)) if own else handle
+    try:
+        ms._chk(ms._lib.mhap_realign_records(ms._h, _ptr(bases), C.c_int64(len(bases)), _ptr(ids), _ptr(offsets), _ptr(lengths),
+                                             C.c_int64(len(ids)), _ptr(records), C.c_int64(len(records)), C.c_int32(band), _ptr(out),
+                                             _ptr(detail)))
+    finally:
+        if own:
+            ms.close()
+    return out, detail
 
 
 def _skip_bytes(skip, k):

@@ -1154,6 +1154,7 @@ namespace mhap {
 HandleView handle_view(mhap_handle* h) {
   HandleView v;
   v.device = h->device; v.stream = h->stream; v.num_cus = h->num_cus; v.Hrow = h->Hrow; v.S = h->P.ordered_sketch_size; v.k = h->P.kmer_size; v.min_olap_length = h->P.min_olap_length;
+  v.max_shift = h->P.max_shift;
   v.n_entries = h->n_entries; v.index_gen = h->index_gen;
   v.d_minhash = h->d_minhash; v.d_ordered = h->d_ordered; v.d_meta = h->d_meta;
   v.h_ids = h->ids.data(); v.h_fwd = h->fwd.data(); v.err = &h->err; v.dist = &h->dist; v.kmer = &h->kmer;

@@ -42,7 +42,12 @@ struct Options {
     for (auto& n : order) { const Opt& o = m.at(n); t += "\t" + n + ", default = " + (o.is_flag ? "false" : o.value) + "\n\t\t" + o.help + "\n"; }
     return t;
   }
-  std::string dump() const { std::string t; for (auto& n : order) t += n + " = " + m.at(n).value + "\n"; return t; }
+  // (the realignment flags are listed only when --realign is given: without it every line the driver writes is what it was before them)
+  std::string dump() const {
+    std::string t;
+    for (auto& n : order) { if (n.compare(0, 9, "--realign") == 0 && !b("--realign")) continue; t += n + " = " + m.at(n).value + "\n"; }
+    return t;
+  }
   // ParseOptions.process (J/utils/ParseOptions.java:209-236,327-368): flags are presence flags, others consume the next arg
   bool parse(int argc, char** argv) {
     for (int a = 1; a < argc; a++) {
@@ -146,10 +151,41 @@ void collect_headers(mhap_fasta_scan* sc) {
 
 // the file the index is built from is mapped and scanned while the HIP runtime comes up
 struct Preload { std::string path; mhap_fasta_scan* scan = nullptr; } g_preload;
-struct Sink { FILE* out; std::string buf; int64_t n = 0; };
+// --realign: a one-byte-per-base copy of every read the search has seen (the index's, then each -q file's), and the handle that aligns
+struct Realign {
+  mhap_handle* h = nullptr;
+  int32_t band = 0; double min_identity = 0.0;
+  std::vector<uint8_t> bases; std::vector<int64_t> ids, offsets; std::vector<int32_t> lengths;
+  std::vector<mhap_record> out;
+  int64_t dropped = 0, kept = 0;
+  double seconds = 0.0;
+  void add(const mhap_fasta& fa) {
+    for (int64_t i = 0; i < fa.n; i++) { ids.push_back(fa.ids[i]); offsets.push_back((int64_t)bases.size() + fa.offsets[i]); lengths.push_back(fa.lengths[i]); }
+    bases.insert(bases.end(), (const uint8_t*)fa.bases, (const uint8_t*)fa.bases + fa.total_bases);
+  }
+};
+struct Sink { FILE* out; std::string buf; int64_t n = 0; Realign* realign = nullptr; };
 int sink_cb(const mhap_record* r, int64_t n, void* user) {
   Sink* s = (Sink*)user;
   char line[512];
+  if (s->realign && n > 0) {   // the batch through the banded aligner; what has no alignment or too low an identity is dropped
+    Realign& R = *s->realign;
+    const double t = now();
+    R.out.resize((size_t)n);
+    const int rc = mhap_realign_records(R.h, R.bases.data(), (int64_t)R.bases.size(), R.ids.data(), R.offsets.data(), R.lengths.data(),
+                                        (int64_t)R.ids.size(), r, n, R.band, R.out.data(), nullptr);
+    if (rc != MHAP_OK) { fprintf(stderr, "Exception in mhap-hip: %s (code %d)\n", mhap_last_error(R.h), rc); return 1; }
+    int64_t k = 0;
+    for (int64_t i = 0; i < n; i++) {
+      const mhap_record& o = R.out[(size_t)i];
+      const bool none = o.score == 0.0 && o.a1 == 0 && o.a2 == 0 && o.b1 == 0 && o.b2 == 0;
+      if (none || o.score < R.min_identity) continue;
+      R.out[(size_t)k++] = o;
+    }
+    R.dropped += n - k; R.kept += k;
+    R.seconds += now() - t;
+    r = R.out.data(); n = k;
+  }
   for (int64_t i = 0; i < n; i++) {
     if (!g_headers.full) { int len = mhap_format_record(&r[i], line, sizeof line); s->buf.append(line, (size_t)len); }
     else {
@@ -302,6 +338,9 @@ int main(int argc, char** argv) {
   o.add("--device", "[int] HIP device ordinal (the first one with --gpus N).", "0");
   o.add("--gpus", "[int] Number of GPUs: the reads are dealt round-robin over devices --device .. --device+N-1, every GPU sketches and indexes its share, and a search gathers the forward query sketches of all GPUs (over xGMI) against every share.", "1");
   o.add("--devices", "Comma-separated HIP device ordinals, one per rank (overrides --device/--gpus; an ordinal may repeat).", "");
+  o.add("--realign", "Realign every overlap on the GPU before it is printed: a banded local alignment of the two reads around the diagonal the overlap implies replaces its interval, and column 3 becomes 1 - aligned identity. FASTA input, one GPU.", "false", true);
+  o.add("--realign-band", "[int] Half-width of the realignment band in bases. 0) the overlap's length times --max-shift.", "0");
+  o.add("--realign-min-identity", "[double] With --realign, drop overlaps whose aligned identity is below this value (overlaps without an alignment are always dropped).", "0.0");
   if (!o.parse(argc, argv)) return 0;
 
   auto bad = [&](const char* m) { printf("%s\n", m); exit(1); };
@@ -341,6 +380,14 @@ int main(int argc, char** argv) {
   }
   if (devs.empty()) bad("No device given.");
   const bool precompute = !o.s("-p").empty();
+  const bool realign = o.b("--realign") && !precompute;
+  if (realign) {   // refused before a handle exists
+    if (o.i("--realign-band") < 0) bad("The realignment band must be >=0.");
+    if (devs.size() > 1) bad("--realign runs on one GPU: give one device (--gpus 1).");
+    bool dat = ends_with(o.s("-s"), ".dat");
+    if (!o.s("-q").empty()) for (const std::string& cf : list_files(o.s("-q"))) dat = dat || ends_with(cf, ".dat");
+    if (dat) bad("--realign needs the reads' bases: give FASTA files, not .dat sketches.");
+  }
   if (precompute && devs.size() > 1) { fprintf(stderr, "Usage 2 (-p) writes its .dat files from one GPU: using device %d only.\n", devs[0]); devs.resize(1); }
   Engine E; E.n = (int)devs.size();
   char err[512] = {0};
@@ -402,6 +449,17 @@ int main(int argc, char** argv) {
   fprintf(stderr, "Time (s) to read and hash from file: %g\n", now() - t_proc);
 
   Sink sink{stdout};
+  Realign RA;
+  if (realign) {
+    RA.h = E.h; RA.band = o.i("--realign-band"); RA.min_identity = o.d("--realign-min-identity");
+    for (const std::string& sf : list_files(o.s("-s"))) {   // (ids as the index assigned them: FastaData's running count)
+      mhap_fasta fa;
+      if (mhap_fasta_read(sf.c_str(), (int64_t)RA.ids.size(), &fa, err, sizeof err) != MHAP_OK) die(err);
+      RA.add(fa);
+      mhap_fasta_free(&fa);
+    }
+    sink.realign = &RA;
+  }
   const double t_score = now();
   if (o.s("-q").empty()) {
     const double t = now();
@@ -437,6 +495,7 @@ int main(int argc, char** argv) {
       mhap_fasta fa;
       if (mhap_fasta_read(cf.c_str(), seq_processed, &fa, err, sizeof err) != MHAP_OK) die(err);   // id offset = reads so far (MhapMain.java:527)
       if (g_headers.full) collect_headers(fa);
+      if (realign) RA.add(fa);
       const mhap_stats s0 = E.stats();
       E.find_reads(fa, sink_cb, &sink);
       const mhap_stats s1 = E.stats();
@@ -450,6 +509,7 @@ int main(int argc, char** argv) {
   }
   sink_flush(sink);
   fprintf(stderr, "Total scoring time (s): %g\n", now() - t_score);
+  if (realign) fprintf(stderr, "Time (s) to realign: %g (%lld overlaps kept, %lld dropped: no alignment or identity below %g)\n", RA.seconds, (long long)RA.kept, (long long)RA.dropped, RA.min_identity);
   fprintf(stderr, "Total time (s): %g\n", now() - t_total);
   // outputFinalStat (MhapMain.java:572-590); the inverted-index counters have no brute-force analogue
   const mhap_stats st = E.stats();

@@ -76,6 +76,7 @@ struct HandleView {
   int device; hipStream_t stream;
   int num_cus;             // compute units the handle's persistent grids are sized for (capped_num_cus)
   int Hrow, S, k, min_olap_length;
+  double max_shift;        // --max-shift of the handle's parameters (the realignment stage's automatic band)
   int64_t n_entries;
   uint64_t index_gen;      // bumped by every change of the entry set
   const int32_t *d_minhash, *d_ordered, *d_meta;

@@ -1,0 +1,446 @@
+// realign_kernels.hip — the realignment stage: banded local alignment of reported overlaps on the GPU (mhap_align_pairs_banded) and the
+// host code that turns overlap records into banded pairs and back (mhap_realign_plan, mhap_realign_records).
+//
+// The contract is mhap_align_pairs' (include/mhap_hip.h) with one sentence added: a cell (i, j) outside the band |j - i - diag| <= band
+// has H = 0 and E = F = -inf and carries nothing.  tests/align_banded_ref.py restates it on the CPU.
+//
+// Geometry.  The band is clipped to the matrix first: the diagonals d = j - i it keeps are [dlo, dlo + W), W <= 2 band + 1, and the rows
+// that own an in-band cell are [ilo, ihi].  Nothing outside is touched, so a band that covers the matrix costs what the matrix costs
+// and a band that misses it costs nothing.
+//
+// Schedule.  As in align_kernels.hip, lane t owns a strip of R consecutive rows of s1 (R cells per step, in registers), walks along s2
+// one column per step and hands the bottom row of its strip (H, F and their carried values) to lane t + 1: __shfl_up inside a wave,
+// a double-buffered LDS slot between waves.  What changes is which columns a lane walks.  The band moves one column per row, so the
+// columns of lane t's strip are those of lane t - 1's shifted right by R: with row0 the first row of the strip, lane t walks the
+// W + R columns  cl0 = row0 + dlo - 1, ..., row0 + R - 1 + dlo + W - 1  (local index q = 0 .. W + R - 1; column cl0 itself holds no
+// in-band cell of the strip, it is walked to pick up H(row0 - 1, cl0), the diagonal predecessor of the strip's first cell).  Lane
+// t needs lane t - 1's bottom row at the same column one step earlier, and that column is lane t - 1's local index q + R, so lane t
+// runs its index q at step s = q + t (R + 1): every lane starts R + 1 steps after the one above — R because the band moved, 1 because
+// the chain advances — and at step s lane t is at column j = (pass row base + dlo - 1) + s - t.  Inside a row the E dependency
+// (i, j - 1) -> (i, j) is the lane's own previous step; the F dependency (i, j) -> (i + 1, j) is the next register of the strip, or
+// the lane below one step later.  For q >= W the cell above the strip is right of the band and the lane takes the boundary (H 0,
+// F -inf) instead of its neighbour's registers; a cell of the strip's W + R columns that is outside the band (the two triangles of
+// R (R + 1) / 2 cells at the ends of a strip) or outside the matrix is masked to the boundary, not computed into anything.
+// A pass of L lanes therefore takes (L - 1)(R + 1) + W + R steps for L R rows, of which every lane works W + R: lanes idle
+// (L - 1)(R + 1) steps each, which is why a batch with enough pairs to fill the device runs one wave per pair (L = 64: 567 idle steps
+// next to W + R, and no barrier) and only a batch too small for that spreads a pair over four waves.
+//
+// Passes.  Rows beyond one pass's L R go to further passes.  The bottom row of a pass goes to HBM as 10 words per in-band column — W
+// entries, indexed by the column's position in the band — and is the top boundary of the next pass: what crosses between passes is
+// sized by 2 band + 1, not by the length of s2.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "device_common.hpp"
+#include "mhap_internal.hpp"
+
+namespace mhap {
+namespace {
+
+constexpr int BA_R = 8;                // rows of s1 per lane
+constexpr int BA_NEG = -(1 << 28);     // minus infinity for E and F
+constexpr uint32_t BA_PAD = 0x100u;    // s1 "byte" of a row that does not exist: its cells are masked
+constexpr int BA_NWB = 4;              // waves of the wide kernel
+
+struct Meta { int bi, bj, cols, errs; };   // begin cell (0-based row, column), columns, errors of the path into a cell
+
+__device__ inline Meta meta_sel(bool c, const Meta& a, const Meta& b) {
+  return Meta{c ? a.bi : b.bi, c ? a.bj : b.bj, c ? a.cols : b.cols, c ? a.errs : b.errs};
+}
+__device__ inline Meta meta_shfl_up(const Meta& m) {
+  return Meta{__shfl_up(m.bi, 1), __shfl_up(m.bj, 1), __shfl_up(m.cols, 1), __shfl_up(m.errs, 1)};
+}
+// (score, end column, end row) order of the end cell: higher score, then smaller j, then smaller i
+__device__ inline bool better_end(int s, int j, int i, int bs, int bj, int bi) {
+  return s > bs || (s == bs && s > 0 && (j < bj || (j == bj && i < bi)));
+}
+
+struct Edge { int H, F; Meta mH, mF; };   // the bottom row of a strip at one column: what the strip below reads
+
+// The band clipped to the m x n matrix: diagonals [dlo, dlo + W) and rows [ilo, ilo + rows).  W = 0: no cell is in the band.
+struct BandGeom { int dlo, W, ilo, rows; };
+__host__ __device__ inline BandGeom band_geom(int64_t m, int64_t n, int64_t diag, int64_t band) {
+  const int64_t lim = (int64_t)1 << 40;          // beyond any matrix: keeps diag +- band inside int64
+  diag = diag < -lim ? -lim : diag > lim ? lim : diag;
+  band = band > lim ? lim : band;
+  const int64_t lo = diag - band > -(m - 1) ? diag - band : -(m - 1), hi = diag + band < n - 1 ? diag + band : n - 1;
+  if (m <= 0 || n <= 0 || band < 0 || hi < lo) return BandGeom{0, 0, 0, 0};
+  const int64_t ilo = -hi > 0 ? -hi : 0, ihi = n - 1 - lo < m - 1 ? n - 1 - lo : m - 1;   // rows with a column j = i + d in [0, n)
+  return BandGeom{(int)lo, (int)(hi - lo + 1), (int)ilo, (int)(ihi - ilo + 1)};
+}
+
+template <int NW>
+__global__ __launch_bounds__(NW * 64) void align_banded_kernel(const uint8_t* __restrict__ bases, const int64_t* __restrict__ pairs,
+                                                               const int32_t* __restrict__ order, int n_order, int* __restrict__ next,
+                                                               int32_t* __restrict__ scratch, int64_t scratch_stride,
+                                                               int32_t* __restrict__ results) {
+  constexpr int T = NW * 64;
+  __shared__ Edge hand[2][NW > 1 ? NW - 1 : 1];     // lane 63 of wave w -> lane 0 of wave w + 1, by step parity
+  __shared__ int best_s[T], best_j[T], best_i[T];
+  __shared__ Meta best_m[T];
+  __shared__ int cur;
+  const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+  int32_t* edge = scratch ? scratch + (int64_t)blockIdx.x * scratch_stride : nullptr;
+  for (;;) {
+    if (t == 0) cur = atomicAdd(next, 1);
+    __syncthreads();
+    const int k = cur;
+    __syncthreads();
+    if (k >= n_order) return;
+    const int pi = order[k];
+    const int64_t* pr = pairs + 7 * (int64_t)pi;
+    const int64_t a_off = pr[0], b_off = pr[2];
+    const int m = (int)pr[1], n = (int)pr[3];
+    const bool b_rc = pr[4] != 0;
+    const BandGeom g = band_geom(m, n, pr[5], pr[6]);
+    const int W = g.W, ihi = g.ilo + g.rows - 1;
+    // lanes and passes: as few passes as T lanes allow, then as few lanes as that many passes need; rows past ihi are masked
+    int passes = 0, L = 1;
+    if (W > 0) {
+      passes = (g.rows + T * BA_R - 1) / (T * BA_R);
+      L = (g.rows + passes * BA_R - 1) / (passes * BA_R);
+    }
+    const int P = L * BA_R;
+    int ls = 0, lj = 0, li = 0;               // this lane's best end cell over all passes
+    Meta lm{0, 0, 0, 0};
+    for (int p = 0; p < passes; p++) {
+      uint32_t c1[BA_R];
+      int Hp[BA_R], Ep[BA_R];
+      Meta Hm[BA_R], Em[BA_R];
+      const int pbase = g.ilo + p * P, row0 = pbase + t * BA_R;
+#pragma unroll
+      for (int r = 0; r < BA_R; r++) {
+        const int i = row0 + r;
+        c1[r] = (t < L && i <= ihi) ? (uint32_t)bases[a_off + i] : BA_PAD;
+        Hp[r] = 0; Ep[r] = BA_NEG; Hm[r] = Meta{0, 0, 0, 0}; Em[r] = Meta{0, 0, 0, 0};
+      }
+      int dH = 0;                                // H(row0 - 1, j - 1) and its carried values
+      Meta dm{0, 0, 0, 0};
+      Edge out{0, BA_NEG, {0, 0, 0, 0}, {0, 0, 0, 0}};
+      int ps = 0, pj = 0, pin = 0;               // this pass's best: strict > is the tie rule within a lane (j, then i, increase)
+      Meta pm{0, 0, 0, 0};
+      // lane t at step s: local column q = s - t (R + 1), column j = jc + s - t.  Steps before lane 0 reaches column 0 and after
+      // the last lane has left its columns or s2 have no active lane.
+      const int jc = pbase + g.dlo - 1;
+      const int s_begin = jc < 0 ? -jc : 0;
+      const int s_end = min((L - 1) * (BA_R + 1) + W + BA_R, n - jc + L - 1);
+      for (int s = s_begin; s < s_end; s++) {
+        const int q = s - t * (BA_R + 1), j = jc + s - t;
+        const bool active = t < L && q >= 0 && q < W + BA_R && j >= 0 && j < n;
+        Edge in;
+        in.H = __shfl_up(out.H, 1); in.F = __shfl_up(out.F, 1); in.mH = meta_shfl_up(out.mH); in.mF = meta_shfl_up(out.mF);
+        if (NW > 1 && lane == 0 && t > 0) in = hand[(s + 1) & 1][wave - 1];
+        if (active) {
+          // the cell above the strip at this column: right of the band for q >= W, the previous pass's bottom row for lane 0
+          if (q >= W || (t == 0 && p == 0)) { in.H = 0; in.F = BA_NEG; in.mH = Meta{0, 0, 0, 0}; in.mF = in.mH; }
+          else if (t == 0) {
+            const int32_t* e = edge + q;
+            in.H = e[0]; in.F = e[W]; in.mH = Meta{e[2 * W], e[3 * W], e[4 * W], e[5 * W]}; in.mF = Meta{e[6 * W], e[7 * W], e[8 * W], e[9 * W]};
+          }
+          const uint32_t c2 = b_rc ? rc_char(bases[b_off + (n - 1 - j)]) : (uint32_t)bases[b_off + j];
+          int upH = in.H, upF = in.F;
+          Meta upmH = in.mH, upmF = in.mF;
+          int diagH = dH;
+          Meta diagm = dm;
+#pragma unroll
+          for (int r = 0; r < BA_R; r++) {
+            const int i = row0 + r;
+            // row r's in-band columns are the local indices r + 1 .. r + W
+            const bool inband = c1[r] != BA_PAD && (unsigned)(q - 1 - r) < (unsigned)W;
+            const bool mis = c1[r] != c2;
+            const int D = diagH + (mis ? -2 : 2);
+            // E(i,j) = max(H(i,j-1) - 2, E(i,j-1) - 1): a deletion (consumes s2); extension wins a tie
+            const int eext = Ep[r] - 1, eopn = Hp[r] - 2;
+            const bool ext = eext >= eopn;
+            int E = ext ? eext : eopn;
+            Meta me = meta_sel(ext, Em[r], Hm[r]);
+            me.cols += 1; me.errs += 1;
+            // F(i,j) = max(H(i-1,j) - 2, F(i-1,j) - 1): an insertion (consumes s1); extension wins a tie
+            const int fext = upF - 1, fopn = upH - 2;
+            const bool fx = fext >= fopn;
+            int F = fx ? fext : fopn;
+            Meta mf = meta_sel(fx, upmF, upmH);
+            mf.cols += 1; mf.errs += 1;
+            // H = max(0, diagonal, E, F), preferring diagonal, then E, then F; a diagonal step out of an H = 0 cell begins a path
+            Meta md = diagm;
+            md.cols += 1; md.errs += mis ? 1 : 0;
+            if (diagH == 0) md = Meta{i, j, 1, mis ? 1 : 0};
+            const bool take_d = D > 0 && D >= E && D >= F;
+            const bool take_e = !take_d && E > 0 && E >= F;
+            const bool take_f = !take_d && !take_e && F > 0;
+            int H = take_d ? D : take_e ? E : take_f ? F : 0;
+            const Meta mh = meta_sel(take_d, md, meta_sel(take_e, me, mf));
+            // a cell outside the band (or the matrix) is the boundary; what it carries is never read: only a positive value's carried
+            // fields reach a result, and nothing positive descends from H = 0, E = F = -inf
+            if (!inband) { H = 0; E = BA_NEG; F = BA_NEG; }
+            diagH = Hp[r]; diagm = Hm[r];
+            Hp[r] = H; Hm[r] = mh; Ep[r] = E; Em[r] = me;
+            upH = H; upF = F; upmH = mh; upmF = mf;
+            if (H > ps) { ps = H; pj = j; pin = i; pm = mh; }
+          }
+          dH = in.H; dm = in.mH;
+          out = Edge{upH, upF, upmH, upmF};
+          // the strip's bottom row is in the band at local indices R .. R + W - 1: position q - R of the W the next pass reads
+          if (t == L - 1 && p + 1 < passes && q >= BA_R) {
+            int32_t* e = edge + (q - BA_R);
+            e[0] = out.H; e[W] = out.F;
+            e[2 * W] = out.mH.bi; e[3 * W] = out.mH.bj; e[4 * W] = out.mH.cols; e[5 * W] = out.mH.errs;
+            e[6 * W] = out.mF.bi; e[7 * W] = out.mF.bj; e[8 * W] = out.mF.cols; e[9 * W] = out.mF.errs;
+          }
+        } else {
+          dH = 0;   // the diagonal predecessor of a lane's first column is left of the band or of the matrix
+        }
+        if constexpr (NW > 1) {
+          if (lane == 63 && wave + 1 < NW) hand[s & 1][wave] = out;
+          __syncthreads();
+        }
+      }
+      if (better_end(ps, pj, pin, ls, lj, li)) { ls = ps; lj = pj; li = pin; lm = pm; }
+      __syncthreads();   // the pass's bottom row (HBM) before the next pass reads it
+    }
+    best_s[t] = ls; best_j[t] = lj; best_i[t] = li; best_m[t] = lm;
+    __syncthreads();
+    if (t == 0) {
+      int b = 0;
+      for (int u = 1; u < T; u++)
+        if (better_end(best_s[u], best_j[u], best_i[u], best_s[b], best_j[b], best_i[b])) b = u;
+      int32_t* o = results + 7 * (int64_t)pi;
+      if (best_s[b] > 0) {
+        o[0] = best_s[b]; o[1] = best_m[b].bi; o[2] = best_i[b]; o[3] = best_m[b].bj; o[4] = best_j[b];
+        o[5] = best_m[b].cols; o[6] = best_m[b].errs;
+      } else {
+        o[0] = 0; o[1] = o[2] = o[3] = o[4] = -1; o[5] = o[6] = 0;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+struct BandedBufs {
+  DevBuf bases, pairs, order, next, scratch, results;
+  void release() { bases.release(); pairs.release(); order.release(); next.release(); scratch.release(); results.release(); }
+};
+
+constexpr int64_t BA_SCRATCH_BUDGET = (int64_t)1 << 30;   // bytes of pass boundaries in flight; fewer workgroups beyond that
+
+// `pairs` (host, validated) against the bases already in B.bases; everything on v.stream, results on the host when it returns.
+int banded_run(const HandleView& v, BandedBufs& B, const int64_t* pairs, int64_t n, int32_t* results, const char* who) {
+  auto fail = [&](hipError_t e, const char* what) {
+    *v.err = std::string(who) + ": " + what + ": " + hipGetErrorString(e);
+    return MHAP_E_HIP;
+  };
+  // A pair whose band has more rows than one wave holds goes to the four-wave kernel only while such pairs are too few to give every
+  // compute unit its waves; with more of them a wave per pair idles less (the header comment) and needs no barrier.
+  std::vector<BandGeom> geo((size_t)n);
+  int64_t n_tall = 0;
+  for (int64_t q = 0; q < n; q++) {
+    geo[(size_t)q] = band_geom(pairs[7 * q + 1], pairs[7 * q + 3], pairs[7 * q + 5], pairs[7 * q + 6]);
+    n_tall += geo[(size_t)q].rows > 64 * BA_R;
+  }
+  const bool spread = n_tall < 4LL * v.num_cus;
+  std::vector<int32_t> big, small;
+  for (int64_t q = 0; q < n; q++) (spread && geo[(size_t)q].rows > 64 * BA_R ? big : small).push_back((int32_t)q);
+  auto cells = [&](int32_t q) { return (double)geo[(size_t)q].rows * (double)geo[(size_t)q].W; };
+  auto by_cells = [&](int32_t a, int32_t b) { const double ca = cells(a), cb = cells(b); return ca != cb ? ca > cb : a < b; };
+  std::stable_sort(big.begin(), big.end(), by_cells);     // longest first
+  std::stable_sort(small.begin(), small.end(), by_cells);
+  std::vector<int32_t> order(big);
+  order.insert(order.end(), small.begin(), small.end());
+  // HBM rows between passes: 10 words per diagonal of the widest band that needs a second pass, one set per workgroup
+  int64_t w_big = 0, w_small = 0;
+  for (int32_t q : big) if (geo[(size_t)q].rows > BA_NWB * 64 * BA_R) w_big = std::max<int64_t>(w_big, geo[(size_t)q].W);
+  for (int32_t q : small) if (geo[(size_t)q].rows > 64 * BA_R) w_small = std::max<int64_t>(w_small, geo[(size_t)q].W);
+  int grid_big = (int)std::min<int64_t>((int64_t)big.size(), 2LL * v.num_cus);        // (the handle's compute units: MHAP_NUM_CUS caps them)
+  int grid_small = (int)std::min<int64_t>((int64_t)small.size(), 8LL * v.num_cus);   // (184 VGPRs: two waves per SIMD)
+  const int64_t stride_big = 10 * w_big, stride_small = 10 * w_small;
+  if (stride_big > 0) grid_big = (int)std::max<int64_t>(1, std::min<int64_t>(grid_big, BA_SCRATCH_BUDGET / 2 / (stride_big * 4)));
+  if (stride_small > 0) grid_small = (int)std::max<int64_t>(1, std::min<int64_t>(grid_small, BA_SCRATCH_BUDGET / 2 / (stride_small * 4)));
+  const int64_t scratch_big = stride_big * grid_big, scratch_words = scratch_big + stride_small * grid_small;
+  hipError_t e;
+  if ((e = B.pairs.ensure(56 * n)) != hipSuccess) return fail(e, "hipMalloc");
+  if ((e = B.order.ensure(4 * n)) != hipSuccess) return fail(e, "hipMalloc");
+  if ((e = B.next.ensure(8)) != hipSuccess) return fail(e, "hipMalloc");
+  if ((e = B.results.ensure(28 * n)) != hipSuccess) return fail(e, "hipMalloc");
+  if (scratch_words > 0 && (e = B.scratch.ensure((size_t)scratch_words * 4)) != hipSuccess) return fail(e, "hipMalloc (pass boundaries)");
+  if ((e = hipMemcpyAsync(B.pairs.p, pairs, 56 * n, hipMemcpyHostToDevice, v.stream)) != hipSuccess) return fail(e, "upload");
+  if ((e = hipMemcpyAsync(B.order.p, order.data(), 4 * n, hipMemcpyHostToDevice, v.stream)) != hipSuccess) return fail(e, "upload");
+  if ((e = hipMemsetAsync(B.next.p, 0, 8, v.stream)) != hipSuccess) return fail(e, "memset");
+  int* nx = B.next.as<int>();
+  if (!big.empty())
+    hipLaunchKernelGGL(align_banded_kernel<BA_NWB>, dim3(grid_big), dim3(BA_NWB * 64), 0, v.stream, B.bases.as<uint8_t>(), B.pairs.as<int64_t>(),
+                       B.order.as<int32_t>(), (int)big.size(), nx, stride_big > 0 ? B.scratch.as<int32_t>() : nullptr, stride_big,
+                       B.results.as<int32_t>());
+  if (!small.empty())
+    hipLaunchKernelGGL(align_banded_kernel<1>, dim3(grid_small), dim3(64), 0, v.stream, B.bases.as<uint8_t>(), B.pairs.as<int64_t>(),
+                       B.order.as<int32_t>() + big.size(), (int)small.size(), nx + 1,
+                       stride_small > 0 ? B.scratch.as<int32_t>() + scratch_big : nullptr, stride_small, B.results.as<int32_t>());
+  if ((e = hipGetLastError()) != hipSuccess) return fail(e, "launch");
+  if ((e = hipMemcpyAsync(results, B.results.p, 28 * n, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return fail(e, "download");
+  if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return fail(e, "kernel");
+  return MHAP_OK;
+}
+
+int check_pairs(const int64_t* pairs, int64_t n, int64_t n_bases, std::string* err, const char* who) {
+  for (int64_t q = 0; q < n; q++) {
+    const int64_t* p = pairs + 7 * q;
+    for (int f = 0; f < 2; f++) {
+      const int64_t off = p[2 * f], len = p[2 * f + 1];
+      if (off < 0 || len < 0 || len > INT32_MAX / 4 || off > n_bases - len) {
+        *err = std::string(who) + ": pair " + std::to_string(q) + " has a segment outside the " + std::to_string(n_bases) + " bases";
+        return MHAP_E_INVALID;
+      }
+    }
+    if (p[6] < 0) { *err = std::string(who) + ": pair " + std::to_string(q) + " has a negative band (" + std::to_string(p[6]) + ")"; return MHAP_E_INVALID; }
+  }
+  return MHAP_OK;
+}
+
+int upload_bases(const HandleView& v, BandedBufs& B, const uint8_t* bases, int64_t n_bases, const char* who) {
+  hipError_t e;
+  (void)hipSetDevice(v.device);
+  if ((e = B.bases.ensure((size_t)std::max<int64_t>(n_bases, 1))) != hipSuccess) { *v.err = std::string(who) + ": hipMalloc: " + hipGetErrorString(e); return MHAP_E_HIP; }
+  if (n_bases > 0 && (e = hipMemcpyAsync(B.bases.p, bases, (size_t)n_bases, hipMemcpyHostToDevice, v.stream)) != hipSuccess) {
+    *v.err = std::string(who) + ": upload: " + hipGetErrorString(e);
+    return MHAP_E_HIP;
+  }
+  return MHAP_OK;
+}
+
+inline int64_t floor_div2(int64_t x) { return x >= 0 ? x / 2 : -((-x + 1) / 2); }
+
+// the plan of one record; `map` finds a read by id
+int plan_one(const mhap_record& r, int64_t q, const std::unordered_map<int64_t, int64_t>& map, const int64_t* offsets, const int32_t* lengths,
+             double max_shift, int32_t band, int64_t* out, std::string* err) {
+  int64_t idx[2];
+  const int64_t ids[2] = {r.from_id, r.to_id};
+  const int32_t lens[2] = {r.alen, r.blen};
+  for (int f = 0; f < 2; f++) {
+    const auto it = map.find(ids[f]);
+    if (it == map.end()) { *err = "mhap_realign_plan: record " + std::to_string(q) + " names read " + std::to_string(ids[f]) + ", which is not among the reads"; return MHAP_E_INVALID; }
+    idx[f] = it->second;
+    if (lengths[idx[f]] != lens[f]) {
+      *err = "mhap_realign_plan: record " + std::to_string(q) + " gives read " + std::to_string(ids[f]) + " the length " + std::to_string(lens[f]) +
+             ", the reads say " + std::to_string(lengths[idx[f]]);
+      return MHAP_E_INVALID;
+    }
+  }
+  const bool rc = r.to_rc != 0;
+  const int64_t b1 = rc ? (int64_t)r.blen - r.b2 - 1 : r.b1, b2 = rc ? (int64_t)r.blen - r.b1 - 1 : r.b2;   // MatchResult's flip undone
+  out[0] = offsets[idx[0]]; out[1] = r.alen; out[2] = offsets[idx[1]]; out[3] = r.blen; out[4] = rc ? 1 : 0;
+  out[5] = floor_div2((b1 + b2) - ((int64_t)r.a1 + r.a2));
+  if (band > 0) out[6] = band;
+  else {
+    // the tolerance the second stage applies around its median shift (BottomOverlapSketch.java:205)
+    const int64_t span = std::max<int64_t>((int64_t)r.a2 - r.a1, b2 - b1);
+    const double w = (double)span * max_shift;   // (int) of a double as Java casts it: toward zero, saturating; anything below 1 gives 1
+    out[6] = w >= 2147483647.0 ? 2147483647 : w >= 1.0 ? (int64_t)w : 1;
+  }
+  return MHAP_OK;
+}
+
+int build_map(const int64_t* read_ids, int64_t n_reads, std::unordered_map<int64_t, int64_t>& map) {
+  map.reserve((size_t)n_reads * 2);
+  for (int64_t i = 0; i < n_reads; i++) map.emplace(read_ids[i], i);   // (the first read of an id wins)
+  return MHAP_OK;
+}
+
+thread_local std::string g_plan_err;
+
+}  // namespace
+}  // namespace mhap
+
+using namespace mhap;
+
+extern "C" int mhap_align_pairs_banded(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const int64_t* pairs, int64_t n, int32_t* results) {
+  if (!h) return MHAP_E_INVALID;
+  HandleView v = handle_view(h);
+  const char* who = "mhap_align_pairs_banded";
+  if (n < 0 || n_bases < 0 || (n > 0 && (!pairs || !results)) || (n_bases > 0 && !bases)) { *v.err = std::string(who) + ": null or negative argument"; return MHAP_E_INVALID; }
+  if (n > INT32_MAX) { *v.err = std::string(who) + ": more than 2^31 - 1 pairs in one call"; return MHAP_E_INVALID; }
+  if (n == 0) return MHAP_OK;
+  int rc = check_pairs(pairs, n, n_bases, v.err, who);
+  if (rc != MHAP_OK) return rc;
+  BandedBufs B;
+  rc = upload_bases(v, B, bases, n_bases, who);
+  if (rc == MHAP_OK) rc = banded_run(v, B, pairs, n, results, who);
+  B.release();
+  return rc;
+}
+
+extern "C" const char* mhap_realign_plan_error(void) { return g_plan_err.c_str(); }
+
+extern "C" int mhap_realign_plan(const mhap_record* recs, int64_t n, const int64_t* read_ids, const int64_t* offsets, const int32_t* lengths,
+                                 int64_t n_reads, double max_shift, int32_t band, int64_t* pairs) {
+  g_plan_err.clear();
+  if (n < 0 || n_reads < 0 || band < 0 || (n > 0 && (!recs || !pairs)) || (n_reads > 0 && (!read_ids || !offsets || !lengths))) {
+    g_plan_err = "mhap_realign_plan: null or negative argument";
+    return MHAP_E_INVALID;
+  }
+  std::unordered_map<int64_t, int64_t> map;
+  build_map(read_ids, n_reads, map);
+  for (int64_t q = 0; q < n; q++) {
+    const int rc = plan_one(recs[q], q, map, offsets, lengths, max_shift, band, pairs + 7 * q, &g_plan_err);
+    if (rc != MHAP_OK) return rc;
+  }
+  return MHAP_OK;
+}
+
+extern "C" int mhap_realign_records(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const int64_t* read_ids, const int64_t* offsets,
+                                    const int32_t* lengths, int64_t n_reads, const mhap_record* recs, int64_t n, int32_t band,
+                                    mhap_record* out, int32_t* detail) {
+  if (!h) return MHAP_E_INVALID;
+  HandleView v = handle_view(h);
+  const char* who = "mhap_realign_records";
+  if (n < 0 || n_bases < 0 || n_reads < 0 || band < 0 || (n > 0 && (!recs || !out)) || (n_bases > 0 && !bases) ||
+      (n_reads > 0 && (!read_ids || !offsets || !lengths))) {
+    *v.err = std::string(who) + ": null or negative argument";
+    return MHAP_E_INVALID;
+  }
+  if (n == 0) return MHAP_OK;
+  for (int64_t i = 0; i < n_reads; i++)
+    if (offsets[i] < 0 || lengths[i] < 0 || offsets[i] > n_bases - lengths[i]) {
+      *v.err = std::string(who) + ": read " + std::to_string(i) + " lies outside the " + std::to_string(n_bases) + " bases";
+      return MHAP_E_INVALID;
+    }
+  std::unordered_map<int64_t, int64_t> map;
+  build_map(read_ids, n_reads, map);
+  // The bases go up once.  Records go through in batches of at most BATCH: 56 + 28 bytes of pairs and results and 4 of work order per
+  // record (5.8 MB) on each side, and the pass boundaries of the workgroups in flight (at most BA_SCRATCH_BUDGET, 1 GiB), whatever n is.
+  constexpr int64_t BATCH = 1 << 16;
+  BandedBufs B;
+  int rc = upload_bases(v, B, bases, n_bases, who);
+  std::vector<int64_t> pairs((size_t)std::min(n, BATCH) * 7);
+  std::vector<int32_t> res((size_t)std::min(n, BATCH) * 7);
+  for (int64_t q0 = 0; q0 < n && rc == MHAP_OK; q0 += BATCH) {
+    const int64_t c = std::min(BATCH, n - q0);
+    for (int64_t q = 0; q < c && rc == MHAP_OK; q++)
+      rc = plan_one(recs[q0 + q], q0 + q, map, offsets, lengths, v.max_shift, band, pairs.data() + 7 * q, v.err);
+    if (rc != MHAP_OK) break;
+    rc = banded_run(v, B, pairs.data(), c, res.data(), who);
+    if (rc != MHAP_OK) break;
+    for (int64_t q = 0; q < c; q++) {
+      const mhap_record& r = recs[q0 + q];
+      const int32_t* a = res.data() + 7 * q;
+      mhap_record o = r;
+      o.pad = 0;
+      const bool ok = a[0] > 0 && a[5] > 0;
+      if (ok) {
+        o.a1 = a[1]; o.a2 = a[2];
+        o.b1 = r.to_rc ? r.blen - a[4] - 1 : a[3];
+        o.b2 = r.to_rc ? r.blen - a[3] - 1 : a[4];
+        o.score = 1.0 - (double)a[6] / (double)a[5];
+      } else {
+        o.a1 = o.a2 = o.b1 = o.b2 = 0; o.score = 0.0;
+      }
+      out[q0 + q] = o;
+      if (detail) { detail[3 * (q0 + q)] = ok ? a[0] : 0; detail[3 * (q0 + q) + 1] = ok ? a[5] : 0; detail[3 * (q0 + q) + 2] = ok ? a[6] : 0; }
+    }
+  }
+  B.release();
+  return rc;
+}
