@@ -256,7 +256,8 @@ int mhap_find_matches_self(mhap_handle* h, int64_t q_first, int64_t q_count, mha
 
 /* Sharded self-overlap for one-process-per-GPU runs: this call searches the forward entries whose read
  * ordinal (position among the index's reads) is congruent to `shard` modulo `nshards`; the union over all
- * shards equals mhap_find_matches_self(h, 0, -1).  Round-robin balances the triangular id rule. */
+ * shards equals mhap_find_matches_self(h, 0, -1).  Round-robin balances the triangular id rule.  The ordinal counts the forward
+ * entries in entry order, placeholders included: entry / 2 for sketched reads, the entry itself in an index of forward rows only. */
 int mhap_find_matches_self_shard(mhap_handle* h, int64_t shard, int64_t nshards, mhap_record_sink sink, void* user);
 
 /* Index-vs-stream (-q mode, toSelf=false): sketch the `n` query reads (forward only,
@@ -355,7 +356,13 @@ int mhap_group_get_stats(mhap_group* g, mhap_stats* sum);           /* counters 
 int mhap_get_stats(mhap_handle* h, mhap_stats* out);
 int mhap_get_kernel_times(mhap_handle* h, mhap_kernel_times* out);
 int mhap_reset_kernel_times(mhap_handle* h);
-/* Use an externally created hipStream_t (e.g. torch's current stream); NULL = library stream. */
+/* Use an externally created hipStream_t (e.g. torch's current stream); NULL = library stream.  The call first waits for the work
+ * the handle queued on the stream it leaves.  Ordering a caller may rely on: the library's kernels are queued on the given stream, so
+ * they run behind whatever the caller queued there before the call, and every entry point returns only once its own work on the
+ * stream is complete.  Nothing else is ordered: the meta words of caller-owned tables (mhap_index_set_device,
+ * mhap_find_matches_device) and the copies of mhap_index_export are read outside that stream, and work on the caller's OTHER
+ * streams is never waited for — such buffers must be complete before the call (the ordered rows excepted, see mhap_index_prepare and
+ * mhap_set_second_stage_gate). */
 int mhap_set_stream(mhap_handle* h, void* hip_stream);
 int mhap_synchronize(mhap_handle* h);
 

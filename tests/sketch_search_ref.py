@@ -83,6 +83,54 @@ def expected_records(entries, queries=None, *, H, k2, num_min_matches, min_store
     return (lines, len(pairs)) if return_compared else lines
 
 
+def oracle_tables(fa, *, H, S, k=16, k2=12, min_olap_length=116, repeat_weight=0.9, both_strands=True, nthreads=16):
+    """The sketch tables of the reads of `fa` from the oracle's primitives (O.minhash, O.ordered), laid out as export() returns them,
+    WITH the status column: entry 2 i = read i forward, 2 i + 1 = its reverse complement (both_strands=False: forward rows only, entry
+    i = read i).  Statuses as orc_run_self sets them (SequenceSketchStreamer.java:129-133, 235-238): 2 for both strands of a read
+    shorter than min_olap_length, 1 for both when the forward strand has no k-mers, 1 for a reverse strand that fails alone.  Rows
+    whose status is not 0 keep seq_length and are zero elsewhere."""
+    n, per = len(fa), 2 if both_strands else 1
+
+    def one(i):
+        s = fa.sequence(i)
+        if len(s) < min_olap_length:
+            return [(2, None, None, 0)] * per
+        out = []
+        for t in ((s, O.rc(s)) if both_strands else (s,)):
+            rc1, mh = O.minhash(t, k, H, repeat_weight)
+            rc2, od, olen = O.ordered(t, k2, S)
+            out.append((1, None, None, 0) if (rc1 or rc2) else (0, mh, od, olen))
+        if out[0][0] != 0:
+            out = [(1, None, None, 0)] * per
+        return out
+
+    with ThreadPoolExecutor(nthreads) as ex:
+        rows = list(ex.map(one, range(n)))
+    m = per * n
+    t = {"ids": np.repeat(np.asarray(fa.ids, np.int64), per), "is_fwd": np.tile(np.array([1, 0][:per], np.uint8), n),
+         "seq_length": np.repeat(np.asarray(fa.lengths, np.int32), per), "minhash": np.zeros((m, max(1, H)), np.int32),
+         "ordered": np.zeros((m, S, 2), np.int32), "ordered_size": np.zeros(m, np.int32), "ordered_seqlen": np.zeros(m, np.int32),
+         "status": np.zeros(m, np.uint8)}
+    for i, r in enumerate(rows):
+        for j, (st, mh, od, olen) in enumerate(r):
+            e = per * i + j
+            t["status"][e] = st
+            if st == 0:
+                t["minhash"][e] = mh
+                t["ordered"][e, :len(od)] = od
+                t["ordered_size"][e], t["ordered_seqlen"][e] = len(od), olen
+    return t
+
+
+def stored_rows(t, forward_only=False):
+    """The rows of oracle_tables / export() that are stored (status 0), without the status column: what add_sketches and
+    expected_records take."""
+    keep = np.asarray(t["status"]) == 0
+    if forward_only:
+        keep &= np.asarray(t["is_fwd"]) != 0
+    return {k: np.asarray(v)[keep] for k, v in t.items() if k != "status"}
+
+
 # ---- rows a Java .dat could hold ------------------------------------------------------------------------------------------------
 def check_row(row, seqlen, S):
     """Assert the invariants of an ordered row as OrderedNGramHashes leaves it: sorted by (signed hash, position), distinct
