@@ -16,10 +16,9 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libmhaphip.so")
 CLI = os.path.join(LIBDIR, "mhap-hip")
 KMERS_CLI = os.path.join(LIBDIR, "mhap-hip-kmers")   # the -f filter file from the reads (mhap_kmers_cli.cpp)
-SOURCES = ["sketch_kernels.hip", "search_kernels.hip", "search_kernels_wide.hip", "search_kernels_wide2.hip", "mhap_capi.hip", "mhap_dist.hip", "mhap_ingest.hip", "kmer_kernels.hip", "align_kernels.hip", "realign_kernels.hip", "ksim_kernels.hip", "host_util.cpp"]
+SOURCES = ["sketch_kernels.hip", "search_kernels.hip", "join_kernels.hip", "mhap_capi.hip", "mhap_dist.hip", "mhap_ingest.hip", "kmer_kernels.hip", "align_kernels.hip", "realign_kernels.hip", "ksim_kernels.hip", "host_util.cpp"]
 HEADERS = ["device_common.hpp", "kernels.hpp", "mhap_internal.hpp", "overlap_lane.hpp", os.path.join("..", "..", "include", "mhap_hip.h")]
 ARCH = "gfx950"
-EXTRA_DEPS = {"search_kernels_wide.hip": ["search_kernels.hip"], "search_kernels_wide2.hip": ["search_kernels.hip"]}   # (a translation unit that includes another one)
 
 
 def _hipcc():
@@ -55,7 +54,7 @@ def stale_objects():
     for s in SOURCES:
         obj = os.path.join(OBJDIR, os.path.splitext(s)[0] + ".o")
         cmd = [f"--offload-arch={ARCH}", *[f for f in CFLAGS if f != "-shared"], "-c", os.path.join(CSRC, s), "-o", obj]
-        dg = _digest([os.path.join(CSRC, s)] + [os.path.join(CSRC, d) for d in EXTRA_DEPS.get(s, [])] + hdrs, cmd)
+        dg = _digest([os.path.join(CSRC, s)] + hdrs, cmd)
         if _stale(obj, dg):
             out.append(s)
     return out
@@ -98,15 +97,12 @@ def _compile_objects(hipcc, flags, only, tag, force, verbose):
     from concurrent.futures import ThreadPoolExecutor
     os.makedirs(OBJDIR, exist_ok=True)
     hdrs = [os.path.join(CSRC, h) for h in HEADERS]
-    # a translation unit that textually includes a listed one is a variant too (-DMH_OJ_GCAP on search_kernels.hip alone left
-    # the two wider passes of the join kernel at the default and the A/B silently mixed configurations)
-    only = list(only) + [s for s, deps in EXTRA_DEPS.items() if s not in only and any(d in only for d in deps)]
     jobs, objs = [], []
     for s in SOURCES:
         variant = bool(flags) and s in only
         obj = os.path.join(OBJDIR, os.path.splitext(s)[0] + (f".{tag}" if variant else "") + ".o")
         cmd = [hipcc, f"--offload-arch={ARCH}", *[f for f in CFLAGS if f != "-shared"], *(flags if variant else []), "-c", os.path.join(CSRC, s), "-o", obj]
-        dg = _digest([os.path.join(CSRC, s)] + [os.path.join(CSRC, d) for d in EXTRA_DEPS.get(s, [])] + hdrs, cmd[1:])
+        dg = _digest([os.path.join(CSRC, s)] + hdrs, cmd[1:])
         objs.append(obj)
         if force or _stale(obj, dg):
             jobs.append((cmd, obj, dg))
@@ -171,9 +167,9 @@ def build(force=False, verbose=False, variants=()):
 
 
 def build_variant(name, flags, only=None, verbose=False):
-    """An ad-hoc variant (tools/build_variant.sh): extra -D flags on the given translation units (default: the two kernel files)."""
+    """An ad-hoc variant (tools/build_variant.sh): extra -D flags on the given translation units (default: the three kernel files)."""
     hipcc = _hipcc()
-    vobjs, _ = _compile_objects(hipcc, list(flags), only or ["sketch_kernels.hip", "search_kernels.hip"], name, False, verbose)
+    vobjs, _ = _compile_objects(hipcc, list(flags), only or ["sketch_kernels.hip", "search_kernels.hip", "join_kernels.hip"], name, False, verbose)
     _link(hipcc, vobjs, variant_path(name), False, verbose)
     return variant_path(name)
 

@@ -87,10 +87,9 @@ struct mhap_handle {
   int num_cus = 256;
   hipStream_t stream = nullptr;
   hipStream_t own_stream = nullptr;
-  int oj_per_cu[3] = {0, 0, 0}, oj_per_cu_S = -1;   // resident join-kernel workgroups per CU (per shape) at ordered sketch size oj_per_cu_S
+  int oj_per_cu[OJ_LEVELS][3] = {}, oj_per_cu_S = -1;   // resident join-kernel workgroups per CU by level and shape at ordered sketch size oj_per_cu_S (0: not asked yet)
   int join_mode = 0;                      // MHAP_JOIN_MODE: 0 = by the candidates per query, 1 = alone, 2 = pair, 3 = team
   int join_wide = 2;                      // MHAP_JOIN_WIDE: further passes of the join kernel (512, then 1 536 joined k-mers) over the pairs handed over: 0, 1 or 2 of them
-  int ojw_per_cu[2] = {1, 1}, ojw_per_cu_S[2] = {-1, -1};
   hipStream_t mh_stream = nullptr;        // MinHash launch of the weighted strands, next to the launch of the weight-1 strands
   hipEvent_t ev_mh_fork = nullptr, ev_mh_join = nullptr, ev_ix_fork = nullptr, ev_ix_join = nullptr;
   // inverted index state: inv_ends / inv_items hold the index of entries [0, inv_ne) when inv_ready
@@ -203,7 +202,7 @@ int sync_stream(mhap_handle* h) {
 // (J/sketch/BottomOverlapSketch.java:391-395) evaluated on the host so libm lives in one place.
 // pass_min[kk] = the smallest number of shared k-mers that reaches the threshold for ANY k' >= kk, read off the score table itself
 // (no monotonicity assumed): a pair with fewer joined k-mers than pass_min[lower bound of its k] cannot be accepted
-// (search_kernels.hip, poshist_kernel).  MinHashSearch.java:229 accepts score >= acceptScore.
+// (join_kernels.hip, poshist_kernel).  MinHashSearch.java:229 accepts score >= acceptScore.
 void build_pass_min(const std::vector<double>& tbl, int S, double threshold, std::vector<int32_t>& pm) {
   pm.assign((size_t)S + 2, INT32_MAX);
   for (int kk = S; kk >= 0; kk--) {
@@ -997,10 +996,10 @@ int search_core(mhap_handle* h, QuerySide& qs, const std::vector<int32_t>& ql_in
     // second stage: one wavefront per candidate from the equal-hash join (MHAP_OVERLAP=lane: the literal per-lane merge for
     // every pair); pairs the join cannot decide exactly come back in slow_cand and take the per-lane merge
     if (h->gate && h->gate(h->gate_user) != 0) return leave(fail(h, MHAP_E_STATE, "second-stage gate aborted the search"));
-    // the join kernel's three shapes (search_kernels.hip): every wave alone, pairs of waves or teams of four sharing a staged query and
+    // the join kernel's three shapes (join_kernels.hip): every wave alone, pairs of waves or teams of four sharing a staged query and
     // its filter — by the candidates per query.  MHAP_JOIN_MODE=alone|pair|team pins one.
     bool fits[3];
-    for (int i = 0; i < 3; i++) fits[i] = overlap_join_lds_bytes(S, i) <= 64 * 1024;
+    for (int i = 0; i < 3; i++) fits[i] = overlap_join_lds_bytes(S, i, 0) <= 64 * 1024;
     const bool use_join = !lane_only && S <= OJ_MAX_S && (fits[0] || fits[1] || fits[2]);
     unsigned long long nslow = use_join ? 0 : ncand;
     const Candidate* slow_list = nullptr; unsigned long long* slow_count_ptr = nullptr;   // (set when the wide second pass ran)
@@ -1014,18 +1013,29 @@ int search_core(mhap_handle* h, QuerySide& qs, const std::vector<int32_t>& ql_in
       int shape = (int64_t)ncand >= 4LL * nq ? 2 : ((int64_t)ncand >= 2LL * nq ? 1 : 0);
       if (h->join_mode > 0) shape = h->join_mode - 1;
       while (!fits[shape]) shape = (shape + 1) % 3;
-      if (h->oj_per_cu_S != S) {
-        for (int i = 0; i < 3; i++) h->oj_per_cu[i] = fits[i] ? overlap_join_blocks_per_cu(S, i) : 0;
-        h->oj_per_cu_S = S;
-      }
-      // candidates per pull of a wave: 8 amortise the counter and keep a query's hashes staged across its candidates — unless the
-      // candidates are few (a small batch of -q reads, one rank's share of a small job): then every resident wave should get some
-      const int per_cu = h->oj_per_cu[shape], wpb = overlap_join_waves_per_block(shape);
-      const int64_t resident_waves = (int64_t)h->num_cus * per_cu * wpb;
-      const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(8, (int64_t)ncand / std::max<int64_t>(resident_waves, 1)));
-      const int64_t want = ((int64_t)ncand + (int64_t)wpb * chunk - 1) / ((int64_t)wpb * chunk);
-      const int jblocks = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)h->num_cus * per_cu, want));
-      // Early "below the threshold" from position histograms (search_kernels.hip, poshist_kernel): pays when the joined k-mers of a pair
+      // One pass of the join kernel per level: level 0 reads the candidates, every further one what the pass before handed over.
+      // {pairs in, pairs handed over, and where among the counters: pairs in, pairs handed over (the kernel counts those handed over for
+      // the duplicated-hash group caps OJ_GROUP_BAD words behind that), the work counter}
+      struct JoinLevel { DevBuf *in, *out; int in_count, out_count, work; };
+      const JoinLevel levels[OJ_LEVELS] = {{&h->cand, &h->slow_cand, 0, 5, 7}, {&h->slow_cand, &h->slow_cand2, 5, 10, 9}, {&h->slow_cand2, &h->slow_cand3, 10, 11, 12}};
+      // a pass's launch.  Candidates per pull of a wave: 8 amortise the counter and keep a query's hashes staged across its candidates —
+      // unless the pairs are few (a small batch of -q reads, one rank's share of a small job): then every resident wave should get some
+      // (fills the handle's cache of resident workgroups per CU on the first call for a level and shape, and empties it when S changes)
+      struct JoinGrid { int chunk, blocks; };
+      auto join_grid = [&](int level, int shp, unsigned long long npairs) {
+        if (h->oj_per_cu_S != S) { memset(h->oj_per_cu, 0, sizeof h->oj_per_cu); h->oj_per_cu_S = S; }
+        int& per_cu = h->oj_per_cu[level][shp];
+        if (per_cu == 0) per_cu = overlap_join_blocks_per_cu(S, shp, level);
+        const int wpb = overlap_join_waves_per_block(shp);
+        const int64_t resident_waves = (int64_t)h->num_cus * per_cu * wpb;
+        JoinGrid g;
+        g.chunk = (int)std::max<int64_t>(1, std::min<int64_t>(8, (int64_t)npairs / std::max<int64_t>(resident_waves, 1)));
+        const int64_t want = ((int64_t)npairs + (int64_t)wpb * g.chunk - 1) / ((int64_t)wpb * g.chunk);
+        g.blocks = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)h->num_cus * per_cu, want));
+        return g;
+      };
+      const JoinGrid jg = join_grid(0, shape, ncand);
+      // Early "below the threshold" from position histograms (join_kernels.hip, poshist_kernel): pays when the joined k-mers of a pair
       // are few next to its windows — repeat-induced candidates, i.e. many candidates per query (sixteen and more); at C2 (40
       // joined k-mers per pair) it rejects nothing and the histograms would cost a pass over the ordered table.  MHAP_OVERLAP_PRUNE=0|1.
       const char* pe = getenv("MHAP_OVERLAP_PRUNE");
@@ -1052,48 +1062,34 @@ int search_core(mhap_handle* h, QuerySide& qs, const std::vector<int32_t>& ql_in
         SCHK(hipGetLastError());
       }
       time_begin(h, MHAP_K_OVERLAP);
-      launch_overlap_join(h->stream, shape, jblocks, chunk, h->cand.as<Candidate>(), ctr + 0, (unsigned long long)cand_cap, h->d_ordered, 2LL * S, h->d_meta,
+      launch_overlap_join(h->stream, 0, shape, jg.blocks, jg.chunk, h->cand.as<Candidate>(), ctr + levels[0].in_count, (unsigned long long)cand_cap, h->d_ordered, 2LL * S, h->d_meta,
                           qs.d_ordered, qs.ord_stride, qs.d_meta, sp, h->score_tbl.as<double>(), recbuf.as<DevRecord>(), ctr + 1,
-                          (unsigned long long)ncand, ctr + 2, h->slow_cand.as<Candidate>(), ctr + 5, ctr + 7, ph, qph, h->pass_min_tbl.as<int32_t>());
+                          (unsigned long long)ncand, ctr + 2, h->slow_cand.as<Candidate>(), ctr + levels[0].out_count, ctr + levels[0].work, ph, qph, h->pass_min_tbl.as<int32_t>());
       time_end(h);
       SCHK(hipGetLastError());
       // (one read-back for the pairs handed over and for the counts the tail needs: nothing else changes them when none were)
       SCHK(hipMemcpyAsync(cj, ctr, 160, hipMemcpyDeviceToHost, h->stream));
       int rcj = sync_stream(h);
       if (rcj != MHAP_OK) return leave(rcj);
-      nslow = cj[5];
+      nslow = cj[levels[0].out_count];
       have_counts = nslow == 0;
       // Further passes: the pairs the join kernel handed over — nearly all of them for MORE THAN 128 JOINED K-MERS, i.e. true overlaps of reads
-      // better than the 15 %-error ones MHAP was built for — go through the same kernel compiled with room for 512, and what that hands
-      // over through the one with room for 1 536 (search_kernels_wide.hip / _wide2.hip), every wave alone; only what is left then (the
+      // better than the 15 %-error ones MHAP was built for — go through the kernel's instantiation with room for 512, and what that hands
+      // over through the one with room for 1 536 (join_kernels.hip, oj_dispatch), every wave alone; only what is left then (the
       // duplicated-hash group caps) takes the per-lane merge.  MHAP_JOIN_WIDE=0 switches the passes off, =1 keeps the first of them only.
-      unsigned long long group_bad = cj[13];   // of the pairs handed over: for the duplicated-hash group caps (ctr + 13 = the first pass's slow_count + 8)
-      for (int level = 0; level < h->join_wide && nslow > 0; level++) {
+      unsigned long long group_bad = cj[levels[0].out_count + OJ_GROUP_BAD];   // of the pairs handed over: for the duplicated-hash group caps
+      for (int level = 1; level <= h->join_wide && nslow > 0; level++) {
         // (pairs handed over for their duplicated-hash groups — repeat-rich reads of low error without a -f filter: hundreds of millions of
         //  them — would be handed on by a wider pass too: 1.4 s of 9.6 wasted on 20 000 such reads)
         if (group_bad * 10 > nslow * 9) break;
-        const size_t wl = level == 0 ? overlap_join_wide_lds_bytes(S, 0) : overlap_join_wide2_lds_bytes(S, 0);
-        if (wl > 64 * 1024) break;
-        DevBuf& in = level == 0 ? h->slow_cand : h->slow_cand2;
-        DevBuf& outb = level == 0 ? h->slow_cand2 : h->slow_cand3;
-        unsigned long long* in_count = level == 0 ? ctr + 5 : ctr + 10;
-        unsigned long long* out_count = level == 0 ? ctr + 10 : ctr + 11;
-        unsigned long long* work = level == 0 ? ctr + 9 : ctr + 12;
-        SCHK(outb.ensure((size_t)nslow * sizeof(Candidate)));
-        if (h->ojw_per_cu_S[level] != S) {
-          h->ojw_per_cu[level] = level == 0 ? overlap_join_wide_blocks_per_cu(S, 0) : overlap_join_wide2_blocks_per_cu(S, 0);
-          h->ojw_per_cu_S[level] = S;
-        }
-        const int wpbw = level == 0 ? overlap_join_wide_waves_per_block(0) : overlap_join_wide2_waves_per_block(0);
-        const int64_t residentw = (int64_t)h->num_cus * h->ojw_per_cu[level] * wpbw;
-        const int chunkw = (int)std::max<int64_t>(1, std::min<int64_t>(8, (int64_t)nslow / std::max<int64_t>(residentw, 1)));
-        const int64_t wantw = ((int64_t)nslow + (int64_t)wpbw * chunkw - 1) / ((int64_t)wpbw * chunkw);
-        const int wblocks = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)h->num_cus * h->ojw_per_cu[level], wantw));
+        if (overlap_join_lds_bytes(S, 0, level) > 64 * 1024) break;
+        const JoinLevel& lv = levels[level];
+        SCHK(lv.out->ensure((size_t)nslow * sizeof(Candidate)));
+        const JoinGrid wg = join_grid(level, 0, nslow);
         time_begin(h, MHAP_K_OVERLAP);
-        (level == 0 ? launch_overlap_join_wide : launch_overlap_join_wide2)(
-            h->stream, 0, wblocks, chunkw, in.as<Candidate>(), in_count, (unsigned long long)ncand, h->d_ordered, 2LL * S, h->d_meta, qs.d_ordered, qs.ord_stride,
-            qs.d_meta, &sp, h->score_tbl.as<double>(), recbuf.as<DevRecord>(), ctr + 1, (unsigned long long)ncand, ctr + 2, outb.as<Candidate>(), out_count, work,
-            nullptr, nullptr, h->pass_min_tbl.as<int32_t>());
+        launch_overlap_join(h->stream, level, 0, wg.blocks, wg.chunk, lv.in->as<Candidate>(), ctr + lv.in_count, (unsigned long long)ncand, h->d_ordered, 2LL * S, h->d_meta,
+                            qs.d_ordered, qs.ord_stride, qs.d_meta, sp, h->score_tbl.as<double>(), recbuf.as<DevRecord>(), ctr + 1, (unsigned long long)ncand, ctr + 2,
+                            lv.out->as<Candidate>(), ctr + lv.out_count, ctr + lv.work, nullptr, nullptr, h->pass_min_tbl.as<int32_t>());
         time_end(h);
         SCHK(hipGetLastError());
         unsigned long long cw[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -1102,9 +1098,9 @@ int search_core(mhap_handle* h, QuerySide& qs, const std::vector<int32_t>& ql_in
         if (rcw != MHAP_OK) return leave(rcw);
         for (int i = 0; i < 8; i++) cj[i] = cw[i];
         const unsigned long long before = nslow;
-        nslow = level == 0 ? cw[10] : cw[11];
-        group_bad = level == 0 ? cw[18] : cw[19];
-        slow_list = outb.as<Candidate>(); slow_count_ptr = out_count;
+        nslow = cw[lv.out_count];
+        group_bad = cw[lv.out_count + OJ_GROUP_BAD];
+        slow_list = lv.out->as<Candidate>(); slow_count_ptr = ctr + lv.out_count;
         have_counts = nslow == 0;
         if (nslow * 10 > before * 9) break;   // (handed over for the duplicated-hash group caps, not for their number of k-mers: a wider pass would hand them on again)
       }
@@ -1113,7 +1109,7 @@ int search_core(mhap_handle* h, QuerySide& qs, const std::vector<int32_t>& ql_in
     if (nslow > 0) {
       // (few pairs — what the join kernel hands over — are spread over more wavefronts while there is at most one per SIMD: 600 pairs of a
       //  c5rank chunk, one per wave, 9 -> 3.5 ms; the 76 000 of the C5 slice at sixteen per wave instead of 64: 3 ms SLOWER — four times
-      //  the instructions on a machine that is then full: search_kernels.hip, overlap_kernel)
+      //  the instructions on a machine that is then full: join_kernels.hip, overlap_kernel)
       int spread = 1;
       while (spread < 64 && (int64_t)nslow * spread * 2 <= (int64_t)h->num_cus * 4 * 64) spread *= 2;
       const int oblocks = (int)std::max<int64_t>(1, std::min<int64_t>(ovl_max_blocks, ((int64_t)nslow * spread + OVL_THREADS - 1) / OVL_THREADS));
@@ -1490,7 +1486,7 @@ int mhap_sketch_batch(mhap_handle* h, const char* bases, const int64_t* offsets,
 }
 
 // Sketches that did not come from this library's kernels (a `.dat` file, a caller's arrays): the second stage ranks and medians positions
-// by their bits and keeps no per-entry window test in its first pass (search_kernels.hip: FIRST => ok), which is only the reference's
+// by their bits and keeps no per-entry window test in its first pass (join_kernels.hip: FIRST => ok), which is only the reference's
 // arithmetic for 0 <= pos < seqLength (J/sketch/BottomOverlapSketch.java:246-276: valid1Upper = seqLength; :548-558 writes pos = an
 // index into the hash array).  A position outside that range is therefore refused here instead of being silently mis-ranked.
 static bool ordered_positions_ok(const int32_t* ordered, const int32_t* ordered_size, const int32_t* ordered_seqlen, int64_t m, int S, int64_t* bad_entry) {

@@ -30,7 +30,7 @@ struct ShiftStats { int32_t med, absmax; };
 
 // Read-only view of one ordered sketch: entry i = (hash, pos).  The algorithms below only ever move FORWARD through a
 // view between two reset() calls, which lets the device view keep one 64-byte line per lane in LDS and prefetch the
-// next line in registers (search_kernels.hip: CachedView).
+// next line in registers (join_kernels.hip: CachedView).
 struct PlainView {
   const int32_t* p;
   int n;

@@ -1448,7 +1448,7 @@ def test_self_overlap_at_large_num_hashes(H):
 def test_low_error_reads_take_the_wide_join_passes(err, monkeypatch):
     """Reads better than the 15 %-error ones MHAP was built for: two overlapping reads then join hundreds of their bottom 12-mers (all of
     them at error 0), more than the 128 the join kernel keeps per pair.  Such pairs go through the same kernel compiled with room for 512
-    and 1 536 (search_kernels_wide.hip / _wide2.hip) instead of the per-lane merge; records against the oracle
+    and 1 536 (join_kernels.hip: overlap_join_kernel<512 / 1536, ...>) instead of the per-lane merge; records against the oracle
     (J/sketch/BottomOverlapSketch.java:592-630), with the passes on (default), with one, and off — and nearly no pair is left for the lane kernel."""
     fa = mhap_amd.synth_reads(260, 5000, seed=900 + int(err * 100), error_rate=err)
     p = MhapParams()

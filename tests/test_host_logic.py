@@ -523,3 +523,16 @@ def test_second_stage_lane_on_error_free_overlaps_takes_the_bounded_selection():
         for key in ("a1", "a2", "b1", "b2", "inter", "k"):
             assert got[key] == want[key], (off, key)
         assert float(got["raw"]) == want["raw"] and want["raw"] > 100
+
+
+def test_build_lists_name_real_files_and_no_unit_includes_another():
+    """Every name in mhap_amd.build.SOURCES and HEADERS exists, and no translation unit of SOURCES includes a .hip file.  An object's
+    digest covers its own source and HEADERS only (build._digest), so that is the invariant under which a changed file rebuilds every
+    object made from it and a variant's -D flags reach every kernel of the unit they name — no list of extra dependencies is kept."""
+    from mhap_amd import build as B
+    assert len(set(B.SOURCES)) == len(B.SOURCES)
+    for name in B.SOURCES + B.HEADERS:
+        assert os.path.isfile(os.path.join(B.CSRC, name)), name
+    for name in B.SOURCES:
+        text = open(os.path.join(B.CSRC, name), encoding="utf-8").read()
+        assert not re.search(r'^[ \t]*#[ \t]*include[ \t]*["<][^">]*\.hip[">]', text, re.M), name

@@ -1,4 +1,4 @@
-"""The second stage (overlap_join_kernel, its two wider builds, the per-lane kernel) pair by pair on crafted sketches: every pair is
+"""The second stage (join_kernels.hip: overlap_join_kernel, its two wider instantiations, the per-lane kernel) pair by pair on crafted sketches: every pair is
 built to sit on one branch — a cap of the join, a sketch size, a hash value, a launch shape — and its record is compared with the
 oracle's literal getOverlapInfo (tests/sketch_search_ref.py, pinned to orc_run_self by tests/test_sketch_search_ref.py).
 
