@@ -95,7 +95,7 @@ typedef struct mhap_kernel_times {
 /* Interface version of this header (bumped whenever a struct layout or a signature changes) and the sizes of its structs as the
  * library was compiled: a binding built against another header — a stale libmhaphip.so shipped next to newer host code — finds
  * out at load time instead of overrunning a buffer. */
-#define MHAP_ABI_VERSION 3
+#define MHAP_ABI_VERSION 4
 int mhap_abi_version(void);
 int mhap_abi_sizes(int32_t* out4);   /* {sizeof mhap_params, mhap_record, mhap_stats, mhap_kernel_times} */
 
@@ -436,6 +436,54 @@ const char* mhap_realign_plan_error(void);
 int mhap_realign_records(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const int64_t* read_ids, const int64_t* offsets,
                          const int32_t* lengths, int64_t n_reads, const mhap_record* recs, int64_t n, int32_t band,
                          mhap_record* out, int32_t* detail /* n x 3: score, columns, errors; may be NULL */);
+
+/* ---- the realignment stage's paths: each alignment column by column, and PAF ---------------- */
+
+/* The path of a banded alignment is the one whose begin cell, columns and errors mhap_align_pairs_banded reports; no rule is added.  It
+ * is read off the recurrences above, starting at the reported end cell in state H:
+ *   in H at (i, j): H = 0 stops.  With D = H(i-1, j-1) + sub: the diagonal when D > 0, D >= E(i,j) and D >= F(i,j); otherwise state E
+ *     when E(i,j) > 0 and E(i,j) >= F(i,j); otherwise state F;
+ *   in E at (i, j): the column consumes s2 only; the predecessor is E at (i, j-1) when E(i,j-1) - 1 >= H(i,j-1) - 2, else H at (i, j-1);
+ *   in F at (i, j): the column consumes s1 only; the predecessor is F at (i-1, j) when F(i-1,j) - 1 >= H(i-1,j) - 2, else H at (i-1, j);
+ *   a cell outside the band has H = 0 and E = F = -infinity, so a path never enters it.
+ * A path is a list of uint32 runs, len << 4 | code, in order from the begin cell to the end cell, with BAM's codes: 7 '=' a diagonal
+ * column on equal bytes, 8 'X' a diagonal column on different bytes, 1 'I' an F column (consumes s1 only), 2 'D' an E column (consumes
+ * s2 only).  len >= 1 and adjacent runs have different codes, except that a run longer than 2^28 - 1 is split into several runs of
+ * its code.  s2 is the reverse complement of the stored segment when b_rc, and the path is in that orientation.  A pair without an
+ * alignment has no runs.  It follows that the lengths of '=', 'X', 'I' sum to read_end - read_begin + 1, those of '=', 'X', 'D' to
+ * ref_end - ref_begin + 1, all of them to `columns`, those of 'X', 'I', 'D' to `errors`, that the first and the last run are '=', and
+ * that +2 per '=' column, -2 per 'X' column and -(2 + (L - 1)) per gap of L columns sum to `score`.
+ *
+ * mhap_align_pairs_banded_paths: mhap_align_pairs_banded (same arguments, same errors, byte-identical results) and the paths of all
+ * pairs in a library-owned object: *out on success, NULL on any error.  The direction of every cell the path can have visited is kept
+ * on the device, 4 bits per cell, for a group of pairs at a time: at most 2 GiB of them, or MHAP_REALIGN_TRACE_BYTES bytes (the
+ * environment, read at each call); a pair that needs more goes alone, and when that cannot be allocated the call fails with
+ * MHAP_E_HIP, the pair's index in the message, and returns nothing. */
+typedef struct mhap_align_paths mhap_align_paths;
+int mhap_align_pairs_banded_paths(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const int64_t* pairs /* n x 7 */, int64_t n,
+                                  int32_t* results /* n x 7 */, mhap_align_paths** out);
+/* mhap_realign_records (same arguments, same errors, byte-identical out and detail) and the path of every record's planned pair:
+ * record q's runs are those of the pair mhap_realign_plan gives it, so on a to_rc record they run along the reverse complement of
+ * the `to` read.  A record without an alignment has no runs. */
+int mhap_realign_records_paths(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const int64_t* read_ids, const int64_t* offsets,
+                               const int32_t* lengths, int64_t n_reads, const mhap_record* recs, int64_t n, int32_t band,
+                               mhap_record* out, int32_t* detail /* may be NULL */, mhap_align_paths** paths);
+/* n = the pairs (records) of the call, n_ops = all their runs; either pointer may be NULL */
+int mhap_align_paths_info(const mhap_align_paths* p, int64_t* n, int64_t* n_ops);
+/* pair q's runs are ops[op_offsets[q] .. op_offsets[q + 1]) */
+int mhap_align_paths_copy(const mhap_align_paths* p, int64_t* op_offsets /* n + 1 */, uint32_t* ops /* n_ops */);
+void mhap_align_paths_free(mhap_align_paths* p);
+
+/* One PAF line of a realigned record (no GPU), tab-separated, no newline:
+ *   qname qlen qstart qend strand tname tlen tstart tend nmatch alnlen 255 NM:i:<errors> AS:i:<score> cg:Z:<cigar>
+ * qlen = alen, qstart = a1, qend = a2 + 1, tlen = blen, tstart = b1, tend = b2 + 1 (b1, b2 of the realigned record are on the `to`
+ * read's own strand), strand '-' when to_rc, nmatch = columns - errors, alnlen = columns; detail3 = the record's {score, columns,
+ * errors}.  cg:Z writes the runs with the letters = X I D: in path order on '+', in reverse order on '-' (PAF's CIGAR runs along the
+ * target's forward strand with the query reverse-complemented, and no operation changes when both sequences are reverse-complemented).
+ * snprintf semantics: returns the line's length; when cap is too small the line is truncated (NUL-terminated when cap > 0) and the
+ * length needed is returned.  -1 for a null record, detail or name, or ops missing with n_ops > 0. */
+int mhap_format_paf(const mhap_record* realigned, const int32_t* detail3, const uint32_t* ops, int64_t n_ops, const char* qname,
+                    const char* tname, char* out, size_t cap);
 
 /* KmerStatSimulator's pair statistics on the GPU (J/main/KmerStatSimulator.java:163-196).  pairs: n rows of 4 int64 {a_off, a_len,
  * b_off, b_len}; a = bases[a_off, a_off + a_len) is the first read, b the second.  skip: n_skip k-mers of k bytes each, back to back, in

@@ -24,6 +24,10 @@ from .api import (  # noqa: F401
     align_pairs_banded,
     realign_plan,
     realign_records,
+    align_pairs_banded_paths,
+    realign_records_paths,
+    cigar_string,
+    format_paf,
     pair_kmer_stats,
     records_to_lines,
     load_library,

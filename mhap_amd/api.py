@@ -72,11 +72,13 @@ EXPORTED_SYMBOLS = [
     "mhap_histogram_stats",
     "mhap_synth_truth", "mhap_align_pairs",
     "mhap_align_pairs_banded", "mhap_realign_plan", "mhap_realign_plan_error", "mhap_realign_records",
+    "mhap_align_pairs_banded_paths", "mhap_realign_records_paths", "mhap_align_paths_info", "mhap_align_paths_copy", "mhap_align_paths_free",
+    "mhap_format_paf",
     "mhap_pair_kmer_stats", "mhap_pair_kmer_stats_paths", "mhap_ksim_create", "mhap_ksim_next", "mhap_ksim_error", "mhap_ksim_destroy",
     "mhap_ksim_dev_create", "mhap_ksim_dev_destroy", "mhap_ksim_dev_pair_stats", "mhap_ksim_dev_trials",
 ]
 MHAP_KMER_HISTOGRAM = 1   # mhap_kmer_count_finish_flags
-ABI_VERSION = 3   # MHAP_ABI_VERSION of include/mhap_hip.h this binding was written against
+ABI_VERSION = 4   # MHAP_ABI_VERSION of include/mhap_hip.h this binding was written against
 
 
 def load_library(build_if_missing=True):
@@ -147,6 +149,13 @@ def load_library(build_if_missing=True):
     lib.mhap_realign_plan.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int32, C.c_void_p]
     lib.mhap_realign_records.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                          C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.mhap_align_pairs_banded_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.mhap_realign_records_paths.argtypes = lib.mhap_realign_records.argtypes + [C.c_void_p]
+    lib.mhap_align_paths_info.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mhap_align_paths_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mhap_align_paths_free.restype = None
+    lib.mhap_align_paths_free.argtypes = [C.c_void_p]
+    lib.mhap_format_paf.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t]
     for name in EXPORTED_SYMBOLS:
         getattr(lib, name)  # AttributeError here = header/library mismatch
     # a stale library next to newer host code (or the reverse) must not get as far as a struct copy
@@ -405,6 +414,100 @@ def realign_records(records, fasta, band=0, max_shift=0.2, device=0, handle=None
         if own:
             ms.close()
     return out, detail
+
+
+def _take_paths(lib, obj):
+    """(op_offsets, ops) of a mhap_align_paths object, which is freed."""
+    try:
+        n, n_ops = C.c_int64(0), C.c_int64(0)
+        lib.mhap_align_paths_info(obj, C.byref(n), C.byref(n_ops))
+        op_offsets = np.zeros(n.value + 1, np.int64)
+        ops = np.zeros(n_ops.value, np.uint32)
+        if lib.mhap_align_paths_copy(obj, _ptr(op_offsets), _ptr(ops) if n_ops.value else None) != 0:
+            raise MhapError("mhap_align_paths_copy failed")
+        return op_offsets, ops
+    finally:
+        lib.mhap_align_paths_free(obj)
+
+
+def align_pairs_banded_paths(bases, pairs7, handle=None, device=0):
+    """align_pairs_banded and every alignment's path (mhap_align_pairs_banded_paths; the path contract is in its header comment).
+    Returns (results, op_offsets, ops): results as align_pairs_banded returns them; pair q's runs are the uint32 values
+    ops[op_offsets[q]:op_offsets[q + 1]], each len << 4 | code with code 7 '=', 8 'X', 1 'I', 2 'D', from the begin cell to the end
+    cell (cigar_string writes them out)."""
+    bases = np.ascontiguousarray(bases, dtype=np.uint8)
+    pairs7 = np.ascontiguousarray(np.asarray(pairs7, dtype=np.int64).reshape(-1, 7))
+    out = np.zeros((len(pairs7), 7), dtype=np.int32)
+    if len(pairs7) == 0:
+        return out, np.zeros(1, np.int64), np.zeros(0, np.uint32)
+    own = handle is None
+    ms = MinHashSearch(MhapParams(num_hashes=1, ordered_sketch_size=1, device=device)) if own else handle
+    try:
+        obj = C.c_void_p()
+        ms._chk(ms._lib.mhap_align_pairs_banded_paths(ms._h, _ptr(bases), C.c_int64(len(bases)), _ptr(pairs7), C.c_int64(len(pairs7)),
+                                                      _ptr(out), C.byref(obj)))
+        op_offsets, ops = _take_paths(ms._lib, obj)
+    finally:
+        if own:
+            ms.close()
+    return out, op_offsets, ops
+
+
+def realign_records_paths(records, fasta, band=0, max_shift=0.2, handle=None, device=0, query_fasta=None):
+    """realign_records and every alignment's path (mhap_realign_records_paths).  Returns (records, detail, op_offsets, ops): the first
+    two as realign_records returns them, the runs as align_pairs_banded_paths returns them for the pairs of realign_plan — on a
+    to_rc record they run along the reverse complement of the `to` read (format_paf turns them round)."""
+    records = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
+    out = np.zeros(len(records), dtype=RECORD_DTYPE)
+    detail = np.zeros((len(records), 3), dtype=np.int32)
+    if len(records) == 0:
+        return out, detail, np.zeros(1, np.int64), np.zeros(0, np.uint32)
+    bases, ids, offsets, lengths = _all_reads(fasta, query_fasta)
+    bases = np.ascontiguousarray(bases, np.uint8)
+    ids, offsets = np.ascontiguousarray(ids, np.int64), np.ascontiguousarray(offsets, np.int64)
+    lengths = np.ascontiguousarray(lengths, np.int32)
+    own = handle is None
+    ms = MinHashSearch(MhapParams(num_hashes=1, ordered_sketch_size=1, max_shift=max_shift, device=device)) if own else handle
+    try:
+        obj = C.c_void_p()
+        ms._chk(ms._lib.mhap_realign_records_paths(ms._h, _ptr(bases), C.c_int64(len(bases)), _ptr(ids), _ptr(offsets), _ptr(lengths),
+                                                   C.c_int64(len(ids)), _ptr(records), C.c_int64(len(records)), C.c_int32(band),
+                                                   _ptr(out), _ptr(detail), C.byref(obj)))
+        op_offsets, ops = _take_paths(ms._lib, obj)
+    finally:
+        if own:
+            ms.close()
+    return out, detail, op_offsets, ops
+
+
+_CIGAR_LETTERS = "MIDNSHP=X???????"   # BAM's codes; the aligner writes 7, 8, 1 and 2
+
+
+def cigar_string(ops, reverse=False):
+    """The runs of one path (uint32, len << 4 | code) as a CIGAR with = X I D; reverse=True: in reverse order, which is the CIGAR of
+    the same alignment with both sequences reverse-complemented."""
+    ops = [int(x) for x in np.asarray(ops, dtype=np.uint32).reshape(-1).tolist()]
+    return "".join(f"{op >> 4}{_CIGAR_LETTERS[op & 15]}" for op in (reversed(ops) if reverse else ops))
+
+
+def format_paf(record, detail, ops, qname=None, tname=None):
+    """One PAF line of a realigned record (mhap_format_paf): record and detail as realign_records_paths returns them, ops the
+    record's runs.  The names default to the two ids, which is what columns 1 and 2 of the 12-column line hold."""
+    lib = load_library()
+    arr = np.zeros(1, dtype=RECORD_DTYPE)
+    for k in RECORD_DTYPE.names:
+        if k != "pad":
+            arr[0][k] = record[k] if not isinstance(record, MatchResult) else getattr(record, k)
+    detail = np.ascontiguousarray(detail, dtype=np.int32).reshape(3)
+    ops = np.ascontiguousarray(ops, dtype=np.uint32).reshape(-1)
+    qname = str(int(arr[0]["from_id"]) if qname is None else qname).encode()
+    tname = str(int(arr[0]["to_id"]) if tname is None else tname).encode()
+    cap = 256 + len(qname) + len(tname) + 12 * len(ops)
+    buf = C.create_string_buffer(cap)
+    n = lib.mhap_format_paf(_ptr(arr), _ptr(detail), _ptr(ops) if len(ops) else None, C.c_int64(len(ops)), qname, tname, buf, C.c_size_t(cap))
+    if n < 0 or n >= cap:
+        raise MhapError("mhap_format_paf failed")
+    return buf.value.decode()
 
 
 def _skip_bytes(skip, k):

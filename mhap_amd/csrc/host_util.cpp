@@ -137,6 +137,26 @@ int mhap_format_record(const mhap_record* r, char* out, size_t cap) {
   return (int)len;
 }
 
+int mhap_format_paf(const mhap_record* r, const int32_t* d, const uint32_t* ops, int64_t n_ops, const char* qname, const char* tname,
+                    char* out, size_t cap) {
+  if (!r || !d || !qname || !tname || n_ops < 0 || (n_ops > 0 && !ops)) return -1;
+  std::string s;
+  s.reserve(160 + strlen(qname) + strlen(tname) + (size_t)n_ops * 5);
+  auto put = [&s](long long v) { s += std::to_string(v); };
+  s += qname; s += '\t'; put(r->alen); s += '\t'; put(r->a1); s += '\t'; put((long long)r->a2 + 1); s += '\t';
+  s += r->to_rc ? '-' : '+'; s += '\t';
+  s += tname; s += '\t'; put(r->blen); s += '\t'; put(r->b1); s += '\t'; put((long long)r->b2 + 1); s += '\t';
+  put((long long)d[1] - d[2]); s += '\t'; put(d[1]); s += "\t255\tNM:i:"; put(d[2]); s += "\tAS:i:"; put(d[0]); s += "\tcg:Z:";
+  static const char letters[16] = {'M', 'I', 'D', 'N', 'S', 'H', 'P', '=', 'X', '?', '?', '?', '?', '?', '?', '?'};   // BAM's codes
+  for (int64_t k = 0; k < n_ops; k++) {
+    const uint32_t op = ops[r->to_rc ? n_ops - 1 - k : k];
+    put((long long)(op >> 4)); s += letters[op & 15u];
+  }
+  if (s.size() > (size_t)INT32_MAX) return -1;
+  if (out && cap) { const size_t c = std::min(s.size(), cap - 1); memcpy(out, s.data(), c); out[c] = 0; }
+  return (int)s.size();
+}
+
 // FastaData.enqueueNextSequenceInFile (J/impl/FastaData.java:125-204).  Deviation (documented in DESIGN.md):
 // an empty record is skipped instead of stopping a worker thread (reference behaviour is thread-count dependent).
 int mhap_fasta_read(const char* path, int64_t id_offset, mhap_fasta* out, char* err, size_t errcap) {

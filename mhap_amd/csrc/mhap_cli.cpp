@@ -157,6 +157,8 @@ struct Realign {
   int32_t band = 0; double min_identity = 0.0;
   std::vector<uint8_t> bases; std::vector<int64_t> ids, offsets; std::vector<int32_t> lengths;
   std::vector<mhap_record> out;
+  bool paf = false;                                   // --realign-paf: the alignments' paths too, printed as PAF lines
+  std::vector<int32_t> detail; std::vector<int64_t> op_offsets, row; std::vector<uint32_t> ops;   // row[k]: the batch row of kept record k
   int64_t dropped = 0, kept = 0;
   double seconds = 0.0;
   void add(const mhap_fasta& fa) {
@@ -172,19 +174,52 @@ int sink_cb(const mhap_record* r, int64_t n, void* user) {
     Realign& R = *s->realign;
     const double t = now();
     R.out.resize((size_t)n);
-    const int rc = mhap_realign_records(R.h, R.bases.data(), (int64_t)R.bases.size(), R.ids.data(), R.offsets.data(), R.lengths.data(),
-                                        (int64_t)R.ids.size(), r, n, R.band, R.out.data(), nullptr);
+    int rc;
+    if (R.paf) {
+      R.detail.resize((size_t)n * 3);
+      mhap_align_paths* paths = nullptr;
+      rc = mhap_realign_records_paths(R.h, R.bases.data(), (int64_t)R.bases.size(), R.ids.data(), R.offsets.data(), R.lengths.data(),
+                                      (int64_t)R.ids.size(), r, n, R.band, R.out.data(), R.detail.data(), &paths);
+      if (rc == MHAP_OK) {
+        int64_t n_ops = 0;
+        mhap_align_paths_info(paths, nullptr, &n_ops);
+        R.op_offsets.resize((size_t)n + 1); R.ops.resize((size_t)std::max<int64_t>(n_ops, 1));
+        mhap_align_paths_copy(paths, R.op_offsets.data(), R.ops.data());
+        mhap_align_paths_free(paths);
+      }
+    } else {
+      rc = mhap_realign_records(R.h, R.bases.data(), (int64_t)R.bases.size(), R.ids.data(), R.offsets.data(), R.lengths.data(),
+                                (int64_t)R.ids.size(), r, n, R.band, R.out.data(), nullptr);
+    }
     if (rc != MHAP_OK) { fprintf(stderr, "Exception in mhap-hip: %s (code %d)\n", mhap_last_error(R.h), rc); return 1; }
     int64_t k = 0;
+    R.row.resize((size_t)n);
     for (int64_t i = 0; i < n; i++) {
       const mhap_record& o = R.out[(size_t)i];
       const bool none = o.score == 0.0 && o.a1 == 0 && o.a2 == 0 && o.b1 == 0 && o.b2 == 0;
       if (none || o.score < R.min_identity) continue;
+      R.row[(size_t)k] = i;
       R.out[(size_t)k++] = o;
     }
     R.dropped += n - k; R.kept += k;
     R.seconds += now() - t;
     r = R.out.data(); n = k;
+  }
+  if (s->realign && s->realign->paf) {   // one PAF line per kept record; the names are columns 1 and 2 of the 12-column line
+    const Realign& R = *s->realign;
+    std::string pl;
+    for (int64_t i = 0; i < n; i++) {
+      const int64_t q = R.row[(size_t)i], o0 = R.op_offsets[(size_t)q], o1 = R.op_offsets[(size_t)q + 1];
+      const std::string qn = header_of(r[i].from_id), tn = header_of(r[i].to_id);
+      pl.resize(256 + qn.size() + tn.size() + 12 * (size_t)(o1 - o0));
+      const int len = mhap_format_paf(&r[i], R.detail.data() + 3 * q, R.ops.data() + o0, o1 - o0, qn.c_str(), tn.c_str(), &pl[0], pl.size());
+      if (len < 0 || (size_t)len >= pl.size()) { fprintf(stderr, "Exception in mhap-hip: mhap_format_paf failed\n"); return 1; }
+      s->buf.append(pl.data(), (size_t)len);
+      s->buf.push_back('\n');
+      if (s->buf.size() > (8u << 20)) { fwrite(s->buf.data(), 1, s->buf.size(), s->out); s->buf.clear(); }
+    }
+    s->n += n;
+    return 0;
   }
   for (int64_t i = 0; i < n; i++) {
     if (!g_headers.full) { int len = mhap_format_record(&r[i], line, sizeof line); s->buf.append(line, (size_t)len); }
@@ -341,6 +376,7 @@ int main(int argc, char** argv) {
   o.add("--realign", "Realign every overlap on the GPU before it is printed: a banded local alignment of the two reads around the diagonal the overlap implies replaces its interval, and column 3 becomes 1 - aligned identity. FASTA input, one GPU.", "false", true);
   o.add("--realign-band", "[int] Half-width of the realignment band in bases. 0) the overlap's length times --max-shift.", "0");
   o.add("--realign-min-identity", "[double] With --realign, drop overlaps whose aligned identity is below this value (overlaps without an alignment are always dropped).", "0.0");
+  o.add("--realign-paf", "With --realign, print one PAF line per overlap instead of the 12 columns: the alignment's interval, its matches and columns, and its path as a cg:Z CIGAR with = X I D.", "false", true);
   if (!o.parse(argc, argv)) return 0;
 
   auto bad = [&](const char* m) { printf("%s\n", m); exit(1); };
@@ -381,6 +417,7 @@ int main(int argc, char** argv) {
   if (devs.empty()) bad("No device given.");
   const bool precompute = !o.s("-p").empty();
   const bool realign = o.b("--realign") && !precompute;
+  if (o.b("--realign-paf") && !o.b("--realign")) bad("--realign-paf prints the alignments of --realign: give --realign too.");
   if (realign) {   // refused before a handle exists
     if (o.i("--realign-band") < 0) bad("The realignment band must be >=0.");
     if (devs.size() > 1) bad("--realign runs on one GPU: give one device (--gpus 1).");
@@ -451,7 +488,7 @@ int main(int argc, char** argv) {
   Sink sink{stdout};
   Realign RA;
   if (realign) {
-    RA.h = E.h; RA.band = o.i("--realign-band"); RA.min_identity = o.d("--realign-min-identity");
+    RA.h = E.h; RA.band = o.i("--realign-band"); RA.min_identity = o.d("--realign-min-identity"); RA.paf = o.b("--realign-paf");
     for (const std::string& sf : list_files(o.s("-s"))) {   // (ids as the index assigned them: FastaData's running count)
       mhap_fasta fa;
       if (mhap_fasta_read(sf.c_str(), (int64_t)RA.ids.size(), &fa, err, sizeof err) != MHAP_OK) die(err);

@@ -1,5 +1,6 @@
-// realign_kernels.hip — the realignment stage: banded local alignment of reported overlaps on the GPU (mhap_align_pairs_banded) and the
-// host code that turns overlap records into banded pairs and back (mhap_realign_plan, mhap_realign_records).
+// realign_kernels.hip — the realignment stage: banded local alignment of reported overlaps on the GPU (mhap_align_pairs_banded), the
+// alignments' paths as run-length CIGAR operations (mhap_align_pairs_banded_paths) and the host code that turns overlap records into
+// banded pairs and back (mhap_realign_plan, mhap_realign_records, mhap_realign_records_paths).
 //
 // The contract is mhap_align_pairs' (include/mhap_hip.h) with one sentence added: a cell (i, j) outside the band |j - i - diag| <= band
 // has H = 0 and E = F = -inf and carries nothing.  tests/align_banded_ref.py restates it on the CPU.
@@ -28,6 +29,23 @@
 // Passes.  Rows beyond one pass's L R go to further passes.  The bottom row of a pass goes to HBM as 10 words per in-band column — W
 // entries, indexed by the column's position in the band — and is the top boundary of the next pass: what crosses between passes is
 // sized by 2 band + 1, not by the length of s2.
+//
+// Paths (mhap_align_pairs_banded_paths, mhap_realign_records_paths).  The kernel above already follows one path per pair — the header
+// fixes the end cell, the predecessor preference and extension over opening — and reports its begin cell, columns and errors.  The path
+// itself comes from two more kernels over the pairs that have an alignment, after the results are on the host:
+//  * where the path lies: rows [read_begin, read_end], columns [ref_begin, ref_end], and, with I = columns - columns of s2 covered
+//    insertions and D = columns - rows covered deletions on it, the I + D + 1 diagonals [-I, D] around its begin cell's (cut to the
+//    pair's band).  Restricting the matrix to that changes no choice on the path: every value on the path is reached through cells on
+//    the path, so it keeps its value, and every other value can only fall — the alternative a choice was preferred over stays
+//    unpreferred in H (diagonal, then E, then F), and in E and F an extension that won still wins, an opening that won strictly still
+//    wins.  The diagonal predecessor of the begin cell is outside the restriction, H = 0 as it was.
+//  * trace_fill_kernel runs the same wavefront schedule over that sub-matrix without the carried fields (69 / 82 VGPRs instead of 184)
+//    and stores 4 bits per cell: H's choice (diagonal on equal bytes, diagonal on different bytes, E, F), "E extended", "F extended".
+//    Word (x, g) holds diagonal x of the 8 rows of row group g, so a lane's strip is one g; the pair's words are [x][g].
+//  * trace_walk_kernel, one lane per pair, walks back from the end cell for exactly `columns` columns, one word serving up to 8 diagonal
+//    steps, and writes the runs backwards from the end of a slice of 2 errors + 1 entries (no path has more runs); the host cuts the
+//    slices down to the runs.  A walk that does not end in front of the begin cell is an error of the call, never a shorter path.
+// Pairs go through in groups whose trace fits TRACE_BUDGET (2 GiB) or MHAP_REALIGN_TRACE_BYTES; a pair beyond it goes alone.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -38,6 +56,12 @@
 
 #include "device_common.hpp"
 #include "mhap_internal.hpp"
+
+// The paths of one call (mhap_align_pairs_banded_paths, mhap_realign_records_paths): pair q's runs are ops[offsets[q], offsets[q + 1]).
+struct mhap_align_paths {
+  std::vector<int64_t> offsets{0};
+  std::vector<uint32_t> ops;
+};
 
 namespace mhap {
 namespace {
@@ -285,6 +309,309 @@ int banded_run(const HandleView& v, BandedBufs& B, const int64_t* pairs, int64_t
   return MHAP_OK;
 }
 
+// ---- paths: the alignment itself, as run-length operations -----------------------------------------------------------------------------
+// (the file header, "Paths", is the design)
+
+constexpr uint32_t OP_I = 1, OP_D = 2, OP_EQ = 7, OP_X = 8;   // BAM's codes
+constexpr uint32_t OP_MAXLEN = (1u << 28) - 1;                // a longer run is split
+constexpr int64_t TRACE_BUDGET = (int64_t)2 << 30;            // bytes of direction nibbles in flight; MHAP_REALIGN_TRACE_BYTES overrides
+
+// The sub-matrix of one pair that has an alignment: rows [read_begin, read_end] of s1, columns [ref_begin, ref_end] of s2 and the
+// diagonals the path can have visited.  i, j, d below are relative to its first cell.
+struct TracePair {
+  int64_t a_off, b_off;        // first byte of the rows' bases; first STORED byte of the columns' bases (their last when rc)
+  int64_t trace_off, ops_off;  // the pair's words in the trace buffer, its slice of the ops buffer
+  int32_t m, n, rc;
+  int32_t dlo, W, ilo, rows;   // diagonals [dlo, dlo + W), rows [ilo, ilo + rows) with a cell on one of them
+  int32_t G;                   // row groups of 8: passes x lanes of the kernel that fills the trace
+  int32_t cols, ops_cap;       // columns of the path; entries of the ops slice (2 errors + 1, and one per split)
+};
+
+// the diagonals [lo, hi] clipped to the m x n matrix (band_geom without the centre and half-width)
+inline BandGeom diag_geom(int64_t m, int64_t n, int64_t lo, int64_t hi) {
+  lo = std::max<int64_t>(lo, -(m - 1)); hi = std::min<int64_t>(hi, n - 1);
+  if (m <= 0 || n <= 0 || hi < lo) return BandGeom{0, 0, 0, 0};
+  const int64_t ilo = -hi > 0 ? -hi : 0, ihi = n - 1 - lo < m - 1 ? n - 1 - lo : m - 1;
+  return BandGeom{(int)lo, (int)(hi - lo + 1), (int)ilo, (int)(ihi - ilo + 1)};
+}
+
+__host__ __device__ inline void trace_shape(int rows, int T, int& passes, int& L) {   // align_banded_kernel's passes and lanes for `rows` band rows
+  passes = (rows + T * BA_R - 1) / (T * BA_R);
+  L = (rows + passes * BA_R - 1) / (passes * BA_R);
+}
+
+// align_banded_kernel's schedule over a TracePair, carrying no path fields and keeping no best cell: what it leaves is one nibble per
+// in-band cell — bits 0-1 H's choice (0 diagonal on equal bytes, 1 diagonal on different bytes, 2 E, 3 F; the choice of a cell with
+// H = 0 is never read, a walk ends by its column count), bit 2 "E extended", bit 3 "F extended".  Word (x, g) of a pair holds diagonal
+// dlo + x of the 8 rows ilo + 8 g ...: a lane's strip is one g, its 8 cells of one step lie on 8 diagonals, so a lane keeps the 8 words
+// in flight in registers (acc[k]: diagonal index q - 1 - k), completes one per step and stores it whole.
+template <int NW>
+__global__ __launch_bounds__(NW * 64) void trace_fill_kernel(const uint8_t* __restrict__ bases, const TracePair* __restrict__ tps,
+                                                             const int32_t* __restrict__ order, int n_order, int* __restrict__ next,
+                                                             int32_t* __restrict__ scratch, int64_t scratch_stride,
+                                                             uint32_t* __restrict__ trace) {
+  constexpr int T = NW * 64;
+  __shared__ int hand[2][NW > 1 ? NW - 1 : 1][2];   // H, F of lane 63 of wave w for lane 0 of wave w + 1, by step parity
+  __shared__ int cur;
+  const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+  int32_t* edge = scratch ? scratch + (int64_t)blockIdx.x * scratch_stride : nullptr;
+  for (;;) {
+    if (t == 0) cur = atomicAdd(next, 1);
+    __syncthreads();
+    const int k = cur;
+    __syncthreads();
+    if (k >= n_order) return;
+    const TracePair tp = tps[order[k]];
+    const int n = tp.n, W = tp.W, ihi = tp.ilo + tp.rows - 1;
+    const bool b_rc = tp.rc != 0;
+    int passes, L;
+    trace_shape(tp.rows, T, passes, L);
+    const int P = L * BA_R;
+    const int64_t G = (int64_t)passes * L;
+    uint32_t* tr = trace + tp.trace_off;
+    for (int p = 0; p < passes; p++) {
+      uint32_t c1[BA_R], acc[BA_R];
+      int Hp[BA_R], Ep[BA_R];
+      const int pbase = tp.ilo + p * P, row0 = pbase + t * BA_R;
+#pragma unroll
+      for (int r = 0; r < BA_R; r++) {
+        const int i = row0 + r;
+        c1[r] = (t < L && i <= ihi) ? (uint32_t)bases[tp.a_off + i] : BA_PAD;
+        Hp[r] = 0; Ep[r] = BA_NEG; acc[r] = 0;
+      }
+      int dH = 0, outH = 0, outF = BA_NEG;
+      const int jc = pbase + tp.dlo - 1;
+      const int s_begin = jc < 0 ? -jc : 0;
+      // BA_R steps more than align_banded_kernel takes at the right edge of s2: the words in flight there still have to come out
+      const int s_end = min((L - 1) * (BA_R + 1) + W + BA_R, n - jc + L - 1 + BA_R);
+      for (int s = s_begin; s < s_end; s++) {
+        const int q = s - t * (BA_R + 1), j = jc + s - t;
+        const bool inq = t < L && q >= 0 && q < W + BA_R;
+        const bool active = inq && j >= 0 && j < n;
+        int inH = __shfl_up(outH, 1), inF = __shfl_up(outF, 1);
+        if (NW > 1 && lane == 0 && t > 0) { inH = hand[(s + 1) & 1][wave - 1][0]; inF = hand[(s + 1) & 1][wave - 1][1]; }
+        if (active) {
+          if (q >= W || (t == 0 && p == 0)) { inH = 0; inF = BA_NEG; }
+          else if (t == 0) { inH = edge[q]; inF = edge[W + q]; }
+          const uint32_t c2 = b_rc ? rc_char(bases[tp.b_off + (n - 1 - j)]) : (uint32_t)bases[tp.b_off + j];
+          int upH = inH, upF = inF, diagH = dH;
+#pragma unroll
+          for (int r = 0; r < BA_R; r++) {
+            const bool inband = c1[r] != BA_PAD && (unsigned)(q - 1 - r) < (unsigned)W;
+            const bool mis = c1[r] != c2;
+            const int D = diagH + (mis ? -2 : 2);
+            const int eext = Ep[r] - 1, eopn = Hp[r] - 2;
+            const bool ext = eext >= eopn;
+            int E = ext ? eext : eopn;
+            const int fext = upF - 1, fopn = upH - 2;
+            const bool fx = fext >= fopn;
+            int F = fx ? fext : fopn;
+            const bool take_d = D > 0 && D >= E && D >= F;
+            const bool take_e = !take_d && E > 0 && E >= F;
+            const bool take_f = !take_d && !take_e && F > 0;
+            int H = take_d ? D : take_e ? E : take_f ? F : 0;
+            const uint32_t nib = (take_d ? (mis ? 1u : 0u) : take_e ? 2u : 3u) | (ext ? 4u : 0u) | (fx ? 8u : 0u);
+            if (!inband) { H = 0; E = BA_NEG; F = BA_NEG; }
+            else acc[r] |= nib << (4 * r);
+            diagH = Hp[r];
+            Hp[r] = H; Ep[r] = E;
+            upH = H; upF = F;
+          }
+          dH = inH;
+          outH = upH; outF = upF;
+          if (t == L - 1 && p + 1 < passes && q >= BA_R) { edge[q - BA_R] = outH; edge[W + q - BA_R] = outF; }
+        } else {
+          dH = 0;
+        }
+        if (inq) {   // diagonal index q - BA_R has had its 8 rows (those outside the matrix or the band stay 0)
+          if (q >= BA_R) tr[(int64_t)(q - BA_R) * G + (p * L + t)] = acc[BA_R - 1];
+#pragma unroll
+          for (int r = BA_R - 1; r > 0; r--) acc[r] = acc[r - 1];
+          acc[0] = 0;
+        }
+        if constexpr (NW > 1) {
+          if (lane == 63 && wave + 1 < NW) { hand[s & 1][wave][0] = outH; hand[s & 1][wave][1] = outF; }
+          __syncthreads();
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// One lane per pair walks its nibbles from the end cell for exactly `cols` columns and writes the runs backwards from the end of the
+// pair's slice, so that they stand in path order at the slice's tail.  A word serves up to 8 diagonal steps; it is fetched again only
+// when the walk leaves its 8 rows or its diagonal.  n_ops[q]: the runs written, or -1 when the walk left the sub-matrix, overran its
+// slice or did not end in front of the begin cell — the trace and the first pass disagree, which the host reports as an error.
+__global__ __launch_bounds__(64) void trace_walk_kernel(const TracePair* __restrict__ tps, int n_pairs, const uint32_t* __restrict__ trace,
+                                                        uint32_t* __restrict__ ops, int32_t* __restrict__ n_ops) {
+  const int q = blockIdx.x * 64 + threadIdx.x;
+  if (q >= n_pairs) return;
+  const TracePair tp = tps[q];
+  const uint32_t* tr = trace + tp.trace_off;
+  uint32_t* slice = ops + tp.ops_off;
+  int pos = tp.ops_cap, i = tp.m - 1, j = tp.n - 1, st = 0, left = tp.cols;   // st: 0 in H, 1 in E, 2 in F
+  int64_t have = -1;
+  uint32_t word = 0, code = 0, len = 0;
+  bool ok = true;
+  for (int64_t guard = 2 * (int64_t)tp.cols + 2; left > 0 && guard > 0; guard--) {
+    const int x = j - i - tp.dlo, ri = i - tp.ilo;
+    if (i < 0 || j < 0 || (unsigned)x >= (unsigned)tp.W || (unsigned)ri >= (unsigned)tp.rows) { ok = false; break; }
+    const int64_t idx = (int64_t)x * tp.G + (ri >> 3);
+    if (idx != have) { word = tr[idx]; have = idx; }
+    const uint32_t nib = (word >> (4 * (ri & 7))) & 15u;
+    uint32_t c;
+    if (st == 0) {
+      const uint32_t hc = nib & 3u;
+      if (hc >= 2u) { st = (int)hc - 1; continue; }
+      c = hc == 0u ? OP_EQ : OP_X; i--; j--;
+    } else if (st == 1) { c = OP_D; j--; st = (nib & 4u) ? 1 : 0; }
+    else { c = OP_I; i--; st = (nib & 8u) ? 2 : 0; }
+    left--;
+    if (c == code && len < OP_MAXLEN) len++;
+    else {
+      if (len) { if (pos == 0) { ok = false; break; } slice[--pos] = len << 4 | code; }
+      code = c; len = 1;
+    }
+  }
+  if (ok && len) { if (pos == 0) ok = false; else slice[--pos] = len << 4 | code; }
+  ok = ok && left == 0 && i == -1 && j == -1 && st == 0;
+  n_ops[q] = ok ? tp.ops_cap - pos : -1;
+}
+
+struct PathBufs {
+  DevBuf tps, order, next, scratch, trace, ops, n_ops;
+  void release() { tps.release(); order.release(); next.release(); scratch.release(); trace.release(); ops.release(); n_ops.release(); }
+};
+
+int64_t trace_budget() {
+  if (const char* e = getenv("MHAP_REALIGN_TRACE_BYTES")) {
+    char* end = nullptr;
+    const long long v = strtoll(e, &end, 10);
+    if (end != e && *end == '\0' && v >= 1) return (int64_t)v;
+  }
+  return TRACE_BUDGET;
+}
+
+// The paths of `pairs` (validated, their bases in B.bases) whose `results` banded_run has just returned, appended to `out`.  q0: the
+// index of pairs[0] in the caller's numbering, for messages.
+int paths_run(const HandleView& v, BandedBufs& B, PathBufs& PB, const int64_t* pairs, int64_t n, const int32_t* results, int64_t q0,
+              mhap_align_paths& out, const char* who) {
+  auto fail = [&](hipError_t e, const std::string& what) {
+    *v.err = std::string(who) + ": " + what + ": " + hipGetErrorString(e);
+    return MHAP_E_HIP;
+  };
+  // the sub-matrix of every pair that has an alignment.  With I = columns - (ref_end - ref_begin + 1) insertions and D = columns -
+  // (read_end - read_begin + 1) deletions on the path, the path stays on the diagonals [-I, D] around its begin cell's.
+  std::vector<TracePair> tps;
+  std::vector<int64_t> owner;       // index into pairs
+  std::vector<int64_t> est_words;   // trace words, an upper bound over both kernel forms
+  for (int64_t q = 0; q < n; q++) {
+    const int64_t* p = pairs + 7 * q;
+    const int32_t* a = results + 7 * q;
+    if (a[0] <= 0 || a[5] <= 0) continue;
+    TracePair tp{};
+    tp.m = a[2] - a[1] + 1; tp.n = a[4] - a[3] + 1; tp.rc = p[4] != 0;
+    tp.a_off = p[0] + a[1];
+    tp.b_off = tp.rc ? p[2] + (p[3] - 1 - a[4]) : p[2] + a[3];
+    const BandGeom g = band_geom(p[1], p[3], p[5], p[6]);
+    const int64_t d0 = (int64_t)a[3] - a[1], ins = (int64_t)a[5] - tp.n, del = (int64_t)a[5] - tp.m;
+    const BandGeom s = diag_geom(tp.m, tp.n, std::max<int64_t>(-ins, g.dlo - d0), std::min<int64_t>(del, (int64_t)g.dlo + g.W - 1 - d0));
+    tp.dlo = s.dlo; tp.W = s.W; tp.ilo = s.ilo; tp.rows = s.rows;
+    tp.cols = a[5];
+    tp.ops_cap = (int32_t)std::min<int64_t>(2 * (int64_t)a[6] + 1 + a[5] / OP_MAXLEN, a[5]);
+    if (s.W <= 0 || ins < 0 || del < 0) { *v.err = std::string(who) + ": internal error: pair " + std::to_string(q0 + q) + " has an alignment outside its band"; return MHAP_E_HIP; }
+    tps.push_back(tp);
+    owner.push_back(q);
+    est_words.push_back((int64_t)s.W * ((s.rows + BA_R - 1) / BA_R + (s.rows + 64 * BA_R - 1) / (64 * BA_R)));
+  }
+  const int64_t budget = trace_budget();
+  const size_t first_offset = out.offsets.size();   // offsets[first_offset + q] = end of pair q's runs
+  out.offsets.resize(first_offset + (size_t)n, out.offsets.back());
+  std::vector<int32_t> counts;
+  std::vector<uint32_t> slices;
+  std::vector<std::vector<uint32_t>> runs((size_t)n);   // per pair, until the offsets are known (groups finish in pair order)
+  hipError_t e;
+  for (size_t g0 = 0; g0 < tps.size();) {
+    // a group: pairs in order while their trace fits the budget; a pair beyond the budget goes alone
+    size_t g1 = g0;
+    int64_t bytes = 0;
+    while (g1 < tps.size() && (g1 == g0 || bytes + 4 * est_words[g1] <= budget) && g1 - g0 < ((size_t)1 << 20)) bytes += 4 * est_words[g1++];
+    const int64_t ng = (int64_t)(g1 - g0);
+    int64_t n_tall = 0;
+    for (size_t u = g0; u < g1; u++) n_tall += tps[u].rows > 64 * BA_R;
+    const bool spread = n_tall < 4LL * v.num_cus;   // banded_run's rule
+    std::vector<int32_t> big, small;
+    int64_t words = 0, n_slices = 0, w_big = 0, w_small = 0;
+    for (size_t u = g0; u < g1; u++) {
+      TracePair& tp = tps[u];
+      const bool wide = spread && tp.rows > 64 * BA_R;
+      int passes, L;
+      trace_shape(tp.rows, wide ? BA_NWB * 64 : 64, passes, L);
+      tp.G = passes * L;
+      tp.trace_off = words; words += (int64_t)tp.W * tp.G;
+      tp.ops_off = n_slices; n_slices += tp.ops_cap;
+      (wide ? big : small).push_back((int32_t)(u - g0));
+      if (passes > 1) (wide ? w_big : w_small) = std::max<int64_t>(wide ? w_big : w_small, tp.W);
+    }
+    auto cells = [&](int32_t u) { return (double)tps[g0 + u].rows * (double)tps[g0 + u].W; };
+    auto by_cells = [&](int32_t a, int32_t b) { const double ca = cells(a), cb = cells(b); return ca != cb ? ca > cb : a < b; };
+    std::stable_sort(big.begin(), big.end(), by_cells);
+    std::stable_sort(small.begin(), small.end(), by_cells);
+    std::vector<int32_t> order(big);
+    order.insert(order.end(), small.begin(), small.end());
+    int grid_big = (int)std::min<int64_t>((int64_t)big.size(), 4LL * v.num_cus);       // (69 and 82 VGPRs: the fill kernels fit twice the
+    int grid_small = (int)std::min<int64_t>((int64_t)small.size(), 16LL * v.num_cus);   // workgroups per compute unit of banded_run's)
+    const int64_t stride_big = 2 * w_big, stride_small = 2 * w_small;
+    const int64_t scratch_big = stride_big * grid_big, scratch_words = scratch_big + stride_small * grid_small;
+    const std::string which = "pair " + std::to_string(q0 + owner[g0]) + (ng > 1 ? " and the " + std::to_string(ng - 1) + " after it" : "");
+    if ((e = PB.trace.ensure((size_t)std::max<int64_t>(words, 1) * 4)) != hipSuccess)
+      return fail(e, "hipMalloc of " + std::to_string(words * 4) + " bytes of trace for " + which);
+    if ((e = PB.tps.ensure(sizeof(TracePair) * (size_t)ng)) != hipSuccess) return fail(e, "hipMalloc");
+    if ((e = PB.order.ensure(4 * (size_t)ng)) != hipSuccess) return fail(e, "hipMalloc");
+    if ((e = PB.next.ensure(8)) != hipSuccess) return fail(e, "hipMalloc");
+    if ((e = PB.n_ops.ensure(4 * (size_t)ng)) != hipSuccess) return fail(e, "hipMalloc");
+    if ((e = PB.ops.ensure(4 * (size_t)n_slices)) != hipSuccess) return fail(e, "hipMalloc of the runs of " + which);
+    if (scratch_words > 0 && (e = PB.scratch.ensure((size_t)scratch_words * 4)) != hipSuccess) return fail(e, "hipMalloc (pass boundaries)");
+    if ((e = hipMemcpyAsync(PB.tps.p, tps.data() + g0, sizeof(TracePair) * (size_t)ng, hipMemcpyHostToDevice, v.stream)) != hipSuccess) return fail(e, "upload");
+    if ((e = hipMemcpyAsync(PB.order.p, order.data(), 4 * (size_t)ng, hipMemcpyHostToDevice, v.stream)) != hipSuccess) return fail(e, "upload");
+    if ((e = hipMemsetAsync(PB.next.p, 0, 8, v.stream)) != hipSuccess) return fail(e, "memset");
+    int* nx = PB.next.as<int>();
+    if (!big.empty())
+      hipLaunchKernelGGL(trace_fill_kernel<BA_NWB>, dim3(grid_big), dim3(BA_NWB * 64), 0, v.stream, B.bases.as<uint8_t>(), PB.tps.as<TracePair>(),
+                         PB.order.as<int32_t>(), (int)big.size(), nx, stride_big > 0 ? PB.scratch.as<int32_t>() : nullptr, stride_big,
+                         PB.trace.as<uint32_t>());
+    if (!small.empty())
+      hipLaunchKernelGGL(trace_fill_kernel<1>, dim3(grid_small), dim3(64), 0, v.stream, B.bases.as<uint8_t>(), PB.tps.as<TracePair>(),
+                         PB.order.as<int32_t>() + big.size(), (int)small.size(), nx + 1,
+                         stride_small > 0 ? PB.scratch.as<int32_t>() + scratch_big : nullptr, stride_small, PB.trace.as<uint32_t>());
+    hipLaunchKernelGGL(trace_walk_kernel, dim3((unsigned)((ng + 63) / 64)), dim3(64), 0, v.stream, PB.tps.as<TracePair>(), (int)ng,
+                       PB.trace.as<uint32_t>(), PB.ops.as<uint32_t>(), PB.n_ops.as<int32_t>());
+    if ((e = hipGetLastError()) != hipSuccess) return fail(e, "launch");
+    counts.resize((size_t)ng);
+    slices.resize((size_t)n_slices);
+    if ((e = hipMemcpyAsync(counts.data(), PB.n_ops.p, 4 * (size_t)ng, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return fail(e, "download");
+    if ((e = hipMemcpyAsync(slices.data(), PB.ops.p, 4 * (size_t)n_slices, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return fail(e, "download");
+    if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return fail(e, "kernel");
+    for (int64_t u = 0; u < ng; u++) {
+      const TracePair& tp = tps[g0 + (size_t)u];
+      const int32_t c = counts[(size_t)u];
+      if (c < 0) {
+        *v.err = std::string(who) + ": internal error: the trace of pair " + std::to_string(q0 + owner[g0 + (size_t)u]) + " does not lead back to its begin cell";
+        return MHAP_E_HIP;
+      }
+      const uint32_t* tail = slices.data() + tp.ops_off + (tp.ops_cap - c);
+      runs[(size_t)owner[g0 + (size_t)u]].assign(tail, tail + c);
+    }
+    g0 = g1;
+  }
+  for (int64_t q = 0; q < n; q++) {
+    out.ops.insert(out.ops.end(), runs[(size_t)q].begin(), runs[(size_t)q].end());
+    out.offsets[first_offset + (size_t)q] = (int64_t)out.ops.size();
+  }
+  return MHAP_OK;
+}
+
 int check_pairs(const int64_t* pairs, int64_t n, int64_t n_bases, std::string* err, const char* who) {
   for (int64_t q = 0; q < n; q++) {
     const int64_t* p = pairs + 7 * q;
@@ -356,21 +683,59 @@ thread_local std::string g_plan_err;
 
 using namespace mhap;
 
-extern "C" int mhap_align_pairs_banded(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const int64_t* pairs, int64_t n, int32_t* results) {
+namespace {
+
+// mhap_align_pairs_banded, and with `paths` the path of every pair as well (an object the caller then owns)
+int align_banded_impl(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const int64_t* pairs, int64_t n, int32_t* results,
+                      mhap_align_paths** paths, const char* who) {
+  if (paths) *paths = nullptr;
   if (!h) return MHAP_E_INVALID;
   HandleView v = handle_view(h);
-  const char* who = "mhap_align_pairs_banded";
   if (n < 0 || n_bases < 0 || (n > 0 && (!pairs || !results)) || (n_bases > 0 && !bases)) { *v.err = std::string(who) + ": null or negative argument"; return MHAP_E_INVALID; }
   if (n > INT32_MAX) { *v.err = std::string(who) + ": more than 2^31 - 1 pairs in one call"; return MHAP_E_INVALID; }
-  if (n == 0) return MHAP_OK;
+  if (n == 0) { if (paths) *paths = new mhap_align_paths(); return MHAP_OK; }
   int rc = check_pairs(pairs, n, n_bases, v.err, who);
   if (rc != MHAP_OK) return rc;
   BandedBufs B;
+  PathBufs PB;
+  mhap_align_paths* out = paths ? new mhap_align_paths() : nullptr;
   rc = upload_bases(v, B, bases, n_bases, who);
   if (rc == MHAP_OK) rc = banded_run(v, B, pairs, n, results, who);
+  if (rc == MHAP_OK && out) rc = paths_run(v, B, PB, pairs, n, results, 0, *out, who);
   B.release();
+  PB.release();
+  if (rc != MHAP_OK) delete out;
+  else if (paths) *paths = out;
   return rc;
 }
+
+}  // namespace
+
+extern "C" int mhap_align_pairs_banded(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const int64_t* pairs, int64_t n, int32_t* results) {
+  return align_banded_impl(h, bases, n_bases, pairs, n, results, nullptr, "mhap_align_pairs_banded");
+}
+
+extern "C" int mhap_align_pairs_banded_paths(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const int64_t* pairs, int64_t n,
+                                             int32_t* results, mhap_align_paths** out) {
+  if (!out) return MHAP_E_INVALID;
+  return align_banded_impl(h, bases, n_bases, pairs, n, results, out, "mhap_align_pairs_banded_paths");
+}
+
+extern "C" int mhap_align_paths_info(const mhap_align_paths* p, int64_t* n, int64_t* n_ops) {
+  if (!p) return MHAP_E_INVALID;
+  if (n) *n = (int64_t)p->offsets.size() - 1;
+  if (n_ops) *n_ops = (int64_t)p->ops.size();
+  return MHAP_OK;
+}
+
+extern "C" int mhap_align_paths_copy(const mhap_align_paths* p, int64_t* op_offsets, uint32_t* ops) {
+  if (!p || !op_offsets || (!ops && !p->ops.empty())) return MHAP_E_INVALID;
+  std::copy(p->offsets.begin(), p->offsets.end(), op_offsets);
+  std::copy(p->ops.begin(), p->ops.end(), ops);
+  return MHAP_OK;
+}
+
+extern "C" void mhap_align_paths_free(mhap_align_paths* p) { delete p; }
 
 extern "C" const char* mhap_realign_plan_error(void) { return g_plan_err.c_str(); }
 
@@ -390,18 +755,21 @@ extern "C" int mhap_realign_plan(const mhap_record* recs, int64_t n, const int64
   return MHAP_OK;
 }
 
-extern "C" int mhap_realign_records(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const int64_t* read_ids, const int64_t* offsets,
-                                    const int32_t* lengths, int64_t n_reads, const mhap_record* recs, int64_t n, int32_t band,
-                                    mhap_record* out, int32_t* detail) {
+namespace {
+
+// mhap_realign_records, and with `paths` the path of every record's planned pair as well (an object the caller then owns)
+int realign_impl(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const int64_t* read_ids, const int64_t* offsets,
+                 const int32_t* lengths, int64_t n_reads, const mhap_record* recs, int64_t n, int32_t band, mhap_record* out,
+                 int32_t* detail, mhap_align_paths** paths, const char* who) {
+  if (paths) *paths = nullptr;
   if (!h) return MHAP_E_INVALID;
   HandleView v = handle_view(h);
-  const char* who = "mhap_realign_records";
   if (n < 0 || n_bases < 0 || n_reads < 0 || band < 0 || (n > 0 && (!recs || !out)) || (n_bases > 0 && !bases) ||
       (n_reads > 0 && (!read_ids || !offsets || !lengths))) {
     *v.err = std::string(who) + ": null or negative argument";
     return MHAP_E_INVALID;
   }
-  if (n == 0) return MHAP_OK;
+  if (n == 0) { if (paths) *paths = new mhap_align_paths(); return MHAP_OK; }
   for (int64_t i = 0; i < n_reads; i++)
     if (offsets[i] < 0 || lengths[i] < 0 || offsets[i] > n_bases - lengths[i]) {
       *v.err = std::string(who) + ": read " + std::to_string(i) + " lies outside the " + std::to_string(n_bases) + " bases";
@@ -413,6 +781,8 @@ extern "C" int mhap_realign_records(mhap_handle* h, const uint8_t* bases, int64_
   // record (5.8 MB) on each side, and the pass boundaries of the workgroups in flight (at most BA_SCRATCH_BUDGET, 1 GiB), whatever n is.
   constexpr int64_t BATCH = 1 << 16;
   BandedBufs B;
+  PathBufs PB;
+  mhap_align_paths* po = paths ? new mhap_align_paths() : nullptr;
   int rc = upload_bases(v, B, bases, n_bases, who);
   std::vector<int64_t> pairs((size_t)std::min(n, BATCH) * 7);
   std::vector<int32_t> res((size_t)std::min(n, BATCH) * 7);
@@ -423,6 +793,7 @@ extern "C" int mhap_realign_records(mhap_handle* h, const uint8_t* bases, int64_
     if (rc != MHAP_OK) break;
     rc = banded_run(v, B, pairs.data(), c, res.data(), who);
     if (rc != MHAP_OK) break;
+    if (po && (rc = paths_run(v, B, PB, pairs.data(), c, res.data(), q0, *po, who)) != MHAP_OK) break;
     for (int64_t q = 0; q < c; q++) {
       const mhap_record& r = recs[q0 + q];
       const int32_t* a = res.data() + 7 * q;
@@ -442,5 +813,23 @@ extern "C" int mhap_realign_records(mhap_handle* h, const uint8_t* bases, int64_
     }
   }
   B.release();
+  PB.release();
+  if (rc != MHAP_OK) delete po;
+  else if (paths) *paths = po;
   return rc;
+}
+
+}  // namespace
+
+extern "C" int mhap_realign_records(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const int64_t* read_ids, const int64_t* offsets,
+                                    const int32_t* lengths, int64_t n_reads, const mhap_record* recs, int64_t n, int32_t band,
+                                    mhap_record* out, int32_t* detail) {
+  return realign_impl(h, bases, n_bases, read_ids, offsets, lengths, n_reads, recs, n, band, out, detail, nullptr, "mhap_realign_records");
+}
+
+extern "C" int mhap_realign_records_paths(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const int64_t* read_ids, const int64_t* offsets,
+                                          const int32_t* lengths, int64_t n_reads, const mhap_record* recs, int64_t n, int32_t band,
+                                          mhap_record* out, int32_t* detail, mhap_align_paths** paths) {
+  if (!paths) return MHAP_E_INVALID;
+  return realign_impl(h, bases, n_bases, read_ids, offsets, lengths, n_reads, recs, n, band, out, detail, paths, "mhap_realign_records_paths");
 }

@@ -1,5 +1,6 @@
 """Realign a file of MHAP overlaps on the GPU: `python -m mhap_amd.realign overlaps.txt reads.fasta [queries.fasta] [--band W]
-[--min-identity X]` prints what `mhap-hip --realign` prints for the same overlaps.
+[--min-identity X] [--paf]` prints what `mhap-hip --realign` prints for the same overlaps (with --paf: what `--realign --realign-paf`
+prints, one PAF line per overlap with the alignment's path as a cg:Z CIGAR).
 
 Every record's interval is an estimate made from the shared k-mers of two sketches; this tool aligns the two reads inside a band around
 the diagonal that interval implies (mhap_realign_records) and prints the record with the alignment's ends and 1 - identity in column 3.
@@ -42,10 +43,15 @@ def read_overlaps(path):
     return np.array(rows, dtype=api.RECORD_DTYPE) if rows else np.zeros(0, api.RECORD_DTYPE)
 
 
-def keep(records, min_identity=0.0):
-    """The driver's rule: a record without an alignment, or with an identity below min_identity, is dropped."""
+def kept_rows(records, min_identity=0.0):
+    """The driver's rule: a record without an alignment, or with an identity below min_identity, is dropped.  The rows that stay."""
     none = (records["score"] == 0.0) & (records["a1"] == 0) & (records["a2"] == 0) & (records["b1"] == 0) & (records["b2"] == 0)
-    return records[~none & ~(records["score"] < min_identity)]
+    return np.nonzero(~none & ~(records["score"] < min_identity))[0]
+
+
+def keep(records, min_identity=0.0):
+    """The records that kept_rows keeps."""
+    return records[kept_rows(records, min_identity)]
 
 
 def main(argv=None):
@@ -58,15 +64,23 @@ def main(argv=None):
     ap.add_argument("--min-identity", type=float, default=0.0)
     ap.add_argument("--query-id-offset", type=int, default=None)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--paf", action="store_true", help="print PAF lines with the alignment's path (cg:Z) instead of the 12 columns")
     a = ap.parse_args(argv)
     if a.band < 0:
         ap.error("--band must be >= 0")
     recs = read_overlaps(a.overlaps)
     fasta = api.FastaData.from_file(a.reads)
     queries = api.FastaData.from_file(a.queries, len(fasta) if a.query_id_offset is None else a.query_id_offset) if a.queries else None
-    out, _ = api.realign_records(recs, fasta, band=a.band, max_shift=a.max_shift, device=a.device, query_fasta=queries)
-    kept = keep(out, a.min_identity)
-    sys.stdout.write("".join(line + "\n" for line in api.records_to_lines(kept)))
+    if a.paf:
+        out, detail, op_offsets, ops = api.realign_records_paths(recs, fasta, band=a.band, max_shift=a.max_shift, device=a.device,
+                                                                 query_fasta=queries)
+        kept = keep(out, a.min_identity)
+        sys.stdout.write("".join(api.format_paf(out[q], detail[q], ops[op_offsets[q]:op_offsets[q + 1]]) + "\n"
+                                 for q in kept_rows(out, a.min_identity).tolist()))
+    else:
+        out, _ = api.realign_records(recs, fasta, band=a.band, max_shift=a.max_shift, device=a.device, query_fasta=queries)
+        kept = keep(out, a.min_identity)
+        sys.stdout.write("".join(line + "\n" for line in api.records_to_lines(kept)))
     print(f"Realigned {len(recs)} overlaps: {len(kept)} kept, {len(recs) - len(kept)} dropped (no alignment or identity below "
           f"{a.min_identity:g})", file=sys.stderr)
     return 0

@@ -105,6 +105,25 @@ def main():
         print(f"  of which the upload of the {len(fasta.bases) / 1e9:.2f} GB of bases and one record: {spread(one)}")
         print(f"  {int((detail[:, 0] > 0).sum())} records aligned, {int((detail[:, 0] == 0).sum())} without an alignment; "
               f"mean aligned identity {float(out['score'][detail[:, 0] > 0].mean()):.4f}; warm search before it: {t_search * 1e3:.1f} ms")
+        # 3. the same records with their paths (mhap_realign_records_paths), alternating with the call without them
+        mhap_amd.realign_records_paths(recs, fasta, handle=ms)            # warm-up: the trace buffers' first hipMalloc
+        tn, tp = [], []
+        for _ in range(max(3, a.repeats)):
+            tn.append(timed(lambda: mhap_amd.realign_records(recs, fasta, handle=ms))[0])
+            t, (_, dp, op_offsets, ops) = timed(lambda: mhap_amd.realign_records_paths(recs, fasta, handle=ms))
+            tp.append(t)
+        mn, mp = sorted(tn)[len(tn) // 2], sorted(tp)[len(tp) // 2]
+        res = mhap_amd.align_pairs_banded(fasta.bases, auto, handle=ms)
+        ok = res[:, 0] > 0
+        rows, cols2 = (res[ok, 2] - res[ok, 1] + 1).astype(np.int64), (res[ok, 4] - res[ok, 3] + 1).astype(np.int64)
+        diags = np.minimum((res[ok, 5] - rows) + (res[ok, 5] - cols2) + 1, 2 * auto[ok, 6] + 1)
+        trace = diags * ((rows + 7) // 8) * 4
+        print(f"realign all {len(recs)} records without paths: {spread(tn)}")
+        print(f"realign all {len(recs)} records with paths:    {spread(tp)}; with / without: {mp / mn:.3f}; {len(ops)} runs, "
+              f"{len(ops) / max(1, int(ok.sum())):.0f} per aligned record")
+        print(f"  trace: {trace.sum() / 1e9:.2f} GB over {int(ok.sum())} records, mean {trace.mean() / 1e6:.2f} MB, max {trace.max() / 1e6:.2f} MB "
+              f"(mean {diags.mean():.0f} diagonals x {rows.mean():.0f} rows at 4 bits a cell); budget "
+              f"{os.environ.get('MHAP_REALIGN_TRACE_BYTES', 'default (2 GiB)')}")
         if not mb < mf:
             print("realign_bench: the banded kernel is NOT faster than the full-matrix kernel", file=sys.stderr)
             sys.exit(3)
