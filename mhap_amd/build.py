@@ -85,6 +85,9 @@ VARIANTS = {
     # the weight-1 MinHash kernel with a 31-entry candidate queue per wave: every row overflows it, so the exact redo path
     # (sketch_kernels.hip, `if (!ok)` in minhash_w1_kernel) is EXECUTED against the oracle (tests/test_gpu_parity.py)
     "qcap64": (["-DMH_QCAP=64"], ["sketch_kernels.hip"]),
+    # ordered_kernel records which of its selection paths made every strand's row and launch_ordered prints the codes, one
+    # `[ordered paths]` line per launch (tests/test_ordered_paths_gpu.py compares them with tests/ordered_paths_ref.py)
+    "ordpaths": (["-DMH_ORD_PATHS"], ["sketch_kernels.hip"]),
 }
 
 

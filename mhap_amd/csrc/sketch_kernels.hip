@@ -13,6 +13,11 @@
 
 #include "kernels.hpp"
 #include <algorithm>
+#ifdef MH_ORD_PATHS
+#include <cstdio>
+#include <string>
+#include <vector>
+#endif
 
 namespace mhap {
 
@@ -2195,6 +2200,25 @@ __device__ unsigned long long g_ord_prof[8];
 #else
 #define ORD_TICK(k) do { } while (0)
 #endif
+// -DMH_ORD_PATHS (build variant `ordpaths`, tests/test_ordered_paths_gpu.py): every strand records which of the kernel's selection paths made
+// its row — bits 0-3 the one-pass attempt (0 not attempted, 1 accepted, 2 rejected: fewer than K keys staged, 3 rejected: more than cap,
+// 4 rejected: a crowded bin), bits 4-7 how the row was made (1 all keys through the network, 2 one-pass buckets, 3 level-0 buckets,
+// 4 + L the network after the exact selection ended at level L), bit 8 stage_wide, bit 9 MHAP_RD_MAT; 0 = skipped strand.
+// launch_ordered prints them.  Without the flag the macros are empty: the shipped kernel has no extra argument, store or branch.
+#ifdef MH_ORD_PATHS
+__device__ uint32_t* g_ord_paths;   // one code per strand of the launch
+#define ORD_PATH_VARS uint32_t ord_att = 0; int ord_lv = 0
+#define ORD_PATH_ATT(a) do { ord_att = (uint32_t)(a); } while (0)
+#define ORD_PATH_LEVEL(l) do { ord_lv = (l); } while (0)
+#define ORD_PATH_HOW(how) do { if (threadIdx.x == 0 && g_ord_paths) g_ord_paths[blockIdx.x] = ord_att | ((uint32_t)(how) << 4) | (stage_wide ? 256u : 0u) | (mat ? 512u : 0u); } while (0)
+#define ORD_PATH_NETWORK ORD_PATH_HOW(n > cap ? 4 + ord_lv : 1)
+#else
+#define ORD_PATH_VARS do { } while (0)
+#define ORD_PATH_ATT(a) do { } while (0)
+#define ORD_PATH_LEVEL(l) do { } while (0)
+#define ORD_PATH_HOW(how) do { } while (0)
+#define ORD_PATH_NETWORK do { } while (0)
+#endif
 // h * 5 + 0xe6546b64 of the murmur3_x86_32 body as a shift-add and an add: the compiler turns the multiply-add into v_mad_u64_u32
 // (quarter rate; 48 of them per eight hashes in the pass below)
 __device__ __forceinline__ uint32_t mm3_mul5c(uint32_t h) {
@@ -2266,6 +2290,7 @@ __global__ __launch_bounds__(ORD_THREADS) void ordered_kernel(const ReadDesc* __
   const int K = S < n ? S : n;   // BottomOverlapSketch.java:548
   if (threadIdx.x == 0) { meta[0] = K; meta[1] = n; meta[2] = rd.length; }
   if (K <= 0) return;
+  ORD_PATH_VARS;
 
   // ---- one-pass path.  murmur3 hashes are uniform, so the K-th smallest key is close to the K/n quantile of the hash range:
   // one pass keeps the positions of the keys below a cut placed a few standard deviations above that quantile (and their
@@ -2342,6 +2367,7 @@ __global__ __launch_bounds__(ORD_THREADS) void ordered_kernel(const ReadDesc* __
     ORD_TICK(1);
     const uint32_t m = s_fill;
     bool ok = m >= (uint32_t)K && m <= (uint32_t)cap;
+    ORD_PATH_ATT(m < (uint32_t)K ? 2 : m > (uint32_t)cap ? 3 : 1);
     if (ok) {
       // exclusive prefix over the bins up to the cut: per-lane sums, shuffle scan inside a wavefront, wavefront totals through LDS
       const int per = ORD_BINS / ORD_THREADS;
@@ -2358,6 +2384,7 @@ __global__ __launch_bounds__(ORD_THREADS) void ordered_kernel(const ReadDesc* __
       for (int j = 0; j < per; j++) { const uint32_t b = threadIdx.x * per + j; bstart[b] = (uint16_t)run; run += hist[b]; }
       ok = s_cnt == 0;
       __syncthreads();
+      if (!ok) ORD_PATH_ATT(4);
     }
     ORD_TICK(2);
     if (ok) {
@@ -2413,6 +2440,7 @@ __global__ __launch_bounds__(ORD_THREADS) void ordered_kernel(const ReadDesc* __
 #ifdef MH_ORD_PROF
       if (threadIdx.x == 0) atomicAdd(&g_ord_prof[7], 1ULL);
 #endif
+      ORD_PATH_HOW(2);
       return;
     }
     __syncthreads();
@@ -2477,6 +2505,7 @@ __global__ __launch_bounds__(ORD_THREADS) void ordered_kernel(const ReadDesc* __
       prefmask |= (uint64_t)(nb - 1) << sh;
       bound = prefix | (sh > 0 ? ((1ULL << sh) - 1) : 0ULL);
       if (below + bincnt <= (uint32_t)cap) {   // candidates (<= bound) fit the sort buffer
+        ORD_PATH_LEVEL(lv);
         if (lv == 0) {
           // Hashes are close to uniform, so the 2048 first-level bins hold a handful of keys each: give every bin up to the
           // cut its own slice of the buffer (exclusive prefix of the counts) and sort inside the bins only — O(n) instead
@@ -2529,8 +2558,10 @@ __global__ __launch_bounds__(ORD_THREADS) void ordered_kernel(const ReadDesc* __
       const uint32_t j = s0 + rank;
       if (j < (uint32_t)K) { orow[2 * j] = (int32_t)((uint32_t)(key >> 32) ^ 0x80000000u); orow[2 * j + 1] = (int32_t)(uint32_t)key; }
     }
+    ORD_PATH_HOW(3);
     return;
   }
+  ORD_PATH_NETWORK;
   // compact candidates into LDS, pad, sort
   __syncthreads();
   for (int i = threadIdx.x; i < n; i += ORD_THREADS) {
@@ -2596,6 +2627,13 @@ void launch_ordered(hipStream_t st, const ReadDesc* descs, int64_t nstrands, int
   if (nstrands <= 0 || count <= 0) return;
   const int code_words = max_len_codes > 0 ? (max_len_codes + 15) / 16 + 4 : 0;
   const int stage_wide = max_len - k2 + 1 > 65535 ? 1 : 0;
+#ifdef MH_ORD_PATHS
+  uint32_t* d_paths = nullptr;
+  if (hipMalloc(&d_paths, (size_t)count * sizeof(uint32_t)) != hipSuccess) d_paths = nullptr;   // (the kernel then records nothing)
+  if (d_paths) (void)hipMemsetAsync(d_paths, 0, (size_t)count * sizeof(uint32_t), st);
+  (void)hipStreamSynchronize(st);   // (an earlier part of the launch group still reads the pointer)
+  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_ord_paths), &d_paths, sizeof(d_paths));
+#endif
   hipLaunchKernelGGL(ordered_kernel, dim3((unsigned)count), dim3(ORD_THREADS), ordered_lds_bytes(cap, code_words, stage_wide), st, descs, nstrands, h32,
                      store, luts, code_words, stage_wide, k2, S, cap, out_rows, out_stride, out_meta, meta_stride, first);
 #ifdef MH_ORD_PROF
@@ -2607,6 +2645,22 @@ void launch_ordered(hipStream_t st, const ReadDesc* descs, int64_t nstrands, int
           (double)hp[4] / hp[7], (double)hp[5] / hp[7]);
   unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   (void)hipMemcpyToSymbol(HIP_SYMBOL(g_ord_prof), z, sizeof(z));
+#endif
+#ifdef MH_ORD_PATHS
+  // one witness line per launch: [ordered paths] first F count C cap CAP S S codes: xxx xxx ... (three hex digits per strand)
+  {
+    std::vector<uint32_t> h_paths((size_t)count, 0u);
+    if (d_paths) (void)hipMemcpyAsync(h_paths.data(), d_paths, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+    (void)hipStreamSynchronize(st);
+    if (d_paths) (void)hipFree(d_paths);
+    std::string line;
+    line.reserve((size_t)count * 4 + 96);
+    char tmp[96];
+    snprintf(tmp, sizeof(tmp), "[ordered paths] first %lld count %lld cap %d S %d codes:", (long long)first, (long long)count, cap, S);
+    line += tmp;
+    for (uint32_t c : h_paths) { snprintf(tmp, sizeof(tmp), " %03x", c & 0xFFFu); line += tmp; }
+    fprintf(stderr, "%s\n", line.c_str());
+  }
 #endif
 }
 

@@ -878,12 +878,14 @@ def test_minhash_large_num_hashes_and_short_strands():
 
 
 def test_long_reads_partitioned_kmer_weights():
-    """Reads with more k-mers than the LDS weight table holds (24 576): hash-partitioned passes; >65 534: wider positions."""
+    """Reads with more k-mers than the LDS weight table holds (24 576): hash-partitioned passes; >65 534: wider positions.
+    S = 128 never attempts the ordered kernel's one-pass path; S = 1536 (the production size) does, here with 32-bit staged positions."""
     rnd = random.Random(123)
     a = _rand_seq(rnd, 40000)
     seqs = [_rand_seq(rnd, 26000), _rand_seq(rnd, 70000), _rand_seq(rnd, 131500), a + a[:15000] + a[5000:9000], "ACGTTGCAAT" * 3000]
     fa = FastaData.from_strings(seqs)
-    _assert_sketch_parity(fa, MhapParams(num_hashes=32, ordered_sketch_size=128))
+    for S in (128, 1536):
+        _assert_sketch_parity(fa, MhapParams(num_hashes=32, ordered_sketch_size=S))
 
 
 def _mutate(rnd, s, rate):
@@ -945,21 +947,25 @@ def test_overlap_join_groups_and_lane_fallback(monkeypatch):
 
 def test_fused_and_separate_kmer_hashing_agree(monkeypatch):
     """k=16/k2=12 packed strands are hashed inside the weight kernel (block-mix tables); raw-byte strands of the same batch
-    and MHAP_FUSED_HASH=0 use hash_kmers_kernel.  All three give the oracle's sketches."""
+    and MHAP_FUSED_HASH=0 use hash_kmers_kernel.  All three give the oracle's sketches, at S = 256 (the ordered kernel's exact selection) and at
+    S = 1536 (its one-pass path, on recomputed and on stored hashes)."""
     rnd = random.Random(99)
     seqs = [_rand_seq(rnd, rnd.randrange(20, 9000)) for _ in range(60)]
     seqs += [_rand_seq(rnd, 4000, "ACGTN"), _rand_seq(rnd, 12303), _rand_seq(rnd, 12304), _rand_seq(rnd, 16), _rand_seq(rnd, 27),
              "ACGT" * 1000, _rand_seq(rnd, 2500).lower()]
     fa = FastaData.from_strings(seqs)
-    p = MhapParams(num_hashes=64, ordered_sketch_size=256, min_olap_length=0)
-    _assert_sketch_parity(fa, p)
-    with MinHashSearch(p) as ms:
-        a = ms.sketch(fa)
-    monkeypatch.setenv("MHAP_FUSED_HASH", "0")
-    with MinHashSearch(p) as ms:
-        b = ms.sketch(fa)
-    for key in ("minhash", "ordered", "ordered_size", "status"):
-        assert np.array_equal(a[key], b[key]), key
+    for S in (256, 1536):
+        p = MhapParams(num_hashes=64, ordered_sketch_size=S, min_olap_length=0)
+        monkeypatch.delenv("MHAP_FUSED_HASH", raising=False)
+        _assert_sketch_parity(fa, p)
+        with MinHashSearch(p) as ms:
+            a = ms.sketch(fa)
+        monkeypatch.setenv("MHAP_FUSED_HASH", "0")
+        _assert_sketch_parity(fa, p)
+        with MinHashSearch(p) as ms:
+            b = ms.sketch(fa)
+        for key in ("minhash", "ordered", "ordered_size", "status"):
+            assert np.array_equal(a[key], b[key]), (S, key)
 
 
 def test_perchain_minhash_switch_agrees(monkeypatch, capfd):
