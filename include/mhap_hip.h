@@ -485,6 +485,73 @@ void mhap_align_paths_free(mhap_align_paths* p);
 int mhap_format_paf(const mhap_record* realigned, const int32_t* detail3, const uint32_t* ops, int64_t n_ops, const char* qname,
                     const char* tname, char* out, size_t cap);
 
+/* A paths object from runs the caller holds (no GPU): pair q's runs are ops[op_offsets[q] .. op_offsets[q + 1]), op_offsets[0] = 0 and
+ * non-decreasing.  What mhap_align_paths_copy wrote gives back an equal object; freed with mhap_align_paths_free.  MHAP_E_INVALID (and
+ * *out = NULL) for a null pointer, n < 0 or offsets that are not such a list. */
+int mhap_align_paths_from_runs(const int64_t* op_offsets /* n + 1 */, int64_t n, const uint32_t* ops, mhap_align_paths** out);
+
+/* ---- read correction: a pile-up vote over every read from the realigned overlaps' paths, and a majority call ---------------------- */
+
+/* The plain method: every realigned overlap votes column by column on both of its reads, and each read position takes the majority.
+ * No partial-order graph, no selection of overlaps, no cap on coverage.  A, C, G, T below are the upper-case bytes; bytes are the ones
+ * the aligner compared (s2 is the reverse complement, through Utils.rc's table, of the stored `to` read when to_rc).
+ *
+ * Which records vote.  A realigned record is out[q] of mhap_realign_records_paths with its runs: s1 = read A (`from`), rows i from
+ * a1; s2 = read B (`to`), reverse-complemented when to_rc, columns j from (to_rc ? blen - b2 - 1 : b1).  A record without runs (no
+ * alignment) votes nothing, a record whose two ids are equal votes nothing, and nothing is de-duplicated: a record given twice votes
+ * twice.  Every other record votes twice, once per view; a view is a list of columns in increasing target order:
+ *   view A (target A, evidence B):   '=' / 'X' -> M(t = i, e = s2[j]);   'I' (consumes s1 only) -> Del(t = i);   'D' -> Ins(e = s2[j])
+ *   view B (target B, evidence A), !to_rc:   '=' / 'X' -> M(t = j, e = s1[i]);   'D' -> Del(t = j);   'I' -> Ins(e = s1[i])
+ *   view B, to_rc: the !to_rc list in reverse order, every t replaced by blen - 1 - t and every e by its complement through the same
+ *     table (a byte the table does not change stays what it is).
+ * Paths begin and end with '=', so every group of consecutive Ins columns lies between two target-consuming columns and belongs to the
+ * target position t of the one before it (in the view's order).
+ *
+ * Votes.  22 counters per target position t: base[4] (A, C, G, T), del, span, ins[KI = 4][4].
+ *   M(t, e) adds 1 to base[t][e] when e is A, C, G or T, else nothing;   Del(t) adds 1 to del[t];
+ *   for every two consecutive target-consuming columns t, t' of a view, span[t] += 1 (the view continues past t);
+ *   in the Ins group after t the k-th byte (k from 0) adds 1 to ins[t][k][e] when k < 4 and e is A, C, G or T; any other byte votes
+ *   nothing but still takes its slot.
+ * Counters are 16 bits wide, two to a 32-bit word, so that a vote is one integer atomic add of 1 or 1 << 16: with 2 spare counters
+ * that is 24 counters, 48 bytes per base of the read set, resident on the device from begin to free.  The width is exact because the
+ * host counts the views it accepts per target, in arrival order (record by record, view A before view B): a view adds at most 1 to
+ * any counter, and a view whose target already has 65 535 accepted views is skipped whole and counted in skipped_views.  Integer sums
+ * do not depend on arrival order, so the result is the same from run to run and however the records are split over calls.
+ *
+ * The call for a read of length L, with min_cov (4 unless the caller says otherwise) and own = the read's byte at t, for t = 0 .. L - 1:
+ *   1. d = base[t][A] + base[t][C] + base[t][G] + base[t][T] + del[t].
+ *   2. d < min_cov: emit own and count the position as low.
+ *   3. Otherwise add 1 to base[t][own] when own is A, C, G or T, and total = d + 1.
+ *   4. 2 del[t] > total: emit nothing and count a deletion.
+ *   5. Otherwise emit the base with the most votes: own when it is among those tied for the maximum, else the first of A, C, G, T at
+ *      the maximum, own itself when every base count is 0; count a substitution when the emitted byte differs from own.
+ *   6. Whatever 2 - 5 did: when t < L - 1 and span[t] >= min_cov, for k = 0 .. 3 with m = max over b of ins[t][k][b]: 2 m > span[t] + 1
+ *      emits that base (the first of A, C, G, T at the maximum) and counts an insertion; otherwise the junction is done.
+ * Per read the result is the corrected bytes and six int32 {len_in, len_out, n_sub, n_del, n_ins, n_low}; a read nobody voted on
+ * comes back unchanged with n_low = len_in.
+ *
+ * The session.  mhap_correct_begin uploads the bases of the reads (read_ids[r], offsets[r], lengths[r]) once and allocates and zeroes
+ * the vote table; the handle must outlive the session, whose errors are the handle's (mhap_last_error).  mhap_correct_add takes the
+ * realigned records and the paths object of one mhap_realign_records_paths call (or mhap_align_paths_from_runs), any number of times,
+ * n = 0 included; the runs go up again, 4 bytes each, and one wave per accepted view adds its votes (correct_kernels.hip).  A record's
+ * reads are found by id as mhap_realign_plan finds them; MHAP_E_INVALID, naming the record, for an id not among read_ids, an alen or
+ * blen that disagrees with the read's length, a paths object of another n, or runs that are not a path between (a1, the first column)
+ * and (a2, the last) beginning and ending with '='; a refused call has cast no vote.  mhap_correct_finish makes the call for every
+ * read on the device (min_cov >= 1) and returns out_offsets (read r's corrected bytes are [out_offsets[r], out_offsets[r + 1]) of the
+ * output), the six counts per read and the views skipped so far; it may be repeated, and more records may be added after it.
+ * mhap_correct_copy writes the out_offsets[n_reads] bytes of the last finish.  Votes cross to the host only through
+ * mhap_correct_votes: the 24 counters of every position of read read_index (its position in read_ids), position-major, in the order
+ * base A C G T, del, span, ins[0] A C G T, ins[1] .., ins[2] .., ins[3] .., and the two spare ones, which stay 0. */
+typedef struct mhap_correct_session mhap_correct_session;
+int mhap_correct_begin(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const int64_t* read_ids, const int64_t* offsets,
+                       const int32_t* lengths, int64_t n_reads, mhap_correct_session** session);
+int mhap_correct_add(mhap_correct_session* s, const mhap_record* realigned, int64_t n, const mhap_align_paths* paths);
+int mhap_correct_finish(mhap_correct_session* s, int32_t min_cov, int64_t* out_offsets /* n_reads + 1 */, int32_t* stats /* n_reads x 6 */,
+                        int64_t* skipped_views);
+int mhap_correct_copy(mhap_correct_session* s, uint8_t* bytes);
+int mhap_correct_votes(mhap_correct_session* s, int64_t read_index, uint16_t* counters /* length x 24 */);
+void mhap_correct_free(mhap_correct_session* s);
+
 /* KmerStatSimulator's pair statistics on the GPU (J/main/KmerStatSimulator.java:163-196).  pairs: n rows of 4 int64 {a_off, a_len,
  * b_off, b_len}; a = bases[a_off, a_off + a_len) is the first read, b the second.  skip: n_skip k-mers of k bytes each, back to back, in
  * any order (the skip set of loadSkipMers; entries of another length never match and are left out by the caller).  For each pair,

@@ -28,6 +28,8 @@ from .api import (  # noqa: F401
     realign_records_paths,
     cigar_string,
     format_paf,
+    CorrectSession,
+    correct_reads,
     pair_kmer_stats,
     records_to_lines,
     load_library,

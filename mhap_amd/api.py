@@ -73,7 +73,8 @@ EXPORTED_SYMBOLS = [
     "mhap_synth_truth", "mhap_align_pairs",
     "mhap_align_pairs_banded", "mhap_realign_plan", "mhap_realign_plan_error", "mhap_realign_records",
     "mhap_align_pairs_banded_paths", "mhap_realign_records_paths", "mhap_align_paths_info", "mhap_align_paths_copy", "mhap_align_paths_free",
-    "mhap_format_paf",
+    "mhap_format_paf", "mhap_align_paths_from_runs",
+    "mhap_correct_begin", "mhap_correct_add", "mhap_correct_finish", "mhap_correct_copy", "mhap_correct_votes", "mhap_correct_free",
     "mhap_pair_kmer_stats", "mhap_pair_kmer_stats_paths", "mhap_ksim_create", "mhap_ksim_next", "mhap_ksim_error", "mhap_ksim_destroy",
     "mhap_ksim_dev_create", "mhap_ksim_dev_destroy", "mhap_ksim_dev_pair_stats", "mhap_ksim_dev_trials",
 ]
@@ -156,6 +157,14 @@ def load_library(build_if_missing=True):
     lib.mhap_align_paths_free.restype = None
     lib.mhap_align_paths_free.argtypes = [C.c_void_p]
     lib.mhap_format_paf.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t]
+    lib.mhap_align_paths_from_runs.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.mhap_correct_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.mhap_correct_add.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.mhap_correct_finish.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mhap_correct_copy.argtypes = [C.c_void_p, C.c_void_p]
+    lib.mhap_correct_votes.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+    lib.mhap_correct_free.restype = None
+    lib.mhap_correct_free.argtypes = [C.c_void_p]
     for name in EXPORTED_SYMBOLS:
         getattr(lib, name)  # AttributeError here = header/library mismatch
     # a stale library next to newer host code (or the reverse) must not get as far as a struct copy
@@ -508,6 +517,110 @@ def format_paf(record, detail, ops, qname=None, tname=None):
     if n < 0 or n >= cap:
         raise MhapError("mhap_format_paf failed")
     return buf.value.decode()
+
+
+CORRECT_STATS = ("len_in", "len_out", "n_sub", "n_del", "n_ins", "n_low")   # the six counts per read of a correction
+CORRECT_COUNTERS = 24   # per position: base A C G T, del, span, ins[k][A C G T] for k = 0 .. 3, two spare
+
+
+class CorrectSession:
+    """Read correction on the GPU (mhap_correct_begin / _add / _finish / _votes; the contract is the "read correction" section of
+    include/mhap_hip.h): every realigned overlap votes column by column on both of its reads, and each position takes the majority.
+    The vote table (48 bytes per base) stays on the device from begin to close.
+
+        with CorrectSession(fasta) as cs:
+            cs.add(records, op_offsets, ops)          # what realign_records_paths returned; any number of times
+            seqs, stats, skipped = cs.finish(min_cov=4)
+
+    handle: a MinHashSearch whose device and stream to use (else one is made and closed with the session)."""
+
+    def __init__(self, fasta, query_fasta=None, handle=None, device=0):
+        self._own = handle is None
+        self._ms = MinHashSearch(MhapParams(num_hashes=1, ordered_sketch_size=1, device=device)) if self._own else handle
+        self._lib = self._ms._lib
+        self._s = C.c_void_p()
+        bases, ids, offsets, lengths = _all_reads(fasta, query_fasta)
+        self._bases = np.ascontiguousarray(bases, np.uint8)
+        self.ids, self._offsets = np.ascontiguousarray(ids, np.int64), np.ascontiguousarray(offsets, np.int64)
+        self.lengths = np.ascontiguousarray(lengths, np.int32)
+        try:
+            self._ms._chk(self._lib.mhap_correct_begin(self._ms._h, _ptr(self._bases), C.c_int64(len(self._bases)), _ptr(self.ids),
+                                                       _ptr(self._offsets), _ptr(self.lengths), C.c_int64(len(self.ids)), C.byref(self._s)))
+        except Exception:
+            if self._own:
+                self._ms.close()
+            raise
+
+    @classmethod
+    def begin(cls, fasta, query_fasta=None, handle=None, device=0):
+        """The constructor under the C entry point's name: the bases go up and the vote table is zeroed."""
+        return cls(fasta, query_fasta=query_fasta, handle=handle, device=device)
+
+    def add(self, records, op_offsets, ops):
+        """The votes of realigned records and their runs (pair q's are ops[op_offsets[q]:op_offsets[q + 1]])."""
+        records = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
+        op_offsets = np.ascontiguousarray(op_offsets, dtype=np.int64)
+        ops = np.ascontiguousarray(ops, dtype=np.uint32)
+        if len(op_offsets) != len(records) + 1:
+            raise MhapError(f"CorrectSession.add: {len(records)} records need {len(records) + 1} run offsets, not {len(op_offsets)}")
+        obj = C.c_void_p()
+        if self._lib.mhap_align_paths_from_runs(_ptr(op_offsets), C.c_int64(len(records)), _ptr(ops) if len(ops) else None, C.byref(obj)) != 0:
+            raise MhapError("CorrectSession.add: op_offsets is not a list of run offsets over ops")
+        try:
+            self._ms._chk(self._lib.mhap_correct_add(self._s, _ptr(records) if len(records) else None, C.c_int64(len(records)), obj))
+        finally:
+            self._lib.mhap_align_paths_free(obj)
+
+    def finish(self, min_cov=4):
+        """(seqs, stats, skipped_views): the corrected bytes of every read, an int32 array (n, 6) of CORRECT_STATS, and the views the
+        65 535-per-target cap has skipped so far.  `offsets` and `bytes` keep the flat form: read r is bytes[offsets[r]:offsets[r + 1]]."""
+        n = len(self.ids)
+        self.offsets = np.zeros(n + 1, np.int64)
+        stats = np.zeros((n, 6), np.int32)
+        skipped = C.c_int64(0)
+        self._ms._chk(self._lib.mhap_correct_finish(self._s, C.c_int32(min_cov), _ptr(self.offsets), _ptr(stats) if n else None, C.byref(skipped)))
+        self.bytes = np.zeros(int(self.offsets[n]), np.uint8)
+        self._ms._chk(self._lib.mhap_correct_copy(self._s, _ptr(self.bytes) if len(self.bytes) else None))
+        raw = self.bytes.tobytes()
+        return [raw[int(self.offsets[r]):int(self.offsets[r + 1])] for r in range(n)], stats, int(skipped.value)
+
+    def votes(self, read_index):
+        """The raw counters of one read: a uint16 array (length, CORRECT_COUNTERS)."""
+        if not 0 <= read_index < len(self.ids):
+            raise MhapError(f"CorrectSession.votes: read {read_index} is not among the {len(self.ids)} reads")
+        out = np.zeros((int(self.lengths[read_index]), CORRECT_COUNTERS), np.uint16)
+        self._ms._chk(self._lib.mhap_correct_votes(self._s, C.c_int64(read_index), _ptr(out) if len(out) else None))
+        return out
+
+    def table_bytes(self):
+        return 48 * int(self.lengths.astype(np.int64).sum())
+
+    def close(self):
+        if self._s:
+            self._lib.mhap_correct_free(self._s)
+            self._s = C.c_void_p()
+            if self._own:
+                self._ms.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def correct_reads(records, fasta, op_offsets, ops, min_cov=4, query_fasta=None, handle=None, device=0):
+    """Correct every read of `fasta` (and `query_fasta`) from realigned records and their runs, as realign_records_paths returned them:
+    (seqs, stats, skipped_views) of CorrectSession.finish."""
+    with CorrectSession(fasta, query_fasta=query_fasta, handle=handle, device=device) as cs:
+        cs.add(records, op_offsets, ops)
+        return cs.finish(min_cov)
 
 
 def _skip_bytes(skip, k):

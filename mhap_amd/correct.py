@@ -1,0 +1,97 @@
+"""Correct reads on the GPU from a file of MHAP overlaps: `python -m mhap_amd.correct overlaps.txt reads.fasta [queries.fasta] [--band W]
+[--min-identity X] [--min-coverage N] [-o out.fasta]` writes what `mhap-hip --realign --correct out.fasta` writes for the same overlaps.
+
+The overlaps are parsed and realigned as `python -m mhap_amd.realign` does, with every alignment's path; the records that tool would
+drop (no alignment, or an identity below --min-identity) cast no vote.  Every other record votes column by column on both of its reads
+(api.CorrectSession; the contract is the "read correction" section of include/mhap_hip.h) and each read position takes the majority.
+Output is FASTA, one unwrapped line per read: `>ID len=<corrected length> sub=<substitutions> del=<deletions> ins=<insertions>
+low=<positions below --min-coverage>`, the ids numeric as the records print them; one line on stderr gives the totals.
+"""
+import argparse
+import sys
+
+import numpy as np
+
+from . import api
+from .realign import kept_rows, read_overlaps
+
+BATCH = 1 << 16   # records realigned and voted per call
+
+
+def select_paths(op_offsets, ops, rows):
+    """(op_offsets, ops) of the pairs `rows` of a paths result, in that order."""
+    rows = np.asarray(rows, dtype=np.int64)
+    lens = (op_offsets[rows + 1] - op_offsets[rows]) if len(rows) else np.zeros(0, np.int64)
+    out = np.zeros(len(rows) + 1, np.int64)
+    np.cumsum(lens, out=out[1:])
+    parts = [ops[op_offsets[q]:op_offsets[q + 1]] for q in rows.tolist()]
+    return out, (np.concatenate(parts).astype(np.uint32) if parts else np.zeros(0, np.uint32))
+
+
+def format_fasta(names, seqs, stats):
+    """The corrected reads as FASTA text: `>NAME len= sub= del= ins= low=` and the bases on one line, per read."""
+    out = []
+    for name, seq, st in zip(names, seqs, np.asarray(stats).tolist()):
+        out.append(f">{name} len={st[1]} sub={st[2]} del={st[3]} ins={st[4]} low={st[5]}\n{bytes(seq).decode('latin-1')}\n")
+    return "".join(out)
+
+
+def totals_line(stats, skipped_views):
+    """The one stderr line of a correction (the driver prints the same)."""
+    t = np.asarray(stats, dtype=np.int64).reshape(-1, 6).sum(axis=0).tolist()
+    return (f"Corrected {len(stats)} reads: {t[0]} bases in, {t[1]} out; {t[2]} substitutions, {t[3]} deletions, {t[4]} insertions, "
+            f"{t[5]} positions of low coverage; skipped_views = {skipped_views}")
+
+
+def correct_overlaps(recs, fasta, queries=None, band=0, max_shift=0.2, min_identity=0.0, min_cov=4, device=0, batch=BATCH):
+    """Realign `recs` with paths in batches and vote: (seqs, stats, skipped_views, records that voted)."""
+    voted = 0
+    with api.MinHashSearch(api.MhapParams(num_hashes=1, ordered_sketch_size=1, max_shift=max_shift, device=device)) as ms:
+        with api.CorrectSession(fasta, query_fasta=queries, handle=ms) as cs:
+            for q0 in range(0, len(recs), batch):
+                out, _, op_offsets, ops = api.realign_records_paths(recs[q0:q0 + batch], fasta, band=band, handle=ms, query_fasta=queries)
+                rows = kept_rows(out, min_identity)
+                ko, kops = select_paths(op_offsets, ops, rows)
+                cs.add(out[rows], ko, kops)
+                voted += len(rows)
+            seqs, stats, skipped = cs.finish(min_cov)
+            ids = cs.ids.tolist()
+    return ids, seqs, stats, skipped, voted
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m mhap_amd.correct", description=__doc__.split("\n\n")[0])
+    ap.add_argument("overlaps")
+    ap.add_argument("reads")
+    ap.add_argument("queries", nargs="?")
+    ap.add_argument("--band", type=int, default=0, help="half-width of the band in bases; 0: the overlap's length times --max-shift")
+    ap.add_argument("--max-shift", type=float, default=0.2)
+    ap.add_argument("--min-identity", type=float, default=0.0, help="overlaps realigned below this identity cast no vote")
+    ap.add_argument("--min-coverage", type=int, default=4, help="votes a position needs before it is changed (min_cov)")
+    ap.add_argument("--query-id-offset", type=int, default=None)
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("-o", "--output", default=None, help="the FASTA file to write (default: stdout)")
+    a = ap.parse_args(argv)
+    if a.band < 0:
+        ap.error("--band must be >= 0")
+    if a.min_coverage < 1:
+        ap.error("--min-coverage must be >= 1")
+    recs = read_overlaps(a.overlaps)
+    fasta = api.FastaData.from_file(a.reads)
+    queries = api.FastaData.from_file(a.queries, len(fasta) if a.query_id_offset is None else a.query_id_offset) if a.queries else None
+    ids, seqs, stats, skipped, voted = correct_overlaps(recs, fasta, queries, band=a.band, max_shift=a.max_shift, min_identity=a.min_identity,
+                                                        min_cov=a.min_coverage, device=a.device)
+    text = format_fasta(ids, seqs, stats)
+    if a.output:
+        with open(a.output, "w") as fh:
+            fh.write(text)
+    else:
+        sys.stdout.write(text)
+    print(f"Realigned {len(recs)} overlaps: {voted} voted, {len(recs) - voted} dropped (no alignment or identity below {a.min_identity:g})",
+          file=sys.stderr)
+    print(totals_line(stats, skipped), file=sys.stderr)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,0 +1,462 @@
+// correct_kernels.hip — read correction: a pile-up vote over every read from the realigned overlaps' paths and a majority call per
+// position (mhap_correct_begin / _add / _finish / _copy / _votes / _free).  The contract — the two views of a record, the 22 counters,
+// the 65 535-view cap and the call — is the prose of include/mhap_hip.h ("read correction"); tests/consensus_ref.py restates it.
+//
+// The vote table.  24 counters of 16 bits per base, two to a word: 12 words per base, kept as 12 planes per read — word p of position t
+// of a read of length L that starts at table position v is table[12 v + p L + t] — so that the lanes of a wave, which take consecutive
+// columns of a path and with them consecutive target positions, add to consecutive words of a plane.  Counter c (the order of
+// mhap_correct_votes) is the low (c even) or high (c odd) half of word c / 2:
+//   word 0 base A | C    word 1 base G | T    word 2 del | span    words 3 + 2 k, 4 + 2 k ins[k] A | C, G | T    word 11 spare
+// A vote is atomicAdd(word, 1) or atomicAdd(word, 1 << 16); the host's cap on accepted views per target keeps every half below 2^16,
+// so no add carries into its neighbour.  Position-major words (one 48-byte row per base) would put a wave's adds 48 bytes apart.
+// Integer atomic rates on this chip are not measured; the layout follows from the shape the float-atomic measurements prefer.
+//
+// vote_kernel: one wave per accepted (record, view).  The runs go through 64 at a time: lane l takes run l of the chunk, the lanes
+// scan the run lengths (rows consumed, columns consumed, columns of the path) to get every run's first (i, j) and first path column,
+// and leave them in LDS; then the chunk's path columns are dealt to the lanes 64 at a time, each lane finding its run by a binary
+// search over the 64 starts.  An Ins group's t and k come from its run's start (and its length, in the reversed view), never from a
+// neighbouring lane.  The reversed view of a to_rc record is not walked backwards: votes are sums, so only what depends on the
+// order is turned round — t -> blen - 1 - t, the complement, the end of the view at which no span is counted, the side of an Ins
+// group its target position lies on and the direction k counts in.
+//
+// call_kernel: one workgroup per read, 256 positions at a time: every thread decides its position (0 to 5 bytes), the workgroup scans
+// the emitted lengths, and in the second of two launches writes the bytes.  The first launch leaves the six counts per read; the reads'
+// output offsets are the prefix sums of their len_out, made on the host, which returns them anyway.
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "device_common.hpp"
+#include "mhap_internal.hpp"
+
+namespace mhap {
+namespace {
+
+constexpr uint32_t OP_I = 1, OP_D = 2, OP_EQ = 7, OP_X = 8;   // BAM's codes (realign_kernels.hip)
+constexpr int CK_WORDS = 12;          // words per position: 24 counters of 16 bits
+constexpr int CK_KI = 4;              // inserted bytes voted on per junction
+constexpr uint32_t CK_CAP = 65535;    // accepted views per target
+constexpr int CK_T = 256;             // threads of the call kernel
+
+// one accepted view of one record
+struct VoteItem {
+  int64_t a_off, b_off;     // first stored byte of read A, of read B
+  int64_t v_words;          // first word of the target's planes
+  int64_t ops_off;          // the record's runs in the uploaded ops
+  int32_t alen, blen;
+  int32_t i0, j0;           // first row of s1, first column of s2 (in the aligner's orientation)
+  int32_t n_ops;
+  int32_t view;             // 0: target A; 1: target B
+  int32_t rc;               // s2 is the reverse complement of read B
+  int32_t pad;
+};
+
+__device__ inline int base_code(uint32_t c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1; }
+
+__device__ inline void vote(uint32_t* __restrict__ table, int64_t v_words, int tlen, int t, int counter) {
+  if ((unsigned)t >= (unsigned)tlen) return;   // (add validated the path: never taken)
+  atomicAdd(table + v_words + (int64_t)(counter >> 1) * tlen + t, (counter & 1) ? 0x10000u : 1u);
+}
+
+__global__ __launch_bounds__(64) void vote_kernel(const uint8_t* __restrict__ bases, const VoteItem* __restrict__ items,
+                                                  const uint32_t* __restrict__ ops, uint32_t* __restrict__ table) {
+  __shared__ int s_col[65], s_i[64], s_j[64];
+  __shared__ uint32_t s_op[64];
+  const VoteItem it = items[blockIdx.x];
+  const int lane = threadIdx.x;
+  const uint32_t* runs = ops + it.ops_off;
+  const bool target_b = it.view != 0, rev = target_b && it.rc != 0;
+  const int tlen = target_b ? it.blen : it.alen;
+  int ci = it.i0, cj = it.j0;   // (i, j) of the first column of the chunk's first run
+  for (int r0 = 0; r0 < it.n_ops; r0 += 64) {
+    const int idx = r0 + lane;
+    const uint32_t op = idx < it.n_ops ? runs[idx] : 0u;
+    const int len = (int)(op >> 4);
+    const uint32_t code = op & 15u;
+    const int di = (code == OP_EQ || code == OP_X || code == OP_I) ? len : 0;
+    const int dj = (code == OP_EQ || code == OP_X || code == OP_D) ? len : 0;
+    int si = di, sj = dj, sc = len;   // inclusive scans over the lanes
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int ui = __shfl_up(si, d), uj = __shfl_up(sj, d), uc = __shfl_up(sc, d);
+      if (lane >= d) { si += ui; sj += uj; sc += uc; }
+    }
+    __syncthreads();   // the previous chunk's columns are done with the arrays
+    s_op[lane] = op; s_i[lane] = ci + si - di; s_j[lane] = cj + sj - dj; s_col[lane] = sc - len;
+    if (lane == 63) s_col[64] = sc;
+    __syncthreads();
+    ci += __shfl(si, 63); cj += __shfl(sj, 63);
+    const int total = s_col[64];
+    for (int x = lane; x < total; x += 64) {
+      int lo = 0, hi = 63;   // the last run of the chunk that starts at or before column x (runs of length 0 are padding at the end)
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (s_col[mid] <= x) lo = mid; else hi = mid - 1;
+      }
+      // (several runs cannot start at one column except the padding, which starts at `total` > x)
+      const uint32_t rop = s_op[lo];
+      const int rlen = (int)(rop >> 4), c = x - s_col[lo], ridx = r0 + lo;
+      const uint32_t rcode = rop & 15u;
+      const bool diag = rcode == OP_EQ || rcode == OP_X;
+      const int i = s_i[lo] + ((diag || rcode == OP_I) ? c : 0), j = s_j[lo] + ((diag || rcode == OP_D) ? c : 0);
+      const bool consumes_target = diag || rcode == (target_b ? OP_D : OP_I);
+      if (consumes_target) {
+        const int t = !target_b ? i : rev ? it.blen - 1 - j : j;
+        if (diag) {
+          uint32_t e = target_b ? (uint32_t)bases[it.a_off + i]
+                                : (it.rc ? rc_char(bases[it.b_off + (it.blen - 1 - j)]) : (uint32_t)bases[it.b_off + j]);
+          if (rev) e = rc_char(e);
+          const int b = base_code(e);
+          if (b >= 0) vote(table, it.v_words, tlen, t, b);
+        } else {
+          vote(table, it.v_words, tlen, t, 4);
+        }
+        // the view continues past t unless this is its last column: the path's last, or its first in the reversed view
+        const bool view_end = rev ? (ridx == 0 && c == 0) : (ridx == it.n_ops - 1 && c == rlen - 1);
+        if (!view_end) vote(table, it.v_words, tlen, t, 5);
+      } else {
+        // an Ins column: the group is this run (a run split at 2^28 - 1 columns continues a group whose first four slots are taken)
+        const int k = rev ? rlen - 1 - c : c;
+        if (k < CK_KI) {
+          const int nb = rev ? ridx + 1 : ridx - 1;
+          const bool split = nb >= 0 && nb < it.n_ops && (runs[nb] & 15u) == rcode;
+          if (!split) {
+            // the target position before the group in the view's order: the row / column consumed last, or next in the reversed view
+            const int t = !target_b ? s_i[lo] - 1 : rev ? it.blen - 1 - s_j[lo] : s_j[lo] - 1;
+            uint32_t e = target_b ? (uint32_t)bases[it.a_off + i]
+                                  : (it.rc ? rc_char(bases[it.b_off + (it.blen - 1 - j)]) : (uint32_t)bases[it.b_off + j]);
+            if (rev) e = rc_char(e);
+            const int b = base_code(e);
+            if (b >= 0) vote(table, it.v_words, tlen, t, 6 + 4 * k + b);
+          }
+        }
+      }
+    }
+  }
+}
+
+// the decision for one position: the bytes it emits (at most 1 + CK_KI) and what it counts
+struct Decision { int n; uint8_t bytes[1 + CK_KI]; int sub, del, ins, low; };
+
+__device__ inline Decision decide(const uint32_t* __restrict__ w, int64_t len, int64_t t, uint32_t own, int min_cov) {
+  Decision D{0, {0, 0, 0, 0, 0}, 0, 0, 0, 0};
+  const uint32_t w0 = w[t], w1 = w[len + t], w2 = w[2 * len + t];
+  int base[4] = {(int)(w0 & 0xFFFFu), (int)(w0 >> 16), (int)(w1 & 0xFFFFu), (int)(w1 >> 16)};
+  const int del = (int)(w2 & 0xFFFFu), span = (int)(w2 >> 16);
+  const int d = base[0] + base[1] + base[2] + base[3] + del;
+  if (d < min_cov) {
+    D.bytes[D.n++] = (uint8_t)own; D.low = 1;
+  } else {
+    const int ob = base_code(own);
+    if (ob >= 0) base[ob] += 1;
+    const int total = d + 1;
+    if (2 * del > total) D.del = 1;
+    else {
+      int best = 0;
+      for (int b = 1; b < 4; b++) if (base[b] > base[best]) best = b;
+      uint32_t out;
+      if (base[best] == 0 || (ob >= 0 && base[ob] == base[best])) out = own;
+      else out = (0x54474341u >> (8 * best)) & 0xFFu;   // "ACGT"
+      D.bytes[D.n++] = (uint8_t)out;
+      D.sub = out != own;
+    }
+  }
+  if (t < len - 1 && span >= min_cov) {
+    for (int k = 0; k < CK_KI; k++) {
+      const uint32_t x0 = w[(3 + 2 * k) * len + t], x1 = w[(4 + 2 * k) * len + t];
+      const int v[4] = {(int)(x0 & 0xFFFFu), (int)(x0 >> 16), (int)(x1 & 0xFFFFu), (int)(x1 >> 16)};
+      int best = 0;
+      for (int b = 1; b < 4; b++) if (v[b] > v[best]) best = b;
+      if (2 * v[best] <= span + 1) break;
+      D.bytes[D.n++] = (uint8_t)((0x54474341u >> (8 * best)) & 0xFFu);
+      D.ins += 1;
+    }
+  }
+  return D;
+}
+
+// reads: per read {offset in bases, first table position}; lengths; out_offsets == nullptr: count only (stats), else write the bytes
+__global__ __launch_bounds__(CK_T) void call_kernel(const uint8_t* __restrict__ bases, const int64_t* __restrict__ read_off,
+                                                    const int64_t* __restrict__ read_pos, const int32_t* __restrict__ lengths,
+                                                    const uint32_t* __restrict__ table, int min_cov, const int64_t* __restrict__ out_offsets,
+                                                    uint8_t* __restrict__ out, int32_t* __restrict__ stats) {
+  __shared__ int wave_sum[CK_T / 64];
+  __shared__ int acc[5];   // len_out, n_sub, n_del, n_ins, n_low
+  const int64_t r = blockIdx.x;
+  const int64_t len = lengths[r];
+  const uint8_t* own = bases + read_off[r];
+  const uint32_t* w = table + (int64_t)CK_WORDS * read_pos[r];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid < 5) acc[tid] = 0;
+  int64_t written = 0;   // bytes emitted by the tiles before this one
+  int my[5] = {0, 0, 0, 0, 0};
+  for (int64_t t0 = 0; t0 < len; t0 += CK_T) {
+    const int64_t t = t0 + tid;
+    Decision D{0, {0, 0, 0, 0, 0}, 0, 0, 0, 0};
+    if (t < len) D = decide(w, len, t, own[t], min_cov);
+    my[0] += D.n; my[1] += D.sub; my[2] += D.del; my[3] += D.ins; my[4] += D.low;
+    int incl = D.n;   // inclusive scan of the emitted lengths over the workgroup
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int u = __shfl_up(incl, d);
+      if (lane >= d) incl += u;
+    }
+    __syncthreads();   // wave_sum of the previous tile has been read
+    if (lane == 63) wave_sum[wave] = incl;
+    __syncthreads();
+    int before = 0, tile = 0;
+    for (int u = 0; u < CK_T / 64; u++) { if (u < wave) before += wave_sum[u]; tile += wave_sum[u]; }
+    if (out_offsets) {
+      uint8_t* o = out + out_offsets[r] + written + before + (incl - D.n);
+      for (int u = 0; u < D.n; u++) o[u] = D.bytes[u];
+    }
+    written += tile;
+  }
+  __syncthreads();
+  for (int u = 0; u < 5; u++) if (my[u]) atomicAdd(&acc[u], my[u]);
+  __syncthreads();
+  if (tid == 0 && !out_offsets) {
+    int32_t* s = stats + 6 * r;
+    s[0] = (int32_t)len; s[1] = acc[0]; s[2] = acc[1]; s[3] = acc[2]; s[4] = acc[3]; s[5] = acc[4];
+  }
+}
+
+}  // namespace
+}  // namespace mhap
+
+using namespace mhap;
+
+struct mhap_correct_session {
+  mhap_handle* h = nullptr;
+  int64_t n_reads = 0, n_bases = 0, n_pos = 0;          // n_pos: bases of the reads = positions of the table
+  std::vector<int64_t> offsets, pos;                    // read r: its bytes in the bases, its first table position
+  std::vector<int32_t> lengths;
+  std::unordered_map<int64_t, int64_t> by_id;
+  std::vector<uint32_t> views;                          // accepted views per target
+  int64_t skipped = 0, out_bytes = -1;                  // out_bytes < 0: no finish yet
+  DevBuf bases, table, read_off, read_pos, read_len, items, ops, out_off, out, stats;
+  void release() {
+    bases.release(); table.release(); read_off.release(); read_pos.release(); read_len.release(); items.release(); ops.release();
+    out_off.release(); out.release(); stats.release();
+  }
+};
+
+namespace {
+
+int hip_fail(const HandleView& v, const char* who, const char* what, hipError_t e) {
+  *v.err = std::string(who) + ": " + what + ": " + hipGetErrorString(e);
+  return MHAP_E_HIP;
+}
+
+}  // namespace
+
+extern "C" int mhap_correct_begin(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const int64_t* read_ids, const int64_t* offsets,
+                                  const int32_t* lengths, int64_t n_reads, mhap_correct_session** session) {
+  const char* who = "mhap_correct_begin";
+  if (session) *session = nullptr;
+  if (!h) return MHAP_E_INVALID;
+  HandleView v = handle_view(h);
+  if (!session || n_bases < 0 || n_reads < 0 || (n_bases > 0 && !bases) || (n_reads > 0 && (!read_ids || !offsets || !lengths))) {
+    *v.err = std::string(who) + ": null or negative argument";
+    return MHAP_E_INVALID;
+  }
+  for (int64_t i = 0; i < n_reads; i++)
+    if (offsets[i] < 0 || lengths[i] < 0 || offsets[i] > n_bases - lengths[i]) {
+      *v.err = std::string(who) + ": read " + std::to_string(i) + " lies outside the " + std::to_string(n_bases) + " bases";
+      return MHAP_E_INVALID;
+    }
+  mhap_correct_session* s = new mhap_correct_session();
+  s->h = h; s->n_reads = n_reads; s->n_bases = n_bases;
+  s->offsets.assign(offsets, offsets + n_reads);
+  s->lengths.assign(lengths, lengths + n_reads);
+  s->pos.resize((size_t)n_reads);
+  s->views.assign((size_t)n_reads, 0u);
+  s->by_id.reserve((size_t)n_reads * 2);
+  for (int64_t i = 0; i < n_reads; i++) {
+    s->by_id.emplace(read_ids[i], i);   // (the first read of an id wins, as in mhap_realign_plan)
+    s->pos[(size_t)i] = s->n_pos;
+    s->n_pos += lengths[i];
+  }
+  (void)hipSetDevice(v.device);
+  hipError_t e = hipSuccess;
+  const size_t table_bytes = (size_t)std::max<int64_t>(s->n_pos, 1) * CK_WORDS * 4, rb = (size_t)std::max<int64_t>(n_reads, 1);
+  auto up = [&](DevBuf& b, const void* src, size_t bytes) {
+    if (e == hipSuccess) e = b.ensure(std::max<size_t>(bytes, 1));
+    if (e == hipSuccess && bytes > 0) e = hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, v.stream);
+  };
+  up(s->bases, bases, (size_t)n_bases);
+  up(s->read_off, s->offsets.data(), 8 * (size_t)n_reads);
+  up(s->read_pos, s->pos.data(), 8 * (size_t)n_reads);
+  up(s->read_len, s->lengths.data(), 4 * (size_t)n_reads);
+  if (e == hipSuccess) e = s->stats.ensure(24 * rb);
+  if (e == hipSuccess) e = s->out_off.ensure(8 * (rb + 1));
+  if (e == hipSuccess) e = s->table.ensure(table_bytes);
+  if (e == hipSuccess) e = hipMemsetAsync(s->table.p, 0, table_bytes, v.stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(v.stream);
+  if (e != hipSuccess) {
+    s->release();
+    delete s;
+    return hip_fail(v, who, "the vote table (48 bytes per base) and the bases", e);
+  }
+  *session = s;
+  return MHAP_OK;
+}
+
+extern "C" int mhap_correct_add(mhap_correct_session* s, const mhap_record* recs, int64_t n, const mhap_align_paths* paths) {
+  const char* who = "mhap_correct_add";
+  if (!s) return MHAP_E_INVALID;
+  HandleView v = handle_view(s->h);
+  if (n < 0 || !paths || (n > 0 && !recs)) { *v.err = std::string(who) + ": null or negative argument"; return MHAP_E_INVALID; }
+  if ((int64_t)paths->offsets.size() - 1 != n) {
+    *v.err = std::string(who) + ": the paths are those of " + std::to_string((int64_t)paths->offsets.size() - 1) + " records, not of " + std::to_string(n);
+    return MHAP_E_INVALID;
+  }
+  auto bad = [&](int64_t q, const std::string& what) {
+    *v.err = std::string(who) + ": record " + std::to_string(q) + " " + what;
+    return MHAP_E_INVALID;
+  };
+  std::vector<VoteItem> items;
+  std::vector<std::pair<int64_t, int>> accepted;   // (target read, views) to take back when a later record is refused
+  int64_t skipped = 0;
+  auto undo = [&]() { for (auto& a : accepted) s->views[(size_t)a.first] -= (uint32_t)a.second; };
+  for (int64_t q = 0; q < n; q++) {
+    const mhap_record& r = recs[q];
+    const int64_t o0 = paths->offsets[(size_t)q], o1 = paths->offsets[(size_t)q + 1];
+    if (o1 == o0 || r.from_id == r.to_id) continue;
+    int64_t idx[2];
+    const int64_t ids[2] = {r.from_id, r.to_id};
+    const int32_t lens[2] = {r.alen, r.blen};
+    for (int f = 0; f < 2; f++) {
+      const auto it = s->by_id.find(ids[f]);
+      if (it == s->by_id.end()) { undo(); return bad(q, "names read " + std::to_string(ids[f]) + ", which is not among the reads"); }
+      idx[f] = it->second;
+      if (s->lengths[(size_t)idx[f]] != lens[f]) {
+        undo();
+        return bad(q, "gives read " + std::to_string(ids[f]) + " the length " + std::to_string(lens[f]) + ", the reads say " +
+                          std::to_string(s->lengths[(size_t)idx[f]]));
+      }
+    }
+    // the runs are a path from (a1, j0) to (a2, j1), '=' at both ends
+    const bool rc = r.to_rc != 0;
+    const int64_t i0 = r.a1, j0 = rc ? (int64_t)r.blen - r.b2 - 1 : r.b1, j1 = rc ? (int64_t)r.blen - r.b1 - 1 : r.b2;
+    int64_t rows = 0, cols = 0;
+    bool ok = o1 - o0 <= INT32_MAX && (paths->ops[(size_t)o0] & 15u) == OP_EQ && (paths->ops[(size_t)o1 - 1] & 15u) == OP_EQ;
+    for (int64_t u = o0; u < o1 && ok; u++) {
+      const uint32_t op = paths->ops[(size_t)u], code = op & 15u;
+      const int64_t len = op >> 4;
+      if (len < 1 || (code != OP_EQ && code != OP_X && code != OP_I && code != OP_D)) ok = false;
+      if (code != OP_D) rows += len;
+      if (code != OP_I) cols += len;
+    }
+    ok = ok && i0 >= 0 && j0 >= 0 && r.a2 < r.alen && j1 < r.blen && rows == (int64_t)r.a2 - i0 + 1 && cols == j1 - j0 + 1;
+    if (!ok) { undo(); return bad(q, "has runs that are not a path between its aligned ends"); }
+    for (int view = 0; view < 2; view++) {
+      const int64_t target = idx[view];
+      if (s->views[(size_t)target] >= CK_CAP) { skipped++; continue; }
+      s->views[(size_t)target] += 1;
+      accepted.emplace_back(target, 1);
+      VoteItem it{};
+      it.a_off = s->offsets[(size_t)idx[0]]; it.b_off = s->offsets[(size_t)idx[1]];
+      it.v_words = (int64_t)CK_WORDS * s->pos[(size_t)target];
+      it.ops_off = o0; it.alen = r.alen; it.blen = r.blen; it.i0 = (int32_t)i0; it.j0 = (int32_t)j0;
+      it.n_ops = (int32_t)(o1 - o0); it.view = view; it.rc = rc ? 1 : 0;
+      items.push_back(it);
+    }
+  }
+  s->skipped += skipped;
+  if (items.empty()) return MHAP_OK;
+  (void)hipSetDevice(v.device);
+  hipError_t e;
+  // a grid of at most 2^20 views at a time: the items of one launch are 64 MB
+  constexpr size_t CHUNK = (size_t)1 << 20;
+  if ((e = s->ops.ensure(4 * paths->ops.size())) != hipSuccess) return hip_fail(v, who, "hipMalloc of the runs", e);
+  if ((e = s->items.ensure(sizeof(VoteItem) * std::min(items.size(), CHUNK))) != hipSuccess) return hip_fail(v, who, "hipMalloc", e);
+  if ((e = hipMemcpyAsync(s->ops.p, paths->ops.data(), 4 * paths->ops.size(), hipMemcpyHostToDevice, v.stream)) != hipSuccess) return hip_fail(v, who, "upload", e);
+  for (size_t g0 = 0; g0 < items.size(); g0 += CHUNK) {
+    const size_t c = std::min(CHUNK, items.size() - g0);
+    if ((e = hipMemcpyAsync(s->items.p, items.data() + g0, sizeof(VoteItem) * c, hipMemcpyHostToDevice, v.stream)) != hipSuccess) return hip_fail(v, who, "upload", e);
+    hipLaunchKernelGGL(vote_kernel, dim3((unsigned)c), dim3(64), 0, v.stream, s->bases.as<uint8_t>(), s->items.as<VoteItem>(),
+                       s->ops.as<uint32_t>(), s->table.as<uint32_t>());
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(v, who, "launch", e);
+    if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return hip_fail(v, who, "kernel", e);   // (items is reused by the next chunk)
+  }
+  return MHAP_OK;
+}
+
+extern "C" int mhap_correct_finish(mhap_correct_session* s, int32_t min_cov, int64_t* out_offsets, int32_t* stats, int64_t* skipped_views) {
+  const char* who = "mhap_correct_finish";
+  if (!s) return MHAP_E_INVALID;
+  HandleView v = handle_view(s->h);
+  if (!out_offsets || (s->n_reads > 0 && !stats)) { *v.err = std::string(who) + ": null argument"; return MHAP_E_INVALID; }
+  if (min_cov < 1) { *v.err = std::string(who) + ": min_cov must be at least 1 (" + std::to_string(min_cov) + ")"; return MHAP_E_INVALID; }
+  if (skipped_views) *skipped_views = s->skipped;
+  s->out_bytes = -1;
+  out_offsets[0] = 0;
+  if (s->n_reads == 0) { s->out_bytes = 0; return MHAP_OK; }
+  if (s->n_reads > INT32_MAX) { *v.err = std::string(who) + ": more than 2^31 - 1 reads"; return MHAP_E_INVALID; }
+  (void)hipSetDevice(v.device);
+  hipError_t e;
+  const dim3 grid((unsigned)s->n_reads), block(CK_T);
+  hipLaunchKernelGGL(call_kernel, grid, block, 0, v.stream, s->bases.as<uint8_t>(), s->read_off.as<int64_t>(), s->read_pos.as<int64_t>(),
+                     s->read_len.as<int32_t>(), s->table.as<uint32_t>(), (int)min_cov, (const int64_t*)nullptr, (uint8_t*)nullptr,
+                     s->stats.as<int32_t>());
+  if ((e = hipGetLastError()) != hipSuccess) return hip_fail(v, who, "launch", e);
+  if ((e = hipMemcpyAsync(stats, s->stats.p, 24 * (size_t)s->n_reads, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return hip_fail(v, who, "download", e);
+  if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return hip_fail(v, who, "kernel", e);
+  for (int64_t r = 0; r < s->n_reads; r++) out_offsets[r + 1] = out_offsets[r] + stats[6 * r + 1];
+  const int64_t total = out_offsets[s->n_reads];
+  if ((e = s->out.ensure((size_t)std::max<int64_t>(total, 1))) != hipSuccess) return hip_fail(v, who, "hipMalloc of the corrected bytes", e);
+  if ((e = hipMemcpyAsync(s->out_off.p, out_offsets, 8 * (size_t)(s->n_reads + 1), hipMemcpyHostToDevice, v.stream)) != hipSuccess) return hip_fail(v, who, "upload", e);
+  hipLaunchKernelGGL(call_kernel, grid, block, 0, v.stream, s->bases.as<uint8_t>(), s->read_off.as<int64_t>(), s->read_pos.as<int64_t>(),
+                     s->read_len.as<int32_t>(), s->table.as<uint32_t>(), (int)min_cov, s->out_off.as<int64_t>(), s->out.as<uint8_t>(),
+                     s->stats.as<int32_t>());
+  if ((e = hipGetLastError()) != hipSuccess) return hip_fail(v, who, "launch", e);
+  if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return hip_fail(v, who, "kernel", e);
+  s->out_bytes = total;
+  return MHAP_OK;
+}
+
+extern "C" int mhap_correct_copy(mhap_correct_session* s, uint8_t* bytes) {
+  const char* who = "mhap_correct_copy";
+  if (!s) return MHAP_E_INVALID;
+  HandleView v = handle_view(s->h);
+  if (s->out_bytes < 0) { *v.err = std::string(who) + ": no mhap_correct_finish has completed"; return MHAP_E_INVALID; }
+  if (s->out_bytes == 0) return MHAP_OK;
+  if (!bytes) { *v.err = std::string(who) + ": null argument"; return MHAP_E_INVALID; }
+  (void)hipSetDevice(v.device);
+  hipError_t e;
+  if ((e = hipMemcpyAsync(bytes, s->out.p, (size_t)s->out_bytes, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return hip_fail(v, who, "download", e);
+  if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return hip_fail(v, who, "download", e);
+  return MHAP_OK;
+}
+
+extern "C" int mhap_correct_votes(mhap_correct_session* s, int64_t read_index, uint16_t* counters) {
+  const char* who = "mhap_correct_votes";
+  if (!s) return MHAP_E_INVALID;
+  HandleView v = handle_view(s->h);
+  if (read_index < 0 || read_index >= s->n_reads) { *v.err = std::string(who) + ": read " + std::to_string(read_index) + " is not among the " + std::to_string(s->n_reads) + " reads"; return MHAP_E_INVALID; }
+  const int64_t len = s->lengths[(size_t)read_index];
+  if (len == 0) return MHAP_OK;
+  if (!counters) { *v.err = std::string(who) + ": null argument"; return MHAP_E_INVALID; }
+  (void)hipSetDevice(v.device);
+  std::vector<uint32_t> w((size_t)len * CK_WORDS);
+  hipError_t e;
+  if ((e = hipMemcpyAsync(w.data(), s->table.as<uint32_t>() + (int64_t)CK_WORDS * s->pos[(size_t)read_index], w.size() * 4, hipMemcpyDeviceToHost,
+                          v.stream)) != hipSuccess) return hip_fail(v, who, "download", e);
+  if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return hip_fail(v, who, "download", e);
+  for (int64_t t = 0; t < len; t++)
+    for (int p = 0; p < CK_WORDS; p++) {
+      const uint32_t x = w[(size_t)(p * len + t)];
+      counters[24 * t + 2 * p] = (uint16_t)(x & 0xFFFFu);
+      counters[24 * t + 2 * p + 1] = (uint16_t)(x >> 16);
+    }
+  return MHAP_OK;
+}
+
+extern "C" void mhap_correct_free(mhap_correct_session* s) {
+  if (!s) return;
+  s->release();
+  delete s;
+}

@@ -42,10 +42,15 @@ struct Options {
     for (auto& n : order) { const Opt& o = m.at(n); t += "\t" + n + ", default = " + (o.is_flag ? "false" : o.value) + "\n\t\t" + o.help + "\n"; }
     return t;
   }
-  // (the realignment flags are listed only when --realign is given: without it every line the driver writes is what it was before them)
+  // (the realignment flags are listed only when --realign is given, the correction flags only when --correct is: without them every
+  // line the driver writes is what it was before them)
   std::string dump() const {
     std::string t;
-    for (auto& n : order) { if (n.compare(0, 9, "--realign") == 0 && !b("--realign")) continue; t += n + " = " + m.at(n).value + "\n"; }
+    for (auto& n : order) {
+      if (n.compare(0, 9, "--realign") == 0 && !b("--realign")) continue;
+      if (n.compare(0, 9, "--correct") == 0 && !isset("--correct")) continue;
+      t += n + " = " + m.at(n).value + "\n";
+    }
     return t;
   }
   // ParseOptions.process (J/utils/ParseOptions.java:209-236,327-368): flags are presence flags, others consume the next arg
@@ -161,6 +166,9 @@ struct Realign {
   std::vector<int32_t> detail; std::vector<int64_t> op_offsets, row; std::vector<uint32_t> ops;   // row[k]: the batch row of kept record k
   int64_t dropped = 0, kept = 0;
   double seconds = 0.0;
+  mhap_correct_session* correct = nullptr;            // --correct: every kept record votes on both of its reads
+  std::vector<int64_t> vote_offsets; std::vector<uint32_t> vote_ops;
+  double correct_seconds = 0.0;
   void add(const mhap_fasta& fa) {
     for (int64_t i = 0; i < fa.n; i++) { ids.push_back(fa.ids[i]); offsets.push_back((int64_t)bases.size() + fa.offsets[i]); lengths.push_back(fa.lengths[i]); }
     bases.insert(bases.end(), (const uint8_t*)fa.bases, (const uint8_t*)fa.bases + fa.total_bases);
@@ -175,7 +183,7 @@ int sink_cb(const mhap_record* r, int64_t n, void* user) {
     const double t = now();
     R.out.resize((size_t)n);
     int rc;
-    if (R.paf) {
+    if (R.paf || R.correct) {
       R.detail.resize((size_t)n * 3);
       mhap_align_paths* paths = nullptr;
       rc = mhap_realign_records_paths(R.h, R.bases.data(), (int64_t)R.bases.size(), R.ids.data(), R.offsets.data(), R.lengths.data(),
@@ -203,6 +211,21 @@ int sink_cb(const mhap_record* r, int64_t n, void* user) {
     }
     R.dropped += n - k; R.kept += k;
     R.seconds += now() - t;
+    if (R.correct) {   // the kept records and their runs into the vote table; the dropped ones cast no vote
+      const double tc = now();
+      R.vote_offsets.assign(1, 0); R.vote_ops.clear();
+      for (int64_t i = 0; i < k; i++) {
+        const int64_t q = R.row[(size_t)i];
+        R.vote_ops.insert(R.vote_ops.end(), R.ops.begin() + R.op_offsets[(size_t)q], R.ops.begin() + R.op_offsets[(size_t)q + 1]);
+        R.vote_offsets.push_back((int64_t)R.vote_ops.size());
+      }
+      mhap_align_paths* kept_paths = nullptr;
+      rc = mhap_align_paths_from_runs(R.vote_offsets.data(), k, R.vote_ops.data(), &kept_paths);
+      if (rc == MHAP_OK) rc = mhap_correct_add(R.correct, R.out.data(), k, kept_paths);
+      mhap_align_paths_free(kept_paths);
+      if (rc != MHAP_OK) { fprintf(stderr, "Exception in mhap-hip: %s (code %d)\n", mhap_last_error(R.h), rc); return 1; }
+      R.correct_seconds += now() - tc;
+    }
     r = R.out.data(); n = k;
   }
   if (s->realign && s->realign->paf) {   // one PAF line per kept record; the names are columns 1 and 2 of the 12-column line
@@ -377,6 +400,8 @@ int main(int argc, char** argv) {
   o.add("--realign-band", "[int] Half-width of the realignment band in bases. 0) the overlap's length times --max-shift.", "0");
   o.add("--realign-min-identity", "[double] With --realign, drop overlaps whose aligned identity is below this value (overlaps without an alignment are always dropped).", "0.0");
   o.add("--realign-paf", "With --realign, print one PAF line per overlap instead of the 12 columns: the alignment's interval, its matches and columns, and its path as a cg:Z CIGAR with = X I D.", "false", true);
+  o.add("--correct", "With --realign: correct every read of -s from the realigned overlaps and write the corrected reads to this FASTA file. Each overlap votes column by column on both of its reads and every position takes the majority; overlaps that --realign drops cast no vote. Self overlaps only (no -q), one GPU.", "");
+  o.add("--correct-min-coverage", "[int] With --correct, the votes a read position needs before it is changed.", "4");
   if (!o.parse(argc, argv)) return 0;
 
   auto bad = [&](const char* m) { printf("%s\n", m); exit(1); };
@@ -418,6 +443,15 @@ int main(int argc, char** argv) {
   const bool precompute = !o.s("-p").empty();
   const bool realign = o.b("--realign") && !precompute;
   if (o.b("--realign-paf") && !o.b("--realign")) bad("--realign-paf prints the alignments of --realign: give --realign too.");
+  const bool correct = o.isset("--correct");
+  if (correct) {   // refused before a handle exists
+    if (!o.b("--realign")) bad("--correct votes with the alignments of --realign: give --realign too.");
+    if (!o.s("-q").empty()) bad("--correct corrects the reads of -s from their overlaps with each other: it takes no -q.");
+    if (ends_with(o.s("-s"), ".dat")) bad("--correct needs the reads' bases: give FASTA files, not .dat sketches.");
+    if (devs.size() > 1) bad("--correct runs on one GPU: give one device (--gpus 1).");
+    if (o.s("--correct").empty()) bad("--correct needs the name of the FASTA file to write.");
+    if (o.i("--correct-min-coverage") < 1) bad("The correction's minimum coverage must be >=1.");
+  }
   if (realign) {   // refused before a handle exists
     if (o.i("--realign-band") < 0) bad("The realignment band must be >=0.");
     if (devs.size() > 1) bad("--realign runs on one GPU: give one device (--gpus 1).");
@@ -496,6 +530,8 @@ int main(int argc, char** argv) {
       mhap_fasta_free(&fa);
     }
     sink.realign = &RA;
+    if (correct) chk(E.h, mhap_correct_begin(E.h, RA.bases.data(), (int64_t)RA.bases.size(), RA.ids.data(), RA.offsets.data(), RA.lengths.data(),
+                                             (int64_t)RA.ids.size(), &RA.correct));
   }
   const double t_score = now();
   if (o.s("-q").empty()) {
@@ -547,6 +583,37 @@ int main(int argc, char** argv) {
   sink_flush(sink);
   fprintf(stderr, "Total scoring time (s): %g\n", now() - t_score);
   if (realign) fprintf(stderr, "Time (s) to realign: %g (%lld overlaps kept, %lld dropped: no alignment or identity below %g)\n", RA.seconds, (long long)RA.kept, (long long)RA.dropped, RA.min_identity);
+  if (RA.correct) {   // the call for every read, after the last batch has voted; the FASTA file is all it writes
+    const double tc = now();
+    const int64_t nr = (int64_t)RA.ids.size();
+    std::vector<int64_t> off((size_t)nr + 1);
+    std::vector<int32_t> st((size_t)std::max<int64_t>(nr, 1) * 6);
+    int64_t skipped = 0;
+    chk(E.h, mhap_correct_finish(RA.correct, o.i("--correct-min-coverage"), off.data(), st.data(), &skipped));
+    std::vector<uint8_t> bytes((size_t)std::max<int64_t>(off[(size_t)nr], 1));
+    chk(E.h, mhap_correct_copy(RA.correct, bytes.data()));
+    mhap_correct_free(RA.correct);
+    RA.correct = nullptr;
+    FILE* f = fopen(o.s("--correct").c_str(), "wb");
+    if (!f) die("cannot write " + o.s("--correct"));
+    long long tot[6] = {0, 0, 0, 0, 0, 0};
+    std::string text;
+    for (int64_t r = 0; r < nr; r++) {
+      const int32_t* c = st.data() + 6 * r;
+      for (int u = 0; u < 6; u++) tot[u] += c[u];
+      text += ">" + header_of(RA.ids[(size_t)r]) + " len=" + std::to_string(c[1]) + " sub=" + std::to_string(c[2]) + " del=" + std::to_string(c[3]) +
+              " ins=" + std::to_string(c[4]) + " low=" + std::to_string(c[5]) + "\n";
+      text.append((const char*)bytes.data() + off[(size_t)r], (size_t)(off[(size_t)r + 1] - off[(size_t)r]));
+      text.push_back('\n');
+      if (text.size() > (8u << 20)) { fwrite(text.data(), 1, text.size(), f); text.clear(); }
+    }
+    fwrite(text.data(), 1, text.size(), f);
+    if (fclose(f) != 0) die("cannot write " + o.s("--correct"));
+    RA.correct_seconds += now() - tc;
+    fprintf(stderr, "Corrected %lld reads: %lld bases in, %lld out; %lld substitutions, %lld deletions, %lld insertions, %lld positions of low coverage; skipped_views = %lld\n",
+            (long long)nr, tot[0], tot[1], tot[2], tot[3], tot[4], tot[5], (long long)skipped);
+    fprintf(stderr, "Time (s) to vote and correct: %g\n", RA.correct_seconds);
+  }
   fprintf(stderr, "Total time (s): %g\n", now() - t_total);
   // outputFinalStat (MhapMain.java:572-590); the inverted-index counters have no brute-force analogue
   const mhap_stats st = E.stats();

@@ -14,6 +14,13 @@
 
 #include "../../include/mhap_hip.h"
 
+// The paths of one call (mhap_align_pairs_banded_paths, mhap_realign_records_paths; realign_kernels.hip): pair q's runs are
+// ops[offsets[q], offsets[q + 1]).  The correction stage (correct_kernels.hip) reads them.
+struct mhap_align_paths {
+  std::vector<int64_t> offsets{0};
+  std::vector<uint32_t> ops;
+};
+
 namespace mhap {
 
 // Host threads worth starting: the hardware threads, capped by the container's CPU quota when there is one (cgroup v2 cpu.max) —

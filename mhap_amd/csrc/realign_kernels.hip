@@ -57,12 +57,6 @@
 #include "device_common.hpp"
 #include "mhap_internal.hpp"
 
-// The paths of one call (mhap_align_pairs_banded_paths, mhap_realign_records_paths): pair q's runs are ops[offsets[q], offsets[q + 1]).
-struct mhap_align_paths {
-  std::vector<int64_t> offsets{0};
-  std::vector<uint32_t> ops;
-};
-
 namespace mhap {
 namespace {
 
@@ -736,6 +730,19 @@ extern "C" int mhap_align_paths_copy(const mhap_align_paths* p, int64_t* op_offs
 }
 
 extern "C" void mhap_align_paths_free(mhap_align_paths* p) { delete p; }
+
+extern "C" int mhap_align_paths_from_runs(const int64_t* op_offsets, int64_t n, const uint32_t* ops, mhap_align_paths** out) {
+  if (out) *out = nullptr;
+  if (!out || !op_offsets || n < 0 || op_offsets[0] != 0) return MHAP_E_INVALID;
+  for (int64_t q = 0; q < n; q++)
+    if (op_offsets[q + 1] < op_offsets[q]) return MHAP_E_INVALID;
+  if (op_offsets[n] > 0 && !ops) return MHAP_E_INVALID;
+  mhap_align_paths* p = new mhap_align_paths();
+  p->offsets.assign(op_offsets, op_offsets + n + 1);
+  p->ops.assign(ops, ops + op_offsets[n]);
+  *out = p;
+  return MHAP_OK;
+}
 
 extern "C" const char* mhap_realign_plan_error(void) { return g_plan_err.c_str(); }
 
