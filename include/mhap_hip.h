@@ -552,6 +552,84 @@ int mhap_correct_copy(mhap_correct_session* s, uint8_t* bytes);
 int mhap_correct_votes(mhap_correct_session* s, int64_t read_index, uint16_t* counters /* length x 24 */);
 void mhap_correct_free(mhap_correct_session* s);
 
+/* ---- string graph: dovetails, contained reads and transitive reduction over the realigned overlaps, and GFA ------------------------- */
+
+/* The layout step that follows an overlapper (Myers 2005): every realigned overlap is classed, contained reads are set aside, the
+ * dovetails become the arcs of a bidirected graph and the arcs that a two-arc path explains are removed.  Left out: read trimming,
+ * chimera detection, tip and bubble removal, unitig sequences.  Everything is integer arithmetic (sums and products of lengths in
+ * int64); the only floating comparison is score < min_identity on the record's double.
+ *
+ * Input.  A table of reads (read_ids[r], lengths[r]; no bases), realigned records (out[q] of mhap_realign_records) and the parameters
+ * max_hang (1000), int_frac_permille (800), min_ovlp (2000), fuzz (1000), min_identity (0.0).
+ *
+ * Vertices.  Read r (its position in read_ids) has the vertices 2 r (forward) and 2 r + 1 (reverse complement); v ^ 1 is the other strand.
+ *
+ * The class of a record.  qs = a1, qe = a2 + 1, ql = alen, tl = blen; (ts, te) = (b1, b2 + 1) when !to_rc, else (tl - b2 - 1, tl - b1):
+ * the `to` read as aligned; tl5 = ts, tl3 = tl - te; ext5 = min(qs, tl5), ext3 = min(ql - qe, tl3).  The first rule that holds:
+ *   0 NONE         from_id == to_id, or score == 0 (no alignment), or score < min_identity;
+ *   1 INTERNAL     ext5 > max_hang, or ext3 > max_hang, or (qe - qs) * 1000 < (qe - qs + ext5 + ext3) * int_frac_permille;
+ *   2 A_CONTAINED  qs <= tl5 and ql - qe <= tl3: the `from` read is contained;
+ *   3 B_CONTAINED  qs >= tl5 and ql - qe >= tl3: the `to` read is contained;
+ *   4 SHORT        qe - qs + ext5 + ext3 < min_ovlp, or te - ts + ext5 + ext3 < min_ovlp;
+ *   5 DOVETAIL     everything else (both inequalities are strict here).
+ * A dovetail gives two arcs (u, v, len); with A, B the two reads' positions in read_ids and o = to_rc (0 or 1):
+ *   qs > tl5:    (2 A, 2 B + o, qs - tl5)   and  (2 B + (1 - o), 2 A + 1, tl3 - (ql - qe));
+ *   otherwise:   (2 B + o, 2 A, tl5 - qs)   and  (2 A + 1, 2 B + (1 - o), (ql - qe) - tl3).
+ * len is how far v begins after u begins; ol = length(read(u)) - len is the overlap the arc stands for.
+ *
+ * Contained reads.  A read is contained when any record classes it so, and every arc with a contained read at either end is dropped.
+ *
+ * The arc list.  The surviving arcs sorted by (u, len, v); of the arcs with equal (u, v) only the first is kept.  An arc's q is the
+ * arrival index (over all adds, from 0) of a record that produced a kept arc's (u, v, len): a label, on which nothing else depends.
+ * The complement of u -> v is v ^ 1 -> u ^ 1; a record gives an arc and its complement, so the complement is always in the list.
+ *
+ * Reduction.  Every vertex is reduced on its own, on the de-duplicated list as it is before any reduction.  For vertex v with the
+ * arcs v -> w_i in list order:
+ *   1. every w_i is IN_PLAY;   2. longest = len(the last arc) + fuzz;
+ *   3. pass 1, over i in order: skip w_i unless it is still IN_PLAY; the arcs w_i -> x in list order, stopping at the first with
+ *      len(v -> w_i) + len(w_i -> x) > longest: an x that is IN_PLAY becomes ELIMINATED;
+ *   4. pass 2, over every i whatever its mark: of the arcs w_i -> x in list order the first, then every arc with len < fuzz, stopping
+ *      at the first later arc with len >= fuzz: an x that is IN_PLAY becomes ELIMINATED;
+ *   5. the arcs v -> w with w ELIMINATED are `reduced`.
+ * The final arcs are those that are not reduced and whose complement is not reduced.
+ *
+ * Results.  The class of every record (one byte, in arrival order), a contained flag per read, the arc list as rows of 7 int32
+ * {u, v, len, ol, q, reduced, final}, and MHAP_GRAPH_COUNTS int64 counts: records, the six classes in the order above, contained
+ * reads, arcs, reduced arcs, final arcs.  Everything except the q labels and the order of the per-record classes is invariant under
+ * any permutation of the records and any split of them over calls.
+ *
+ * The session.  mhap_graph_begin takes the table of reads (params NULL: the defaults); the handle must outlive the session, whose
+ * errors are the handle's (mhap_last_error).  mhap_graph_add classes the records on the device (graph_kernels.hip), any number of
+ * times, n = 0 included, and does not wait for the device.  A record's reads are found by id as mhap_realign_plan finds them;
+ * MHAP_E_INVALID, naming the record, for an id not among read_ids or an alen / blen that disagrees with the table; a refused call
+ * adds nothing.  mhap_graph_finish builds the list, reduces it and returns the counts; it may be repeated, and more records may be
+ * added after it.  mhap_graph_info: the reads, the records added so far and the arcs of the last finish (-1 before the first); any
+ * pointer may be NULL.  mhap_graph_copy_arcs writes the rows of the last finish, mhap_graph_copy_classes one byte per record added
+ * so far, mhap_graph_copy_read_flags one byte (0 / 1) per read.  Device memory: 33 bytes per record and 8 per read from begin to
+ * free, and from the first finish on 48 more per read and 73 per surviving arc.
+ *
+ * GFA 1.  `H\tVN:Z:1.0`, then `S\t<id>\t*\tLN:i:<length>` for every read that is not contained, in read_ids order, then one L line per
+ * final arc in list order; every line ends with '\n' and ids are numeric.  The text depends on the set of records only.
+ * mhap_format_gfa_link (no GPU) writes the L line of one row, `L\t<id(u)>\t<+|->\t<id(v)>\t<+|->\t<ol>M` without the newline, '-' for
+ * an odd vertex: snprintf semantics as mhap_format_paf; -1 for a null pointer. */
+typedef struct mhap_graph_params {
+  int32_t max_hang, int_frac_permille, min_ovlp, fuzz;
+  double min_identity;
+} mhap_graph_params;
+#define MHAP_GRAPH_COUNTS 11
+typedef struct mhap_graph_session mhap_graph_session;
+void mhap_graph_default_params(mhap_graph_params* p);
+int mhap_graph_begin(mhap_handle* h, const int64_t* read_ids, const int32_t* lengths, int64_t n_reads, const mhap_graph_params* params,
+                     mhap_graph_session** session);
+int mhap_graph_add(mhap_graph_session* s, const mhap_record* realigned, int64_t n);
+int mhap_graph_finish(mhap_graph_session* s, int64_t* counts /* MHAP_GRAPH_COUNTS */);
+int mhap_graph_info(const mhap_graph_session* s, int64_t* n_reads, int64_t* n_records, int64_t* n_arcs);
+int mhap_graph_copy_arcs(mhap_graph_session* s, int32_t* rows /* n_arcs x 7 */);
+int mhap_graph_copy_classes(mhap_graph_session* s, uint8_t* classes /* n_records */);
+int mhap_graph_copy_read_flags(mhap_graph_session* s, uint8_t* flags /* n_reads */);
+void mhap_graph_free(mhap_graph_session* s);
+int mhap_format_gfa_link(const int32_t* row7, const int64_t* read_ids, char* out, size_t cap);
+
 /* KmerStatSimulator's pair statistics on the GPU (J/main/KmerStatSimulator.java:163-196).  pairs: n rows of 4 int64 {a_off, a_len,
  * b_off, b_len}; a = bases[a_off, a_off + a_len) is the first read, b the second.  skip: n_skip k-mers of k bytes each, back to back, in
  * any order (the skip set of loadSkipMers; entries of another length never match and are left out by the caller).  For each pair,

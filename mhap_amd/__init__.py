@@ -30,6 +30,10 @@ from .api import (  # noqa: F401
     format_paf,
     CorrectSession,
     correct_reads,
+    GraphSession,
+    string_graph,
+    format_gfa,
+    format_gfa_link,
     pair_kmer_stats,
     records_to_lines,
     load_library,

@@ -75,6 +75,8 @@ EXPORTED_SYMBOLS = [
     "mhap_align_pairs_banded_paths", "mhap_realign_records_paths", "mhap_align_paths_info", "mhap_align_paths_copy", "mhap_align_paths_free",
     "mhap_format_paf", "mhap_align_paths_from_runs",
     "mhap_correct_begin", "mhap_correct_add", "mhap_correct_finish", "mhap_correct_copy", "mhap_correct_votes", "mhap_correct_free",
+    "mhap_graph_default_params", "mhap_graph_begin", "mhap_graph_add", "mhap_graph_finish", "mhap_graph_info", "mhap_graph_copy_arcs",
+    "mhap_graph_copy_classes", "mhap_graph_copy_read_flags", "mhap_graph_free", "mhap_format_gfa_link",
     "mhap_pair_kmer_stats", "mhap_pair_kmer_stats_paths", "mhap_ksim_create", "mhap_ksim_next", "mhap_ksim_error", "mhap_ksim_destroy",
     "mhap_ksim_dev_create", "mhap_ksim_dev_destroy", "mhap_ksim_dev_pair_stats", "mhap_ksim_dev_trials",
 ]
@@ -165,6 +167,17 @@ def load_library(build_if_missing=True):
     lib.mhap_correct_votes.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
     lib.mhap_correct_free.restype = None
     lib.mhap_correct_free.argtypes = [C.c_void_p]
+    lib.mhap_graph_default_params.restype = None
+    lib.mhap_graph_default_params.argtypes = [C.c_void_p]
+    lib.mhap_graph_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.mhap_graph_add.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    lib.mhap_graph_finish.argtypes = [C.c_void_p, C.c_void_p]
+    lib.mhap_graph_info.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    for name in ("mhap_graph_copy_arcs", "mhap_graph_copy_classes", "mhap_graph_copy_read_flags"):
+        getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p]
+    lib.mhap_graph_free.restype = None
+    lib.mhap_graph_free.argtypes = [C.c_void_p]
+    lib.mhap_format_gfa_link.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     for name in EXPORTED_SYMBOLS:
         getattr(lib, name)  # AttributeError here = header/library mismatch
     # a stale library next to newer host code (or the reverse) must not get as far as a struct copy
@@ -621,6 +634,137 @@ def correct_reads(records, fasta, op_offsets, ops, min_cov=4, query_fasta=None, 
     with CorrectSession(fasta, query_fasta=query_fasta, handle=handle, device=device) as cs:
         cs.add(records, op_offsets, ops)
         return cs.finish(min_cov)
+
+
+GRAPH_CLASSES = ("none", "internal", "a_contained", "b_contained", "short", "dovetail")   # the class codes 0 .. 5 of a record
+GRAPH_COUNTS = ("records",) + GRAPH_CLASSES + ("contained_reads", "arcs", "reduced", "final")   # mhap_graph_finish's counts, in order
+GRAPH_ARC_FIELDS = ("u", "v", "len", "ol", "q", "reduced", "final")
+
+
+class _GraphParams(C.Structure):
+    _fields_ = [("max_hang", C.c_int32), ("int_frac_permille", C.c_int32), ("min_ovlp", C.c_int32), ("fuzz", C.c_int32),
+                ("min_identity", C.c_double)]
+
+
+def format_gfa_link(row, read_ids):
+    """The GFA L line of one arc row (mhap_format_gfa_link, no GPU), without the newline."""
+    lib = load_library()
+    row = np.ascontiguousarray(row, dtype=np.int32).reshape(7)
+    read_ids = np.ascontiguousarray(read_ids, dtype=np.int64)
+    buf = C.create_string_buffer(96)
+    n = lib.mhap_format_gfa_link(_ptr(row), _ptr(read_ids), buf, C.c_size_t(96))
+    if n < 0 or n >= 96:
+        raise MhapError("mhap_format_gfa_link failed")
+    return buf.value.decode()
+
+
+def format_gfa(read_ids, lengths, contained, arcs):
+    """GFA 1 text of a string graph: the header, an S line per read that is not contained (in read_ids order), an L line per final
+    arc (in list order).  The "string graph" section of include/mhap_hip.h has the format."""
+    arcs = np.ascontiguousarray(arcs, dtype=np.int32).reshape(-1, 7)
+    out = ["H\tVN:Z:1.0\n"]
+    out += [f"S\t{i}\t*\tLN:i:{n}\n" for i, n, c in zip(np.asarray(read_ids).tolist(), np.asarray(lengths).tolist(), np.asarray(contained).tolist()) if not c]
+    out += [format_gfa_link(r, read_ids) + "\n" for r in arcs[arcs[:, 6] != 0]]
+    return "".join(out)
+
+
+class GraphSession:
+    """The string graph of realigned overlaps on the GPU (mhap_graph_begin / _add / _finish / _copy_*; the contract is the "string
+    graph" section of include/mhap_hip.h): every record is classed, contained reads are set aside, the dovetails become arcs and
+    the arcs a two-arc path explains are reduced.
+
+        with GraphSession(fasta.ids, fasta.lengths) as gs:
+            gs.add(records)                       # what realign_records returned; any number of times
+            arcs, counts = gs.finish()            # int32 (n, 7) of GRAPH_ARC_FIELDS, a dict of GRAPH_COUNTS
+            text = gs.gfa()
+
+    handle: a MinHashSearch whose device and stream to use (else one is made and closed with the session)."""
+
+    def __init__(self, read_ids, lengths, max_hang=1000, int_frac_permille=800, min_ovlp=2000, fuzz=1000, min_identity=0.0, handle=None,
+                 device=0):
+        self._own = handle is None
+        self._ms = MinHashSearch(MhapParams(num_hashes=1, ordered_sketch_size=1, device=device)) if self._own else handle
+        self._lib = self._ms._lib
+        self._s = C.c_void_p()
+        self.ids = np.ascontiguousarray(read_ids, np.int64)
+        self.lengths = np.ascontiguousarray(lengths, np.int32)
+        if len(self.ids) != len(self.lengths):
+            raise MhapError(f"GraphSession: {len(self.ids)} ids and {len(self.lengths)} lengths")
+        p = _GraphParams(max_hang, int_frac_permille, min_ovlp, fuzz, min_identity)
+        self.arcs = np.zeros((0, 7), np.int32)
+        try:
+            self._ms._chk(self._lib.mhap_graph_begin(self._ms._h, _ptr(self.ids) if len(self.ids) else None,
+                                                     _ptr(self.lengths) if len(self.ids) else None, C.c_int64(len(self.ids)), C.byref(p),
+                                                     C.byref(self._s)))
+        except Exception:
+            if self._own:
+                self._ms.close()
+            raise
+
+    def add(self, records):
+        """Class realigned records (nothing waits for the device)."""
+        records = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
+        self._ms._chk(self._lib.mhap_graph_add(self._s, _ptr(records) if len(records) else None, C.c_int64(len(records))))
+
+    def finish(self):
+        """(arcs, counts): the de-duplicated arc list as an int32 array (n, 7) of GRAPH_ARC_FIELDS and a dict of GRAPH_COUNTS."""
+        counts = np.zeros(len(GRAPH_COUNTS), np.int64)
+        self._ms._chk(self._lib.mhap_graph_finish(self._s, _ptr(counts)))
+        self.arcs = np.zeros((int(counts[GRAPH_COUNTS.index("arcs")]), 7), np.int32)
+        self._ms._chk(self._lib.mhap_graph_copy_arcs(self._s, _ptr(self.arcs) if len(self.arcs) else None))
+        self.counts = dict(zip(GRAPH_COUNTS, counts.tolist()))
+        return self.arcs, self.counts
+
+    def info(self):
+        """(reads, records added so far, arcs of the last finish or -1)."""
+        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._ms._chk(self._lib.mhap_graph_info(self._s, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def classes(self):
+        """The class code of every record added so far, in arrival order (uint8; GRAPH_CLASSES names them)."""
+        out = np.zeros(self.info()[1], np.uint8)
+        self._ms._chk(self._lib.mhap_graph_copy_classes(self._s, _ptr(out) if len(out) else None))
+        return out
+
+    def contained(self):
+        """One byte per read: 1 when some record classes it contained."""
+        out = np.zeros(len(self.ids), np.uint8)
+        self._ms._chk(self._lib.mhap_graph_copy_read_flags(self._s, _ptr(out) if len(out) else None))
+        return out
+
+    def gfa(self):
+        """The GFA 1 text of the last finish."""
+        return format_gfa(self.ids, self.lengths, self.contained(), self.arcs)
+
+    def close(self):
+        if self._s:
+            self._lib.mhap_graph_free(self._s)
+            self._s = C.c_void_p()
+            if self._own:
+                self._ms.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def string_graph(records, fasta, query_fasta=None, handle=None, device=0, **params):
+    """The string graph of realigned records over the reads of `fasta` (and `query_fasta`): (arcs, counts, contained, gfa text) of a
+    GraphSession; params: max_hang, int_frac_permille, min_ovlp, fuzz, min_identity."""
+    _, ids, _, lengths = _all_reads(fasta, query_fasta)
+    with GraphSession(ids, lengths, handle=handle, device=device, **params) as gs:
+        gs.add(records)
+        arcs, counts = gs.finish()
+        return arcs, counts, gs.contained(), gs.gfa()
 
 
 def _skip_bytes(skip, k):

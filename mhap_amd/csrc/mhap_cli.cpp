@@ -42,13 +42,14 @@ struct Options {
     for (auto& n : order) { const Opt& o = m.at(n); t += "\t" + n + ", default = " + (o.is_flag ? "false" : o.value) + "\n\t\t" + o.help + "\n"; }
     return t;
   }
-  // (the realignment flags are listed only when --realign is given, the correction flags only when --correct is: without them every
-  // line the driver writes is what it was before them)
+  // (the realignment flags are listed only when --realign is given, the correction flags only when --correct is, the graph's only
+  // when --gfa is: without them every line the driver writes is what it was before them)
   std::string dump() const {
     std::string t;
     for (auto& n : order) {
       if (n.compare(0, 9, "--realign") == 0 && !b("--realign")) continue;
       if (n.compare(0, 9, "--correct") == 0 && !isset("--correct")) continue;
+      if (n.compare(0, 5, "--gfa") == 0 && !isset("--gfa")) continue;
       t += n + " = " + m.at(n).value + "\n";
     }
     return t;
@@ -169,6 +170,8 @@ struct Realign {
   mhap_correct_session* correct = nullptr;            // --correct: every kept record votes on both of its reads
   std::vector<int64_t> vote_offsets; std::vector<uint32_t> vote_ops;
   double correct_seconds = 0.0;
+  mhap_graph_session* graph = nullptr;                // --gfa: every kept record is classed for the string graph
+  double graph_seconds = 0.0;
   void add(const mhap_fasta& fa) {
     for (int64_t i = 0; i < fa.n; i++) { ids.push_back(fa.ids[i]); offsets.push_back((int64_t)bases.size() + fa.offsets[i]); lengths.push_back(fa.lengths[i]); }
     bases.insert(bases.end(), (const uint8_t*)fa.bases, (const uint8_t*)fa.bases + fa.total_bases);
@@ -225,6 +228,12 @@ int sink_cb(const mhap_record* r, int64_t n, void* user) {
       mhap_align_paths_free(kept_paths);
       if (rc != MHAP_OK) { fprintf(stderr, "Exception in mhap-hip: %s (code %d)\n", mhap_last_error(R.h), rc); return 1; }
       R.correct_seconds += now() - tc;
+    }
+    if (R.graph) {   // the kept records into the string graph (queued: nothing waits)
+      const double tg = now();
+      rc = mhap_graph_add(R.graph, R.out.data(), k);
+      if (rc != MHAP_OK) { fprintf(stderr, "Exception in mhap-hip: %s (code %d)\n", mhap_last_error(R.h), rc); return 1; }
+      R.graph_seconds += now() - tg;
     }
     r = R.out.data(); n = k;
   }
@@ -402,6 +411,10 @@ int main(int argc, char** argv) {
   o.add("--realign-paf", "With --realign, print one PAF line per overlap instead of the 12 columns: the alignment's interval, its matches and columns, and its path as a cg:Z CIGAR with = X I D.", "false", true);
   o.add("--correct", "With --realign: correct every read of -s from the realigned overlaps and write the corrected reads to this FASTA file. Each overlap votes column by column on both of its reads and every position takes the majority; overlaps that --realign drops cast no vote. Self overlaps only (no -q), one GPU.", "");
   o.add("--correct-min-coverage", "[int] With --correct, the votes a read position needs before it is changed.", "4");
+  o.add("--gfa", "With --realign: build the string graph of the realigned overlaps on the GPU (dovetails, contained reads set aside, transitive arcs reduced) and write it to this file as GFA 1: an S line per read that is not contained, an L line per final arc. Self overlaps only (no -q), one GPU.", "");
+  o.add("--gfa-max-hang", "[int] With --gfa, the longest unaligned end an overlap may leave on both reads before it counts as an internal match.", "1000");
+  o.add("--gfa-min-overlap", "[int] With --gfa, the shortest overlap that becomes an arc.", "2000");
+  o.add("--gfa-fuzz", "[int] With --gfa, the slack of the transitive reduction in bases.", "1000");
   if (!o.parse(argc, argv)) return 0;
 
   auto bad = [&](const char* m) { printf("%s\n", m); exit(1); };
@@ -451,6 +464,15 @@ int main(int argc, char** argv) {
     if (devs.size() > 1) bad("--correct runs on one GPU: give one device (--gpus 1).");
     if (o.s("--correct").empty()) bad("--correct needs the name of the FASTA file to write.");
     if (o.i("--correct-min-coverage") < 1) bad("The correction's minimum coverage must be >=1.");
+  }
+  const bool gfa = o.isset("--gfa");
+  if (gfa) {   // refused before a handle exists
+    if (!o.b("--realign")) bad("--gfa builds the graph from the alignments of --realign: give --realign too.");
+    if (!o.s("-q").empty()) bad("--gfa lays out the reads of -s from their overlaps with each other: it takes no -q.");
+    if (ends_with(o.s("-s"), ".dat")) bad("--gfa needs the overlaps realigned on the reads' bases: give FASTA files, not .dat sketches.");
+    if (devs.size() > 1) bad("--gfa runs on one GPU: give one device (--gpus 1).");
+    if (o.s("--gfa").empty()) bad("--gfa needs the name of the GFA file to write.");
+    if (o.i("--gfa-max-hang") < 0 || o.i("--gfa-min-overlap") < 0 || o.i("--gfa-fuzz") < 0) bad("The values of --gfa-max-hang, --gfa-min-overlap and --gfa-fuzz must be >=0.");
   }
   if (realign) {   // refused before a handle exists
     if (o.i("--realign-band") < 0) bad("The realignment band must be >=0.");
@@ -532,6 +554,12 @@ int main(int argc, char** argv) {
     sink.realign = &RA;
     if (correct) chk(E.h, mhap_correct_begin(E.h, RA.bases.data(), (int64_t)RA.bases.size(), RA.ids.data(), RA.offsets.data(), RA.lengths.data(),
                                              (int64_t)RA.ids.size(), &RA.correct));
+    if (gfa) {
+      mhap_graph_params gp;
+      mhap_graph_default_params(&gp);
+      gp.max_hang = o.i("--gfa-max-hang"); gp.min_ovlp = o.i("--gfa-min-overlap"); gp.fuzz = o.i("--gfa-fuzz");
+      chk(E.h, mhap_graph_begin(E.h, RA.ids.data(), RA.lengths.data(), (int64_t)RA.ids.size(), &gp, &RA.graph));
+    }
   }
   const double t_score = now();
   if (o.s("-q").empty()) {
@@ -613,6 +641,44 @@ int main(int argc, char** argv) {
     fprintf(stderr, "Corrected %lld reads: %lld bases in, %lld out; %lld substitutions, %lld deletions, %lld insertions, %lld positions of low coverage; skipped_views = %lld\n",
             (long long)nr, tot[0], tot[1], tot[2], tot[3], tot[4], tot[5], (long long)skipped);
     fprintf(stderr, "Time (s) to vote and correct: %g\n", RA.correct_seconds);
+  }
+  if (RA.graph) {   // the list and its reduction, after the last batch has been classed; the GFA file is all it writes
+    const double tg = now();
+    const int64_t nr = (int64_t)RA.ids.size();
+    int64_t gc[MHAP_GRAPH_COUNTS];
+    chk(E.h, mhap_graph_finish(RA.graph, gc));
+    const int64_t na = gc[8];
+    std::vector<int32_t> rows((size_t)std::max<int64_t>(na, 1) * 7);
+    std::vector<uint8_t> contained((size_t)std::max<int64_t>(nr, 1));
+    chk(E.h, mhap_graph_copy_arcs(RA.graph, rows.data()));
+    chk(E.h, mhap_graph_copy_read_flags(RA.graph, contained.data()));
+    mhap_graph_free(RA.graph);
+    RA.graph = nullptr;
+    FILE* f = fopen(o.s("--gfa").c_str(), "wb");
+    if (!f) die("cannot write " + o.s("--gfa"));
+    std::string text = "H\tVN:Z:1.0\n";
+    char line[128];
+    for (int64_t r = 0; r < nr; r++) {
+      if (contained[(size_t)r]) continue;
+      text += "S\t" + std::to_string(RA.ids[(size_t)r]) + "\t*\tLN:i:" + std::to_string(RA.lengths[(size_t)r]) + "\n";
+      if (text.size() > (8u << 20)) { fwrite(text.data(), 1, text.size(), f); text.clear(); }
+    }
+    for (int64_t i = 0; i < na; i++) {
+      if (!rows[(size_t)i * 7 + 6]) continue;
+      const int len = mhap_format_gfa_link(rows.data() + 7 * i, RA.ids.data(), line, sizeof line);
+      if (len < 0 || (size_t)len >= sizeof line) die("mhap_format_gfa_link failed");
+      text.append(line, (size_t)len);
+      text.push_back('\n');
+      if (text.size() > (8u << 20)) { fwrite(text.data(), 1, text.size(), f); text.clear(); }
+    }
+    fwrite(text.data(), 1, text.size(), f);
+    if (fclose(f) != 0) die("cannot write " + o.s("--gfa"));
+    RA.graph_seconds += now() - tg;
+    fprintf(stderr, "String graph of %lld overlaps: %lld none, %lld internal, %lld contained (from), %lld contained (to), %lld short, %lld dovetail; "
+                    "%lld contained reads, %lld arcs, %lld reduced, %lld final\n",
+            (long long)gc[0], (long long)gc[1], (long long)gc[2], (long long)gc[3], (long long)gc[4], (long long)gc[5], (long long)gc[6],
+            (long long)gc[7], (long long)gc[8], (long long)gc[9], (long long)gc[10]);
+    fprintf(stderr, "Time (s) to class, build and reduce the graph: %g\n", RA.graph_seconds);
   }
   fprintf(stderr, "Total time (s): %g\n", now() - t_total);
   // outputFinalStat (MhapMain.java:572-590); the inverted-index counters have no brute-force analogue
