@@ -535,10 +535,13 @@ int mhap_align_paths_from_runs(const int64_t* op_offsets /* n + 1 */, int64_t n,
  * realigned records and the paths object of one mhap_realign_records_paths call (or mhap_align_paths_from_runs), any number of times,
  * n = 0 included; the runs go up again, 4 bytes each, and one wave per accepted view adds its votes (correct_kernels.hip).  A record's
  * reads are found by id as mhap_realign_plan finds them; MHAP_E_INVALID, naming the record, for an id not among read_ids, an alen or
- * blen that disagrees with the read's length, a paths object of another n, or runs that are not a path between (a1, the first column)
- * and (a2, the last) beginning and ending with '='; a refused call has cast no vote.  mhap_correct_finish makes the call for every
- * read on the device (min_cov >= 1) and returns out_offsets (read r's corrected bytes are [out_offsets[r], out_offsets[r + 1]) of the
- * output), the six counts per read and the views skipped so far; it may be repeated, and more records may be added after it.
+ * blen that disagrees with the read's length, a paths object of another n, runs that are not a path between (a1, the first column)
+ * and (a2, the last) beginning and ending with '=', or two adjacent runs of one code unless the earlier one has the length 2^28 - 1
+ * (a split run, the paths' own rule above: the vote takes the later run for the continuation of the earlier, so a hand-made path
+ * that merely repeats a code would vote differently from the columns it spells); a refused call has cast no vote.
+ * mhap_correct_finish makes the call for every read on the device (min_cov >= 1) and returns out_offsets (read r's corrected bytes
+ * are [out_offsets[r], out_offsets[r + 1]) of the output), the six counts per read and the views skipped so far; it may be repeated,
+ * and more records may be added after it.
  * mhap_correct_copy writes the out_offsets[n_reads] bytes of the last finish.  Votes cross to the host only through
  * mhap_correct_votes: the 24 counters of every position of read read_index (its position in read_ids), position-major, in the order
  * base A C G T, del, span, ins[0] A C G T, ins[1] .., ins[2] .., ins[3] .., and the two spare ones, which stay 0. */

@@ -35,7 +35,8 @@ namespace mhap {
 namespace {
 
 constexpr uint32_t OP_I = 1, OP_D = 2, OP_EQ = 7, OP_X = 8;   // BAM's codes (realign_kernels.hip)
-constexpr int CK_WORDS = 12;          // words per position: 24 counters of 16 bits
+constexpr uint32_t RUN_MAX = (1u << 28) - 1;   // the longest run of a path: a longer one is split into several of its code
+constexpr int CK_WORDS = 12;         // words per position: 24 counters of 16 bits
 constexpr int CK_KI = 4;              // inserted bytes voted on per junction
 constexpr uint32_t CK_CAP = 65535;    // accepted views per target
 constexpr int CK_T = 256;             // threads of the call kernel
@@ -352,6 +353,15 @@ extern "C" int mhap_correct_add(mhap_correct_session* s, const mhap_record* recs
     }
     ok = ok && i0 >= 0 && j0 >= 0 && r.a2 < r.alen && j1 < r.blen && rows == (int64_t)r.a2 - i0 + 1 && cols == j1 - j0 + 1;
     if (!ok) { undo(); return bad(q, "has runs that are not a path between its aligned ends"); }
+    // two adjacent runs of one code are one run split at 2^28 - 1 columns, or no path of the aligner's: the kernel takes the second
+    // for the continuation of the first
+    for (int64_t u = o0 + 1; u < o1; u++) {
+      const uint32_t prev = paths->ops[(size_t)u - 1];
+      if ((prev & 15u) == (paths->ops[(size_t)u] & 15u) && (prev >> 4) != RUN_MAX) {
+        undo();
+        return bad(q, "has runs " + std::to_string(u - 1 - o0) + " and " + std::to_string(u - o0) + " of one code, and the earlier is not a run split at 2^28 - 1 columns");
+      }
+    }
     for (int view = 0; view < 2; view++) {
       const int64_t target = idx[view];
       if (s->views[(size_t)target] >= CK_CAP) { skipped++; continue; }

@@ -15,6 +15,7 @@ from align_ref import rc_bytes
 OP_I, OP_D, OP_EQ, OP_X = 1, 2, 7, 8
 KI = 4
 CAP = 65535
+RUN_MAX = (1 << 28) - 1                   # the longest run of a path; a longer one is split into several of its code
 NCOUNT = 24
 DEL, SPAN, INS0 = 4, 5, 6
 ACGT = b"ACGT"
@@ -109,6 +110,16 @@ class Consensus:
             np.add.at(self.votes[target], (arr[:, 0], arr[:, 1]), 1)
 
     def add(self, records, op_offsets, ops):
+        # refused before any vote: two adjacent runs of one code unless the earlier is a run split at 2^28 - 1
+        ops, starts = np.asarray(ops, np.int64), np.asarray(op_offsets, np.int64)
+        same = ((ops[:-1] & 15) == (ops[1:] & 15)) & (ops[:-1] >> 4 != RUN_MAX)
+        firsts = starts[(starts > 0) & (starts < len(ops))]
+        same[firsts - 1] = False                                            # the last run of one record and the first of the next
+        for u in np.flatnonzero(same).tolist():
+            q = int(np.searchsorted(starts, u, side="right")) - 1          # the record of run u
+            if int(records[q]["from_id"]) != int(records[q]["to_id"]):
+                raise ValueError(f"record {q} has runs {u - int(starts[q])} and {u + 1 - int(starts[q])} of one code, and the earlier is "
+                                 "not a run split at 2^28 - 1 columns")
         for q in range(len(records)):
             rec = records[q]
             runs = tuple(int(x) for x in ops[int(op_offsets[q]):int(op_offsets[q + 1])])

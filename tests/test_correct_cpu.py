@@ -14,6 +14,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import align_paths_ref as pref  # noqa: E402
 import consensus_ref as cref  # noqa: E402
+import handmade_paths as hp  # noqa: E402
 from align_ref import rc_bytes  # noqa: E402
 
 A, C, G, T, N = b"ACGTN"
@@ -209,6 +210,115 @@ def test_records_that_vote_nothing():
     c.add(_record(1, 2, 8, 8, 0, 0, 0, runs), [0, 1], runs)
     c.add(_record(1, 2, 8, 8, 0, 0, 0, runs), [0, 1], runs)         # nothing is de-duplicated
     assert c.votes[0][:, :4].sum() == 16 and c.views == [2, 2]
+
+
+# ---- hand-made paths (tests/handmade_paths.py, what tests/test_correct_paths_gpu.py is built from) ----------------------------------
+
+def _handmade_paths():
+    """(runs, flank_a, flank_b) of every shape the helper is used for: runs_with at both parities of every kind, the parity shift
+    included, gap runs next to each other, long runs, a path of one run."""
+    out = []
+    for kind in "IDX=":
+        for at, total in ((62, 129), (63, 129), (64, 129), (65, 129), (127, 131), (128, 131), (1, 3), (2, 5), (4, 9), (5, 11)):
+            if kind == ("=" if at % 2 else "X") and not 2 <= at <= total - 3:
+                continue                                            # no room for the shift
+            out.append((hp.runs_with(kind, 1 + (at + total) % 6, at, total), (at % 4, at % 3), (at % 2, at % 5)))
+    for text in ("5=", "3= 2I 3D 1=", "1= 6D 1I 4D 2=", "2= 200I 1= 65D 1X 64= 1X 63=", "1= 1X 1="):
+        out.append((hp.cigar(text), (2, 1), (0, 3)))
+    return out
+
+
+@pytest.mark.parametrize("to_rc", [0, 1])
+def test_handmade_paths_obey_the_headers_identities(to_rc):
+    """Every path tests/handmade_paths.py makes is one mhap_correct_add accepts: '=' at both ends, no two adjacent runs of one code,
+    the rows and columns of the runs between the record's aligned ends, equal bytes on '=' and different bytes on 'X' columns; the two
+    views of consensus_ref.views_of cover exactly the record's two intervals, one target position after the other; and the votes of
+    consensus_ref.tally obey the coverage identity that the GPU tests assert on the session's counters."""
+    rng = np.random.default_rng(21)
+    for runs, flank_a, flank_b in _handmade_paths():
+        assert hp.check_canonical(runs) == [int(r) for r in runs]
+        s1, s2 = hp.pair_from_runs(rng, runs, flank_a, flank_b)
+        rec = hp.record_for(1, 2, s1, s2, flank_a[0], flank_b[0], runs, to_rc)[0]
+        rows, cols = hp.rows_cols(runs)
+        assert len(s1) == sum(flank_a) + rows and len(s2) == sum(flank_b) + cols
+        assert rec["a1"] == flank_a[0] and rec["a2"] - rec["a1"] + 1 == rows and rec["b2"] - rec["b1"] + 1 == cols
+        assert (rec["alen"], rec["blen"], rec["to_rc"]) == (len(s1), len(s2), to_rc)
+        j0 = rec["blen"] - rec["b2"] - 1 if to_rc else rec["b1"]
+        assert j0 == flank_b[0]
+        i, j = flank_a[0], flank_b[0]
+        for r in runs:
+            for _ in range(r >> 4):
+                if r & 15 in (cref.OP_EQ, cref.OP_X):
+                    assert (s1[i] == s2[j]) == (r & 15 == cref.OP_EQ), (hp.as_text(runs), i, j)
+                i, j = i + (r & 15 != cref.OP_D), j + (r & 15 != cref.OP_I)
+        assert (i, j) == (len(s1) - flank_a[1], len(s2) - flank_b[1])
+        va, vb = cref.views_of(s1, s2, flank_a[0], flank_b[0], runs, bool(to_rc), len(s2))
+        ia, ib = hp.target_intervals([rec])
+        assert [c[1] for c in va if c[0] != "Ins"] == list(range(ia[0], ia[1] + 1)) and ia == (flank_a[0], flank_a[0] + rows - 1)
+        assert [c[1] for c in vb if c[0] != "Ins"] == list(range(ib[0], ib[1] + 1))
+        assert ib == ((flank_b[1], flank_b[1] + cols - 1) if to_rc else (flank_b[0], flank_b[0] + cols - 1))
+        assert va[0][0] == va[-1][0] == vb[0][0] == vb[-1][0] == "M"
+        for view, interval, length in ((va, ia, len(s1)), (vb, ib, len(s2))):
+            votes = np.zeros((length, cref.NCOUNT), np.int64)
+            for t, c in cref.tally(view):
+                votes[t, c] += 1
+            assert hp.coverage_identity(votes, [interval]) == []
+            assert hp.coverage_identity(votes, [interval, interval]) != [] and hp.coverage_identity(votes, []) != []      # (it can fail)
+
+
+def test_runs_with_puts_the_run_where_it_is_asked_for():
+    for kind in "IDX":
+        for at, total in ((62, 129), (63, 129), (64, 129), (65, 129), (127, 131), (128, 131)):
+            for length in (1, 4, 6):
+                runs = hp.runs_with(kind, length, at, total)
+                assert len(runs) == total and runs[at] == hp.run(kind, length)
+                assert all(r >> 4 <= 3 and r & 15 in (cref.OP_EQ, cref.OP_X, cref.OP_I, cref.OP_D) for u, r in enumerate(runs) if u != at)
+                assert sum(r & 15 in (cref.OP_I, cref.OP_D) for u, r in enumerate(runs) if u != at) == (2 if kind == "X" and at % 2 == 0 else 0)
+    with pytest.raises(ValueError):
+        hp.runs_with("I", 1, 0, 5)
+    with pytest.raises(ValueError):
+        hp.runs_with("=", 1, 1, 5)
+    for bad in ("2X 1=", "1= 2I", "1= 2I 3I 1=", "1= 0X 1=", ""):
+        with pytest.raises(ValueError):
+            hp.check_canonical(hp.cigar(bad) if bad != "1= 0X 1=" else [1 << 4 | 7, 0 << 4 | 8, 1 << 4 | 7])
+    assert hp.as_text(hp.cigar("3= 2I1D 10=")) == "3=2I1D10="
+
+
+def test_a_read_made_to_fit_a_given_s2():
+    rng = np.random.default_rng(22)
+    runs = hp.cigar("2= 1X 3D 2= 4I 1=")
+    _, s2 = hp.pair_from_runs(rng, runs, (1, 1), (2, 3))
+    s1, same = hp.pair_from_runs(rng, runs, (1, 1), (2, 3), s2=s2)
+    assert same == s2 and len(s1) == 2 + 10
+    assert s1[1:3] == s2[2:4] and s1[3] != s2[4] and s1[4:6] == s2[8:10] and s1[10] == s2[10]
+
+
+@pytest.mark.parametrize("bad,merged", [("3= 2D 3D 3=", "3= 5D 3="), ("3= 2I 3I 3=", "3= 5I 3="), ("2= 1X 1X 2=", "2= 2X 2="), ("2= 3= 1X 1=", "5= 1X 1=")])
+@pytest.mark.parametrize("to_rc", [0, 1])
+def test_adjacent_runs_of_one_code_are_refused(bad, merged, to_rc):
+    """The paths' rule, now a condition of add: two adjacent runs of one code are refused, by the record's index and before any vote,
+    unless the earlier one is 2^28 - 1 columns long (a split run); the same columns as one run are accepted."""
+    rng = np.random.default_rng(23)
+    good = hp.cigar(merged)
+    s1, s2 = hp.pair_from_runs(rng, good, (1, 2), (2, 1))
+    reads = [s1, rc_bytes(s2) if to_rc else s2]
+    rec = hp.record_for(1, 2, s1, s2, 1, 2, good, to_rc)
+    c = cref.Consensus(reads, [1, 2])
+    runs = good + hp.cigar(bad)
+    with pytest.raises(ValueError, match="record 1 has runs"):
+        c.add(np.concatenate([rec, rec]), [0, len(good), len(runs)], runs)
+    assert c.votes[0].sum() == 0 and c.votes[1].sum() == 0 and c.views == [0, 0] and c.skipped_views == 0
+    same = rec.copy()
+    same["to_id"] = same["from_id"]
+    c.add(same, [0, len(runs) - len(good)], hp.cigar(bad))          # a record of a read with itself votes nothing and is not looked at
+    c.add(np.concatenate([rec, rec]), [0, len(good), 2 * len(good)], good + good)
+    assert c.views == [2, 2]
+    # the last run of one record and the first of the next are not adjacent, and a run of 2^28 - 1 columns may be followed by its code
+    # (a path that long fits no read: add gets as far as looking for its columns)
+    c.add(np.concatenate([rec, rec]), [0, len(good), 2 * len(good)], good + good)
+    split = [cref.RUN_MAX << 4 | cref.OP_EQ, 1 << 4 | cref.OP_EQ]
+    with pytest.raises(IndexError):
+        c.add(rec, [0, 2], split)
 
 
 # ---- the quality condition ----------------------------------------------------------------------------------------------------------

@@ -252,6 +252,88 @@ def test_invalid_records_are_refused_with_their_index(layout):
         mhap_amd.GraphSession(ids, lengths, int_frac_permille=1001)
 
 
+# ---- read tables past the scan's tile of 1 024 vertices --------------------------------------------------------------------------------
+
+def _padded(pad, ids, lengths, recs):
+    """`pad` reads that no record names (ids 1 .. pad, unequal lengths) in front of the given reads, whose ids move up by pad."""
+    recs = recs.copy()
+    recs["from_id"] += pad
+    recs["to_id"] += pad
+    return list(range(1, pad + 1)) + [i + pad for i in ids], [1000 + 7 * k for k in range(pad)] + list(lengths), recs
+
+
+@pytest.mark.parametrize("pad,degree,edge", [(509, 3, 1024), (510, 3, 1024), (511, 3, 1024), (512, 3, 1024), (1023, 3, 2048), (1024, 3, 2048),
+                                             (480, 65, 1024)])
+def test_hub_across_the_edge_of_a_scan_tile(pad, degree, edge):
+    """scan_kernel makes start and fstart 1 024 vertices at a time: `carry` takes the sum from tile to tile, a barrier keeps wave_sum
+    of the tile before from being overwritten while it is read, and start[nv] = carry closes the last segment.  No other test has
+    more than 410 vertices.  Here the vertices of a hub (read `pad` and the reads after it) lie on both sides of vertex 1 024 or
+    2 048, or begin on it; with degree 65 segments of more than a wave's width lie on both sides.  scatter, dedup, place, reduce and
+    find_arc all find a vertex's arcs through these sums."""
+    ids, lengths, recs = _padded(pad, *sg.hub(degree))
+    assert 2 * len(ids) > edge and 2 * pad <= edge < 2 * len(ids)                                      # the precondition
+    arcs, counts, _, _ = _check(ids, lengths, [recs])
+    assert int((arcs[:, 0] == 2 * pad).sum()) == degree and counts["dovetail"] == degree * (degree + 1) // 2
+    assert (arcs[:, 0] >= edge).any() and (arcs[:, 0] < edge).any() == (2 * pad < edge)                # kept arcs at or above the edge
+    assert counts["final"] > 0 and counts["reduced"] == (degree - 1) * degree
+
+
+@pytest.fixture(scope="module", params=[2, 3])
+def big_layout(request):
+    ids, lengths, reads, recs = sg.layout(request.param, n_reads=1100, genome=880000, jitter=300)
+    ref = sg.Graph(ids, lengths)
+    ref.add(recs)
+    ref.finish()
+    return ids, lengths, recs, ref
+
+
+def test_layout_of_1100_reads_in_one_add_and_shuffled_over_three(big_layout):
+    """2 200 vertices: three tiles of the scan, the last one partial, with arcs in all of them, so that the carry into the second and
+    into the third tile is not 0 and start[nv] is the sum of all three."""
+    ids, lengths, recs, ref = big_layout
+    rows = np.asarray(ref.rows, np.int64)
+    assert 2 * len(ids) > 2048 and len(recs) > 5000
+    for lo, hi in ((0, 1024), (1024, 2048), (2048, 2200)):                                             # the precondition
+        tile = rows[(rows[:, 0] >= lo) & (rows[:, 0] < hi)]
+        assert tile[:, 6].any() and tile[:, 5].any(), (lo, len(tile))
+    with mhap_amd.GraphSession(ids, lengths) as gs:
+        gs.add(recs)
+        gs.finish()
+        one = _compare(gs, ref, recs)
+    perm = np.random.default_rng(12).permutation(len(recs))
+    parts = [perm[:len(perm) // 3], perm[len(perm) // 3:len(perm) // 3 + 1], perm[len(perm) // 3 + 1:]]
+    refs = sg.Graph(ids, lengths)
+    with mhap_amd.GraphSession(ids, lengths) as gs:
+        for part in parts:
+            gs.add(recs[part])
+            refs.add(recs[part])
+        gs.finish()
+        refs.finish()
+        shuffled = _compare(gs, refs, recs[perm])
+    assert sg.strip_q(shuffled[0]) == sg.strip_q(one[0]) and shuffled[1] == one[1] and shuffled[2].tolist() == one[2].tolist() and shuffled[3] == one[3]
+    high = one[0][one[0][:, 0] >= 2048]
+    assert high[:, 6].any() and high[:, 5].any()
+
+
+@pytest.mark.parametrize("n_reads", [511, 512, 513])
+def test_read_counts_at_the_edge_of_a_scan_tile(n_reads):
+    """nv = 1 022, 1 024 and 1 026: the last tile is almost full, full, and two vertices long, and start[nv] is written after one tile
+    and after two.  The arcs are those of a hub of degree 2 on the last three reads; finished twice."""
+    ids, lengths, recs = _padded(n_reads - 3, *sg.hub(2))
+    assert len(ids) == n_reads
+    ref = sg.Graph(ids, lengths)
+    ref.add(recs)
+    ref.finish()
+    with mhap_amd.GraphSession(ids, lengths) as gs:
+        gs.add(recs)
+        gs.finish()
+        a = _compare(gs, ref, recs)
+        gs.finish()
+        b = _compare(gs, ref, recs)
+    assert a[0].tolist() == b[0].tolist() and a[1] == b[1] and a[3] == b[3]
+    assert a[1]["arcs"] == 6 and int(a[0][:, 0].max()) == 2 * n_reads - 1
+
+
 # ---- end to end ----------------------------------------------------------------------------------------------------------------------
 
 def _cli(args, timeout=600):
