@@ -559,7 +559,7 @@ void mhap_correct_free(mhap_correct_session* s);
 
 /* The layout step that follows an overlapper (Myers 2005): every realigned overlap is classed, contained reads are set aside, the
  * dovetails become the arcs of a bidirected graph and the arcs that a two-arc path explains are removed.  Left out: read trimming,
- * chimera detection, tip and bubble removal, unitig sequences.  Everything is integer arithmetic (sums and products of lengths in
+ * chimera detection, tip and bubble removal.  Everything is integer arithmetic (sums and products of lengths in
  * int64); the only floating comparison is score < min_identity on the record's double.
  *
  * Input.  A table of reads (read_ids[r], lengths[r]; no bases), realigned records (out[q] of mhap_realign_records) and the parameters
@@ -614,7 +614,61 @@ void mhap_correct_free(mhap_correct_session* s);
  * GFA 1.  `H\tVN:Z:1.0`, then `S\t<id>\t*\tLN:i:<length>` for every read that is not contained, in read_ids order, then one L line per
  * final arc in list order; every line ends with '\n' and ids are numeric.  The text depends on the set of records only.
  * mhap_format_gfa_link (no GPU) writes the L line of one row, `L\t<id(u)>\t<+|->\t<id(v)>\t<+|->\t<ol>M` without the newline, '-' for
- * an odd vertex: snprintf semantics as mhap_format_paf; -1 for a null pointer. */
+ * an odd vertex: snprintf semantics as mhap_format_paf; -1 for a null pointer.
+ *
+ * ---- unitigs: the final arcs compacted into chains, with their sequences -----------------------------------------------------------
+ * Tip removal, bubble popping, chimera detection and a consensus over a unitig's reads are not part of this: a unitig is spelled
+ * from the reads as stored (the correction stage may be run before).  Integer arithmetic; offsets and lengths in bases are int64.
+ *
+ * Input.  The state of a session after a mhap_graph_finish: the arc list with its `final` flags, the contained flags, the read
+ * lengths.  Only final arcs count.  `final` is symmetric (u -> v is final exactly when v ^ 1 -> u ^ 1 is), so in-degree(v) =
+ * out-degree(v ^ 1); no arc joins the two strands of one read (such a record classes as NONE).
+ *
+ * Joined arcs.  next(v) = w when v has exactly one final out-arc v -> w and w ^ 1 has exactly one final out-arc (w has in-degree 1);
+ * otherwise v has no next.  prev is the inverse of next, and next(v) = w <=> next(w ^ 1) = v ^ 1.  A contained read has no vertices
+ * here; every other read has both of its vertices in play, a read that no arc touches included.
+ *
+ * Unitigs.  The maximal chains of next, and the cycles of next.  Every chain has a twin, its reverse complement (the vertices ^ 1 in
+ * reverse order), with which it shares no read.  A linear chain is kept in the orientation with head < tail ^ 1; a cycle in the
+ * orientation that holds the smallest vertex number of the cycle and its twin, and it starts at that vertex.  Unitigs are numbered
+ * from 0 in ascending order of their first vertex, linear and circular together.
+ *
+ * Layout.  Member i of a unitig is a vertex v_i with span_i: the len of the joined arc v_i -> v_i+1; for the last member of a circular
+ * unitig the len of the closing arc back to member 0; for the last member of a linear unitig the whole read length.  offset_i is the
+ * sum of the spans before it, the unitig's length the sum of all its spans.  (1 <= len < length(read(u)) for every arc, so a span
+ * never exceeds its read.)
+ *
+ * Sequence.  For each member in order, the first span_i bytes of its read in the member's orientation, concatenated: an even vertex
+ * uses the stored bytes, an odd vertex the reverse complement through the table of Utils.rc that the realignment and correction
+ * kernels use for to_rc reads (upper-cased, complemented; a byte the table does not know stays as it is).
+ *
+ * Links.  Every final arc that is not a joined arc; it leaves the tail of a unitig or of a twin and enters the head of a unitig or
+ * of a twin.  A row is 6 int32 {from_unitig, from_orient, to_unitig, to_orient, ol, arc}: orient 0 is the kept orientation, 1 the
+ * twin, arc the index in the arc list.  Links are in arc-list order; circular unitigs have none.
+ *
+ * Counts.  MHAP_UNITIG_COUNTS int64: unitigs, circular unitigs, members, joined arcs, links, bases of the longest unitig, bases of
+ * all unitigs.  Everything above depends on the set of records only, not on their order or their split over adds.
+ *
+ * The calls.  mhap_graph_unitigs needs a completed finish with no record added after it (MHAP_E_INVALID otherwise) and builds
+ * everything anew on the device (graph_kernels.hip: one lane per vertex for next / prev / span; list ranking by pointer doubling,
+ * ceil(log2(max(2, vertices in play))) rounds queued without a host wait, once for the chains, once to carry a cycle's smallest
+ * vertex round it and once for the cycles cut there; numbering and placement by prefix sums, no ordering by atomics).  A later
+ * mhap_graph_finish invalidates the unitigs: the copy and spell calls return MHAP_E_INVALID until mhap_graph_unitigs has run again.
+ * mhap_graph_unitigs_info: the sizes the copy calls need (n_unitigs -1 while invalid); any pointer may be NULL.
+ * mhap_graph_copy_unitigs: member k's of unitig i are unitig_start[i] .. unitig_start[i + 1].  mhap_graph_spell writes the sequences
+ * of all unitigs back to back (unitig i at the sum of the lengths before it); read r's bytes are bases[offsets[r], offsets[r] +
+ * lengths[r]), and a read outside the n_bases bases refuses the call with a message.  mhap_graph_spell_device is the same with
+ * `bases` already on the handle's device (offsets and out on the host).  The spelling kernel runs over tiles of MHAP_SPELL_CHUNK
+ * output bytes, which find their members by binary search, so neither a long read nor a run of short spans serialises; every
+ * output byte has exactly one writer.  Device memory, from the first mhap_graph_unitigs to mhap_graph_free: 130 bytes per vertex
+ * (two per read), 12 per arc, 24 per member, 17 per unitig, 24 per link; the spell calls add 8 per read, the output, and
+ * mhap_graph_spell the bases.
+ *
+ * GFA 1 of the unitig graph (a second text: the one above is unchanged).  `H\tVN:Z:1.0`; per unitig k
+ * `S\tutg%06d{l|c}\t<sequence>\tLN:i:<length>\tnr:i:<members>` with the number k + 1 and l for linear, c for circular, followed by
+ * its members as `a\t<utg name>\t<offset>\t<read id>:1-<span>\t<+|->\t<span>`; last one `L\t<utg>\t<+|->\t<utg>\t<+|->\t<ol>M` per link in
+ * link order ('-' for the twin).  Every line ends with '\n'.  mhap_format_gfa_unitig_link (no GPU) writes the L line of one link row
+ * without the newline: snprintf semantics, -1 for a null pointer. */
 typedef struct mhap_graph_params {
   int32_t max_hang, int_frac_permille, min_ovlp, fuzz;
   double min_identity;
@@ -632,6 +686,17 @@ int mhap_graph_copy_classes(mhap_graph_session* s, uint8_t* classes /* n_records
 int mhap_graph_copy_read_flags(mhap_graph_session* s, uint8_t* flags /* n_reads */);
 void mhap_graph_free(mhap_graph_session* s);
 int mhap_format_gfa_link(const int32_t* row7, const int64_t* read_ids, char* out, size_t cap);
+#define MHAP_UNITIG_COUNTS 7
+#define MHAP_SPELL_CHUNK 4096
+int mhap_graph_unitigs(mhap_graph_session* s, int64_t* counts /* MHAP_UNITIG_COUNTS */);
+int mhap_graph_unitigs_info(const mhap_graph_session* s, int64_t* n_unitigs, int64_t* n_members, int64_t* n_links, int64_t* n_bases);
+int mhap_graph_copy_unitigs(mhap_graph_session* s, int64_t* unitig_start /* n + 1 */, int64_t* unitig_len /* n */, uint8_t* circular /* n */);
+int mhap_graph_copy_layout(mhap_graph_session* s, int32_t* vertex /* members */, int64_t* offset /* members */, int32_t* span /* members */);
+int mhap_graph_copy_links(mhap_graph_session* s, int32_t* rows /* links x 6 */);
+int mhap_graph_spell(mhap_graph_session* s, const uint8_t* bases, int64_t n_bases, const int64_t* offsets /* n_reads */, uint8_t* out /* all bases */);
+int mhap_graph_spell_device(mhap_graph_session* s, const uint8_t* device_bases, int64_t n_bases, const int64_t* offsets /* n_reads */,
+                            uint8_t* out /* all bases */);
+int mhap_format_gfa_unitig_link(const int32_t* row6, char* out, size_t cap);
 
 /* KmerStatSimulator's pair statistics on the GPU (J/main/KmerStatSimulator.java:163-196).  pairs: n rows of 4 int64 {a_off, a_len,
  * b_off, b_len}; a = bases[a_off, a_off + a_len) is the first read, b the second.  skip: n_skip k-mers of k bytes each, back to back, in

@@ -34,6 +34,9 @@ from .api import (  # noqa: F401
     string_graph,
     format_gfa,
     format_gfa_link,
+    unitigs,
+    format_unitig_gfa,
+    format_gfa_unitig_link,
     pair_kmer_stats,
     records_to_lines,
     load_library,

@@ -77,6 +77,8 @@ EXPORTED_SYMBOLS = [
     "mhap_correct_begin", "mhap_correct_add", "mhap_correct_finish", "mhap_correct_copy", "mhap_correct_votes", "mhap_correct_free",
     "mhap_graph_default_params", "mhap_graph_begin", "mhap_graph_add", "mhap_graph_finish", "mhap_graph_info", "mhap_graph_copy_arcs",
     "mhap_graph_copy_classes", "mhap_graph_copy_read_flags", "mhap_graph_free", "mhap_format_gfa_link",
+    "mhap_graph_unitigs", "mhap_graph_unitigs_info", "mhap_graph_copy_unitigs", "mhap_graph_copy_layout", "mhap_graph_copy_links",
+    "mhap_graph_spell", "mhap_graph_spell_device", "mhap_format_gfa_unitig_link",
     "mhap_pair_kmer_stats", "mhap_pair_kmer_stats_paths", "mhap_ksim_create", "mhap_ksim_next", "mhap_ksim_error", "mhap_ksim_destroy",
     "mhap_ksim_dev_create", "mhap_ksim_dev_destroy", "mhap_ksim_dev_pair_stats", "mhap_ksim_dev_trials",
 ]
@@ -178,6 +180,14 @@ def load_library(build_if_missing=True):
     lib.mhap_graph_free.restype = None
     lib.mhap_graph_free.argtypes = [C.c_void_p]
     lib.mhap_format_gfa_link.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+    lib.mhap_graph_unitigs.argtypes = [C.c_void_p, C.c_void_p]
+    lib.mhap_graph_unitigs_info.argtypes = [C.c_void_p] + [C.c_void_p] * 4
+    lib.mhap_graph_copy_unitigs.argtypes = [C.c_void_p] + [C.c_void_p] * 3
+    lib.mhap_graph_copy_layout.argtypes = [C.c_void_p] + [C.c_void_p] * 3
+    lib.mhap_graph_copy_links.argtypes = [C.c_void_p, C.c_void_p]
+    for name in ("mhap_graph_spell", "mhap_graph_spell_device"):
+        getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.mhap_format_gfa_unitig_link.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     for name in EXPORTED_SYMBOLS:
         getattr(lib, name)  # AttributeError here = header/library mismatch
     # a stale library next to newer host code (or the reverse) must not get as far as a struct copy
@@ -641,6 +651,10 @@ GRAPH_COUNTS = ("records",) + GRAPH_CLASSES + ("contained_reads", "arcs", "reduc
 GRAPH_ARC_FIELDS = ("u", "v", "len", "ol", "q", "reduced", "final")
 
 
+UNITIG_COUNTS = ("unitigs", "circular", "members", "joined_arcs", "links", "longest_bases", "total_bases")   # mhap_graph_unitigs' counts
+UNITIG_LINK_FIELDS = ("from_unitig", "from_orient", "to_unitig", "to_orient", "ol", "arc")
+
+
 class _GraphParams(C.Structure):
     _fields_ = [("max_hang", C.c_int32), ("int_frac_permille", C.c_int32), ("min_ovlp", C.c_int32), ("fuzz", C.c_int32),
                 ("min_identity", C.c_double)]
@@ -668,6 +682,41 @@ def format_gfa(read_ids, lengths, contained, arcs):
     return "".join(out)
 
 
+def format_gfa_unitig_link(row):
+    """The GFA L line of one link row of the unitig graph (mhap_format_gfa_unitig_link, no GPU), without the newline."""
+    lib = load_library()
+    row = np.ascontiguousarray(row, dtype=np.int32).reshape(6)
+    buf = C.create_string_buffer(96)
+    n = lib.mhap_format_gfa_unitig_link(_ptr(row), buf, C.c_size_t(96))
+    if n < 0 or n >= 96:
+        raise MhapError("mhap_format_gfa_unitig_link failed")
+    return buf.value.decode()
+
+
+def unitig_counts_line(counts):
+    """The one stderr line of the unitigs (the driver prints the same); counts: the MHAP_UNITIG_COUNTS values in order."""
+    c = [int(x) for x in counts]
+    return (f"Unitigs: {c[0]} unitigs ({c[1]} circular) of {c[2]} reads, {c[3]} joined arcs, {c[4]} links; longest {c[5]} bases, "
+            f"{c[6]} bases in all")
+
+
+def format_unitig_gfa(read_ids, unitigs, sequences):
+    """GFA 1 text of the unitig graph: the header, per unitig its S line and an `a` line per member, then an L line per link.
+    unitigs: the dict of GraphSession.unitigs(); sequences: a list of bytes, one per unitig.  The "unitigs" part of the string-graph
+    section of include/mhap_hip.h has the format."""
+    ids = np.asarray(read_ids).tolist()
+    start, ulen, circ = unitigs["unitig_start"].tolist(), unitigs["unitig_len"].tolist(), unitigs["circular"].tolist()
+    vertex, offset, span = unitigs["vertex"].tolist(), unitigs["offset"].tolist(), unitigs["span"].tolist()
+    out = ["H\tVN:Z:1.0\n"]
+    for k, seq in enumerate(sequences):
+        name = f"utg{k + 1:06d}{'c' if circ[k] else 'l'}"
+        out.append(f"S\t{name}\t{seq.decode('latin-1')}\tLN:i:{ulen[k]}\tnr:i:{start[k + 1] - start[k]}\n")
+        out += [f"a\t{name}\t{offset[m]}\t{ids[vertex[m] >> 1]}:1-{span[m]}\t{'-' if vertex[m] & 1 else '+'}\t{span[m]}\n"
+                for m in range(start[k], start[k + 1])]
+    out += [format_gfa_unitig_link(r) + "\n" for r in np.ascontiguousarray(unitigs["links"], dtype=np.int32).reshape(-1, 6)]
+    return "".join(out)
+
+
 class GraphSession:
     """The string graph of realigned overlaps on the GPU (mhap_graph_begin / _add / _finish / _copy_*; the contract is the "string
     graph" section of include/mhap_hip.h): every record is classed, contained reads are set aside, the dovetails become arcs and
@@ -677,6 +726,8 @@ class GraphSession:
             gs.add(records)                       # what realign_records returned; any number of times
             arcs, counts = gs.finish()            # int32 (n, 7) of GRAPH_ARC_FIELDS, a dict of GRAPH_COUNTS
             text = gs.gfa()
+            u = gs.unitigs()                      # the final arcs compacted into chains: a dict of arrays
+            seqs = gs.unitig_sequences(fasta)     # their sequences, a list of bytes; gs.unitig_gfa(fasta) is the GFA text
 
     handle: a MinHashSearch whose device and stream to use (else one is made and closed with the session)."""
 
@@ -692,6 +743,7 @@ class GraphSession:
             raise MhapError(f"GraphSession: {len(self.ids)} ids and {len(self.lengths)} lengths")
         p = _GraphParams(max_hang, int_frac_permille, min_ovlp, fuzz, min_identity)
         self.arcs = np.zeros((0, 7), np.int32)
+        self.unitigs_table = None
         try:
             self._ms._chk(self._lib.mhap_graph_begin(self._ms._h, _ptr(self.ids) if len(self.ids) else None,
                                                      _ptr(self.lengths) if len(self.ids) else None, C.c_int64(len(self.ids)), C.byref(p),
@@ -709,6 +761,7 @@ class GraphSession:
     def finish(self):
         """(arcs, counts): the de-duplicated arc list as an int32 array (n, 7) of GRAPH_ARC_FIELDS and a dict of GRAPH_COUNTS."""
         counts = np.zeros(len(GRAPH_COUNTS), np.int64)
+        self.unitigs_table = None
         self._ms._chk(self._lib.mhap_graph_finish(self._s, _ptr(counts)))
         self.arcs = np.zeros((int(counts[GRAPH_COUNTS.index("arcs")]), 7), np.int32)
         self._ms._chk(self._lib.mhap_graph_copy_arcs(self._s, _ptr(self.arcs) if len(self.arcs) else None))
@@ -736,6 +789,55 @@ class GraphSession:
     def gfa(self):
         """The GFA 1 text of the last finish."""
         return format_gfa(self.ids, self.lengths, self.contained(), self.arcs)
+
+    def unitigs(self):
+        """The unitigs of the last finish (mhap_graph_unitigs / _copy_*): a dict of unitig_start (n + 1), unitig_len (n), circular (n),
+        the members' vertex, offset, span, the link rows (links, 6) of UNITIG_LINK_FIELDS, and counts, a dict of UNITIG_COUNTS."""
+        counts = np.zeros(len(UNITIG_COUNTS), np.int64)
+        self._ms._chk(self._lib.mhap_graph_unitigs(self._s, _ptr(counts)))
+        n, members, links = (int(counts[UNITIG_COUNTS.index(k)]) for k in ("unitigs", "members", "links"))
+        u = dict(unitig_start=np.zeros(n + 1, np.int64), unitig_len=np.zeros(n, np.int64), circular=np.zeros(n, np.uint8),
+                 vertex=np.zeros(members, np.int32), offset=np.zeros(members, np.int64), span=np.zeros(members, np.int32),
+                 links=np.zeros((links, 6), np.int32), counts=dict(zip(UNITIG_COUNTS, counts.tolist())))
+        opt = lambda a: _ptr(a) if len(a) else None
+        self._ms._chk(self._lib.mhap_graph_copy_unitigs(self._s, _ptr(u["unitig_start"]), opt(u["unitig_len"]), opt(u["circular"])))
+        self._ms._chk(self._lib.mhap_graph_copy_layout(self._s, opt(u["vertex"]), opt(u["offset"]), opt(u["span"])))
+        self._ms._chk(self._lib.mhap_graph_copy_links(self._s, opt(u["links"])))
+        self.unitigs_table = u
+        return u
+
+    def spell_into(self, bases, offsets, out):
+        """mhap_graph_spell: the sequences of all unitigs back to back into the uint8 array `out` (total_bases of the counts long);
+        read r's bytes are bases[offsets[r]:offsets[r] + lengths[r]]."""
+        bases = np.ascontiguousarray(bases, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        if len(offsets) != len(self.ids):
+            raise MhapError(f"GraphSession: {len(offsets)} offsets for {len(self.ids)} reads")
+        if out.dtype != np.uint8 or not out.flags.c_contiguous or (self.unitigs_table is not None and len(out) != self.unitigs_table["counts"]["total_bases"]):
+            raise MhapError("GraphSession.spell_into: out must be a contiguous uint8 array of total_bases bytes")
+        self._ms._chk(self._lib.mhap_graph_spell(self._s, _ptr(bases) if len(bases) else None, C.c_int64(len(bases)),
+                                                 _ptr(offsets) if len(offsets) else None, _ptr(out) if len(out) else None))
+        return out
+
+    def unitig_sequences(self, fasta, query_fasta=None):
+        """The sequence of every unitig, a list of bytes (mhap_graph_spell): `fasta` (and `query_fasta`) hold the session's reads in
+        read_ids order.  Runs unitigs() first when it has not run since the last finish."""
+        u = self.unitigs_table or self.unitigs()
+        bases, _, offsets, _ = _all_reads(fasta, query_fasta)
+        raw = self.spell_into(bases, offsets, np.zeros(int(u["counts"]["total_bases"]), np.uint8)).tobytes()
+        ends = np.cumsum(u["unitig_len"]).tolist()
+        return [raw[e - n:e] for e, n in zip(ends, u["unitig_len"].tolist())]
+
+    def unitig_gfa(self, fasta, query_fasta=None):
+        """The GFA 1 text of the unitig graph of the last finish, with sequences."""
+        seqs = self.unitig_sequences(fasta, query_fasta)
+        return format_unitig_gfa(self.ids, self.unitigs_table, seqs)
+
+    def unitigs_info(self):
+        """(unitigs or -1 while there are none for the last finish, members, links, bases)."""
+        a, b, c, d = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._ms._chk(self._lib.mhap_graph_unitigs_info(self._s, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return a.value, b.value, c.value, d.value
 
     def close(self):
         if self._s:
@@ -765,6 +867,18 @@ def string_graph(records, fasta, query_fasta=None, handle=None, device=0, **para
         gs.add(records)
         arcs, counts = gs.finish()
         return arcs, counts, gs.contained(), gs.gfa()
+
+
+def unitigs(records, fasta, query_fasta=None, handle=None, device=0, **params):
+    """The unitigs of the string graph of realigned records over the reads of `fasta` (and `query_fasta`): (the dict of
+    GraphSession.unitigs(), the sequences as a list of bytes, the GFA text of the unitig graph); params as string_graph's."""
+    _, ids, _, lengths = _all_reads(fasta, query_fasta)
+    with GraphSession(ids, lengths, handle=handle, device=device, **params) as gs:
+        gs.add(records)
+        gs.finish()
+        u = gs.unitigs()
+        seqs = gs.unitig_sequences(fasta, query_fasta)
+        return u, seqs, format_unitig_gfa(ids, u, seqs)
 
 
 def _skip_bytes(skip, k):

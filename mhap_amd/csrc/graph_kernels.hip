@@ -1,5 +1,5 @@
-// graph_kernels.hip — the string graph of the realigned overlaps (mhap_graph_begin / _add / _finish / _copy_* / _free) and the GFA link
-// line.  The contract — the class of a record, the arcs of a dovetail, contained reads, the arc list, the reduction and the final
+// graph_kernels.hip — the string graph of the realigned overlaps (mhap_graph_begin / _add / _finish / _copy_* / _free), its unitigs
+// (mhap_graph_unitigs / _copy_unitigs / _copy_layout / _copy_links / _spell; the kernels' list is in front of them) and the GFA link lines.  The contract — the class of a record, the arcs of a dovetail, contained reads, the arc list, the reduction and the final
 // arcs — is the prose of include/mhap_hip.h ("string graph"); tests/string_graph_ref.py restates it.
 //
 // add: the host finds every record's two reads (and refuses the call before anything is queued), packs the record into 32 bytes and
@@ -24,6 +24,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "device_common.hpp"
 #include "mhap_internal.hpp"
 
 namespace mhap {
@@ -99,7 +100,8 @@ __global__ __launch_bounds__(256) void scatter_kernel(const GArc* __restrict__ a
 }
 
 // start[0 .. n] = the exclusive prefix sums of deg[0 .. n): one workgroup, 1024 values at a time with a carry
-__global__ __launch_bounds__(1024) void scan_kernel(const int32_t* __restrict__ deg, int64_t n, int64_t* __restrict__ start) {
+template <class T>
+__global__ __launch_bounds__(1024) void scan_kernel(const T* __restrict__ deg, int64_t n, int64_t* __restrict__ start) {
   __shared__ int64_t wave_sum[16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int64_t carry = 0;
@@ -243,6 +245,261 @@ __global__ __launch_bounds__(256) void flags_kernel(const uint32_t* __restrict__
   if ((threadIdx.x & 63) == 0 && m) atomicAdd(counts + GC_CONTAINED, (unsigned long long)__popcll(m));
 }
 
+// ---- unitigs ("unitigs" in the string-graph section of include/mhap_hip.h; tests/unitig_ref.py restates it) -------------------------
+//   outdeg_kernel    one lane per vertex over its segment of the list: the final arcs, and the target and index of the only one
+//   next_kernel      one lane per vertex: next, span, and prev of the target (which has one arc in, so one writer)
+//   rank_init / rank_round   pointer doubling towards the head: (pointer, members, bases) between a vertex and the vertex it points at;
+//                    a head points at itself with (0, 0), so it is a fixed point and every round reads one buffer and writes the other
+//   cyc_init / min_round     a vertex whose pointer has not reached a head is on a cycle; the same doubling carries the smallest vertex
+//                    of the 2^k vertices that end at it; cut_init makes that vertex a head and the rank rounds run once more
+//   tails_kernel     the last member tells its head the tail, the members and the bases;  select_kernel keeps a head by the rule
+//   three scans      the unitig's number, its first member, its first base;  *_scatter: the tables in their canonical places
+//   linkflag_kernel -> scan -> link_scatter: the final arcs that are not joined, in list order
+//   spell_kernel     one workgroup per SPELL_CHUNK bytes of the output, 16 per lane, found in the members by binary search: two lanes
+//                    search all members for the tile's ends, every lane then searches between them
+enum { UC_CIRCULAR = 0, UC_JOINED = 1, UC_LONGEST = 2, UC_DEVICE = 3 };
+enum { SPELL_CHUNK = MHAP_SPELL_CHUNK, SPELL_T = SPELL_CHUNK / 16 };
+
+__global__ __launch_bounds__(256) void outdeg_kernel(int64_t nv, const int64_t* __restrict__ fstart, const int32_t* __restrict__ V,
+                                                     const int32_t* __restrict__ rows, int32_t* __restrict__ fout, int32_t* __restrict__ cand,
+                                                     int32_t* __restrict__ carc) {
+  const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (v >= nv) return;
+  int32_t n = 0, c = -1, a = -1;
+  for (int64_t i = fstart[v], e = fstart[v + 1]; i < e; i++)
+    if (rows[7 * i + 6]) { n++; c = V[i]; a = (int32_t)i; }
+  fout[v] = n; cand[v] = c; carc[v] = a;
+}
+
+// prev is -1 everywhere before the launch
+__global__ __launch_bounds__(256) void next_kernel(int64_t nv, const int32_t* __restrict__ fout, const int32_t* __restrict__ cand,
+                                                   const int32_t* __restrict__ carc, const int32_t* __restrict__ LEN,
+                                                   const int32_t* __restrict__ lengths, int32_t* __restrict__ next, int32_t* __restrict__ prev,
+                                                   int32_t* __restrict__ span, unsigned long long* __restrict__ ucounts) {
+  const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  bool joined = false;
+  if (v < nv) {
+    int32_t w = -1, sp = lengths[v >> 1];
+    if (fout[v] == 1) {
+      const int32_t c = cand[v];
+      if (fout[c ^ 1] == 1) { w = c; sp = LEN[carc[v]]; prev[c] = (int32_t)v; joined = true; }   // (c has one arc in: this one)
+    }
+    next[v] = w; span[v] = sp;
+  }
+  const unsigned long long m = __ballot(joined);
+  if ((threadIdx.x & 63) == 0 && m) atomicAdd(ucounts + UC_JOINED, (unsigned long long)__popcll(m));
+}
+
+// P < 0: the vertex of a contained read, which is in no unitig
+__global__ __launch_bounds__(256) void rank_init_kernel(int64_t nv, const uint32_t* __restrict__ contained, const int32_t* __restrict__ prev,
+                                                        const int32_t* __restrict__ span, int32_t* __restrict__ P, uint32_t* __restrict__ R,
+                                                        unsigned long long* __restrict__ O) {
+  const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (v >= nv) return;
+  const int32_t p = prev[v];
+  if (contained[v >> 1]) { P[v] = -1; R[v] = 0; O[v] = 0; }
+  else if (p < 0) { P[v] = (int32_t)v; R[v] = 0; O[v] = 0; }
+  else { P[v] = p; R[v] = 1; O[v] = (unsigned long long)span[p]; }
+}
+
+// (on a cycle the sums mean nothing and may wrap, which is why they are unsigned; cut_init starts them again)
+__global__ __launch_bounds__(256) void rank_round_kernel(int64_t nv, const int32_t* __restrict__ Pi, const uint32_t* __restrict__ Ri,
+                                                         const unsigned long long* __restrict__ Oi, int32_t* __restrict__ Po,
+                                                         uint32_t* __restrict__ Ro, unsigned long long* __restrict__ Oo) {
+  const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (v >= nv) return;
+  const int32_t p = Pi[v];
+  if (p < 0) { Po[v] = -1; Ro[v] = 0; Oo[v] = 0; return; }
+  Po[v] = Pi[p]; Ro[v] = Ri[v] + Ri[p]; Oo[v] = Oi[v] + Oi[p];
+}
+
+__global__ __launch_bounds__(256) void cyc_init_kernel(int64_t nv, const int32_t* __restrict__ P, const int32_t* __restrict__ prev,
+                                                       uint8_t* __restrict__ cyc, int32_t* __restrict__ Q, int32_t* __restrict__ M) {
+  const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (v >= nv) return;
+  const int32_t p = P[v];
+  const bool c = p >= 0 && prev[p] >= 0;   // after the rounds a chain's vertex points at its head, which has no prev
+  cyc[v] = c ? 1 : 0; Q[v] = c ? prev[v] : -1; M[v] = (int32_t)v;
+}
+
+__global__ __launch_bounds__(256) void min_round_kernel(int64_t nv, const uint8_t* __restrict__ cyc, const int32_t* __restrict__ Qi,
+                                                        const int32_t* __restrict__ Mi, int32_t* __restrict__ Qo, int32_t* __restrict__ Mo) {
+  const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (v >= nv) return;
+  if (!cyc[v]) { Qo[v] = -1; Mo[v] = Mi[v]; return; }
+  const int32_t q = Qi[v];
+  Qo[v] = Qi[q]; Mo[v] = min(Mi[v], Mi[q]);
+}
+
+// the cycle is cut in front of its smallest vertex; a lane writes its own entries only
+__global__ __launch_bounds__(256) void cut_init_kernel(int64_t nv, const uint8_t* __restrict__ cyc, const int32_t* __restrict__ M,
+                                                       const int32_t* __restrict__ prev, const int32_t* __restrict__ span, int32_t* __restrict__ P,
+                                                       uint32_t* __restrict__ R, unsigned long long* __restrict__ O) {
+  const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (v >= nv || !cyc[v]) return;
+  const int32_t p = prev[v];
+  if (M[v] == (int32_t)v) { P[v] = (int32_t)v; R[v] = 0; O[v] = 0; }
+  else { P[v] = p; R[v] = 1; O[v] = (unsigned long long)span[p]; }
+}
+
+// cnt and ulen are 0 everywhere before the launch; a chain has one last member, so a head has one writer
+__global__ __launch_bounds__(256) void tails_kernel(int64_t nv, const int32_t* __restrict__ P, const uint32_t* __restrict__ R,
+                                                    const unsigned long long* __restrict__ O, const int32_t* __restrict__ next,
+                                                    const int32_t* __restrict__ span, const uint8_t* __restrict__ cyc, const int32_t* __restrict__ M,
+                                                    int32_t* __restrict__ tail, int32_t* __restrict__ cnt, int64_t* __restrict__ ulen) {
+  const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (v >= nv) return;
+  const int32_t h = P[v];
+  if (h < 0) return;
+  if (next[v] < 0 || (cyc[v] && next[v] == M[v])) { tail[h] = (int32_t)v; cnt[h] = (int32_t)(R[v] + 1); ulen[h] = (int64_t)(O[v] + (unsigned long long)span[v]); }
+}
+
+__global__ __launch_bounds__(256) void select_kernel(int64_t nv, const int32_t* __restrict__ P, const uint8_t* __restrict__ cyc,
+                                                     const int32_t* __restrict__ M, const int32_t* __restrict__ tail, int32_t* __restrict__ kept,
+                                                     int32_t* __restrict__ cnt, int64_t* __restrict__ ulen, unsigned long long* __restrict__ ucounts) {
+  const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  bool k = false, circ = false;
+  if (v < nv) {
+    if (P[v] == (int32_t)v) {
+      circ = cyc[v] != 0;
+      k = circ ? M[v] < M[v ^ 1] : (int32_t)v < (tail[v] ^ 1);
+      if (!k) { cnt[v] = 0; ulen[v] = 0; }
+      else atomicMax(ucounts + UC_LONGEST, (unsigned long long)ulen[v]);
+    }
+    kept[v] = k ? 1 : 0;
+  }
+  const unsigned long long m = __ballot(k && circ);
+  if ((threadIdx.x & 63) == 0 && m) atomicAdd(ucounts + UC_CIRCULAR, (unsigned long long)__popcll(m));
+}
+
+__global__ __launch_bounds__(256) void linkflag_kernel(int64_t n, const int32_t* __restrict__ rows, const int32_t* __restrict__ next,
+                                                       int32_t* __restrict__ islink) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int32_t* r = rows + 7 * i;
+  islink[i] = (r[6] && next[r[0]] != r[1]) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void unitig_scatter_kernel(int64_t nv, const int32_t* __restrict__ kept, const int64_t* __restrict__ unum,
+                                                             const int64_t* __restrict__ mstart, const int64_t* __restrict__ ulen,
+                                                             const uint8_t* __restrict__ cyc, int64_t* __restrict__ u_start,
+                                                             int64_t* __restrict__ u_len, uint8_t* __restrict__ u_circ) {
+  const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (v >= nv || !kept[v]) return;
+  const int64_t k = unum[v];
+  u_start[k] = mstart[v]; u_len[k] = ulen[v]; u_circ[k] = cyc[v];
+}
+
+__global__ __launch_bounds__(256) void member_scatter_kernel(int64_t nv, const int32_t* __restrict__ P, const uint32_t* __restrict__ R,
+                                                             const unsigned long long* __restrict__ O, const int32_t* __restrict__ span,
+                                                             const int32_t* __restrict__ kept, const int64_t* __restrict__ mstart,
+                                                             const int64_t* __restrict__ bstart, int32_t* __restrict__ m_vertex,
+                                                             int64_t* __restrict__ m_offset, int32_t* __restrict__ m_span, int64_t* __restrict__ m_dst) {
+  const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (v >= nv) return;
+  const int32_t h = P[v];
+  if (h < 0 || !kept[h]) return;
+  const int64_t at = mstart[h] + R[v];
+  m_vertex[at] = (int32_t)v; m_offset[at] = (int64_t)O[v]; m_span[at] = span[v]; m_dst[at] = bstart[h] + (int64_t)O[v];
+}
+
+// a link leaves the tail of a unitig or of a twin and enters the head of one: the chain of u or of u ^ 1 is the kept one
+__global__ __launch_bounds__(256) void link_scatter_kernel(int64_t n, const int32_t* __restrict__ rows, const int32_t* __restrict__ islink,
+                                                           const int64_t* __restrict__ lstart, const int32_t* __restrict__ P,
+                                                           const int32_t* __restrict__ kept, const int64_t* __restrict__ unum,
+                                                           int32_t* __restrict__ links) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n || !islink[i]) return;
+  const int32_t* r = rows + 7 * i;
+  int32_t* o = links + 6 * lstart[i];
+  for (int e = 0; e < 2; e++) {
+    const int32_t x = r[e], h = P[x];
+    const bool own = kept[h] != 0;
+    o[2 * e] = (int32_t)unum[own ? h : P[x ^ 1]];
+    o[2 * e + 1] = own ? 0 : 1;
+  }
+  o[4] = r[3]; o[5] = (int32_t)i;
+}
+
+__device__ inline uint32_t rc_word(uint32_t x, const uint8_t* tab) {   // the four bytes reversed and complemented
+  return (uint32_t)tab[x >> 24] | ((uint32_t)tab[(x >> 16) & 255] << 8) | ((uint32_t)tab[(x >> 8) & 255] << 16) | ((uint32_t)tab[x & 255] << 24);
+}
+
+// One lane per 16 bytes of the output, which begins on a 16-byte boundary.  Where the 16 bytes come from one member and the words
+// around their source lie inside `bases`, they are loaded as aligned words, shifted into place and stored as one uint4; otherwise
+// (a member boundary, the last bytes of the output, the ends of `bases`) they are gathered byte by byte.  Every byte has one writer.
+__global__ __launch_bounds__(SPELL_T) void spell_kernel(const uint8_t* __restrict__ bases, int64_t n_bases, const int64_t* __restrict__ roff,
+                                                        const int32_t* __restrict__ lengths, int64_t n_members,
+                                                        const int32_t* __restrict__ m_vertex, const int32_t* __restrict__ m_span,
+                                                        const int64_t* __restrict__ m_dst, int64_t total, uint8_t* __restrict__ out) {
+  __shared__ uint8_t tab[256];
+  static_assert(SPELL_T == 256, "one lane per entry of the table");
+  __shared__ int64_t edge[2];   // the members that begin at or before the tile's first byte, and at or before its last
+  tab[threadIdx.x] = (uint8_t)rc_char(threadIdx.x);
+  const int64_t tile0 = (int64_t)blockIdx.x * SPELL_CHUNK;
+  if (threadIdx.x < 2) {
+    const int64_t b = threadIdx.x == 0 ? tile0 : min(tile0 + SPELL_CHUNK, total) - 1;
+    int64_t lo = 0, hi = n_members;
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (m_dst[mid] <= b) lo = mid + 1; else hi = mid;
+    }
+    edge[threadIdx.x] = lo;
+  }
+  __syncthreads();
+  const int64_t b0 = tile0 + 16 * (int64_t)threadIdx.x;
+  if (b0 >= total) return;
+  const int nb = (int)min((int64_t)16, total - b0);
+  int64_t lo = edge[0], hi = edge[1];   // the last member that begins at or before b0 (members of span 0 before it begin there too)
+  while (lo < hi) {                     // (a tile lies in a few members: a step or two)
+    const int64_t mid = (lo + hi) >> 1;
+    if (m_dst[mid] <= b0) lo = mid + 1; else hi = mid;
+  }
+  int64_t at = lo - 1;
+  int32_t v = m_vertex[at], sp = m_span[at], L = lengths[v >> 1];
+  int64_t off = roff[v >> 1], j = b0 - m_dst[at];
+  uint32_t w[4] = {0, 0, 0, 0};
+  bool done = false;
+  if (nb == 16 && j + 16 <= sp) {
+    const int64_t s = (v & 1) ? off + L - 16 - j : off + j;
+    const uint8_t* a = bases + s;
+    const unsigned mis = (unsigned)((uintptr_t)a & 3);
+    if (mis == 0) {
+      const uint32_t* p = (const uint32_t*)a;
+      w[0] = p[0]; w[1] = p[1]; w[2] = p[2]; w[3] = p[3];
+      done = true;
+    } else if (s >= (int64_t)mis && s - mis + 20 <= n_bases) {
+      const uint32_t* p = (const uint32_t*)(a - mis);
+      const uint32_t x0 = p[0], x1 = p[1], x2 = p[2], x3 = p[3], x4 = p[4];
+      const unsigned sh = 8 * mis;
+      w[0] = (x0 >> sh) | (x1 << (32 - sh)); w[1] = (x1 >> sh) | (x2 << (32 - sh));
+      w[2] = (x2 >> sh) | (x3 << (32 - sh)); w[3] = (x3 >> sh) | (x4 << (32 - sh));
+      done = true;
+    }
+    if (done && (v & 1)) {
+      const uint32_t t0 = rc_word(w[3], tab), t1 = rc_word(w[2], tab), t2 = rc_word(w[1], tab), t3 = rc_word(w[0], tab);
+      w[0] = t0; w[1] = t1; w[2] = t2; w[3] = t3;
+    }
+  }
+  if (!done) {
+#pragma unroll
+    for (int t = 0; t < 16; t++) {
+      if (t < nb) {
+        while (j >= sp && at + 1 < n_members) {   // (b0 + t < total: a member with this byte follows)
+          at++;
+          v = m_vertex[at]; sp = m_span[at]; L = lengths[v >> 1]; off = roff[v >> 1]; j = 0;
+        }
+        const uint32_t c = (v & 1) ? (uint32_t)tab[bases[off + L - 1 - j]] : (uint32_t)bases[off + j];
+        w[t >> 2] |= c << (8 * (t & 3));
+        j++;
+      }
+    }
+  }
+  if (nb == 16) *(uint4*)(out + b0) = make_uint4(w[0], w[1], w[2], w[3]);
+  else
+    for (int t = 0; t < nb; t++) out[b0 + t] = (uint8_t)(w[t >> 2] >> (8 * (t & 3)));
+}
+
 }  // namespace
 }  // namespace mhap
 
@@ -261,6 +518,10 @@ struct mhap_graph_session {
   std::deque<Pending> pending;
   DevBuf d_lengths, contained, counts;                    // counts: MHAP_GRAPH_COUNTS x uint64, the classes summed over the adds
   DevBuf deg, fill, start, fstart, tmp, keep, U, V, LEN, Q, bt_v, bt_pos, mark, rows;
+  // unitigs: rebuilt by every mhap_graph_unitigs, invalid (n_unitigs < 0) from the next finish on
+  int64_t n_contained = 0, finish_records = 0, n_unitigs = -1, n_members = 0, n_links = 0, n_ubases = 0;
+  DevBuf fout, cand, carc, unext, uprev, uspan, uP[2], uR[2], uO[2], uQ[2], uM[2], cyc, tail, cnt, ulen, kept, unum, mstart, bstart, islink, lstart,
+      ucounts, u_start, u_len, u_circ, m_vertex, m_offset, m_span, m_dst, links, d_roff, d_bases, spelled;
   void reap(bool all) {
     while (!pending.empty() && (all || hipEventQuery(pending.front().ev) == hipSuccess)) {
       (void)hipEventDestroy(pending.front().ev);
@@ -271,7 +532,10 @@ struct mhap_graph_session {
   void release() {
     for (auto& c : chunks) { c.items.release(); c.cls.release(); }
     chunks.clear();
-    for (DevBuf* b : {&d_lengths, &contained, &counts, &deg, &fill, &start, &fstart, &tmp, &keep, &U, &V, &LEN, &Q, &bt_v, &bt_pos, &mark, &rows}) b->release();
+    for (DevBuf* b : {&d_lengths, &contained, &counts, &deg, &fill, &start, &fstart, &tmp, &keep, &U, &V, &LEN, &Q, &bt_v, &bt_pos, &mark, &rows,
+                       &fout, &cand, &carc, &unext, &uprev, &uspan, &uP[0], &uP[1], &uR[0], &uR[1], &uO[0], &uO[1], &uQ[0], &uQ[1], &uM[0], &uM[1], &cyc,
+                       &tail, &cnt, &ulen, &kept, &unum, &mstart, &bstart, &islink, &lstart, &ucounts, &u_start, &u_len, &u_circ, &m_vertex, &m_offset,
+                       &m_span, &m_dst, &links, &d_roff, &d_bases, &spelled}) b->release();
   }
 };
 
@@ -397,6 +661,7 @@ extern "C" int mhap_graph_finish(mhap_graph_session* s, int64_t* counts) {
   if (!counts) { *v.err = std::string(who) + ": null argument"; return MHAP_E_INVALID; }
   (void)hipSetDevice(v.device);
   s->n_arcs = -1;
+  s->n_unitigs = -1;
   const int64_t nv = 2 * s->n_reads;
   hipError_t e = hipSuccess;
   auto fail = [&](const char* what) { return hip_fail(v, who, what, e); };
@@ -411,7 +676,7 @@ extern "C" int mhap_graph_finish(mhap_graph_session* s, int64_t* counts) {
   for (auto& c : s->chunks)
     hipLaunchKernelGGL(count_kernel, dim3(blocks256(2 * c.n)), dim3(256), 0, v.stream, c.items.as<GArc>(), 2 * c.n, s->contained.as<uint32_t>(),
                        s->deg.as<int32_t>());
-  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, v.stream, s->deg.as<int32_t>(), nv, s->start.as<int64_t>());
+  hipLaunchKernelGGL(scan_kernel<int32_t>, dim3(1), dim3(1024), 0, v.stream, s->deg.as<int32_t>(), nv, s->start.as<int64_t>());
   if ((e = hipGetLastError()) != hipSuccess) return fail("launch");
   int64_t n_live = 0, n_arcs = 0;
   if ((e = hipMemcpyAsync(&n_live, s->start.as<int64_t>() + nv, 8, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return fail("download");
@@ -425,7 +690,7 @@ extern "C" int mhap_graph_finish(mhap_graph_session* s, int64_t* counts) {
                        s->start.as<int64_t>(), s->fill.as<int32_t>(), s->tmp.as<GArc>());
   if (nv > 0) hipLaunchKernelGGL(dedup_kernel, dim3((unsigned)nv), dim3(64), 0, v.stream, s->tmp.as<GArc>(), s->start.as<int64_t>(), s->keep.as<uint8_t>(),
                                  s->deg.as<int32_t>());   // (deg has been scanned: it now takes the kept arcs per u)
-  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, v.stream, s->deg.as<int32_t>(), nv, s->fstart.as<int64_t>());
+  hipLaunchKernelGGL(scan_kernel<int32_t>, dim3(1), dim3(1024), 0, v.stream, s->deg.as<int32_t>(), nv, s->fstart.as<int64_t>());
   if ((e = hipGetLastError()) != hipSuccess) return fail("launch");
   if ((e = hipMemcpyAsync(&n_arcs, s->fstart.as<int64_t>() + nv, 8, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return fail("download");
   if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return fail("kernel");
@@ -452,6 +717,8 @@ extern "C" int mhap_graph_finish(mhap_graph_session* s, int64_t* counts) {
   counts[GC_RECORDS] = s->n_records;
   counts[GC_ARCS] = n_arcs;
   s->n_arcs = n_arcs;
+  s->n_contained = (int64_t)hc[GC_CONTAINED];
+  s->finish_records = s->n_records;
   return MHAP_OK;
 }
 
@@ -514,6 +781,218 @@ extern "C" int mhap_graph_copy_read_flags(mhap_graph_session* s, uint8_t* flags)
   return MHAP_OK;
 }
 
+extern "C" int mhap_graph_unitigs(mhap_graph_session* s, int64_t* counts) {
+  const char* who = "mhap_graph_unitigs";
+  if (!s) return MHAP_E_INVALID;
+  HandleView v = handle_view(s->h);
+  if (!counts) { *v.err = std::string(who) + ": null argument"; return MHAP_E_INVALID; }
+  if (s->n_arcs < 0) { *v.err = std::string(who) + ": no mhap_graph_finish has completed"; return MHAP_E_INVALID; }
+  if (s->n_records != s->finish_records) {   // (an add may have set contained flags the list does not know of)
+    *v.err = std::string(who) + ": records were added after the last mhap_graph_finish";
+    return MHAP_E_INVALID;
+  }
+  (void)hipSetDevice(v.device);
+  s->n_unitigs = -1;
+  const int64_t nv = 2 * s->n_reads, na = s->n_arcs;
+  for (int k = 0; k < MHAP_UNITIG_COUNTS; k++) counts[k] = 0;
+  if (nv == 0) { s->n_unitigs = s->n_members = s->n_links = s->n_ubases = 0; return MHAP_OK; }
+  hipError_t e = hipSuccess;
+  auto fail = [&](const char* what) { return hip_fail(v, who, what, e); };
+  const size_t v4 = 4 * (size_t)nv, v8 = 8 * (size_t)nv, s8 = 8 * (size_t)(nv + 1), a4 = 4 * (size_t)std::max<int64_t>(na, 1), as8 = 8 * (size_t)(na + 1);
+  for (DevBuf* b : {&s->fout, &s->cand, &s->carc, &s->unext, &s->uprev, &s->uspan, &s->uP[0], &s->uP[1], &s->uR[0], &s->uR[1], &s->uQ[0], &s->uQ[1],
+                    &s->uM[0], &s->uM[1], &s->tail, &s->cnt, &s->kept})
+    if ((e = b->ensure(v4)) != hipSuccess) return fail("hipMalloc of the vertex tables");
+  for (DevBuf* b : {&s->uO[0], &s->uO[1], &s->ulen})
+    if ((e = b->ensure(v8)) != hipSuccess) return fail("hipMalloc of the vertex tables");
+  for (DevBuf* b : {&s->unum, &s->mstart, &s->bstart})
+    if ((e = b->ensure(s8)) != hipSuccess) return fail("hipMalloc of the vertex tables");
+  if ((e = s->cyc.ensure((size_t)nv)) != hipSuccess || (e = s->ucounts.ensure(8 * UC_DEVICE)) != hipSuccess || (e = s->islink.ensure(a4)) != hipSuccess ||
+      (e = s->lstart.ensure(as8)) != hipSuccess) return fail("hipMalloc of the vertex tables");
+  unsigned long long* d_uc = s->ucounts.as<unsigned long long>();
+  if ((e = hipMemsetAsync(s->uprev.p, 0xFF, v4, v.stream)) != hipSuccess || (e = hipMemsetAsync(s->tail.p, 0xFF, v4, v.stream)) != hipSuccess ||
+      (e = hipMemsetAsync(s->cnt.p, 0, v4, v.stream)) != hipSuccess || (e = hipMemsetAsync(s->ulen.p, 0, v8, v.stream)) != hipSuccess ||
+      (e = hipMemsetAsync(d_uc, 0, 8 * UC_DEVICE, v.stream)) != hipSuccess) return fail("memset");
+  const dim3 gv(blocks256(nv)), b256(256);
+  hipLaunchKernelGGL(outdeg_kernel, gv, b256, 0, v.stream, nv, s->fstart.as<int64_t>(), s->V.as<int32_t>(), s->rows.as<int32_t>(), s->fout.as<int32_t>(),
+                     s->cand.as<int32_t>(), s->carc.as<int32_t>());
+  hipLaunchKernelGGL(next_kernel, gv, b256, 0, v.stream, nv, s->fout.as<int32_t>(), s->cand.as<int32_t>(), s->carc.as<int32_t>(), s->LEN.as<int32_t>(),
+                     s->d_lengths.as<int32_t>(), s->unext.as<int32_t>(), s->uprev.as<int32_t>(), s->uspan.as<int32_t>(), d_uc);
+  // the rounds: 2^rounds >= the vertices in play, which no chain and no cycle exceeds; nothing waits between them
+  const int64_t in_play = std::max<int64_t>(2, 2 * (s->n_reads - s->n_contained));
+  int rounds = 1;
+  while (((int64_t)1 << rounds) < in_play) rounds++;
+  int cur = 0;
+  auto rank_rounds = [&]() {
+    for (int r = 0; r < rounds; r++, cur ^= 1)
+      hipLaunchKernelGGL(rank_round_kernel, gv, b256, 0, v.stream, nv, s->uP[cur].as<int32_t>(), s->uR[cur].as<uint32_t>(),
+                         s->uO[cur].as<unsigned long long>(), s->uP[cur ^ 1].as<int32_t>(), s->uR[cur ^ 1].as<uint32_t>(),
+                         s->uO[cur ^ 1].as<unsigned long long>());
+  };
+  hipLaunchKernelGGL(rank_init_kernel, gv, b256, 0, v.stream, nv, s->contained.as<uint32_t>(), s->uprev.as<int32_t>(), s->uspan.as<int32_t>(),
+                     s->uP[0].as<int32_t>(), s->uR[0].as<uint32_t>(), s->uO[0].as<unsigned long long>());
+  rank_rounds();
+  hipLaunchKernelGGL(cyc_init_kernel, gv, b256, 0, v.stream, nv, s->uP[cur].as<int32_t>(), s->uprev.as<int32_t>(), s->cyc.as<uint8_t>(),
+                     s->uQ[0].as<int32_t>(), s->uM[0].as<int32_t>());
+  int mc = 0;
+  for (int r = 0; r < rounds; r++, mc ^= 1)
+    hipLaunchKernelGGL(min_round_kernel, gv, b256, 0, v.stream, nv, s->cyc.as<uint8_t>(), s->uQ[mc].as<int32_t>(), s->uM[mc].as<int32_t>(),
+                       s->uQ[mc ^ 1].as<int32_t>(), s->uM[mc ^ 1].as<int32_t>());
+  const int32_t* M = s->uM[mc].as<int32_t>();
+  hipLaunchKernelGGL(cut_init_kernel, gv, b256, 0, v.stream, nv, s->cyc.as<uint8_t>(), M, s->uprev.as<int32_t>(), s->uspan.as<int32_t>(),
+                     s->uP[cur].as<int32_t>(), s->uR[cur].as<uint32_t>(), s->uO[cur].as<unsigned long long>());
+  rank_rounds();
+  const int32_t* P = s->uP[cur].as<int32_t>();
+  const uint32_t* R = s->uR[cur].as<uint32_t>();
+  const unsigned long long* O = s->uO[cur].as<unsigned long long>();
+  hipLaunchKernelGGL(tails_kernel, gv, b256, 0, v.stream, nv, P, R, O, s->unext.as<int32_t>(), s->uspan.as<int32_t>(), s->cyc.as<uint8_t>(), M,
+                     s->tail.as<int32_t>(), s->cnt.as<int32_t>(), s->ulen.as<int64_t>());
+  hipLaunchKernelGGL(select_kernel, gv, b256, 0, v.stream, nv, P, s->cyc.as<uint8_t>(), M, s->tail.as<int32_t>(), s->kept.as<int32_t>(),
+                     s->cnt.as<int32_t>(), s->ulen.as<int64_t>(), d_uc);
+  hipLaunchKernelGGL(scan_kernel<int32_t>, dim3(1), dim3(1024), 0, v.stream, s->kept.as<int32_t>(), nv, s->unum.as<int64_t>());
+  hipLaunchKernelGGL(scan_kernel<int32_t>, dim3(1), dim3(1024), 0, v.stream, s->cnt.as<int32_t>(), nv, s->mstart.as<int64_t>());
+  hipLaunchKernelGGL(scan_kernel<int64_t>, dim3(1), dim3(1024), 0, v.stream, s->ulen.as<int64_t>(), nv, s->bstart.as<int64_t>());
+  if (na > 0) hipLaunchKernelGGL(linkflag_kernel, dim3(blocks256(na)), b256, 0, v.stream, na, s->rows.as<int32_t>(), s->unext.as<int32_t>(),
+                                 s->islink.as<int32_t>());
+  hipLaunchKernelGGL(scan_kernel<int32_t>, dim3(1), dim3(1024), 0, v.stream, s->islink.as<int32_t>(), na, s->lstart.as<int64_t>());
+  if ((e = hipGetLastError()) != hipSuccess) return fail("launch");
+  int64_t nu = 0, nm = 0, nb = 0, nl = 0;
+  if ((e = hipMemcpyAsync(&nu, s->unum.as<int64_t>() + nv, 8, hipMemcpyDeviceToHost, v.stream)) != hipSuccess ||
+      (e = hipMemcpyAsync(&nm, s->mstart.as<int64_t>() + nv, 8, hipMemcpyDeviceToHost, v.stream)) != hipSuccess ||
+      (e = hipMemcpyAsync(&nb, s->bstart.as<int64_t>() + nv, 8, hipMemcpyDeviceToHost, v.stream)) != hipSuccess ||
+      (e = hipMemcpyAsync(&nl, s->lstart.as<int64_t>() + na, 8, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return fail("download");
+  if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return fail("kernel");
+  const size_t ub = (size_t)std::max<int64_t>(nu, 1), mb = (size_t)std::max<int64_t>(nm, 1), lb = (size_t)std::max<int64_t>(nl, 1);
+  if ((e = s->u_start.ensure(8 * ub)) != hipSuccess || (e = s->u_len.ensure(8 * ub)) != hipSuccess || (e = s->u_circ.ensure(ub)) != hipSuccess ||
+      (e = s->m_vertex.ensure(4 * mb)) != hipSuccess || (e = s->m_offset.ensure(8 * mb)) != hipSuccess || (e = s->m_span.ensure(4 * mb)) != hipSuccess ||
+      (e = s->m_dst.ensure(8 * mb)) != hipSuccess || (e = s->links.ensure(24 * lb)) != hipSuccess) return fail("hipMalloc of the unitigs");
+  hipLaunchKernelGGL(unitig_scatter_kernel, gv, b256, 0, v.stream, nv, s->kept.as<int32_t>(), s->unum.as<int64_t>(), s->mstart.as<int64_t>(),
+                     s->ulen.as<int64_t>(), s->cyc.as<uint8_t>(), s->u_start.as<int64_t>(), s->u_len.as<int64_t>(), s->u_circ.as<uint8_t>());
+  hipLaunchKernelGGL(member_scatter_kernel, gv, b256, 0, v.stream, nv, P, R, O, s->uspan.as<int32_t>(), s->kept.as<int32_t>(), s->mstart.as<int64_t>(),
+                     s->bstart.as<int64_t>(), s->m_vertex.as<int32_t>(), s->m_offset.as<int64_t>(), s->m_span.as<int32_t>(), s->m_dst.as<int64_t>());
+  if (nl > 0) hipLaunchKernelGGL(link_scatter_kernel, dim3(blocks256(na)), b256, 0, v.stream, na, s->rows.as<int32_t>(), s->islink.as<int32_t>(),
+                                 s->lstart.as<int64_t>(), P, s->kept.as<int32_t>(), s->unum.as<int64_t>(), s->links.as<int32_t>());
+  if ((e = hipGetLastError()) != hipSuccess) return fail("launch");
+  unsigned long long hc[UC_DEVICE];
+  if ((e = hipMemcpyAsync(hc, d_uc, sizeof hc, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return fail("download");
+  if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return fail("kernel");
+  counts[0] = nu; counts[1] = (int64_t)hc[UC_CIRCULAR]; counts[2] = nm; counts[3] = (int64_t)hc[UC_JOINED]; counts[4] = nl;
+  counts[5] = (int64_t)hc[UC_LONGEST]; counts[6] = nb;
+  s->n_members = nm; s->n_links = nl; s->n_ubases = nb;
+  s->n_unitigs = nu;
+  return MHAP_OK;
+}
+
+namespace {
+
+// the session of a copy or spell call: its unitigs must be those of the last finish
+int need_unitigs(mhap_graph_session* s, const char* who) {
+  if (s->n_unitigs >= 0) return MHAP_OK;
+  *handle_view(s->h).err = std::string(who) + ": no mhap_graph_unitigs has completed since the last mhap_graph_finish";
+  return MHAP_E_INVALID;
+}
+
+int null_arg(mhap_graph_session* s, const char* who) {
+  *handle_view(s->h).err = std::string(who) + ": null argument";
+  return MHAP_E_INVALID;
+}
+
+}  // namespace
+
+extern "C" int mhap_graph_unitigs_info(const mhap_graph_session* s, int64_t* n_unitigs, int64_t* n_members, int64_t* n_links, int64_t* n_bases) {
+  if (!s) return MHAP_E_INVALID;
+  if (n_unitigs) *n_unitigs = s->n_unitigs;
+  if (n_members) *n_members = s->n_unitigs < 0 ? 0 : s->n_members;
+  if (n_links) *n_links = s->n_unitigs < 0 ? 0 : s->n_links;
+  if (n_bases) *n_bases = s->n_unitigs < 0 ? 0 : s->n_ubases;
+  return MHAP_OK;
+}
+
+extern "C" int mhap_graph_copy_unitigs(mhap_graph_session* s, int64_t* unitig_start, int64_t* unitig_len, uint8_t* circular) {
+  const char* who = "mhap_graph_copy_unitigs";
+  if (!s) return MHAP_E_INVALID;
+  int rc = need_unitigs(s, who);
+  if (rc != MHAP_OK) return rc;
+  if (!unitig_start) return null_arg(s, who);
+  unitig_start[s->n_unitigs] = s->n_members;
+  if (s->n_unitigs == 0) return MHAP_OK;
+  if (!unitig_len || !circular) return null_arg(s, who);
+  if ((rc = download(s, who, unitig_start, s->u_start.p, 8 * (size_t)s->n_unitigs)) != MHAP_OK) return rc;
+  if ((rc = download(s, who, unitig_len, s->u_len.p, 8 * (size_t)s->n_unitigs)) != MHAP_OK) return rc;
+  return download(s, who, circular, s->u_circ.p, (size_t)s->n_unitigs);
+}
+
+extern "C" int mhap_graph_copy_layout(mhap_graph_session* s, int32_t* vertex, int64_t* offset, int32_t* span) {
+  const char* who = "mhap_graph_copy_layout";
+  if (!s) return MHAP_E_INVALID;
+  int rc = need_unitigs(s, who);
+  if (rc != MHAP_OK) return rc;
+  if (s->n_members == 0) return MHAP_OK;
+  if (!vertex || !offset || !span) return null_arg(s, who);
+  if ((rc = download(s, who, vertex, s->m_vertex.p, 4 * (size_t)s->n_members)) != MHAP_OK) return rc;
+  if ((rc = download(s, who, offset, s->m_offset.p, 8 * (size_t)s->n_members)) != MHAP_OK) return rc;
+  return download(s, who, span, s->m_span.p, 4 * (size_t)s->n_members);
+}
+
+extern "C" int mhap_graph_copy_links(mhap_graph_session* s, int32_t* rows) {
+  const char* who = "mhap_graph_copy_links";
+  if (!s) return MHAP_E_INVALID;
+  const int rc = need_unitigs(s, who);
+  if (rc != MHAP_OK) return rc;
+  if (s->n_links == 0) return MHAP_OK;
+  if (!rows) return null_arg(s, who);
+  return download(s, who, rows, s->links.p, 24 * (size_t)s->n_links);
+}
+
+extern "C" int mhap_graph_spell_device(mhap_graph_session* s, const uint8_t* d_bases, int64_t n_bases, const int64_t* offsets, uint8_t* out) {
+  const char* who = "mhap_graph_spell";
+  if (!s) return MHAP_E_INVALID;
+  HandleView v = handle_view(s->h);
+  const int rc = need_unitigs(s, who);
+  if (rc != MHAP_OK) return rc;
+  if (n_bases < 0 || (s->n_reads > 0 && !offsets)) { *v.err = std::string(who) + ": null or negative argument"; return MHAP_E_INVALID; }
+  for (int64_t r = 0; r < s->n_reads; r++)
+    if (offsets[r] < 0 || offsets[r] > n_bases || (int64_t)s->lengths[(size_t)r] > n_bases - offsets[r]) {
+      *v.err = std::string(who) + ": read " + std::to_string(r) + " is [" + std::to_string(offsets[r]) + ", " +
+               std::to_string(offsets[r] + s->lengths[(size_t)r]) + ") of " + std::to_string(n_bases) + " bases";
+      return MHAP_E_INVALID;
+    }
+  if (s->n_ubases == 0) return MHAP_OK;
+  if (!d_bases || !out) return null_arg(s, who);
+  (void)hipSetDevice(v.device);
+  hipError_t e;
+  if ((e = s->d_roff.ensure(8 * (size_t)s->n_reads)) != hipSuccess || (e = s->spelled.ensure((size_t)s->n_ubases)) != hipSuccess)
+    return hip_fail(v, who, "hipMalloc", e);
+  if ((e = hipMemcpyAsync(s->d_roff.p, offsets, 8 * (size_t)s->n_reads, hipMemcpyHostToDevice, v.stream)) != hipSuccess) return hip_fail(v, who, "upload", e);
+  const int64_t tiles = (s->n_ubases + SPELL_CHUNK - 1) / SPELL_CHUNK;
+  if (tiles > INT32_MAX) { (void)hipStreamSynchronize(v.stream); *v.err = std::string(who) + ": more than 2^31 - 1 tiles of output"; return MHAP_E_INVALID; }
+  hipLaunchKernelGGL(spell_kernel, dim3((unsigned)tiles), dim3(SPELL_T), 0, v.stream, d_bases, n_bases, s->d_roff.as<int64_t>(), s->d_lengths.as<int32_t>(),
+                     s->n_members, s->m_vertex.as<int32_t>(), s->m_span.as<int32_t>(), s->m_dst.as<int64_t>(), s->n_ubases, s->spelled.as<uint8_t>());
+  if ((e = hipGetLastError()) != hipSuccess) { (void)hipStreamSynchronize(v.stream); return hip_fail(v, who, "launch", e); }
+  if ((e = hipMemcpyAsync(out, s->spelled.p, (size_t)s->n_ubases, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) {
+    (void)hipStreamSynchronize(v.stream);
+    return hip_fail(v, who, "download", e);
+  }
+  if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return hip_fail(v, who, "kernel", e);
+  return MHAP_OK;
+}
+
+extern "C" int mhap_graph_spell(mhap_graph_session* s, const uint8_t* bases, int64_t n_bases, const int64_t* offsets, uint8_t* out) {
+  const char* who = "mhap_graph_spell";
+  if (!s) return MHAP_E_INVALID;
+  HandleView v = handle_view(s->h);
+  const int rc = need_unitigs(s, who);
+  if (rc != MHAP_OK) return rc;
+  if (n_bases < 0 || (n_bases > 0 && !bases)) { *v.err = std::string(who) + ": null or negative argument"; return MHAP_E_INVALID; }
+  (void)hipSetDevice(v.device);
+  hipError_t e;
+  if ((e = s->d_bases.ensure((size_t)std::max<int64_t>(n_bases, 1))) != hipSuccess) return hip_fail(v, who, "hipMalloc of the bases", e);
+  if (n_bases > 0) {   // (waited for: the caller's bytes are free when the call returns, whatever it returns)
+    if ((e = hipMemcpyAsync(s->d_bases.p, bases, (size_t)n_bases, hipMemcpyHostToDevice, v.stream)) != hipSuccess ||
+        (e = hipStreamSynchronize(v.stream)) != hipSuccess) return hip_fail(v, who, "upload", e);
+  }
+  return mhap_graph_spell_device(s, s->d_bases.as<uint8_t>(), n_bases, offsets, out);
+}
+
 extern "C" void mhap_graph_free(mhap_graph_session* s) {
   if (!s) return;
   HandleView v = handle_view(s->h);
@@ -528,4 +1007,9 @@ extern "C" int mhap_format_gfa_link(const int32_t* row7, const int64_t* read_ids
   if (!row7 || !read_ids || (!out && cap > 0)) return -1;
   return snprintf(out, cap, "L\t%lld\t%c\t%lld\t%c\t%dM", (long long)read_ids[row7[0] >> 1], (row7[0] & 1) ? '-' : '+',
                   (long long)read_ids[row7[1] >> 1], (row7[1] & 1) ? '-' : '+', row7[3]);
+}
+
+extern "C" int mhap_format_gfa_unitig_link(const int32_t* row6, char* out, size_t cap) {
+  if (!row6 || (!out && cap > 0)) return -1;
+  return snprintf(out, cap, "L\tutg%06dl\t%c\tutg%06dl\t%c\t%dM", row6[0] + 1, row6[1] ? '-' : '+', row6[2] + 1, row6[3] ? '-' : '+', row6[4]);
 }

@@ -412,6 +412,7 @@ int main(int argc, char** argv) {
   o.add("--correct", "With --realign: correct every read of -s from the realigned overlaps and write the corrected reads to this FASTA file. Each overlap votes column by column on both of its reads and every position takes the majority; overlaps that --realign drops cast no vote. Self overlaps only (no -q), one GPU.", "");
   o.add("--correct-min-coverage", "[int] With --correct, the votes a read position needs before it is changed.", "4");
   o.add("--gfa", "With --realign: build the string graph of the realigned overlaps on the GPU (dovetails, contained reads set aside, transitive arcs reduced) and write it to this file as GFA 1: an S line per read that is not contained, an L line per final arc. Self overlaps only (no -q), one GPU.", "");
+  o.add("--gfa-unitigs", "With --gfa: compact the final arcs of the string graph into unitigs on the GPU and write them to this second file as GFA 1: an S line with the sequence per unitig, spelled from the reads as stored, an a line per read of it, an L line per arc between unitigs.", "");
   o.add("--gfa-max-hang", "[int] With --gfa, the longest unaligned end an overlap may leave on both reads before it counts as an internal match.", "1000");
   o.add("--gfa-min-overlap", "[int] With --gfa, the shortest overlap that becomes an arc.", "2000");
   o.add("--gfa-fuzz", "[int] With --gfa, the slack of the transitive reduction in bases.", "1000");
@@ -466,6 +467,10 @@ int main(int argc, char** argv) {
     if (o.i("--correct-min-coverage") < 1) bad("The correction's minimum coverage must be >=1.");
   }
   const bool gfa = o.isset("--gfa");
+  if (o.isset("--gfa-unitigs")) {   // refused before a handle exists
+    if (!gfa) bad("--gfa-unitigs compacts the graph of --gfa: give --gfa too.");
+    if (o.s("--gfa-unitigs").empty()) bad("--gfa-unitigs needs the name of the GFA file to write.");
+  }
   if (gfa) {   // refused before a handle exists
     if (!o.b("--realign")) bad("--gfa builds the graph from the alignments of --realign: give --realign too.");
     if (!o.s("-q").empty()) bad("--gfa lays out the reads of -s from their overlaps with each other: it takes no -q.");
@@ -652,6 +657,46 @@ int main(int argc, char** argv) {
     std::vector<uint8_t> contained((size_t)std::max<int64_t>(nr, 1));
     chk(E.h, mhap_graph_copy_arcs(RA.graph, rows.data()));
     chk(E.h, mhap_graph_copy_read_flags(RA.graph, contained.data()));
+    int64_t uc[MHAP_UNITIG_COUNTS];
+    const bool unitigs = o.isset("--gfa-unitigs");
+    if (unitigs) {   // the chains of the final arcs and their bases, while the graph is on the device; the second file is all it writes
+      chk(E.h, mhap_graph_unitigs(RA.graph, uc));
+      const size_t nu = (size_t)uc[0], nm = (size_t)uc[2], nl = (size_t)uc[4];
+      std::vector<int64_t> ustart(nu + 1), ulen(nu + 1), moff(nm + 1);
+      std::vector<uint8_t> circ(nu + 1), seq((size_t)uc[6] + 1);
+      std::vector<int32_t> mv(nm + 1), msp(nm + 1), links(6 * nl + 6);
+      chk(E.h, mhap_graph_copy_unitigs(RA.graph, ustart.data(), ulen.data(), circ.data()));
+      chk(E.h, mhap_graph_copy_layout(RA.graph, mv.data(), moff.data(), msp.data()));
+      chk(E.h, mhap_graph_copy_links(RA.graph, links.data()));
+      chk(E.h, mhap_graph_spell(RA.graph, RA.bases.data(), (int64_t)RA.bases.size(), RA.offsets.data(), seq.data()));
+      FILE* f = fopen(o.s("--gfa-unitigs").c_str(), "wb");
+      if (!f) die("cannot write " + o.s("--gfa-unitigs"));
+      std::string text = "H\tVN:Z:1.0\n";
+      char name[32], line[128];
+      size_t at = 0;
+      for (size_t k = 0; k < nu; k++) {
+        snprintf(name, sizeof name, "utg%06lld%c", (long long)k + 1, circ[k] ? 'c' : 'l');
+        text += std::string("S\t") + name + "\t";
+        text.append((const char*)seq.data() + at, (size_t)ulen[k]);
+        at += (size_t)ulen[k];
+        text += "\tLN:i:" + std::to_string(ulen[k]) + "\tnr:i:" + std::to_string(ustart[k + 1] - ustart[k]) + "\n";
+        for (int64_t m = ustart[k]; m < ustart[k + 1]; m++) {
+          const std::string sp = std::to_string(msp[(size_t)m]);
+          text += std::string("a\t") + name + "\t" + std::to_string(moff[(size_t)m]) + "\t" + std::to_string(RA.ids[(size_t)(mv[(size_t)m] >> 1)]) + ":1-" + sp +
+                  "\t" + ((mv[(size_t)m] & 1) ? "-" : "+") + "\t" + sp + "\n";
+        }
+        if (text.size() > (8u << 20)) { fwrite(text.data(), 1, text.size(), f); text.clear(); }
+      }
+      for (size_t i = 0; i < nl; i++) {
+        const int len = mhap_format_gfa_unitig_link(links.data() + 6 * i, line, sizeof line);
+        if (len < 0 || (size_t)len >= sizeof line) die("mhap_format_gfa_unitig_link failed");
+        text.append(line, (size_t)len);
+        text.push_back('\n');
+        if (text.size() > (8u << 20)) { fwrite(text.data(), 1, text.size(), f); text.clear(); }
+      }
+      fwrite(text.data(), 1, text.size(), f);
+      if (fclose(f) != 0) die("cannot write " + o.s("--gfa-unitigs"));
+    }
     mhap_graph_free(RA.graph);
     RA.graph = nullptr;
     FILE* f = fopen(o.s("--gfa").c_str(), "wb");
@@ -678,6 +723,9 @@ int main(int argc, char** argv) {
                     "%lld contained reads, %lld arcs, %lld reduced, %lld final\n",
             (long long)gc[0], (long long)gc[1], (long long)gc[2], (long long)gc[3], (long long)gc[4], (long long)gc[5], (long long)gc[6],
             (long long)gc[7], (long long)gc[8], (long long)gc[9], (long long)gc[10]);
+    if (unitigs)
+      fprintf(stderr, "Unitigs: %lld unitigs (%lld circular) of %lld reads, %lld joined arcs, %lld links; longest %lld bases, %lld bases in all\n",
+              (long long)uc[0], (long long)uc[1], (long long)uc[2], (long long)uc[3], (long long)uc[4], (long long)uc[5], (long long)uc[6]);
     fprintf(stderr, "Time (s) to class, build and reduce the graph: %g\n", RA.graph_seconds);
   }
   fprintf(stderr, "Total time (s): %g\n", now() - t_total);
