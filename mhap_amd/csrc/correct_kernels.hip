@@ -244,15 +244,6 @@ struct mhap_correct_session {
   }
 };
 
-namespace {
-
-int hip_fail(const HandleView& v, const char* who, const char* what, hipError_t e) {
-  *v.err = std::string(who) + ": " + what + ": " + hipGetErrorString(e);
-  return MHAP_E_HIP;
-}
-
-}  // namespace
-
 extern "C" int mhap_correct_begin(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const int64_t* read_ids, const int64_t* offsets,
                                   const int32_t* lengths, int64_t n_reads, mhap_correct_session** session) {
   const char* who = "mhap_correct_begin";

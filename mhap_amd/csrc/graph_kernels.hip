@@ -541,11 +541,6 @@ struct mhap_graph_session {
 
 namespace {
 
-int hip_fail(const HandleView& v, const char* who, const char* what, hipError_t e) {
-  *v.err = std::string(who) + ": " + what + ": " + hipGetErrorString(e);
-  return MHAP_E_HIP;
-}
-
 unsigned blocks256(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace

@@ -93,6 +93,11 @@ struct HandleView {
   void** kmer;             // the open k-mer count (kmer_kernels.hip), or null
 };
 HandleView handle_view(mhap_handle* h);
+// a HIP call of entry point `who` failed at `what`: the handle's message, and the code to return
+inline int hip_fail(const HandleView& v, const char* who, const std::string& what, hipError_t e) {
+  *v.err = std::string(who) + ": " + what + ": " + hipGetErrorString(e);
+  return MHAP_E_HIP;
+}
 void mhap_dist_release(void* dist_state);
 // Eager exchange (mhap_dist.hip; mhap_dist_set_eager): an add on a rank of a multi-GPU job gathers its forward rows while the add is
 // still computing — the ordered rows (6/7 of the bytes) as soon as the ordered-sketch kernel has written them, under the MinHash

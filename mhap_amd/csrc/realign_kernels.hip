@@ -9,7 +9,8 @@
 // that own an in-band cell are [ilo, ihi].  Nothing outside is touched, so a band that covers the matrix costs what the matrix costs
 // and a band that misses it costs nothing.
 //
-// Schedule.  As in align_kernels.hip, lane t owns a strip of R consecutive rows of s1 (R cells per step, in registers), walks along s2
+// Schedule (the cell rule, the chain between lanes, the work claim and the launch path are align_common.hpp's; BandWalk below is this
+// paragraph as code, for both kernels that walk a band).  As in align_kernels.hip, lane t owns a strip of R consecutive rows of s1 (R cells per step, in registers), walks along s2
 // one column per step and hands the bottom row of its strip (H, F and their carried values) to lane t + 1: __shfl_up inside a wave,
 // a double-buffered LDS slot between waves.  What changes is which columns a lane walks.  The band moves one column per row, so the
 // columns of lane t's strip are those of lane t - 1's shifted right by R: with row0 the first row of the strip, lane t walks the
@@ -39,7 +40,7 @@
 //    the path, so it keeps its value, and every other value can only fall — the alternative a choice was preferred over stays
 //    unpreferred in H (diagonal, then E, then F), and in E and F an extension that won still wins, an opening that won strictly still
 //    wins.  The diagonal predecessor of the begin cell is outside the restriction, H = 0 as it was.
-//  * trace_fill_kernel runs the same wavefront schedule over that sub-matrix without the carried fields (69 / 82 VGPRs instead of 184)
+//  * trace_fill_kernel runs the same wavefront schedule over that sub-matrix without the carried fields (69 / 81 VGPRs instead of 165)
 //    and stores 4 bits per cell: H's choice (diagonal on equal bytes, diagonal on different bytes, E, F), "E extended", "F extended".
 //    Word (x, g) holds diagonal x of the 8 rows of row group g, so a lane's strip is one g; the pair's words are [x][g].
 //  * trace_walk_kernel, one lane per pair, walks back from the end cell for exactly `columns` columns, one word serving up to 8 diagonal
@@ -54,31 +55,12 @@
 #include <unordered_map>
 #include <vector>
 
+#include "align_common.hpp"
 #include "device_common.hpp"
 #include "mhap_internal.hpp"
 
 namespace mhap {
 namespace {
-
-constexpr int BA_R = 8;                // rows of s1 per lane
-constexpr int BA_NEG = -(1 << 28);     // minus infinity for E and F
-constexpr uint32_t BA_PAD = 0x100u;    // s1 "byte" of a row that does not exist: its cells are masked
-constexpr int BA_NWB = 4;              // waves of the wide kernel
-
-struct Meta { int bi, bj, cols, errs; };   // begin cell (0-based row, column), columns, errors of the path into a cell
-
-__device__ inline Meta meta_sel(bool c, const Meta& a, const Meta& b) {
-  return Meta{c ? a.bi : b.bi, c ? a.bj : b.bj, c ? a.cols : b.cols, c ? a.errs : b.errs};
-}
-__device__ inline Meta meta_shfl_up(const Meta& m) {
-  return Meta{__shfl_up(m.bi, 1), __shfl_up(m.bj, 1), __shfl_up(m.cols, 1), __shfl_up(m.errs, 1)};
-}
-// (score, end column, end row) order of the end cell: higher score, then smaller j, then smaller i
-__device__ inline bool better_end(int s, int j, int i, int bs, int bj, int bi) {
-  return s > bs || (s == bs && s > 0 && (j < bj || (j == bj && i < bi)));
-}
-
-struct Edge { int H, F; Meta mH, mF; };   // the bottom row of a strip at one column: what the strip below reads
 
 // The band clipped to the m x n matrix: diagonals [dlo, dlo + W) and rows [ilo, ilo + rows).  W = 0: no cell is in the band.
 struct BandGeom { int dlo, W, ilo, rows; };
@@ -92,23 +74,54 @@ __host__ __device__ inline BandGeom band_geom(int64_t m, int64_t n, int64_t diag
   return BandGeom{(int)lo, (int)(hi - lo + 1), (int)ilo, (int)(ihi - ilo + 1)};
 }
 
+// Lanes and passes of a band of `rows` rows in a workgroup of T lanes: as few passes as T lanes allow, then as few lanes as that many
+// passes need; rows past the last are masked.  No rows: no pass.
+__host__ __device__ inline void band_shape(int rows, int T, int& passes, int& L) {
+  passes = (rows + T * AL_R - 1) / (T * AL_R);
+  L = passes > 0 ? (rows + passes * AL_R - 1) / (passes * AL_R) : 1;
+}
+
+// The schedule above for one lane: where lane t of L is in a pass and at a step of it.  align_banded_kernel and trace_fill_kernel take
+// every bound, index and band test from here, so they cannot walk different cells.
+struct BandWalk {
+  int W, n, L, t;                        // the band's diagonals, the columns of s2, the lanes of a pass, this lane
+  int pbase, row0, jc, s_begin, s_end;   // a pass: its first row, the lane's first row, the column before lane 0's first, the steps with work
+  int q, j;                              // a step: the lane's local column index and its column of s2
+  bool inq, active;                      // q is one of the lane's W + R columns; and j is a column of s2
+
+  // Pass p of a band whose rows begin at ilo and whose diagonals begin at dlo.  Steps before lane 0 reaches column 0 and after the
+  // last lane has left its columns or s2 (and `extra` steps more) have no active lane.
+  __device__ __forceinline__ void pass(int ilo, int dlo, int p, int extra) {
+    pbase = ilo + p * L * AL_R; row0 = pbase + t * AL_R; jc = pbase + dlo - 1;
+    s_begin = jc < 0 ? -jc : 0;
+    s_end = min((L - 1) * (AL_R + 1) + W + AL_R, n - jc + L - 1 + extra);
+  }
+  // lane t at step s: local column q = s - t (R + 1), column j = jc + s - t
+  __device__ __forceinline__ void step(int s) {
+    q = s - t * (AL_R + 1); j = jc + s - t;
+    inq = t < L && q >= 0 && q < W + AL_R;
+    active = inq && j >= 0 && j < n;
+  }
+  // the cell above the strip at this column is the boundary: right of the band for q >= W, above the band's first row for lane 0 of
+  // pass 0 (lane 0 of a later pass reads the previous pass's bottom row at position q)
+  __device__ __forceinline__ bool above_is_boundary(int p) const { return q >= W || (t == 0 && p == 0); }
+  // row r of the strip (its byte c1) has a cell of the band at this column: its in-band columns are the local indices r + 1 .. r + W
+  __device__ __forceinline__ bool inband(uint32_t c1, int r) const { return c1 != AL_PAD && (unsigned)(q - 1 - r) < (unsigned)W; }
+  // the strip's bottom row is in the band at local indices R .. R + W - 1: position q - R of the W the next pass reads
+  __device__ __forceinline__ bool hands_down(int p, int passes) const { return t == L - 1 && p + 1 < passes && q >= AL_R; }
+};
+
 template <int NW>
 __global__ __launch_bounds__(NW * 64) void align_banded_kernel(const uint8_t* __restrict__ bases, const int64_t* __restrict__ pairs,
                                                                const int32_t* __restrict__ order, int n_order, int* __restrict__ next,
                                                                int32_t* __restrict__ scratch, int64_t scratch_stride,
                                                                int32_t* __restrict__ results) {
   constexpr int T = NW * 64;
-  __shared__ Edge hand[2][NW > 1 ? NW - 1 : 1];     // lane 63 of wave w -> lane 0 of wave w + 1, by step parity
-  __shared__ int best_s[T], best_j[T], best_i[T];
-  __shared__ Meta best_m[T];
-  __shared__ int cur;
-  const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+  __shared__ Edge hand[2][NW > 1 ? NW - 1 : 1];
+  const int t = threadIdx.x;
   int32_t* edge = scratch ? scratch + (int64_t)blockIdx.x * scratch_stride : nullptr;
   for (;;) {
-    if (t == 0) cur = atomicAdd(next, 1);
-    __syncthreads();
-    const int k = cur;
-    __syncthreads();
+    const int k = claim_next(next);
     if (k >= n_order) return;
     const int pi = order[k];
     const int64_t* pr = pairs + 7 * (int64_t)pi;
@@ -116,191 +129,78 @@ __global__ __launch_bounds__(NW * 64) void align_banded_kernel(const uint8_t* __
     const int m = (int)pr[1], n = (int)pr[3];
     const bool b_rc = pr[4] != 0;
     const BandGeom g = band_geom(m, n, pr[5], pr[6]);
-    const int W = g.W, ihi = g.ilo + g.rows - 1;
-    // lanes and passes: as few passes as T lanes allow, then as few lanes as that many passes need; rows past ihi are masked
-    int passes = 0, L = 1;
-    if (W > 0) {
-      passes = (g.rows + T * BA_R - 1) / (T * BA_R);
-      L = (g.rows + passes * BA_R - 1) / (passes * BA_R);
-    }
-    const int P = L * BA_R;
-    int ls = 0, lj = 0, li = 0;               // this lane's best end cell over all passes
-    Meta lm{0, 0, 0, 0};
+    const int ihi = g.ilo + g.rows - 1;
+    BandWalk w;
+    w.W = g.W; w.n = n; w.t = t;
+    int passes;
+    band_shape(g.rows, T, passes, w.L);
+    BestEnd lane_best{0, 0, 0, {0, 0, 0, 0}};   // this lane's best end cell over all passes
     for (int p = 0; p < passes; p++) {
-      uint32_t c1[BA_R];
-      int Hp[BA_R], Ep[BA_R];
-      Meta Hm[BA_R], Em[BA_R];
-      const int pbase = g.ilo + p * P, row0 = pbase + t * BA_R;
+      Strip S;
+      S.reset();
+      w.pass(g.ilo, g.dlo, p, 0);
 #pragma unroll
-      for (int r = 0; r < BA_R; r++) {
-        const int i = row0 + r;
-        c1[r] = (t < L && i <= ihi) ? (uint32_t)bases[a_off + i] : BA_PAD;
-        Hp[r] = 0; Ep[r] = BA_NEG; Hm[r] = Meta{0, 0, 0, 0}; Em[r] = Meta{0, 0, 0, 0};
+      for (int r = 0; r < AL_R; r++) {
+        const int i = w.row0 + r;
+        S.c1[r] = (t < w.L && i <= ihi) ? (uint32_t)bases[a_off + i] : AL_PAD;
       }
-      int dH = 0;                                // H(row0 - 1, j - 1) and its carried values
-      Meta dm{0, 0, 0, 0};
-      Edge out{0, BA_NEG, {0, 0, 0, 0}, {0, 0, 0, 0}};
-      int ps = 0, pj = 0, pin = 0;               // this pass's best: strict > is the tie rule within a lane (j, then i, increase)
-      Meta pm{0, 0, 0, 0};
-      // lane t at step s: local column q = s - t (R + 1), column j = jc + s - t.  Steps before lane 0 reaches column 0 and after
-      // the last lane has left its columns or s2 have no active lane.
-      const int jc = pbase + g.dlo - 1;
-      const int s_begin = jc < 0 ? -jc : 0;
-      const int s_end = min((L - 1) * (BA_R + 1) + W + BA_R, n - jc + L - 1);
-      for (int s = s_begin; s < s_end; s++) {
-        const int q = s - t * (BA_R + 1), j = jc + s - t;
-        const bool active = t < L && q >= 0 && q < W + BA_R && j >= 0 && j < n;
-        Edge in;
-        in.H = __shfl_up(out.H, 1); in.F = __shfl_up(out.F, 1); in.mH = meta_shfl_up(out.mH); in.mF = meta_shfl_up(out.mF);
-        if (NW > 1 && lane == 0 && t > 0) in = hand[(s + 1) & 1][wave - 1];
-        if (active) {
-          // the cell above the strip at this column: right of the band for q >= W, the previous pass's bottom row for lane 0
-          if (q >= W || (t == 0 && p == 0)) { in.H = 0; in.F = BA_NEG; in.mH = Meta{0, 0, 0, 0}; in.mF = in.mH; }
-          else if (t == 0) {
-            const int32_t* e = edge + q;
-            in.H = e[0]; in.F = e[W]; in.mH = Meta{e[2 * W], e[3 * W], e[4 * W], e[5 * W]}; in.mF = Meta{e[6 * W], e[7 * W], e[8 * W], e[9 * W]};
-          }
-          const uint32_t c2 = b_rc ? rc_char(bases[b_off + (n - 1 - j)]) : (uint32_t)bases[b_off + j];
-          int upH = in.H, upF = in.F;
-          Meta upmH = in.mH, upmF = in.mF;
-          int diagH = dH;
-          Meta diagm = dm;
-#pragma unroll
-          for (int r = 0; r < BA_R; r++) {
-            const int i = row0 + r;
-            // row r's in-band columns are the local indices r + 1 .. r + W
-            const bool inband = c1[r] != BA_PAD && (unsigned)(q - 1 - r) < (unsigned)W;
-            const bool mis = c1[r] != c2;
-            const int D = diagH + (mis ? -2 : 2);
-            // E(i,j) = max(H(i,j-1) - 2, E(i,j-1) - 1): a deletion (consumes s2); extension wins a tie
-            const int eext = Ep[r] - 1, eopn = Hp[r] - 2;
-            const bool ext = eext >= eopn;
-            int E = ext ? eext : eopn;
-            Meta me = meta_sel(ext, Em[r], Hm[r]);
-            me.cols += 1; me.errs += 1;
-            // F(i,j) = max(H(i-1,j) - 2, F(i-1,j) - 1): an insertion (consumes s1); extension wins a tie
-            const int fext = upF - 1, fopn = upH - 2;
-            const bool fx = fext >= fopn;
-            int F = fx ? fext : fopn;
-            Meta mf = meta_sel(fx, upmF, upmH);
-            mf.cols += 1; mf.errs += 1;
-            // H = max(0, diagonal, E, F), preferring diagonal, then E, then F; a diagonal step out of an H = 0 cell begins a path
-            Meta md = diagm;
-            md.cols += 1; md.errs += mis ? 1 : 0;
-            if (diagH == 0) md = Meta{i, j, 1, mis ? 1 : 0};
-            const bool take_d = D > 0 && D >= E && D >= F;
-            const bool take_e = !take_d && E > 0 && E >= F;
-            const bool take_f = !take_d && !take_e && F > 0;
-            int H = take_d ? D : take_e ? E : take_f ? F : 0;
-            const Meta mh = meta_sel(take_d, md, meta_sel(take_e, me, mf));
-            // a cell outside the band (or the matrix) is the boundary; what it carries is never read: only a positive value's carried
-            // fields reach a result, and nothing positive descends from H = 0, E = F = -inf
-            if (!inband) { H = 0; E = BA_NEG; F = BA_NEG; }
-            diagH = Hp[r]; diagm = Hm[r];
-            Hp[r] = H; Hm[r] = mh; Ep[r] = E; Em[r] = me;
-            upH = H; upF = F; upmH = mh; upmF = mf;
-            if (H > ps) { ps = H; pj = j; pin = i; pm = mh; }
-          }
-          dH = in.H; dm = in.mH;
-          out = Edge{upH, upF, upmH, upmF};
-          // the strip's bottom row is in the band at local indices R .. R + W - 1: position q - R of the W the next pass reads
-          if (t == L - 1 && p + 1 < passes && q >= BA_R) {
-            int32_t* e = edge + (q - BA_R);
-            e[0] = out.H; e[W] = out.F;
-            e[2 * W] = out.mH.bi; e[3 * W] = out.mH.bj; e[4 * W] = out.mH.cols; e[5 * W] = out.mH.errs;
-            e[6 * W] = out.mF.bi; e[7 * W] = out.mF.bj; e[8 * W] = out.mF.cols; e[9 * W] = out.mF.errs;
-          }
+      for (int s = w.s_begin; s < w.s_end; s++) {
+        w.step(s);
+        Edge in = edge_from_above<NW>(S.out, hand, s);
+        if (w.active) {
+          if (w.above_is_boundary(p)) in = edge_boundary();
+          else if (t == 0) in = edge_load(edge + w.q, w.W);
+          const uint32_t c2 = b_rc ? rc_char(bases[b_off + (n - 1 - w.j)]) : (uint32_t)bases[b_off + w.j];
+          S.column(in, c2, w.row0, w.j, [&](uint32_t c1, int r) { return w.inband(c1, r); });
+          if (w.hands_down(p, passes)) edge_store(edge + (w.q - AL_R), w.W, S.out);
         } else {
-          dH = 0;   // the diagonal predecessor of a lane's first column is left of the band or of the matrix
+          S.dH = 0;   // the diagonal predecessor of a lane's first column is left of the band or of the matrix
         }
-        if constexpr (NW > 1) {
-          if (lane == 63 && wave + 1 < NW) hand[s & 1][wave] = out;
-          __syncthreads();
-        }
+        edge_to_below<NW>(S.out, hand, s);
       }
-      if (better_end(ps, pj, pin, ls, lj, li)) { ls = ps; lj = pj; li = pin; lm = pm; }
+      if (better_end(S.best, lane_best)) lane_best = S.best;
       __syncthreads();   // the pass's bottom row (HBM) before the next pass reads it
     }
-    best_s[t] = ls; best_j[t] = lj; best_i[t] = li; best_m[t] = lm;
-    __syncthreads();
-    if (t == 0) {
-      int b = 0;
-      for (int u = 1; u < T; u++)
-        if (better_end(best_s[u], best_j[u], best_i[u], best_s[b], best_j[b], best_i[b])) b = u;
-      int32_t* o = results + 7 * (int64_t)pi;
-      if (best_s[b] > 0) {
-        o[0] = best_s[b]; o[1] = best_m[b].bi; o[2] = best_i[b]; o[3] = best_m[b].bj; o[4] = best_j[b];
-        o[5] = best_m[b].cols; o[6] = best_m[b].errs;
-      } else {
-        o[0] = 0; o[1] = o[2] = o[3] = o[4] = -1; o[5] = o[6] = 0;
-      }
-    }
-    __syncthreads();
+    write_best_end<T>(lane_best, results + 7 * (int64_t)pi);
   }
 }
 
-struct BandedBufs {
-  DevBuf bases, pairs, order, next, scratch, results;
-  void release() { bases.release(); pairs.release(); order.release(); next.release(); scratch.release(); results.release(); }
-};
-
 constexpr int64_t BA_SCRATCH_BUDGET = (int64_t)1 << 30;   // bytes of pass boundaries in flight; fewer workgroups beyond that
 
-// `pairs` (host, validated) against the bases already in B.bases; everything on v.stream, results on the host when it returns.
-int banded_run(const HandleView& v, BandedBufs& B, const int64_t* pairs, int64_t n, int32_t* results, const char* who) {
-  auto fail = [&](hipError_t e, const char* what) {
-    *v.err = std::string(who) + ": " + what + ": " + hipGetErrorString(e);
-    return MHAP_E_HIP;
-  };
-  // A pair whose band has more rows than one wave holds goes to the four-wave kernel only while such pairs are too few to give every
-  // compute unit its waves; with more of them a wave per pair idles less (the header comment) and needs no barrier.
-  std::vector<BandGeom> geo((size_t)n);
+// The wide form's share of n items whose band has rows(q) rows and W(q) diagonals, and their order.  An item with more rows than one
+// wave holds goes to the four-wave kernel only while such items are too few to give every compute unit its waves; with more of them a
+// wave per item idles less (the header comment) and needs no barrier.  w_big, w_small: the widest band of each form that needs a
+// second pass, which is what a workgroup keeps in HBM between passes.
+template <class Rows, class Width>
+std::vector<int32_t> band_order(const HandleView& v, int64_t n, Rows rows, Width W, size_t& n_big, int64_t& w_big, int64_t& w_small) {
   int64_t n_tall = 0;
-  for (int64_t q = 0; q < n; q++) {
-    geo[(size_t)q] = band_geom(pairs[7 * q + 1], pairs[7 * q + 3], pairs[7 * q + 5], pairs[7 * q + 6]);
-    n_tall += geo[(size_t)q].rows > 64 * BA_R;
-  }
+  for (int64_t q = 0; q < n; q++) n_tall += rows(q) > 64 * AL_R;
   const bool spread = n_tall < 4LL * v.num_cus;
-  std::vector<int32_t> big, small;
-  for (int64_t q = 0; q < n; q++) (spread && geo[(size_t)q].rows > 64 * BA_R ? big : small).push_back((int32_t)q);
-  auto cells = [&](int32_t q) { return (double)geo[(size_t)q].rows * (double)geo[(size_t)q].W; };
-  auto by_cells = [&](int32_t a, int32_t b) { const double ca = cells(a), cb = cells(b); return ca != cb ? ca > cb : a < b; };
-  std::stable_sort(big.begin(), big.end(), by_cells);     // longest first
-  std::stable_sort(small.begin(), small.end(), by_cells);
-  std::vector<int32_t> order(big);
-  order.insert(order.end(), small.begin(), small.end());
-  // HBM rows between passes: 10 words per diagonal of the widest band that needs a second pass, one set per workgroup
-  int64_t w_big = 0, w_small = 0;
-  for (int32_t q : big) if (geo[(size_t)q].rows > BA_NWB * 64 * BA_R) w_big = std::max<int64_t>(w_big, geo[(size_t)q].W);
-  for (int32_t q : small) if (geo[(size_t)q].rows > 64 * BA_R) w_small = std::max<int64_t>(w_small, geo[(size_t)q].W);
-  int grid_big = (int)std::min<int64_t>((int64_t)big.size(), 2LL * v.num_cus);        // (the handle's compute units: MHAP_NUM_CUS caps them)
-  int grid_small = (int)std::min<int64_t>((int64_t)small.size(), 8LL * v.num_cus);   // (184 VGPRs: two waves per SIMD)
-  const int64_t stride_big = 10 * w_big, stride_small = 10 * w_small;
-  if (stride_big > 0) grid_big = (int)std::max<int64_t>(1, std::min<int64_t>(grid_big, BA_SCRATCH_BUDGET / 2 / (stride_big * 4)));
-  if (stride_small > 0) grid_small = (int)std::max<int64_t>(1, std::min<int64_t>(grid_small, BA_SCRATCH_BUDGET / 2 / (stride_small * 4)));
-  const int64_t scratch_big = stride_big * grid_big, scratch_words = scratch_big + stride_small * grid_small;
+  std::vector<int32_t> order = longest_first(
+      n, [&](int64_t q) { return spread && rows(q) > 64 * AL_R; }, [&](int64_t q) { return (double)rows(q) * (double)W(q); }, n_big);
+  w_big = w_small = 0;
+  for (size_t u = 0; u < order.size(); u++) {
+    const int32_t q = order[u];
+    if (rows(q) > (u < n_big ? AL_NWB : 1) * 64 * AL_R) (u < n_big ? w_big : w_small) = std::max<int64_t>(u < n_big ? w_big : w_small, W(q));
+  }
+  return order;
+}
+
+// `pairs` (host, validated) against the bases already in B.bases; everything on v.stream, results on the host when it returns.
+int banded_run(const HandleView& v, AlignBufs& B, const int64_t* pairs, int64_t n, int32_t* results, const char* who) {
+  std::vector<BandGeom> geo((size_t)n);
+  for (int64_t q = 0; q < n; q++) geo[(size_t)q] = band_geom(pairs[7 * q + 1], pairs[7 * q + 3], pairs[7 * q + 5], pairs[7 * q + 6]);
+  size_t n_big;
+  int64_t w_big, w_small;
+  const std::vector<int32_t> order = band_order(v, n, [&](int64_t q) { return geo[(size_t)q].rows; }, [&](int64_t q) { return geo[(size_t)q].W; },
+                                                n_big, w_big, w_small);
+  // HBM rows between passes: 10 words per diagonal, one set per workgroup; 2 and 8 workgroups per compute unit are two waves per SIMD
+  const FormShape big{grid_size(n_big, 2, v, 10 * w_big, BA_SCRATCH_BUDGET / 2), 10 * w_big};
+  const FormShape small{grid_size((size_t)n - n_big, 8, v, 10 * w_small, BA_SCRATCH_BUDGET / 2), 10 * w_small};
   hipError_t e;
-  if ((e = B.pairs.ensure(56 * n)) != hipSuccess) return fail(e, "hipMalloc");
-  if ((e = B.order.ensure(4 * n)) != hipSuccess) return fail(e, "hipMalloc");
-  if ((e = B.next.ensure(8)) != hipSuccess) return fail(e, "hipMalloc");
-  if ((e = B.results.ensure(28 * n)) != hipSuccess) return fail(e, "hipMalloc");
-  if (scratch_words > 0 && (e = B.scratch.ensure((size_t)scratch_words * 4)) != hipSuccess) return fail(e, "hipMalloc (pass boundaries)");
-  if ((e = hipMemcpyAsync(B.pairs.p, pairs, 56 * n, hipMemcpyHostToDevice, v.stream)) != hipSuccess) return fail(e, "upload");
-  if ((e = hipMemcpyAsync(B.order.p, order.data(), 4 * n, hipMemcpyHostToDevice, v.stream)) != hipSuccess) return fail(e, "upload");
-  if ((e = hipMemsetAsync(B.next.p, 0, 8, v.stream)) != hipSuccess) return fail(e, "memset");
-  int* nx = B.next.as<int>();
-  if (!big.empty())
-    hipLaunchKernelGGL(align_banded_kernel<BA_NWB>, dim3(grid_big), dim3(BA_NWB * 64), 0, v.stream, B.bases.as<uint8_t>(), B.pairs.as<int64_t>(),
-                       B.order.as<int32_t>(), (int)big.size(), nx, stride_big > 0 ? B.scratch.as<int32_t>() : nullptr, stride_big,
-                       B.results.as<int32_t>());
-  if (!small.empty())
-    hipLaunchKernelGGL(align_banded_kernel<1>, dim3(grid_small), dim3(64), 0, v.stream, B.bases.as<uint8_t>(), B.pairs.as<int64_t>(),
-                       B.order.as<int32_t>() + big.size(), (int)small.size(), nx + 1,
-                       stride_small > 0 ? B.scratch.as<int32_t>() + scratch_big : nullptr, stride_small, B.results.as<int32_t>());
-  if ((e = hipGetLastError()) != hipSuccess) return fail(e, "launch");
-  if ((e = hipMemcpyAsync(results, B.results.p, 28 * n, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return fail(e, "download");
-  if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return fail(e, "kernel");
-  return MHAP_OK;
+  if ((e = B.results.ensure(28 * n)) != hipSuccess) return hip_fail(v, who, "hipMalloc", e);
+  const int rc = launch_forms(v, who, B, align_banded_kernel<AL_NWB>, align_banded_kernel<1>, pairs, 56, order, n_big, big, small, B.results.as<int32_t>());
+  return rc != MHAP_OK ? rc : download_results(v, who, B, results, n);
 }
 
 // ---- paths: the alignment itself, as run-length operations -----------------------------------------------------------------------------
@@ -329,11 +229,6 @@ inline BandGeom diag_geom(int64_t m, int64_t n, int64_t lo, int64_t hi) {
   return BandGeom{(int)lo, (int)(hi - lo + 1), (int)ilo, (int)(ihi - ilo + 1)};
 }
 
-__host__ __device__ inline void trace_shape(int rows, int T, int& passes, int& L) {   // align_banded_kernel's passes and lanes for `rows` band rows
-  passes = (rows + T * BA_R - 1) / (T * BA_R);
-  L = (rows + passes * BA_R - 1) / (passes * BA_R);
-}
-
 // align_banded_kernel's schedule over a TracePair, carrying no path fields and keeping no best cell: what it leaves is one nibble per
 // in-band cell — bits 0-1 H's choice (0 diagonal on equal bytes, 1 diagonal on different bytes, 2 E, 3 F; the choice of a cell with
 // H = 0 is never read, a walk ends by its column count), bit 2 "E extended", bit 3 "F extended".  Word (x, g) of a pair holds diagonal
@@ -345,88 +240,66 @@ __global__ __launch_bounds__(NW * 64) void trace_fill_kernel(const uint8_t* __re
                                                              int32_t* __restrict__ scratch, int64_t scratch_stride,
                                                              uint32_t* __restrict__ trace) {
   constexpr int T = NW * 64;
-  __shared__ int hand[2][NW > 1 ? NW - 1 : 1][2];   // H, F of lane 63 of wave w for lane 0 of wave w + 1, by step parity
-  __shared__ int cur;
-  const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
-  int32_t* edge = scratch ? scratch + (int64_t)blockIdx.x * scratch_stride : nullptr;
+  __shared__ EdgeHF hand[2][NW > 1 ? NW - 1 : 1];
+  const int t = threadIdx.x;
+  int32_t* edge = scratch ? scratch + (int64_t)blockIdx.x * scratch_stride : nullptr;   // H, then F, of the W entries between passes
   for (;;) {
-    if (t == 0) cur = atomicAdd(next, 1);
-    __syncthreads();
-    const int k = cur;
-    __syncthreads();
+    const int k = claim_next(next);
     if (k >= n_order) return;
     const TracePair tp = tps[order[k]];
     const int n = tp.n, W = tp.W, ihi = tp.ilo + tp.rows - 1;
     const bool b_rc = tp.rc != 0;
-    int passes, L;
-    trace_shape(tp.rows, T, passes, L);
-    const int P = L * BA_R;
-    const int64_t G = (int64_t)passes * L;
+    BandWalk w;
+    w.W = W; w.n = n; w.t = t;
+    int passes;
+    band_shape(tp.rows, T, passes, w.L);
+    const int64_t G = (int64_t)passes * w.L;
     uint32_t* tr = trace + tp.trace_off;
     for (int p = 0; p < passes; p++) {
-      uint32_t c1[BA_R], acc[BA_R];
-      int Hp[BA_R], Ep[BA_R];
-      const int pbase = tp.ilo + p * P, row0 = pbase + t * BA_R;
+      uint32_t c1[AL_R], acc[AL_R];
+      int Hp[AL_R], Ep[AL_R];
+      // AL_R steps more than align_banded_kernel takes at the right edge of s2: the words in flight there still have to come out
+      w.pass(tp.ilo, tp.dlo, p, AL_R);
 #pragma unroll
-      for (int r = 0; r < BA_R; r++) {
-        const int i = row0 + r;
-        c1[r] = (t < L && i <= ihi) ? (uint32_t)bases[tp.a_off + i] : BA_PAD;
-        Hp[r] = 0; Ep[r] = BA_NEG; acc[r] = 0;
+      for (int r = 0; r < AL_R; r++) {
+        const int i = w.row0 + r;
+        c1[r] = (t < w.L && i <= ihi) ? (uint32_t)bases[tp.a_off + i] : AL_PAD;
+        Hp[r] = 0; Ep[r] = AL_NEG; acc[r] = 0;
       }
-      int dH = 0, outH = 0, outF = BA_NEG;
-      const int jc = pbase + tp.dlo - 1;
-      const int s_begin = jc < 0 ? -jc : 0;
-      // BA_R steps more than align_banded_kernel takes at the right edge of s2: the words in flight there still have to come out
-      const int s_end = min((L - 1) * (BA_R + 1) + W + BA_R, n - jc + L - 1 + BA_R);
-      for (int s = s_begin; s < s_end; s++) {
-        const int q = s - t * (BA_R + 1), j = jc + s - t;
-        const bool inq = t < L && q >= 0 && q < W + BA_R;
-        const bool active = inq && j >= 0 && j < n;
-        int inH = __shfl_up(outH, 1), inF = __shfl_up(outF, 1);
-        if (NW > 1 && lane == 0 && t > 0) { inH = hand[(s + 1) & 1][wave - 1][0]; inF = hand[(s + 1) & 1][wave - 1][1]; }
-        if (active) {
-          if (q >= W || (t == 0 && p == 0)) { inH = 0; inF = BA_NEG; }
-          else if (t == 0) { inH = edge[q]; inF = edge[W + q]; }
-          const uint32_t c2 = b_rc ? rc_char(bases[tp.b_off + (n - 1 - j)]) : (uint32_t)bases[tp.b_off + j];
-          int upH = inH, upF = inF, diagH = dH;
+      int dH = 0;
+      EdgeHF out{0, AL_NEG};
+      for (int s = w.s_begin; s < w.s_end; s++) {
+        w.step(s);
+        EdgeHF in = edge_from_above<NW>(out, hand, s);
+        if (w.active) {
+          if (w.above_is_boundary(p)) in = EdgeHF{0, AL_NEG};
+          else if (t == 0) in = EdgeHF{edge[w.q], edge[W + w.q]};
+          const uint32_t c2 = b_rc ? rc_char(bases[tp.b_off + (n - 1 - w.j)]) : (uint32_t)bases[tp.b_off + w.j];
+          int upH = in.H, upF = in.F, diagH = dH;
 #pragma unroll
-          for (int r = 0; r < BA_R; r++) {
-            const bool inband = c1[r] != BA_PAD && (unsigned)(q - 1 - r) < (unsigned)W;
+          for (int r = 0; r < AL_R; r++) {
             const bool mis = c1[r] != c2;
-            const int D = diagH + (mis ? -2 : 2);
-            const int eext = Ep[r] - 1, eopn = Hp[r] - 2;
-            const bool ext = eext >= eopn;
-            int E = ext ? eext : eopn;
-            const int fext = upF - 1, fopn = upH - 2;
-            const bool fx = fext >= fopn;
-            int F = fx ? fext : fopn;
-            const bool take_d = D > 0 && D >= E && D >= F;
-            const bool take_e = !take_d && E > 0 && E >= F;
-            const bool take_f = !take_d && !take_e && F > 0;
-            int H = take_d ? D : take_e ? E : take_f ? F : 0;
-            const uint32_t nib = (take_d ? (mis ? 1u : 0u) : take_e ? 2u : 3u) | (ext ? 4u : 0u) | (fx ? 8u : 0u);
-            if (!inband) { H = 0; E = BA_NEG; F = BA_NEG; }
-            else acc[r] |= nib << (4 * r);
+            Cell c = cell_rule(diagH, Hp[r], Ep[r], upH, upF, mis);
+            const uint32_t nib = (c.take_d ? (mis ? 1u : 0u) : c.take_e ? 2u : 3u) | (c.ext ? 4u : 0u) | (c.fx ? 8u : 0u);
+            if (w.inband(c1[r], r)) acc[r] |= nib << (4 * r);
+            else { c.H = 0; c.E = AL_NEG; c.F = AL_NEG; }
             diagH = Hp[r];
-            Hp[r] = H; Ep[r] = E;
-            upH = H; upF = F;
+            Hp[r] = c.H; Ep[r] = c.E;
+            upH = c.H; upF = c.F;
           }
-          dH = inH;
-          outH = upH; outF = upF;
-          if (t == L - 1 && p + 1 < passes && q >= BA_R) { edge[q - BA_R] = outH; edge[W + q - BA_R] = outF; }
+          dH = in.H;
+          out = EdgeHF{upH, upF};
+          if (w.hands_down(p, passes)) { edge[w.q - AL_R] = out.H; edge[W + w.q - AL_R] = out.F; }
         } else {
           dH = 0;
         }
-        if (inq) {   // diagonal index q - BA_R has had its 8 rows (those outside the matrix or the band stay 0)
-          if (q >= BA_R) tr[(int64_t)(q - BA_R) * G + (p * L + t)] = acc[BA_R - 1];
+        if (w.inq) {   // diagonal index q - AL_R has had its 8 rows (those outside the matrix or the band stay 0)
+          if (w.q >= AL_R) tr[(int64_t)(w.q - AL_R) * G + (p * w.L + t)] = acc[AL_R - 1];
 #pragma unroll
-          for (int r = BA_R - 1; r > 0; r--) acc[r] = acc[r - 1];
+          for (int r = AL_R - 1; r > 0; r--) acc[r] = acc[r - 1];
           acc[0] = 0;
         }
-        if constexpr (NW > 1) {
-          if (lane == 63 && wave + 1 < NW) { hand[s & 1][wave][0] = outH; hand[s & 1][wave][1] = outF; }
-          __syncthreads();
-        }
+        edge_to_below<NW>(out, hand, s);
       }
       __syncthreads();
     }
@@ -473,11 +346,6 @@ __global__ __launch_bounds__(64) void trace_walk_kernel(const TracePair* __restr
   n_ops[q] = ok ? tp.ops_cap - pos : -1;
 }
 
-struct PathBufs {
-  DevBuf tps, order, next, scratch, trace, ops, n_ops;
-  void release() { tps.release(); order.release(); next.release(); scratch.release(); trace.release(); ops.release(); n_ops.release(); }
-};
-
 int64_t trace_budget() {
   if (const char* e = getenv("MHAP_REALIGN_TRACE_BYTES")) {
     char* end = nullptr;
@@ -489,12 +357,8 @@ int64_t trace_budget() {
 
 // The paths of `pairs` (validated, their bases in B.bases) whose `results` banded_run has just returned, appended to `out`.  q0: the
 // index of pairs[0] in the caller's numbering, for messages.
-int paths_run(const HandleView& v, BandedBufs& B, PathBufs& PB, const int64_t* pairs, int64_t n, const int32_t* results, int64_t q0,
+int paths_run(const HandleView& v, AlignBufs& B, const int64_t* pairs, int64_t n, const int32_t* results, int64_t q0,
               mhap_align_paths& out, const char* who) {
-  auto fail = [&](hipError_t e, const std::string& what) {
-    *v.err = std::string(who) + ": " + what + ": " + hipGetErrorString(e);
-    return MHAP_E_HIP;
-  };
   // the sub-matrix of every pair that has an alignment.  With I = columns - (ref_end - ref_begin + 1) insertions and D = columns -
   // (read_end - read_begin + 1) deletions on the path, the path stays on the diagonals [-I, D] around its begin cell's.
   std::vector<TracePair> tps;
@@ -517,7 +381,7 @@ int paths_run(const HandleView& v, BandedBufs& B, PathBufs& PB, const int64_t* p
     if (s.W <= 0 || ins < 0 || del < 0) { *v.err = std::string(who) + ": internal error: pair " + std::to_string(q0 + q) + " has an alignment outside its band"; return MHAP_E_HIP; }
     tps.push_back(tp);
     owner.push_back(q);
-    est_words.push_back((int64_t)s.W * ((s.rows + BA_R - 1) / BA_R + (s.rows + 64 * BA_R - 1) / (64 * BA_R)));
+    est_words.push_back((int64_t)s.W * ((s.rows + AL_R - 1) / AL_R + (s.rows + 64 * AL_R - 1) / (64 * AL_R)));
   }
   const int64_t budget = trace_budget();
   const size_t first_offset = out.offsets.size();   // offsets[first_offset + q] = end of pair q's runs
@@ -532,61 +396,39 @@ int paths_run(const HandleView& v, BandedBufs& B, PathBufs& PB, const int64_t* p
     int64_t bytes = 0;
     while (g1 < tps.size() && (g1 == g0 || bytes + 4 * est_words[g1] <= budget) && g1 - g0 < ((size_t)1 << 20)) bytes += 4 * est_words[g1++];
     const int64_t ng = (int64_t)(g1 - g0);
-    int64_t n_tall = 0;
-    for (size_t u = g0; u < g1; u++) n_tall += tps[u].rows > 64 * BA_R;
-    const bool spread = n_tall < 4LL * v.num_cus;   // banded_run's rule
-    std::vector<int32_t> big, small;
-    int64_t words = 0, n_slices = 0, w_big = 0, w_small = 0;
+    size_t n_big;
+    int64_t w_big, w_small;
+    const std::vector<int32_t> order = band_order(v, ng, [&](int64_t u) { return tps[g0 + (size_t)u].rows; }, [&](int64_t u) { return tps[g0 + (size_t)u].W; },
+                                                  n_big, w_big, w_small);   // banded_run's rule
+    std::vector<char> wide((size_t)ng, 0);
+    for (size_t u = 0; u < n_big; u++) wide[(size_t)order[u]] = 1;
+    int64_t words = 0, n_slices = 0;
     for (size_t u = g0; u < g1; u++) {
       TracePair& tp = tps[u];
-      const bool wide = spread && tp.rows > 64 * BA_R;
       int passes, L;
-      trace_shape(tp.rows, wide ? BA_NWB * 64 : 64, passes, L);
+      band_shape(tp.rows, wide[u - g0] ? AL_NWB * 64 : 64, passes, L);
       tp.G = passes * L;
       tp.trace_off = words; words += (int64_t)tp.W * tp.G;
       tp.ops_off = n_slices; n_slices += tp.ops_cap;
-      (wide ? big : small).push_back((int32_t)(u - g0));
-      if (passes > 1) (wide ? w_big : w_small) = std::max<int64_t>(wide ? w_big : w_small, tp.W);
     }
-    auto cells = [&](int32_t u) { return (double)tps[g0 + u].rows * (double)tps[g0 + u].W; };
-    auto by_cells = [&](int32_t a, int32_t b) { const double ca = cells(a), cb = cells(b); return ca != cb ? ca > cb : a < b; };
-    std::stable_sort(big.begin(), big.end(), by_cells);
-    std::stable_sort(small.begin(), small.end(), by_cells);
-    std::vector<int32_t> order(big);
-    order.insert(order.end(), small.begin(), small.end());
-    int grid_big = (int)std::min<int64_t>((int64_t)big.size(), 4LL * v.num_cus);       // (69 and 82 VGPRs: the fill kernels fit twice the
-    int grid_small = (int)std::min<int64_t>((int64_t)small.size(), 16LL * v.num_cus);   // workgroups per compute unit of banded_run's)
-    const int64_t stride_big = 2 * w_big, stride_small = 2 * w_small;
-    const int64_t scratch_big = stride_big * grid_big, scratch_words = scratch_big + stride_small * grid_small;
+    // 69 and 81 VGPRs: the fill kernels fit twice the workgroups per compute unit of banded_run's; H and F of W entries between passes
+    const FormShape big{grid_size(n_big, 4, v), 2 * w_big}, small{grid_size((size_t)ng - n_big, 16, v), 2 * w_small};
     const std::string which = "pair " + std::to_string(q0 + owner[g0]) + (ng > 1 ? " and the " + std::to_string(ng - 1) + " after it" : "");
-    if ((e = PB.trace.ensure((size_t)std::max<int64_t>(words, 1) * 4)) != hipSuccess)
-      return fail(e, "hipMalloc of " + std::to_string(words * 4) + " bytes of trace for " + which);
-    if ((e = PB.tps.ensure(sizeof(TracePair) * (size_t)ng)) != hipSuccess) return fail(e, "hipMalloc");
-    if ((e = PB.order.ensure(4 * (size_t)ng)) != hipSuccess) return fail(e, "hipMalloc");
-    if ((e = PB.next.ensure(8)) != hipSuccess) return fail(e, "hipMalloc");
-    if ((e = PB.n_ops.ensure(4 * (size_t)ng)) != hipSuccess) return fail(e, "hipMalloc");
-    if ((e = PB.ops.ensure(4 * (size_t)n_slices)) != hipSuccess) return fail(e, "hipMalloc of the runs of " + which);
-    if (scratch_words > 0 && (e = PB.scratch.ensure((size_t)scratch_words * 4)) != hipSuccess) return fail(e, "hipMalloc (pass boundaries)");
-    if ((e = hipMemcpyAsync(PB.tps.p, tps.data() + g0, sizeof(TracePair) * (size_t)ng, hipMemcpyHostToDevice, v.stream)) != hipSuccess) return fail(e, "upload");
-    if ((e = hipMemcpyAsync(PB.order.p, order.data(), 4 * (size_t)ng, hipMemcpyHostToDevice, v.stream)) != hipSuccess) return fail(e, "upload");
-    if ((e = hipMemsetAsync(PB.next.p, 0, 8, v.stream)) != hipSuccess) return fail(e, "memset");
-    int* nx = PB.next.as<int>();
-    if (!big.empty())
-      hipLaunchKernelGGL(trace_fill_kernel<BA_NWB>, dim3(grid_big), dim3(BA_NWB * 64), 0, v.stream, B.bases.as<uint8_t>(), PB.tps.as<TracePair>(),
-                         PB.order.as<int32_t>(), (int)big.size(), nx, stride_big > 0 ? PB.scratch.as<int32_t>() : nullptr, stride_big,
-                         PB.trace.as<uint32_t>());
-    if (!small.empty())
-      hipLaunchKernelGGL(trace_fill_kernel<1>, dim3(grid_small), dim3(64), 0, v.stream, B.bases.as<uint8_t>(), PB.tps.as<TracePair>(),
-                         PB.order.as<int32_t>() + big.size(), (int)small.size(), nx + 1,
-                         stride_small > 0 ? PB.scratch.as<int32_t>() + scratch_big : nullptr, stride_small, PB.trace.as<uint32_t>());
-    hipLaunchKernelGGL(trace_walk_kernel, dim3((unsigned)((ng + 63) / 64)), dim3(64), 0, v.stream, PB.tps.as<TracePair>(), (int)ng,
-                       PB.trace.as<uint32_t>(), PB.ops.as<uint32_t>(), PB.n_ops.as<int32_t>());
-    if ((e = hipGetLastError()) != hipSuccess) return fail(e, "launch");
+    if ((e = B.trace.ensure((size_t)std::max<int64_t>(words, 1) * 4)) != hipSuccess)
+      return hip_fail(v, who, "hipMalloc of " + std::to_string(words * 4) + " bytes of trace for " + which, e);
+    if ((e = B.n_ops.ensure(4 * (size_t)ng)) != hipSuccess) return hip_fail(v, who, "hipMalloc", e);
+    if ((e = B.ops.ensure(4 * (size_t)n_slices)) != hipSuccess) return hip_fail(v, who, "hipMalloc of the runs of " + which, e);
+    const int rc = launch_forms(v, who, B, trace_fill_kernel<AL_NWB>, trace_fill_kernel<1>, (const TracePair*)tps.data() + g0, sizeof(TracePair), order,
+                                n_big, big, small, B.trace.as<uint32_t>());
+    if (rc != MHAP_OK) return rc;
+    hipLaunchKernelGGL(trace_walk_kernel, dim3((unsigned)((ng + 63) / 64)), dim3(64), 0, v.stream, B.items.as<TracePair>(), (int)ng,
+                       B.trace.as<uint32_t>(), B.ops.as<uint32_t>(), B.n_ops.as<int32_t>());
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(v, who, "launch", e);
     counts.resize((size_t)ng);
     slices.resize((size_t)n_slices);
-    if ((e = hipMemcpyAsync(counts.data(), PB.n_ops.p, 4 * (size_t)ng, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return fail(e, "download");
-    if ((e = hipMemcpyAsync(slices.data(), PB.ops.p, 4 * (size_t)n_slices, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return fail(e, "download");
-    if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return fail(e, "kernel");
+    if ((e = hipMemcpyAsync(counts.data(), B.n_ops.p, 4 * (size_t)ng, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return hip_fail(v, who, "download", e);
+    if ((e = hipMemcpyAsync(slices.data(), B.ops.p, 4 * (size_t)n_slices, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return hip_fail(v, who, "download", e);
+    if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return hip_fail(v, who, "kernel", e);
     for (int64_t u = 0; u < ng; u++) {
       const TracePair& tp = tps[g0 + (size_t)u];
       const int32_t c = counts[(size_t)u];
@@ -617,17 +459,6 @@ int check_pairs(const int64_t* pairs, int64_t n, int64_t n_bases, std::string* e
       }
     }
     if (p[6] < 0) { *err = std::string(who) + ": pair " + std::to_string(q) + " has a negative band (" + std::to_string(p[6]) + ")"; return MHAP_E_INVALID; }
-  }
-  return MHAP_OK;
-}
-
-int upload_bases(const HandleView& v, BandedBufs& B, const uint8_t* bases, int64_t n_bases, const char* who) {
-  hipError_t e;
-  (void)hipSetDevice(v.device);
-  if ((e = B.bases.ensure((size_t)std::max<int64_t>(n_bases, 1))) != hipSuccess) { *v.err = std::string(who) + ": hipMalloc: " + hipGetErrorString(e); return MHAP_E_HIP; }
-  if (n_bases > 0 && (e = hipMemcpyAsync(B.bases.p, bases, (size_t)n_bases, hipMemcpyHostToDevice, v.stream)) != hipSuccess) {
-    *v.err = std::string(who) + ": upload: " + hipGetErrorString(e);
-    return MHAP_E_HIP;
   }
   return MHAP_OK;
 }
@@ -690,14 +521,11 @@ int align_banded_impl(mhap_handle* h, const uint8_t* bases, int64_t n_bases, con
   if (n == 0) { if (paths) *paths = new mhap_align_paths(); return MHAP_OK; }
   int rc = check_pairs(pairs, n, n_bases, v.err, who);
   if (rc != MHAP_OK) return rc;
-  BandedBufs B;
-  PathBufs PB;
+  AlignBufs B;
   mhap_align_paths* out = paths ? new mhap_align_paths() : nullptr;
   rc = upload_bases(v, B, bases, n_bases, who);
   if (rc == MHAP_OK) rc = banded_run(v, B, pairs, n, results, who);
-  if (rc == MHAP_OK && out) rc = paths_run(v, B, PB, pairs, n, results, 0, *out, who);
-  B.release();
-  PB.release();
+  if (rc == MHAP_OK && out) rc = paths_run(v, B, pairs, n, results, 0, *out, who);
   if (rc != MHAP_OK) delete out;
   else if (paths) *paths = out;
   return rc;
@@ -787,8 +615,7 @@ int realign_impl(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const in
   // The bases go up once.  Records go through in batches of at most BATCH: 56 + 28 bytes of pairs and results and 4 of work order per
   // record (5.8 MB) on each side, and the pass boundaries of the workgroups in flight (at most BA_SCRATCH_BUDGET, 1 GiB), whatever n is.
   constexpr int64_t BATCH = 1 << 16;
-  BandedBufs B;
-  PathBufs PB;
+  AlignBufs B;
   mhap_align_paths* po = paths ? new mhap_align_paths() : nullptr;
   int rc = upload_bases(v, B, bases, n_bases, who);
   std::vector<int64_t> pairs((size_t)std::min(n, BATCH) * 7);
@@ -800,7 +627,7 @@ int realign_impl(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const in
     if (rc != MHAP_OK) break;
     rc = banded_run(v, B, pairs.data(), c, res.data(), who);
     if (rc != MHAP_OK) break;
-    if (po && (rc = paths_run(v, B, PB, pairs.data(), c, res.data(), q0, *po, who)) != MHAP_OK) break;
+    if (po && (rc = paths_run(v, B, pairs.data(), c, res.data(), q0, *po, who)) != MHAP_OK) break;
     for (int64_t q = 0; q < c; q++) {
       const mhap_record& r = recs[q0 + q];
       const int32_t* a = res.data() + 7 * q;
@@ -819,8 +646,6 @@ int realign_impl(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const in
       if (detail) { detail[3 * (q0 + q)] = ok ? a[0] : 0; detail[3 * (q0 + q) + 1] = ok ? a[5] : 0; detail[3 * (q0 + q) + 2] = ok ? a[6] : 0; }
     }
   }
-  B.release();
-  PB.release();
   if (rc != MHAP_OK) delete po;
   else if (paths) *paths = po;
   return rc;
