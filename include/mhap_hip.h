@@ -558,8 +558,8 @@ void mhap_correct_free(mhap_correct_session* s);
 /* ---- string graph: dovetails, contained reads and transitive reduction over the realigned overlaps, and GFA ------------------------- */
 
 /* The layout step that follows an overlapper (Myers 2005): every realigned overlap is classed, contained reads are set aside, the
- * dovetails become the arcs of a bidirected graph and the arcs that a two-arc path explains are removed.  Left out: read trimming,
- * chimera detection, tip and bubble removal.  Everything is integer arithmetic (sums and products of lengths in
+ * dovetails become the arcs of a bidirected graph and the arcs that a two-arc path explains are removed.  Tips and simple bubbles are
+ * removed on request ("graph cleaning" below).  Left out: read trimming, chimera detection.  Everything is integer arithmetic (sums and products of lengths in
  * int64); the only floating comparison is score < min_identity on the record's double.
  *
  * Input.  A table of reads (read_ids[r], lengths[r]; no bases), realigned records (out[q] of mhap_realign_records) and the parameters
@@ -617,7 +617,8 @@ void mhap_correct_free(mhap_correct_session* s);
  * an odd vertex: snprintf semantics as mhap_format_paf; -1 for a null pointer.
  *
  * ---- unitigs: the final arcs compacted into chains, with their sequences -----------------------------------------------------------
- * Tip removal, bubble popping, chimera detection and a consensus over a unitig's reads are not part of this: a unitig is spelled
+ * Tips and simple bubbles go only when mhap_graph_clean is called ("graph cleaning" below); chimera detection and a consensus over a
+ * unitig's reads are not part of this: a unitig is spelled
  * from the reads as stored (the correction stage may be run before).  Integer arithmetic; offsets and lengths in bases are int64.
  *
  * Input.  The state of a session after a mhap_graph_finish: the arc list with its `final` flags, the contained flags, the read
@@ -668,7 +669,55 @@ void mhap_correct_free(mhap_correct_session* s);
  * `S\tutg%06d{l|c}\t<sequence>\tLN:i:<length>\tnr:i:<members>` with the number k + 1 and l for linear, c for circular, followed by
  * its members as `a\t<utg name>\t<offset>\t<read id>:1-<span>\t<+|->\t<span>`; last one `L\t<utg>\t<+|->\t<utg>\t<+|->\t<ol>M` per link in
  * link order ('-' for the twin).  Every line ends with '\n'.  mhap_format_gfa_unitig_link (no GPU) writes the L line of one link row
- * without the newline: snprintf semantics, -1 for a null pointer. */
+ * without the newline: snprintf semantics, -1 for a null pointer.
+ *
+ * ---- graph cleaning: tips clipped and simple bubbles popped, in rounds ---------------------------------------------------------------
+ * An opt-in stage behind mhap_graph_finish: short dead-end branches (a missed overlap, a read with a bad end) and two-path bubbles (a
+ * local disagreement) are removed, so that unitigs run through where they were.  Integer only; it depends on the set of records only.
+ * It is defined on the unitig graph of a snapshot: every decision of a round is a function of that round's tables alone, never of
+ * another decision of the same round.  Not done: read trimming, chimera detection, consensus, bubbles that are not simple.
+ *
+ * State.  A `dropped` byte per read (0 in play, 1 tip, 2 bubble) and a `removed` byte per arc of the list (1 when the arc is final
+ * and either of its reads is dropped); all zero when a cleaning begins.
+ *
+ * A round.  The unitigs are built exactly as above with two changes: a dropped read has no vertices, as a contained read has none,
+ * and only the final arcs that are not removed count.  An oriented unitig is (X, o): o = 0 the kept orientation, 1 the twin.  The
+ * out-links of (X, o) are the link rows that leave it; its in-links from (W, w) are exactly the out-links (X, 1 - o) -> (W, 1 - w),
+ * every link's complement being in the table.  rank(X) = (members, bases, -number), compared lexicographically: two different
+ * unitigs never tie.
+ *
+ * Tips.  (T, o) is a tip candidate when T is linear, members(T) <= tip_reads, (T, o) has no in-link and at least one out-link; so in
+ * at most one orientation, and an isolated chain, a lone read or a circular unitig never is one.  A candidate is removed when every
+ * target (J, j) of its out-links has a holder: an in-link from some (W, w) with W != T where (W, w) is no tip candidate or
+ * rank(W) > rank(T).  A junction thus keeps its best way in, and a terminal fork loses only its lesser arms.
+ *
+ * Bubbles.  (B, o) is a branch between (S, s) and (E, e) when B is linear, bases(B) <= bubble_bases, (B, o) has exactly one in-link,
+ * from (S, s), and exactly one out-link, to (E, e), and B is neither S nor E.  A branch is removed when a branch (B', o') of another
+ * unitig between the same (S, s) and (E, e) has rank(B') > rank(B).  S may have any number of out-links; only such simple bubbles
+ * are popped.  The twin (B, 1 - o) is a branch between (E, 1 - e) and (S, 1 - s) with the same siblings: one verdict from either side.
+ *
+ * Applying a round.  Every member read of a removed unitig gets dropped = 1 (tip) or 2 (bubble) — no unitig is both, a tip having no
+ * in-link — and `removed` is computed again.  Rounds repeat until one removes nothing or max_rounds have run; the count of rounds
+ * includes the last, empty one.  Then the unitigs are built once more, from the cleaned graph: the build the copy and spell calls serve.
+ *
+ * Parameters: tip_reads (4), bubble_bases (50 000), max_rounds (16).  Counts: MHAP_CLEAN_COUNTS int64: rounds, tip unitigs, tip reads,
+ * bubble unitigs, bubble reads, arcs removed.
+ *
+ * The calls.  mhap_graph_clean (params NULL: the defaults) needs a completed finish with no record added after it, as
+ * mhap_graph_unitigs does; MHAP_E_INVALID for a negative parameter or max_rounds < 1.  It may be repeated: each call starts again
+ * from the uncleaned graph.  After it mhap_graph_unitigs_info, _copy_unitigs, _copy_layout, _copy_links, _spell and _spell_device
+ * serve the cleaned unitigs, and mhap_graph_unitigs_counts gives their MHAP_UNITIG_COUNTS (always those of the unitigs now served:
+ * of the last mhap_graph_unitigs or mhap_graph_clean, MHAP_E_INVALID while there are none); a link row's `arc` is still the index in the arc list, which does not change (mhap_graph_copy_arcs
+ * and its rows are what they were).  mhap_graph_unitigs keeps its meaning: it builds the uncleaned unitigs, which the copy calls then
+ * serve again, and does not disturb the two bytes.  mhap_graph_copy_dropped writes one byte per read, mhap_graph_copy_removed one per
+ * arc; both return MHAP_E_INVALID before the first clean and after a later mhap_graph_finish, which forgets the clean state and
+ * invalidates the unitigs as before.  On the device (graph_kernels.hip) a round is the unitig build and six kernels, one lane per
+ * oriented unitig, unitig, member or arc, placed by binary search in the link table, which is in arc-list order; the host waits
+ * once per round, for the round's counts.  Device memory, from the first mhap_graph_clean to mhap_graph_free: 20 bytes per read and
+ * 1 per arc, and the unitig tables at their largest: 41 bytes per read (a unitig and a member each) and 24 per arc (a link each).
+ *
+ * GFA.  The text of the cleaned read graph is the GFA 1 text of the string graph without the S lines of dropped reads and the L
+ * lines of removed arcs; the text of the cleaned unitig graph is the unitig text of the cleaned unitigs. */
 typedef struct mhap_graph_params {
   int32_t max_hang, int_frac_permille, min_ovlp, fuzz;
   double min_identity;
@@ -697,6 +746,13 @@ int mhap_graph_spell(mhap_graph_session* s, const uint8_t* bases, int64_t n_base
 int mhap_graph_spell_device(mhap_graph_session* s, const uint8_t* device_bases, int64_t n_bases, const int64_t* offsets /* n_reads */,
                             uint8_t* out /* all bases */);
 int mhap_format_gfa_unitig_link(const int32_t* row6, char* out, size_t cap);
+typedef struct mhap_clean_params { int32_t tip_reads, bubble_bases, max_rounds; } mhap_clean_params;
+#define MHAP_CLEAN_COUNTS 6
+void mhap_graph_default_clean_params(mhap_clean_params* p);
+int mhap_graph_clean(mhap_graph_session* s, const mhap_clean_params* params /* NULL: the defaults */, int64_t* counts /* MHAP_CLEAN_COUNTS */);
+int mhap_graph_copy_dropped(mhap_graph_session* s, uint8_t* per_read /* n_reads */);
+int mhap_graph_copy_removed(mhap_graph_session* s, uint8_t* per_arc /* n_arcs */);
+int mhap_graph_unitigs_counts(mhap_graph_session* s, int64_t* counts /* MHAP_UNITIG_COUNTS */);
 
 /* KmerStatSimulator's pair statistics on the GPU (J/main/KmerStatSimulator.java:163-196).  pairs: n rows of 4 int64 {a_off, a_len,
  * b_off, b_len}; a = bases[a_off, a_off + a_len) is the first read, b the second.  skip: n_skip k-mers of k bytes each, back to back, in

@@ -79,6 +79,8 @@ EXPORTED_SYMBOLS = [
     "mhap_graph_copy_classes", "mhap_graph_copy_read_flags", "mhap_graph_free", "mhap_format_gfa_link",
     "mhap_graph_unitigs", "mhap_graph_unitigs_info", "mhap_graph_copy_unitigs", "mhap_graph_copy_layout", "mhap_graph_copy_links",
     "mhap_graph_spell", "mhap_graph_spell_device", "mhap_format_gfa_unitig_link",
+    "mhap_graph_default_clean_params", "mhap_graph_clean", "mhap_graph_copy_dropped", "mhap_graph_copy_removed",
+    "mhap_graph_unitigs_counts",
     "mhap_pair_kmer_stats", "mhap_pair_kmer_stats_paths", "mhap_ksim_create", "mhap_ksim_next", "mhap_ksim_error", "mhap_ksim_destroy",
     "mhap_ksim_dev_create", "mhap_ksim_dev_destroy", "mhap_ksim_dev_pair_stats", "mhap_ksim_dev_trials",
 ]
@@ -188,6 +190,12 @@ def load_library(build_if_missing=True):
     for name in ("mhap_graph_spell", "mhap_graph_spell_device"):
         getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.mhap_format_gfa_unitig_link.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    lib.mhap_graph_default_clean_params.restype = None
+    lib.mhap_graph_default_clean_params.argtypes = [C.c_void_p]
+    lib.mhap_graph_clean.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mhap_graph_copy_dropped.argtypes = [C.c_void_p, C.c_void_p]
+    lib.mhap_graph_copy_removed.argtypes = [C.c_void_p, C.c_void_p]
+    lib.mhap_graph_unitigs_counts.argtypes = [C.c_void_p, C.c_void_p]
     for name in EXPORTED_SYMBOLS:
         getattr(lib, name)  # AttributeError here = header/library mismatch
     # a stale library next to newer host code (or the reverse) must not get as far as a struct copy
@@ -655,6 +663,13 @@ UNITIG_COUNTS = ("unitigs", "circular", "members", "joined_arcs", "links", "long
 UNITIG_LINK_FIELDS = ("from_unitig", "from_orient", "to_unitig", "to_orient", "ol", "arc")
 
 
+CLEAN_COUNTS = ("rounds", "tip_unitigs", "tip_reads", "bubble_unitigs", "bubble_reads", "arcs_removed")   # mhap_graph_clean's counts
+
+
+class _CleanParams(C.Structure):
+    _fields_ = [("tip_reads", C.c_int32), ("bubble_bases", C.c_int32), ("max_rounds", C.c_int32)]
+
+
 class _GraphParams(C.Structure):
     _fields_ = [("max_hang", C.c_int32), ("int_frac_permille", C.c_int32), ("min_ovlp", C.c_int32), ("fuzz", C.c_int32),
                 ("min_identity", C.c_double)]
@@ -672,13 +687,19 @@ def format_gfa_link(row, read_ids):
     return buf.value.decode()
 
 
-def format_gfa(read_ids, lengths, contained, arcs):
+def format_gfa(read_ids, lengths, contained, arcs, dropped=None, removed=None):
     """GFA 1 text of a string graph: the header, an S line per read that is not contained (in read_ids order), an L line per final
-    arc (in list order).  The "string graph" section of include/mhap_hip.h has the format."""
+    arc (in list order).  The "string graph" section of include/mhap_hip.h has the format.  With the `dropped` and `removed` bytes
+    of a cleaning, the text of the cleaned graph: no S line for a dropped read, no L line for a removed arc."""
     arcs = np.ascontiguousarray(arcs, dtype=np.int32).reshape(-1, 7)
+    gone = np.asarray(contained) != 0
+    keep = arcs[:, 6] != 0
+    if dropped is not None:
+        gone = gone | (np.asarray(dropped) != 0)
+        keep = keep & (np.asarray(removed) == 0)
     out = ["H\tVN:Z:1.0\n"]
-    out += [f"S\t{i}\t*\tLN:i:{n}\n" for i, n, c in zip(np.asarray(read_ids).tolist(), np.asarray(lengths).tolist(), np.asarray(contained).tolist()) if not c]
-    out += [format_gfa_link(r, read_ids) + "\n" for r in arcs[arcs[:, 6] != 0]]
+    out += [f"S\t{i}\t*\tLN:i:{n}\n" for i, n, c in zip(np.asarray(read_ids).tolist(), np.asarray(lengths).tolist(), gone.tolist()) if not c]
+    out += [format_gfa_link(r, read_ids) + "\n" for r in arcs[keep]]
     return "".join(out)
 
 
@@ -698,6 +719,12 @@ def unitig_counts_line(counts):
     c = [int(x) for x in counts]
     return (f"Unitigs: {c[0]} unitigs ({c[1]} circular) of {c[2]} reads, {c[3]} joined arcs, {c[4]} links; longest {c[5]} bases, "
             f"{c[6]} bases in all")
+
+
+def clean_counts_line(counts):
+    """The one stderr line of a graph cleaning (the driver prints the same); counts: the MHAP_CLEAN_COUNTS values in order."""
+    c = [int(x) for x in counts]
+    return f"Cleaned in {c[0]} rounds: {c[1]} tips ({c[2]} reads), {c[3]} bubbles ({c[4]} reads), {c[5]} arcs removed"
 
 
 def format_unitig_gfa(read_ids, unitigs, sequences):
@@ -728,6 +755,8 @@ class GraphSession:
             text = gs.gfa()
             u = gs.unitigs()                      # the final arcs compacted into chains: a dict of arrays
             seqs = gs.unitig_sequences(fasta)     # their sequences, a list of bytes; gs.unitig_gfa(fasta) is the GFA text
+            gs.clean()                            # tips and simple bubbles removed in rounds: a dict of CLEAN_COUNTS; after it
+                                                  # gs.cleaned_unitigs(), gs.gfa(cleaned=True), and the two calls above follow it
 
     handle: a MinHashSearch whose device and stream to use (else one is made and closed with the session)."""
 
@@ -744,6 +773,7 @@ class GraphSession:
         p = _GraphParams(max_hang, int_frac_permille, min_ovlp, fuzz, min_identity)
         self.arcs = np.zeros((0, 7), np.int32)
         self.unitigs_table = None
+        self.cleaned_table = None
         try:
             self._ms._chk(self._lib.mhap_graph_begin(self._ms._h, _ptr(self.ids) if len(self.ids) else None,
                                                      _ptr(self.lengths) if len(self.ids) else None, C.c_int64(len(self.ids)), C.byref(p),
@@ -762,6 +792,7 @@ class GraphSession:
         """(arcs, counts): the de-duplicated arc list as an int32 array (n, 7) of GRAPH_ARC_FIELDS and a dict of GRAPH_COUNTS."""
         counts = np.zeros(len(GRAPH_COUNTS), np.int64)
         self.unitigs_table = None
+        self.cleaned_table = None
         self._ms._chk(self._lib.mhap_graph_finish(self._s, _ptr(counts)))
         self.arcs = np.zeros((int(counts[GRAPH_COUNTS.index("arcs")]), 7), np.int32)
         self._ms._chk(self._lib.mhap_graph_copy_arcs(self._s, _ptr(self.arcs) if len(self.arcs) else None))
@@ -786,25 +817,69 @@ class GraphSession:
         self._ms._chk(self._lib.mhap_graph_copy_read_flags(self._s, _ptr(out) if len(out) else None))
         return out
 
-    def gfa(self):
-        """The GFA 1 text of the last finish."""
+    def gfa(self, cleaned=False):
+        """The GFA 1 text of the last finish; cleaned=True: without the reads and arcs the last clean() removed."""
+        if cleaned:
+            return format_gfa(self.ids, self.lengths, self.contained(), self.arcs, self.dropped(), self.removed())
         return format_gfa(self.ids, self.lengths, self.contained(), self.arcs)
 
-    def unitigs(self):
-        """The unitigs of the last finish (mhap_graph_unitigs / _copy_*): a dict of unitig_start (n + 1), unitig_len (n), circular (n),
-        the members' vertex, offset, span, the link rows (links, 6) of UNITIG_LINK_FIELDS, and counts, a dict of UNITIG_COUNTS."""
-        counts = np.zeros(len(UNITIG_COUNTS), np.int64)
-        self._ms._chk(self._lib.mhap_graph_unitigs(self._s, _ptr(counts)))
-        n, members, links = (int(counts[UNITIG_COUNTS.index(k)]) for k in ("unitigs", "members", "links"))
+    def _copy_unitigs(self):
+        """The tables of the unitigs the session serves now, without their counts."""
+        n, members, links, _ = self.unitigs_info()
         u = dict(unitig_start=np.zeros(n + 1, np.int64), unitig_len=np.zeros(n, np.int64), circular=np.zeros(n, np.uint8),
                  vertex=np.zeros(members, np.int32), offset=np.zeros(members, np.int64), span=np.zeros(members, np.int32),
-                 links=np.zeros((links, 6), np.int32), counts=dict(zip(UNITIG_COUNTS, counts.tolist())))
+                 links=np.zeros((links, 6), np.int32))
         opt = lambda a: _ptr(a) if len(a) else None
         self._ms._chk(self._lib.mhap_graph_copy_unitigs(self._s, _ptr(u["unitig_start"]), opt(u["unitig_len"]), opt(u["circular"])))
         self._ms._chk(self._lib.mhap_graph_copy_layout(self._s, opt(u["vertex"]), opt(u["offset"]), opt(u["span"])))
         self._ms._chk(self._lib.mhap_graph_copy_links(self._s, opt(u["links"])))
+        return u
+
+    def unitigs(self):
+        """The unitigs of the last finish (mhap_graph_unitigs / _copy_*): a dict of unitig_start (n + 1), unitig_len (n), circular (n),
+        the members' vertex, offset, span, the link rows (links, 6) of UNITIG_LINK_FIELDS, and counts, a dict of UNITIG_COUNTS.
+        Always the uncleaned ones, after a clean() too."""
+        counts = np.zeros(len(UNITIG_COUNTS), np.int64)
+        self._ms._chk(self._lib.mhap_graph_unitigs(self._s, _ptr(counts)))
+        u = self._copy_unitigs()
+        u["counts"] = dict(zip(UNITIG_COUNTS, counts.tolist()))
         self.unitigs_table = u
         return u
+
+    def clean(self, tip_reads=4, bubble_bases=50000, max_rounds=16):
+        """Clip tips and pop simple bubbles in rounds (mhap_graph_clean; "graph cleaning" in include/mhap_hip.h): a dict of
+        CLEAN_COUNTS.  Afterwards the session serves the cleaned unitigs: cleaned_unitigs() has their tables, unitig_sequences and
+        unitig_gfa follow them, gfa(cleaned=True) is the cleaned read graph.  Each call starts again from the uncleaned graph."""
+        counts = np.zeros(len(CLEAN_COUNTS), np.int64)
+        self.cleaned_table = None
+        self.unitigs_table = None
+        p = _CleanParams(tip_reads, bubble_bases, max_rounds)
+        self._ms._chk(self._lib.mhap_graph_clean(self._s, C.byref(p), _ptr(counts)))
+        u = self._copy_unitigs()
+        ucounts = np.zeros(len(UNITIG_COUNTS), np.int64)
+        self._ms._chk(self._lib.mhap_graph_unitigs_counts(self._s, _ptr(ucounts)))
+        u["counts"] = dict(zip(UNITIG_COUNTS, ucounts.tolist()))
+        self.cleaned_table = self.unitigs_table = u
+        self.clean_counts = dict(zip(CLEAN_COUNTS, counts.tolist()))
+        return self.clean_counts
+
+    def cleaned_unitigs(self):
+        """The unitigs of the last clean(), in the shape of unitigs(), as they were read then: nothing is built again."""
+        if self.cleaned_table is None:
+            raise MhapError("GraphSession.cleaned_unitigs: no clean() since the last finish()")
+        return self.cleaned_table
+
+    def dropped(self):
+        """One byte per read after a clean(): 0 in play, 1 dropped as a tip, 2 as a bubble."""
+        out = np.zeros(len(self.ids), np.uint8)
+        self._ms._chk(self._lib.mhap_graph_copy_dropped(self._s, _ptr(out) if len(out) else None))
+        return out
+
+    def removed(self):
+        """One byte per arc of the list after a clean(): 1 when the arc is final and one of its reads is dropped."""
+        out = np.zeros(len(self.arcs), np.uint8)
+        self._ms._chk(self._lib.mhap_graph_copy_removed(self._s, _ptr(out) if len(out) else None))
+        return out
 
     def spell_into(self, bases, offsets, out):
         """mhap_graph_spell: the sequences of all unitigs back to back into the uint8 array `out` (total_bases of the counts long);

@@ -1,5 +1,6 @@
 // graph_kernels.hip — the string graph of the realigned overlaps (mhap_graph_begin / _add / _finish / _copy_* / _free), its unitigs
-// (mhap_graph_unitigs / _copy_unitigs / _copy_layout / _copy_links / _spell; the kernels' list is in front of them) and the GFA link lines.  The contract — the class of a record, the arcs of a dovetail, contained reads, the arc list, the reduction and the final
+// (mhap_graph_unitigs / _copy_unitigs / _copy_layout / _copy_links / _spell; the kernels' list is in front of them), the cleaning of
+// the graph in rounds (mhap_graph_clean / _copy_dropped / _copy_removed; its kernels' list is in front of them too) and the GFA link lines.  The contract — the class of a record, the arcs of a dovetail, contained reads, the arc list, the reduction and the final
 // arcs — is the prose of include/mhap_hip.h ("string graph"); tests/string_graph_ref.py restates it.
 //
 // add: the host finds every record's two reads (and refuses the call before anything is queued), packs the record into 32 bytes and
@@ -260,14 +261,24 @@ __global__ __launch_bounds__(256) void flags_kernel(const uint32_t* __restrict__
 enum { UC_CIRCULAR = 0, UC_JOINED = 1, UC_LONGEST = 2, UC_DEVICE = 3 };
 enum { SPELL_CHUNK = MHAP_SPELL_CHUNK, SPELL_T = SPELL_CHUNK / 16 };
 
+// The masks of a build.  `dropped` (one byte per read) and `removed` (one byte per arc) are the state of the graph cleaning: with
+// MASKED a vertex is in play when its read is neither contained nor dropped and an arc counts when it is final and not removed;
+// without, the two pointers are not read and the kernels are those of the uncleaned unitigs.
+template <bool MASKED>
+__device__ inline bool counted(const int32_t* __restrict__ rows, const uint8_t* __restrict__ removed, int64_t i) {
+  if (MASKED) return rows[7 * i + 6] != 0 && removed[i] == 0;
+  return rows[7 * i + 6] != 0;
+}
+
+template <bool MASKED>
 __global__ __launch_bounds__(256) void outdeg_kernel(int64_t nv, const int64_t* __restrict__ fstart, const int32_t* __restrict__ V,
-                                                     const int32_t* __restrict__ rows, int32_t* __restrict__ fout, int32_t* __restrict__ cand,
-                                                     int32_t* __restrict__ carc) {
+                                                     const int32_t* __restrict__ rows, const uint8_t* __restrict__ removed,
+                                                     int32_t* __restrict__ fout, int32_t* __restrict__ cand, int32_t* __restrict__ carc) {
   const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (v >= nv) return;
   int32_t n = 0, c = -1, a = -1;
   for (int64_t i = fstart[v], e = fstart[v + 1]; i < e; i++)
-    if (rows[7 * i + 6]) { n++; c = V[i]; a = (int32_t)i; }
+    if (counted<MASKED>(rows, removed, i)) { n++; c = V[i]; a = (int32_t)i; }
   fout[v] = n; cand[v] = c; carc[v] = a;
 }
 
@@ -290,14 +301,16 @@ __global__ __launch_bounds__(256) void next_kernel(int64_t nv, const int32_t* __
   if ((threadIdx.x & 63) == 0 && m) atomicAdd(ucounts + UC_JOINED, (unsigned long long)__popcll(m));
 }
 
-// P < 0: the vertex of a contained read, which is in no unitig
-__global__ __launch_bounds__(256) void rank_init_kernel(int64_t nv, const uint32_t* __restrict__ contained, const int32_t* __restrict__ prev,
+// P < 0: the vertex of a contained or dropped read, which is in no unitig
+template <bool MASKED>
+__global__ __launch_bounds__(256) void rank_init_kernel(int64_t nv, const uint32_t* __restrict__ contained, const uint8_t* __restrict__ dropped,
+                                                        const int32_t* __restrict__ prev,
                                                         const int32_t* __restrict__ span, int32_t* __restrict__ P, uint32_t* __restrict__ R,
                                                         unsigned long long* __restrict__ O) {
   const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (v >= nv) return;
   const int32_t p = prev[v];
-  if (contained[v >> 1]) { P[v] = -1; R[v] = 0; O[v] = 0; }
+  if (contained[v >> 1] || (MASKED && dropped[v >> 1])) { P[v] = -1; R[v] = 0; O[v] = 0; }
   else if (p < 0) { P[v] = (int32_t)v; R[v] = 0; O[v] = 0; }
   else { P[v] = p; R[v] = 1; O[v] = (unsigned long long)span[p]; }
 }
@@ -372,12 +385,13 @@ __global__ __launch_bounds__(256) void select_kernel(int64_t nv, const int32_t* 
   if ((threadIdx.x & 63) == 0 && m) atomicAdd(ucounts + UC_CIRCULAR, (unsigned long long)__popcll(m));
 }
 
-__global__ __launch_bounds__(256) void linkflag_kernel(int64_t n, const int32_t* __restrict__ rows, const int32_t* __restrict__ next,
-                                                       int32_t* __restrict__ islink) {
+template <bool MASKED>
+__global__ __launch_bounds__(256) void linkflag_kernel(int64_t n, const int32_t* __restrict__ rows, const uint8_t* __restrict__ removed,
+                                                       const int32_t* __restrict__ next, int32_t* __restrict__ islink) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const int32_t* r = rows + 7 * i;
-  islink[i] = (r[6] && next[r[0]] != r[1]) ? 1 : 0;
+  islink[i] = (counted<MASKED>(rows, removed, i) && next[r[0]] != r[1]) ? 1 : 0;
 }
 
 __global__ __launch_bounds__(256) void unitig_scatter_kernel(int64_t nv, const int32_t* __restrict__ kept, const int64_t* __restrict__ unum,
@@ -500,6 +514,160 @@ __global__ __launch_bounds__(SPELL_T) void spell_kernel(const uint8_t* __restric
     for (int t = 0; t < nb; t++) out[b0 + t] = (uint8_t)(w[t >> 2] >> (8 * (t & 3)));
 }
 
+// ---- graph cleaning ("graph cleaning" in the string-graph section of include/mhap_hip.h; tests/graph_clean_ref.py restates it) -----
+// A round builds the unitigs of the graph as it stands (the kernels above, with the dropped and removed bytes as masks, into tables
+// of their largest possible sizes, so that nothing waits for a size) and decides on that snapshot.  x = 2 X + o is an oriented unitig.
+//   origin_kernel    one lane per x: the rows of the link table that leave x.  The table is in arc-list order and an oriented unitig
+//                    has one tail vertex, so they are the rows whose arc lies in that vertex's segment: two binary searches
+//   degree_kernel    one lane per x: out-degree = its rows, in-degree = the rows of x ^ 1 (every link's complement is in the table),
+//                    and the tip-candidate flag
+//   tip_kernel       one lane per unitig: the candidate's out-links, and for each target its in-links, looking for a holder
+//   bubble_kernel    one lane per unitig: its S and E, then S's out-links for a better sibling between the same two
+//   drop_kernel      one lane per member: finds its unitig by binary search and, where that is removed, writes its own read
+//   removed_kernel   one lane per arc
+// A lane decides from the snapshot only and writes its own element only.  The loops over links are lane-serial: a unitig end has as
+// many links as its read keeps final arcs after the reduction, one to a handful at any coverage, and the loops are exact for any
+// number of them (a star of hundreds of tips costs the lanes at its centre that many steps, no more).
+enum { CC_ROUNDS = 0, CC_TIPS, CC_TIP_READS, CC_BUBBLES, CC_BUBBLE_READS, CC_ARCS };
+
+struct UTables {   // the unitigs of a round where the kernels find them; the sizes stay on the device
+  const int64_t *nu, *nm, *nl;
+  const int64_t *u_start, *u_len;
+  const uint8_t* u_circ;
+  const int32_t *m_vertex, *links;
+};
+
+__device__ inline int64_t members_of(const UTables& U, int64_t X) { return (X + 1 < *U.nu ? U.u_start[X + 1] : *U.nm) - U.u_start[X]; }
+
+// rank(A) > rank(B) for two different unitigs: (members, bases, -number)
+__device__ inline bool outranks(const UTables& U, int64_t A, int64_t B) {
+  const int64_t ma = members_of(U, A), mb = members_of(U, B);
+  if (ma != mb) return ma > mb;
+  if (U.u_len[A] != U.u_len[B]) return U.u_len[A] > U.u_len[B];
+  return A < B;
+}
+
+// the first link row whose arc is >= a
+__device__ inline int32_t first_link_from(const int32_t* __restrict__ links, int64_t nl, int64_t a) {
+  int64_t lo = 0, hi = nl;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (links[6 * mid + 5] < a) lo = mid + 1; else hi = mid;
+  }
+  return (int32_t)lo;
+}
+
+__global__ __launch_bounds__(256) void origin_kernel(UTables U, const int64_t* __restrict__ fstart, int32_t* __restrict__ lo,
+                                                     int32_t* __restrict__ hi) {
+  const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x, X = x >> 1;
+  if (X >= *U.nu) return;
+  int32_t a = 0, b = 0;
+  if (!U.u_circ[X]) {
+    const int32_t t = (x & 1) ? (U.m_vertex[U.u_start[X]] ^ 1) : U.m_vertex[U.u_start[X] + members_of(U, X) - 1];
+    a = first_link_from(U.links, *U.nl, fstart[t]);
+    b = first_link_from(U.links, *U.nl, fstart[t + 1]);
+  }
+  lo[x] = a; hi[x] = b;
+}
+
+__global__ __launch_bounds__(256) void degree_kernel(UTables U, const int32_t* __restrict__ lo, const int32_t* __restrict__ hi,
+                                                     int32_t tip_reads, uint8_t* __restrict__ cand) {
+  const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x, X = x >> 1;
+  if (X >= *U.nu) return;
+  const int32_t out = hi[x] - lo[x], in = hi[x ^ 1] - lo[x ^ 1];
+  cand[x] = (!U.u_circ[X] && members_of(U, X) <= tip_reads && in == 0 && out >= 1) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void tip_kernel(UTables U, const int32_t* __restrict__ lo, const int32_t* __restrict__ hi,
+                                                  const uint8_t* __restrict__ cand, uint8_t* __restrict__ verdict,
+                                                  unsigned long long* __restrict__ counts) {
+  const int64_t T = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  bool tip = false;
+  if (T < *U.nu) {
+    const int o = cand[2 * T] ? 0 : cand[2 * T + 1] ? 1 : -1;   // (a candidate in at most one orientation)
+    tip = o >= 0;
+    for (int32_t l = tip ? lo[2 * T + o] : 0, le = tip ? hi[2 * T + o] : 0; l < le && tip; l++) {
+      const int64_t y = 2 * (int64_t)U.links[6 * l + 2] + U.links[6 * l + 3];
+      bool held = false;   // the in-links of y are the out-links of y ^ 1: a row (y ^ 1) -> (W, 1 - w) is the in-link from (W, w)
+      for (int32_t m = lo[y ^ 1], me = hi[y ^ 1]; m < me && !held; m++) {
+        const int64_t W = U.links[6 * m + 2], w = 1 - U.links[6 * m + 3];
+        held = W != T && (!cand[2 * W + w] || outranks(U, W, T));
+      }
+      tip = held;
+    }
+    verdict[T] = tip ? 1 : 0;
+  }
+  const unsigned long long m = __ballot(tip);
+  if ((threadIdx.x & 63) == 0 && m) atomicAdd(counts + CC_TIPS, (unsigned long long)__popcll(m));
+}
+
+// x is a branch between S and E: one link in, one out, short enough; returns E (-1: no branch) and sets S
+__device__ inline int64_t branch_ends(const UTables& U, const int32_t* __restrict__ lo, const int32_t* __restrict__ hi, int32_t bubble_bases,
+                                      int64_t x, int64_t* S) {
+  const int64_t B = x >> 1;
+  if (U.u_circ[B] || U.u_len[B] > bubble_bases || hi[x] - lo[x] != 1 || hi[x ^ 1] - lo[x ^ 1] != 1) return -1;
+  const int32_t* out = U.links + 6 * (int64_t)lo[x];
+  const int32_t* in = U.links + 6 * (int64_t)lo[x ^ 1];
+  const int64_t E = 2 * (int64_t)out[2] + out[3], s = 2 * (int64_t)in[2] + (1 - in[3]);
+  if ((E >> 1) == B || (s >> 1) == B) return -1;
+  *S = s;
+  return E;
+}
+
+// (runs behind tip_kernel, which has written every verdict; a tip has no link in and a branch has one, so no unitig is both)
+__global__ __launch_bounds__(256) void bubble_kernel(UTables U, const int32_t* __restrict__ lo, const int32_t* __restrict__ hi,
+                                                     int32_t bubble_bases, uint8_t* __restrict__ verdict, unsigned long long* __restrict__ counts) {
+  const int64_t B = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  bool pop = false;
+  if (B < *U.nu) {
+    int64_t S = 0, S2 = 0;
+    const int64_t E = branch_ends(U, lo, hi, bubble_bases, 2 * B, &S);   // (seen from the twin the verdict is the same: one side is enough)
+    if (E >= 0)
+      for (int32_t m = lo[S], me = hi[S]; m < me && !pop; m++) {
+        const int64_t y = 2 * (int64_t)U.links[6 * m + 2] + U.links[6 * m + 3];
+        pop = (y >> 1) != B && branch_ends(U, lo, hi, bubble_bases, y, &S2) == E && S2 == S && outranks(U, y >> 1, B);
+      }
+    if (pop) verdict[B] = 2;
+  }
+  const unsigned long long m = __ballot(pop);
+  if ((threadIdx.x & 63) == 0 && m) atomicAdd(counts + CC_BUBBLES, (unsigned long long)__popcll(m));
+}
+
+__global__ __launch_bounds__(256) void drop_kernel(UTables U, const uint8_t* __restrict__ verdict, uint8_t* __restrict__ dropped,
+                                                   unsigned long long* __restrict__ counts) {
+  const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  int what = 0;
+  if (m < *U.nm) {
+    int64_t lo = 0, hi = *U.nu;   // the last unitig that begins at or before m
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (U.u_start[mid] <= m) lo = mid + 1; else hi = mid;
+    }
+    what = verdict[lo - 1];
+    if (what) dropped[U.m_vertex[m] >> 1] = (uint8_t)what;
+  }
+  const unsigned long long t = __ballot(what == 1), b = __ballot(what == 2);
+  if ((threadIdx.x & 63) == 0) {
+    if (t) atomicAdd(counts + CC_TIP_READS, (unsigned long long)__popcll(t));
+    if (b) atomicAdd(counts + CC_BUBBLE_READS, (unsigned long long)__popcll(b));
+  }
+}
+
+// removed[i] = the arc is final and one of its reads is dropped; the count takes the arcs that were not removed before
+__global__ __launch_bounds__(256) void removed_kernel(int64_t n, const int32_t* __restrict__ rows, const uint8_t* __restrict__ dropped,
+                                                      uint8_t* __restrict__ removed, unsigned long long* __restrict__ counts) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  bool fresh = false;
+  if (i < n) {
+    const int32_t* r = rows + 7 * i;
+    const bool gone = r[6] && (dropped[r[0] >> 1] || dropped[r[1] >> 1]);
+    fresh = gone && !removed[i];
+    removed[i] = gone ? 1 : 0;
+  }
+  const unsigned long long m = __ballot(fresh);
+  if ((threadIdx.x & 63) == 0 && m) atomicAdd(counts + CC_ARCS, (unsigned long long)__popcll(m));
+}
+
 }  // namespace
 }  // namespace mhap
 
@@ -522,6 +690,11 @@ struct mhap_graph_session {
   int64_t n_contained = 0, finish_records = 0, n_unitigs = -1, n_members = 0, n_links = 0, n_ubases = 0;
   DevBuf fout, cand, carc, unext, uprev, uspan, uP[2], uR[2], uO[2], uQ[2], uM[2], cyc, tail, cnt, ulen, kept, unum, mstart, bstart, islink, lstart,
       ucounts, u_start, u_len, u_circ, m_vertex, m_offset, m_span, m_dst, links, d_roff, d_bases, spelled;
+  int64_t last_counts[MHAP_UNITIG_COUNTS] = {0};          // the counts of the unitigs now served
+  int u_cur = 0;                                          // which of uP / uR / uO the last build's ranks ended in
+  // cleaning: the dropped and removed bytes hold from a mhap_graph_clean to the next finish
+  bool cleaned = false;
+  DevBuf dropped, removed, ccounts, o_lo, o_hi, o_cand, verdict;
   void reap(bool all) {
     while (!pending.empty() && (all || hipEventQuery(pending.front().ev) == hipSuccess)) {
       (void)hipEventDestroy(pending.front().ev);
@@ -535,7 +708,7 @@ struct mhap_graph_session {
     for (DevBuf* b : {&d_lengths, &contained, &counts, &deg, &fill, &start, &fstart, &tmp, &keep, &U, &V, &LEN, &Q, &bt_v, &bt_pos, &mark, &rows,
                        &fout, &cand, &carc, &unext, &uprev, &uspan, &uP[0], &uP[1], &uR[0], &uR[1], &uO[0], &uO[1], &uQ[0], &uQ[1], &uM[0], &uM[1], &cyc,
                        &tail, &cnt, &ulen, &kept, &unum, &mstart, &bstart, &islink, &lstart, &ucounts, &u_start, &u_len, &u_circ, &m_vertex, &m_offset,
-                       &m_span, &m_dst, &links, &d_roff, &d_bases, &spelled}) b->release();
+                       &m_span, &m_dst, &links, &d_roff, &d_bases, &spelled, &dropped, &removed, &ccounts, &o_lo, &o_hi, &o_cand, &verdict}) b->release();
   }
 };
 
@@ -657,6 +830,7 @@ extern "C" int mhap_graph_finish(mhap_graph_session* s, int64_t* counts) {
   (void)hipSetDevice(v.device);
   s->n_arcs = -1;
   s->n_unitigs = -1;
+  s->cleaned = false;   // (a clean starts from zeroed bytes: nothing to zero here)
   const int64_t nv = 2 * s->n_reads;
   hipError_t e = hipSuccess;
   auto fail = [&](const char* what) { return hip_fail(v, who, what, e); };
@@ -776,21 +950,23 @@ extern "C" int mhap_graph_copy_read_flags(mhap_graph_session* s, uint8_t* flags)
   return MHAP_OK;
 }
 
-extern "C" int mhap_graph_unitigs(mhap_graph_session* s, int64_t* counts) {
-  const char* who = "mhap_graph_unitigs";
-  if (!s) return MHAP_E_INVALID;
-  HandleView v = handle_view(s->h);
-  if (!counts) { *v.err = std::string(who) + ": null argument"; return MHAP_E_INVALID; }
+namespace {
+
+// The refusals mhap_graph_unitigs and mhap_graph_clean share.
+int need_finish(mhap_graph_session* s, const HandleView& v, const char* who) {
   if (s->n_arcs < 0) { *v.err = std::string(who) + ": no mhap_graph_finish has completed"; return MHAP_E_INVALID; }
   if (s->n_records != s->finish_records) {   // (an add may have set contained flags the list does not know of)
     *v.err = std::string(who) + ": records were added after the last mhap_graph_finish";
     return MHAP_E_INVALID;
   }
-  (void)hipSetDevice(v.device);
-  s->n_unitigs = -1;
+  return MHAP_OK;
+}
+
+// A unitig build in two halves, queued without a wait, over the vertices and arcs the masks leave (both null: the uncleaned graph).
+// Front: everything up to the four numbering scans, whose last entries are the sizes.  Back: the tables in their places; they must
+// hold the sizes of this build (mhap_graph_unitigs reads the sizes in between, a cleaning round allocates for the largest possible).
+int unitigs_front(mhap_graph_session* s, const HandleView& v, const char* who, const uint8_t* dropped, const uint8_t* removed) {
   const int64_t nv = 2 * s->n_reads, na = s->n_arcs;
-  for (int k = 0; k < MHAP_UNITIG_COUNTS; k++) counts[k] = 0;
-  if (nv == 0) { s->n_unitigs = s->n_members = s->n_links = s->n_ubases = 0; return MHAP_OK; }
   hipError_t e = hipSuccess;
   auto fail = [&](const char* what) { return hip_fail(v, who, what, e); };
   const size_t v4 = 4 * (size_t)nv, v8 = 8 * (size_t)nv, s8 = 8 * (size_t)(nv + 1), a4 = 4 * (size_t)std::max<int64_t>(na, 1), as8 = 8 * (size_t)(na + 1);
@@ -808,8 +984,9 @@ extern "C" int mhap_graph_unitigs(mhap_graph_session* s, int64_t* counts) {
       (e = hipMemsetAsync(s->cnt.p, 0, v4, v.stream)) != hipSuccess || (e = hipMemsetAsync(s->ulen.p, 0, v8, v.stream)) != hipSuccess ||
       (e = hipMemsetAsync(d_uc, 0, 8 * UC_DEVICE, v.stream)) != hipSuccess) return fail("memset");
   const dim3 gv(blocks256(nv)), b256(256);
-  hipLaunchKernelGGL(outdeg_kernel, gv, b256, 0, v.stream, nv, s->fstart.as<int64_t>(), s->V.as<int32_t>(), s->rows.as<int32_t>(), s->fout.as<int32_t>(),
-                     s->cand.as<int32_t>(), s->carc.as<int32_t>());
+  const bool masks = dropped != nullptr;   // (both or neither)
+  hipLaunchKernelGGL(masks ? outdeg_kernel<true> : outdeg_kernel<false>, gv, b256, 0, v.stream, nv, s->fstart.as<int64_t>(), s->V.as<int32_t>(),
+                     s->rows.as<int32_t>(), removed, s->fout.as<int32_t>(), s->cand.as<int32_t>(), s->carc.as<int32_t>());
   hipLaunchKernelGGL(next_kernel, gv, b256, 0, v.stream, nv, s->fout.as<int32_t>(), s->cand.as<int32_t>(), s->carc.as<int32_t>(), s->LEN.as<int32_t>(),
                      s->d_lengths.as<int32_t>(), s->unext.as<int32_t>(), s->uprev.as<int32_t>(), s->uspan.as<int32_t>(), d_uc);
   // the rounds: 2^rounds >= the vertices in play, which no chain and no cycle exceeds; nothing waits between them
@@ -823,7 +1000,7 @@ extern "C" int mhap_graph_unitigs(mhap_graph_session* s, int64_t* counts) {
                          s->uO[cur].as<unsigned long long>(), s->uP[cur ^ 1].as<int32_t>(), s->uR[cur ^ 1].as<uint32_t>(),
                          s->uO[cur ^ 1].as<unsigned long long>());
   };
-  hipLaunchKernelGGL(rank_init_kernel, gv, b256, 0, v.stream, nv, s->contained.as<uint32_t>(), s->uprev.as<int32_t>(), s->uspan.as<int32_t>(),
+  hipLaunchKernelGGL(masks ? rank_init_kernel<true> : rank_init_kernel<false>, gv, b256, 0, v.stream, nv, s->contained.as<uint32_t>(), dropped, s->uprev.as<int32_t>(), s->uspan.as<int32_t>(),
                      s->uP[0].as<int32_t>(), s->uR[0].as<uint32_t>(), s->uO[0].as<unsigned long long>());
   rank_rounds();
   hipLaunchKernelGGL(cyc_init_kernel, gv, b256, 0, v.stream, nv, s->uP[cur].as<int32_t>(), s->uprev.as<int32_t>(), s->cyc.as<uint8_t>(),
@@ -836,6 +1013,7 @@ extern "C" int mhap_graph_unitigs(mhap_graph_session* s, int64_t* counts) {
   hipLaunchKernelGGL(cut_init_kernel, gv, b256, 0, v.stream, nv, s->cyc.as<uint8_t>(), M, s->uprev.as<int32_t>(), s->uspan.as<int32_t>(),
                      s->uP[cur].as<int32_t>(), s->uR[cur].as<uint32_t>(), s->uO[cur].as<unsigned long long>());
   rank_rounds();
+  s->u_cur = cur;   // where the ranks ended: the back half reads them
   const int32_t* P = s->uP[cur].as<int32_t>();
   const uint32_t* R = s->uR[cur].as<uint32_t>();
   const unsigned long long* O = s->uO[cur].as<unsigned long long>();
@@ -846,35 +1024,169 @@ extern "C" int mhap_graph_unitigs(mhap_graph_session* s, int64_t* counts) {
   hipLaunchKernelGGL(scan_kernel<int32_t>, dim3(1), dim3(1024), 0, v.stream, s->kept.as<int32_t>(), nv, s->unum.as<int64_t>());
   hipLaunchKernelGGL(scan_kernel<int32_t>, dim3(1), dim3(1024), 0, v.stream, s->cnt.as<int32_t>(), nv, s->mstart.as<int64_t>());
   hipLaunchKernelGGL(scan_kernel<int64_t>, dim3(1), dim3(1024), 0, v.stream, s->ulen.as<int64_t>(), nv, s->bstart.as<int64_t>());
-  if (na > 0) hipLaunchKernelGGL(linkflag_kernel, dim3(blocks256(na)), b256, 0, v.stream, na, s->rows.as<int32_t>(), s->unext.as<int32_t>(),
-                                 s->islink.as<int32_t>());
+  if (na > 0) hipLaunchKernelGGL(masks ? linkflag_kernel<true> : linkflag_kernel<false>, dim3(blocks256(na)), b256, 0, v.stream, na,
+                                 s->rows.as<int32_t>(), removed, s->unext.as<int32_t>(), s->islink.as<int32_t>());
   hipLaunchKernelGGL(scan_kernel<int32_t>, dim3(1), dim3(1024), 0, v.stream, s->islink.as<int32_t>(), na, s->lstart.as<int64_t>());
   if ((e = hipGetLastError()) != hipSuccess) return fail("launch");
+  return MHAP_OK;
+}
+
+// the tables for nu unitigs, nm members and nl links
+int unitigs_tables(mhap_graph_session* s, const HandleView& v, const char* who, int64_t nu, int64_t nm, int64_t nl) {
+  const size_t ub = (size_t)std::max<int64_t>(nu, 1), mb = (size_t)std::max<int64_t>(nm, 1), lb = (size_t)std::max<int64_t>(nl, 1);
+  hipError_t e;
+  if ((e = s->u_start.ensure(8 * ub)) != hipSuccess || (e = s->u_len.ensure(8 * ub)) != hipSuccess || (e = s->u_circ.ensure(ub)) != hipSuccess ||
+      (e = s->m_vertex.ensure(4 * mb)) != hipSuccess || (e = s->m_offset.ensure(8 * mb)) != hipSuccess || (e = s->m_span.ensure(4 * mb)) != hipSuccess ||
+      (e = s->m_dst.ensure(8 * mb)) != hipSuccess || (e = s->links.ensure(24 * lb)) != hipSuccess) return hip_fail(v, who, "hipMalloc of the unitigs", e);
+  return MHAP_OK;
+}
+
+int unitigs_back(mhap_graph_session* s, const HandleView& v, const char* who, bool links) {
+  const int64_t nv = 2 * s->n_reads, na = s->n_arcs;
+  const dim3 gv(blocks256(nv)), b256(256);
+  const int32_t* P = s->uP[s->u_cur].as<int32_t>();
+  const uint32_t* R = s->uR[s->u_cur].as<uint32_t>();
+  const unsigned long long* O = s->uO[s->u_cur].as<unsigned long long>();
+  hipLaunchKernelGGL(unitig_scatter_kernel, gv, b256, 0, v.stream, nv, s->kept.as<int32_t>(), s->unum.as<int64_t>(), s->mstart.as<int64_t>(),
+                     s->ulen.as<int64_t>(), s->cyc.as<uint8_t>(), s->u_start.as<int64_t>(), s->u_len.as<int64_t>(), s->u_circ.as<uint8_t>());
+  hipLaunchKernelGGL(member_scatter_kernel, gv, b256, 0, v.stream, nv, P, R, O, s->uspan.as<int32_t>(), s->kept.as<int32_t>(), s->mstart.as<int64_t>(),
+                     s->bstart.as<int64_t>(), s->m_vertex.as<int32_t>(), s->m_offset.as<int64_t>(), s->m_span.as<int32_t>(), s->m_dst.as<int64_t>());
+  if (links) hipLaunchKernelGGL(link_scatter_kernel, dim3(blocks256(na)), b256, 0, v.stream, na, s->rows.as<int32_t>(), s->islink.as<int32_t>(),
+                                s->lstart.as<int64_t>(), P, s->kept.as<int32_t>(), s->unum.as<int64_t>(), s->links.as<int32_t>());
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? hip_fail(v, who, "launch", e) : MHAP_OK;
+}
+
+// The unitigs the copy and spell calls serve, built anew over what the masks leave; counts: MHAP_UNITIG_COUNTS.
+int build_unitigs(mhap_graph_session* s, const HandleView& v, const char* who, const uint8_t* dropped, const uint8_t* removed, int64_t* counts) {
+  s->n_unitigs = -1;
+  const int64_t nv = 2 * s->n_reads, na = s->n_arcs;
+  for (int k = 0; k < MHAP_UNITIG_COUNTS; k++) counts[k] = 0;
+  for (int k = 0; k < MHAP_UNITIG_COUNTS; k++) s->last_counts[k] = 0;
+  if (nv == 0) { s->n_unitigs = s->n_members = s->n_links = s->n_ubases = 0; return MHAP_OK; }
+  hipError_t e = hipSuccess;
+  auto fail = [&](const char* what) { return hip_fail(v, who, what, e); };
+  int rc = unitigs_front(s, v, who, dropped, removed);
+  if (rc != MHAP_OK) return rc;
   int64_t nu = 0, nm = 0, nb = 0, nl = 0;
   if ((e = hipMemcpyAsync(&nu, s->unum.as<int64_t>() + nv, 8, hipMemcpyDeviceToHost, v.stream)) != hipSuccess ||
       (e = hipMemcpyAsync(&nm, s->mstart.as<int64_t>() + nv, 8, hipMemcpyDeviceToHost, v.stream)) != hipSuccess ||
       (e = hipMemcpyAsync(&nb, s->bstart.as<int64_t>() + nv, 8, hipMemcpyDeviceToHost, v.stream)) != hipSuccess ||
       (e = hipMemcpyAsync(&nl, s->lstart.as<int64_t>() + na, 8, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return fail("download");
   if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return fail("kernel");
-  const size_t ub = (size_t)std::max<int64_t>(nu, 1), mb = (size_t)std::max<int64_t>(nm, 1), lb = (size_t)std::max<int64_t>(nl, 1);
-  if ((e = s->u_start.ensure(8 * ub)) != hipSuccess || (e = s->u_len.ensure(8 * ub)) != hipSuccess || (e = s->u_circ.ensure(ub)) != hipSuccess ||
-      (e = s->m_vertex.ensure(4 * mb)) != hipSuccess || (e = s->m_offset.ensure(8 * mb)) != hipSuccess || (e = s->m_span.ensure(4 * mb)) != hipSuccess ||
-      (e = s->m_dst.ensure(8 * mb)) != hipSuccess || (e = s->links.ensure(24 * lb)) != hipSuccess) return fail("hipMalloc of the unitigs");
-  hipLaunchKernelGGL(unitig_scatter_kernel, gv, b256, 0, v.stream, nv, s->kept.as<int32_t>(), s->unum.as<int64_t>(), s->mstart.as<int64_t>(),
-                     s->ulen.as<int64_t>(), s->cyc.as<uint8_t>(), s->u_start.as<int64_t>(), s->u_len.as<int64_t>(), s->u_circ.as<uint8_t>());
-  hipLaunchKernelGGL(member_scatter_kernel, gv, b256, 0, v.stream, nv, P, R, O, s->uspan.as<int32_t>(), s->kept.as<int32_t>(), s->mstart.as<int64_t>(),
-                     s->bstart.as<int64_t>(), s->m_vertex.as<int32_t>(), s->m_offset.as<int64_t>(), s->m_span.as<int32_t>(), s->m_dst.as<int64_t>());
-  if (nl > 0) hipLaunchKernelGGL(link_scatter_kernel, dim3(blocks256(na)), b256, 0, v.stream, na, s->rows.as<int32_t>(), s->islink.as<int32_t>(),
-                                 s->lstart.as<int64_t>(), P, s->kept.as<int32_t>(), s->unum.as<int64_t>(), s->links.as<int32_t>());
-  if ((e = hipGetLastError()) != hipSuccess) return fail("launch");
+  if ((rc = unitigs_tables(s, v, who, nu, nm, nl)) != MHAP_OK || (rc = unitigs_back(s, v, who, nl > 0)) != MHAP_OK) return rc;
   unsigned long long hc[UC_DEVICE];
-  if ((e = hipMemcpyAsync(hc, d_uc, sizeof hc, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return fail("download");
+  if ((e = hipMemcpyAsync(hc, s->ucounts.p, sizeof hc, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return fail("download");
   if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return fail("kernel");
   counts[0] = nu; counts[1] = (int64_t)hc[UC_CIRCULAR]; counts[2] = nm; counts[3] = (int64_t)hc[UC_JOINED]; counts[4] = nl;
   counts[5] = (int64_t)hc[UC_LONGEST]; counts[6] = nb;
+  for (int k = 0; k < MHAP_UNITIG_COUNTS; k++) s->last_counts[k] = counts[k];
   s->n_members = nm; s->n_links = nl; s->n_ubases = nb;
   s->n_unitigs = nu;
   return MHAP_OK;
+}
+
+}  // namespace
+
+extern "C" int mhap_graph_unitigs(mhap_graph_session* s, int64_t* counts) {
+  const char* who = "mhap_graph_unitigs";
+  if (!s) return MHAP_E_INVALID;
+  HandleView v = handle_view(s->h);
+  if (!counts) { *v.err = std::string(who) + ": null argument"; return MHAP_E_INVALID; }
+  const int rc = need_finish(s, v, who);
+  if (rc != MHAP_OK) return rc;
+  (void)hipSetDevice(v.device);
+  return build_unitigs(s, v, who, nullptr, nullptr, counts);
+}
+
+extern "C" void mhap_graph_default_clean_params(mhap_clean_params* p) {
+  if (!p) return;
+  p->tip_reads = 4; p->bubble_bases = 50000; p->max_rounds = 16;
+}
+
+extern "C" int mhap_graph_clean(mhap_graph_session* s, const mhap_clean_params* params, int64_t* counts) {
+  const char* who = "mhap_graph_clean";
+  if (!s) return MHAP_E_INVALID;
+  HandleView v = handle_view(s->h);
+  if (!counts) { *v.err = std::string(who) + ": null argument"; return MHAP_E_INVALID; }
+  mhap_clean_params p;
+  mhap_graph_default_clean_params(&p);
+  if (params) p = *params;
+  if (p.tip_reads < 0 || p.bubble_bases < 0 || p.max_rounds < 1) {
+    *v.err = std::string(who) + ": tip_reads and bubble_bases must be >= 0 and max_rounds >= 1";
+    return MHAP_E_INVALID;
+  }
+  int rc = need_finish(s, v, who);
+  if (rc != MHAP_OK) return rc;
+  (void)hipSetDevice(v.device);
+  s->n_unitigs = -1;
+  s->cleaned = false;
+  const int64_t nr = s->n_reads, nv = 2 * nr, na = s->n_arcs;
+  hipError_t e = hipSuccess;
+  auto fail = [&](const char* what) { return hip_fail(v, who, what, e); };
+  const size_t rb = (size_t)std::max<int64_t>(nr, 1), ab = (size_t)std::max<int64_t>(na, 1);
+  if ((e = s->dropped.ensure(rb)) != hipSuccess || (e = s->removed.ensure(ab)) != hipSuccess || (e = s->ccounts.ensure(8 * MHAP_CLEAN_COUNTS)) != hipSuccess ||
+      (e = s->o_lo.ensure(4 * 2 * rb)) != hipSuccess || (e = s->o_hi.ensure(4 * 2 * rb)) != hipSuccess || (e = s->o_cand.ensure(2 * rb)) != hipSuccess ||
+      (e = s->verdict.ensure(rb)) != hipSuccess) return fail("hipMalloc of the clean state");
+  // every call starts again from the uncleaned graph
+  if ((e = hipMemsetAsync(s->dropped.p, 0, rb, v.stream)) != hipSuccess || (e = hipMemsetAsync(s->removed.p, 0, ab, v.stream)) != hipSuccess ||
+      (e = hipMemsetAsync(s->ccounts.p, 0, 8 * MHAP_CLEAN_COUNTS, v.stream)) != hipSuccess) return fail("memset");
+  unsigned long long hc[MHAP_CLEAN_COUNTS] = {0};
+  int64_t rounds = 0;
+  if (nv > 0) {
+    // a round's tables at their largest: a unitig and a member per read, a link per arc
+    if ((rc = unitigs_tables(s, v, who, nr, nr, na)) != MHAP_OK) return rc;
+    uint8_t* dropped = s->dropped.as<uint8_t>();
+    uint8_t* removed = s->removed.as<uint8_t>();
+    unsigned long long* d_cc = s->ccounts.as<unsigned long long>();
+    const dim3 gx(blocks256(nv)), gr(blocks256(nr)), b256(256);
+    unsigned long long before = 0;
+    while (rounds < p.max_rounds) {
+      if ((rc = unitigs_front(s, v, who, dropped, removed)) != MHAP_OK || (rc = unitigs_back(s, v, who, na > 0)) != MHAP_OK) return rc;
+      const UTables U{s->unum.as<int64_t>() + nv, s->mstart.as<int64_t>() + nv, s->lstart.as<int64_t>() + na, s->u_start.as<int64_t>(),
+                      s->u_len.as<int64_t>(), s->u_circ.as<uint8_t>(), s->m_vertex.as<int32_t>(), s->links.as<int32_t>()};
+      hipLaunchKernelGGL(origin_kernel, gx, b256, 0, v.stream, U, s->fstart.as<int64_t>(), s->o_lo.as<int32_t>(), s->o_hi.as<int32_t>());
+      hipLaunchKernelGGL(degree_kernel, gx, b256, 0, v.stream, U, s->o_lo.as<int32_t>(), s->o_hi.as<int32_t>(), p.tip_reads, s->o_cand.as<uint8_t>());
+      hipLaunchKernelGGL(tip_kernel, gr, b256, 0, v.stream, U, s->o_lo.as<int32_t>(), s->o_hi.as<int32_t>(), s->o_cand.as<uint8_t>(),
+                         s->verdict.as<uint8_t>(), d_cc);
+      hipLaunchKernelGGL(bubble_kernel, gr, b256, 0, v.stream, U, s->o_lo.as<int32_t>(), s->o_hi.as<int32_t>(), p.bubble_bases, s->verdict.as<uint8_t>(), d_cc);
+      hipLaunchKernelGGL(drop_kernel, gr, b256, 0, v.stream, U, s->verdict.as<uint8_t>(), dropped, d_cc);
+      if (na > 0) hipLaunchKernelGGL(removed_kernel, dim3(blocks256(na)), b256, 0, v.stream, na, s->rows.as<int32_t>(), dropped, removed, d_cc);
+      if ((e = hipGetLastError()) != hipSuccess) return fail("launch");
+      // the one wait of a round: did it remove anything
+      if ((e = hipMemcpyAsync(hc, d_cc, sizeof hc, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return fail("download");
+      if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return fail("kernel");
+      rounds++;
+      if (hc[CC_TIPS] + hc[CC_BUBBLES] == before) break;
+      before = hc[CC_TIPS] + hc[CC_BUBBLES];
+    }
+  } else rounds = 1;
+  int64_t uc[MHAP_UNITIG_COUNTS];
+  if ((rc = build_unitigs(s, v, who, s->dropped.as<uint8_t>(), s->removed.as<uint8_t>(), uc)) != MHAP_OK) return rc;
+  for (int k = 0; k < MHAP_CLEAN_COUNTS; k++) counts[k] = (int64_t)hc[k];
+  counts[CC_ROUNDS] = rounds;
+  s->cleaned = true;
+  return MHAP_OK;
+}
+
+extern "C" int mhap_graph_copy_dropped(mhap_graph_session* s, uint8_t* per_read) {
+  const char* who = "mhap_graph_copy_dropped";
+  if (!s) return MHAP_E_INVALID;
+  HandleView v = handle_view(s->h);
+  if (!s->cleaned) { *v.err = std::string(who) + ": no mhap_graph_clean has completed since the last mhap_graph_finish"; return MHAP_E_INVALID; }
+  if (s->n_reads == 0) return MHAP_OK;
+  if (!per_read) { *v.err = std::string(who) + ": null argument"; return MHAP_E_INVALID; }
+  return download(s, who, per_read, s->dropped.p, (size_t)s->n_reads);
+}
+
+extern "C" int mhap_graph_copy_removed(mhap_graph_session* s, uint8_t* per_arc) {
+  const char* who = "mhap_graph_copy_removed";
+  if (!s) return MHAP_E_INVALID;
+  HandleView v = handle_view(s->h);
+  if (!s->cleaned) { *v.err = std::string(who) + ": no mhap_graph_clean has completed since the last mhap_graph_finish"; return MHAP_E_INVALID; }
+  if (s->n_arcs == 0) return MHAP_OK;
+  if (!per_arc) { *v.err = std::string(who) + ": null argument"; return MHAP_E_INVALID; }
+  return download(s, who, per_arc, s->removed.p, (size_t)s->n_arcs);
 }
 
 namespace {
@@ -899,6 +1211,16 @@ extern "C" int mhap_graph_unitigs_info(const mhap_graph_session* s, int64_t* n_u
   if (n_members) *n_members = s->n_unitigs < 0 ? 0 : s->n_members;
   if (n_links) *n_links = s->n_unitigs < 0 ? 0 : s->n_links;
   if (n_bases) *n_bases = s->n_unitigs < 0 ? 0 : s->n_ubases;
+  return MHAP_OK;
+}
+
+extern "C" int mhap_graph_unitigs_counts(mhap_graph_session* s, int64_t* counts) {
+  const char* who = "mhap_graph_unitigs_counts";
+  if (!s) return MHAP_E_INVALID;
+  const int rc = need_unitigs(s, who);
+  if (rc != MHAP_OK) return rc;
+  if (!counts) return null_arg(s, who);
+  for (int k = 0; k < MHAP_UNITIG_COUNTS; k++) counts[k] = s->last_counts[k];
   return MHAP_OK;
 }
 

@@ -43,13 +43,14 @@ struct Options {
     return t;
   }
   // (the realignment flags are listed only when --realign is given, the correction flags only when --correct is, the graph's only
-  // when --gfa is: without them every line the driver writes is what it was before them)
+  // when --gfa is, the cleaning's only when --gfa-clean is: without them every line the driver writes is what it was before them)
   std::string dump() const {
     std::string t;
     for (auto& n : order) {
       if (n.compare(0, 9, "--realign") == 0 && !b("--realign")) continue;
       if (n.compare(0, 9, "--correct") == 0 && !isset("--correct")) continue;
       if (n.compare(0, 5, "--gfa") == 0 && !isset("--gfa")) continue;
+      if ((n == "--gfa-clean" || n == "--gfa-tip-reads" || n == "--gfa-bubble-bases" || n == "--gfa-clean-rounds") && !b("--gfa-clean")) continue;
       t += n + " = " + m.at(n).value + "\n";
     }
     return t;
@@ -416,6 +417,10 @@ int main(int argc, char** argv) {
   o.add("--gfa-max-hang", "[int] With --gfa, the longest unaligned end an overlap may leave on both reads before it counts as an internal match.", "1000");
   o.add("--gfa-min-overlap", "[int] With --gfa, the shortest overlap that becomes an arc.", "2000");
   o.add("--gfa-fuzz", "[int] With --gfa, the slack of the transitive reduction in bases.", "1000");
+  o.add("--gfa-clean", "With --gfa: clean the string graph on the GPU before the files are written: tips are clipped and simple bubbles popped, in rounds. The --gfa file is then the cleaned graph and the --gfa-unitigs file holds the unitigs of the cleaned graph.", "false", true);
+  o.add("--gfa-tip-reads", "[int] With --gfa-clean, the most reads a tip may have.", "4");
+  o.add("--gfa-bubble-bases", "[int] With --gfa-clean, the most bases a popped bubble branch may have.", "50000");
+  o.add("--gfa-clean-rounds", "[int] With --gfa-clean, the most rounds of cleaning.", "16");
   if (!o.parse(argc, argv)) return 0;
 
   auto bad = [&](const char* m) { printf("%s\n", m); exit(1); };
@@ -471,6 +476,10 @@ int main(int argc, char** argv) {
     if (!gfa) bad("--gfa-unitigs compacts the graph of --gfa: give --gfa too.");
     if (o.s("--gfa-unitigs").empty()) bad("--gfa-unitigs needs the name of the GFA file to write.");
   }
+  for (const char* n : {"--gfa-clean", "--gfa-tip-reads", "--gfa-bubble-bases", "--gfa-clean-rounds"})   // refused before a handle exists
+    if (o.isset(n) && !gfa) bad((std::string(n) + " cleans the graph of --gfa: give --gfa too.").c_str());
+  if (o.i("--gfa-tip-reads") < 0 || o.i("--gfa-bubble-bases") < 0 || o.i("--gfa-clean-rounds") < 1)
+    bad("The values of --gfa-tip-reads and --gfa-bubble-bases must be >=0 and that of --gfa-clean-rounds >=1.");
   if (gfa) {   // refused before a handle exists
     if (!o.b("--realign")) bad("--gfa builds the graph from the alignments of --realign: give --realign too.");
     if (!o.s("-q").empty()) bad("--gfa lays out the reads of -s from their overlaps with each other: it takes no -q.");
@@ -657,10 +666,21 @@ int main(int argc, char** argv) {
     std::vector<uint8_t> contained((size_t)std::max<int64_t>(nr, 1));
     chk(E.h, mhap_graph_copy_arcs(RA.graph, rows.data()));
     chk(E.h, mhap_graph_copy_read_flags(RA.graph, contained.data()));
-    int64_t uc[MHAP_UNITIG_COUNTS];
-    const bool unitigs = o.isset("--gfa-unitigs");
+    int64_t uc[MHAP_UNITIG_COUNTS], cc[MHAP_CLEAN_COUNTS];
+    const bool unitigs = o.isset("--gfa-unitigs"), clean = o.b("--gfa-clean");
+    std::vector<uint8_t> removed((size_t)std::max<int64_t>(na, 1), 0);
+    if (clean) {   // tips and bubbles go before either file is written: a dropped read counts as a contained one does, a removed arc is not final
+      mhap_clean_params cp;
+      cp.tip_reads = o.i("--gfa-tip-reads"); cp.bubble_bases = o.i("--gfa-bubble-bases"); cp.max_rounds = o.i("--gfa-clean-rounds");
+      std::vector<uint8_t> dropped((size_t)std::max<int64_t>(nr, 1));
+      chk(E.h, mhap_graph_clean(RA.graph, &cp, cc));
+      chk(E.h, mhap_graph_copy_dropped(RA.graph, dropped.data()));
+      chk(E.h, mhap_graph_copy_removed(RA.graph, removed.data()));
+      for (int64_t r = 0; r < nr; r++) if (dropped[(size_t)r]) contained[(size_t)r] = 1;
+    }
     if (unitigs) {   // the chains of the final arcs and their bases, while the graph is on the device; the second file is all it writes
-      chk(E.h, mhap_graph_unitigs(RA.graph, uc));
+      if (clean) chk(E.h, mhap_graph_unitigs_counts(RA.graph, uc));   // (the clean has built the unitigs of the cleaned graph)
+      else chk(E.h, mhap_graph_unitigs(RA.graph, uc));
       const size_t nu = (size_t)uc[0], nm = (size_t)uc[2], nl = (size_t)uc[4];
       std::vector<int64_t> ustart(nu + 1), ulen(nu + 1), moff(nm + 1);
       std::vector<uint8_t> circ(nu + 1), seq((size_t)uc[6] + 1);
@@ -709,7 +729,7 @@ int main(int argc, char** argv) {
       if (text.size() > (8u << 20)) { fwrite(text.data(), 1, text.size(), f); text.clear(); }
     }
     for (int64_t i = 0; i < na; i++) {
-      if (!rows[(size_t)i * 7 + 6]) continue;
+      if (!rows[(size_t)i * 7 + 6] || removed[(size_t)i]) continue;
       const int len = mhap_format_gfa_link(rows.data() + 7 * i, RA.ids.data(), line, sizeof line);
       if (len < 0 || (size_t)len >= sizeof line) die("mhap_format_gfa_link failed");
       text.append(line, (size_t)len);
@@ -723,6 +743,9 @@ int main(int argc, char** argv) {
                     "%lld contained reads, %lld arcs, %lld reduced, %lld final\n",
             (long long)gc[0], (long long)gc[1], (long long)gc[2], (long long)gc[3], (long long)gc[4], (long long)gc[5], (long long)gc[6],
             (long long)gc[7], (long long)gc[8], (long long)gc[9], (long long)gc[10]);
+    if (clean)
+      fprintf(stderr, "Cleaned in %lld rounds: %lld tips (%lld reads), %lld bubbles (%lld reads), %lld arcs removed\n", (long long)cc[0], (long long)cc[1],
+              (long long)cc[2], (long long)cc[3], (long long)cc[4], (long long)cc[5]);
     if (unitigs)
       fprintf(stderr, "Unitigs: %lld unitigs (%lld circular) of %lld reads, %lld joined arcs, %lld links; longest %lld bases, %lld bases in all\n",
               (long long)uc[0], (long long)uc[1], (long long)uc[2], (long long)uc[3], (long long)uc[4], (long long)uc[5], (long long)uc[6]);

@@ -1,6 +1,7 @@
 """The string graph of a file of MHAP overlaps, on the GPU: `python -m mhap_amd.graph overlaps.txt reads.fasta [--band W]
-[--min-identity X] [--max-hang N] [--int-frac F] [--min-overlap N] [--fuzz N] -o out.gfa [--unitigs utg.gfa]` writes what
-`mhap-hip --realign --gfa out.gfa [--gfa-unitigs utg.gfa]` writes for the same overlaps.
+[--min-identity X] [--max-hang N] [--int-frac F] [--min-overlap N] [--fuzz N] -o out.gfa [--unitigs utg.gfa] [--clean [--tip-reads N]
+[--bubble-bases N] [--clean-rounds N]]` writes what `mhap-hip --realign --gfa out.gfa [--gfa-unitigs utg.gfa] [--gfa-clean ...]`
+writes for the same overlaps.
 
 The overlaps are parsed and realigned as `python -m mhap_amd.realign` does; the records that tool would drop (no alignment, or an
 identity below --min-identity) take no part.  Every other record is classed (internal match, containment, too short, dovetail), reads
@@ -9,7 +10,11 @@ explains are reduced (api.GraphSession; the contract is the "string graph" secti
 per read that is not contained, without its sequence, and an L line per final arc; the ids are numeric, as the records print them.
 With --unitigs the final arcs are compacted into unitigs on the GPU as well and a second GFA 1 file is written: an S line with
 the sequence per unitig, an `a` line per read of it, an L line per arc between unitigs ("unitigs" in the same section).
-Not done: read trimming, chimera detection, tip and bubble removal.  One line on stderr gives the counts (two with --unitigs).
+With --clean the graph is cleaned on the GPU before either file is written: tips of at most --tip-reads reads are clipped and simple
+bubbles whose lesser branch has at most --bubble-bases bases are popped, in at most --clean-rounds rounds ("graph cleaning" in the same
+section); the -o file is then the cleaned read graph and the --unitigs file the cleaned unitig graph.
+Not done: read trimming, chimera detection, consensus, bubbles that are not simple.  One line on stderr gives the counts (one more
+with --clean, one more with --unitigs).
 """
 import argparse
 import sys
@@ -27,19 +32,22 @@ def counts_line(c):
             f"{c['arcs']} arcs, {c['reduced']} reduced, {c['final']} final")
 
 
-def graph_overlaps(recs, fasta, band=0, max_shift=0.2, min_identity=0.0, device=0, batch=BATCH, unitigs=False, **params):
+def graph_overlaps(recs, fasta, band=0, max_shift=0.2, min_identity=0.0, device=0, batch=BATCH, unitigs=False, clean=None, **params):
     """Realign `recs` in batches and build the graph: (gfa text, arcs, counts, contained); with unitigs=True two more: the GFA text
-    of the unitig graph and the dict of GraphSession.unitigs()."""
+    of the unitig graph and the dict of GraphSession.unitigs().  clean: None, or a dict of GraphSession.clean's parameters: the graph
+    is cleaned first, both texts and the dict are those of the cleaned graph, and the dict of CLEAN_COUNTS comes last."""
     with api.MinHashSearch(api.MhapParams(num_hashes=1, ordered_sketch_size=1, max_shift=max_shift, device=device)) as ms:
         with api.GraphSession(fasta.ids, fasta.lengths, handle=ms, **params) as gs:
             for q0 in range(0, len(recs), batch):
                 out, _ = api.realign_records(recs[q0:q0 + batch], fasta, band=band, handle=ms)
                 gs.add(out[kept_rows(out, min_identity)])
             arcs, counts = gs.finish()
+            tail = () if clean is None else (gs.clean(**clean),)
+            text = gs.gfa(cleaned=clean is not None)
             if unitigs:
                 utext = gs.unitig_gfa(fasta)
-                return gs.gfa(), arcs, counts, gs.contained(), utext, gs.unitigs_table
-            return gs.gfa(), arcs, counts, gs.contained()
+                return (text, arcs, counts, gs.contained(), utext, gs.unitigs_table) + tail
+            return (text, arcs, counts, gs.contained()) + tail
 
 
 def main(argv=None):
@@ -56,7 +64,13 @@ def main(argv=None):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("-o", "--output", default=None, help="the GFA file to write (default: stdout)")
     ap.add_argument("--unitigs", default=None, help="also compact the final arcs into unitigs and write their GFA, with sequences, to this file")
+    ap.add_argument("--clean", action="store_true", help="clip tips and pop simple bubbles on the GPU before the files are written")
+    ap.add_argument("--tip-reads", type=int, default=4, help="with --clean, the most reads a tip may have")
+    ap.add_argument("--bubble-bases", type=int, default=50000, help="with --clean, the most bases a popped branch may have")
+    ap.add_argument("--clean-rounds", type=int, default=16, help="with --clean, the most rounds")
     a = ap.parse_args(argv)
+    if a.tip_reads < 0 or a.bubble_bases < 0 or a.clean_rounds < 1:
+        ap.error("--tip-reads and --bubble-bases must be >= 0 and --clean-rounds >= 1")
     if a.band < 0:
         ap.error("--band must be >= 0")
     if a.max_hang < 0 or a.min_overlap < 0 or a.fuzz < 0 or not 0.0 <= a.int_frac <= 1.0:
@@ -64,6 +78,7 @@ def main(argv=None):
     recs = read_overlaps(a.overlaps)
     fasta = api.FastaData.from_file(a.reads)
     res = graph_overlaps(recs, fasta, band=a.band, max_shift=a.max_shift, min_identity=a.min_identity, device=a.device, unitigs=bool(a.unitigs),
+                         clean=dict(tip_reads=a.tip_reads, bubble_bases=a.bubble_bases, max_rounds=a.clean_rounds) if a.clean else None,
                          max_hang=a.max_hang, int_frac_permille=int(round(a.int_frac * 1000)), min_ovlp=a.min_overlap, fuzz=a.fuzz)
     text, counts = res[0], res[2]
     if a.output:
@@ -72,6 +87,8 @@ def main(argv=None):
     else:
         sys.stdout.write(text)
     print(counts_line(counts), file=sys.stderr)
+    if a.clean:
+        print(api.clean_counts_line([res[-1][k] for k in api.CLEAN_COUNTS]), file=sys.stderr)
     if a.unitigs:
         with open(a.unitigs, "w") as fh:
             fh.write(res[4])
