@@ -617,9 +617,9 @@ void mhap_correct_free(mhap_correct_session* s);
  * an odd vertex: snprintf semantics as mhap_format_paf; -1 for a null pointer.
  *
  * ---- unitigs: the final arcs compacted into chains, with their sequences -----------------------------------------------------------
- * Tips and simple bubbles go only when mhap_graph_clean is called ("graph cleaning" below); chimera detection and a consensus over a
- * unitig's reads are not part of this: a unitig is spelled
- * from the reads as stored (the correction stage may be run before).  Integer arithmetic; offsets and lengths in bases are int64.
+ * Tips and simple bubbles go only when mhap_graph_clean is called ("graph cleaning" below); chimera detection is not part of this.  A
+ * unitig is spelled from the reads as stored (the correction stage may be run before); the consensus over a unitig's reads is a
+ * stage of its own behind this one ("unitig consensus" below).  Integer arithmetic; offsets and lengths in bases are int64.
  *
  * Input.  The state of a session after a mhap_graph_finish: the arc list with its `final` flags, the contained flags, the read
  * lengths.  Only final arcs count.  `final` is symmetric (u -> v is final exactly when v ^ 1 -> u ^ 1 is), so in-degree(v) =
@@ -675,7 +675,7 @@ void mhap_correct_free(mhap_correct_session* s);
  * An opt-in stage behind mhap_graph_finish: short dead-end branches (a missed overlap, a read with a bad end) and two-path bubbles (a
  * local disagreement) are removed, so that unitigs run through where they were.  Integer only; it depends on the set of records only.
  * It is defined on the unitig graph of a snapshot: every decision of a round is a function of that round's tables alone, never of
- * another decision of the same round.  Not done: read trimming, chimera detection, consensus, bubbles that are not simple.
+ * another decision of the same round.  Not done: read trimming, chimera detection, bubbles that are not simple.
  *
  * State.  A `dropped` byte per read (0 in play, 1 tip, 2 bubble) and a `removed` byte per arc of the list (1 when the arc is final
  * and either of its reads is dropped); all zero when a cleaning begins.
@@ -753,6 +753,92 @@ int mhap_graph_clean(mhap_graph_session* s, const mhap_clean_params* params /* N
 int mhap_graph_copy_dropped(mhap_graph_session* s, uint8_t* per_read /* n_reads */);
 int mhap_graph_copy_removed(mhap_graph_session* s, uint8_t* per_arc /* n_arcs */);
 int mhap_graph_unitigs_counts(mhap_graph_session* s, int64_t* counts /* MHAP_UNITIG_COUNTS */);
+
+/* ---- unitig consensus: every read placed on a unitig, aligned to the draft, a pile-up vote and a majority call per draft position ---- */
+
+/* A unitig as spelled carries the error rate of one read at every position, and the contained reads, which hold most of the coverage,
+ * contribute nothing.  This stage places every read it can on a served unitig, aligns it to the draft in a band round its place with
+ * the banded aligner above, lets every alignment vote as view A of the correction contract ("read correction"), and calls every draft
+ * position as that contract calls a read position.  One round; no quality values, no chimera detection, no read trimming.
+ *
+ * Draft.  The spelling of the unitigs the graph session serves (of the last mhap_graph_unitigs or mhap_graph_clean), exactly what
+ * mhap_graph_spell writes; unitig k has the length ulen[k].  A unitig of 2^31 bases or more refuses the run and is named.
+ *
+ * Placement.  A placement of read X is (unitig, strand, p): X in orientation `strand` (0 as stored, 1 reverse-complemented) begins at
+ * draft position p, which may be negative or lie beyond the end.
+ *   Members.  Member i of a unitig, vertex v, is placed exactly: on its unitig, strand v & 1, p = offset_i.
+ *   Records.  A record places the non-member read X when its class under the graph session's parameters (the rule of "string graph",
+ *   the same code) is neither NONE nor INTERNAL, exactly one of its two reads is a member of a served unitig — call it M — and X is
+ *   the other.  A member is never placed from a record; contained reads and reads dropped by a cleaning are the non-members that matter.
+ *   Frame.  In the aligner's frame A is forward over [qs, qe) and B has strand to_rc over [ts, te) (qs, qe, ts, te as in "string
+ *   graph").  When M's strand in that frame differs from M's strand in its unitig (v & 1) the frame is reversed: every interval [s, e)
+ *   on a read of length L becomes [L - e, L - s) and both strands flip.  Then M lies over [ms, me) in unitig orientation and X has
+ *   strand sX over [xs, xe).
+ *   Candidate.  p = floor(((offset_M + ms) + (offset_M + me) - (xs + xe)) / 2) in int64, floor toward -infinity, on M's unitig with
+ *   strand sX.
+ *   Choice.  Of the qualifying candidates of X: the greatest xe - xs, then the smallest member vertex, then the smallest (p, sX).  The
+ *   choice depends on the set of records only, not on their order, their split over adds or their repetition.
+ *   A non-member without a qualifying record is unplaced.
+ *   Circular unitigs.  p is reduced modulo ulen into [0, ulen), and the unitig is then the linear sequence it is spelled as: a read
+ *   that runs over the cut votes only where its best local alignment lies.  No alignment wraps round.
+ *
+ * Guard.  The counters are 16 bits wide, as in correction, and exact because each placed read casts one view and a view adds at most
+ * 1 to any counter: for every tile of MHAP_CONSENSUS_TILE draft positions of a unitig (tile j = positions [j T, (j + 1) T)) the
+ * placed reads whose window (below) meets the tile are counted, and a tile above 65 535 refuses the run with MHAP_E_INVALID, the
+ * unitig and the tile in the message, before any vote.  MHAP_CONSENSUS_TILE_CAP=c (1 .. 65 534, tests only, read at each run) lowers
+ * the 65 535.
+ *
+ * Plan and align.  One pair per placed read, over one array holding the reads followed by the drafts: band = the given band when
+ * > 0, else max(1, (int)(length(X) * max_shift)) with the handle's max_shift; w0 = max(0, p - band), w1 = min(ulen, p + length(X) +
+ * band); s1 = draft[w0, w1), s2 = the stored read with b_rc = strand, diag = w0 - p.  The pairs go through
+ * mhap_align_pairs_banded_paths' contract, unchanged.  An empty window (w1 <= w0) counts as no alignment; a pair without an
+ * alignment votes nothing and is counted.
+ *
+ * Vote.  One view per aligned pair: view A of the correction contract with the target the unitig and t = w0 + i — M, Del, Ins columns,
+ * span, ins[KI = 4][4], only A, C, G, T vote.  24 counters (22 and 2 spare) per draft position, 48 bytes, in the planes of the
+ * correction table laid out per unitig; the column walk is the correction kernel's own code.
+ *
+ * Call.  The six steps of the correction call with own = the draft byte and L = ulen, min_cov from the parameters.  On the device the
+ * call runs over tiles of MHAP_CONSENSUS_TILE positions, so a long unitig does not serialise: the junction after t belongs to t's
+ * tile, t < L - 1 is the unitig's rule and not the tile's, and every output byte has one writer.
+ *
+ * Results.  The consensus bytes of all unitigs back to back with out_offsets (n + 1); per unitig six int64 {len_in, len_out, n_sub,
+ * n_del, n_ins, n_low}; the placement table, per read five int64 {unitig or -1, strand, p, how (0 member, 1 record, 2 unplaced),
+ * aligned 0 / 1}; the position map, one int64 per draft position (unitigs back to back): the bytes its unitig's consensus holds before
+ * what this position emits, the exclusive prefix of the emitted lengths; and MHAP_CONSENSUS_COUNTS int64 counts: members, reads placed
+ * by a record, unplaced reads, aligned, without alignment, bases in, bases out, substitutions, deletions, insertions, low positions.
+ *
+ * The session.  mhap_consensus_begin sits on a graph session, which must outlive it, and on that session's handle, whose errors are
+ * the session's (mhap_last_error); it keeps the reads' bytes (read r of the graph's table is bases[offsets[r], offsets[r] +
+ * lengths[r])) and the parameters (NULL: band 0 = automatic, min_cov 4).  mhap_consensus_add takes the records the graph was given,
+ * any number of times, n = 0 included; a record's reads are found and its lengths checked as mhap_graph_add does, a refused call adds
+ * nothing, and the records stay on the device, 32 bytes each.  mhap_consensus_run needs served unitigs (MHAP_E_INVALID otherwise), does
+ * everything above and returns the counts; it may be repeated, and more records may be added after it.  A mhap_graph_finish,
+ * mhap_graph_unitigs or mhap_graph_clean on the graph session after the begin invalidates the consensus session: every call but
+ * mhap_consensus_free then returns MHAP_E_INVALID.  mhap_consensus_info: the sizes the copy calls need (n_unitigs -1 before the first
+ * completed run).  mhap_consensus_copy, _copy_placements and _copy_map write the results of the last run; mhap_consensus_votes (tests)
+ * the 24 counters of every position of one unitig in the order of mhap_correct_votes; mhap_consensus_times the host's wall time of
+ * the last run's four stages in seconds: placement (the tables, the draft and the guard included), alignment, vote, call.  Device memory (consensus_kernels.hip has the
+ * kernels): 8 bytes per read from begin and 32 per record from the first add on; during and after a run 1 byte per base of the reads, 132 per
+ * read, 58 per draft base (the draft, the votes, the map, and one more in the graph session), 32 per tile, the output, 4 per run of
+ * a path and 56 per aligned read, besides what the aligner takes for a call. */
+typedef struct mhap_consensus_params { int32_t band, min_cov; } mhap_consensus_params;
+#define MHAP_CONSENSUS_TILE 4096
+#define MHAP_CONSENSUS_COUNTS 11
+typedef struct mhap_consensus_session mhap_consensus_session;
+void mhap_consensus_default_params(mhap_consensus_params* p);
+int mhap_consensus_begin(mhap_graph_session* g, const uint8_t* bases, int64_t n_bases, const int64_t* offsets /* n_reads */,
+                         const mhap_consensus_params* params /* NULL: the defaults */, mhap_consensus_session** session);
+int mhap_consensus_add(mhap_consensus_session* s, const mhap_record* realigned, int64_t n);
+int mhap_consensus_run(mhap_consensus_session* s, int64_t* counts /* MHAP_CONSENSUS_COUNTS */);
+int mhap_consensus_info(mhap_consensus_session* s, int64_t* n_unitigs, int64_t* n_reads, int64_t* n_draft_bases, int64_t* n_out_bytes);
+int mhap_consensus_copy(mhap_consensus_session* s, uint8_t* bytes /* n_out_bytes */, int64_t* out_offsets /* n_unitigs + 1 */,
+                        int64_t* stats /* n_unitigs x 6 */);
+int mhap_consensus_copy_placements(mhap_consensus_session* s, int64_t* rows /* n_reads x 5 */);
+int mhap_consensus_copy_map(mhap_consensus_session* s, int64_t* map /* n_draft_bases */);
+int mhap_consensus_votes(mhap_consensus_session* s, int64_t unitig, uint16_t* counters /* length x 24 */);
+int mhap_consensus_times(mhap_consensus_session* s, double* seconds /* 4: placement, alignment, vote, call */);
+void mhap_consensus_free(mhap_consensus_session* s);
 
 /* KmerStatSimulator's pair statistics on the GPU (J/main/KmerStatSimulator.java:163-196).  pairs: n rows of 4 int64 {a_off, a_len,
  * b_off, b_len}; a = bases[a_off, a_off + a_len) is the first read, b the second.  skip: n_skip k-mers of k bytes each, back to back, in

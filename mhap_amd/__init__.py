@@ -37,6 +37,9 @@ from .api import (  # noqa: F401
     unitigs,
     format_unitig_gfa,
     format_gfa_unitig_link,
+    ConsensusSession,
+    format_consensus_gfa,
+    consensus_counts_line,
     pair_kmer_stats,
     records_to_lines,
     load_library,

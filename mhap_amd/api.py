@@ -81,6 +81,9 @@ EXPORTED_SYMBOLS = [
     "mhap_graph_spell", "mhap_graph_spell_device", "mhap_format_gfa_unitig_link",
     "mhap_graph_default_clean_params", "mhap_graph_clean", "mhap_graph_copy_dropped", "mhap_graph_copy_removed",
     "mhap_graph_unitigs_counts",
+    "mhap_consensus_default_params", "mhap_consensus_begin", "mhap_consensus_add", "mhap_consensus_run", "mhap_consensus_info",
+    "mhap_consensus_copy", "mhap_consensus_copy_placements", "mhap_consensus_copy_map", "mhap_consensus_votes", "mhap_consensus_times",
+    "mhap_consensus_free",
     "mhap_pair_kmer_stats", "mhap_pair_kmer_stats_paths", "mhap_ksim_create", "mhap_ksim_next", "mhap_ksim_error", "mhap_ksim_destroy",
     "mhap_ksim_dev_create", "mhap_ksim_dev_destroy", "mhap_ksim_dev_pair_stats", "mhap_ksim_dev_trials",
 ]
@@ -196,6 +199,19 @@ def load_library(build_if_missing=True):
     lib.mhap_graph_copy_dropped.argtypes = [C.c_void_p, C.c_void_p]
     lib.mhap_graph_copy_removed.argtypes = [C.c_void_p, C.c_void_p]
     lib.mhap_graph_unitigs_counts.argtypes = [C.c_void_p, C.c_void_p]
+    lib.mhap_consensus_default_params.restype = None
+    lib.mhap_consensus_default_params.argtypes = [C.c_void_p]
+    lib.mhap_consensus_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mhap_consensus_add.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    lib.mhap_consensus_run.argtypes = [C.c_void_p, C.c_void_p]
+    lib.mhap_consensus_info.argtypes = [C.c_void_p] + [C.c_void_p] * 4
+    lib.mhap_consensus_copy.argtypes = [C.c_void_p] + [C.c_void_p] * 3
+    lib.mhap_consensus_copy_placements.argtypes = [C.c_void_p, C.c_void_p]
+    lib.mhap_consensus_copy_map.argtypes = [C.c_void_p, C.c_void_p]
+    lib.mhap_consensus_votes.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+    lib.mhap_consensus_times.argtypes = [C.c_void_p, C.c_void_p]
+    lib.mhap_consensus_free.restype = None
+    lib.mhap_consensus_free.argtypes = [C.c_void_p]
     for name in EXPORTED_SYMBOLS:
         getattr(lib, name)  # AttributeError here = header/library mismatch
     # a stale library next to newer host code (or the reverse) must not get as far as a struct copy
@@ -920,6 +936,154 @@ class GraphSession:
             self._s = C.c_void_p()
             if self._own:
                 self._ms.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+CONSENSUS_COUNTS = ("members", "placed_by_record", "unplaced", "aligned", "no_alignment", "bases_in", "bases_out", "substitutions",
+                    "deletions", "insertions", "low")   # mhap_consensus_run's counts, in order
+CONSENSUS_STATS = ("len_in", "len_out", "n_sub", "n_del", "n_ins", "n_low")
+CONSENSUS_PLACEMENT_FIELDS = ("unitig", "strand", "p", "how", "aligned")   # how: 0 member, 1 record, 2 unplaced
+CONSENSUS_TILE = 4096
+
+
+class _ConsensusParams(C.Structure):
+    _fields_ = [("band", C.c_int32), ("min_cov", C.c_int32)]
+
+
+def consensus_counts_line(counts):
+    """The one stderr line of a unitig consensus (the driver prints the same); counts: the MHAP_CONSENSUS_COUNTS values in order."""
+    c = [int(x) for x in counts]
+    return (f"Consensus: {c[0]} members, {c[1]} reads placed by an overlap, {c[2]} unplaced; {c[3]} aligned, {c[4]} without alignment; "
+            f"{c[5]} bases in, {c[6]} out: {c[7]} substitutions, {c[8]} deletions, {c[9]} insertions, {c[10]} low positions")
+
+
+def format_consensus_gfa(read_ids, unitigs, sequences, position_maps):
+    """The GFA 1 text of the unitig graph with consensus: format_unitig_gfa's, except that the S lines carry the consensus sequence
+    and LN:i: its length, and the offset of every `a` line goes through the unitig's position map (position_maps[k][offset]).
+    sequences: the consensus bytes per unitig; position_maps: one int64 array per unitig, ulen[k] long."""
+    ids = np.asarray(read_ids).tolist()
+    start, circ = unitigs["unitig_start"].tolist(), unitigs["circular"].tolist()
+    vertex, offset, span = unitigs["vertex"].tolist(), unitigs["offset"].tolist(), unitigs["span"].tolist()
+    out = ["H\tVN:Z:1.0\n"]
+    for k, seq in enumerate(sequences):
+        name = f"utg{k + 1:06d}{'c' if circ[k] else 'l'}"
+        out.append(f"S\t{name}\t{seq.decode('latin-1')}\tLN:i:{len(seq)}\tnr:i:{start[k + 1] - start[k]}\n")
+        out += [f"a\t{name}\t{int(position_maps[k][offset[m]])}\t{ids[vertex[m] >> 1]}:1-{span[m]}\t{'-' if vertex[m] & 1 else '+'}\t{span[m]}\n"
+                for m in range(start[k], start[k + 1])]
+    out += [format_gfa_unitig_link(r) + "\n" for r in np.ascontiguousarray(unitigs["links"], dtype=np.int32).reshape(-1, 6)]
+    return "".join(out)
+
+
+class ConsensusSession:
+    """The consensus of the unitigs a GraphSession serves (mhap_consensus_begin / _add / _run / _copy*; the contract is the "unitig
+    consensus" section of include/mhap_hip.h): every read is placed on a unitig — members exactly, the others through their best
+    overlap with a member — aligned to the draft, and every draft position takes the majority of the pile.
+
+        gs.unitigs()                                  # or gs.clean()
+        with ConsensusSession(gs, fasta) as cs:
+            cs.add(records)                           # the records the graph was given; any number of times
+            counts = cs.run()                         # a dict of CONSENSUS_COUNTS
+            seqs = cs.sequences()                     # the consensus bytes per unitig; cs.stats is int64 (n, 6) of CONSENSUS_STATS
+            text = cs.gfa()                           # the unitig GFA with consensus
+
+    A later finish(), unitigs() or clean() of the graph session invalidates this one."""
+
+    def __init__(self, graph_session, fasta, band=0, min_cov=4, query_fasta=None):
+        self._gs = graph_session
+        self._ms = graph_session._ms
+        self._lib = self._ms._lib
+        self._s = C.c_void_p()
+        bases, ids, offsets, lengths = _all_reads(fasta, query_fasta)
+        if len(ids) != len(graph_session.ids):
+            raise MhapError(f"ConsensusSession: {len(ids)} reads for a graph of {len(graph_session.ids)}")
+        self._bases = np.ascontiguousarray(bases, np.uint8)
+        self._offsets = np.ascontiguousarray(offsets, np.int64)
+        p = _ConsensusParams(band, min_cov)
+        self._ms._chk(self._lib.mhap_consensus_begin(graph_session._s, _ptr(self._bases) if len(self._bases) else None, C.c_int64(len(self._bases)),
+                                                     _ptr(self._offsets) if len(self._offsets) else None, C.byref(p), C.byref(self._s)))
+
+    def add(self, records):
+        """The realigned records the graph was given (they stay on the device, 32 bytes each)."""
+        records = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
+        self._ms._chk(self._lib.mhap_consensus_add(self._s, _ptr(records) if len(records) else None, C.c_int64(len(records))))
+
+    def run(self):
+        """Place, align, vote and call: a dict of CONSENSUS_COUNTS.  Afterwards `bytes`, `out_offsets` (n + 1), `stats` (n, 6)."""
+        counts = np.zeros(len(CONSENSUS_COUNTS), np.int64)
+        self._ms._chk(self._lib.mhap_consensus_run(self._s, _ptr(counts)))
+        n, _, _, nout = self.info()
+        self.out_offsets, self.stats, self.bytes = np.zeros(n + 1, np.int64), np.zeros((n, 6), np.int64), np.zeros(nout, np.uint8)
+        self._ms._chk(self._lib.mhap_consensus_copy(self._s, _ptr(self.bytes) if nout else None, _ptr(self.out_offsets), _ptr(self.stats) if n else None))
+        self.counts = dict(zip(CONSENSUS_COUNTS, counts.tolist()))
+        return self.counts
+
+    def info(self):
+        """(unitigs of the last run or -1, reads, draft bases, consensus bytes)."""
+        v = [C.c_int64(0) for _ in range(4)]
+        self._ms._chk(self._lib.mhap_consensus_info(self._s, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def sequences(self):
+        """The consensus of every unitig of the last run, a list of bytes."""
+        n, _, _, nout = self.info()
+        off, raw = np.zeros(n + 1, np.int64), np.zeros(nout, np.uint8)
+        stats = np.zeros((max(n, 0), 6), np.int64)
+        self._ms._chk(self._lib.mhap_consensus_copy(self._s, _ptr(raw) if nout else None, _ptr(off), _ptr(stats) if n > 0 else None))
+        raw = raw.tobytes()
+        return [raw[int(off[k]):int(off[k + 1])] for k in range(n)]
+
+    def placements(self):
+        """The placement table: int64 (reads, 5) of CONSENSUS_PLACEMENT_FIELDS."""
+        out = np.zeros((self.info()[1], 5), np.int64)
+        self._ms._chk(self._lib.mhap_consensus_copy_placements(self._s, _ptr(out) if len(out) else None))
+        return out
+
+    def position_maps(self):
+        """Per unitig an int64 array over its draft positions: the consensus bytes before what the position emits."""
+        n, _, nd, _ = self.info()
+        out = np.zeros(nd, np.int64)
+        self._ms._chk(self._lib.mhap_consensus_copy_map(self._s, _ptr(out) if nd else None))
+        ends = np.cumsum(self.stats[:, 0]).tolist() if n > 0 else []
+        return [out[e - int(ln):e] for e, ln in zip(ends, self.stats[:, 0].tolist())]
+
+    def votes(self, k):
+        """The raw counters of unitig k: a uint16 array (draft length, CORRECT_COUNTERS).  Tests only."""
+        n = self.info()[0]
+        if not 0 <= k < n:
+            raise MhapError(f"ConsensusSession.votes: unitig {k} is not among the {n} unitigs")
+        out = np.zeros((int(self.stats[k, 0]), CORRECT_COUNTERS), np.uint16)
+        self._ms._chk(self._lib.mhap_consensus_votes(self._s, C.c_int64(k), _ptr(out) if len(out) else None))
+        return out
+
+    def times(self):
+        """The host's wall time of the last run's stages in seconds: a dict of placement, alignment, vote, call."""
+        out = np.zeros(4, np.float64)
+        self._ms._chk(self._lib.mhap_consensus_times(self._s, _ptr(out)))
+        return dict(zip(("placement", "alignment", "vote", "call"), out.tolist()))
+
+    def gfa(self):
+        """The GFA 1 text of the unitig graph with consensus, from the unitigs the graph session serves (format_consensus_gfa)."""
+        u = self._gs.unitigs_table
+        if u is None:
+            raise MhapError("ConsensusSession.gfa: the graph session has no unitigs() or clean() since its last finish()")
+        return format_consensus_gfa(self._gs.ids, u, self.sequences(), self.position_maps())
+
+    def close(self):
+        if self._s:
+            if self._gs._s:   # (the graph session's handle may be gone with it)
+                self._lib.mhap_consensus_free(self._s)
+            self._s = C.c_void_p()
 
     def __enter__(self):
         return self

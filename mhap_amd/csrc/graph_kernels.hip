@@ -26,21 +26,18 @@
 #include <vector>
 
 #include "device_common.hpp"
+#include "graph_class.hpp"
 #include "mhap_internal.hpp"
 
 namespace mhap {
 namespace {
 
-enum { G_NONE = 0, G_INTERNAL, G_A_CONTAINED, G_B_CONTAINED, G_SHORT, G_DOVETAIL, G_CLASSES };
 // counts: records, the six classes, contained reads, arcs, reduced, final
 enum { GC_RECORDS = 0, GC_CLASS0 = 1, GC_CONTAINED = 7, GC_ARCS = 8, GC_REDUCED = 9, GC_FINAL = 10 };
 
-// a record as it goes up: the two reads' positions in the table (brc = 2 B + to_rc), the aligned ends, the identity
-struct GItem { int32_t a, brc, a1, a2, b1, b2; double score; };
+// (GItem, the record as it goes up, the class codes and the parameters are graph_class.hpp's)
 struct GArc { int32_t u, v, len, q; };   // two of them over a GItem; u = -1: no arc
-static_assert(sizeof(GItem) == 32 && sizeof(GArc) == 16, "an item is two arcs");
-
-struct GParams { int32_t max_hang, permille, min_ovlp, fuzz; double min_identity; };
+static_assert(sizeof(GArc) == 16, "an item is two arcs");
 
 __global__ __launch_bounds__(256) void classify_kernel(int4* __restrict__ items, int64_t n, int32_t q0, const int32_t* __restrict__ lengths,
                                                        GParams P, uint8_t* __restrict__ cls, uint32_t* __restrict__ contained,
@@ -52,23 +49,14 @@ __global__ __launch_bounds__(256) void classify_kernel(int4* __restrict__ items,
     const int32_t A = w0.x, B = w0.y >> 1, o = w0.y & 1;
     const double score = __hiloint2double(w1.w, w1.z);
     GArc e0{-1, 0, 0, 0}, e1{-1, 0, 0, 0};
-    if (A == B || score == 0.0 || score < P.min_identity) c = G_NONE;
-    else {
-      const int32_t qs = w0.z, qe = w0.w + 1, ql = lengths[A], tl = lengths[B];
-      const int32_t ts = o ? tl - w1.y - 1 : w1.x, te = o ? tl - w1.x : w1.y + 1;
-      const int32_t tl5 = ts, tl3 = tl - te, q3 = ql - qe;
-      const int32_t ext5 = min(qs, tl5), ext3 = min(q3, tl3);
-      const int64_t span = (int64_t)qe - qs, ext = (int64_t)ext5 + ext3;
-      if (ext5 > P.max_hang || ext3 > P.max_hang || span * 1000 < (span + ext) * P.permille) c = G_INTERNAL;
-      else if (qs <= tl5 && q3 <= tl3) { c = G_A_CONTAINED; atomicOr(contained + A, 1u); }
-      else if (qs >= tl5 && q3 >= tl3) { c = G_B_CONTAINED; atomicOr(contained + B, 1u); }
-      else if (span + ext < P.min_ovlp || (int64_t)te - ts + ext < P.min_ovlp) c = G_SHORT;
-      else {
-        c = G_DOVETAIL;
-        const int32_t lab = q0 + (int32_t)q;
-        if (qs > tl5) { e0 = GArc{2 * A, 2 * B + o, qs - tl5, lab}; e1 = GArc{2 * B + (1 - o), 2 * A + 1, tl3 - q3, lab}; }
-        else { e0 = GArc{2 * B + o, 2 * A, tl5 - qs, lab}; e1 = GArc{2 * A + 1, 2 * B + (1 - o), q3 - tl3, lab}; }
-      }
+    GGeom g;
+    c = graph_class(A, B, o, w0.z, w0.w, w1.x, w1.y, score, lengths[A], lengths[B], P, g);
+    if (c == G_A_CONTAINED) atomicOr(contained + A, 1u);
+    else if (c == G_B_CONTAINED) atomicOr(contained + B, 1u);
+    else if (c == G_DOVETAIL) {
+      const int32_t lab = q0 + (int32_t)q;
+      if (g.qs > g.tl5) { e0 = GArc{2 * A, 2 * B + o, g.qs - g.tl5, lab}; e1 = GArc{2 * B + (1 - o), 2 * A + 1, g.tl3 - g.q3, lab}; }
+      else { e0 = GArc{2 * B + o, 2 * A, g.tl5 - g.qs, lab}; e1 = GArc{2 * A + 1, 2 * B + (1 - o), g.q3 - g.tl3, lab}; }
     }
     items[2 * q] = make_int4(e0.u, e0.v, e0.len, e0.q);
     items[2 * q + 1] = make_int4(e1.u, e1.v, e1.len, e1.q);
@@ -694,6 +682,7 @@ struct mhap_graph_session {
   int u_cur = 0;                                          // which of uP / uR / uO the last build's ranks ended in
   // cleaning: the dropped and removed bytes hold from a mhap_graph_clean to the next finish
   bool cleaned = false;
+  uint64_t unitig_gen = 0;                                // bumped whenever the served unitigs go or change: a consensus session's key
   DevBuf dropped, removed, ccounts, o_lo, o_hi, o_cand, verdict;
   void reap(bool all) {
     while (!pending.empty() && (all || hipEventQuery(pending.front().ev) == hipSuccess)) {
@@ -830,6 +819,7 @@ extern "C" int mhap_graph_finish(mhap_graph_session* s, int64_t* counts) {
   (void)hipSetDevice(v.device);
   s->n_arcs = -1;
   s->n_unitigs = -1;
+  s->unitig_gen++;
   s->cleaned = false;   // (a clean starts from zeroed bytes: nothing to zero here)
   const int64_t nv = 2 * s->n_reads;
   hipError_t e = hipSuccess;
@@ -1060,6 +1050,7 @@ int unitigs_back(mhap_graph_session* s, const HandleView& v, const char* who, bo
 // The unitigs the copy and spell calls serve, built anew over what the masks leave; counts: MHAP_UNITIG_COUNTS.
 int build_unitigs(mhap_graph_session* s, const HandleView& v, const char* who, const uint8_t* dropped, const uint8_t* removed, int64_t* counts) {
   s->n_unitigs = -1;
+  s->unitig_gen++;
   const int64_t nv = 2 * s->n_reads, na = s->n_arcs;
   for (int k = 0; k < MHAP_UNITIG_COUNTS; k++) counts[k] = 0;
   for (int k = 0; k < MHAP_UNITIG_COUNTS; k++) s->last_counts[k] = 0;
@@ -1318,6 +1309,15 @@ extern "C" void mhap_graph_free(mhap_graph_session* s) {
   s->reap(true);
   s->release();
   delete s;
+}
+
+// what the unitig consensus (consensus_kernels.hip) reads of a graph session besides its public calls
+mhap::GraphView mhap::graph_view(const mhap_graph_session* s) {
+  return GraphView{s->h, s->P, s->n_reads, s->ids.data(), s->lengths.data(), s->unitig_gen, s->n_unitigs};
+}
+int64_t mhap::graph_find_read(const mhap_graph_session* s, int64_t id) {
+  const auto it = s->by_id.find(id);
+  return it == s->by_id.end() ? -1 : (int64_t)it->second;
 }
 
 extern "C" int mhap_format_gfa_link(const int32_t* row7, const int64_t* read_ids, char* out, size_t cap) {

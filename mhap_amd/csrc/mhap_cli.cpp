@@ -43,7 +43,7 @@ struct Options {
     return t;
   }
   // (the realignment flags are listed only when --realign is given, the correction flags only when --correct is, the graph's only
-  // when --gfa is, the cleaning's only when --gfa-clean is: without them every line the driver writes is what it was before them)
+  // when --gfa is, the cleaning's only when --gfa-clean is, the consensus' only when --gfa-consensus is: without them every line the driver writes is what it was before them)
   std::string dump() const {
     std::string t;
     for (auto& n : order) {
@@ -51,6 +51,7 @@ struct Options {
       if (n.compare(0, 9, "--correct") == 0 && !isset("--correct")) continue;
       if (n.compare(0, 5, "--gfa") == 0 && !isset("--gfa")) continue;
       if ((n == "--gfa-clean" || n == "--gfa-tip-reads" || n == "--gfa-bubble-bases" || n == "--gfa-clean-rounds") && !b("--gfa-clean")) continue;
+      if (n.compare(0, 15, "--gfa-consensus") == 0 && !b("--gfa-consensus")) continue;
       t += n + " = " + m.at(n).value + "\n";
     }
     return t;
@@ -173,6 +174,8 @@ struct Realign {
   double correct_seconds = 0.0;
   mhap_graph_session* graph = nullptr;                // --gfa: every kept record is classed for the string graph
   double graph_seconds = 0.0;
+  bool keep_records = false;                          // --gfa-consensus: the kept records wait here until the graph is finished
+  std::vector<mhap_record> kept_records;
   void add(const mhap_fasta& fa) {
     for (int64_t i = 0; i < fa.n; i++) { ids.push_back(fa.ids[i]); offsets.push_back((int64_t)bases.size() + fa.offsets[i]); lengths.push_back(fa.lengths[i]); }
     bases.insert(bases.end(), (const uint8_t*)fa.bases, (const uint8_t*)fa.bases + fa.total_bases);
@@ -235,6 +238,7 @@ int sink_cb(const mhap_record* r, int64_t n, void* user) {
       rc = mhap_graph_add(R.graph, R.out.data(), k);
       if (rc != MHAP_OK) { fprintf(stderr, "Exception in mhap-hip: %s (code %d)\n", mhap_last_error(R.h), rc); return 1; }
       R.graph_seconds += now() - tg;
+      if (R.keep_records) R.kept_records.insert(R.kept_records.end(), R.out.begin(), R.out.begin() + k);
     }
     r = R.out.data(); n = k;
   }
@@ -421,6 +425,9 @@ int main(int argc, char** argv) {
   o.add("--gfa-tip-reads", "[int] With --gfa-clean, the most reads a tip may have.", "4");
   o.add("--gfa-bubble-bases", "[int] With --gfa-clean, the most bases a popped bubble branch may have.", "50000");
   o.add("--gfa-clean-rounds", "[int] With --gfa-clean, the most rounds of cleaning.", "16");
+  o.add("--gfa-consensus", "With --gfa-unitigs: place every read on a unitig, align it to the unitig and let the reads vote on the GPU; the --gfa-unitigs file then carries the consensus sequences, their lengths, and a-line offsets mapped into them.", "false", true);
+  o.add("--gfa-consensus-fasta", "With --gfa-consensus, also write the consensus sequences to this FASTA file.", "");
+  o.add("--gfa-consensus-min-cov", "[int] With --gfa-consensus, the depth below which a position keeps the unitig's own base.", "4");
   if (!o.parse(argc, argv)) return 0;
 
   auto bad = [&](const char* m) { printf("%s\n", m); exit(1); };
@@ -480,6 +487,12 @@ int main(int argc, char** argv) {
     if (o.isset(n) && !gfa) bad((std::string(n) + " cleans the graph of --gfa: give --gfa too.").c_str());
   if (o.i("--gfa-tip-reads") < 0 || o.i("--gfa-bubble-bases") < 0 || o.i("--gfa-clean-rounds") < 1)
     bad("The values of --gfa-tip-reads and --gfa-bubble-bases must be >=0 and that of --gfa-clean-rounds >=1.");
+  for (const char* n : {"--gfa-consensus", "--gfa-consensus-fasta", "--gfa-consensus-min-cov"})   // refused before a handle exists
+    if (o.isset(n) && !o.isset("--gfa-unitigs")) bad((std::string(n) + " works on the unitigs of --gfa-unitigs: give --gfa-unitigs too.").c_str());
+  for (const char* n : {"--gfa-consensus-fasta", "--gfa-consensus-min-cov"})
+    if (o.isset(n) && !o.b("--gfa-consensus")) bad((std::string(n) + " belongs to --gfa-consensus: give --gfa-consensus too.").c_str());
+  if (o.isset("--gfa-consensus-fasta") && o.s("--gfa-consensus-fasta").empty()) bad("--gfa-consensus-fasta needs the name of the FASTA file to write.");
+  if (o.i("--gfa-consensus-min-cov") < 1) bad("The value of --gfa-consensus-min-cov must be >=1.");
   if (gfa) {   // refused before a handle exists
     if (!o.b("--realign")) bad("--gfa builds the graph from the alignments of --realign: give --realign too.");
     if (!o.s("-q").empty()) bad("--gfa lays out the reads of -s from their overlaps with each other: it takes no -q.");
@@ -573,6 +586,7 @@ int main(int argc, char** argv) {
       mhap_graph_default_params(&gp);
       gp.max_hang = o.i("--gfa-max-hang"); gp.min_ovlp = o.i("--gfa-min-overlap"); gp.fuzz = o.i("--gfa-fuzz");
       chk(E.h, mhap_graph_begin(E.h, RA.ids.data(), RA.lengths.data(), (int64_t)RA.ids.size(), &gp, &RA.graph));
+      RA.keep_records = o.b("--gfa-consensus");
     }
   }
   const double t_score = now();
@@ -666,8 +680,8 @@ int main(int argc, char** argv) {
     std::vector<uint8_t> contained((size_t)std::max<int64_t>(nr, 1));
     chk(E.h, mhap_graph_copy_arcs(RA.graph, rows.data()));
     chk(E.h, mhap_graph_copy_read_flags(RA.graph, contained.data()));
-    int64_t uc[MHAP_UNITIG_COUNTS], cc[MHAP_CLEAN_COUNTS];
-    const bool unitigs = o.isset("--gfa-unitigs"), clean = o.b("--gfa-clean");
+    int64_t uc[MHAP_UNITIG_COUNTS], cc[MHAP_CLEAN_COUNTS], kc[MHAP_CONSENSUS_COUNTS];
+    const bool unitigs = o.isset("--gfa-unitigs"), clean = o.b("--gfa-clean"), consensus = o.b("--gfa-consensus");
     std::vector<uint8_t> removed((size_t)std::max<int64_t>(na, 1), 0);
     if (clean) {   // tips and bubbles go before either file is written: a dropped read counts as a contained one does, a removed arc is not final
       mhap_clean_params cp;
@@ -688,23 +702,45 @@ int main(int argc, char** argv) {
       chk(E.h, mhap_graph_copy_unitigs(RA.graph, ustart.data(), ulen.data(), circ.data()));
       chk(E.h, mhap_graph_copy_layout(RA.graph, mv.data(), moff.data(), msp.data()));
       chk(E.h, mhap_graph_copy_links(RA.graph, links.data()));
-      chk(E.h, mhap_graph_spell(RA.graph, RA.bases.data(), (int64_t)RA.bases.size(), RA.offsets.data(), seq.data()));
+      std::vector<int64_t> cons_off(nu + 1, 0), cons_map;   // --gfa-consensus: unitig k's bytes in seq, the position map of all unitigs
+      if (!consensus) chk(E.h, mhap_graph_spell(RA.graph, RA.bases.data(), (int64_t)RA.bases.size(), RA.offsets.data(), seq.data()));
+      else {   // the kept records, fed now that the unitigs are served; the consensus takes the place of the spelling
+        mhap_consensus_params kp;
+        mhap_consensus_default_params(&kp);
+        kp.min_cov = o.i("--gfa-consensus-min-cov");
+        mhap_consensus_session* cs = nullptr;
+        chk(E.h, mhap_consensus_begin(RA.graph, (const uint8_t*)RA.bases.data(), (int64_t)RA.bases.size(), RA.offsets.data(), &kp, &cs));
+        chk(E.h, mhap_consensus_add(cs, RA.kept_records.data(), (int64_t)RA.kept_records.size()));
+        chk(E.h, mhap_consensus_run(cs, kc));
+        int64_t n_draft = 0, n_out = 0;
+        chk(E.h, mhap_consensus_info(cs, nullptr, nullptr, &n_draft, &n_out));
+        std::vector<int64_t> stats(6 * nu + 6);
+        seq.assign((size_t)n_out + 1, 0);
+        cons_map.assign((size_t)n_draft + 1, 0);
+        chk(E.h, mhap_consensus_copy(cs, seq.data(), cons_off.data(), stats.data()));
+        chk(E.h, mhap_consensus_copy_map(cs, cons_map.data()));
+        mhap_consensus_free(cs);
+        std::vector<mhap_record>().swap(RA.kept_records);
+      }
       FILE* f = fopen(o.s("--gfa-unitigs").c_str(), "wb");
       if (!f) die("cannot write " + o.s("--gfa-unitigs"));
       std::string text = "H\tVN:Z:1.0\n";
       char name[32], line[128];
-      size_t at = 0;
+      size_t at = 0, draft_at = 0;   // unitig k's sequence in seq, its first position in the map
       for (size_t k = 0; k < nu; k++) {
         snprintf(name, sizeof name, "utg%06lld%c", (long long)k + 1, circ[k] ? 'c' : 'l');
+        const size_t slen = consensus ? (size_t)(cons_off[k + 1] - cons_off[k]) : (size_t)ulen[k];
         text += std::string("S\t") + name + "\t";
-        text.append((const char*)seq.data() + at, (size_t)ulen[k]);
-        at += (size_t)ulen[k];
-        text += "\tLN:i:" + std::to_string(ulen[k]) + "\tnr:i:" + std::to_string(ustart[k + 1] - ustart[k]) + "\n";
+        text.append((const char*)seq.data() + at, slen);
+        at += slen;
+        text += "\tLN:i:" + std::to_string(slen) + "\tnr:i:" + std::to_string(ustart[k + 1] - ustart[k]) + "\n";
         for (int64_t m = ustart[k]; m < ustart[k + 1]; m++) {
           const std::string sp = std::to_string(msp[(size_t)m]);
-          text += std::string("a\t") + name + "\t" + std::to_string(moff[(size_t)m]) + "\t" + std::to_string(RA.ids[(size_t)(mv[(size_t)m] >> 1)]) + ":1-" + sp +
+          const int64_t off = consensus ? cons_map[draft_at + (size_t)moff[(size_t)m]] : moff[(size_t)m];
+          text += std::string("a\t") + name + "\t" + std::to_string(off) + "\t" + std::to_string(RA.ids[(size_t)(mv[(size_t)m] >> 1)]) + ":1-" + sp +
                   "\t" + ((mv[(size_t)m] & 1) ? "-" : "+") + "\t" + sp + "\n";
         }
+        draft_at += (size_t)ulen[k];
         if (text.size() > (8u << 20)) { fwrite(text.data(), 1, text.size(), f); text.clear(); }
       }
       for (size_t i = 0; i < nl; i++) {
@@ -716,6 +752,16 @@ int main(int argc, char** argv) {
       }
       fwrite(text.data(), 1, text.size(), f);
       if (fclose(f) != 0) die("cannot write " + o.s("--gfa-unitigs"));
+      if (consensus && o.isset("--gfa-consensus-fasta")) {
+        FILE* ff = fopen(o.s("--gfa-consensus-fasta").c_str(), "wb");
+        if (!ff) die("cannot write " + o.s("--gfa-consensus-fasta"));
+        for (size_t k = 0; k < nu; k++) {
+          fprintf(ff, ">utg%06lld%c\n", (long long)k + 1, circ[k] ? 'c' : 'l');
+          fwrite(seq.data() + cons_off[k], 1, (size_t)(cons_off[k + 1] - cons_off[k]), ff);
+          fputc('\n', ff);
+        }
+        if (fclose(ff) != 0) die("cannot write " + o.s("--gfa-consensus-fasta"));
+      }
     }
     mhap_graph_free(RA.graph);
     RA.graph = nullptr;
@@ -749,6 +795,11 @@ int main(int argc, char** argv) {
     if (unitigs)
       fprintf(stderr, "Unitigs: %lld unitigs (%lld circular) of %lld reads, %lld joined arcs, %lld links; longest %lld bases, %lld bases in all\n",
               (long long)uc[0], (long long)uc[1], (long long)uc[2], (long long)uc[3], (long long)uc[4], (long long)uc[5], (long long)uc[6]);
+    if (consensus)
+      fprintf(stderr, "Consensus: %lld members, %lld reads placed by an overlap, %lld unplaced; %lld aligned, %lld without alignment; %lld bases in, "
+                      "%lld out: %lld substitutions, %lld deletions, %lld insertions, %lld low positions\n",
+              (long long)kc[0], (long long)kc[1], (long long)kc[2], (long long)kc[3], (long long)kc[4], (long long)kc[5], (long long)kc[6],
+              (long long)kc[7], (long long)kc[8], (long long)kc[9], (long long)kc[10]);
     fprintf(stderr, "Time (s) to class, build and reduce the graph: %g\n", RA.graph_seconds);
   }
   fprintf(stderr, "Total time (s): %g\n", now() - t_total);

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/mhap_hip.h"
+#include "graph_class.hpp"
 
 // The paths of one call (mhap_align_pairs_banded_paths, mhap_realign_records_paths; realign_kernels.hip): pair q's runs are
 // ops[offsets[q], offsets[q + 1]).  The correction stage (correct_kernels.hip) reads them.
@@ -99,6 +100,13 @@ inline int hip_fail(const HandleView& v, const char* who, const std::string& wha
   return MHAP_E_HIP;
 }
 void mhap_dist_release(void* dist_state);
+// A graph session as the unitig consensus sees it: the handle, the parameters of the class rule, the table of reads (host) and the
+// generation of the served unitigs, which every mhap_graph_finish, _unitigs and _clean bumps (n_unitigs < 0: none are served).
+struct GraphView {
+  mhap_handle* h; GParams P; int64_t n_reads; const int64_t* ids; const int32_t* lengths; uint64_t unitig_gen; int64_t n_unitigs;
+};
+GraphView graph_view(const mhap_graph_session* s);
+int64_t graph_find_read(const mhap_graph_session* s, int64_t id);   // the read's position in read_ids (the first of an id), or -1
 // Eager exchange (mhap_dist.hip; mhap_dist_set_eager): an add on a rank of a multi-GPU job gathers its forward rows while the add is
 // still computing — the ordered rows (6/7 of the bytes) as soon as the ordered-sketch kernel has written them, under the MinHash
 // kernel; the MinHash rows, meta and ids right behind the MinHash kernel, under the index build — so that the collective search

@@ -1,0 +1,156 @@
+// vote_common.hpp — what the pile-up votes of read correction (correct_kernels.hip) and of the unitig consensus (consensus_kernels.hip)
+// share: a view's item, the walk over the columns of its path, which casts the votes, and the decision of the call for one position.
+// The contract is the "read correction" section of include/mhap_hip.h; correct_kernels.hip describes the table's planes and the walk.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "device_common.hpp"
+
+namespace mhap {
+
+constexpr uint32_t OP_I = 1, OP_D = 2, OP_EQ = 7, OP_X = 8;   // BAM's codes (realign_kernels.hip)
+constexpr uint32_t RUN_MAX = (1u << 28) - 1;   // the longest run of a path: a longer one is split into several of its code
+constexpr int CK_WORDS = 12;         // words per position: 24 counters of 16 bits
+constexpr int CK_KI = 4;              // inserted bytes voted on per junction
+constexpr uint32_t CK_CAP = 65535;    // accepted views per target
+constexpr int CK_T = 256;             // threads of the call kernel
+
+// one accepted view of one record
+struct VoteItem {
+  int64_t a_off, b_off;     // first stored byte of read A, of read B
+  int64_t v_words;          // first word of the target's planes
+  int64_t ops_off;          // the record's runs in the uploaded ops
+  int32_t alen, blen;
+  int32_t i0, j0;           // first row of s1, first column of s2 (in the aligner's orientation)
+  int32_t n_ops;
+  int32_t view;             // 0: target A; 1: target B
+  int32_t rc;               // s2 is the reverse complement of read B
+  int32_t pad;
+};
+
+__device__ inline int base_code(uint32_t c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1; }
+
+__device__ inline void vote(uint32_t* __restrict__ table, int64_t v_words, int tlen, int t, int counter) {
+  if ((unsigned)t >= (unsigned)tlen) return;   // (add validated the path: never taken)
+  atomicAdd(table + v_words + (int64_t)(counter >> 1) * tlen + t, (counter & 1) ? 0x10000u : 1u);
+}
+
+// The column walk of one view: every column of the path `it` names casts its vote.  One wave; the caller is a kernel of 64 threads.
+__device__ inline void vote_walk(const uint8_t* __restrict__ bases, const VoteItem& it, const uint32_t* __restrict__ ops,
+                                 uint32_t* __restrict__ table) {
+  __shared__ int s_col[65], s_i[64], s_j[64];
+  __shared__ uint32_t s_op[64];
+  const int lane = threadIdx.x;
+  const uint32_t* runs = ops + it.ops_off;
+  const bool target_b = it.view != 0, rev = target_b && it.rc != 0;
+  const int tlen = target_b ? it.blen : it.alen;
+  int ci = it.i0, cj = it.j0;   // (i, j) of the first column of the chunk's first run
+  for (int r0 = 0; r0 < it.n_ops; r0 += 64) {
+    const int idx = r0 + lane;
+    const uint32_t op = idx < it.n_ops ? runs[idx] : 0u;
+    const int len = (int)(op >> 4);
+    const uint32_t code = op & 15u;
+    const int di = (code == OP_EQ || code == OP_X || code == OP_I) ? len : 0;
+    const int dj = (code == OP_EQ || code == OP_X || code == OP_D) ? len : 0;
+    int si = di, sj = dj, sc = len;   // inclusive scans over the lanes
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int ui = __shfl_up(si, d), uj = __shfl_up(sj, d), uc = __shfl_up(sc, d);
+      if (lane >= d) { si += ui; sj += uj; sc += uc; }
+    }
+    __syncthreads();   // the previous chunk's columns are done with the arrays
+    s_op[lane] = op; s_i[lane] = ci + si - di; s_j[lane] = cj + sj - dj; s_col[lane] = sc - len;
+    if (lane == 63) s_col[64] = sc;
+    __syncthreads();
+    ci += __shfl(si, 63); cj += __shfl(sj, 63);
+    const int total = s_col[64];
+    for (int x = lane; x < total; x += 64) {
+      int lo = 0, hi = 63;   // the last run of the chunk that starts at or before column x (runs of length 0 are padding at the end)
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (s_col[mid] <= x) lo = mid; else hi = mid - 1;
+      }
+      // (several runs cannot start at one column except the padding, which starts at `total` > x)
+      const uint32_t rop = s_op[lo];
+      const int rlen = (int)(rop >> 4), c = x - s_col[lo], ridx = r0 + lo;
+      const uint32_t rcode = rop & 15u;
+      const bool diag = rcode == OP_EQ || rcode == OP_X;
+      const int i = s_i[lo] + ((diag || rcode == OP_I) ? c : 0), j = s_j[lo] + ((diag || rcode == OP_D) ? c : 0);
+      const bool consumes_target = diag || rcode == (target_b ? OP_D : OP_I);
+      if (consumes_target) {
+        const int t = !target_b ? i : rev ? it.blen - 1 - j : j;
+        if (diag) {
+          uint32_t e = target_b ? (uint32_t)bases[it.a_off + i]
+                                : (it.rc ? rc_char(bases[it.b_off + (it.blen - 1 - j)]) : (uint32_t)bases[it.b_off + j]);
+          if (rev) e = rc_char(e);
+          const int b = base_code(e);
+          if (b >= 0) vote(table, it.v_words, tlen, t, b);
+        } else {
+          vote(table, it.v_words, tlen, t, 4);
+        }
+        // the view continues past t unless this is its last column: the path's last, or its first in the reversed view
+        const bool view_end = rev ? (ridx == 0 && c == 0) : (ridx == it.n_ops - 1 && c == rlen - 1);
+        if (!view_end) vote(table, it.v_words, tlen, t, 5);
+      } else {
+        // an Ins column: the group is this run (a run split at 2^28 - 1 columns continues a group whose first four slots are taken)
+        const int k = rev ? rlen - 1 - c : c;
+        if (k < CK_KI) {
+          const int nb = rev ? ridx + 1 : ridx - 1;
+          const bool split = nb >= 0 && nb < it.n_ops && (runs[nb] & 15u) == rcode;
+          if (!split) {
+            // the target position before the group in the view's order: the row / column consumed last, or next in the reversed view
+            const int t = !target_b ? s_i[lo] - 1 : rev ? it.blen - 1 - s_j[lo] : s_j[lo] - 1;
+            uint32_t e = target_b ? (uint32_t)bases[it.a_off + i]
+                                  : (it.rc ? rc_char(bases[it.b_off + (it.blen - 1 - j)]) : (uint32_t)bases[it.b_off + j]);
+            if (rev) e = rc_char(e);
+            const int b = base_code(e);
+            if (b >= 0) vote(table, it.v_words, tlen, t, 6 + 4 * k + b);
+          }
+        }
+      }
+    }
+  }
+}
+
+// the decision for one position: the bytes it emits (at most 1 + CK_KI) and what it counts
+struct Decision { int n; uint8_t bytes[1 + CK_KI]; int sub, del, ins, low; };
+
+__device__ inline Decision decide(const uint32_t* __restrict__ w, int64_t len, int64_t t, uint32_t own, int min_cov) {
+  Decision D{0, {0, 0, 0, 0, 0}, 0, 0, 0, 0};
+  const uint32_t w0 = w[t], w1 = w[len + t], w2 = w[2 * len + t];
+  int base[4] = {(int)(w0 & 0xFFFFu), (int)(w0 >> 16), (int)(w1 & 0xFFFFu), (int)(w1 >> 16)};
+  const int del = (int)(w2 & 0xFFFFu), span = (int)(w2 >> 16);
+  const int d = base[0] + base[1] + base[2] + base[3] + del;
+  if (d < min_cov) {
+    D.bytes[D.n++] = (uint8_t)own; D.low = 1;
+  } else {
+    const int ob = base_code(own);
+    if (ob >= 0) base[ob] += 1;
+    const int total = d + 1;
+    if (2 * del > total) D.del = 1;
+    else {
+      int best = 0;
+      for (int b = 1; b < 4; b++) if (base[b] > base[best]) best = b;
+      uint32_t out;
+      if (base[best] == 0 || (ob >= 0 && base[ob] == base[best])) out = own;
+      else out = (0x54474341u >> (8 * best)) & 0xFFu;   // "ACGT"
+      D.bytes[D.n++] = (uint8_t)out;
+      D.sub = out != own;
+    }
+  }
+  if (t < len - 1 && span >= min_cov) {
+    for (int k = 0; k < CK_KI; k++) {
+      const uint32_t x0 = w[(3 + 2 * k) * len + t], x1 = w[(4 + 2 * k) * len + t];
+      const int v[4] = {(int)(x0 & 0xFFFFu), (int)(x0 >> 16), (int)(x1 & 0xFFFFu), (int)(x1 >> 16)};
+      int best = 0;
+      for (int b = 1; b < 4; b++) if (v[b] > v[best]) best = b;
+      if (2 * v[best] <= span + 1) break;
+      D.bytes[D.n++] = (uint8_t)((0x54474341u >> (8 * best)) & 0xFFu);
+      D.ins += 1;
+    }
+  }
+  return D;
+}
+
+}  // namespace mhap

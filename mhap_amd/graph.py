@@ -1,7 +1,7 @@
 """The string graph of a file of MHAP overlaps, on the GPU: `python -m mhap_amd.graph overlaps.txt reads.fasta [--band W]
 [--min-identity X] [--max-hang N] [--int-frac F] [--min-overlap N] [--fuzz N] -o out.gfa [--unitigs utg.gfa] [--clean [--tip-reads N]
-[--bubble-bases N] [--clean-rounds N]]` writes what `mhap-hip --realign --gfa out.gfa [--gfa-unitigs utg.gfa] [--gfa-clean ...]`
-writes for the same overlaps.
+[--bubble-bases N] [--clean-rounds N]] [--consensus [--consensus-fasta F] [--consensus-min-cov N]]` writes what `mhap-hip --realign
+--gfa out.gfa [--gfa-unitigs utg.gfa] [--gfa-clean ...]` writes for the same overlaps.
 
 The overlaps are parsed and realigned as `python -m mhap_amd.realign` does; the records that tool would drop (no alignment, or an
 identity below --min-identity) take no part.  Every other record is classed (internal match, containment, too short, dovetail), reads
@@ -13,8 +13,11 @@ the sequence per unitig, an `a` line per read of it, an L line per arc between u
 With --clean the graph is cleaned on the GPU before either file is written: tips of at most --tip-reads reads are clipped and simple
 bubbles whose lesser branch has at most --bubble-bases bases are popped, in at most --clean-rounds rounds ("graph cleaning" in the same
 section); the -o file is then the cleaned read graph and the --unitigs file the cleaned unitig graph.
-Not done: read trimming, chimera detection, consensus, bubbles that are not simple.  One line on stderr gives the counts (one more
-with --clean, one more with --unitigs).
+With --consensus (which needs --unitigs) every read is placed on a unitig, aligned to it and votes, and the --unitigs file carries the
+consensus sequences, their lengths and `a` offsets mapped into them ("unitig consensus" in the same header); --consensus-fasta also
+writes them as FASTA.
+Not done: read trimming, chimera detection, bubbles that are not simple.  One line on stderr gives the counts (one more
+with --clean, one more with --unitigs, one more with --consensus).
 """
 import argparse
 import sys
@@ -32,18 +35,42 @@ def counts_line(c):
             f"{c['arcs']} arcs, {c['reduced']} reduced, {c['final']} final")
 
 
-def graph_overlaps(recs, fasta, band=0, max_shift=0.2, min_identity=0.0, device=0, batch=BATCH, unitigs=False, clean=None, **params):
+def consensus_fasta(seqs, circular):
+    """The FASTA text of consensus sequences: `>utg%06d{l|c}` as the GFA names them, one line per sequence."""
+    return "".join(f">utg{k + 1:06d}{'c' if circular[k] else 'l'}\n{s.decode('latin-1')}\n" for k, s in enumerate(seqs))
+
+
+def graph_overlaps(recs, fasta, band=0, max_shift=0.2, min_identity=0.0, device=0, batch=BATCH, unitigs=False, clean=None, consensus=None,
+                   **params):
     """Realign `recs` in batches and build the graph: (gfa text, arcs, counts, contained); with unitigs=True two more: the GFA text
     of the unitig graph and the dict of GraphSession.unitigs().  clean: None, or a dict of GraphSession.clean's parameters: the graph
-    is cleaned first, both texts and the dict are those of the cleaned graph, and the dict of CLEAN_COUNTS comes last."""
+    is cleaned first, both texts and the dict are those of the cleaned graph, and the dict of CLEAN_COUNTS comes last.
+    consensus: None, or a dict of ConsensusSession's parameters (min_cov, band), with unitigs=True: the unitig text carries the consensus,
+    and the result is a dict instead: gfa, arcs, counts, contained, unitig_gfa, unitigs, clean_counts (or None), consensus_counts,
+    consensus_seqs."""
     with api.MinHashSearch(api.MhapParams(num_hashes=1, ordered_sketch_size=1, max_shift=max_shift, device=device)) as ms:
         with api.GraphSession(fasta.ids, fasta.lengths, handle=ms, **params) as gs:
+            kept = []
             for q0 in range(0, len(recs), batch):
                 out, _ = api.realign_records(recs[q0:q0 + batch], fasta, band=band, handle=ms)
-                gs.add(out[kept_rows(out, min_identity)])
+                out = out[kept_rows(out, min_identity)]
+                gs.add(out)
+                if consensus is not None:
+                    kept.append(out)       # held until the graph is finished, then fed to the consensus
             arcs, counts = gs.finish()
             tail = () if clean is None else (gs.clean(**clean),)
             text = gs.gfa(cleaned=clean is not None)
+            if consensus is not None:
+                if not unitigs:
+                    raise api.MhapError("graph_overlaps: consensus needs unitigs=True")
+                if clean is None:
+                    gs.unitigs()
+                with api.ConsensusSession(gs, fasta, **consensus) as cs:
+                    for out in kept:
+                        cs.add(out)
+                    ccounts = cs.run()
+                    return dict(gfa=text, arcs=arcs, counts=counts, contained=gs.contained(), unitig_gfa=cs.gfa(), unitigs=gs.unitigs_table,
+                                clean_counts=tail[0] if tail else None, consensus_counts=ccounts, consensus_seqs=cs.sequences())
             if unitigs:
                 utext = gs.unitig_gfa(fasta)
                 return (text, arcs, counts, gs.contained(), utext, gs.unitigs_table) + tail
@@ -68,7 +95,16 @@ def main(argv=None):
     ap.add_argument("--tip-reads", type=int, default=4, help="with --clean, the most reads a tip may have")
     ap.add_argument("--bubble-bases", type=int, default=50000, help="with --clean, the most bases a popped branch may have")
     ap.add_argument("--clean-rounds", type=int, default=16, help="with --clean, the most rounds")
+    ap.add_argument("--consensus", action="store_true", help="with --unitigs, write the consensus of every unitig's reads instead of its raw spelling")
+    ap.add_argument("--consensus-fasta", default=None, help="with --consensus, also write the consensus sequences to this FASTA file")
+    ap.add_argument("--consensus-min-cov", type=int, default=4, help="with --consensus, the depth below which a position keeps the draft's base")
     a = ap.parse_args(argv)
+    if a.consensus and not a.unitigs:
+        ap.error("--consensus needs --unitigs")
+    if (a.consensus_fasta or a.consensus_min_cov != 4) and not a.consensus:
+        ap.error("--consensus-fasta and --consensus-min-cov need --consensus")
+    if a.consensus_min_cov < 1:
+        ap.error("--consensus-min-cov must be >= 1")
     if a.tip_reads < 0 or a.bubble_bases < 0 or a.clean_rounds < 1:
         ap.error("--tip-reads and --bubble-bases must be >= 0 and --clean-rounds >= 1")
     if a.band < 0:
@@ -79,7 +115,11 @@ def main(argv=None):
     fasta = api.FastaData.from_file(a.reads)
     res = graph_overlaps(recs, fasta, band=a.band, max_shift=a.max_shift, min_identity=a.min_identity, device=a.device, unitigs=bool(a.unitigs),
                          clean=dict(tip_reads=a.tip_reads, bubble_bases=a.bubble_bases, max_rounds=a.clean_rounds) if a.clean else None,
+                         consensus=dict(min_cov=a.consensus_min_cov) if a.consensus else None,
                          max_hang=a.max_hang, int_frac_permille=int(round(a.int_frac * 1000)), min_ovlp=a.min_overlap, fuzz=a.fuzz)
+    if a.consensus:
+        res = (res["gfa"], res["arcs"], res["counts"], res["contained"], res["unitig_gfa"], res["unitigs"], res["consensus_counts"],
+               res["consensus_seqs"]) + ((res["clean_counts"],) if a.clean else ())
     text, counts = res[0], res[2]
     if a.output:
         with open(a.output, "w") as fh:
@@ -93,6 +133,11 @@ def main(argv=None):
         with open(a.unitigs, "w") as fh:
             fh.write(res[4])
         print(api.unitig_counts_line([res[5]["counts"][k] for k in api.UNITIG_COUNTS]), file=sys.stderr)
+    if a.consensus:
+        print(api.consensus_counts_line([res[6][k] for k in api.CONSENSUS_COUNTS]), file=sys.stderr)
+        if a.consensus_fasta:
+            with open(a.consensus_fasta, "w") as fh:
+                fh.write(consensus_fasta(res[7], res[5]["circular"].tolist()))
     return 0
 
 
