@@ -559,7 +559,7 @@ void mhap_correct_free(mhap_correct_session* s);
 
 /* The layout step that follows an overlapper (Myers 2005): every realigned overlap is classed, contained reads are set aside, the
  * dovetails become the arcs of a bidirected graph and the arcs that a two-arc path explains are removed.  Tips and simple bubbles are
- * removed on request ("graph cleaning" below).  Left out: read trimming, chimera detection.  Everything is integer arithmetic (sums and products of lengths in
+ * removed on request ("graph cleaning" below).  Reads are trimmed and chimeras split in a stage of their own in front of this one ("read trimming" below), whose reads and records this one takes unchanged.  Everything is integer arithmetic (sums and products of lengths in
  * int64); the only floating comparison is score < min_identity on the record's double.
  *
  * Input.  A table of reads (read_ids[r], lengths[r]; no bases), realigned records (out[q] of mhap_realign_records) and the parameters
@@ -839,6 +839,102 @@ int mhap_consensus_copy_map(mhap_consensus_session* s, int64_t* map /* n_draft_b
 int mhap_consensus_votes(mhap_consensus_session* s, int64_t unitig, uint16_t* counters /* length x 24 */);
 int mhap_consensus_times(mhap_consensus_session* s, double* seconds /* 4: placement, alignment, vote, call */);
 void mhap_consensus_free(mhap_consensus_session* s);
+
+/* ---- read trimming: every read cut to the stretch that other reads support, chimeras split, records rewritten onto the cut reads ---- */
+
+/* The step in front of the string graph (the coverage rule of miniasm's first pass): a chimeric read joins two loci and a read with
+ * an unsupported end keeps hangs that cost it its dovetails; neither the class rule nor the cleaning removes what follows.  Here
+ * every aligned interval is shrunk by end_clip at both ends and piled up per read, and a read keeps the longest stretch that
+ * min_cov of them cover, widened again by end_clip.  At a chimeric junction the overlaps of both sides end, so after the shrink
+ * nothing covers it and the read falls into two stretches, of which the longer survives.  One round; left out: a second round on
+ * the trimmed records, selection of best overlaps, any repeat-aware rule (a repeat's false overlaps count as coverage).
+ * Everything is integer arithmetic in int64; the only floating comparison is score < min_identity on the record's double.  The
+ * result is a function of the multiset of records: invariant under any permutation of the records and any split of them over
+ * calls.  Nothing is de-duplicated: a record given twice counts twice, as in the correction stage.
+ *
+ * Input.  A table of reads (read_ids[r], lengths[r]; no bases), realigned records as for mhap_graph_add, and the parameters
+ * min_cov (3), end_clip (500), min_span (2000), min_identity (0.0); the defaults are choices, not measurements.  min_cov >= 1,
+ * end_clip >= 0 and min_span >= 0, else MHAP_E_INVALID.
+ *
+ * Eligible record.  from_id != to_id, score != 0 and not score < min_identity.
+ *
+ * Contributions.  An eligible record gives read A (`from`) the interval [a1 + end_clip, a2 + 1 - end_clip) when a2 + 1 - a1 >= min_span
+ * and the interval is not empty, and read B (`to`) the interval [b1 + end_clip, b2 + 1 - end_clip) under the same two conditions on
+ * b: b1, b2 are in B's own forward coordinates already (the class rule's ts / te show it), so to_rc plays no part.  The two sides
+ * are judged independently.
+ *
+ * Coverage.  cov_r[p] = the number of contributed intervals of read r that contain p.   Runs.  A run is a maximal stretch of
+ * positions with cov >= min_cov.
+ *
+ * Clear range.  Of the longest runs [s, e) the one that begins first; the clear range is [s - end_clip, e + end_clip), which lies in
+ * [0, length] by construction.  A read without a run is deleted and has the clear range (0, 0).
+ *
+ * Per-read result.  Four int32 {begin, end, runs, covered} — covered: the positions with cov >= min_cov — and one flag byte: bit 0
+ * MHAP_TRIM_DELETED, bit 1 MHAP_TRIM_CUT5 (begin > 0), bit 2 MHAP_TRIM_CUT3 (end < length), bit 3 MHAP_TRIM_GAPPED (runs > 1: a
+ * chimera or a gap in coverage, which overlaps cannot tell apart; the read is unusable across either).  A deleted read has no
+ * other bit.  MHAP_TRIM_COUNTS int64 counts: reads, deleted, cut5, cut3, gapped, bases in, bases kept, eligible records.
+ *
+ * A record rewritten onto the trimmed reads (trim_common.hpp: one function for host and device).  Frame as in the class rule: qs = a1,
+ * qe = a2 + 1; (ts, te) = (b1, b2 + 1) when !to_rc, else (blen - b2 - 1, blen - b1).  A's clear range is (ca, ea); B's in the frame is
+ * (cb, eb) = clear[B] when !to_rc, else (blen - end_B, blen - begin_B).  SQ = qe - qs, ST = te - ts; div is the floor:
+ *   d5q = max(0, ca - qs)   d5t = max(0, cb - ts)   d3q = max(0, qe - ea)   d3t = max(0, te - eb)
+ *   s5q = max(d5q, d5t * SQ div ST)    s5t = max(d5t, d5q * ST div SQ)
+ *   s3q = max(d3q, d3t * SQ div ST)    s3t = max(d3t, d3q * ST div SQ)
+ *   qs' = qs + s5q   qe' = qe - s3q   ts' = ts + s5t   te' = te - s3t
+ * The record is kept iff it is eligible, neither read is deleted (an explicit clear range with end <= begin is a deleted read), SQ > 0,
+ * ST > 0, qe' > qs' and te' > ts'; every other record is void.  A kept record comes out with a1 = qs' - ca, a2 = qe' - 1 - ca,
+ * alen = ea - ca and, with u = ts' - cb, v = te' - cb, blen = eb - cb: (b1, b2) = (u, v - 1) when !to_rc, else (blen - v, blen - u - 1);
+ * ids, score, raw and to_rc unchanged.  A record between two untouched reads therefore comes out byte for byte as it went in.
+ *
+ * The session.  mhap_trim_begin takes the table of reads (params NULL: the defaults); the handle must outlive the session, whose
+ * errors are the handle's (mhap_last_error).  mhap_trim_add piles the records up on the device (trim_kernels.hip: one lane per
+ * record, up to four atomic adds of +1 / -1 into a per-base difference array), any number of times, n = 0 included, and does not
+ * wait for the device; ids and alen / blen are checked as mhap_graph_add checks them, and a record with score != 0 must have
+ * 0 <= a1 <= a2 < alen and 0 <= b1 <= b2 < blen: MHAP_E_INVALID naming the record, and a refused call adds nothing.
+ * mhap_trim_finish makes the rows and flags (one workgroup per read over tiles of MHAP_TRIM_TILE positions) and returns the counts;
+ * it may be repeated, and more records may be added after it.  mhap_trim_copy writes the rows and flags of the last finish.
+ * mhap_trim_coverage (tests): cov of every position of read read_index as the adds so far have left it.  mhap_trim_apply, after a
+ * finish: out[q] = in[q] rewritten and keep[q] = 1 for a kept record, out[q] = in[q] and keep[q] = 0 for a void one; records are
+ * checked as in the add; the caller compacts.  mhap_trim_clip_record uses no GPU and takes explicit clear ranges {begin, end} of the
+ * two reads: 1 kept (out rewritten), 0 void (out = in), -1 for a null pointer or bad parameters.  Device memory from begin to free:
+ * 4 bytes per base and 48 per read (each read's slots rounded up to four), 32 per record of the largest add, 64 of the largest apply.
+ *
+ * Refinement, in front of the add.  The realignment's local alignment (+2 / -2, gaps 2 + 1 per base) keeps gaining score between
+ * unrelated sequences, so the overlap of a chimeric read comes back running through the junction and the coverage rule would see no
+ * gap there.  Before a record is piled up, its path ("the realignment stage's paths") is therefore scored again, +1 per '=' column
+ * and -penalty per X, I or D column, and the record is cut to the best stretch: the runs are walked in order with a running sum
+ * that starts again from 0 at an '=' run when it is <= 0, and the best stretch is the one behind the first strictly greatest sum
+ * seen at the end of an '=' run; it begins and ends with '=' columns.  penalty 2 (the tools' default) breaks even at an identity of
+ * 2 / 3: two reads with up to 15 % error each agree in 0.85^2 = 0.72 of their columns or more and gain, an alignment through unrelated
+ * sequence agrees in little over half and loses.  The refined record has the stretch's a1, a2, b1, b2 (b flipped back when to_rc) and
+ * score = 1 - errors / columns of the stretch; everything else is unchanged, and a record whose path has no '=' column comes back as
+ * it is.  mhap_trim_refine does it on the device, one lane per record (paths: those of the n records, as mhap_realign_records_paths
+ * or mhap_align_paths_from_runs gives them; MHAP_E_INVALID for another number of records, for runs outside the object or penalty < 1);
+ * mhap_trim_refine_record is the same rule on the host for one record and its runs: 1 refined, 0 unchanged, -1 for a bad argument. */
+typedef struct mhap_trim_params {
+  int32_t min_cov, end_clip, min_span;
+  double min_identity;
+} mhap_trim_params;
+#define MHAP_TRIM_COUNTS 8
+#define MHAP_TRIM_TILE 4096
+#define MHAP_TRIM_DELETED 1
+#define MHAP_TRIM_CUT5 2
+#define MHAP_TRIM_CUT3 4
+#define MHAP_TRIM_GAPPED 8
+typedef struct mhap_trim_session mhap_trim_session;
+void mhap_trim_default_params(mhap_trim_params* p);
+int mhap_trim_begin(mhap_handle* h, const int64_t* read_ids, const int32_t* lengths, int64_t n_reads, const mhap_trim_params* params,
+                    mhap_trim_session** session);
+int mhap_trim_add(mhap_trim_session* s, const mhap_record* realigned, int64_t n);
+int mhap_trim_finish(mhap_trim_session* s, int64_t* counts /* MHAP_TRIM_COUNTS */);
+int mhap_trim_copy(mhap_trim_session* s, int32_t* rows /* n_reads x 4 */, uint8_t* flags /* n_reads */);
+int mhap_trim_coverage(mhap_trim_session* s, int64_t read_index, int32_t* cov /* length */);
+int mhap_trim_apply(mhap_trim_session* s, const mhap_record* in, int64_t n, mhap_record* out, uint8_t* keep /* n */);
+int mhap_trim_clip_record(const mhap_record* in, const int32_t* clearA /* 2 */, const int32_t* clearB /* 2 */, const mhap_trim_params* params,
+                          mhap_record* out);
+int mhap_trim_refine(mhap_handle* h, const mhap_record* realigned, int64_t n, const mhap_align_paths* paths, int32_t penalty, mhap_record* out);
+int mhap_trim_refine_record(const mhap_record* in, const uint32_t* ops, int64_t n_ops, int32_t penalty, mhap_record* out);
+void mhap_trim_free(mhap_trim_session* s);
 
 /* KmerStatSimulator's pair statistics on the GPU (J/main/KmerStatSimulator.java:163-196).  pairs: n rows of 4 int64 {a_off, a_len,
  * b_off, b_len}; a = bases[a_off, a_off + a_len) is the first read, b the second.  skip: n_skip k-mers of k bytes each, back to back, in

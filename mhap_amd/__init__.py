@@ -40,6 +40,11 @@ from .api import (  # noqa: F401
     ConsensusSession,
     format_consensus_gfa,
     consensus_counts_line,
+    TrimSession,
+    trim_counts_line,
+    trim_clip_record,
+    trim_refine,
+    trim_refine_record,
     pair_kmer_stats,
     records_to_lines,
     load_library,

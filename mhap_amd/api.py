@@ -84,6 +84,8 @@ EXPORTED_SYMBOLS = [
     "mhap_consensus_default_params", "mhap_consensus_begin", "mhap_consensus_add", "mhap_consensus_run", "mhap_consensus_info",
     "mhap_consensus_copy", "mhap_consensus_copy_placements", "mhap_consensus_copy_map", "mhap_consensus_votes", "mhap_consensus_times",
     "mhap_consensus_free",
+    "mhap_trim_default_params", "mhap_trim_begin", "mhap_trim_add", "mhap_trim_finish", "mhap_trim_copy", "mhap_trim_coverage",
+    "mhap_trim_apply", "mhap_trim_clip_record", "mhap_trim_free", "mhap_trim_refine", "mhap_trim_refine_record",
     "mhap_pair_kmer_stats", "mhap_pair_kmer_stats_paths", "mhap_ksim_create", "mhap_ksim_next", "mhap_ksim_error", "mhap_ksim_destroy",
     "mhap_ksim_dev_create", "mhap_ksim_dev_destroy", "mhap_ksim_dev_pair_stats", "mhap_ksim_dev_trials",
 ]
@@ -933,6 +935,176 @@ class GraphSession:
     def close(self):
         if self._s:
             self._lib.mhap_graph_free(self._s)
+            self._s = C.c_void_p()
+            if self._own:
+                self._ms.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+TRIM_COUNTS = ("reads", "deleted", "cut5", "cut3", "gapped", "bases_in", "bases_kept", "eligible_records")   # mhap_trim_finish's counts
+TRIM_ROW_FIELDS = ("begin", "end", "runs", "covered")
+TRIM_DELETED, TRIM_CUT5, TRIM_CUT3, TRIM_GAPPED = 1, 2, 4, 8   # the bits of a read's flag byte
+TRIM_TILE = 4096   # MHAP_TRIM_TILE: the positions the run kernel takes at a time
+
+
+class _TrimParams(C.Structure):
+    _fields_ = [("min_cov", C.c_int32), ("end_clip", C.c_int32), ("min_span", C.c_int32), ("min_identity", C.c_double)]
+
+
+def trim_counts_line(counts):
+    """The one stderr line of a trimming (the driver prints the same); counts: the MHAP_TRIM_COUNTS values in order."""
+    c = [int(x) for x in counts]
+    return (f"Trim: {c[0]} reads, {c[1]} deleted, {c[2]} cut at 5', {c[3]} cut at 3', {c[4]} gapped; {c[6]} of {c[5]} bases kept, "
+            f"{c[7]} eligible overlaps")
+
+
+def trim_clip_record(record, clear_a, clear_b, min_cov=3, end_clip=500, min_span=2000, min_identity=0.0):
+    """One record rewritten onto explicit clear ranges (mhap_trim_clip_record, no GPU): (kept, record)."""
+    lib = load_library()
+    rec = np.ascontiguousarray(record, dtype=RECORD_DTYPE).reshape(1)
+    out = np.zeros(1, RECORD_DTYPE)
+    ca, cb = np.ascontiguousarray(clear_a, np.int32).reshape(2), np.ascontiguousarray(clear_b, np.int32).reshape(2)
+    p = _TrimParams(min_cov, end_clip, min_span, min_identity)
+    rc = lib.mhap_trim_clip_record(_ptr(rec), _ptr(ca), _ptr(cb), C.byref(p), _ptr(out))
+    if rc < 0:
+        raise MhapError("mhap_trim_clip_record: bad parameters")
+    return bool(rc), out[0]
+
+
+TRIM_PENALTY = 2   # the refinement's cost of an error column next to +1 for a match: break-even at an identity of 2 / 3
+
+
+def trim_refine_record(record, ops, penalty=TRIM_PENALTY):
+    """One record cut to the best stretch of its path (mhap_trim_refine_record, no GPU): (refined, record)."""
+    lib = load_library()
+    rec = np.ascontiguousarray(record, dtype=RECORD_DTYPE).reshape(1)
+    ops = np.ascontiguousarray(ops, dtype=np.uint32)
+    out = np.zeros(1, RECORD_DTYPE)
+    rc = lib.mhap_trim_refine_record(_ptr(rec), _ptr(ops) if len(ops) else None, C.c_int64(len(ops)), C.c_int32(penalty), _ptr(out))
+    if rc < 0:
+        raise MhapError("mhap_trim_refine_record: bad argument")
+    return bool(rc), out[0]
+
+
+def trim_refine(records, op_offsets, ops, penalty=TRIM_PENALTY, handle=None, device=0):
+    """Realigned records cut to the best stretch of their paths on the GPU (mhap_trim_refine; "read trimming" in include/mhap_hip.h):
+    records, op_offsets and ops as realign_records_paths returns them.  The refined records."""
+    records = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
+    op_offsets = np.ascontiguousarray(op_offsets, dtype=np.int64)
+    ops = np.ascontiguousarray(ops, dtype=np.uint32)
+    if len(op_offsets) != len(records) + 1:
+        raise MhapError(f"trim_refine: {len(records)} records need {len(records) + 1} run offsets, not {len(op_offsets)}")
+    ms = handle or MinHashSearch(MhapParams(num_hashes=1, ordered_sketch_size=1, device=device))
+    try:
+        obj = C.c_void_p()
+        if ms._lib.mhap_align_paths_from_runs(_ptr(op_offsets), C.c_int64(len(records)), _ptr(ops) if len(ops) else None, C.byref(obj)) != 0:
+            raise MhapError("trim_refine: op_offsets is not a list of run offsets over ops")
+        out = np.zeros(len(records), RECORD_DTYPE)
+        try:
+            ms._chk(ms._lib.mhap_trim_refine(ms._h, _ptr(records) if len(records) else None, C.c_int64(len(records)), obj, C.c_int32(penalty),
+                                             _ptr(out) if len(out) else None))
+        finally:
+            ms._lib.mhap_align_paths_free(obj)
+        return out
+    finally:
+        if handle is None:
+            ms.close()
+
+
+class TrimSession:
+    """Reads cut to the stretch that other reads support (mhap_trim_begin / _add / _finish / _copy / _apply; the contract is the
+    "read trimming" section of include/mhap_hip.h).
+
+        with TrimSession(fasta.ids, fasta.lengths) as ts:
+            ts.add(records)                       # what realign_records returned; any number of times
+            counts = ts.finish()                  # a dict of TRIM_COUNTS
+            rows, flags = ts.table()              # int32 (n, 4) of TRIM_ROW_FIELDS, uint8 (n) of the TRIM_* bits
+            out, keep = ts.apply(records)         # the records on the trimmed reads; out[keep != 0] are the ones that stay
+            cut = ts.trimmed(fasta)               # the surviving reads as a FastaData over the same bases
+
+    handle: a MinHashSearch whose device and stream to use (else one is made and closed with the session)."""
+
+    def __init__(self, read_ids, lengths, min_cov=3, end_clip=500, min_span=2000, min_identity=0.0, handle=None, device=0):
+        self._own = handle is None
+        self._ms = MinHashSearch(MhapParams(num_hashes=1, ordered_sketch_size=1, device=device)) if self._own else handle
+        self._lib = self._ms._lib
+        self._s = C.c_void_p()
+        self.ids = np.ascontiguousarray(read_ids, np.int64)
+        self.lengths = np.ascontiguousarray(lengths, np.int32)
+        self.rows = self.flags = None
+        try:
+            if len(self.ids) != len(self.lengths):
+                raise MhapError(f"TrimSession: {len(self.ids)} ids and {len(self.lengths)} lengths")
+            p = _TrimParams(min_cov, end_clip, min_span, min_identity)
+            self._ms._chk(self._lib.mhap_trim_begin(self._ms._h, _ptr(self.ids) if len(self.ids) else None,
+                                                    _ptr(self.lengths) if len(self.ids) else None, C.c_int64(len(self.ids)), C.byref(p),
+                                                    C.byref(self._s)))
+        except Exception:
+            if self._own:
+                self._ms.close()
+            raise
+
+    def add(self, records):
+        """Pile realigned records up (nothing waits for the device)."""
+        records = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
+        self._ms._chk(self._lib.mhap_trim_add(self._s, _ptr(records) if len(records) else None, C.c_int64(len(records))))
+
+    def finish(self):
+        """Make every read's row and flags; returns a dict of TRIM_COUNTS."""
+        counts = np.zeros(len(TRIM_COUNTS), np.int64)
+        self.rows = self.flags = None
+        self._ms._chk(self._lib.mhap_trim_finish(self._s, _ptr(counts)))
+        self.counts = dict(zip(TRIM_COUNTS, counts.tolist()))
+        return self.counts
+
+    def table(self):
+        """(rows, flags) of the last finish: int32 (n, 4) of TRIM_ROW_FIELDS and one byte of TRIM_* bits per read."""
+        if self.rows is None:
+            rows, flags = np.zeros((len(self.ids), 4), np.int32), np.zeros(len(self.ids), np.uint8)
+            self._ms._chk(self._lib.mhap_trim_copy(self._s, _ptr(rows) if len(rows) else None, _ptr(flags) if len(flags) else None))
+            self.rows, self.flags = rows, flags
+        return self.rows, self.flags
+
+    def coverage(self, read_index):
+        """cov of every position of one read as the adds so far have left it (int32)."""
+        if not 0 <= read_index < len(self.ids):
+            raise MhapError("TrimSession.coverage: no such read")
+        out = np.zeros(int(self.lengths[read_index]), np.int32)
+        self._ms._chk(self._lib.mhap_trim_coverage(self._s, C.c_int64(read_index), _ptr(out) if len(out) else None))
+        return out
+
+    def apply(self, records):
+        """(out, keep): the records rewritten onto the trimmed reads of the last finish and one byte per record, 0 for a void one
+        (which comes back as it went in); out[keep != 0] is the compacted list."""
+        records = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
+        out, keep = np.zeros(len(records), RECORD_DTYPE), np.zeros(len(records), np.uint8)
+        opt = lambda a: _ptr(a) if len(a) else None
+        self._ms._chk(self._lib.mhap_trim_apply(self._s, opt(records), C.c_int64(len(records)), opt(out), opt(keep)))
+        return out, keep
+
+    def trimmed(self, fasta):
+        """The surviving reads of the last finish as a FastaData: ids, trimmed lengths, and offsets shifted by `begin` into the same
+        `bases` (nothing is copied).  `fasta` holds the session's reads in read_ids order."""
+        if len(fasta) != len(self.ids):
+            raise MhapError(f"TrimSession.trimmed: {len(fasta)} reads for a session of {len(self.ids)}")
+        rows, flags = self.table()
+        live = np.flatnonzero((flags & TRIM_DELETED) == 0)
+        return FastaData(fasta.bases, fasta.offsets[live] + rows[live, 0], rows[live, 1] - rows[live, 0], self.ids[live])
+
+    def close(self):
+        if self._s:
+            self._lib.mhap_trim_free(self._s)
             self._s = C.c_void_p()
             if self._own:
                 self._ms.close()

@@ -43,7 +43,7 @@ struct Options {
     return t;
   }
   // (the realignment flags are listed only when --realign is given, the correction flags only when --correct is, the graph's only
-  // when --gfa is, the cleaning's only when --gfa-clean is, the consensus' only when --gfa-consensus is: without them every line the driver writes is what it was before them)
+  // when --gfa is, the cleaning's only when --gfa-clean is, the consensus' only when --gfa-consensus is, the trimming's only when --trim is: without them every line the driver writes is what it was before them)
   std::string dump() const {
     std::string t;
     for (auto& n : order) {
@@ -52,6 +52,7 @@ struct Options {
       if (n.compare(0, 5, "--gfa") == 0 && !isset("--gfa")) continue;
       if ((n == "--gfa-clean" || n == "--gfa-tip-reads" || n == "--gfa-bubble-bases" || n == "--gfa-clean-rounds") && !b("--gfa-clean")) continue;
       if (n.compare(0, 15, "--gfa-consensus") == 0 && !b("--gfa-consensus")) continue;
+      if (n.compare(0, 6, "--trim") == 0 && !b("--trim")) continue;
       t += n + " = " + m.at(n).value + "\n";
     }
     return t;
@@ -176,6 +177,10 @@ struct Realign {
   double graph_seconds = 0.0;
   bool keep_records = false;                          // --gfa-consensus: the kept records wait here until the graph is finished
   std::vector<mhap_record> kept_records;
+  mhap_trim_session* trim = nullptr;                  // --trim: every kept record's intervals are piled up on its two reads
+  int32_t trim_penalty = 0;                           // > 0: each record is first cut to the best stretch of its path
+  std::vector<mhap_record> refined;
+  double trim_seconds = 0.0;
   void add(const mhap_fasta& fa) {
     for (int64_t i = 0; i < fa.n; i++) { ids.push_back(fa.ids[i]); offsets.push_back((int64_t)bases.size() + fa.offsets[i]); lengths.push_back(fa.lengths[i]); }
     bases.insert(bases.end(), (const uint8_t*)fa.bases, (const uint8_t*)fa.bases + fa.total_bases);
@@ -190,7 +195,7 @@ int sink_cb(const mhap_record* r, int64_t n, void* user) {
     const double t = now();
     R.out.resize((size_t)n);
     int rc;
-    if (R.paf || R.correct) {
+    if (R.paf || R.correct || (R.trim && R.trim_penalty > 0)) {
       R.detail.resize((size_t)n * 3);
       mhap_align_paths* paths = nullptr;
       rc = mhap_realign_records_paths(R.h, R.bases.data(), (int64_t)R.bases.size(), R.ids.data(), R.offsets.data(), R.lengths.data(),
@@ -218,7 +223,8 @@ int sink_cb(const mhap_record* r, int64_t n, void* user) {
     }
     R.dropped += n - k; R.kept += k;
     R.seconds += now() - t;
-    if (R.correct) {   // the kept records and their runs into the vote table; the dropped ones cast no vote
+    const bool refine = R.trim && R.trim_penalty > 0;
+    if (R.correct || refine) {   // the kept records and their runs: into the vote table, and cut to their best stretch for the trimming
       const double tc = now();
       R.vote_offsets.assign(1, 0); R.vote_ops.clear();
       for (int64_t i = 0; i < k; i++) {
@@ -228,18 +234,31 @@ int sink_cb(const mhap_record* r, int64_t n, void* user) {
       }
       mhap_align_paths* kept_paths = nullptr;
       rc = mhap_align_paths_from_runs(R.vote_offsets.data(), k, R.vote_ops.data(), &kept_paths);
-      if (rc == MHAP_OK) rc = mhap_correct_add(R.correct, R.out.data(), k, kept_paths);
+      if (rc == MHAP_OK && R.correct) rc = mhap_correct_add(R.correct, R.out.data(), k, kept_paths);   // (the dropped ones cast no vote)
+      if (R.correct) R.correct_seconds += now() - tc;
+      if (rc == MHAP_OK && refine) {
+        const double tt = now();
+        R.refined.resize((size_t)std::max<int64_t>(k, 1));
+        rc = mhap_trim_refine(R.h, R.out.data(), k, kept_paths, R.trim_penalty, R.refined.data());
+        R.trim_seconds += now() - tt;
+      }
       mhap_align_paths_free(kept_paths);
       if (rc != MHAP_OK) { fprintf(stderr, "Exception in mhap-hip: %s (code %d)\n", mhap_last_error(R.h), rc); return 1; }
-      R.correct_seconds += now() - tc;
+    }
+    const mhap_record* for_trim = refine ? R.refined.data() : R.out.data();
+    if (R.trim) {   // the kept records onto the coverage of their reads (queued: nothing waits)
+      const double tt = now();
+      rc = mhap_trim_add(R.trim, for_trim, k);
+      if (rc != MHAP_OK) { fprintf(stderr, "Exception in mhap-hip: %s (code %d)\n", mhap_last_error(R.h), rc); return 1; }
+      R.trim_seconds += now() - tt;
     }
     if (R.graph) {   // the kept records into the string graph (queued: nothing waits)
       const double tg = now();
       rc = mhap_graph_add(R.graph, R.out.data(), k);
       if (rc != MHAP_OK) { fprintf(stderr, "Exception in mhap-hip: %s (code %d)\n", mhap_last_error(R.h), rc); return 1; }
       R.graph_seconds += now() - tg;
-      if (R.keep_records) R.kept_records.insert(R.kept_records.end(), R.out.begin(), R.out.begin() + k);
     }
+    if (R.keep_records) R.kept_records.insert(R.kept_records.end(), for_trim, for_trim + k);   // (with --trim the graph takes what the trimming took)
     r = R.out.data(); n = k;
   }
   if (s->realign && s->realign->paf) {   // one PAF line per kept record; the names are columns 1 and 2 of the 12-column line
@@ -428,6 +447,13 @@ int main(int argc, char** argv) {
   o.add("--gfa-consensus", "With --gfa-unitigs: place every read on a unitig, align it to the unitig and let the reads vote on the GPU; the --gfa-unitigs file then carries the consensus sequences, their lengths, and a-line offsets mapped into them.", "false", true);
   o.add("--gfa-consensus-fasta", "With --gfa-consensus, also write the consensus sequences to this FASTA file.", "");
   o.add("--gfa-consensus-min-cov", "[int] With --gfa-consensus, the depth below which a position keeps the unitig's own base.", "4");
+  o.add("--trim", "With --realign: trim every read of -s on the GPU to the longest stretch that enough realigned overlaps cover, which also splits chimeric reads at their junction. The overlaps printed stay the untrimmed ones; with --gfa the graph, its unitigs and their consensus are built on the trimmed reads and the overlaps rewritten onto them. Self overlaps only (no -q), one GPU.", "false", true);
+  o.add("--trim-min-cov", "[int] With --trim, the shrunk overlaps a position needs to be kept.", "3");
+  o.add("--trim-end-clip", "[int] With --trim, the bases every aligned interval is shrunk by at both ends.", "500");
+  o.add("--trim-min-span", "[int] With --trim, the shortest aligned interval that counts.", "2000");
+  o.add("--trim-penalty", "[int] With --trim, every overlap is first cut to the best stretch of its alignment under +1 per match and this cost per error column, so that an overlap the aligner ran through a chimeric junction ends there. 0) overlaps as realigned.", "2");
+  o.add("--trim-fasta", "With --trim, write the trimmed reads to this FASTA file; deleted reads are left out.", "");
+  o.add("--trim-table", "With --trim, write one line per read to this file: id length begin end runs covered flags.", "");
   if (!o.parse(argc, argv)) return 0;
 
   auto bad = [&](const char* m) { printf("%s\n", m); exit(1); };
@@ -501,6 +527,19 @@ int main(int argc, char** argv) {
     if (o.s("--gfa").empty()) bad("--gfa needs the name of the GFA file to write.");
     if (o.i("--gfa-max-hang") < 0 || o.i("--gfa-min-overlap") < 0 || o.i("--gfa-fuzz") < 0) bad("The values of --gfa-max-hang, --gfa-min-overlap and --gfa-fuzz must be >=0.");
   }
+  const bool trim = o.b("--trim");
+  for (const char* n : {"--trim-min-cov", "--trim-end-clip", "--trim-min-span", "--trim-penalty", "--trim-fasta", "--trim-table"})   // refused before a handle exists
+    if (o.isset(n) && !trim) bad((std::string(n) + " belongs to --trim: give --trim too.").c_str());
+  if (trim) {   // refused before a handle exists
+    if (!o.b("--realign")) bad("--trim piles up the alignments of --realign: give --realign too.");
+    if (!o.s("-q").empty()) bad("--trim trims the reads of -s from their overlaps with each other: it takes no -q.");
+    if (ends_with(o.s("-s"), ".dat")) bad("--trim needs the overlaps realigned on the reads' bases: give FASTA files, not .dat sketches.");
+    if (devs.size() > 1) bad("--trim runs on one GPU: give one device (--gpus 1).");
+    if (o.i("--trim-min-cov") < 1 || o.i("--trim-end-clip") < 0 || o.i("--trim-min-span") < 0 || o.i("--trim-penalty") < 0)
+      bad("The value of --trim-min-cov must be >=1 and those of --trim-end-clip, --trim-min-span and --trim-penalty >=0.");
+    for (const char* n : {"--trim-fasta", "--trim-table"})
+      if (o.isset(n) && o.s(n).empty()) bad((std::string(n) + " needs the name of the file to write.").c_str());
+  }
   if (realign) {   // refused before a handle exists
     if (o.i("--realign-band") < 0) bad("The realignment band must be >=0.");
     if (devs.size() > 1) bad("--realign runs on one GPU: give one device (--gpus 1).");
@@ -570,6 +609,9 @@ int main(int argc, char** argv) {
 
   Sink sink{stdout};
   Realign RA;
+  mhap_graph_params gp;
+  mhap_graph_default_params(&gp);
+  gp.max_hang = o.i("--gfa-max-hang"); gp.min_ovlp = o.i("--gfa-min-overlap"); gp.fuzz = o.i("--gfa-fuzz");
   if (realign) {
     RA.h = E.h; RA.band = o.i("--realign-band"); RA.min_identity = o.d("--realign-min-identity"); RA.paf = o.b("--realign-paf");
     for (const std::string& sf : list_files(o.s("-s"))) {   // (ids as the index assigned them: FastaData's running count)
@@ -581,10 +623,15 @@ int main(int argc, char** argv) {
     sink.realign = &RA;
     if (correct) chk(E.h, mhap_correct_begin(E.h, RA.bases.data(), (int64_t)RA.bases.size(), RA.ids.data(), RA.offsets.data(), RA.lengths.data(),
                                              (int64_t)RA.ids.size(), &RA.correct));
-    if (gfa) {
-      mhap_graph_params gp;
-      mhap_graph_default_params(&gp);
-      gp.max_hang = o.i("--gfa-max-hang"); gp.min_ovlp = o.i("--gfa-min-overlap"); gp.fuzz = o.i("--gfa-fuzz");
+    mhap_trim_params tp;
+    mhap_trim_default_params(&tp);
+    if (trim) {
+      tp.min_cov = o.i("--trim-min-cov"); tp.end_clip = o.i("--trim-end-clip"); tp.min_span = o.i("--trim-min-span");
+      chk(E.h, mhap_trim_begin(E.h, RA.ids.data(), RA.lengths.data(), (int64_t)RA.ids.size(), &tp, &RA.trim));
+      RA.trim_penalty = o.i("--trim-penalty");
+    }
+    if (gfa && trim) RA.keep_records = true;   // the graph begins after the trimming, on the trimmed reads: the records wait for it
+    else if (gfa) {
       chk(E.h, mhap_graph_begin(E.h, RA.ids.data(), RA.lengths.data(), (int64_t)RA.ids.size(), &gp, &RA.graph));
       RA.keep_records = o.b("--gfa-consensus");
     }
@@ -669,6 +716,69 @@ int main(int argc, char** argv) {
     fprintf(stderr, "Corrected %lld reads: %lld bases in, %lld out; %lld substitutions, %lld deletions, %lld insertions, %lld positions of low coverage; skipped_views = %lld\n",
             (long long)nr, tot[0], tot[1], tot[2], tot[3], tot[4], tot[5], (long long)skipped);
     fprintf(stderr, "Time (s) to vote and correct: %g\n", RA.correct_seconds);
+  }
+  if (RA.trim) {   // every read's clear range, after the last batch has been piled up; with --gfa the graph begins here, on the trimmed reads
+    const double tt = now();
+    const int64_t nr = (int64_t)RA.ids.size();
+    int64_t tc[MHAP_TRIM_COUNTS];
+    chk(E.h, mhap_trim_finish(RA.trim, tc));
+    std::vector<int32_t> trows((size_t)std::max<int64_t>(nr, 1) * 4);
+    std::vector<uint8_t> tflags((size_t)std::max<int64_t>(nr, 1));
+    chk(E.h, mhap_trim_copy(RA.trim, trows.data(), tflags.data()));
+    if (o.isset("--trim-fasta")) {
+      FILE* f = fopen(o.s("--trim-fasta").c_str(), "wb");
+      if (!f) die("cannot write " + o.s("--trim-fasta"));
+      std::string text;
+      for (int64_t r = 0; r < nr; r++) {
+        if (tflags[(size_t)r] & MHAP_TRIM_DELETED) continue;
+        const int32_t* c = trows.data() + 4 * r;
+        text += ">" + header_of(RA.ids[(size_t)r]) + " len=" + std::to_string(c[1] - c[0]) + " begin=" + std::to_string(c[0]) + " end=" + std::to_string(c[1]) +
+                " runs=" + std::to_string(c[2]) + "\n";
+        text.append((const char*)RA.bases.data() + RA.offsets[(size_t)r] + c[0], (size_t)(c[1] - c[0]));
+        text.push_back('\n');
+        if (text.size() > (8u << 20)) { fwrite(text.data(), 1, text.size(), f); text.clear(); }
+      }
+      fwrite(text.data(), 1, text.size(), f);
+      if (fclose(f) != 0) die("cannot write " + o.s("--trim-fasta"));
+    }
+    if (o.isset("--trim-table")) {
+      FILE* f = fopen(o.s("--trim-table").c_str(), "wb");
+      if (!f) die("cannot write " + o.s("--trim-table"));
+      for (int64_t r = 0; r < nr; r++) {
+        const int32_t* c = trows.data() + 4 * r;
+        fprintf(f, "%lld\t%d\t%d\t%d\t%d\t%d\t%d\n", (long long)RA.ids[(size_t)r], RA.lengths[(size_t)r], c[0], c[1], c[2], c[3], (int)tflags[(size_t)r]);
+      }
+      if (fclose(f) != 0) die("cannot write " + o.s("--trim-table"));
+    }
+    if (gfa) {   // the records rewritten and compacted, the table of the surviving reads, and the graph over both
+      const int64_t nk = (int64_t)RA.kept_records.size();
+      std::vector<mhap_record> applied((size_t)std::max<int64_t>(nk, 1));
+      std::vector<uint8_t> keep((size_t)std::max<int64_t>(nk, 1));
+      chk(E.h, mhap_trim_apply(RA.trim, RA.kept_records.data(), nk, applied.data(), keep.data()));
+      size_t w = 0;
+      for (int64_t q = 0; q < nk; q++) if (keep[(size_t)q]) applied[w++] = applied[(size_t)q];
+      applied.resize(w);
+      RA.kept_records.swap(applied);
+      size_t live = 0;
+      for (int64_t r = 0; r < nr; r++) {   // (the bases stay where they are: a trimmed read begins `begin` bytes later)
+        if (tflags[(size_t)r] & MHAP_TRIM_DELETED) continue;
+        RA.ids[live] = RA.ids[(size_t)r];
+        RA.offsets[live] = RA.offsets[(size_t)r] + trows[(size_t)r * 4];
+        RA.lengths[live++] = trows[(size_t)r * 4 + 1] - trows[(size_t)r * 4];
+      }
+      RA.ids.resize(live); RA.offsets.resize(live); RA.lengths.resize(live);
+      const double tg = now();
+      chk(E.h, mhap_graph_begin(E.h, RA.ids.data(), RA.lengths.data(), (int64_t)live, &gp, &RA.graph));
+      chk(E.h, mhap_graph_add(RA.graph, RA.kept_records.data(), (int64_t)RA.kept_records.size()));
+      RA.graph_seconds += now() - tg;
+      if (!o.b("--gfa-consensus")) std::vector<mhap_record>().swap(RA.kept_records);
+    }
+    mhap_trim_free(RA.trim);
+    RA.trim = nullptr;
+    RA.trim_seconds += now() - tt;
+    fprintf(stderr, "Trim: %lld reads, %lld deleted, %lld cut at 5', %lld cut at 3', %lld gapped; %lld of %lld bases kept, %lld eligible overlaps\n",
+            (long long)tc[0], (long long)tc[1], (long long)tc[2], (long long)tc[3], (long long)tc[4], (long long)tc[6], (long long)tc[5], (long long)tc[7]);
+    fprintf(stderr, "Time (s) to pile up and trim: %g\n", RA.trim_seconds);
   }
   if (RA.graph) {   // the list and its reduction, after the last batch has been classed; the GFA file is all it writes
     const double tg = now();

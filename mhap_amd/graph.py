@@ -16,8 +16,11 @@ section); the -o file is then the cleaned read graph and the --unitigs file the 
 With --consensus (which needs --unitigs) every read is placed on a unitig, aligned to it and votes, and the --unitigs file carries the
 consensus sequences, their lengths and `a` offsets mapped into them ("unitig consensus" in the same header); --consensus-fasta also
 writes them as FASTA.
-Not done: read trimming, chimera detection, bubbles that are not simple.  One line on stderr gives the counts (one more
-with --clean, one more with --unitigs, one more with --consensus).
+With --trim [--trim-min-cov N] [--trim-end-clip N] [--trim-min-span N] [--trim-penalty N] the reads are trimmed and chimeras split on the GPU first
+("read trimming" in the same header; `python -m mhap_amd.trim` writes the trimmed reads themselves): every output is then built on
+the surviving reads, their trimmed lengths and the overlaps rewritten onto them.
+Not done: bubbles that are not simple, a second trimming round.  One line on stderr gives the counts (one more with --trim, in
+front; one more with --clean, one more with --unitigs, one more with --consensus).
 """
 import argparse
 import sys
@@ -41,19 +44,30 @@ def consensus_fasta(seqs, circular):
 
 
 def graph_overlaps(recs, fasta, band=0, max_shift=0.2, min_identity=0.0, device=0, batch=BATCH, unitigs=False, clean=None, consensus=None,
-                   **params):
+                   trim=None, **params):
     """Realign `recs` in batches and build the graph: (gfa text, arcs, counts, contained); with unitigs=True two more: the GFA text
     of the unitig graph and the dict of GraphSession.unitigs().  clean: None, or a dict of GraphSession.clean's parameters: the graph
     is cleaned first, both texts and the dict are those of the cleaned graph, and the dict of CLEAN_COUNTS comes last.
     consensus: None, or a dict of ConsensusSession's parameters (min_cov, band), with unitigs=True: the unitig text carries the consensus,
     and the result is a dict instead: gfa, arcs, counts, contained, unitig_gfa, unitigs, clean_counts (or None), consensus_counts,
-    consensus_seqs."""
+    consensus_seqs.
+    trim: None, or a dict of TrimSession's parameters (min_cov, end_clip, min_span): the reads are trimmed first ("read trimming" in
+    the same header) and everything above is built on the surviving reads, their trimmed lengths and the records rewritten onto
+    them; the dict of TRIM_COUNTS then comes last of all (key trim_counts of the dict)."""
     with api.MinHashSearch(api.MhapParams(num_hashes=1, ordered_sketch_size=1, max_shift=max_shift, device=device)) as ms:
+        tcounts = ()
+        if trim is not None:   # every record is realigned and held, the reads are cut, and the graph sees the rewritten records only
+            from .trim import trim_overlaps
+            t = trim_overlaps(recs, fasta, band=band, max_shift=max_shift, min_identity=min_identity, batch=batch, handle=ms, **trim)
+            fasta, tcounts = t["reads"], (t["counts"],)
+            batches = (t["applied"][q0:q0 + batch] for q0 in range(0, len(t["applied"]), batch))
+        else:
+            batches = (api.realign_records(recs[q0:q0 + batch], fasta, band=band, handle=ms)[0] for q0 in range(0, len(recs), batch))
         with api.GraphSession(fasta.ids, fasta.lengths, handle=ms, **params) as gs:
             kept = []
-            for q0 in range(0, len(recs), batch):
-                out, _ = api.realign_records(recs[q0:q0 + batch], fasta, band=band, handle=ms)
-                out = out[kept_rows(out, min_identity)]
+            for out in batches:
+                if trim is None:
+                    out = out[kept_rows(out, min_identity)]
                 gs.add(out)
                 if consensus is not None:
                     kept.append(out)       # held until the graph is finished, then fed to the consensus
@@ -70,11 +84,12 @@ def graph_overlaps(recs, fasta, band=0, max_shift=0.2, min_identity=0.0, device=
                         cs.add(out)
                     ccounts = cs.run()
                     return dict(gfa=text, arcs=arcs, counts=counts, contained=gs.contained(), unitig_gfa=cs.gfa(), unitigs=gs.unitigs_table,
-                                clean_counts=tail[0] if tail else None, consensus_counts=ccounts, consensus_seqs=cs.sequences())
+                                clean_counts=tail[0] if tail else None, consensus_counts=ccounts, consensus_seqs=cs.sequences(),
+                                trim_counts=tcounts[0] if tcounts else None)
             if unitigs:
                 utext = gs.unitig_gfa(fasta)
-                return (text, arcs, counts, gs.contained(), utext, gs.unitigs_table) + tail
-            return (text, arcs, counts, gs.contained()) + tail
+                return (text, arcs, counts, gs.contained(), utext, gs.unitigs_table) + tail + tcounts
+            return (text, arcs, counts, gs.contained()) + tail + tcounts
 
 
 def main(argv=None):
@@ -98,7 +113,16 @@ def main(argv=None):
     ap.add_argument("--consensus", action="store_true", help="with --unitigs, write the consensus of every unitig's reads instead of its raw spelling")
     ap.add_argument("--consensus-fasta", default=None, help="with --consensus, also write the consensus sequences to this FASTA file")
     ap.add_argument("--consensus-min-cov", type=int, default=4, help="with --consensus, the depth below which a position keeps the draft's base")
+    ap.add_argument("--trim", action="store_true", help="trim the reads and split chimeras on the GPU first; every output is built on the trimmed reads")
+    ap.add_argument("--trim-min-cov", type=int, default=3, help="with --trim, the shrunk overlaps a position needs to be kept")
+    ap.add_argument("--trim-end-clip", type=int, default=500, help="with --trim, the bases every aligned interval is shrunk by at both ends")
+    ap.add_argument("--trim-min-span", type=int, default=2000, help="with --trim, the shortest aligned interval that counts")
+    ap.add_argument("--trim-penalty", type=int, default=api.TRIM_PENALTY, help="with --trim, the cost of an error column when overlaps are cut to their best stretch; 0: not cut")
     a = ap.parse_args(argv)
+    if (a.trim_min_cov != 3 or a.trim_end_clip != 500 or a.trim_min_span != 2000 or a.trim_penalty != api.TRIM_PENALTY) and not a.trim:
+        ap.error("--trim-min-cov, --trim-end-clip, --trim-min-span and --trim-penalty need --trim")
+    if a.trim_min_cov < 1 or a.trim_end_clip < 0 or a.trim_min_span < 0 or a.trim_penalty < 0:
+        ap.error("--trim-min-cov must be >= 1, --trim-end-clip, --trim-min-span and --trim-penalty >= 0")
     if a.consensus and not a.unitigs:
         ap.error("--consensus needs --unitigs")
     if (a.consensus_fasta or a.consensus_min_cov != 4) and not a.consensus:
@@ -116,7 +140,12 @@ def main(argv=None):
     res = graph_overlaps(recs, fasta, band=a.band, max_shift=a.max_shift, min_identity=a.min_identity, device=a.device, unitigs=bool(a.unitigs),
                          clean=dict(tip_reads=a.tip_reads, bubble_bases=a.bubble_bases, max_rounds=a.clean_rounds) if a.clean else None,
                          consensus=dict(min_cov=a.consensus_min_cov) if a.consensus else None,
+                         trim=dict(min_cov=a.trim_min_cov, end_clip=a.trim_end_clip, min_span=a.trim_min_span, penalty=a.trim_penalty) if a.trim else None,
                          max_hang=a.max_hang, int_frac_permille=int(round(a.int_frac * 1000)), min_ovlp=a.min_overlap, fuzz=a.fuzz)
+    tcounts = None
+    if a.trim:
+        tcounts = res["trim_counts"] if a.consensus else res[-1]
+        res = res if a.consensus else res[:-1]
     if a.consensus:
         res = (res["gfa"], res["arcs"], res["counts"], res["contained"], res["unitig_gfa"], res["unitigs"], res["consensus_counts"],
                res["consensus_seqs"]) + ((res["clean_counts"],) if a.clean else ())
@@ -126,6 +155,8 @@ def main(argv=None):
             fh.write(text)
     else:
         sys.stdout.write(text)
+    if a.trim:
+        print(api.trim_counts_line([tcounts[k] for k in api.TRIM_COUNTS]), file=sys.stderr)
     print(counts_line(counts), file=sys.stderr)
     if a.clean:
         print(api.clean_counts_line([res[-1][k] for k in api.CLEAN_COUNTS]), file=sys.stderr)

@@ -225,3 +225,26 @@ def c3_fasta_path():
     """BASELINE configs[2] (E. coli PacBio P6-C4 reads) is not in either tree: supplied on the box through MHAP_C3_FASTA."""
     p = os.environ.get("MHAP_C3_FASTA")
     return p if p and os.path.exists(p) else None
+
+
+def plant_chimeras(fasta, n, seed):
+    """`n` two-piece chimeras planted into a copy of `fasta`: a chosen read keeps its first j bases and takes the last length - j
+    bases of another read for the rest, j drawn from the middle fifth of the read, so its length (and every offset) stays.  Returns
+    (reads, junctions): junctions is int64 (n, 3) of {read index, j, the other read's index}, in ascending read index.  The reads
+    chosen and their partners are all different reads at least as long as the piece taken from them."""
+    rng = np.random.default_rng(seed)
+    if 2 * n > len(fasta):
+        raise ValueError(f"plant_chimeras: {n} chimeras need {2 * n} reads, there are {len(fasta)}")
+    picked = rng.choice(len(fasta), 2 * n, replace=False)
+    victims, partners = np.sort(picked[:n]), picked[n:]
+    bases = fasta.bases.copy()
+    rows = np.zeros((n, 3), np.int64)
+    for k, (v, p) in enumerate(zip(victims.tolist(), partners.tolist())):
+        lv, lp = int(fasta.lengths[v]), int(fasta.lengths[p])
+        j = int(rng.integers(2 * lv // 5, 3 * lv // 5 + 1))
+        take = min(lv - j, lp)
+        j = lv - take
+        ov, op = int(fasta.offsets[v]), int(fasta.offsets[p])
+        bases[ov + j:ov + lv] = fasta.bases[op + lp - take:op + lp]
+        rows[k] = (v, j, p)
+    return FastaData(bases, fasta.offsets.copy(), fasta.lengths.copy(), fasta.ids.copy()), rows
