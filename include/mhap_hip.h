@@ -847,7 +847,8 @@ void mhap_consensus_free(mhap_consensus_session* s);
  * every aligned interval is shrunk by end_clip at both ends and piled up per read, and a read keeps the longest stretch that
  * min_cov of them cover, widened again by end_clip.  At a chimeric junction the overlaps of both sides end, so after the shrink
  * nothing covers it and the read falls into two stretches, of which the longer survives.  One round; left out: a second round on
- * the trimmed records, selection of best overlaps, any repeat-aware rule (a repeat's false overlaps count as coverage).
+ * the trimmed records, selection of best overlaps.  A repeat's false overlaps count as coverage here; "repeat marking" below sets
+ * them aside in front of this stage when it is asked to, within its two-copy limit.
  * Everything is integer arithmetic in int64; the only floating comparison is score < min_identity on the record's double.  The
  * result is a function of the multiset of records: invariant under any permutation of the records and any split of them over
  * calls.  Nothing is de-duplicated: a record given twice counts twice, as in the correction stage.
@@ -935,6 +936,84 @@ int mhap_trim_clip_record(const mhap_record* in, const int32_t* clearA /* 2 */, 
 int mhap_trim_refine(mhap_handle* h, const mhap_record* realigned, int64_t n, const mhap_align_paths* paths, int32_t penalty, mhap_record* out);
 int mhap_trim_refine_record(const mhap_record* in, const uint32_t* ops, int64_t n_ops, int32_t penalty, mhap_record* out);
 void mhap_trim_free(mhap_trim_session* s);
+
+/* ---- repeat marking: repeats found from the overlap pile-up, overlaps that lie in nothing but repeat set aside ---- */
+
+/* An opt-in step in front of the trimming and the string graph (the overlap-based repeat rule of Canu and Falcon as integer
+ * arithmetic).  Two reads from different copies of a repeat overlap inside the repeat; where the repeat sits at a read's end that
+ * overlap looks like a dovetail, becomes an arc between two loci, counts as support in the trimming, is a fork and no tip to the
+ * cleaning, and makes the consensus vote reads of one copy onto another.  Here the aligned intervals are piled up per read, the
+ * stretches of a read that lie well above the typical depth are marked, and every overlap that has no anchor outside such stretches
+ * on either of its reads is void.  The result is a function of the multiset of records: invariant under any permutation of the
+ * records and any split of them over calls, and the same bytes from run to run.  Nothing is de-duplicated.
+ *
+ * Input.  A table of reads (read_ids[r], lengths[r]; no bases), realigned records as for mhap_trim_add, and the parameters
+ * factor_pct (200), max_cov (0: derive it), min_run (500), min_unique (500), min_identity (0.0); the defaults are choices, not
+ * measurements.  factor_pct >= 100, max_cov >= 0, min_run >= 1 and min_unique >= 0, else MHAP_E_INVALID.
+ *
+ * Eligible record.  The trimming's rule: from_id != to_id, score != 0 and not score < min_identity.
+ *
+ * Coverage.  An eligible record gives read A the interval [a1, a2 + 1) and read B the interval [b1, b2 + 1) (b is in B's forward
+ * coordinates already, so to_rc plays no part): the trimming's contribution with end_clip = 0 and min_span = 0, no shrink and no
+ * minimum span.  cov_r[p] = the number of contributed intervals of read r that contain p.
+ *
+ * Typical depth D.  hist[c] = the positions p in [0, length_r) over all reads with min(cov_r[p], MHAP_REPEAT_BINS - 1) == c; N1 = the
+ * sum of hist[c] over c >= 1; D = the smallest c >= 1 with 2 * (hist[1] + ... + hist[c]) >= N1 (the lower median of the covered
+ * positions), 0 when N1 == 0.  When max_cov == 0 and D == MHAP_REPEAT_BINS - 1 the last bin has swallowed the median: the finish fails
+ * with MHAP_E_INVALID and a message that says to give max_cov.
+ *
+ * Threshold T.  max_cov when max_cov > 0, else D * factor_pct div 100.  Position p of read r is a repeat position iff cov_r[p] > T.
+ *
+ * Repeat intervals.  The maximal runs [s, e) of repeat positions of read r with e - s >= min_run, ascending.  CSR: int64
+ * offsets[n_reads + 1] and int32 pairs {begin, end}.  Per read four int32 {intervals, repeat_bases (the sum of e - s), max_cov (the
+ * greatest cov_r[p], 0 for an empty read), first_begin or -1} and one flag byte: bit 0 MHAP_REPEAT_SOME (an interval), bit 1
+ * MHAP_REPEAT_WHOLE (one interval, and it is [0, length)).  MHAP_REPEAT_COUNTS int64 counts: reads, reads with an interval,
+ * whole-repeat reads, intervals, repeat bases, bases, eligible records, D, T.
+ *
+ * Judging a record.  For an eligible record uA = (a2 + 1 - a1) - (the positions of [a1, a2 + 1) inside A's intervals) and uB likewise
+ * on B; keep = 1 iff uA >= min_unique and uB >= min_unique, else 0.  An ineligible record has keep = 1 and uA = uB = -1: later stages
+ * have their own rule for it.  Records are never rewritten.
+ *
+ * What it does not do.  A two-copy repeat at ordinary depth piles up to about twice D only where the reads of both copies happen to
+ * lie, which is not reliably above any usable threshold: on exact records the default keeps all or nearly all of its false overlaps
+ * at three of four seeds, factor_pct 150 still keeps 212 of 467 at one, and 140 and 125 void up to 36 and 419 of about 8 600 true
+ * overlaps with a good anchor (EXPERIMENTS.md, "Repeat marking").  Intervals are neither padded nor merged, so a dip in the
+ * pile-up inside a repeat splits its interval and a run shorter than min_run is no interval at all.  One round: the depth is not
+ * measured again without the void records.
+ *
+ * The session mirrors mhap_trim_*.  mhap_repeat_begin takes the table of reads (params NULL: the defaults); the handle must outlive
+ * the session, whose errors are the handle's.  mhap_repeat_add piles records up (the trimming's add kernel, shared, with the
+ * parameters above), any number of times, n = 0 included, without waiting; the same checks and refusals as mhap_trim_add, and a
+ * refused call adds nothing.  mhap_repeat_finish makes the bins, D and T, the rows, flags, offsets and intervals, waits once and
+ * returns the counts; it may be repeated, and more records may be added after it.  mhap_repeat_copy writes the rows, flags, offsets
+ * and intervals (counts[3] pairs) of the last finish; mhap_repeat_histogram its MHAP_REPEAT_BINS bins.  mhap_repeat_apply, after a
+ * finish: keep[q] and unique[2 q], unique[2 q + 1] = uA, uB; records are checked as in the add; the caller compacts.
+ * mhap_repeat_judge_record uses no GPU and takes explicit interval lists {begin, end} of the two reads (ascending, disjoint, inside
+ * the read): 1 keep, 0 void, -1 for a null pointer, bad parameters, a bad list or an eligible record outside its reads; unique
+ * (may be NULL) takes uA, uB.  Device memory from begin to free: 4 bytes per base (the difference array, each read's slots rounded
+ * up to four), 45 per read, 12 per interval the reads could have (the sum of (length + 1) div (min_run + 1)), 32 per record of the
+ * largest add and 48 of the largest apply, 32 KiB of bins. */
+typedef struct mhap_repeat_params {
+  int32_t factor_pct, max_cov, min_run, min_unique;
+  double min_identity;
+} mhap_repeat_params;
+#define MHAP_REPEAT_COUNTS 9
+#define MHAP_REPEAT_BINS 4096
+#define MHAP_REPEAT_SOME 1
+#define MHAP_REPEAT_WHOLE 2
+typedef struct mhap_repeat_session mhap_repeat_session;
+void mhap_repeat_default_params(mhap_repeat_params* p);
+int mhap_repeat_begin(mhap_handle* h, const int64_t* read_ids, const int32_t* lengths, int64_t n_reads, const mhap_repeat_params* params,
+                      mhap_repeat_session** session);
+int mhap_repeat_add(mhap_repeat_session* s, const mhap_record* realigned, int64_t n);
+int mhap_repeat_finish(mhap_repeat_session* s, int64_t* counts /* MHAP_REPEAT_COUNTS */);
+int mhap_repeat_copy(mhap_repeat_session* s, int32_t* rows /* n_reads x 4 */, uint8_t* flags /* n_reads */, int64_t* offsets /* n_reads + 1 */,
+                     int32_t* intervals /* counts[3] x 2 */);
+int mhap_repeat_histogram(mhap_repeat_session* s, int64_t* bins /* MHAP_REPEAT_BINS */);
+int mhap_repeat_apply(mhap_repeat_session* s, const mhap_record* in, int64_t n, uint8_t* keep /* n */, int32_t* unique /* n x 2 */);
+int mhap_repeat_judge_record(const mhap_record* in, const int32_t* intervalsA, int64_t nA, const int32_t* intervalsB, int64_t nB,
+                             const mhap_repeat_params* params, int32_t* unique /* 2, or NULL */);
+void mhap_repeat_free(mhap_repeat_session* s);
 
 /* KmerStatSimulator's pair statistics on the GPU (J/main/KmerStatSimulator.java:163-196).  pairs: n rows of 4 int64 {a_off, a_len,
  * b_off, b_len}; a = bases[a_off, a_off + a_len) is the first read, b the second.  skip: n_skip k-mers of k bytes each, back to back, in

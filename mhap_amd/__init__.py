@@ -45,6 +45,9 @@ from .api import (  # noqa: F401
     trim_clip_record,
     trim_refine,
     trim_refine_record,
+    RepeatSession,
+    repeat_counts_line,
+    repeat_judge_record,
     pair_kmer_stats,
     records_to_lines,
     load_library,

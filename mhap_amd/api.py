@@ -86,6 +86,8 @@ EXPORTED_SYMBOLS = [
     "mhap_consensus_free",
     "mhap_trim_default_params", "mhap_trim_begin", "mhap_trim_add", "mhap_trim_finish", "mhap_trim_copy", "mhap_trim_coverage",
     "mhap_trim_apply", "mhap_trim_clip_record", "mhap_trim_free", "mhap_trim_refine", "mhap_trim_refine_record",
+    "mhap_repeat_default_params", "mhap_repeat_begin", "mhap_repeat_add", "mhap_repeat_finish", "mhap_repeat_copy", "mhap_repeat_histogram",
+    "mhap_repeat_apply", "mhap_repeat_judge_record", "mhap_repeat_free",
     "mhap_pair_kmer_stats", "mhap_pair_kmer_stats_paths", "mhap_ksim_create", "mhap_ksim_next", "mhap_ksim_error", "mhap_ksim_destroy",
     "mhap_ksim_dev_create", "mhap_ksim_dev_destroy", "mhap_ksim_dev_pair_stats", "mhap_ksim_dev_trials",
 ]
@@ -1105,6 +1107,133 @@ class TrimSession:
     def close(self):
         if self._s:
             self._lib.mhap_trim_free(self._s)
+            self._s = C.c_void_p()
+            if self._own:
+                self._ms.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+REPEAT_COUNTS = ("reads", "reads_with_interval", "whole_reads", "intervals", "repeat_bases", "bases", "eligible_records", "depth",
+                 "threshold")   # mhap_repeat_finish's counts
+REPEAT_ROW_FIELDS = ("intervals", "repeat_bases", "max_cov", "first_begin")
+REPEAT_SOME, REPEAT_WHOLE = 1, 2   # the bits of a read's flag byte
+REPEAT_BINS = 4096   # MHAP_REPEAT_BINS: the bins of the depth histogram, the last one holding every greater depth
+REPEAT_DEFAULTS = dict(factor_pct=200, max_cov=0, min_run=500, min_unique=500, min_identity=0.0)   # choices, not measurements
+
+
+class _RepeatParams(C.Structure):
+    _fields_ = [("factor_pct", C.c_int32), ("max_cov", C.c_int32), ("min_run", C.c_int32), ("min_unique", C.c_int32),
+                ("min_identity", C.c_double)]
+
+
+def repeat_counts_line(counts):
+    """The one stderr line of a repeat marking (the driver prints the same); counts: the MHAP_REPEAT_COUNTS values in order."""
+    c = [int(x) for x in counts]
+    return (f"Repeats: {c[0]} reads, {c[1]} with a repeat, {c[2]} repeat throughout; {c[3]} intervals, {c[4]} of {c[5]} bases; "
+            f"{c[6]} eligible overlaps, depth {c[7]}, threshold {c[8]}")
+
+
+def repeat_judge_record(record, intervals_a, intervals_b, factor_pct=200, max_cov=0, min_run=500, min_unique=500, min_identity=0.0):
+    """One record against explicit interval lists [(begin, end), ...] of its two reads (mhap_repeat_judge_record, no GPU):
+    (keep, uA, uB)."""
+    lib = load_library()
+    rec = np.ascontiguousarray(record, dtype=RECORD_DTYPE).reshape(1)
+    ia, ib = (np.ascontiguousarray(x, np.int32).reshape(-1, 2) for x in (intervals_a, intervals_b))
+    u = np.zeros(2, np.int32)
+    p = _RepeatParams(factor_pct, max_cov, min_run, min_unique, min_identity)
+    rc = lib.mhap_repeat_judge_record(_ptr(rec), _ptr(ia) if len(ia) else None, C.c_int64(len(ia)), _ptr(ib) if len(ib) else None,
+                                      C.c_int64(len(ib)), C.byref(p), _ptr(u))
+    if rc < 0:
+        raise MhapError("mhap_repeat_judge_record: bad parameters, interval list or record")
+    return bool(rc), int(u[0]), int(u[1])
+
+
+class RepeatSession:
+    """Repeats marked from the overlap pile-up (mhap_repeat_begin / _add / _finish / _copy / _histogram / _apply; the contract is the
+    "repeat marking" section of include/mhap_hip.h).
+
+        with RepeatSession(fasta.ids, fasta.lengths) as rs:
+            rs.add(records)                       # realigned (and refined) records; any number of times
+            counts = rs.finish()                  # a dict of REPEAT_COUNTS
+            rows, flags, offsets, intervals = rs.table()   # read r's intervals: intervals[offsets[r]:offsets[r + 1]], (begin, end)
+            bins = rs.histogram()                 # int64 (REPEAT_BINS)
+            keep, unique = rs.apply(records)      # records[keep != 0] are the ones that stay; unique: int32 (n, 2) of uA, uB
+
+    handle: a MinHashSearch whose device and stream to use (else one is made and closed with the session)."""
+
+    def __init__(self, read_ids, lengths, factor_pct=200, max_cov=0, min_run=500, min_unique=500, min_identity=0.0, handle=None, device=0):
+        self._own = handle is None
+        self._ms = MinHashSearch(MhapParams(num_hashes=1, ordered_sketch_size=1, device=device)) if self._own else handle
+        self._lib = self._ms._lib
+        self._s = C.c_void_p()
+        self.ids = np.ascontiguousarray(read_ids, np.int64)
+        self.lengths = np.ascontiguousarray(lengths, np.int32)
+        self._table = self.counts = None
+        try:
+            if len(self.ids) != len(self.lengths):
+                raise MhapError(f"RepeatSession: {len(self.ids)} ids and {len(self.lengths)} lengths")
+            p = _RepeatParams(factor_pct, max_cov, min_run, min_unique, min_identity)
+            self._ms._chk(self._lib.mhap_repeat_begin(self._ms._h, _ptr(self.ids) if len(self.ids) else None,
+                                                      _ptr(self.lengths) if len(self.ids) else None, C.c_int64(len(self.ids)), C.byref(p),
+                                                      C.byref(self._s)))
+        except Exception:
+            if self._own:
+                self._ms.close()
+            raise
+
+    def add(self, records):
+        """Pile realigned records up (nothing waits for the device)."""
+        records = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
+        self._ms._chk(self._lib.mhap_repeat_add(self._s, _ptr(records) if len(records) else None, C.c_int64(len(records))))
+
+    def finish(self):
+        """Make the histogram, the depth and threshold and every read's intervals; returns a dict of REPEAT_COUNTS."""
+        counts = np.zeros(len(REPEAT_COUNTS), np.int64)
+        self._table = self.counts = None
+        self._ms._chk(self._lib.mhap_repeat_finish(self._s, _ptr(counts)))
+        self.counts = dict(zip(REPEAT_COUNTS, counts.tolist()))
+        return self.counts
+
+    def table(self):
+        """(rows, flags, offsets, intervals) of the last finish: int32 (n, 4) of REPEAT_ROW_FIELDS, one byte of REPEAT_* bits per read,
+        int64 (n + 1) and int32 (intervals, 2)."""
+        if self._table is None:
+            n = len(self.ids)
+            rows, flags, offsets = np.zeros((n, 4), np.int32), np.zeros(n, np.uint8), np.zeros(n + 1, np.int64)
+            iv = np.zeros((self.counts["intervals"] if self.counts else 0, 2), np.int32)   # (without a finish the copy refuses)
+            opt = lambda a: _ptr(a) if len(a) else None
+            self._ms._chk(self._lib.mhap_repeat_copy(self._s, opt(rows), opt(flags), _ptr(offsets), opt(iv)))
+            self._table = (rows, flags, offsets, iv)
+        return self._table
+
+    def histogram(self):
+        """The REPEAT_BINS bins of the last finish (int64): positions by depth, the last bin holding every greater depth."""
+        bins = np.zeros(REPEAT_BINS, np.int64)
+        self._ms._chk(self._lib.mhap_repeat_histogram(self._s, _ptr(bins)))
+        return bins
+
+    def apply(self, records):
+        """(keep, unique): one byte per record, 0 for a void one, and int32 (n, 2) of uA, uB (-1, -1 for an ineligible record)."""
+        records = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
+        keep, unique = np.zeros(len(records), np.uint8), np.zeros((len(records), 2), np.int32)
+        opt = lambda a: _ptr(a) if len(a) else None
+        self._ms._chk(self._lib.mhap_repeat_apply(self._s, opt(records), C.c_int64(len(records)), opt(keep), opt(unique)))
+        return keep, unique
+
+    def close(self):
+        if self._s:
+            self._lib.mhap_repeat_free(self._s)
             self._s = C.c_void_p()
             if self._own:
                 self._ms.close()

@@ -226,4 +226,30 @@ __device__ inline uint32_t strand_char(const uint8_t* __restrict__ store, const 
   return (0x54474341u >> (8 * code)) & 0xFFu;  // "ACGT"
 }
 
+// (graph_kernels.hip and repeat_kernels.hip)  start[0 .. n] = the exclusive prefix sums of deg[0 .. n): one workgroup, 1024 values at a time with a carry
+template <class T>
+__global__ __launch_bounds__(1024) void scan_kernel(const T* __restrict__ deg, int64_t n, int64_t* __restrict__ start) {
+  __shared__ int64_t wave_sum[16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int64_t carry = 0;
+  for (int64_t i0 = 0; i0 < n; i0 += 1024) {
+    const int64_t i = i0 + tid;
+    const int64_t x = i < n ? deg[i] : 0;
+    int64_t incl = x;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int64_t u = __shfl_up(incl, d);
+      if (lane >= d) incl += u;
+    }
+    __syncthreads();   // wave_sum of the previous tile has been read
+    if (lane == 63) wave_sum[wave] = incl;
+    __syncthreads();
+    int64_t before = 0, tile = 0;
+    for (int u = 0; u < 16; u++) { if (u < wave) before += wave_sum[u]; tile += wave_sum[u]; }
+    if (i < n) start[i] = carry + before + incl - x;
+    carry += tile;
+  }
+  if (tid == 0) start[n] = carry;
+}
+
 }  // namespace mhap

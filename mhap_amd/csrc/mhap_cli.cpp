@@ -43,7 +43,7 @@ struct Options {
     return t;
   }
   // (the realignment flags are listed only when --realign is given, the correction flags only when --correct is, the graph's only
-  // when --gfa is, the cleaning's only when --gfa-clean is, the consensus' only when --gfa-consensus is, the trimming's only when --trim is: without them every line the driver writes is what it was before them)
+  // when --gfa is, the cleaning's only when --gfa-clean is, the consensus' only when --gfa-consensus is, the trimming's only when --trim is, the repeat stage's only when --repeat-filter is: without them every line the driver writes is what it was before them)
   std::string dump() const {
     std::string t;
     for (auto& n : order) {
@@ -53,6 +53,7 @@ struct Options {
       if ((n == "--gfa-clean" || n == "--gfa-tip-reads" || n == "--gfa-bubble-bases" || n == "--gfa-clean-rounds") && !b("--gfa-clean")) continue;
       if (n.compare(0, 15, "--gfa-consensus") == 0 && !b("--gfa-consensus")) continue;
       if (n.compare(0, 6, "--trim") == 0 && !b("--trim")) continue;
+      if (n.compare(0, 8, "--repeat") == 0 && !b("--repeat-filter")) continue;
       t += n + " = " + m.at(n).value + "\n";
     }
     return t;
@@ -181,6 +182,10 @@ struct Realign {
   int32_t trim_penalty = 0;                           // > 0: each record is first cut to the best stretch of its path
   std::vector<mhap_record> refined;
   double trim_seconds = 0.0;
+  mhap_repeat_session* repeat = nullptr;              // --repeat-filter: the refined copies are piled up; every kept record waits to be judged
+  bool hold_plain = false;                            // the graph takes the survivors as realigned: those copies wait too
+  std::vector<mhap_record> held_refined, held_plain;
+  double repeat_seconds = 0.0;
   void add(const mhap_fasta& fa) {
     for (int64_t i = 0; i < fa.n; i++) { ids.push_back(fa.ids[i]); offsets.push_back((int64_t)bases.size() + fa.offsets[i]); lengths.push_back(fa.lengths[i]); }
     bases.insert(bases.end(), (const uint8_t*)fa.bases, (const uint8_t*)fa.bases + fa.total_bases);
@@ -195,7 +200,7 @@ int sink_cb(const mhap_record* r, int64_t n, void* user) {
     const double t = now();
     R.out.resize((size_t)n);
     int rc;
-    if (R.paf || R.correct || (R.trim && R.trim_penalty > 0)) {
+    if (R.paf || R.correct || ((R.trim || R.repeat) && R.trim_penalty > 0)) {
       R.detail.resize((size_t)n * 3);
       mhap_align_paths* paths = nullptr;
       rc = mhap_realign_records_paths(R.h, R.bases.data(), (int64_t)R.bases.size(), R.ids.data(), R.offsets.data(), R.lengths.data(),
@@ -223,7 +228,7 @@ int sink_cb(const mhap_record* r, int64_t n, void* user) {
     }
     R.dropped += n - k; R.kept += k;
     R.seconds += now() - t;
-    const bool refine = R.trim && R.trim_penalty > 0;
+    const bool refine = (R.trim || R.repeat) && R.trim_penalty > 0;
     if (R.correct || refine) {   // the kept records and their runs: into the vote table, and cut to their best stretch for the trimming
       const double tc = now();
       R.vote_offsets.assign(1, 0); R.vote_ops.clear();
@@ -246,19 +251,26 @@ int sink_cb(const mhap_record* r, int64_t n, void* user) {
       if (rc != MHAP_OK) { fprintf(stderr, "Exception in mhap-hip: %s (code %d)\n", mhap_last_error(R.h), rc); return 1; }
     }
     const mhap_record* for_trim = refine ? R.refined.data() : R.out.data();
-    if (R.trim) {   // the kept records onto the coverage of their reads (queued: nothing waits)
+    if (R.repeat) {   // the refined copies onto the pile-up (queued: nothing waits); trimming and graph take the survivors after the last batch
+      const double tr = now();
+      rc = mhap_repeat_add(R.repeat, for_trim, k);
+      if (rc != MHAP_OK) { fprintf(stderr, "Exception in mhap-hip: %s (code %d)\n", mhap_last_error(R.h), rc); return 1; }
+      R.held_refined.insert(R.held_refined.end(), for_trim, for_trim + k);
+      if (R.hold_plain) R.held_plain.insert(R.held_plain.end(), R.out.data(), R.out.data() + k);
+      R.repeat_seconds += now() - tr;
+    } else if (R.trim) {   // the kept records onto the coverage of their reads (queued: nothing waits)
       const double tt = now();
       rc = mhap_trim_add(R.trim, for_trim, k);
       if (rc != MHAP_OK) { fprintf(stderr, "Exception in mhap-hip: %s (code %d)\n", mhap_last_error(R.h), rc); return 1; }
       R.trim_seconds += now() - tt;
     }
-    if (R.graph) {   // the kept records into the string graph (queued: nothing waits)
+    if (R.graph && !R.repeat) {   // the kept records into the string graph (queued: nothing waits)
       const double tg = now();
       rc = mhap_graph_add(R.graph, R.out.data(), k);
       if (rc != MHAP_OK) { fprintf(stderr, "Exception in mhap-hip: %s (code %d)\n", mhap_last_error(R.h), rc); return 1; }
       R.graph_seconds += now() - tg;
     }
-    if (R.keep_records) R.kept_records.insert(R.kept_records.end(), for_trim, for_trim + k);   // (with --trim the graph takes what the trimming took)
+    if (R.keep_records && !R.repeat) R.kept_records.insert(R.kept_records.end(), for_trim, for_trim + k);   // (with --trim the graph takes what the trimming took)
     r = R.out.data(); n = k;
   }
   if (s->realign && s->realign->paf) {   // one PAF line per kept record; the names are columns 1 and 2 of the 12-column line
@@ -452,6 +464,12 @@ int main(int argc, char** argv) {
   o.add("--trim-end-clip", "[int] With --trim, the bases every aligned interval is shrunk by at both ends.", "500");
   o.add("--trim-min-span", "[int] With --trim, the shortest aligned interval that counts.", "2000");
   o.add("--trim-penalty", "[int] With --trim, every overlap is first cut to the best stretch of its alignment under +1 per match and this cost per error column, so that an overlap the aligner ran through a chimeric junction ends there. 0) overlaps as realigned.", "2");
+  o.add("--repeat-filter", "With --realign: mark the repeats of every read of -s on the GPU from the pile-up of the realigned overlaps, each cut to the best stretch of its alignment (--trim-penalty), and set aside the overlaps that lie in nothing but repeat on either read: they reach neither --trim nor --gfa. The overlaps printed, --correct and --realign-paf stay on all overlaps. A repeat of two copies at ordinary depth is not reliably found. Self overlaps only (no -q), one GPU.", "false", true);
+  o.add("--repeat-factor", "[int] With --repeat-filter, a position is repeat when its depth exceeds the typical depth times this, in percent.", "200");
+  o.add("--repeat-max-cov", "[int] With --repeat-filter, the depth above which a position is repeat. 0) derive it from the typical depth.", "0");
+  o.add("--repeat-min-run", "[int] With --repeat-filter, the shortest stretch of repeat positions that is marked.", "500");
+  o.add("--repeat-min-unique", "[int] With --repeat-filter, the aligned bases outside repeats an overlap needs on both reads.", "500");
+  o.add("--repeat-table", "With --repeat-filter, write one line per repeat interval to this file: read_id begin end.", "");
   o.add("--trim-fasta", "With --trim, write the trimmed reads to this FASTA file; deleted reads are left out.", "");
   o.add("--trim-table", "With --trim, write one line per read to this file: id length begin end runs covered flags.", "");
   if (!o.parse(argc, argv)) return 0;
@@ -528,8 +546,21 @@ int main(int argc, char** argv) {
     if (o.i("--gfa-max-hang") < 0 || o.i("--gfa-min-overlap") < 0 || o.i("--gfa-fuzz") < 0) bad("The values of --gfa-max-hang, --gfa-min-overlap and --gfa-fuzz must be >=0.");
   }
   const bool trim = o.b("--trim");
-  for (const char* n : {"--trim-min-cov", "--trim-end-clip", "--trim-min-span", "--trim-penalty", "--trim-fasta", "--trim-table"})   // refused before a handle exists
+  const bool repeat = o.b("--repeat-filter");
+  for (const char* n : {"--trim-min-cov", "--trim-end-clip", "--trim-min-span", "--trim-fasta", "--trim-table"})   // refused before a handle exists
     if (o.isset(n) && !trim) bad((std::string(n) + " belongs to --trim: give --trim too.").c_str());
+  if (o.isset("--trim-penalty") && !trim && !repeat) bad("--trim-penalty belongs to --trim: give --trim too.");
+  for (const char* n : {"--repeat-factor", "--repeat-max-cov", "--repeat-min-run", "--repeat-min-unique", "--repeat-table"})
+    if (o.isset(n) && !repeat) bad((std::string(n) + " belongs to --repeat-filter: give --repeat-filter too.").c_str());
+  if (repeat) {   // refused wherever --trim is, before a handle exists
+    if (!o.b("--realign")) bad("--repeat-filter piles up the alignments of --realign: give --realign too.");
+    if (!o.s("-q").empty()) bad("--repeat-filter marks the reads of -s from their overlaps with each other: it takes no -q.");
+    if (ends_with(o.s("-s"), ".dat")) bad("--repeat-filter needs the overlaps realigned on the reads' bases: give FASTA files, not .dat sketches.");
+    if (devs.size() > 1) bad("--repeat-filter runs on one GPU: give one device (--gpus 1).");
+    if (o.i("--repeat-factor") < 100 || o.i("--repeat-max-cov") < 0 || o.i("--repeat-min-run") < 1 || o.i("--repeat-min-unique") < 0 || o.i("--trim-penalty") < 0)
+      bad("The value of --repeat-factor must be >=100, that of --repeat-min-run >=1 and those of --repeat-max-cov, --repeat-min-unique and --trim-penalty >=0.");
+    if (o.isset("--repeat-table") && o.s("--repeat-table").empty()) bad("--repeat-table needs the name of the file to write.");
+  }
   if (trim) {   // refused before a handle exists
     if (!o.b("--realign")) bad("--trim piles up the alignments of --realign: give --realign too.");
     if (!o.s("-q").empty()) bad("--trim trims the reads of -s from their overlaps with each other: it takes no -q.");
@@ -612,6 +643,8 @@ int main(int argc, char** argv) {
   mhap_graph_params gp;
   mhap_graph_default_params(&gp);
   gp.max_hang = o.i("--gfa-max-hang"); gp.min_ovlp = o.i("--gfa-min-overlap"); gp.fuzz = o.i("--gfa-fuzz");
+  mhap_trim_params tp;
+  mhap_trim_default_params(&tp);
   if (realign) {
     RA.h = E.h; RA.band = o.i("--realign-band"); RA.min_identity = o.d("--realign-min-identity"); RA.paf = o.b("--realign-paf");
     for (const std::string& sf : list_files(o.s("-s"))) {   // (ids as the index assigned them: FastaData's running count)
@@ -623,13 +656,15 @@ int main(int argc, char** argv) {
     sink.realign = &RA;
     if (correct) chk(E.h, mhap_correct_begin(E.h, RA.bases.data(), (int64_t)RA.bases.size(), RA.ids.data(), RA.offsets.data(), RA.lengths.data(),
                                              (int64_t)RA.ids.size(), &RA.correct));
-    mhap_trim_params tp;
-    mhap_trim_default_params(&tp);
-    if (trim) {
-      tp.min_cov = o.i("--trim-min-cov"); tp.end_clip = o.i("--trim-end-clip"); tp.min_span = o.i("--trim-min-span");
-      chk(E.h, mhap_trim_begin(E.h, RA.ids.data(), RA.lengths.data(), (int64_t)RA.ids.size(), &tp, &RA.trim));
-      RA.trim_penalty = o.i("--trim-penalty");
-    }
+    if (trim) { tp.min_cov = o.i("--trim-min-cov"); tp.end_clip = o.i("--trim-end-clip"); tp.min_span = o.i("--trim-min-span"); }
+    if (trim || repeat) RA.trim_penalty = o.i("--trim-penalty");
+    if (repeat) {   // (with --trim too, the trimming begins once the repeat stage has freed its device arrays)
+      mhap_repeat_params rp;
+      mhap_repeat_default_params(&rp);
+      rp.factor_pct = o.i("--repeat-factor"); rp.max_cov = o.i("--repeat-max-cov"); rp.min_run = o.i("--repeat-min-run"); rp.min_unique = o.i("--repeat-min-unique");
+      chk(E.h, mhap_repeat_begin(E.h, RA.ids.data(), RA.lengths.data(), (int64_t)RA.ids.size(), &rp, &RA.repeat));
+      RA.hold_plain = gfa && !trim;
+    } else if (trim) chk(E.h, mhap_trim_begin(E.h, RA.ids.data(), RA.lengths.data(), (int64_t)RA.ids.size(), &tp, &RA.trim));
     if (gfa && trim) RA.keep_records = true;   // the graph begins after the trimming, on the trimmed reads: the records wait for it
     else if (gfa) {
       chk(E.h, mhap_graph_begin(E.h, RA.ids.data(), RA.lengths.data(), (int64_t)RA.ids.size(), &gp, &RA.graph));
@@ -716,6 +751,51 @@ int main(int argc, char** argv) {
     fprintf(stderr, "Corrected %lld reads: %lld bases in, %lld out; %lld substitutions, %lld deletions, %lld insertions, %lld positions of low coverage; skipped_views = %lld\n",
             (long long)nr, tot[0], tot[1], tot[2], tot[3], tot[4], tot[5], (long long)skipped);
     fprintf(stderr, "Time (s) to vote and correct: %g\n", RA.correct_seconds);
+  }
+  if (RA.repeat) {   // the intervals of every read and the judgement of every held record, after the last batch; trimming and graph take the survivors
+    const double tr = now();
+    const int64_t nr = (int64_t)RA.ids.size(), nk = (int64_t)RA.held_refined.size();
+    int64_t rcn[MHAP_REPEAT_COUNTS];
+    chk(E.h, mhap_repeat_finish(RA.repeat, rcn));
+    if (o.isset("--repeat-table")) {
+      std::vector<int32_t> rrows((size_t)std::max<int64_t>(nr, 1) * 4), riv((size_t)std::max<int64_t>(rcn[3], 1) * 2);
+      std::vector<uint8_t> rflags((size_t)std::max<int64_t>(nr, 1));
+      std::vector<int64_t> roff((size_t)nr + 1);
+      chk(E.h, mhap_repeat_copy(RA.repeat, rrows.data(), rflags.data(), roff.data(), riv.data()));
+      FILE* f = fopen(o.s("--repeat-table").c_str(), "wb");
+      if (!f) die("cannot write " + o.s("--repeat-table"));
+      for (int64_t r = 0; r < nr; r++)
+        for (int64_t i = roff[(size_t)r]; i < roff[(size_t)r + 1]; i++)
+          fprintf(f, "%lld\t%d\t%d\n", (long long)RA.ids[(size_t)r], riv[(size_t)i * 2], riv[(size_t)i * 2 + 1]);
+      if (fclose(f) != 0) die("cannot write " + o.s("--repeat-table"));
+    }
+    std::vector<uint8_t> keep((size_t)std::max<int64_t>(nk, 1));
+    std::vector<int32_t> unique((size_t)std::max<int64_t>(nk, 1) * 2);
+    chk(E.h, mhap_repeat_apply(RA.repeat, RA.held_refined.data(), nk, keep.data(), unique.data()));
+    mhap_repeat_free(RA.repeat);   // (its device arrays go before the trimming allocates its own)
+    RA.repeat = nullptr;
+    std::vector<mhap_record>& survivors = RA.hold_plain ? RA.held_plain : RA.held_refined;   // the graph: as realigned; the trimming: refined
+    size_t w = 0;
+    for (int64_t q = 0; q < nk; q++) if (keep[(size_t)q]) survivors[w++] = survivors[(size_t)q];
+    survivors.resize(w);
+    RA.repeat_seconds += now() - tr;
+    fprintf(stderr, "Repeats: %lld reads, %lld with a repeat, %lld repeat throughout; %lld intervals, %lld of %lld bases; %lld eligible overlaps, depth %lld, threshold %lld\n",
+            (long long)rcn[0], (long long)rcn[1], (long long)rcn[2], (long long)rcn[3], (long long)rcn[4], (long long)rcn[5], (long long)rcn[6],
+            (long long)rcn[7], (long long)rcn[8]);
+    fprintf(stderr, "Time (s) to mark repeats: %g (%lld of %lld overlaps set aside)\n", RA.repeat_seconds, (long long)(nk - (int64_t)w), (long long)nk);
+    if (trim) {
+      const double tt = now();
+      chk(E.h, mhap_trim_begin(E.h, RA.ids.data(), RA.lengths.data(), nr, &tp, &RA.trim));
+      chk(E.h, mhap_trim_add(RA.trim, survivors.data(), (int64_t)w));
+      RA.trim_seconds += now() - tt;
+    } else if (RA.graph) {
+      const double tg = now();
+      chk(E.h, mhap_graph_add(RA.graph, survivors.data(), (int64_t)w));
+      RA.graph_seconds += now() - tg;
+    }
+    if (RA.keep_records) RA.kept_records.swap(survivors);
+    std::vector<mhap_record>().swap(RA.held_refined);
+    std::vector<mhap_record>().swap(RA.held_plain);
   }
   if (RA.trim) {   // every read's clear range, after the last batch has been piled up; with --gfa the graph begins here, on the trimmed reads
     const double tt = now();

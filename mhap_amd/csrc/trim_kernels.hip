@@ -5,6 +5,7 @@
 //
 // begin: read r owns lengths[r] + 1 int32 slots of one difference array, at an offset rounded up to four slots (so that a read's
 //        slots begin on a 16-byte word); the array is zeroed once.
+// The difference array, the add and the tile's coverage scan are pileup_common.hpp's, shared with the repeat marking.
 // add:   the host finds every record's two reads (and refuses the call before anything is queued), packs the record into 32 bytes
 //        (GItem) and queues one upload and add_kernel, one lane per record: +1 at an interval's begin, -1 at its end, up to four
 //        atomicAdd(int32).  Integer adds commute, so the array is a function of the multiset of records.  Nothing waits; the items'
@@ -23,15 +24,13 @@
 //        ends, columns and errors of the best stretch; the runs of a call are uploaded for it and freed behind it.
 #include <hip/hip_runtime.h>
 
-#include <deque>
-#include <numeric>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "device_common.hpp"
 #include "graph_class.hpp"
 #include "mhap_internal.hpp"
+#include "pileup_common.hpp"
 #include "trim_common.hpp"
 
 namespace mhap {
@@ -40,31 +39,8 @@ namespace {
 // counts: reads, deleted, cut5, cut3, gapped, bases in, bases kept, eligible records
 enum { TC_READS = 0, TC_DELETED, TC_CUT5, TC_CUT3, TC_GAPPED, TC_BASES_IN, TC_BASES_KEPT, TC_ELIGIBLE };
 static_assert(TC_ELIGIBLE + 1 == MHAP_TRIM_COUNTS, "the counts of the header");
-enum { TRIM_T = 256, TRIM_WAVES = TRIM_T / 64, TRIM_LOADS = 4 };
-static_assert(TRIM_T * TRIM_LOADS * 4 == MHAP_TRIM_TILE, "a tile is four 16-byte loads per lane");
-
-typedef unsigned long long u64;
-
-__global__ __launch_bounds__(256) void add_kernel(const int4* __restrict__ items, int64_t n, const int32_t* __restrict__ lengths,
-                                                  const int64_t* __restrict__ off, TParams P, int32_t* __restrict__ diff,
-                                                  u64* __restrict__ eligible) {
-  const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  bool el = false;
-  if (q < n) {
-    const int4 w0 = items[2 * q], w1 = items[2 * q + 1];
-    const int32_t A = w0.x, B = w0.y >> 1;
-    el = trim_eligible(A, B, __hiloint2double(w1.w, w1.z), P);
-    if (el) {
-      int64_t s, e;   // (the host has refused ends outside the read; the bounds are looked at again where the store is)
-      if (trim_interval(w0.z, w0.w, P, s, e) && s >= 0 && e <= lengths[A]) { atomicAdd(diff + off[A] + s, 1); atomicAdd(diff + off[A] + e, -1); }
-      if (trim_interval(w1.x, w1.y, P, s, e) && s >= 0 && e <= lengths[B]) { atomicAdd(diff + off[B] + s, 1); atomicAdd(diff + off[B] + e, -1); }
-    }
-  }
-  const u64 m = __ballot(el);   // one add per wave
-  if ((threadIdx.x & 63) == 0 && m) atomicAdd(eligible, (u64)__popcll(m));
-}
-
-__device__ inline int32_t quad(const int4& d, int k) { return k == 0 ? d.x : k == 1 ? d.y : k == 2 ? d.z : d.w; }
+enum { TRIM_T = PILE_T, TRIM_WAVES = PILE_WAVES, TRIM_LOADS = PILE_LOADS };
+static_assert(PILE_TILE == MHAP_TRIM_TILE, "a tile is four 16-byte loads per lane");
 
 __global__ __launch_bounds__(TRIM_T) void run_kernel(const int32_t* __restrict__ diff, const int64_t* __restrict__ off,
                                                      const int32_t* __restrict__ lengths, const int32_t* __restrict__ order, TParams P,
@@ -79,42 +55,14 @@ __global__ __launch_bounds__(TRIM_T) void run_kernel(const int32_t* __restrict__
   u64 best = 0;   // (length << 32) | (2^32 - 1 - begin): the longest run, the first of equal ones
   for (int64_t g0 = 0; g0 < groups; g0 += TRIM_T * TRIM_LOADS) {
     int4 d[TRIM_LOADS];
-    int32_t tot[TRIM_LOADS], inc[TRIM_LOADS], pre[TRIM_LOADS];
-#pragma unroll
-    for (int j = 0; j < TRIM_LOADS; j++) {
-      const int64_t g = g0 + j * TRIM_T + tid;
-      d[j] = g < groups ? base[g] : make_int4(0, 0, 0, 0);
-      inc[j] = tot[j] = d[j].x + d[j].y + d[j].z + d[j].w;
-    }
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-#pragma unroll
-      for (int j = 0; j < TRIM_LOADS; j++) {
-        const int32_t u = __shfl_up(inc[j], s);
-        if (lane >= s) inc[j] += u;
-      }
-    }
-    if (lane == 63) {
-#pragma unroll
-      for (int j = 0; j < TRIM_LOADS; j++) ws[j][wave] = inc[j];
-    }
-    __syncthreads();   // (wm of the tile before has been read by everyone who comes here)
-    int32_t acc = carry;
-#pragma unroll
-    for (int j = 0; j < TRIM_LOADS; j++) {
-#pragma unroll
-      for (int w = 0; w < TRIM_WAVES; w++) {
-        if (w == wave) pre[j] = acc;
-        acc += ws[j][w];
-      }
-    }
-    carry = acc;
+    int32_t c0[TRIM_LOADS];
+    pile_coverage_tile(base, groups, g0, tid, lane, wave, ws, carry, d, c0);   // (its barrier: wm of the tile before has been read by everyone who comes here)
     // pass 1: coverage, the counts, and the latest first position of a run in each of the lane's groups
     int32_t m[TRIM_LOADS], minc[TRIM_LOADS], mpre[TRIM_LOADS];
 #pragma unroll
     for (int j = 0; j < TRIM_LOADS; j++) {
       const int32_t p0 = (int32_t)((g0 + j * TRIM_T + tid) << 2);
-      int32_t c = pre[j] + inc[j] - tot[j];
+      int32_t c = c0[j];
       m[j] = -1;
 #pragma unroll
       for (int k = 0; k < 4; k++) {
@@ -155,7 +103,7 @@ __global__ __launch_bounds__(TRIM_T) void run_kernel(const int32_t* __restrict__
       const int32_t p0 = (int32_t)((g0 + j * TRIM_T + tid) << 2);
       const int32_t left = __shfl_up(minc[j], 1);
       int32_t cur = lane > 0 && left > mpre[j] ? left : mpre[j];
-      int32_t c = pre[j] + inc[j] - tot[j];
+      int32_t c = c0[j];
 #pragma unroll
       for (int k = 0; k < 4; k++) {
         const int32_t before = c;
@@ -236,70 +184,24 @@ __global__ __launch_bounds__(256) void refine_kernel(const RItem* __restrict__ i
   out[2 * q + 1] = make_int4((int32_t)r.columns, (int32_t)r.errors, 1, 0);
 }
 
-unsigned blocks256(int64_t n) { return (unsigned)((n + 255) / 256); }
-
 }  // namespace
 }  // namespace mhap
 
 using namespace mhap;
 
-struct mhap_trim_session {
-  mhap_handle* h = nullptr;
+struct mhap_trim_session : Pile {
   TParams P{};
-  int64_t n_reads = 0, n_records = 0, bases_in = 0, n_slots = 0;
   bool finished = false;
-  std::vector<int64_t> ids, slot_off;                     // slot_off[r]: read r's first slot of the difference array
-  std::vector<int32_t> lengths;
-  std::unordered_map<int64_t, int32_t> by_id;
-  struct Pending { std::vector<GItem> host; hipEvent_t ev = nullptr; };   // packed records an upload may still be reading
-  std::deque<Pending> pending;
-  DevBuf d_lengths, d_off, d_order, diff, rows, flags, counts, items, applied;   // counts: MHAP_TRIM_COUNTS x uint64
-  void reap(bool all) {
-    while (!pending.empty() && (all || hipEventQuery(pending.front().ev) == hipSuccess)) {
-      (void)hipEventDestroy(pending.front().ev);
-      pending.pop_front();
-    }
-    (void)hipGetLastError();   // (an event that has not passed is no error of the call that looked)
-  }
+  DevBuf rows, flags, counts, applied;   // counts: MHAP_TRIM_COUNTS x uint64
   void release() {
-    for (DevBuf* b : {&d_lengths, &d_off, &d_order, &diff, &rows, &flags, &counts, &items, &applied}) b->release();
+    release_pile();
+    for (DevBuf* b : {&rows, &flags, &counts, &applied}) b->release();
   }
 };
 
 namespace {
 
 bool params_ok(const mhap_trim_params& p) { return p.min_cov >= 1 && p.end_clip >= 0 && p.min_span >= 0; }
-
-// the records of a call as items; a refused record leaves its message in err
-bool pack_records(const mhap_trim_session* s, const char* who, const mhap_record* recs, int64_t n, std::vector<GItem>& items, std::string& err) {
-  items.resize((size_t)n);
-  for (int64_t q = 0; q < n; q++) {
-    const mhap_record& r = recs[q];
-    int32_t idx[2];
-    const int64_t ids[2] = {r.from_id, r.to_id};
-    const int32_t lens[2] = {r.alen, r.blen}, x1[2] = {r.a1, r.b1}, x2[2] = {r.a2, r.b2};
-    for (int f = 0; f < 2; f++) {
-      const auto it = s->by_id.find(ids[f]);
-      if (it == s->by_id.end()) {
-        err = std::string(who) + ": record " + std::to_string(q) + " names read " + std::to_string(ids[f]) + ", which is not among the reads";
-        return false;
-      }
-      idx[f] = it->second;
-      if (s->lengths[(size_t)idx[f]] != lens[f]) {
-        err = std::string(who) + ": record " + std::to_string(q) + " gives read " + std::to_string(ids[f]) + " the length " + std::to_string(lens[f]) +
-              ", the reads say " + std::to_string(s->lengths[(size_t)idx[f]]);
-        return false;
-      }
-      if (r.score != 0.0 && (x1[f] < 0 || x2[f] < x1[f] || x2[f] >= lens[f])) {
-        err = std::string(who) + ": record " + std::to_string(q) + " aligns " + std::to_string(x1[f]) + " .. " + std::to_string(x2[f]) + " of read " +
-              std::to_string(ids[f]) + ", which has " + std::to_string(lens[f]) + " bases";
-        return false;
-      }
-    }
-    items[(size_t)q] = GItem{idx[0], 2 * idx[1] + (r.to_rc != 0 ? 1 : 0), r.a1, r.a2, r.b1, r.b2, r.score};
-  }
-  return true;
-}
 
 }  // namespace
 
@@ -314,47 +216,19 @@ extern "C" int mhap_trim_begin(mhap_handle* h, const int64_t* read_ids, const in
   if (session) *session = nullptr;
   if (!h) return MHAP_E_INVALID;
   HandleView v = handle_view(h);
-  if (!session || n_reads < 0 || (n_reads > 0 && (!read_ids || !lengths))) { *v.err = std::string(who) + ": null or negative argument"; return MHAP_E_INVALID; }
-  if (n_reads >= ((int64_t)1 << 30)) { *v.err = std::string(who) + ": 2^30 reads or more"; return MHAP_E_INVALID; }
+  if (!Pile::table_ok(v, who, session, read_ids, lengths, n_reads)) return MHAP_E_INVALID;
   mhap_trim_params p;
   mhap_trim_default_params(&p);
   if (params) p = *params;
   if (!params_ok(p)) { *v.err = std::string(who) + ": min_cov must be >= 1, end_clip and min_span >= 0"; return MHAP_E_INVALID; }
-  for (int64_t i = 0; i < n_reads; i++)
-    if (lengths[i] < 0 || lengths[i] > INT32_MAX - 8) {
-      *v.err = std::string(who) + ": read " + std::to_string(i) + " has a negative length or one above 2^31 - 9";
-      return MHAP_E_INVALID;
-    }
   mhap_trim_session* s = new mhap_trim_session();
-  s->h = h; s->n_reads = n_reads;
   s->P = TParams{p.min_cov, p.end_clip, p.min_span, p.min_identity};
-  s->ids.assign(read_ids, read_ids + n_reads);
-  s->lengths.assign(lengths, lengths + n_reads);
-  s->by_id.reserve((size_t)n_reads * 2);
-  s->slot_off.resize((size_t)n_reads + 1);
-  for (int64_t i = 0; i < n_reads; i++) {
-    s->by_id.emplace(read_ids[i], (int32_t)i);   // (the first read of an id wins, as in mhap_realign_plan)
-    s->slot_off[(size_t)i] = s->n_slots;
-    s->n_slots += ((int64_t)lengths[i] + 4) & ~(int64_t)3;
-    s->bases_in += lengths[i];
-  }
-  s->slot_off[(size_t)n_reads] = s->n_slots;
-  std::vector<int32_t> order((size_t)n_reads);   // longest reads first: the long workgroups start early
-  std::iota(order.begin(), order.end(), 0);
-  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return lengths[a] > lengths[b]; });
   (void)hipSetDevice(v.device);
-  const size_t nr = (size_t)std::max<int64_t>(n_reads, 1), db = 4 * (size_t)std::max<int64_t>(s->n_slots, 4);
-  hipError_t e = s->d_lengths.ensure(4 * nr);
-  if (e == hipSuccess) e = s->d_order.ensure(4 * nr);
-  if (e == hipSuccess) e = s->d_off.ensure(8 * (nr + 1));
+  const size_t nr = (size_t)std::max<int64_t>(n_reads, 1);
+  hipError_t e = s->begin_pile(v, h, read_ids, lengths, n_reads);
   if (e == hipSuccess) e = s->rows.ensure(16 * nr);
   if (e == hipSuccess) e = s->flags.ensure(nr);
   if (e == hipSuccess) e = s->counts.ensure(8 * MHAP_TRIM_COUNTS);
-  if (e == hipSuccess) e = s->diff.ensure(db);
-  if (e == hipSuccess && n_reads > 0) e = hipMemcpyAsync(s->d_lengths.p, s->lengths.data(), 4 * (size_t)n_reads, hipMemcpyHostToDevice, v.stream);
-  if (e == hipSuccess && n_reads > 0) e = hipMemcpyAsync(s->d_order.p, order.data(), 4 * (size_t)n_reads, hipMemcpyHostToDevice, v.stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(s->d_off.p, s->slot_off.data(), 8 * ((size_t)n_reads + 1), hipMemcpyHostToDevice, v.stream);
-  if (e == hipSuccess) e = hipMemsetAsync(s->diff.p, 0, db, v.stream);
   if (e == hipSuccess) e = hipMemsetAsync(s->counts.p, 0, 8 * MHAP_TRIM_COUNTS, v.stream);
   if (e == hipSuccess) e = hipStreamSynchronize(v.stream);
   if (e != hipSuccess) {
@@ -369,35 +243,7 @@ extern "C" int mhap_trim_begin(mhap_handle* h, const int64_t* read_ids, const in
 extern "C" int mhap_trim_add(mhap_trim_session* s, const mhap_record* recs, int64_t n) {
   const char* who = "mhap_trim_add";
   if (!s) return MHAP_E_INVALID;
-  HandleView v = handle_view(s->h);
-  if (n < 0 || (n > 0 && !recs)) { *v.err = std::string(who) + ": null or negative argument"; return MHAP_E_INVALID; }
-  if (n > INT32_MAX) { *v.err = std::string(who) + ": more than 2^31 - 1 records in one call"; return MHAP_E_INVALID; }
-  s->reap(false);
-  if (n == 0) return MHAP_OK;
-  mhap_trim_session::Pending p;
-  if (!pack_records(s, who, recs, n, p.host, *v.err)) return MHAP_E_INVALID;
-  (void)hipSetDevice(v.device);
-  hipError_t e = s->items.ensure(sizeof(GItem) * (size_t)n);   // (a larger buffer frees the old one, which waits for the device)
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&p.ev, hipEventDisableTiming);
-  if (e != hipSuccess) return hip_fail(v, who, "hipMalloc of the records", e);
-  e = hipMemcpyAsync(s->items.p, p.host.data(), sizeof(GItem) * (size_t)n, hipMemcpyHostToDevice, v.stream);
-  if (e != hipSuccess) {   // nothing was queued behind the upload: nothing of this call stays
-    (void)hipStreamSynchronize(v.stream);
-    (void)hipEventDestroy(p.ev);
-    return hip_fail(v, who, "upload", e);
-  }
-  hipLaunchKernelGGL(add_kernel, dim3(blocks256(n)), dim3(256), 0, v.stream, s->items.as<int4>(), n, s->d_lengths.as<int32_t>(),
-                     s->d_off.as<int64_t>(), s->P, s->diff.as<int32_t>(), s->counts.as<u64>() + TC_ELIGIBLE);
-  e = hipGetLastError();
-  if (e == hipSuccess) e = hipEventRecord(p.ev, v.stream);
-  if (e != hipSuccess) {
-    (void)hipStreamSynchronize(v.stream);
-    (void)hipEventDestroy(p.ev);
-    return hip_fail(v, who, "launch", e);
-  }
-  s->pending.push_back(std::move(p));
-  s->n_records += n;
-  return MHAP_OK;
+  return s->add_records(who, recs, n, s->P, s->counts.as<u64>() + TC_ELIGIBLE);
 }
 
 extern "C" int mhap_trim_finish(mhap_trim_session* s, int64_t* counts) {
@@ -427,19 +273,6 @@ extern "C" int mhap_trim_finish(mhap_trim_session* s, int64_t* counts) {
   return MHAP_OK;
 }
 
-namespace {
-
-int trim_download(mhap_trim_session* s, const char* who, void* dst, const void* src, size_t bytes) {
-  HandleView v = handle_view(s->h);
-  (void)hipSetDevice(v.device);
-  hipError_t e;
-  if ((e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return hip_fail(v, who, "download", e);
-  if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return hip_fail(v, who, "download", e);
-  return MHAP_OK;
-}
-
-}  // namespace
-
 extern "C" int mhap_trim_copy(mhap_trim_session* s, int32_t* rows, uint8_t* flags) {
   const char* who = "mhap_trim_copy";
   if (!s) return MHAP_E_INVALID;
@@ -447,8 +280,8 @@ extern "C" int mhap_trim_copy(mhap_trim_session* s, int32_t* rows, uint8_t* flag
   if (!s->finished) { *v.err = std::string(who) + ": no mhap_trim_finish has completed"; return MHAP_E_INVALID; }
   if (s->n_reads == 0) return MHAP_OK;
   if (!rows || !flags) { *v.err = std::string(who) + ": null argument"; return MHAP_E_INVALID; }
-  const int rc = trim_download(s, who, rows, s->rows.p, 16 * (size_t)s->n_reads);
-  return rc != MHAP_OK ? rc : trim_download(s, who, flags, s->flags.p, (size_t)s->n_reads);
+  const int rc = s->download(who, rows, s->rows.p, 16 * (size_t)s->n_reads);
+  return rc != MHAP_OK ? rc : s->download(who, flags, s->flags.p, (size_t)s->n_reads);
 }
 
 extern "C" int mhap_trim_coverage(mhap_trim_session* s, int64_t read_index, int32_t* cov) {
@@ -459,7 +292,7 @@ extern "C" int mhap_trim_coverage(mhap_trim_session* s, int64_t read_index, int3
   const int64_t len = s->lengths[(size_t)read_index];
   if (len == 0) return MHAP_OK;
   if (!cov) { *v.err = std::string(who) + ": null argument"; return MHAP_E_INVALID; }
-  const int rc = trim_download(s, who, cov, s->diff.as<int32_t>() + s->slot_off[(size_t)read_index], 4 * (size_t)len);
+  const int rc = s->download(who, cov, s->diff.as<int32_t>() + s->slot_off[(size_t)read_index], 4 * (size_t)len);
   if (rc != MHAP_OK) return rc;
   for (int64_t p = 1; p < len; p++) cov[p] += cov[p - 1];   // the differences as the add kernel left them, summed here
   return MHAP_OK;
@@ -474,15 +307,10 @@ extern "C" int mhap_trim_apply(mhap_trim_session* s, const mhap_record* in, int6
   if (n > INT32_MAX) { *v.err = std::string(who) + ": more than 2^31 - 1 records in one call"; return MHAP_E_INVALID; }
   if (n == 0) return MHAP_OK;
   std::vector<GItem> items;
-  if (!pack_records(s, who, in, n, items, *v.err)) return MHAP_E_INVALID;
-  (void)hipSetDevice(v.device);
+  int rc = MHAP_OK;
+  if (!s->upload_for_apply(v, who, in, n, items, rc)) return rc;
   hipError_t e;
-  if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return hip_fail(v, who, "the stream", e);   // (an add may still read the items' buffer)
-  s->reap(true);
-  if ((e = s->items.ensure(sizeof(GItem) * (size_t)n)) != hipSuccess || (e = s->applied.ensure(32 * (size_t)n)) != hipSuccess)
-    return hip_fail(v, who, "hipMalloc of the records", e);
-  if ((e = hipMemcpyAsync(s->items.p, items.data(), sizeof(GItem) * (size_t)n, hipMemcpyHostToDevice, v.stream)) != hipSuccess)
-    return hip_fail(v, who, "upload", e);
+  if ((e = s->applied.ensure(32 * (size_t)n)) != hipSuccess) { (void)hipStreamSynchronize(v.stream); return hip_fail(v, who, "hipMalloc of the records", e); }
   hipLaunchKernelGGL(apply_kernel, dim3(blocks256(n)), dim3(256), 0, v.stream, s->items.as<int4>(), n, s->d_lengths.as<int32_t>(),
                      s->rows.as<int32_t>(), s->flags.as<uint8_t>(), s->P, s->applied.as<int4>());
   if ((e = hipGetLastError()) != hipSuccess) { (void)hipStreamSynchronize(v.stream); return hip_fail(v, who, "launch", e); }

@@ -1,6 +1,6 @@
 """The string graph of a file of MHAP overlaps, on the GPU: `python -m mhap_amd.graph overlaps.txt reads.fasta [--band W]
 [--min-identity X] [--max-hang N] [--int-frac F] [--min-overlap N] [--fuzz N] -o out.gfa [--unitigs utg.gfa] [--clean [--tip-reads N]
-[--bubble-bases N] [--clean-rounds N]] [--consensus [--consensus-fasta F] [--consensus-min-cov N]]` writes what `mhap-hip --realign
+[--bubble-bases N] [--clean-rounds N]] [--consensus [--consensus-fasta F] [--consensus-min-cov N]] [--repeat-filter ...]` writes what `mhap-hip --realign
 --gfa out.gfa [--gfa-unitigs utg.gfa] [--gfa-clean ...]` writes for the same overlaps.
 
 The overlaps are parsed and realigned as `python -m mhap_amd.realign` does; the records that tool would drop (no alignment, or an
@@ -19,13 +19,16 @@ writes them as FASTA.
 With --trim [--trim-min-cov N] [--trim-end-clip N] [--trim-min-span N] [--trim-penalty N] the reads are trimmed and chimeras split on the GPU first
 ("read trimming" in the same header; `python -m mhap_amd.trim` writes the trimmed reads themselves): every output is then built on
 the surviving reads, their trimmed lengths and the overlaps rewritten onto them.
-Not done: bubbles that are not simple, a second trimming round.  One line on stderr gives the counts (one more with --trim, in
-front; one more with --clean, one more with --unitigs, one more with --consensus).
+With --repeat-filter [--repeat-factor PCT] [--repeat-max-cov N] [--repeat-min-run N] [--repeat-min-unique N] repeats are marked from the
+overlap pile-up first ("repeat marking" in the same header; `python -m mhap_amd.repeats` writes the intervals) and the overlaps that
+lie in nothing but repeat reach neither the trimming nor the graph; a two-copy repeat at ordinary depth is not reliably found.
+Not done: bubbles that are not simple, a second trimming round.  One line on stderr gives the counts (one more with --repeat-filter
+and one more with --trim, in front; one more with --clean, one more with --unitigs, one more with --consensus).
 """
 import argparse
 import sys
 
-from . import api
+from . import api, repeats
 from .realign import kept_rows, read_overlaps
 
 BATCH = 1 << 16   # records realigned and classed per call
@@ -44,7 +47,7 @@ def consensus_fasta(seqs, circular):
 
 
 def graph_overlaps(recs, fasta, band=0, max_shift=0.2, min_identity=0.0, device=0, batch=BATCH, unitigs=False, clean=None, consensus=None,
-                   trim=None, **params):
+                   trim=None, repeat=None, **params):
     """Realign `recs` in batches and build the graph: (gfa text, arcs, counts, contained); with unitigs=True two more: the GFA text
     of the unitig graph and the dict of GraphSession.unitigs().  clean: None, or a dict of GraphSession.clean's parameters: the graph
     is cleaned first, both texts and the dict are those of the cleaned graph, and the dict of CLEAN_COUNTS comes last.
@@ -53,20 +56,31 @@ def graph_overlaps(recs, fasta, band=0, max_shift=0.2, min_identity=0.0, device=
     consensus_seqs.
     trim: None, or a dict of TrimSession's parameters (min_cov, end_clip, min_span): the reads are trimmed first ("read trimming" in
     the same header) and everything above is built on the surviving reads, their trimmed lengths and the records rewritten onto
-    them; the dict of TRIM_COUNTS then comes last of all (key trim_counts of the dict)."""
+    them; the dict of TRIM_COUNTS then comes last of all (key trim_counts of the dict).
+    repeat: None, or a dict of RepeatSession's parameters and `penalty`: every kept record is judged on its refined copy ("repeat
+    marking" in the same header) and the void ones reach neither the trimming nor the graph; without trim the graph takes the
+    survivors as realigned.  The dict of REPEAT_COUNTS then comes behind the trimming's (key repeat_counts of the dict)."""
     with api.MinHashSearch(api.MhapParams(num_hashes=1, ordered_sketch_size=1, max_shift=max_shift, device=device)) as ms:
         tcounts = ()
+        if repeat is not None:
+            repeat = dict(repeat)
+            rpenalty = repeat.pop("penalty", api.TRIM_PENALTY)
         if trim is not None:   # every record is realigned and held, the reads are cut, and the graph sees the rewritten records only
             from .trim import trim_overlaps
-            t = trim_overlaps(recs, fasta, band=band, max_shift=max_shift, min_identity=min_identity, batch=batch, handle=ms, **trim)
-            fasta, tcounts = t["reads"], (t["counts"],)
+            t = trim_overlaps(recs, fasta, band=band, max_shift=max_shift, min_identity=min_identity, batch=batch, handle=ms, repeat=repeat, **trim)
+            fasta, tcounts = t["reads"], (t["counts"],) + (() if repeat is None else (t["repeat"]["counts"],))
             batches = (t["applied"][q0:q0 + batch] for q0 in range(0, len(t["applied"]), batch))
+        elif repeat is not None:
+            from .repeats import repeat_overlaps
+            t = repeat_overlaps(recs, fasta, band=band, max_shift=max_shift, min_identity=min_identity, batch=batch, handle=ms, penalty=rpenalty, **repeat)
+            survivors, tcounts = t["realigned"][t["keep"] != 0], (t["counts"],)
+            batches = (survivors[q0:q0 + batch] for q0 in range(0, len(survivors), batch))
         else:
             batches = (api.realign_records(recs[q0:q0 + batch], fasta, band=band, handle=ms)[0] for q0 in range(0, len(recs), batch))
         with api.GraphSession(fasta.ids, fasta.lengths, handle=ms, **params) as gs:
             kept = []
             for out in batches:
-                if trim is None:
+                if trim is None and repeat is None:
                     out = out[kept_rows(out, min_identity)]
                 gs.add(out)
                 if consensus is not None:
@@ -85,7 +99,7 @@ def graph_overlaps(recs, fasta, band=0, max_shift=0.2, min_identity=0.0, device=
                     ccounts = cs.run()
                     return dict(gfa=text, arcs=arcs, counts=counts, contained=gs.contained(), unitig_gfa=cs.gfa(), unitigs=gs.unitigs_table,
                                 clean_counts=tail[0] if tail else None, consensus_counts=ccounts, consensus_seqs=cs.sequences(),
-                                trim_counts=tcounts[0] if tcounts else None)
+                                trim_counts=tcounts[0] if trim is not None else None, repeat_counts=tcounts[-1] if repeat is not None else None)
             if unitigs:
                 utext = gs.unitig_gfa(fasta)
                 return (text, arcs, counts, gs.contained(), utext, gs.unitigs_table) + tail + tcounts
@@ -118,9 +132,18 @@ def main(argv=None):
     ap.add_argument("--trim-end-clip", type=int, default=500, help="with --trim, the bases every aligned interval is shrunk by at both ends")
     ap.add_argument("--trim-min-span", type=int, default=2000, help="with --trim, the shortest aligned interval that counts")
     ap.add_argument("--trim-penalty", type=int, default=api.TRIM_PENALTY, help="with --trim, the cost of an error column when overlaps are cut to their best stretch; 0: not cut")
+    ap.add_argument("--repeat-filter", action="store_true", help="mark repeats from the overlap pile-up first and drop the overlaps that lie in nothing but repeat")
+    repeats.add_arguments(ap, "repeat-")
     a = ap.parse_args(argv)
-    if (a.trim_min_cov != 3 or a.trim_end_clip != 500 or a.trim_min_span != 2000 or a.trim_penalty != api.TRIM_PENALTY) and not a.trim:
-        ap.error("--trim-min-cov, --trim-end-clip, --trim-min-span and --trim-penalty need --trim")
+    rp, message = repeats.parameters(a, "repeat-")
+    if message:
+        ap.error(message)
+    if rp != {k: v for k, v in api.REPEAT_DEFAULTS.items() if k in rp} and not a.repeat_filter:
+        ap.error("--repeat-factor, --repeat-max-cov, --repeat-min-run and --repeat-min-unique need --repeat-filter")
+    if (a.trim_min_cov != 3 or a.trim_end_clip != 500 or a.trim_min_span != 2000) and not a.trim:
+        ap.error("--trim-min-cov, --trim-end-clip and --trim-min-span need --trim")
+    if a.trim_penalty != api.TRIM_PENALTY and not (a.trim or a.repeat_filter):
+        ap.error("--trim-penalty needs --trim or --repeat-filter")
     if a.trim_min_cov < 1 or a.trim_end_clip < 0 or a.trim_min_span < 0 or a.trim_penalty < 0:
         ap.error("--trim-min-cov must be >= 1, --trim-end-clip, --trim-min-span and --trim-penalty >= 0")
     if a.consensus and not a.unitigs:
@@ -141,8 +164,12 @@ def main(argv=None):
                          clean=dict(tip_reads=a.tip_reads, bubble_bases=a.bubble_bases, max_rounds=a.clean_rounds) if a.clean else None,
                          consensus=dict(min_cov=a.consensus_min_cov) if a.consensus else None,
                          trim=dict(min_cov=a.trim_min_cov, end_clip=a.trim_end_clip, min_span=a.trim_min_span, penalty=a.trim_penalty) if a.trim else None,
+                         repeat=dict(rp, penalty=a.trim_penalty) if a.repeat_filter else None,
                          max_hang=a.max_hang, int_frac_permille=int(round(a.int_frac * 1000)), min_ovlp=a.min_overlap, fuzz=a.fuzz)
-    tcounts = None
+    tcounts = rcounts = None
+    if a.repeat_filter:
+        rcounts = res["repeat_counts"] if a.consensus else res[-1]
+        res = res if a.consensus else res[:-1]
     if a.trim:
         tcounts = res["trim_counts"] if a.consensus else res[-1]
         res = res if a.consensus else res[:-1]
@@ -155,6 +182,8 @@ def main(argv=None):
             fh.write(text)
     else:
         sys.stdout.write(text)
+    if a.repeat_filter:
+        print(api.repeat_counts_line([rcounts[k] for k in api.REPEAT_COUNTS]), file=sys.stderr)
     if a.trim:
         print(api.trim_counts_line([tcounts[k] for k in api.TRIM_COUNTS]), file=sys.stderr)
     print(counts_line(counts), file=sys.stderr)

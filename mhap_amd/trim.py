@@ -1,5 +1,6 @@
 """Trim reads and split chimeras on the GPU from a file of MHAP overlaps: `python -m mhap_amd.trim overlaps.txt reads.fasta [--band W]
-[--min-identity X] [--min-cov N] [--end-clip N] [--min-span N] [--penalty N] -o trimmed.fasta [--table t.tsv] [--records trimmed.txt]` writes what
+[--min-identity X] [--min-cov N] [--end-clip N] [--min-span N] [--penalty N] [--repeat-filter [--repeat-factor PCT] [--repeat-max-cov N]
+[--repeat-min-run N] [--repeat-min-unique N]] -o trimmed.fasta [--table t.tsv] [--records trimmed.txt]` writes what
 `mhap-hip --realign --trim --trim-fasta trimmed.fasta --trim-table t.tsv` writes for the same overlaps.
 
 The overlaps are parsed and realigned as `python -m mhap_amd.realign` does; the records that tool would drop (no alignment, or an
@@ -11,14 +12,16 @@ keeps the longer.  Output is FASTA, one unwrapped line per surviving read: `>ID 
 end=<one past the last> runs=<stretches>`, the ids numeric as the records print them; --table writes one line per read, deleted ones
 included: `id length begin end runs covered flags`, tab-separated; --records writes the overlaps rewritten onto the trimmed reads, the
 void ones left out.  One line on stderr gives the counts.
-Not done: a second round on the trimmed overlaps, selection of best overlaps, any repeat-aware rule.
+With --repeat-filter the refined overlaps that lie in nothing but repeat are set aside first and count as no support (`python -m
+mhap_amd.repeats`; "repeat marking" in the same header, with its two-copy limit); one more line on stderr, in front.
+Not done: a second round on the trimmed overlaps, selection of best overlaps.
 """
 import argparse
 import sys
 
 import numpy as np
 
-from . import api
+from . import api, repeats
 from .correct import select_paths
 from .realign import kept_rows, read_overlaps
 
@@ -44,12 +47,26 @@ def format_table(ids, lengths, rows, flags):
                                            np.asarray(flags).tolist()))
 
 
-def trim_overlaps(recs, fasta, band=0, max_shift=0.2, min_identity=0.0, device=0, batch=BATCH, handle=None, penalty=api.TRIM_PENALTY, **params):
+def trim_overlaps(recs, fasta, band=0, max_shift=0.2, min_identity=0.0, device=0, batch=BATCH, handle=None, penalty=api.TRIM_PENALTY, repeat=None,
+                  **params):
     """Realign `recs` in batches with their paths, cut every kept record to the best stretch of its path (penalty 0: not at all) and
     trim: a dict of rows, flags, counts, records (the kept realigned records, refined, untrimmed), applied
-    (those rewritten onto the trimmed reads, void ones left out) and reads (the surviving reads, a FastaData over fasta's bases)."""
+    (those rewritten onto the trimmed reads, void ones left out) and reads (the surviving reads, a FastaData over fasta's bases).
+    repeat: None, or a dict of RepeatSession's parameters: the refined records go through the repeat stage first ("repeat marking"
+    in include/mhap_hip.h), only its survivors are piled up and are `records`, and its dict is the key `repeat`."""
     ms = handle or api.MinHashSearch(api.MhapParams(num_hashes=1, ordered_sketch_size=1, max_shift=max_shift, device=device))
     try:
+        if repeat is not None:   # the repeat session has freed its device arrays before the trim session allocates its own
+            from .repeats import mark_records, refined_overlaps
+            _, cut = refined_overlaps(recs, fasta, ms, band=band, min_identity=min_identity, batch=batch, penalty=penalty)
+            marked = mark_records(cut, fasta.ids, fasta.lengths, ms, **repeat)
+            kept = cut[marked["keep"] != 0]
+            with api.TrimSession(fasta.ids, fasta.lengths, handle=ms, **params) as ts:
+                ts.add(kept)
+                counts = ts.finish()
+                rows, flags = ts.table()
+                out, keep = ts.apply(kept)
+                return dict(rows=rows, flags=flags, counts=counts, records=kept, applied=out[keep != 0], reads=ts.trimmed(fasta), repeat=marked)
         with api.TrimSession(fasta.ids, fasta.lengths, handle=ms, **params) as ts:
             kept = []
             for q0 in range(0, len(recs), batch):
@@ -83,6 +100,8 @@ def main(argv=None):
     ap.add_argument("--min-span", type=int, default=2000, help="the shortest aligned interval that counts")
     ap.add_argument("--penalty", type=int, default=api.TRIM_PENALTY,
                     help="the cost of an error column next to +1 for a match when every overlap is cut to the best stretch of its alignment; 0: overlaps as realigned")
+    ap.add_argument("--repeat-filter", action="store_true", help="set aside the overlaps that lie in nothing but repeat before the pile-up")
+    repeats.add_arguments(ap, "repeat-")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("-o", "--output", default=None, help="the FASTA file of the trimmed reads (default: stdout)")
     ap.add_argument("--table", default=None, help="also write one line per read: id length begin end runs covered flags")
@@ -92,10 +111,15 @@ def main(argv=None):
         ap.error("--band must be >= 0")
     if a.min_cov < 1 or a.end_clip < 0 or a.min_span < 0 or a.penalty < 0:
         ap.error("--min-cov must be >= 1, --end-clip, --min-span and --penalty >= 0")
+    rp, message = repeats.parameters(a, "repeat-")
+    if message:
+        ap.error(message)
+    if rp != {k: v for k, v in api.REPEAT_DEFAULTS.items() if k in rp} and not a.repeat_filter:
+        ap.error("--repeat-factor, --repeat-max-cov, --repeat-min-run and --repeat-min-unique need --repeat-filter")
     recs = read_overlaps(a.overlaps)
     fasta = api.FastaData.from_file(a.reads)
     res = trim_overlaps(recs, fasta, band=a.band, max_shift=a.max_shift, min_identity=a.min_identity, device=a.device, min_cov=a.min_cov,
-                        end_clip=a.end_clip, min_span=a.min_span, penalty=a.penalty)
+                        end_clip=a.end_clip, min_span=a.min_span, penalty=a.penalty, repeat=rp if a.repeat_filter else None)
     text = format_fasta(fasta, res["rows"], res["flags"])
     if a.output:
         with open(a.output, "w") as fh:
@@ -108,6 +132,8 @@ def main(argv=None):
     if a.records:
         with open(a.records, "w") as fh:
             fh.write("".join(l + "\n" for l in api.records_to_lines(res["applied"])))
+    if a.repeat_filter:
+        print(api.repeat_counts_line([res["repeat"]["counts"][k] for k in api.REPEAT_COUNTS]), file=sys.stderr)
     print(api.trim_counts_line([res["counts"][k] for k in api.TRIM_COUNTS]), file=sys.stderr)
     return 0
 
