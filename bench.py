@@ -6,14 +6,19 @@ murmur hashes, tf / tf-idf weights, weighted MinHash, ordered bottom-S sketch), 
 candidate count, second-stage overlap scoring, accepted records delivered to the host.  The packed reads are
 resident in HBM before the timed region starts (mhap_stage_reads); record text formatting is outside it.
 
-  python bench.py --gpus 1 --steps K --warmup W [--config c1|c2|c3|c4|c4slice|c5slice] [--dump-outputs DIR]
+  python bench.py --gpus 1 --steps K --warmup W [--config c1|c2|c3|c4|c4slice|c5slice] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs and nothing else: set-up, warm-up, the K timed steps, --dump-outputs, the line.  Its
+line carries what those timed steps themselves yield (`value`, `ms_per_step`, the kernel times summed over them and the roofline
+arithmetic on those).  Every leg that runs something more sits behind --full: the phase-fenced step (`phase_wall_ms`, `sketches_per_sec`),
+the record fingerprints (`records_sha256_sorted_lines`, `records_checksum`), `soak`, and at N = 1 the legs named below.
 
 N > 1 (strong scaling, same data set): rank r sketches reads r, r+N, ... and indexes them — only them; the exchange is inside
 the library (mhap_dist_find_matches_self: the forward query sketches of all ranks are all-gathered over an RCCL communicator the
 library creates — the ordered rows asynchronously, under the candidate stage — and every rank searches them against its own index).
 torch.distributed only carries rank 0's communicator id to the other ranks and does the barrier / max-over-ranks timing.
-Prints ONE JSON line on rank 0.  At N = 1 the line also carries
+Prints ONE JSON line on rank 0.  At N = 1 the line of a --full run also carries
   parity_check : the GPU path and the CPU oracle run on the SAME sample reads, sorted-record SHA-256 compared;
   cpu_baseline : the oracle timed on this box's host cores on that sample (threads = the cgroup CPU quota);
   end_to_end   : the native driver (mhap-hip) from FASTA open to the last record flushed, on the bench data set.
@@ -84,14 +89,18 @@ def main():
     ap.add_argument("--length", type=int, default=0, help="override the configuration's read length")
     ap.add_argument("--hashes", type=int, default=0)
     ap.add_argument("--error-rate", type=float, default=0.15)
-    ap.add_argument("--cpu-sample-reads", type=int, default=0, help="0 = auto (about 15-20 s of CPU work)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip parity_check / cpu_baseline / end_to_end (kernel A/B runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run every other leg: the phase-fenced step, the record fingerprints, the soak leg and, "
+                         "at N = 1, dist_path_1rank / parity_check / cpu_baseline / end_to_end.  `value` and `ms_per_step` are the plain run's")
+    ap.add_argument("--cpu-sample-reads", type=int, default=0, help="--full: reads of the CPU sample; 0 = auto (about 15-20 s of CPU work)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without dist_path_1rank / parity_check / cpu_baseline / end_to_end; a plain run has none of them anyway")
     ap.add_argument("--soak-seconds", type=float, default=-1.0,
-                    help="after the timed region: repeat the step, untimed for `value`, for about this long and report the per-step spread "
+                    help="--full, after the timed region: repeat the step, untimed for `value`, for about this long and report the per-step spread "
                          "(settled clocks; also keeps the GPU busy long enough for a 5 s utilisation sampler to see it).  Default 8, "
                          "0 with --no-cpu-baseline")
     ap.add_argument("--smi-trace", default="",
-                    help="write a clock / power trace of THIS rank's card (tools/smi_trace.py, picked by its PCI address) over the soak leg to "
+                    help="--full: write a clock / power trace of THIS rank's card (tools/smi_trace.py, picked by its PCI address) over the soak leg to "
                          "this file and put its summary into the line's `soak.smi`; a capture without clock or power samples is reported as failed")
     ap.add_argument("--preflight", action="store_true",
                     help="check what an N-GPU run needs (devices, RCCL entry points, peer access, rendezvous variables) and print why "
@@ -114,6 +123,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1 (ms_per_step is the time of one timed step)")
+    if not args.full and (args.soak_seconds > 0 or args.smi_trace or args.cpu_sample_reads):
+        ap.error("--soak-seconds, --smi-trace and --cpu-sample-reads belong to legs that only a --full run has")
     if args.preflight:
         raise SystemExit(preflight(args.gpus))
     if args.dry_collective:
@@ -265,33 +276,13 @@ def main():
     elapsed = time.perf_counter() - t0
     st = ms.stats()
     kt = ms.kernel_times()
-    # one more, untimed, step with a fence between the phases: wall time of the sketch phase (packed reads in HBM -> both tables in
-    # HBM, host bookkeeping included), of the table exchange (N > 1) and of the search phase (tables in HBM -> records on the host)
-    step(timed_phases=True)
-    fence()
-    # output fingerprint of the last step (outside the timed region): SHA-256 of the sorted record lines on one GPU, and an
-    # order- and shard-independent checksum (sum of the first 8 digest bytes of every line, mod 2^64) that is comparable across N
-    # (beyond a few million records the text of every line is not formed in Python: `records_checksum` is then an order-independent
-    #  mix of the binary record fields — comparable across N and across runs of the same build, not with the text-based one)
-    big_output = len(recs) > 4_000_000
-    if big_output:
-        sha = None
-        m64 = np.zeros(len(recs), dtype=np.uint64)
-        with np.errstate(over="ignore"):
-            for f in ("from_id", "to_id", "a1", "a2", "alen", "b1", "b2", "blen", "to_rc"):
-                m64 = (m64 ^ recs[f].astype(np.int64).view(np.uint64)) * np.uint64(0x9E3779B97F4A7C15) + np.uint64(0x632BE59BD9B4E019)
-                m64 ^= m64 >> np.uint64(29)
-            for f in ("score", "raw"):
-                m64 = (m64 ^ np.ascontiguousarray(recs[f], dtype=np.float64).view(np.uint64)) * np.uint64(0xBF58476D1CE4E5B9) + np.uint64(1)
-                m64 ^= m64 >> np.uint64(31)
-            csum = int(m64.sum(dtype=np.uint64))
-        lines = None
-    else:
-        lines = sorted(mhap_amd.records_to_lines(recs))
-        sha = hashlib.sha256("\n".join(lines).encode()).hexdigest() if world == 1 else None
-        csum = 0
-        for ln in lines:
-            csum = (csum + int.from_bytes(hashlib.sha256(ln.encode()).digest()[:8], "little")) & ((1 << 64) - 1)
+    sha, csum, big_output = None, 0, False
+    if args.full:
+        # one more, untimed, step with a fence between the phases: wall time of the sketch phase (packed reads in HBM -> both tables in
+        # HBM, host bookkeeping included), of the table exchange (N > 1) and of the search phase (tables in HBM -> records on the host)
+        step(timed_phases=True)
+        fence()
+        sha, csum, big_output = fingerprint(recs, world)
     dump = None
     if args.dump_outputs:
         dump = dump_outputs(recs, args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}"),
@@ -315,9 +306,9 @@ def main():
     records_checksum = (limbs[0] + (limbs[1] << 16) + (limbs[2] << 32) + (limbs[3] << 48)) & ((1 << 64) - 1)
     sec_per_step = elapsed / max(args.steps, 1)
 
-    # soak leg (outside the timed region, before any CPU-side leg): the same step repeated for ~8 s.  The step count derives from the
-    # rank-max step time, so every rank of an N > 1 run takes the same number of collective searches.
-    soak_s = args.soak_seconds if args.soak_seconds >= 0 else (0.0 if args.no_cpu_baseline else 8.0)
+    # soak leg (--full; outside the timed region, before any CPU-side leg): the same step repeated for ~8 s.  The step count derives from
+    # the rank-max step time, so every rank of an N > 1 run takes the same number of collective searches.
+    soak_s = 0.0 if not args.full else args.soak_seconds if args.soak_seconds >= 0 else (0.0 if args.no_cpu_baseline else 8.0)
     soak = None
     if soak_s > 0 and sec_per_step > 0:
         n_soak = int(max(1, min(2000, round(soak_s / sec_per_step))))
@@ -450,25 +441,17 @@ def main():
                        "name": args.config, "error_rate": args.error_rate,
                        "parallelism": f"reads round-robin over {world} GPU(s); per-rank index of own reads; RCCL all-gather of the forward query sketches inside libmhaphip (mhap_dist_*)" if world > 1 else "1 GPU"},
             "records_per_step": total_records,
-            "sketches_per_sec": round(strands / float(pht[0].item()), 1) if float(pht[0].item()) > 0 else None,
-            "sketches_per_sec_note": "2N strands / wall time of the sketch phase (packed reads in HBM -> MinHash + ordered tables in HBM, host "
-                                     "bookkeeping of the add included; rank max), SURVEY §8(d)",
             "sketches_per_sec_kernels_only": round(strands / (sketch_ms / 1e3), 1) if sketch_ms > 0 else None,
-            "overlaps_per_sec_search_phase": round(total_records / float(pht[2].item()), 1) if float(pht[2].item()) > 0 else None,
-            "phase_wall_ms": {"sketch": round(float(pht[0].item()) * 1e3, 3), "exchange": round(float(pht[1].item()) * 1e3, 3),
-                              "search": round(float(pht[2].item()) * 1e3, 3)},
             "kernel_ms_per_step": {kk: round(v, 3) for kk, v in kernel_ms_per_step.items()},
             "candidates_per_step": int(st["candidates_compared"]),
             "index_elements_per_step": int(st["table_elements"]),
             "overlap_slow_pairs_per_step": int(st["slow_pairs"]),
-            "records_sha256_sorted_lines": sha, "records_checksum": "%016x" % records_checksum,
-            "records_checksum_kind": "binary fields (output too large for text lines in Python)" if big_output else "sha256 of text lines, summed",
             "hbm_traffic_by_kernel": hbm_by_kernel,
             "kernel_ceilings": kernel_ceilings(args.config, n_total, L, world, kernel_ms_per_step, hbm_by_kernel),
             "roofline": roofline, "valu": valu, "roofline_stage2": roofline_stage2,
             "eager_exchange": eager_note,
             "ranks": rank_views,
-            "soak": soak,
+            "full": args.full,
             "input_gen_s": round(t_gen, 2),
             "staging_ms_untimed": round(t_stage * 1e3, 1),
             "value_incl_host_pack_and_pcie": round(total_records / (sec_per_step + t_stage), 2),
@@ -476,12 +459,24 @@ def main():
                   ("this run" if args.config == "c3" else "available: run --config c3"),
             "dump_outputs": dump,
         }
-        if not args.no_cpu_baseline and world == 1 and not force_dist:
+        if args.full:
+            out.update({
+                "sketches_per_sec": round(strands / float(pht[0].item()), 1) if float(pht[0].item()) > 0 else None,
+                "sketches_per_sec_note": "2N strands / wall time of the sketch phase (packed reads in HBM -> MinHash + ordered tables in HBM, host "
+                                         "bookkeeping of the add included; rank max), SURVEY §8(d)",
+                "overlaps_per_sec_search_phase": round(total_records / float(pht[2].item()), 1) if float(pht[2].item()) > 0 else None,
+                "phase_wall_ms": {"sketch": round(float(pht[0].item()) * 1e3, 3), "exchange": round(float(pht[1].item()) * 1e3, 3),
+                                  "search": round(float(pht[2].item()) * 1e3, 3)},
+                "records_sha256_sorted_lines": sha, "records_checksum": "%016x" % records_checksum,
+                "records_checksum_kind": "binary fields (output too large for text lines in Python)" if big_output else "sha256 of text lines, summed",
+                "soak": soak,
+            })
+        if args.full and not args.no_cpu_baseline and world == 1 and not force_dist:
             # the N > 1 code path (collective add + sharded search through a ONE-rank RCCL communicator) timed on the same staged reads,
             # after the timed region: the N = 1 point of a scaling curve takes the plain path above — this says what the other path
             # costs on one GPU, so that the two are never confused (round 4: 7.1 vs 5.1 ms of ordered kernel between them)
             out["dist_path_1rank"] = dist_path_leg(ms, args, recs, mhap_amd.KERNEL_NAMES)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out.update(host_legs(args, cfg, p, flt, filter_path, fa_bench, L, H, S, k, k2, total_records, sha, tmpdir))
         emit(out)
     ms.close()
@@ -489,6 +484,29 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def fingerprint(recs, world):
+    """Output fingerprint of a step's records -> (sha, csum, big_output): SHA-256 of the sorted record lines on one GPU, and an
+    order- and shard-independent checksum (sum of the first 8 digest bytes of every line, mod 2^64) that is comparable across N.
+    Beyond a few million records the text of every line is not formed in Python: the checksum is then an order-independent mix of
+    the binary record fields — comparable across N and across runs of the same build, not with the text-based one."""
+    if len(recs) > 4_000_000:
+        m64 = np.zeros(len(recs), dtype=np.uint64)
+        with np.errstate(over="ignore"):
+            for f in ("from_id", "to_id", "a1", "a2", "alen", "b1", "b2", "blen", "to_rc"):
+                m64 = (m64 ^ recs[f].astype(np.int64).view(np.uint64)) * np.uint64(0x9E3779B97F4A7C15) + np.uint64(0x632BE59BD9B4E019)
+                m64 ^= m64 >> np.uint64(29)
+            for f in ("score", "raw"):
+                m64 = (m64 ^ np.ascontiguousarray(recs[f], dtype=np.float64).view(np.uint64)) * np.uint64(0xBF58476D1CE4E5B9) + np.uint64(1)
+                m64 ^= m64 >> np.uint64(31)
+            return None, int(m64.sum(dtype=np.uint64)), True
+    lines = sorted(mhap_amd.records_to_lines(recs))
+    sha = hashlib.sha256("\n".join(lines).encode()).hexdigest() if world == 1 else None
+    csum = 0
+    for ln in lines:
+        csum = (csum + int.from_bytes(hashlib.sha256(ln.encode()).digest()[:8], "little")) & ((1 << 64) - 1)
+    return sha, csum, False
 
 
 DUMP_MAX_BYTES = 64_000_000

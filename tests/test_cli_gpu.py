@@ -246,7 +246,7 @@ def test_bench_distributed_path_through_the_library_one_rccl_rank():
     from the id torch.distributed broadcasts (mhap_dist_init), collective search (mhap_dist_find_matches_self).  Record count and
     record checksum must equal the plain single-GPU run's."""
     import sys
-    args = ["--reads", "3000", "--length", "3000", "--steps", "1", "--warmup", "0", "--error-rate", "0.05", "--no-cpu-baseline"]
+    args = ["--reads", "3000", "--length", "3000", "--steps", "1", "--warmup", "0", "--error-rate", "0.05", "--full", "--no-cpu-baseline"]
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=900)
     assert one.returncode == 0, one.stderr[-2000:]
     r1 = json.loads(one.stdout.strip().split("\n")[-1])
@@ -268,7 +268,7 @@ def test_bench_dump_outputs_are_the_records_of_the_timed_step(tmp_path):
     run with other step counts writes the same files."""
     import hashlib
     import sys
-    base = ["--reads", "3000", "--length", "3000", "--error-rate", "0.05", "--no-cpu-baseline"]
+    base = ["--reads", "3000", "--length", "3000", "--error-rate", "0.05", "--full", "--no-cpu-baseline"]
     for steps, warmup in ((1, 0), (3, 1)):
         out = tmp_path / f"s{steps}"
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(out)]
@@ -286,6 +286,25 @@ def test_bench_dump_outputs_are_the_records_of_the_timed_step(tmp_path):
         lines = sorted(mhap_amd.records_to_lines(recs))
         assert hashlib.sha256("\n".join(lines).encode()).hexdigest() == d["records_sha256_sorted_lines"]
         assert all(np.array_equal(c, np.load(tmp_path / "s1" / f"{f}.npy")) for f, c in cols.items())
+
+
+def test_bench_plain_run_has_the_headline_and_none_of_the_full_legs(tmp_path):
+    """bench.py without --full: the line carries the headline fields and the timed steps' own figures, writes --dump-outputs, and has none
+    of the legs that run something beside the timed steps (--no-cpu-baseline changes nothing about that)."""
+    import sys
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--reads", "3000",
+                        "--length", "3000", "--error-rate", "0.05", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.strip().split("\n")[-1])
+    assert (d["metric"], d["unit"], d["higher_is_better"], d["dtype"]) == ("overlaps/sec", "overlaps/s", True, "int64")
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["records_per_step"] > 1000 and d["full"] is False
+    assert abs(d["value"] - d["records_per_step"] / (d["ms_per_step"] / 1e3)) <= 1e-3 * d["value"]      # (ms_per_step is rounded to 1 us)
+    assert d["kernel_ms_per_step"]["minhash"] > 0 and d["dump_outputs"]["records"] == d["records_per_step"]
+    assert len(np.load(out / "from_id.npy")) == d["records_per_step"]
+    full_only = {"parity_check", "cpu_baseline", "end_to_end", "dist_path_1rank", "soak", "phase_wall_ms", "sketches_per_sec",
+                 "overlaps_per_sec_search_phase", "records_sha256_sorted_lines", "records_checksum"}
+    assert not full_only & set(d)
 
 
 def test_bench_preflight_says_what_an_n_gpu_run_needs():

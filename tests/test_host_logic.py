@@ -445,6 +445,22 @@ def test_bench_preflight_without_a_gpu_reports_instead_of_hanging():
     assert set(rep["checks"]) >= {"devices", "torch_rccl_backend", "library_rccl_entry_points", "peer_access", "ipc_mode"}
 
 
+def test_bench_options_of_the_full_legs_are_refused_without_full(monkeypatch, capsys):
+    """bench.py --soak-seconds / --smi-trace / --cpu-sample-reads steer legs that only a --full run has: a plain run that names one is
+    refused at the command line (exit code 2, --full in the message) instead of quietly running without the leg."""
+    import importlib.util
+    import sys
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    for opt in (["--soak-seconds", "5"], ["--smi-trace", "trace.txt"], ["--cpu-sample-reads", "500"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "1", "--warmup", "0"] + opt)
+        with pytest.raises(SystemExit) as e:
+            bench.main()
+        out, err = capsys.readouterr()
+        assert e.value.code == 2 and "--full" in err and not out.strip(), (opt, err[-500:])
+
+
 def test_bench_dump_outputs_is_canonical_and_capped(tmp_path):
     """bench.py --dump-outputs: one float64 file per record field, the same files whatever order the records arrive in, and past the
     size cap a sample that depends on the set of records alone (a subset of them, values exact)."""
