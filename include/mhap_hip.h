@@ -493,7 +493,8 @@ int mhap_align_paths_from_runs(const int64_t* op_offsets /* n + 1 */, int64_t n,
 /* ---- read correction: a pile-up vote over every read from the realigned overlaps' paths, and a majority call ---------------------- */
 
 /* The plain method: every realigned overlap votes column by column on both of its reads, and each read position takes the majority.
- * No partial-order graph, no selection of overlaps, no cap on coverage.  A, C, G, T below are the upper-case bytes; bytes are the ones
+ * No partial-order graph and no cap on coverage; which views vote is the caller's choice (mhap_correct_add_views, with the bytes
+ * that "overlap selection" below makes: each read's best views, one round, for this stage only).  A, C, G, T below are the upper-case bytes; bytes are the ones
  * the aligner compared (s2 is the reverse complement, through Utils.rc's table, of the stored `to` read when to_rc).
  *
  * Which records vote.  A realigned record is out[q] of mhap_realign_records_paths with its runs: s1 = read A (`from`), rows i from
@@ -549,6 +550,11 @@ typedef struct mhap_correct_session mhap_correct_session;
 int mhap_correct_begin(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const int64_t* read_ids, const int64_t* offsets,
                        const int32_t* lengths, int64_t n_reads, mhap_correct_session** session);
 int mhap_correct_add(mhap_correct_session* s, const mhap_record* realigned, int64_t n, const mhap_align_paths* paths);
+/* mhap_correct_add with one byte per record that says which of its views vote ("overlap selection" below makes them): bit 0 view A,
+ * bit 1 view B; views == NULL is mhap_correct_add.  A view whose bit is clear casts no vote, does not count towards its target's
+ * 65 535 views and is not a skipped view; every check of the record runs all the same. */
+int mhap_correct_add_views(mhap_correct_session* s, const mhap_record* realigned, int64_t n, const mhap_align_paths* paths,
+                           const uint8_t* views /* n, or NULL */);
 int mhap_correct_finish(mhap_correct_session* s, int32_t min_cov, int64_t* out_offsets /* n_reads + 1 */, int32_t* stats /* n_reads x 6 */,
                         int64_t* skipped_views);
 int mhap_correct_copy(mhap_correct_session* s, uint8_t* bytes);
@@ -847,7 +853,8 @@ void mhap_consensus_free(mhap_consensus_session* s);
  * every aligned interval is shrunk by end_clip at both ends and piled up per read, and a read keeps the longest stretch that
  * min_cov of them cover, widened again by end_clip.  At a chimeric junction the overlaps of both sides end, so after the shrink
  * nothing covers it and the read falls into two stretches, of which the longer survives.  One round; left out: a second round on
- * the trimmed records, selection of best overlaps.  A repeat's false overlaps count as coverage here; "repeat marking" below sets
+ * the trimmed records.  "Overlap selection" below picks each read's best views for the read correction only: nothing is selected in
+ * front of this stage.  A repeat's false overlaps count as coverage here; "repeat marking" below sets
  * them aside in front of this stage when it is asked to, within its two-copy limit.
  * Everything is integer arithmetic in int64; the only floating comparison is score < min_identity on the record's double.  The
  * result is a function of the multiset of records: invariant under any permutation of the records and any split of them over
@@ -1014,6 +1021,73 @@ int mhap_repeat_apply(mhap_repeat_session* s, const mhap_record* in, int64_t n, 
 int mhap_repeat_judge_record(const mhap_record* in, const int32_t* intervalsA, int64_t nA, const int32_t* intervalsB, int64_t nB,
                              const mhap_repeat_params* params, int32_t* unique /* 2, or NULL */);
 void mhap_repeat_free(mhap_repeat_session* s);
+
+/* ---- overlap selection: every read keeps its best_n best views as evidence, the others are set aside view by view ---- */
+
+/* An opt-in step in front of the read correction (the overlap selection of Canu's evidence-coverage cap and minimum evidence length
+ * and of Falcon's max_n_read, as integer arithmetic).  A read inside a repeat family is seen by hundreds of overlaps, most of them
+ * from other copies, and a read at a coverage of 300 pays for 300 views where 40 would do.  Here every view of a record gets a key,
+ * the counted matches on the read it sits on, and a read keeps the best_n views with the greatest keys.  The choice is made per read
+ * and per view: a record may be among the best of its `from` read and not of its `to` read, so the result is two bits per record,
+ * not a shorter list of records.  Every output byte is a function of the multiset of records: invariant under any permutation of the
+ * records and any split of them over calls, and the same from run to run.  Nothing is de-duplicated.
+ *
+ * Input.  A table of reads (read_ids[r], lengths[r]; no bases), realigned records as for mhap_repeat_add, and the parameters best_n
+ * (40), min_span (500) and min_identity (0.0); the defaults are choices, not measurements.  best_n >= 1 and min_span >= 0, else
+ * MHAP_E_INVALID.
+ *
+ * Eligible record.  The trimming's rule and one clause more: from_id != to_id, score != 0, not score < min_identity, and
+ * score == score (a NaN is not eligible).
+ *
+ * Entries.  An eligible record gives up to two entries: view A on read `from` with the span sA = a2 + 1 - a1, view B on read `to`
+ * with the span sB = b2 + 1 - b1 (b is in B's forward coordinates, so to_rc plays no part).  A view exists only when its span is
+ * >= min_span.  Its key is 1 + (uint32) floor((double) span * min(score, 1.0)), a product below 0 (a negative score that a negative
+ * min_identity let through) counting as 0: between 1 and 2^31 - 8, and 0 stands for "no such view".  select_common.hpp holds the
+ * one function, compiled for host and device: one compare, one min, one multiply and one floor, nothing that can be contracted.
+ *
+ * Threshold.  E_r = the entries of read r.  thr_r = 1 when E_r <= best_n, else the best_n-th greatest key of r counted with
+ * multiplicity.  An entry is kept iff key >= thr_r, that is, iff fewer than best_n entries of its read have a strictly greater key.
+ * Ties at the last place are all kept, so a read may keep more than best_n; no tie-break field is needed, and none exists.
+ *
+ * Outputs.  Per read four int32 {entries, kept, thr, greatest key (0 when it has no entry)}.  MHAP_SELECT_COUNTS int64 counts: reads,
+ * reads with an entry, reads with more than best_n entries, entries, kept entries, eligible records.  Per judged record one byte:
+ * bit 0 MHAP_SELECT_A (view A kept), bit 1 MHAP_SELECT_B; an ineligible record, or a view below min_span, has the bit clear.
+ *
+ * What it does not do.  No best-n per read end for the string graph, no selection in front of the trimming or the unitig consensus,
+ * and one round: the keys are not made again from the corrected reads.  The key does not know a repeat from a unique stretch: where
+ * more than best_n copies of a repeat align better than the true neighbours, the copies win.
+ *
+ * The session mirrors mhap_repeat_*.  mhap_select_begin takes the table of reads (params NULL: the defaults); the handle must
+ * outlive the session, whose errors are the handle's.  mhap_select_add (select_kernels.hip) uploads the records once and one lane per
+ * record writes its two entries and counts them per read, any number of times, n = 0 included, without waiting (when the entries'
+ * buffer is full it doubles, and that copy is waited for); the same checks and refusals as mhap_trim_add, a refused call adds
+ * nothing, and a session takes 2^31 - 1 records and 2^30 - 1 reads.  mhap_select_finish makes the segments, thresholds, rows and
+ * counts (a radix select over the key's four bytes, one workgroup per read with more than best_n entries at a time; a segment of
+ * at most MHAP_SELECT_LDS_KEYS keys stays in LDS), waits once and returns the counts; it may be repeated, and more records may be
+ * added after it.  mhap_select_copy writes the rows of the last finish (MHAP_E_STATE before one).  mhap_select_apply, after a finish
+ * (MHAP_E_STATE before one), judges any records, added or not, against the thresholds of the last finish: views[q]; records are
+ * checked as in the add.  mhap_select_judge_record uses no GPU: keys[0], keys[1] = the keys of view A and B, 0 for no such view;
+ * 1 for an eligible record, 0 for an ineligible one, -1 for a null pointer, bad parameters or an eligible record outside its reads.
+ * Device memory from begin to free: 16 bytes per record (the entries; up to twice that after a doubling), 8 per record for the keys
+ * in their segments, 32 per record of the largest add or apply and 1 of the largest apply, and 40 per read. */
+typedef struct mhap_select_params {
+  int32_t best_n, min_span;
+  double min_identity;
+} mhap_select_params;
+#define MHAP_SELECT_COUNTS 6
+#define MHAP_SELECT_LDS_KEYS 8192
+#define MHAP_SELECT_A 1
+#define MHAP_SELECT_B 2
+typedef struct mhap_select_session mhap_select_session;
+void mhap_select_default_params(mhap_select_params* p);
+int mhap_select_begin(mhap_handle* h, const int64_t* read_ids, const int32_t* lengths, int64_t n_reads, const mhap_select_params* params,
+                      mhap_select_session** session);
+int mhap_select_add(mhap_select_session* s, const mhap_record* realigned, int64_t n);
+int mhap_select_finish(mhap_select_session* s, int64_t* counts /* MHAP_SELECT_COUNTS */);
+int mhap_select_copy(mhap_select_session* s, int32_t* rows /* n_reads x 4 */);
+int mhap_select_apply(mhap_select_session* s, const mhap_record* in, int64_t n, uint8_t* views /* n */);
+int mhap_select_judge_record(const mhap_record* in, const mhap_select_params* params, uint32_t* keys /* 2 */);
+void mhap_select_free(mhap_select_session* s);
 
 /* KmerStatSimulator's pair statistics on the GPU (J/main/KmerStatSimulator.java:163-196).  pairs: n rows of 4 int64 {a_off, a_len,
  * b_off, b_len}; a = bases[a_off, a_off + a_len) is the first read, b the second.  skip: n_skip k-mers of k bytes each, back to back, in

@@ -48,6 +48,10 @@ from .api import (  # noqa: F401
     RepeatSession,
     repeat_counts_line,
     repeat_judge_record,
+    SelectSession,
+    select_overlaps,
+    select_counts_line,
+    select_judge_record,
     pair_kmer_stats,
     records_to_lines,
     load_library,

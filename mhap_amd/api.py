@@ -88,6 +88,8 @@ EXPORTED_SYMBOLS = [
     "mhap_trim_apply", "mhap_trim_clip_record", "mhap_trim_free", "mhap_trim_refine", "mhap_trim_refine_record",
     "mhap_repeat_default_params", "mhap_repeat_begin", "mhap_repeat_add", "mhap_repeat_finish", "mhap_repeat_copy", "mhap_repeat_histogram",
     "mhap_repeat_apply", "mhap_repeat_judge_record", "mhap_repeat_free",
+    "mhap_select_default_params", "mhap_select_begin", "mhap_select_add", "mhap_select_finish", "mhap_select_copy", "mhap_select_apply",
+    "mhap_select_judge_record", "mhap_select_free", "mhap_correct_add_views",
     "mhap_pair_kmer_stats", "mhap_pair_kmer_stats_paths", "mhap_ksim_create", "mhap_ksim_next", "mhap_ksim_error", "mhap_ksim_destroy",
     "mhap_ksim_dev_create", "mhap_ksim_dev_destroy", "mhap_ksim_dev_pair_stats", "mhap_ksim_dev_trials",
 ]
@@ -173,6 +175,17 @@ def load_library(build_if_missing=True):
     lib.mhap_align_paths_from_runs.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.mhap_correct_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     lib.mhap_correct_add.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.mhap_correct_add_views.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.mhap_select_default_params.restype = None
+    lib.mhap_select_default_params.argtypes = [C.c_void_p]
+    lib.mhap_select_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.mhap_select_add.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    lib.mhap_select_finish.argtypes = [C.c_void_p, C.c_void_p]
+    lib.mhap_select_copy.argtypes = [C.c_void_p, C.c_void_p]
+    lib.mhap_select_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.mhap_select_judge_record.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mhap_select_free.restype = None
+    lib.mhap_select_free.argtypes = [C.c_void_p]
     lib.mhap_correct_finish.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mhap_correct_copy.argtypes = [C.c_void_p, C.c_void_p]
     lib.mhap_correct_votes.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
@@ -607,9 +620,14 @@ class CorrectSession:
         """The constructor under the C entry point's name: the bases go up and the vote table is zeroed."""
         return cls(fasta, query_fasta=query_fasta, handle=handle, device=device)
 
-    def add(self, records, op_offsets, ops):
-        """The votes of realigned records and their runs (pair q's are ops[op_offsets[q]:op_offsets[q + 1]])."""
+    def add(self, records, op_offsets, ops, views=None):
+        """The votes of realigned records and their runs (pair q's are ops[op_offsets[q]:op_offsets[q + 1]]).  views: one byte per
+        record, bit 0 view A votes, bit 1 view B (SelectSession.apply makes them); None: both views of every record."""
         records = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
+        if views is not None:
+            views = np.ascontiguousarray(views, dtype=np.uint8)
+            if views.shape != (len(records),):
+                raise MhapError(f"CorrectSession.add: {len(records)} records need {len(records)} view bytes, not {views.shape}")
         op_offsets = np.ascontiguousarray(op_offsets, dtype=np.int64)
         ops = np.ascontiguousarray(ops, dtype=np.uint32)
         if len(op_offsets) != len(records) + 1:
@@ -618,7 +636,12 @@ class CorrectSession:
         if self._lib.mhap_align_paths_from_runs(_ptr(op_offsets), C.c_int64(len(records)), _ptr(ops) if len(ops) else None, C.byref(obj)) != 0:
             raise MhapError("CorrectSession.add: op_offsets is not a list of run offsets over ops")
         try:
-            self._ms._chk(self._lib.mhap_correct_add(self._s, _ptr(records) if len(records) else None, C.c_int64(len(records)), obj))
+            recs = _ptr(records) if len(records) else None
+            if views is None:
+                self._ms._chk(self._lib.mhap_correct_add(self._s, recs, C.c_int64(len(records)), obj))
+            else:   # (an empty array has no bytes to point at, and NULL would mean "both")
+                self._ms._chk(self._lib.mhap_correct_add_views(self._s, recs, C.c_int64(len(records)), obj,
+                                                               _ptr(views if len(views) else np.zeros(1, np.uint8))))
         finally:
             self._lib.mhap_align_paths_free(obj)
 
@@ -1249,6 +1272,124 @@ class RepeatSession:
             self.close()
         except Exception:
             pass
+
+
+SELECT_COUNTS = ("reads", "reads_with_entry", "reads_over", "entries", "kept", "eligible_records")   # mhap_select_finish's counts
+SELECT_ROW_FIELDS = ("entries", "kept", "threshold", "max_key")
+SELECT_A, SELECT_B = 1, 2   # the bits of a record's view byte
+SELECT_LDS_KEYS = 8192   # MHAP_SELECT_LDS_KEYS: the longest segment of keys that stays in LDS across the passes of the select
+SELECT_DEFAULTS = dict(best_n=40, min_span=500, min_identity=0.0)   # choices, not measurements
+
+
+class _SelectParams(C.Structure):
+    _fields_ = [("best_n", C.c_int32), ("min_span", C.c_int32), ("min_identity", C.c_double)]
+
+
+def select_counts_line(counts):
+    """The one stderr line of an overlap selection (the driver prints the same); counts: the MHAP_SELECT_COUNTS values in order."""
+    c = [int(x) for x in counts]
+    return (f"Best overlaps: {c[0]} reads, {c[1]} with a view, {c[2]} cut; {c[4]} of {c[3]} views kept; {c[5]} eligible overlaps")
+
+
+def select_table_text(read_ids, rows):
+    """The table file of a selection: one line per read, `read_id entries kept threshold`."""
+    return "".join(f"{i} {r[0]} {r[1]} {r[2]}\n" for i, r in zip(np.asarray(read_ids).tolist(), np.asarray(rows).tolist()))
+
+
+def select_judge_record(record, best_n=40, min_span=500, min_identity=0.0):
+    """The keys of one record's two views (mhap_select_judge_record, no GPU): (eligible, kA, kB), a key of 0 for no such view."""
+    lib = load_library()
+    rec = np.ascontiguousarray(record, dtype=RECORD_DTYPE).reshape(1)
+    keys = np.zeros(2, np.uint32)
+    p = _SelectParams(best_n, min_span, min_identity)
+    rc = lib.mhap_select_judge_record(_ptr(rec), C.byref(p), _ptr(keys))
+    if rc < 0:
+        raise MhapError("mhap_select_judge_record: bad parameters or an eligible record outside its reads")
+    return bool(rc), int(keys[0]), int(keys[1])
+
+
+class SelectSession:
+    """Each read's best overlaps (mhap_select_begin / _add / _finish / _copy / _apply; the contract is the "overlap selection" section
+    of include/mhap_hip.h).
+
+        with SelectSession(fasta.ids, fasta.lengths, best_n=40) as ss:
+            ss.add(records)                       # realigned records; any number of times
+            rows, counts = ss.finish()            # int32 (n, 4) of SELECT_ROW_FIELDS and a dict of SELECT_COUNTS
+            views = ss.apply(records)             # one byte per record: SELECT_A | SELECT_B
+
+    handle: a MinHashSearch whose device and stream to use (else one is made and closed with the session)."""
+
+    def __init__(self, read_ids, lengths, best_n=40, min_span=500, min_identity=0.0, handle=None, device=0):
+        self._own = handle is None
+        self._ms = MinHashSearch(MhapParams(num_hashes=1, ordered_sketch_size=1, device=device)) if self._own else handle
+        self._lib = self._ms._lib
+        self._s = C.c_void_p()
+        self.ids = np.ascontiguousarray(read_ids, np.int64)
+        self.lengths = np.ascontiguousarray(lengths, np.int32)
+        self.rows = self.counts = None
+        try:
+            if len(self.ids) != len(self.lengths):
+                raise MhapError(f"SelectSession: {len(self.ids)} ids and {len(self.lengths)} lengths")
+            p = _SelectParams(best_n, min_span, min_identity)
+            self._ms._chk(self._lib.mhap_select_begin(self._ms._h, _ptr(self.ids) if len(self.ids) else None,
+                                                      _ptr(self.lengths) if len(self.ids) else None, C.c_int64(len(self.ids)), C.byref(p),
+                                                      C.byref(self._s)))
+        except Exception:
+            if self._own:
+                self._ms.close()
+            raise
+
+    def add(self, records):
+        """The entries of realigned records (nothing waits for the device)."""
+        records = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
+        self._ms._chk(self._lib.mhap_select_add(self._s, _ptr(records) if len(records) else None, C.c_int64(len(records))))
+
+    def finish(self):
+        """Make every read's threshold: (rows, counts), int32 (n, 4) of SELECT_ROW_FIELDS and a dict of SELECT_COUNTS."""
+        counts = np.zeros(len(SELECT_COUNTS), np.int64)
+        self.rows = self.counts = None
+        self._ms._chk(self._lib.mhap_select_finish(self._s, _ptr(counts)))
+        rows = np.zeros((len(self.ids), 4), np.int32)
+        self._ms._chk(self._lib.mhap_select_copy(self._s, _ptr(rows) if len(rows) else None))
+        self.rows, self.counts = rows, dict(zip(SELECT_COUNTS, counts.tolist()))
+        return self.rows, self.counts
+
+    def apply(self, records):
+        """One byte per record against the thresholds of the last finish: bit 0 SELECT_A (view A kept), bit 1 SELECT_B."""
+        records = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
+        views = np.zeros(len(records), np.uint8)
+        opt = lambda a: _ptr(a) if len(a) else None
+        self._ms._chk(self._lib.mhap_select_apply(self._s, opt(records), C.c_int64(len(records)), opt(views)))
+        return views
+
+    def close(self):
+        if self._s:
+            self._lib.mhap_select_free(self._s)
+            self._s = C.c_void_p()
+            if self._own:
+                self._ms.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def select_overlaps(records, fasta, best_n=40, min_span=500, min_identity=0.0, query_fasta=None, handle=None, device=0):
+    """Select over the realigned `records` of the reads of `fasta` (and `query_fasta`): (views, rows, counts, ids) — one byte per
+    record, SelectSession.finish's rows and counts, and the ids the rows belong to."""
+    _, ids, _, lengths = _all_reads(fasta, query_fasta)
+    with SelectSession(ids, lengths, best_n=best_n, min_span=min_span, min_identity=min_identity, handle=handle, device=device) as ss:
+        ss.add(records)
+        rows, counts = ss.finish()
+        return ss.apply(records), rows, counts, np.asarray(ids, np.int64)
 
 
 CONSENSUS_COUNTS = ("members", "placed_by_record", "unplaced", "aligned", "no_alignment", "bases_in", "bases_out", "substitutions",

@@ -1,11 +1,16 @@
 """Correct reads on the GPU from a file of MHAP overlaps: `python -m mhap_amd.correct overlaps.txt reads.fasta [queries.fasta] [--band W]
-[--min-identity X] [--min-coverage N] [-o out.fasta]` writes what `mhap-hip --realign --correct out.fasta` writes for the same overlaps.
+[--min-identity X] [--min-coverage N] [--best-overlaps N [--best-min-span S]] [-o out.fasta]` writes what `mhap-hip --realign --correct
+out.fasta` (with the same --best-overlaps flags) writes for the same overlaps.
 
 The overlaps are parsed and realigned as `python -m mhap_amd.realign` does, with every alignment's path; the records that tool would
 drop (no alignment, or an identity below --min-identity) cast no vote.  Every other record votes column by column on both of its reads
 (api.CorrectSession; the contract is the "read correction" section of include/mhap_hip.h) and each read position takes the majority.
 Output is FASTA, one unwrapped line per read: `>ID len=<corrected length> sub=<substitutions> del=<deletions> ins=<insertions>
 low=<positions below --min-coverage>`, the ids numeric as the records print them; one line on stderr gives the totals.
+
+--best-overlaps N makes two passes ("overlap selection" of include/mhap_hip.h): the first realigns without paths and selects each
+read's N best views over the records that would vote (api.SelectSession), the second realigns only the records that keep a view, with
+paths, and votes the selected views.
 """
 import argparse
 import sys
@@ -43,16 +48,44 @@ def totals_line(stats, skipped_views):
             f"{t[5]} positions of low coverage; skipped_views = {skipped_views}")
 
 
-def correct_overlaps(recs, fasta, queries=None, band=0, max_shift=0.2, min_identity=0.0, min_cov=4, device=0, batch=BATCH):
-    """Realign `recs` with paths in batches and vote: (seqs, stats, skipped_views, records that voted)."""
+def select_pass(recs, fasta, queries, ms, band, min_identity, best_n, best_min_span, batch):
+    """The first pass of --best-overlaps: (the rows of `recs` that keep a view, their view bytes, SelectSession.finish's rows and
+    counts, the ids of the rows)."""
+    _, ids, _, lengths = api._all_reads(fasta, queries)
+    with api.SelectSession(ids, lengths, best_n=best_n, min_span=best_min_span, handle=ms) as ss:
+        held = []   # per batch: the rows of recs that would vote, and their realigned records
+        for q0 in range(0, len(recs), batch):
+            out, _ = api.realign_records(recs[q0:q0 + batch], fasta, band=band, handle=ms, query_fasta=queries)
+            rows = kept_rows(out, min_identity)
+            ss.add(out[rows])
+            held.append((q0 + rows, out[rows]))
+        table, counts = ss.finish()
+        which, views = [np.zeros(0, np.int64)], [np.zeros(0, np.uint8)]
+        for rows, out in held:
+            v = ss.apply(out)
+            which.append(rows[v != 0])
+            views.append(v[v != 0])
+    return np.concatenate(which), np.concatenate(views), table, counts, np.asarray(ids, np.int64)
+
+
+def correct_overlaps(recs, fasta, queries=None, band=0, max_shift=0.2, min_identity=0.0, min_cov=4, device=0, batch=BATCH, best_n=0,
+                     best_min_span=500, selection=None):
+    """Realign `recs` with paths in batches and vote: (seqs, stats, skipped_views, records that voted).  best_n > 0: only each read's
+    best_n best views vote; `selection` (a dict) then takes the selection's rows, counts and ids."""
     voted = 0
     with api.MinHashSearch(api.MhapParams(num_hashes=1, ordered_sketch_size=1, max_shift=max_shift, device=device)) as ms:
+        views = None
+        if best_n > 0:
+            which, views, table, counts, sel_ids = select_pass(recs, fasta, queries, ms, band, min_identity, best_n, best_min_span, batch)
+            recs = recs[which]
+            if selection is not None:
+                selection.update(rows=table, counts=counts, ids=sel_ids)
         with api.CorrectSession(fasta, query_fasta=queries, handle=ms) as cs:
             for q0 in range(0, len(recs), batch):
                 out, _, op_offsets, ops = api.realign_records_paths(recs[q0:q0 + batch], fasta, band=band, handle=ms, query_fasta=queries)
                 rows = kept_rows(out, min_identity)
                 ko, kops = select_paths(op_offsets, ops, rows)
-                cs.add(out[rows], ko, kops)
+                cs.add(out[rows], ko, kops, views=None if views is None else views[q0:q0 + batch][rows])
                 voted += len(rows)
             seqs, stats, skipped = cs.finish(min_cov)
             ids = cs.ids.tolist()
@@ -68,10 +101,18 @@ def main(argv=None):
     ap.add_argument("--max-shift", type=float, default=0.2)
     ap.add_argument("--min-identity", type=float, default=0.0, help="overlaps realigned below this identity cast no vote")
     ap.add_argument("--min-coverage", type=int, default=4, help="votes a position needs before it is changed (min_cov)")
+    ap.add_argument("--best-overlaps", type=int, default=0, metavar="N", help="only each read's N best views vote; 0: every view")
+    ap.add_argument("--best-min-span", type=int, default=None, metavar="S", help="a view shorter than this is no evidence (500)")
     ap.add_argument("--query-id-offset", type=int, default=None)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("-o", "--output", default=None, help="the FASTA file to write (default: stdout)")
     a = ap.parse_args(argv)
+    if a.best_overlaps < 0:
+        ap.error("--best-overlaps must be >= 0")
+    if a.best_min_span is not None and a.best_overlaps == 0:
+        ap.error("--best-min-span needs --best-overlaps")
+    if a.best_min_span is not None and a.best_min_span < 0:
+        ap.error("--best-min-span must be >= 0")
     if a.band < 0:
         ap.error("--band must be >= 0")
     if a.min_coverage < 1:
@@ -79,8 +120,11 @@ def main(argv=None):
     recs = read_overlaps(a.overlaps)
     fasta = api.FastaData.from_file(a.reads)
     queries = api.FastaData.from_file(a.queries, len(fasta) if a.query_id_offset is None else a.query_id_offset) if a.queries else None
+    selection = {}
     ids, seqs, stats, skipped, voted = correct_overlaps(recs, fasta, queries, band=a.band, max_shift=a.max_shift, min_identity=a.min_identity,
-                                                        min_cov=a.min_coverage, device=a.device)
+                                                        min_cov=a.min_coverage, device=a.device, best_n=a.best_overlaps,
+                                                        best_min_span=500 if a.best_min_span is None else a.best_min_span,
+                                                        selection=selection)
     text = format_fasta(ids, seqs, stats)
     if a.output:
         with open(a.output, "w") as fh:
@@ -89,6 +133,8 @@ def main(argv=None):
         sys.stdout.write(text)
     print(f"Realigned {len(recs)} overlaps: {voted} voted, {len(recs) - voted} dropped (no alignment or identity below {a.min_identity:g})",
           file=sys.stderr)
+    if selection:
+        print(api.select_counts_line([selection["counts"][k] for k in api.SELECT_COUNTS]), file=sys.stderr)
     print(totals_line(stats, skipped), file=sys.stderr)
     return 0
 

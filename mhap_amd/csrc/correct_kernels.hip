@@ -1,5 +1,5 @@
 // correct_kernels.hip — read correction: a pile-up vote over every read from the realigned overlaps' paths and a majority call per
-// position (mhap_correct_begin / _add / _finish / _copy / _votes / _free).  The contract — the two views of a record, the 22 counters,
+// position (mhap_correct_begin / _add / _add_views / _finish / _copy / _votes / _free).  The contract — the two views of a record, the 22 counters,
 // the 65 535-view cap and the call — is the prose of include/mhap_hip.h ("read correction"); tests/consensus_ref.py restates it.
 //
 // The vote table.  24 counters of 16 bits per base, two to a word: 12 words per base, kept as 12 planes per read — word p of position t
@@ -160,8 +160,9 @@ extern "C" int mhap_correct_begin(mhap_handle* h, const uint8_t* bases, int64_t 
   return MHAP_OK;
 }
 
-extern "C" int mhap_correct_add(mhap_correct_session* s, const mhap_record* recs, int64_t n, const mhap_align_paths* paths) {
-  const char* who = "mhap_correct_add";
+// the add behind mhap_correct_add (views == nullptr: both views of every record) and mhap_correct_add_views
+static int correct_add(const char* who, mhap_correct_session* s, const mhap_record* recs, int64_t n, const mhap_align_paths* paths,
+                       const uint8_t* views) {
   if (!s) return MHAP_E_INVALID;
   HandleView v = handle_view(s->h);
   if (n < 0 || !paths || (n > 0 && !recs)) { *v.err = std::string(who) + ": null or negative argument"; return MHAP_E_INVALID; }
@@ -219,6 +220,7 @@ extern "C" int mhap_correct_add(mhap_correct_session* s, const mhap_record* recs
     }
     for (int view = 0; view < 2; view++) {
       const int64_t target = idx[view];
+      if (views && !(views[q] & (1u << view))) continue;   // not selected: no vote, no place under the cap, not a skipped view
       if (s->views[(size_t)target] >= CK_CAP) { skipped++; continue; }
       s->views[(size_t)target] += 1;
       accepted.emplace_back(target, 1);
@@ -248,6 +250,15 @@ extern "C" int mhap_correct_add(mhap_correct_session* s, const mhap_record* recs
     if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return hip_fail(v, who, "kernel", e);   // (items is reused by the next chunk)
   }
   return MHAP_OK;
+}
+
+extern "C" int mhap_correct_add(mhap_correct_session* s, const mhap_record* recs, int64_t n, const mhap_align_paths* paths) {
+  return correct_add("mhap_correct_add", s, recs, n, paths, nullptr);
+}
+
+extern "C" int mhap_correct_add_views(mhap_correct_session* s, const mhap_record* recs, int64_t n, const mhap_align_paths* paths,
+                                      const uint8_t* views) {
+  return correct_add("mhap_correct_add_views", s, recs, n, paths, views);
 }
 
 extern "C" int mhap_correct_finish(mhap_correct_session* s, int32_t min_cov, int64_t* out_offsets, int32_t* stats, int64_t* skipped_views) {

@@ -43,7 +43,7 @@ struct Options {
     return t;
   }
   // (the realignment flags are listed only when --realign is given, the correction flags only when --correct is, the graph's only
-  // when --gfa is, the cleaning's only when --gfa-clean is, the consensus' only when --gfa-consensus is, the trimming's only when --trim is, the repeat stage's only when --repeat-filter is: without them every line the driver writes is what it was before them)
+  // when --gfa is, the cleaning's only when --gfa-clean is, the consensus' only when --gfa-consensus is, the trimming's only when --trim is, the repeat stage's only when --repeat-filter is, the selection's only when --best-overlaps is: without them every line the driver writes is what it was before them)
   std::string dump() const {
     std::string t;
     for (auto& n : order) {
@@ -54,6 +54,7 @@ struct Options {
       if (n.compare(0, 15, "--gfa-consensus") == 0 && !b("--gfa-consensus")) continue;
       if (n.compare(0, 6, "--trim") == 0 && !b("--trim")) continue;
       if (n.compare(0, 8, "--repeat") == 0 && !b("--repeat-filter")) continue;
+      if (n.compare(0, 6, "--best") == 0 && !isset("--best-overlaps")) continue;
       t += n + " = " + m.at(n).value + "\n";
     }
     return t;
@@ -186,6 +187,10 @@ struct Realign {
   bool hold_plain = false;                            // the graph takes the survivors as realigned: those copies wait too
   std::vector<mhap_record> held_refined, held_plain;
   double repeat_seconds = 0.0;
+  mhap_select_session* select = nullptr;              // --best-overlaps: every kept record gives its two views to the selection
+  bool hold_select = false;                           // with --correct the votes wait: the records as they came and as realigned are held
+  std::vector<mhap_record> held_in, held_out;
+  double select_seconds = 0.0;
   void add(const mhap_fasta& fa) {
     for (int64_t i = 0; i < fa.n; i++) { ids.push_back(fa.ids[i]); offsets.push_back((int64_t)bases.size() + fa.offsets[i]); lengths.push_back(fa.lengths[i]); }
     bases.insert(bases.end(), (const uint8_t*)fa.bases, (const uint8_t*)fa.bases + fa.total_bases);
@@ -200,7 +205,8 @@ int sink_cb(const mhap_record* r, int64_t n, void* user) {
     const double t = now();
     R.out.resize((size_t)n);
     int rc;
-    if (R.paf || R.correct || ((R.trim || R.repeat) && R.trim_penalty > 0)) {
+    const bool vote_now = R.correct && !R.select;   // (with --best-overlaps the votes are cast after the last batch)
+    if (R.paf || vote_now || ((R.trim || R.repeat) && R.trim_penalty > 0)) {
       R.detail.resize((size_t)n * 3);
       mhap_align_paths* paths = nullptr;
       rc = mhap_realign_records_paths(R.h, R.bases.data(), (int64_t)R.bases.size(), R.ids.data(), R.offsets.data(), R.lengths.data(),
@@ -224,12 +230,20 @@ int sink_cb(const mhap_record* r, int64_t n, void* user) {
       const bool none = o.score == 0.0 && o.a1 == 0 && o.a2 == 0 && o.b1 == 0 && o.b2 == 0;
       if (none || o.score < R.min_identity) continue;
       R.row[(size_t)k] = i;
+      if (R.hold_select) R.held_in.push_back(r[i]);
       R.out[(size_t)k++] = o;
     }
     R.dropped += n - k; R.kept += k;
     R.seconds += now() - t;
     const bool refine = (R.trim || R.repeat) && R.trim_penalty > 0;
-    if (R.correct || refine) {   // the kept records and their runs: into the vote table, and cut to their best stretch for the trimming
+    if (R.select) {   // the kept records' views into the selection (queued: nothing waits)
+      const double ts = now();
+      rc = mhap_select_add(R.select, R.out.data(), k);
+      if (rc != MHAP_OK) { fprintf(stderr, "Exception in mhap-hip: %s (code %d)\n", mhap_last_error(R.h), rc); return 1; }
+      if (R.hold_select) R.held_out.insert(R.held_out.end(), R.out.data(), R.out.data() + k);
+      R.select_seconds += now() - ts;
+    }
+    if (vote_now || refine) {   // the kept records and their runs: into the vote table, and cut to their best stretch for the trimming
       const double tc = now();
       R.vote_offsets.assign(1, 0); R.vote_ops.clear();
       for (int64_t i = 0; i < k; i++) {
@@ -239,8 +253,8 @@ int sink_cb(const mhap_record* r, int64_t n, void* user) {
       }
       mhap_align_paths* kept_paths = nullptr;
       rc = mhap_align_paths_from_runs(R.vote_offsets.data(), k, R.vote_ops.data(), &kept_paths);
-      if (rc == MHAP_OK && R.correct) rc = mhap_correct_add(R.correct, R.out.data(), k, kept_paths);   // (the dropped ones cast no vote)
-      if (R.correct) R.correct_seconds += now() - tc;
+      if (rc == MHAP_OK && vote_now) rc = mhap_correct_add(R.correct, R.out.data(), k, kept_paths);   // (the dropped ones cast no vote)
+      if (vote_now) R.correct_seconds += now() - tc;
       if (rc == MHAP_OK && refine) {
         const double tt = now();
         R.refined.resize((size_t)std::max<int64_t>(k, 1));
@@ -470,6 +484,9 @@ int main(int argc, char** argv) {
   o.add("--repeat-min-run", "[int] With --repeat-filter, the shortest stretch of repeat positions that is marked.", "500");
   o.add("--repeat-min-unique", "[int] With --repeat-filter, the aligned bases outside repeats an overlap needs on both reads.", "500");
   o.add("--repeat-table", "With --repeat-filter, write one line per repeat interval to this file: read_id begin end.", "");
+  o.add("--best-overlaps", "[int] With --realign: select each read's N best overlaps on the GPU, by the matches counted on that read, ties at the last place included; with --correct only the selected views of an overlap vote. The overlaps printed, --realign-paf, --gfa and --trim stay on all overlaps. 0) off. Self overlaps only (no -q), one GPU.", "0");
+  o.add("--best-min-span", "[int] With --best-overlaps, the shortest aligned interval on a read that counts as evidence for it.", "500");
+  o.add("--best-table", "With --best-overlaps, write one line per read to this file: read_id entries kept threshold.", "");
   o.add("--trim-fasta", "With --trim, write the trimmed reads to this FASTA file; deleted reads are left out.", "");
   o.add("--trim-table", "With --trim, write one line per read to this file: id length begin end runs covered flags.", "");
   if (!o.parse(argc, argv)) return 0;
@@ -521,6 +538,18 @@ int main(int argc, char** argv) {
     if (devs.size() > 1) bad("--correct runs on one GPU: give one device (--gpus 1).");
     if (o.s("--correct").empty()) bad("--correct needs the name of the FASTA file to write.");
     if (o.i("--correct-min-coverage") < 1) bad("The correction's minimum coverage must be >=1.");
+  }
+  const bool best = o.isset("--best-overlaps") && o.i("--best-overlaps") != 0;
+  for (const char* n : {"--best-min-span", "--best-table"})   // refused before a handle exists
+    if (o.isset(n) && !best) bad((std::string(n) + " belongs to --best-overlaps: give --best-overlaps too.").c_str());
+  if (best) {   // refused before a handle exists
+    if (o.i("--best-overlaps") < 0) bad("The value of --best-overlaps must be >=0.");
+    if (!o.b("--realign")) bad("--best-overlaps selects among the alignments of --realign: give --realign too.");
+    if (!o.s("-q").empty()) bad("--best-overlaps selects for the reads of -s from their overlaps with each other: it takes no -q.");
+    if (ends_with(o.s("-s"), ".dat")) bad("--best-overlaps needs the overlaps realigned on the reads' bases: give FASTA files, not .dat sketches.");
+    if (devs.size() > 1) bad("--best-overlaps runs on one GPU: give one device (--gpus 1).");
+    if (o.i("--best-min-span") < 0) bad("The value of --best-min-span must be >=0.");
+    if (o.isset("--best-table") && o.s("--best-table").empty()) bad("--best-table needs the name of the file to write.");
   }
   const bool gfa = o.isset("--gfa");
   if (o.isset("--gfa-unitigs")) {   // refused before a handle exists
@@ -656,6 +685,13 @@ int main(int argc, char** argv) {
     sink.realign = &RA;
     if (correct) chk(E.h, mhap_correct_begin(E.h, RA.bases.data(), (int64_t)RA.bases.size(), RA.ids.data(), RA.offsets.data(), RA.lengths.data(),
                                              (int64_t)RA.ids.size(), &RA.correct));
+    if (best) {
+      mhap_select_params sp;
+      mhap_select_default_params(&sp);
+      sp.best_n = o.i("--best-overlaps"); sp.min_span = o.i("--best-min-span");
+      chk(E.h, mhap_select_begin(E.h, RA.ids.data(), RA.lengths.data(), (int64_t)RA.ids.size(), &sp, &RA.select));
+      RA.hold_select = correct;
+    }
     if (trim) { tp.min_cov = o.i("--trim-min-cov"); tp.end_clip = o.i("--trim-end-clip"); tp.min_span = o.i("--trim-min-span"); }
     if (trim || repeat) RA.trim_penalty = o.i("--trim-penalty");
     if (repeat) {   // (with --trim too, the trimming begins once the repeat stage has freed its device arrays)
@@ -721,6 +757,71 @@ int main(int argc, char** argv) {
   sink_flush(sink);
   fprintf(stderr, "Total scoring time (s): %g\n", now() - t_score);
   if (realign) fprintf(stderr, "Time (s) to realign: %g (%lld overlaps kept, %lld dropped: no alignment or identity below %g)\n", RA.seconds, (long long)RA.kept, (long long)RA.dropped, RA.min_identity);
+  if (RA.select) {   // every read's threshold after the last batch; with --correct the held records that keep a view are realigned again, with paths, and vote
+    const double ts = now();
+    const int64_t nr = (int64_t)RA.ids.size(), nh = (int64_t)RA.held_out.size();
+    int64_t sc[MHAP_SELECT_COUNTS];
+    chk(E.h, mhap_select_finish(RA.select, sc));
+    if (o.isset("--best-table")) {
+      std::vector<int32_t> srows((size_t)std::max<int64_t>(nr, 1) * 4);
+      chk(E.h, mhap_select_copy(RA.select, srows.data()));
+      FILE* f = fopen(o.s("--best-table").c_str(), "wb");
+      if (!f) die("cannot write " + o.s("--best-table"));
+      std::string text;
+      for (int64_t r = 0; r < nr; r++)
+        text += header_of(RA.ids[(size_t)r]) + " " + std::to_string(srows[4 * (size_t)r]) + " " + std::to_string(srows[4 * (size_t)r + 1]) + " " +
+                std::to_string(srows[4 * (size_t)r + 2]) + "\n";
+      fwrite(text.data(), 1, text.size(), f);
+      if (fclose(f) != 0) die("cannot write " + o.s("--best-table"));
+    }
+    std::vector<uint8_t> views((size_t)std::max<int64_t>(nh, 1));
+    if (RA.correct) chk(E.h, mhap_select_apply(RA.select, RA.held_out.data(), nh, views.data()));
+    mhap_select_free(RA.select);
+    RA.select = nullptr;
+    RA.select_seconds += now() - ts;
+    fprintf(stderr, "Best overlaps: %lld reads, %lld with a view, %lld cut; %lld of %lld views kept; %lld eligible overlaps\n", (long long)sc[0],
+            (long long)sc[1], (long long)sc[2], (long long)sc[4], (long long)sc[3], (long long)sc[5]);
+    fprintf(stderr, "Time (s) to select the best overlaps: %g\n", RA.select_seconds);
+    if (RA.correct) {   // the aligner is deterministic: the records as they came give the alignments of the first pass again, now with their paths
+      const double tc = now();
+      std::vector<mhap_record> in, out, kept;
+      std::vector<uint8_t> vb, kv;
+      for (int64_t q = 0; q < nh; q++)
+        if (views[(size_t)q]) { in.push_back(RA.held_in[(size_t)q]); vb.push_back(views[(size_t)q]); }
+      std::vector<mhap_record>().swap(RA.held_in);
+      std::vector<mhap_record>().swap(RA.held_out);
+      const int64_t total = (int64_t)in.size(), step = 1 << 16;
+      for (int64_t q0 = 0; q0 < total; q0 += step) {
+        const int64_t n = std::min(step, total - q0);
+        out.resize((size_t)n);
+        RA.detail.resize((size_t)n * 3);
+        mhap_align_paths* paths = nullptr;
+        chk(E.h, mhap_realign_records_paths(E.h, RA.bases.data(), (int64_t)RA.bases.size(), RA.ids.data(), RA.offsets.data(), RA.lengths.data(),
+                                            (int64_t)RA.ids.size(), in.data() + q0, n, RA.band, out.data(), RA.detail.data(), &paths));
+        int64_t n_ops = 0;
+        mhap_align_paths_info(paths, nullptr, &n_ops);
+        RA.op_offsets.resize((size_t)n + 1); RA.ops.resize((size_t)std::max<int64_t>(n_ops, 1));
+        mhap_align_paths_copy(paths, RA.op_offsets.data(), RA.ops.data());
+        mhap_align_paths_free(paths);
+        kept.clear(); kv.clear();
+        RA.vote_offsets.assign(1, 0); RA.vote_ops.clear();
+        for (int64_t i = 0; i < n; i++) {   // (the first pass's rule once more: nothing is dropped here unless the aligner differs)
+          const mhap_record& r = out[(size_t)i];
+          const bool none = r.score == 0.0 && r.a1 == 0 && r.a2 == 0 && r.b1 == 0 && r.b2 == 0;
+          if (none || r.score < RA.min_identity) continue;
+          kept.push_back(r); kv.push_back(vb[(size_t)(q0 + i)]);
+          RA.vote_ops.insert(RA.vote_ops.end(), RA.ops.begin() + RA.op_offsets[(size_t)i], RA.ops.begin() + RA.op_offsets[(size_t)i + 1]);
+          RA.vote_offsets.push_back((int64_t)RA.vote_ops.size());
+        }
+        mhap_align_paths* kept_paths = nullptr;
+        if (mhap_align_paths_from_runs(RA.vote_offsets.data(), (int64_t)kept.size(), RA.vote_ops.data(), &kept_paths) != MHAP_OK) die("the paths of the selected overlaps");
+        const int rc = mhap_correct_add_views(RA.correct, kept.data(), (int64_t)kept.size(), kept_paths, kv.empty() ? views.data() : kv.data());
+        mhap_align_paths_free(kept_paths);
+        chk(E.h, rc);
+      }
+      RA.correct_seconds += now() - tc;
+    }
+  }
   if (RA.correct) {   // the call for every read, after the last batch has voted; the FASTA file is all it writes
     const double tc = now();
     const int64_t nr = (int64_t)RA.ids.size();

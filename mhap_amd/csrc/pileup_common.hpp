@@ -1,6 +1,7 @@
 // pileup_common.hpp — what "read trimming" (trim_kernels.hip) and "repeat marking" (repeat_kernels.hip) share, written once: the
 // per-base difference array of a table of reads, the kernel that piles records up on it, the tile step that turns differences into
-// coverage, and the host side of a session up to the add (the table of reads, the packed records, the queued uploads).
+// coverage, and the host side of a session up to the add (the table of reads, the packed records, the queued uploads).  The table
+// and the records without the difference array (ReadTable) are what "overlap selection" (select_kernels.hip) takes from here.
 //
 // Layout: read r owns lengths[r] + 1 int32 slots at an offset rounded up to four slots, so that a read's slots begin on a 16-byte
 // word; the array is zeroed once.  A tile is PILE_TILE positions: four 16-byte loads per lane of a workgroup of 256, each contiguous
@@ -123,17 +124,17 @@ __device__ inline void pile_scan_tile(const T (&v)[PILE_LOADS], int lane, int wa
 
 inline unsigned blocks256(int64_t n) { return (unsigned)((n + 255) / 256); }
 
-// The host side that both sessions begin with: the table of reads, where each read's slots are, the records of a call as items,
-// the uploads an add has queued, and the device arrays of the table and the difference array.
-struct Pile {
+// The host side that every session over a table of reads begins with ("read trimming", "repeat marking", "overlap selection"): the
+// table, the records of a call checked and packed as items, and the uploads an add has queued.
+struct ReadTable {
   mhap_handle* h = nullptr;
-  int64_t n_reads = 0, n_records = 0, bases_in = 0, n_slots = 0;
-  std::vector<int64_t> ids, slot_off;                     // slot_off[r]: read r's first slot of the difference array
-  std::vector<int32_t> lengths, order;                    // order: the reads longest first (the upload reads it until the begin has waited)
+  int64_t n_reads = 0, n_records = 0;
+  std::vector<int64_t> ids;
+  std::vector<int32_t> lengths;
   std::unordered_map<int64_t, int32_t> by_id;
   struct Pending { std::vector<GItem> host; hipEvent_t ev = nullptr; };   // packed records an upload may still be reading
   std::deque<Pending> pending;
-  DevBuf d_lengths, d_off, d_order, diff, items;
+  DevBuf d_lengths, items;
 
   void reap(bool all) {
     while (!pending.empty() && (all || hipEventQuery(pending.front().ev) == hipSuccess)) {
@@ -142,8 +143,8 @@ struct Pile {
     }
     (void)hipGetLastError();   // (an event that has not passed is no error of the call that looked)
   }
-  void release_pile() {
-    for (DevBuf* b : {&d_lengths, &d_off, &d_order, &diff, &items}) b->release();
+  void release_table() {
+    for (DevBuf* b : {&d_lengths, &items}) b->release();
   }
 
   // the arguments every begin refuses; false with the handle's message set
@@ -158,32 +159,15 @@ struct Pile {
     return true;
   }
 
-  // the table on the host and on the device, the difference array zeroed; queued on the handle's stream, not waited for
-  hipError_t begin_pile(const HandleView& v, mhap_handle* handle, const int64_t* read_ids, const int32_t* lens, int64_t n) {
+  // the table on the host and the lengths on the device; queued on the handle's stream, not waited for
+  hipError_t begin_table(const HandleView& v, mhap_handle* handle, const int64_t* read_ids, const int32_t* lens, int64_t n) {
     h = handle; n_reads = n;
     ids.assign(read_ids, read_ids + n);
     lengths.assign(lens, lens + n);
     by_id.reserve((size_t)n * 2);
-    slot_off.resize((size_t)n + 1);
-    for (int64_t i = 0; i < n; i++) {
-      by_id.emplace(read_ids[i], (int32_t)i);   // (the first read of an id wins, as in mhap_realign_plan)
-      slot_off[(size_t)i] = n_slots;
-      n_slots += ((int64_t)lens[i] + 4) & ~(int64_t)3;
-      bases_in += lens[i];
-    }
-    slot_off[(size_t)n] = n_slots;
-    order.resize((size_t)n);   // the long workgroups start early
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return lens[a] > lens[b]; });
-    const size_t nr = (size_t)std::max<int64_t>(n, 1), db = 4 * (size_t)std::max<int64_t>(n_slots, 4);
-    hipError_t e = d_lengths.ensure(4 * nr);
-    if (e == hipSuccess) e = d_order.ensure(4 * nr);
-    if (e == hipSuccess) e = d_off.ensure(8 * (nr + 1));
-    if (e == hipSuccess) e = diff.ensure(db);
+    for (int64_t i = 0; i < n; i++) by_id.emplace(read_ids[i], (int32_t)i);   // (the first read of an id wins, as in mhap_realign_plan)
+    hipError_t e = d_lengths.ensure(4 * (size_t)std::max<int64_t>(n, 1));
     if (e == hipSuccess && n > 0) e = hipMemcpyAsync(d_lengths.p, lengths.data(), 4 * (size_t)n, hipMemcpyHostToDevice, v.stream);
-    if (e == hipSuccess && n > 0) e = hipMemcpyAsync(d_order.p, order.data(), 4 * (size_t)n, hipMemcpyHostToDevice, v.stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_off.p, slot_off.data(), 8 * ((size_t)n + 1), hipMemcpyHostToDevice, v.stream);
-    if (e == hipSuccess) e = hipMemsetAsync(diff.p, 0, db, v.stream);
     return e;
   }
   // the records of a call as items; a refused record leaves its message in err
@@ -217,28 +201,30 @@ struct Pile {
     return true;
   }
 
-  // an add: the records are checked (a refused call queues nothing), uploaded and piled up under P; nothing waits
-  int add_records(const char* who, const mhap_record* recs, int64_t n, const TParams& P, u64* d_eligible) {
-    HandleView v = handle_view(h);
+  // The front of an add: the records are checked (a refused call queues nothing), packed into p and their upload into `items` is
+  // queued.  MHAP_OK with p.ev == nullptr: n == 0, nothing to do.  The caller launches its kernel on the stream and calls commit_add.
+  int queue_add(const HandleView& v, const char* who, const mhap_record* recs, int64_t n, Pending& p) {
     if (n < 0 || (n > 0 && !recs)) { *v.err = std::string(who) + ": null or negative argument"; return MHAP_E_INVALID; }
     if (n > INT32_MAX) { *v.err = std::string(who) + ": more than 2^31 - 1 records in one call"; return MHAP_E_INVALID; }
     reap(false);
     if (n == 0) return MHAP_OK;
-    Pending p;
     if (!pack_records(who, recs, n, p.host, *v.err)) return MHAP_E_INVALID;
     (void)hipSetDevice(v.device);
     hipError_t e = items.ensure(sizeof(GItem) * (size_t)n);   // (a larger buffer frees the old one, which waits for the device)
     if (e == hipSuccess) e = hipEventCreateWithFlags(&p.ev, hipEventDisableTiming);
-    if (e != hipSuccess) return hip_fail(v, who, "hipMalloc of the records", e);
+    if (e != hipSuccess) { p.ev = nullptr; return hip_fail(v, who, "hipMalloc of the records", e); }
     e = hipMemcpyAsync(items.p, p.host.data(), sizeof(GItem) * (size_t)n, hipMemcpyHostToDevice, v.stream);
     if (e != hipSuccess) {   // nothing was queued behind the upload: nothing of this call stays
       (void)hipStreamSynchronize(v.stream);
       (void)hipEventDestroy(p.ev);
+      p.ev = nullptr;
       return hip_fail(v, who, "upload", e);
     }
-    hipLaunchKernelGGL(add_kernel, dim3(blocks256(n)), dim3(256), 0, v.stream, items.as<int4>(), n, d_lengths.as<int32_t>(),
-                       d_off.as<int64_t>(), P, diff.as<int32_t>(), d_eligible);
-    e = hipGetLastError();
+    return MHAP_OK;
+  }
+  // The back of an add, behind the caller's launch: the launch's error is looked at, the event recorded and the records counted.
+  int commit_add(const HandleView& v, const char* who, Pending& p, int64_t n) {
+    hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipEventRecord(p.ev, v.stream);
     if (e != hipSuccess) {
       (void)hipStreamSynchronize(v.stream);
@@ -273,6 +259,53 @@ struct Pile {
     if ((e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return hip_fail(v, who, "download", e);
     if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return hip_fail(v, who, "download", e);
     return MHAP_OK;
+  }
+};
+
+// The table with the per-base difference array of the trimming and the repeat marking on top.
+struct Pile : ReadTable {
+  int64_t bases_in = 0, n_slots = 0;
+  std::vector<int64_t> slot_off;                          // slot_off[r]: read r's first slot of the difference array
+  std::vector<int32_t> order;                             // the reads longest first (the upload reads it until the begin has waited)
+  DevBuf d_off, d_order, diff;
+
+  void release_pile() {
+    release_table();
+    for (DevBuf* b : {&d_off, &d_order, &diff}) b->release();
+  }
+
+  // the table on the host and on the device, the difference array zeroed; queued on the handle's stream, not waited for
+  hipError_t begin_pile(const HandleView& v, mhap_handle* handle, const int64_t* read_ids, const int32_t* lens, int64_t n) {
+    hipError_t e = begin_table(v, handle, read_ids, lens, n);
+    slot_off.resize((size_t)n + 1);
+    for (int64_t i = 0; i < n; i++) {
+      slot_off[(size_t)i] = n_slots;
+      n_slots += ((int64_t)lens[i] + 4) & ~(int64_t)3;
+      bases_in += lens[i];
+    }
+    slot_off[(size_t)n] = n_slots;
+    order.resize((size_t)n);   // the long workgroups start early
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return lens[a] > lens[b]; });
+    const size_t nr = (size_t)std::max<int64_t>(n, 1), db = 4 * (size_t)std::max<int64_t>(n_slots, 4);
+    if (e == hipSuccess) e = d_order.ensure(4 * nr);
+    if (e == hipSuccess) e = d_off.ensure(8 * (nr + 1));
+    if (e == hipSuccess) e = diff.ensure(db);
+    if (e == hipSuccess && n > 0) e = hipMemcpyAsync(d_order.p, order.data(), 4 * (size_t)n, hipMemcpyHostToDevice, v.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_off.p, slot_off.data(), 8 * ((size_t)n + 1), hipMemcpyHostToDevice, v.stream);
+    if (e == hipSuccess) e = hipMemsetAsync(diff.p, 0, db, v.stream);
+    return e;
+  }
+
+  // an add: the records are checked (a refused call queues nothing), uploaded and piled up under P; nothing waits
+  int add_records(const char* who, const mhap_record* recs, int64_t n, const TParams& P, u64* d_eligible) {
+    HandleView v = handle_view(h);
+    Pending p;
+    const int rc = queue_add(v, who, recs, n, p);
+    if (rc != MHAP_OK || !p.ev) return rc;
+    hipLaunchKernelGGL(add_kernel, dim3(blocks256(n)), dim3(256), 0, v.stream, items.as<int4>(), n, d_lengths.as<int32_t>(),
+                       d_off.as<int64_t>(), P, diff.as<int32_t>(), d_eligible);
+    return commit_add(v, who, p, n);
   }
 };
 

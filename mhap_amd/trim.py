@@ -14,7 +14,8 @@ included: `id length begin end runs covered flags`, tab-separated; --records wri
 void ones left out.  One line on stderr gives the counts.
 With --repeat-filter the refined overlaps that lie in nothing but repeat are set aside first and count as no support (`python -m
 mhap_amd.repeats`; "repeat marking" in the same header, with its two-copy limit); one more line on stderr, in front.
-Not done: a second round on the trimmed overlaps, selection of best overlaps.
+Not done: a second round on the trimmed overlaps; no selection of best overlaps in front of the trimming (python -m mhap_amd.best_overlaps
+selects for the read correction only).
 """
 import argparse
 import sys
