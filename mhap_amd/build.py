@@ -156,7 +156,7 @@ def build(force=False, verbose=False, variants=()):
         cli_src = os.path.join(CSRC, src)
         cmd = [hipcc, "-O2", "-std=c++17", "-pthread", cli_src, "-o", exe, f"-L{LIBDIR}", "-lmhaphip",
                "-Wl,-rpath,$ORIGIN"]
-        dg_cli = _digest([cli_src, os.path.join(CSRC, HEADERS[-1])], cmd[1:] + [dg])
+        dg_cli = _digest([cli_src, os.path.join(CSRC, "cli_pipeline.hpp"), os.path.join(CSRC, HEADERS[-1])], cmd[1:] + [dg])
         if force or _stale(exe, dg_cli):
             if verbose:
                 print(" ".join(cmd), file=sys.stderr)

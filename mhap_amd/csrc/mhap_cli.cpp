@@ -7,21 +7,13 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
-#include <algorithm>
-#include <chrono>
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <map>
-#include <string>
 #include <thread>
-#include <vector>
 
-#include "../../include/mhap_hip.h"
+#include "cli_pipeline.hpp"   // everything behind --realign (the realigned batch, the stages, their wiring), and the standard headers both files use
 
 namespace {
+using namespace cli;
 
 struct Opt { std::string help; bool is_flag; std::string value; bool set = false; };
 struct Options {
@@ -74,7 +66,6 @@ struct Options {
   }
 };
 
-double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 bool exists(const std::string& p) { struct stat st; return stat(p.c_str(), &st) == 0; }
 bool is_dir(const std::string& p) { struct stat st; return stat(p.c_str(), &st) == 0 && S_ISDIR(st.st_mode); }
 bool ends_with(const std::string& s, const std::string& e) { return s.size() >= e.size() && s.compare(s.size() - e.size(), e.size(), e) == 0; }
@@ -90,9 +81,6 @@ std::vector<std::string> list_files(const std::string& path) {   // non-hidden e
   return out;
 }
 
-[[noreturn]] void die(const std::string& m) { fprintf(stderr, "Exception in mhap-hip: %s\n", m.c_str()); exit(1); }
-void chk(mhap_handle* h, int rc) { if (rc != MHAP_OK) die(std::string(mhap_last_error(h)) + " (code " + std::to_string(rc) + ")"); }
-
 // One GPU (a handle) or several (a group: one rank per device, reads dealt round-robin, the exchange inside the library).
 struct Engine {
   mhap_handle* h = nullptr;
@@ -103,10 +91,6 @@ struct Engine {
     if (rc == MHAP_OK) return;
     die(std::string(g ? mhap_group_last_error(g) : mhap_last_error(h)) + " (code " + std::to_string(rc) + ")");
   }
-  void add_reads(const mhap_fasta& fa) const {
-    if (fa.n <= 0) return;
-    check(g ? mhap_group_add_reads(g, fa.bases, fa.offsets, fa.lengths, fa.ids, fa.n) : mhap_index_add_reads(h, fa.bases, fa.offsets, fa.lengths, fa.ids, fa.n));
-  }
   void add_scan(const mhap_fasta_scan* sc) const { check(g ? mhap_group_add_scan(g, sc) : mhap_index_add_scan(h, sc)); }
   void find_self(mhap_record_sink sink, void* user) const { check(g ? mhap_group_find_matches_self(g, sink, user) : mhap_find_matches_self(h, 0, -1, sink, user)); }
   void find_reads(const mhap_fasta& fa, mhap_record_sink sink, void* user) const {
@@ -115,7 +99,6 @@ struct Engine {
             : mhap_find_matches_reads(h, fa.bases, fa.offsets, fa.lengths, fa.ids, fa.n, sink, user));
   }
   mhap_stats stats() const { mhap_stats st; check(g ? mhap_group_get_stats(g, &st) : mhap_get_stats(h, &st)); return st; }
-  void clear() const { check(g ? mhap_group_clear(g) : mhap_index_clear(h)); }
   void destroy() { if (g) mhap_group_destroy(g); else if (h) mhap_destroy(h); g = nullptr; h = nullptr; }
 };
 
@@ -131,14 +114,6 @@ struct Rd {
   int64_t i64() { if (o + 8 > n) { ok = false; return 0; } uint64_t v = 0; for (int i = 0; i < 8; i++) v = (v << 8) | p[o++]; return (int64_t)v; }
   std::string utf() { if (o + 2 > n) { ok = false; return ""; } size_t l = ((size_t)p[o] << 8) | p[o + 1]; o += 2; if (o + l > n) { ok = false; return ""; } std::string s((const char*)p + o, l); o += l; return s; }
 };
-
-struct Headers { std::map<int64_t, std::string> byid; bool full = false; };
-Headers g_headers;
-
-std::string header_of(int64_t id) {   // SequenceId.getHeader (J/impl/SequenceId.java:102-108)
-  if (g_headers.full) { auto it = g_headers.byid.find(id); if (it != g_headers.byid.end()) return it->second; }
-  return std::to_string(id);
-}
 
 // --store-full-id: header = first token after '>' split on [\s,]+ (FastaData.java:155-156)
 // --store-full-id: names of the records just read (mhap_fasta.headers), keyed by the ids they were given
@@ -162,165 +137,44 @@ void collect_headers(mhap_fasta_scan* sc) {
 
 // the file the index is built from is mapped and scanned while the HIP runtime comes up
 struct Preload { std::string path; mhap_fasta_scan* scan = nullptr; } g_preload;
-// --realign: a one-byte-per-base copy of every read the search has seen (the index's, then each -q file's), and the handle that aligns
-struct Realign {
-  mhap_handle* h = nullptr;
-  int32_t band = 0; double min_identity = 0.0;
-  std::vector<uint8_t> bases; std::vector<int64_t> ids, offsets; std::vector<int32_t> lengths;
-  std::vector<mhap_record> out;
-  bool paf = false;                                   // --realign-paf: the alignments' paths too, printed as PAF lines
-  std::vector<int32_t> detail; std::vector<int64_t> op_offsets, row; std::vector<uint32_t> ops;   // row[k]: the batch row of kept record k
-  int64_t dropped = 0, kept = 0;
-  double seconds = 0.0;
-  mhap_correct_session* correct = nullptr;            // --correct: every kept record votes on both of its reads
-  std::vector<int64_t> vote_offsets; std::vector<uint32_t> vote_ops;
-  double correct_seconds = 0.0;
-  mhap_graph_session* graph = nullptr;                // --gfa: every kept record is classed for the string graph
-  double graph_seconds = 0.0;
-  bool keep_records = false;                          // --gfa-consensus: the kept records wait here until the graph is finished
-  std::vector<mhap_record> kept_records;
-  mhap_trim_session* trim = nullptr;                  // --trim: every kept record's intervals are piled up on its two reads
-  int32_t trim_penalty = 0;                           // > 0: each record is first cut to the best stretch of its path
-  std::vector<mhap_record> refined;
-  double trim_seconds = 0.0;
-  mhap_repeat_session* repeat = nullptr;              // --repeat-filter: the refined copies are piled up; every kept record waits to be judged
-  bool hold_plain = false;                            // the graph takes the survivors as realigned: those copies wait too
-  std::vector<mhap_record> held_refined, held_plain;
-  double repeat_seconds = 0.0;
-  mhap_select_session* select = nullptr;              // --best-overlaps: every kept record gives its two views to the selection
-  bool hold_select = false;                           // with --correct the votes wait: the records as they came and as realigned are held
-  std::vector<mhap_record> held_in, held_out;
-  double select_seconds = 0.0;
-  void add(const mhap_fasta& fa) {
-    for (int64_t i = 0; i < fa.n; i++) { ids.push_back(fa.ids[i]); offsets.push_back((int64_t)bases.size() + fa.offsets[i]); lengths.push_back(fa.lengths[i]); }
-    bases.insert(bases.end(), (const uint8_t*)fa.bases, (const uint8_t*)fa.bases + fa.total_bases);
-  }
-};
-struct Sink { FILE* out; std::string buf; int64_t n = 0; Realign* realign = nullptr; };
+// stdout: with --realign every batch goes through the pipeline first and what it keeps is printed, as 12 columns or as PAF
+struct Sink { Writer out{stdout}; Pipeline* pipeline = nullptr; };
 int sink_cb(const mhap_record* r, int64_t n, void* user) {
   Sink* s = (Sink*)user;
-  char line[512];
-  if (s->realign && n > 0) {   // the batch through the banded aligner; what has no alignment or too low an identity is dropped
-    Realign& R = *s->realign;
-    const double t = now();
-    R.out.resize((size_t)n);
-    int rc;
-    const bool vote_now = R.correct && !R.select;   // (with --best-overlaps the votes are cast after the last batch)
-    if (R.paf || vote_now || ((R.trim || R.repeat) && R.trim_penalty > 0)) {
-      R.detail.resize((size_t)n * 3);
-      mhap_align_paths* paths = nullptr;
-      rc = mhap_realign_records_paths(R.h, R.bases.data(), (int64_t)R.bases.size(), R.ids.data(), R.offsets.data(), R.lengths.data(),
-                                      (int64_t)R.ids.size(), r, n, R.band, R.out.data(), R.detail.data(), &paths);
-      if (rc == MHAP_OK) {
-        int64_t n_ops = 0;
-        mhap_align_paths_info(paths, nullptr, &n_ops);
-        R.op_offsets.resize((size_t)n + 1); R.ops.resize((size_t)std::max<int64_t>(n_ops, 1));
-        mhap_align_paths_copy(paths, R.op_offsets.data(), R.ops.data());
-        mhap_align_paths_free(paths);
-      }
-    } else {
-      rc = mhap_realign_records(R.h, R.bases.data(), (int64_t)R.bases.size(), R.ids.data(), R.offsets.data(), R.lengths.data(),
-                                (int64_t)R.ids.size(), r, n, R.band, R.out.data(), nullptr);
-    }
-    if (rc != MHAP_OK) { fprintf(stderr, "Exception in mhap-hip: %s (code %d)\n", mhap_last_error(R.h), rc); return 1; }
-    int64_t k = 0;
-    R.row.resize((size_t)n);
-    for (int64_t i = 0; i < n; i++) {
-      const mhap_record& o = R.out[(size_t)i];
-      const bool none = o.score == 0.0 && o.a1 == 0 && o.a2 == 0 && o.b1 == 0 && o.b2 == 0;
-      if (none || o.score < R.min_identity) continue;
-      R.row[(size_t)k] = i;
-      if (R.hold_select) R.held_in.push_back(r[i]);
-      R.out[(size_t)k++] = o;
-    }
-    R.dropped += n - k; R.kept += k;
-    R.seconds += now() - t;
-    const bool refine = (R.trim || R.repeat) && R.trim_penalty > 0;
-    if (R.select) {   // the kept records' views into the selection (queued: nothing waits)
-      const double ts = now();
-      rc = mhap_select_add(R.select, R.out.data(), k);
-      if (rc != MHAP_OK) { fprintf(stderr, "Exception in mhap-hip: %s (code %d)\n", mhap_last_error(R.h), rc); return 1; }
-      if (R.hold_select) R.held_out.insert(R.held_out.end(), R.out.data(), R.out.data() + k);
-      R.select_seconds += now() - ts;
-    }
-    if (vote_now || refine) {   // the kept records and their runs: into the vote table, and cut to their best stretch for the trimming
-      const double tc = now();
-      R.vote_offsets.assign(1, 0); R.vote_ops.clear();
-      for (int64_t i = 0; i < k; i++) {
-        const int64_t q = R.row[(size_t)i];
-        R.vote_ops.insert(R.vote_ops.end(), R.ops.begin() + R.op_offsets[(size_t)q], R.ops.begin() + R.op_offsets[(size_t)q + 1]);
-        R.vote_offsets.push_back((int64_t)R.vote_ops.size());
-      }
-      mhap_align_paths* kept_paths = nullptr;
-      rc = mhap_align_paths_from_runs(R.vote_offsets.data(), k, R.vote_ops.data(), &kept_paths);
-      if (rc == MHAP_OK && vote_now) rc = mhap_correct_add(R.correct, R.out.data(), k, kept_paths);   // (the dropped ones cast no vote)
-      if (vote_now) R.correct_seconds += now() - tc;
-      if (rc == MHAP_OK && refine) {
-        const double tt = now();
-        R.refined.resize((size_t)std::max<int64_t>(k, 1));
-        rc = mhap_trim_refine(R.h, R.out.data(), k, kept_paths, R.trim_penalty, R.refined.data());
-        R.trim_seconds += now() - tt;
-      }
-      mhap_align_paths_free(kept_paths);
-      if (rc != MHAP_OK) { fprintf(stderr, "Exception in mhap-hip: %s (code %d)\n", mhap_last_error(R.h), rc); return 1; }
-    }
-    const mhap_record* for_trim = refine ? R.refined.data() : R.out.data();
-    if (R.repeat) {   // the refined copies onto the pile-up (queued: nothing waits); trimming and graph take the survivors after the last batch
-      const double tr = now();
-      rc = mhap_repeat_add(R.repeat, for_trim, k);
-      if (rc != MHAP_OK) { fprintf(stderr, "Exception in mhap-hip: %s (code %d)\n", mhap_last_error(R.h), rc); return 1; }
-      R.held_refined.insert(R.held_refined.end(), for_trim, for_trim + k);
-      if (R.hold_plain) R.held_plain.insert(R.held_plain.end(), R.out.data(), R.out.data() + k);
-      R.repeat_seconds += now() - tr;
-    } else if (R.trim) {   // the kept records onto the coverage of their reads (queued: nothing waits)
-      const double tt = now();
-      rc = mhap_trim_add(R.trim, for_trim, k);
-      if (rc != MHAP_OK) { fprintf(stderr, "Exception in mhap-hip: %s (code %d)\n", mhap_last_error(R.h), rc); return 1; }
-      R.trim_seconds += now() - tt;
-    }
-    if (R.graph && !R.repeat) {   // the kept records into the string graph (queued: nothing waits)
-      const double tg = now();
-      rc = mhap_graph_add(R.graph, R.out.data(), k);
-      if (rc != MHAP_OK) { fprintf(stderr, "Exception in mhap-hip: %s (code %d)\n", mhap_last_error(R.h), rc); return 1; }
-      R.graph_seconds += now() - tg;
-    }
-    if (R.keep_records && !R.repeat) R.kept_records.insert(R.kept_records.end(), for_trim, for_trim + k);   // (with --trim the graph takes what the trimming took)
-    r = R.out.data(); n = k;
+  const Batch* b = nullptr;
+  if (s->pipeline && n > 0) {
+    if (!(b = s->pipeline->batch(r, n))) return 1;
+    r = b->out.data(); n = b->k;
   }
-  if (s->realign && s->realign->paf) {   // one PAF line per kept record; the names are columns 1 and 2 of the 12-column line
-    const Realign& R = *s->realign;
-    std::string pl;
-    for (int64_t i = 0; i < n; i++) {
-      const int64_t q = R.row[(size_t)i], o0 = R.op_offsets[(size_t)q], o1 = R.op_offsets[(size_t)q + 1];
+  char line[512];
+  std::string pl;
+  for (int64_t i = 0; i < n; i++) {
+    if (b && s->pipeline->paf) {   // one PAF line per kept record; the names are columns 1 and 2 of the 12-column line
+      const int64_t q = b->row[(size_t)i], o0 = b->op_offsets[(size_t)q], o1 = b->op_offsets[(size_t)q + 1];
       const std::string qn = header_of(r[i].from_id), tn = header_of(r[i].to_id);
       pl.resize(256 + qn.size() + tn.size() + 12 * (size_t)(o1 - o0));
-      const int len = mhap_format_paf(&r[i], R.detail.data() + 3 * q, R.ops.data() + o0, o1 - o0, qn.c_str(), tn.c_str(), &pl[0], pl.size());
+      const int len = mhap_format_paf(&r[i], b->detail.data() + 3 * q, b->ops.data() + o0, o1 - o0, qn.c_str(), tn.c_str(), &pl[0], pl.size());
       if (len < 0 || (size_t)len >= pl.size()) { fprintf(stderr, "Exception in mhap-hip: mhap_format_paf failed\n"); return 1; }
-      s->buf.append(pl.data(), (size_t)len);
-      s->buf.push_back('\n');
-      if (s->buf.size() > (8u << 20)) { fwrite(s->buf.data(), 1, s->buf.size(), s->out); s->buf.clear(); }
+      s->out.put(pl.data(), (size_t)len);
+    } else {
+      const int len = mhap_format_record(&r[i], line, sizeof line);
+      const char* p = line;
+      if (g_headers.full) {   // same formatter, headers swapped in for the two id columns
+        int sp = 0; while (*p && sp < 2) { if (*p == ' ') sp++; p++; }
+        s->out.put(header_of(r[i].from_id) + " " + header_of(r[i].to_id) + " ");
+      }
+      s->out.put(p, (size_t)(line + len - p));
     }
-    s->n += n;
-    return 0;
+    s->out.put("\n", 1);
   }
-  for (int64_t i = 0; i < n; i++) {
-    if (!g_headers.full) { int len = mhap_format_record(&r[i], line, sizeof line); s->buf.append(line, (size_t)len); }
-    else {
-      // same formatter, headers swapped in for the two id columns
-      int len = mhap_format_record(&r[i], line, sizeof line);
-      const char* p = line; int sp = 0; while (*p && sp < 2) { if (*p == ' ') sp++; p++; }
-      s->buf += header_of(r[i].from_id) + " " + header_of(r[i].to_id) + " "; s->buf.append(p, (size_t)(line + len - p));
-    }
-    s->buf.push_back('\n');
-    if (s->buf.size() > (8u << 20)) { fwrite(s->buf.data(), 1, s->buf.size(), s->out); s->buf.clear(); }   // 8 MB buffer (Utils.BUFFER_BYTE_SIZE)
-  }
-  s->n += n;
   return 0;
 }
-void sink_flush(Sink& s) { if (!s.buf.empty()) fwrite(s.buf.data(), 1, s.buf.size(), s.out); s.buf.clear(); fflush(s.out); }
+void sink_flush(Sink& s) { s.out.flush(); fflush(stdout); }
 
 // FrequencyCounts file -> (hash, fraction) arrays (J/sketch/FrequencyCounts.java:63-229)
 void load_filter(const Engine& E, const Options& o) {
+  const double t = now();
+  fprintf(stderr, "Reading in filter file %s.\n", o.s("-f").c_str());
   const double rw = o.d("--repeat-weight");
   const double offset = (rw >= 0.0 && rw < 1.0) ? rw : 0.0;   // MhapMain.java:346-350
   char sizes[256];
@@ -333,6 +187,7 @@ void load_filter(const Engine& E, const Options& o) {
     chk(h, rc);
   }
   fprintf(stderr, "Read in k-mer filter for sizes: [%s]\n", sizes);
+  fprintf(stderr, "Time (s) to read filter file: %g\n", now() - t);
 }
 
 // `.dat` reader (SequenceSketchStreamer.readFromBinary :278-320 + SequenceSketch.fromByteStream :61-96)
@@ -366,8 +221,7 @@ void read_dat(const std::string& path, int64_t offset, int H, int S, bool fwd_on
 // `.dat` writer (SequenceSketchStreamer.writeToBinary :322-395; SequenceSketch.getAsByteArray :123-148)
 void write_dat(mhap_handle* h, const std::string& path, int H, int S, int k2) {
   int64_t n = 0; chk(h, mhap_index_size(h, &n));
-  FILE* f = fopen(path.c_str(), "wb");
-  if (!f) die("cannot write " + path);
+  Writer w(path);
   const int64_t CH = 4096;
   std::vector<int64_t> ids(CH); std::vector<uint8_t> fwd(CH), st(CH); std::vector<int32_t> sl(CH), mh(CH * H), od(CH * (size_t)S * 2), osz(CH), olen(CH);
   for (int64_t e0 = 0; e0 < n; e0 += CH) {
@@ -383,9 +237,9 @@ void write_dat(mhap_handle* h, const std::string& path, int H, int S, int k2) {
       for (int i = 0; i < osz[e]; i++) { put32(pay, od[((size_t)e * S + i) * 2]); put32(pay, od[((size_t)e * S + i) * 2 + 1]); }
       put8(out, fwd[e]); put32(out, (int32_t)pay.size()); out += pay;
     }
-    fwrite(out.data(), 1, out.size(), f);
+    w.put(out);
   }
-  fclose(f);
+  w.close();
 }
 
 int64_t add_file_to_index(const Engine& E, const std::string& path, int64_t id_offset, const Options& o, int64_t* strands) {
@@ -418,10 +272,7 @@ int64_t add_file_to_index(const Engine& E, const std::string& path, int64_t id_o
   return st.strands_indexed / 2;
 }
 
-}  // namespace
-
-int main(int argc, char** argv) {
-  Options o;
+void declare_options(Options& o) {
   // --num-threads defaults to the CPUs the process may use: the hardware threads, capped by the container's CPU quota (cgroup v2)
   unsigned hc = std::max(1u, std::thread::hardware_concurrency());
   if (FILE* f = fopen("/sys/fs/cgroup/cpu.max", "r")) {
@@ -489,17 +340,32 @@ int main(int argc, char** argv) {
   o.add("--best-table", "With --best-overlaps, write one line per read to this file: read_id entries kept threshold.", "");
   o.add("--trim-fasta", "With --trim, write the trimmed reads to this FASTA file; deleted reads are left out.", "");
   o.add("--trim-table", "With --trim, write one line per read to this file: id length begin end runs covered flags.", "");
-  if (!o.parse(argc, argv)) return 0;
+}
 
-  auto bad = [&](const char* m) { printf("%s\n", m); exit(1); };
+[[noreturn]] void bad(const std::string& m) { printf("%s\n", m.c_str()); exit(1); }
+// `rest` of "NAME belongs to ...: give ... too." for every given name whose owner is not
+void owned(const Options& o, std::initializer_list<const char*> names, bool owner, const char* rest) {
+  for (const char* n : names) if (o.isset(n) && !owner) bad(std::string(n) + rest);
+}
+// what every stage flag asks for: --realign, self overlaps, the reads' bases, one GPU
+void stage_flag(const Options& o, size_t n_devs, const std::string& flag, const char* uses, const char* does, const char* needs) {
+  if (!o.b("--realign")) bad(flag + " " + uses + " the alignments of --realign: give --realign too.");
+  if (!o.s("-q").empty()) bad(flag + " " + does + " the reads of -s from their overlaps with each other: it takes no -q.");
+  if (ends_with(o.s("-s"), ".dat")) bad(flag + " needs " + needs + ": give FASTA files, not .dat sketches.");
+  if (n_devs > 1) bad(flag + " runs on one GPU: give one device (--gpus 1).");
+}
+
+// Every refusal happens here, before a handle exists: the MHAP-compatible options (MhapMain.java:93-380) and the settings line on stderr,
+// the ranks, then the flags of the stages behind --realign in the order they were added (the first failing check is the one the user sees).
+std::vector<int32_t> check_options(Options& o) {
   const int settings = o.i("--settings");
-  if (settings < 0 || settings > 3) { printf("Please enter valid --settings flag. See options below:\n%s", o.helpText().c_str()); return 1; }
+  if (settings < 0 || settings > 3) { printf("Please enter valid --settings flag. See options below:\n%s", o.helpText().c_str()); exit(1); }
   if (settings == 1) { o.setdef("-k", "16"); o.setdef("--num-min-matches", "3"); o.setdef("--num-hashes", "512"); o.setdef("--threshold", "0.78"); o.setdef("--ordered-sketch-size", "1536"); o.setdef("--ordered-kmer-size", "12"); }
   if (settings == 2) { o.setdef("-k", "16"); o.setdef("--num-min-matches", "3"); o.setdef("--num-hashes", "256"); o.setdef("--threshold", "0.80"); o.setdef("--ordered-sketch-size", "1000"); o.setdef("--ordered-kmer-size", "14"); }
   if (settings == 3) { o.setdef("-k", "16"); o.setdef("--num-min-matches", "2"); o.setdef("--num-hashes", "768"); o.setdef("--threshold", "0.73"); o.setdef("--ordered-sketch-size", "1536"); o.setdef("--ordered-kmer-size", "12"); }
-  if (o.s("-s").empty() && o.s("-p").empty()) { printf("Please set the -s or the -p options. See options below:\n%s", o.helpText().c_str()); return 1; }
-  if (!o.s("-p").empty() && o.s("-q").empty()) { printf("Please set the -q option. See options below:\n%s", o.helpText().c_str()); return 1; }
-  for (const char* k : {"-p", "-s", "-q", "-f"}) if (!o.s(k).empty() && !exists(o.s(k))) { printf("Could not find requested file/folder: %s\n", o.s(k).c_str()); return 1; }
+  if (o.s("-s").empty() && o.s("-p").empty()) { printf("Please set the -s or the -p options. See options below:\n%s", o.helpText().c_str()); exit(1); }
+  if (!o.s("-p").empty() && o.s("-q").empty()) { printf("Please set the -q option. See options below:\n%s", o.helpText().c_str()); exit(1); }
+  for (const char* k : {"-p", "-s", "-q", "-f"}) if (!o.s(k).empty() && !exists(o.s(k))) { printf("Could not find requested file/folder: %s\n", o.s(k).c_str()); exit(1); }
   if (o.i("--num-threads") <= 0) bad("Number of threads must be positive.");
   if (o.i("-k") <= 0) bad("k-mer size must be positive.");
   if (o.i("--num-min-matches") <= 0) bad("Minimum number of matches must be positive.");
@@ -511,14 +377,7 @@ int main(int argc, char** argv) {
   g_headers.full = o.b("--store-full-id");
   setenv("MHAP_HOST_THREADS", o.s("--num-threads").c_str(), 0);
   fprintf(stderr, "Running with these settings:\n%s", o.dump().c_str());
-
-  mhap_params P; mhap_default_params(&P);
-  P.kmer_size = o.i("-k"); P.num_hashes = o.i("--num-hashes"); P.ordered_kmer_size = o.i("--ordered-kmer-size");
-  P.ordered_sketch_size = o.i("--ordered-sketch-size"); P.num_min_matches = o.i("--num-min-matches");
-  P.min_store_length = o.i("--min-store-length"); P.min_olap_length = o.i("--min-olap-length"); P.device = o.i("--device");
-  P.threshold = o.d("--threshold"); P.max_shift = o.d("--max-shift"); P.repeat_weight = o.d("--repeat-weight");
-  // ranks: --devices a,b,c  |  --gpus N from --device on  |  one handle
-  std::vector<int32_t> devs;
+  std::vector<int32_t> devs;   // ranks: --devices a,b,c  |  --gpus N from --device on  |  one handle
   if (!o.s("--devices").empty()) {
     const std::string dl = o.s("--devices");
     for (size_t i = 0; i < dl.size();) { size_t j = dl.find(',', i); if (j == std::string::npos) j = dl.size(); if (j > i) devs.push_back(atoi(dl.substr(i, j - i).c_str())); i = j + 1; }
@@ -527,92 +386,70 @@ int main(int argc, char** argv) {
     for (int r = 0; r < o.i("--gpus"); r++) devs.push_back(o.i("--device") + r);
   }
   if (devs.empty()) bad("No device given.");
-  const bool precompute = !o.s("-p").empty();
-  const bool realign = o.b("--realign") && !precompute;
-  if (o.b("--realign-paf") && !o.b("--realign")) bad("--realign-paf prints the alignments of --realign: give --realign too.");
-  const bool correct = o.isset("--correct");
-  if (correct) {   // refused before a handle exists
-    if (!o.b("--realign")) bad("--correct votes with the alignments of --realign: give --realign too.");
-    if (!o.s("-q").empty()) bad("--correct corrects the reads of -s from their overlaps with each other: it takes no -q.");
-    if (ends_with(o.s("-s"), ".dat")) bad("--correct needs the reads' bases: give FASTA files, not .dat sketches.");
-    if (devs.size() > 1) bad("--correct runs on one GPU: give one device (--gpus 1).");
+  const size_t n_devs = devs.size();
+  owned(o, {"--realign-paf"}, o.b("--realign"), " prints the alignments of --realign: give --realign too.");
+  if (o.isset("--correct")) {
+    stage_flag(o, n_devs, "--correct", "votes with", "corrects", "the reads' bases");
     if (o.s("--correct").empty()) bad("--correct needs the name of the FASTA file to write.");
     if (o.i("--correct-min-coverage") < 1) bad("The correction's minimum coverage must be >=1.");
   }
+  const char* realigned = "the overlaps realigned on the reads' bases";
   const bool best = o.isset("--best-overlaps") && o.i("--best-overlaps") != 0;
-  for (const char* n : {"--best-min-span", "--best-table"})   // refused before a handle exists
-    if (o.isset(n) && !best) bad((std::string(n) + " belongs to --best-overlaps: give --best-overlaps too.").c_str());
-  if (best) {   // refused before a handle exists
+  owned(o, {"--best-min-span", "--best-table"}, best, " belongs to --best-overlaps: give --best-overlaps too.");
+  if (best) {
     if (o.i("--best-overlaps") < 0) bad("The value of --best-overlaps must be >=0.");
-    if (!o.b("--realign")) bad("--best-overlaps selects among the alignments of --realign: give --realign too.");
-    if (!o.s("-q").empty()) bad("--best-overlaps selects for the reads of -s from their overlaps with each other: it takes no -q.");
-    if (ends_with(o.s("-s"), ".dat")) bad("--best-overlaps needs the overlaps realigned on the reads' bases: give FASTA files, not .dat sketches.");
-    if (devs.size() > 1) bad("--best-overlaps runs on one GPU: give one device (--gpus 1).");
+    stage_flag(o, n_devs, "--best-overlaps", "selects among", "selects for", realigned);
     if (o.i("--best-min-span") < 0) bad("The value of --best-min-span must be >=0.");
     if (o.isset("--best-table") && o.s("--best-table").empty()) bad("--best-table needs the name of the file to write.");
   }
   const bool gfa = o.isset("--gfa");
-  if (o.isset("--gfa-unitigs")) {   // refused before a handle exists
-    if (!gfa) bad("--gfa-unitigs compacts the graph of --gfa: give --gfa too.");
-    if (o.s("--gfa-unitigs").empty()) bad("--gfa-unitigs needs the name of the GFA file to write.");
-  }
-  for (const char* n : {"--gfa-clean", "--gfa-tip-reads", "--gfa-bubble-bases", "--gfa-clean-rounds"})   // refused before a handle exists
-    if (o.isset(n) && !gfa) bad((std::string(n) + " cleans the graph of --gfa: give --gfa too.").c_str());
+  owned(o, {"--gfa-unitigs"}, gfa, " compacts the graph of --gfa: give --gfa too.");
+  if (o.isset("--gfa-unitigs") && o.s("--gfa-unitigs").empty()) bad("--gfa-unitigs needs the name of the GFA file to write.");
+  owned(o, {"--gfa-clean", "--gfa-tip-reads", "--gfa-bubble-bases", "--gfa-clean-rounds"}, gfa, " cleans the graph of --gfa: give --gfa too.");
   if (o.i("--gfa-tip-reads") < 0 || o.i("--gfa-bubble-bases") < 0 || o.i("--gfa-clean-rounds") < 1)
     bad("The values of --gfa-tip-reads and --gfa-bubble-bases must be >=0 and that of --gfa-clean-rounds >=1.");
-  for (const char* n : {"--gfa-consensus", "--gfa-consensus-fasta", "--gfa-consensus-min-cov"})   // refused before a handle exists
-    if (o.isset(n) && !o.isset("--gfa-unitigs")) bad((std::string(n) + " works on the unitigs of --gfa-unitigs: give --gfa-unitigs too.").c_str());
-  for (const char* n : {"--gfa-consensus-fasta", "--gfa-consensus-min-cov"})
-    if (o.isset(n) && !o.b("--gfa-consensus")) bad((std::string(n) + " belongs to --gfa-consensus: give --gfa-consensus too.").c_str());
+  owned(o, {"--gfa-consensus", "--gfa-consensus-fasta", "--gfa-consensus-min-cov"}, o.isset("--gfa-unitigs"), " works on the unitigs of --gfa-unitigs: give --gfa-unitigs too.");
+  owned(o, {"--gfa-consensus-fasta", "--gfa-consensus-min-cov"}, o.b("--gfa-consensus"), " belongs to --gfa-consensus: give --gfa-consensus too.");
   if (o.isset("--gfa-consensus-fasta") && o.s("--gfa-consensus-fasta").empty()) bad("--gfa-consensus-fasta needs the name of the FASTA file to write.");
   if (o.i("--gfa-consensus-min-cov") < 1) bad("The value of --gfa-consensus-min-cov must be >=1.");
-  if (gfa) {   // refused before a handle exists
-    if (!o.b("--realign")) bad("--gfa builds the graph from the alignments of --realign: give --realign too.");
-    if (!o.s("-q").empty()) bad("--gfa lays out the reads of -s from their overlaps with each other: it takes no -q.");
-    if (ends_with(o.s("-s"), ".dat")) bad("--gfa needs the overlaps realigned on the reads' bases: give FASTA files, not .dat sketches.");
-    if (devs.size() > 1) bad("--gfa runs on one GPU: give one device (--gpus 1).");
+  if (gfa) {
+    stage_flag(o, n_devs, "--gfa", "builds the graph from", "lays out", realigned);
     if (o.s("--gfa").empty()) bad("--gfa needs the name of the GFA file to write.");
     if (o.i("--gfa-max-hang") < 0 || o.i("--gfa-min-overlap") < 0 || o.i("--gfa-fuzz") < 0) bad("The values of --gfa-max-hang, --gfa-min-overlap and --gfa-fuzz must be >=0.");
   }
-  const bool trim = o.b("--trim");
-  const bool repeat = o.b("--repeat-filter");
-  for (const char* n : {"--trim-min-cov", "--trim-end-clip", "--trim-min-span", "--trim-fasta", "--trim-table"})   // refused before a handle exists
-    if (o.isset(n) && !trim) bad((std::string(n) + " belongs to --trim: give --trim too.").c_str());
-  if (o.isset("--trim-penalty") && !trim && !repeat) bad("--trim-penalty belongs to --trim: give --trim too.");
-  for (const char* n : {"--repeat-factor", "--repeat-max-cov", "--repeat-min-run", "--repeat-min-unique", "--repeat-table"})
-    if (o.isset(n) && !repeat) bad((std::string(n) + " belongs to --repeat-filter: give --repeat-filter too.").c_str());
-  if (repeat) {   // refused wherever --trim is, before a handle exists
-    if (!o.b("--realign")) bad("--repeat-filter piles up the alignments of --realign: give --realign too.");
-    if (!o.s("-q").empty()) bad("--repeat-filter marks the reads of -s from their overlaps with each other: it takes no -q.");
-    if (ends_with(o.s("-s"), ".dat")) bad("--repeat-filter needs the overlaps realigned on the reads' bases: give FASTA files, not .dat sketches.");
-    if (devs.size() > 1) bad("--repeat-filter runs on one GPU: give one device (--gpus 1).");
+  const bool trim = o.b("--trim"), repeat = o.b("--repeat-filter");
+  owned(o, {"--trim-min-cov", "--trim-end-clip", "--trim-min-span", "--trim-fasta", "--trim-table"}, trim, " belongs to --trim: give --trim too.");
+  owned(o, {"--trim-penalty"}, trim || repeat, " belongs to --trim: give --trim too.");
+  owned(o, {"--repeat-factor", "--repeat-max-cov", "--repeat-min-run", "--repeat-min-unique", "--repeat-table"}, repeat, " belongs to --repeat-filter: give --repeat-filter too.");
+  if (repeat) {
+    stage_flag(o, n_devs, "--repeat-filter", "piles up", "marks", realigned);
     if (o.i("--repeat-factor") < 100 || o.i("--repeat-max-cov") < 0 || o.i("--repeat-min-run") < 1 || o.i("--repeat-min-unique") < 0 || o.i("--trim-penalty") < 0)
       bad("The value of --repeat-factor must be >=100, that of --repeat-min-run >=1 and those of --repeat-max-cov, --repeat-min-unique and --trim-penalty >=0.");
     if (o.isset("--repeat-table") && o.s("--repeat-table").empty()) bad("--repeat-table needs the name of the file to write.");
   }
-  if (trim) {   // refused before a handle exists
-    if (!o.b("--realign")) bad("--trim piles up the alignments of --realign: give --realign too.");
-    if (!o.s("-q").empty()) bad("--trim trims the reads of -s from their overlaps with each other: it takes no -q.");
-    if (ends_with(o.s("-s"), ".dat")) bad("--trim needs the overlaps realigned on the reads' bases: give FASTA files, not .dat sketches.");
-    if (devs.size() > 1) bad("--trim runs on one GPU: give one device (--gpus 1).");
+  if (trim) {
+    stage_flag(o, n_devs, "--trim", "piles up", "trims", realigned);
     if (o.i("--trim-min-cov") < 1 || o.i("--trim-end-clip") < 0 || o.i("--trim-min-span") < 0 || o.i("--trim-penalty") < 0)
       bad("The value of --trim-min-cov must be >=1 and those of --trim-end-clip, --trim-min-span and --trim-penalty >=0.");
     for (const char* n : {"--trim-fasta", "--trim-table"})
-      if (o.isset(n) && o.s(n).empty()) bad((std::string(n) + " needs the name of the file to write.").c_str());
+      if (o.isset(n) && o.s(n).empty()) bad(std::string(n) + " needs the name of the file to write.");
   }
-  if (realign) {   // refused before a handle exists
+  if (o.b("--realign") && o.s("-p").empty()) {
     if (o.i("--realign-band") < 0) bad("The realignment band must be >=0.");
-    if (devs.size() > 1) bad("--realign runs on one GPU: give one device (--gpus 1).");
+    if (n_devs > 1) bad("--realign runs on one GPU: give one device (--gpus 1).");
     bool dat = ends_with(o.s("-s"), ".dat");
     if (!o.s("-q").empty()) for (const std::string& cf : list_files(o.s("-q"))) dat = dat || ends_with(cf, ".dat");
     if (dat) bad("--realign needs the reads' bases: give FASTA files, not .dat sketches.");
   }
+  return devs;
+}
+
+// mhap_create is mostly the HIP runtime coming up (~0.25 s): it runs on its own thread while this one maps and scans the FASTA file the index is built from
+Engine create_engine(const Options& o, mhap_params& P, std::vector<int32_t>& devs, bool precompute) {
   if (precompute && devs.size() > 1) { fprintf(stderr, "Usage 2 (-p) writes its .dat files from one GPU: using device %d only.\n", devs[0]); devs.resize(1); }
   Engine E; E.n = (int)devs.size();
   char err[512] = {0};
   const double t_create = now();
-  // mhap_create is mostly the HIP runtime coming up (~0.25 s): it runs on its own thread while this one reads and parses the
-  // FASTA file the index is built from
   int rc_create = MHAP_OK;
   std::thread creator([&]() {
     if (devs.size() == 1) { P.device = devs[0]; rc_create = mhap_create(&P, &E.h, err, sizeof err); }
@@ -628,473 +465,102 @@ int main(int argc, char** argv) {
   if (rc_create != MHAP_OK) die(err);
   if (getenv("MHAP_HOST_PROF")) fprintf(stderr, "[cli] mhap_create + first FASTA scan %.3f s\n", now() - t_create);
   if (E.g) fprintf(stderr, "Using %d GPU ranks (reads dealt round-robin; every rank indexes its share).\n", E.n);
+  return E;
+}
 
-  const double t_total = now();
-  if (!o.s("-f").empty()) {
+// Usage 2: precompute `.dat` (MhapMain.java:384-451)
+void precompute_dat(const Engine& E, const Options& o, const mhap_params& P) {
+  fprintf(stderr, "Processing FASTA files for binary compression...\n");
+  if (!is_dir(o.s("-q"))) die("Target directory doesn't exit.");
+  for (const std::string& pf : list_files(o.s("-p"))) {
     const double t = now();
-    fprintf(stderr, "Reading in filter file %s.\n", o.s("-f").c_str());
-    load_filter(E, o);
-    fprintf(stderr, "Time (s) to read filter file: %g\n", now() - t);
+    chk(E.h, mhap_index_clear(E.h));
+    int64_t strands = 0;
+    add_file_to_index(E, pf, 0, o, &strands);
+    std::string name = pf.substr(pf.find_last_of('/') + 1);
+    size_t dot = name.find_last_of('.'); if (dot != std::string::npos && dot > 0) name = name.substr(0, dot);
+    const std::string out = o.s("-q") + "/" + name + ".dat";
+    write_dat(E.h, out, P.num_hashes, P.ordered_sketch_size, P.ordered_kmer_size);
+    fprintf(stderr, "Processed %lld sequences (fwd and rev).\n", (long long)strands);
+    fprintf(stderr, "Read, hashed, and stored file %s to %s.\n", pf.c_str(), out.c_str());
+    fprintf(stderr, "Time (s): %g\n", now() - t);
   }
+}
 
-  if (precompute) {   // Usage 2: precompute `.dat` (MhapMain.java:384-451)
-    mhap_handle* h = E.h;
-    fprintf(stderr, "Processing FASTA files for binary compression...\n");
-    if (!is_dir(o.s("-q"))) die("Target directory doesn't exit.");
-    for (const std::string& pf : list_files(o.s("-p"))) {
-      const double t = now();
-      chk(h, mhap_index_clear(h));
-      int64_t strands = 0;
-      add_file_to_index(E, pf, 0, o, &strands);
-      std::string name = pf.substr(pf.find_last_of('/') + 1);
-      size_t dot = name.find_last_of('.'); if (dot != std::string::npos && dot > 0) name = name.substr(0, dot);
-      const std::string out = o.s("-q") + "/" + name + ".dat";
-      write_dat(h, out, P.num_hashes, P.ordered_sketch_size, P.ordered_kmer_size);
-      fprintf(stderr, "Processed %lld sequences (fwd and rev).\n", (long long)strands);
-      fprintf(stderr, "Read, hashed, and stored file %s to %s.\n", pf.c_str(), out.c_str());
-      fprintf(stderr, "Time (s): %g\n", now() - t);
-    }
-    fprintf(stderr, "Total time (s): %g\n", now() - t_total);
-    E.destroy();
-    return 0;
+// --realign: the reads of -s (ids as the index assigned them: FastaData's running count), every stage's parameters from its flags, and the sessions that begin before the search
+void begin_pipeline(const Options& o, mhap_handle* h, Pipeline& p) {
+  char err[512] = {0};
+  for (const std::string& sf : list_files(o.s("-s"))) {
+    mhap_fasta fa;
+    if (mhap_fasta_read(sf.c_str(), p.reads.n(), &fa, err, sizeof err) != MHAP_OK) die(err);
+    p.reads.add(fa);
+    mhap_fasta_free(&fa);
   }
+  p.realign.h = p.select.h = p.correct.h = p.repeat.h = p.trim.h = p.graph.h = h;
+  p.realign.reads = &p.reads; p.realign.band = o.i("--realign-band"); p.realign.min_identity = o.d("--realign-min-identity");
+  p.paf = o.b("--realign-paf");
+  p.correct.on = o.isset("--correct"); p.correct.fasta = o.s("--correct"); p.correct.min_cov = o.i("--correct-min-coverage");
+  p.select.on = o.isset("--best-overlaps") && o.i("--best-overlaps") != 0; p.select.table = o.s("--best-table");
+  mhap_select_default_params(&p.select.p);
+  p.select.p.best_n = o.i("--best-overlaps"); p.select.p.min_span = o.i("--best-min-span");
+  p.repeat.on = o.b("--repeat-filter"); p.repeat.table = o.s("--repeat-table");
+  mhap_repeat_default_params(&p.repeat.p);
+  p.repeat.p.factor_pct = o.i("--repeat-factor"); p.repeat.p.max_cov = o.i("--repeat-max-cov"); p.repeat.p.min_run = o.i("--repeat-min-run"); p.repeat.p.min_unique = o.i("--repeat-min-unique");
+  p.trim.on = o.b("--trim"); p.trim.fasta = o.s("--trim-fasta"); p.trim.table = o.s("--trim-table"); p.trim.penalty = o.i("--trim-penalty");
+  mhap_trim_default_params(&p.trim.p);
+  p.trim.p.min_cov = o.i("--trim-min-cov"); p.trim.p.end_clip = o.i("--trim-end-clip"); p.trim.p.min_span = o.i("--trim-min-span");
+  p.graph.on = o.isset("--gfa"); p.graph.gfa = o.s("--gfa"); p.graph.unitigs = o.s("--gfa-unitigs");
+  mhap_graph_default_params(&p.graph.p);
+  p.graph.p.max_hang = o.i("--gfa-max-hang"); p.graph.p.min_ovlp = o.i("--gfa-min-overlap"); p.graph.p.fuzz = o.i("--gfa-fuzz");
+  p.graph.clean = o.b("--gfa-clean"); p.graph.cp.tip_reads = o.i("--gfa-tip-reads"); p.graph.cp.bubble_bases = o.i("--gfa-bubble-bases"); p.graph.cp.max_rounds = o.i("--gfa-clean-rounds");
+  p.graph.consensus = o.b("--gfa-consensus"); p.graph.consensus_fasta = o.s("--gfa-consensus-fasta"); mhap_consensus_default_params(&p.graph.kp); p.graph.kp.min_cov = o.i("--gfa-consensus-min-cov");
+  p.begin();
+}
 
-  fprintf(stderr, "Processing files for storage in reverse index...\n");
-  const double t_proc = now();
-  int64_t strands = 0;
-  int64_t seq_processed = add_file_to_index(E, o.s("-s"), 0, o, &strands);
-  fprintf(stderr, "Stored %lld sequences in the index.\n", (long long)strands);
-  fprintf(stderr, "Processed %lld unique sequences (fwd and rev).\n", (long long)strands);
-  fprintf(stderr, "Time (s) to read and hash from file: %g\n", now() - t_proc);
-
-  Sink sink{stdout};
-  Realign RA;
-  mhap_graph_params gp;
-  mhap_graph_default_params(&gp);
-  gp.max_hang = o.i("--gfa-max-hang"); gp.min_ovlp = o.i("--gfa-min-overlap"); gp.fuzz = o.i("--gfa-fuzz");
-  mhap_trim_params tp;
-  mhap_trim_default_params(&tp);
-  if (realign) {
-    RA.h = E.h; RA.band = o.i("--realign-band"); RA.min_identity = o.d("--realign-min-identity"); RA.paf = o.b("--realign-paf");
-    for (const std::string& sf : list_files(o.s("-s"))) {   // (ids as the index assigned them: FastaData's running count)
-      mhap_fasta fa;
-      if (mhap_fasta_read(sf.c_str(), (int64_t)RA.ids.size(), &fa, err, sizeof err) != MHAP_OK) die(err);
-      RA.add(fa);
-      mhap_fasta_free(&fa);
-    }
-    sink.realign = &RA;
-    if (correct) chk(E.h, mhap_correct_begin(E.h, RA.bases.data(), (int64_t)RA.bases.size(), RA.ids.data(), RA.offsets.data(), RA.lengths.data(),
-                                             (int64_t)RA.ids.size(), &RA.correct));
-    if (best) {
-      mhap_select_params sp;
-      mhap_select_default_params(&sp);
-      sp.best_n = o.i("--best-overlaps"); sp.min_span = o.i("--best-min-span");
-      chk(E.h, mhap_select_begin(E.h, RA.ids.data(), RA.lengths.data(), (int64_t)RA.ids.size(), &sp, &RA.select));
-      RA.hold_select = correct;
-    }
-    if (trim) { tp.min_cov = o.i("--trim-min-cov"); tp.end_clip = o.i("--trim-end-clip"); tp.min_span = o.i("--trim-min-span"); }
-    if (trim || repeat) RA.trim_penalty = o.i("--trim-penalty");
-    if (repeat) {   // (with --trim too, the trimming begins once the repeat stage has freed its device arrays)
-      mhap_repeat_params rp;
-      mhap_repeat_default_params(&rp);
-      rp.factor_pct = o.i("--repeat-factor"); rp.max_cov = o.i("--repeat-max-cov"); rp.min_run = o.i("--repeat-min-run"); rp.min_unique = o.i("--repeat-min-unique");
-      chk(E.h, mhap_repeat_begin(E.h, RA.ids.data(), RA.lengths.data(), (int64_t)RA.ids.size(), &rp, &RA.repeat));
-      RA.hold_plain = gfa && !trim;
-    } else if (trim) chk(E.h, mhap_trim_begin(E.h, RA.ids.data(), RA.lengths.data(), (int64_t)RA.ids.size(), &tp, &RA.trim));
-    if (gfa && trim) RA.keep_records = true;   // the graph begins after the trimming, on the trimmed reads: the records wait for it
-    else if (gfa) {
-      chk(E.h, mhap_graph_begin(E.h, RA.ids.data(), RA.lengths.data(), (int64_t)RA.ids.size(), &gp, &RA.graph));
-      RA.keep_records = o.b("--gfa-consensus");
-    }
-  }
+// Usage 1: the index against itself, then every -q file against it (MhapMain.java:453-570)
+void search(const Engine& E, const Options& o, const mhap_params& P, Sink& sink, int64_t seq_processed) {
+  char err[512] = {0};
   const double t_score = now();
-  if (o.s("-q").empty()) {
-    const double t = now();
+  double t = now();
+  if (o.s("-q").empty() || !o.b("--no-self")) {
     E.find_self(sink_cb, &sink);
     sink_flush(sink);
     fprintf(stderr, "Time (s) to score and output to self: %g\n", now() - t);
-  } else {
-    double t = now();
-    if (!o.b("--no-self")) {
-      E.find_self(sink_cb, &sink);
-      sink_flush(sink);
-      fprintf(stderr, "Time (s) to score and output to self: %g\n", now() - t);
-    }
-    for (const std::string& cf : list_files(o.s("-q"))) {
-      t = now();
-      fprintf(stderr, "Opened fasta file %s.\n", cf.c_str());
-      int64_t nq = 0;
-      if (ends_with(cf, ".dat")) {   // precomputed query sketches: forward entries only (SequenceSketchStreamer.java:291-303)
-        if (E.g) die("--gpus N takes FASTA input (precomputed .dat sketches are searched on one GPU)");
-        mhap_handle* h = E.h;
-        DatEntries d;
-        read_dat(cf, seq_processed, P.num_hashes, P.ordered_sketch_size, true, d);
-        if (g_headers.full) for (size_t i = 0; i < d.ids.size(); i++) g_headers.byid[d.ids[i]] = d.hdr[i];
-        if (!d.ids.empty())
-          chk(h, mhap_find_matches_sketches(h, d.ids.data(), d.seqlen.data(), d.mh.data(), d.ord.data(), d.osz.data(), d.olen.data(),
-                                            (int64_t)d.ids.size(), sink_cb, &sink));
-        sink_flush(sink);
-        seq_processed += (int64_t)d.ids.size();
-        fprintf(stderr, "Processed %lld to sequences.\n", (long long)d.ids.size());
-        fprintf(stderr, "Time (s) to score, hash to-file, and output: %g\n", now() - t);
-        continue;
-      }
+  }
+  for (const std::string& cf : o.s("-q").empty() ? std::vector<std::string>() : list_files(o.s("-q"))) {
+    t = now();
+    fprintf(stderr, "Opened fasta file %s.\n", cf.c_str());
+    int64_t nq = 0;
+    if (ends_with(cf, ".dat")) {   // precomputed query sketches: forward entries only (SequenceSketchStreamer.java:291-303)
+      if (E.g) die("--gpus N takes FASTA input (precomputed .dat sketches are searched on one GPU)");
+      DatEntries d;
+      read_dat(cf, seq_processed, P.num_hashes, P.ordered_sketch_size, true, d);
+      if (g_headers.full) for (size_t i = 0; i < d.ids.size(); i++) g_headers.byid[d.ids[i]] = d.hdr[i];
+      if (!d.ids.empty())
+        chk(E.h, mhap_find_matches_sketches(E.h, d.ids.data(), d.seqlen.data(), d.mh.data(), d.ord.data(), d.osz.data(), d.olen.data(),
+                                          (int64_t)d.ids.size(), sink_cb, &sink));
+      nq = (int64_t)d.ids.size();
+    } else {
       mhap_fasta fa;
       if (mhap_fasta_read(cf.c_str(), seq_processed, &fa, err, sizeof err) != MHAP_OK) die(err);   // id offset = reads so far (MhapMain.java:527)
       if (g_headers.full) collect_headers(fa);
-      if (realign) RA.add(fa);
+      if (sink.pipeline) sink.pipeline->reads.add(fa);
       const mhap_stats s0 = E.stats();
       E.find_reads(fa, sink_cb, &sink);
-      const mhap_stats s1 = E.stats();
-      nq = s1.queries_searched - s0.queries_searched;   // forward sketches produced = getNumberProcessed() (MhapMain.java:537)
+      nq = E.stats().queries_searched - s0.queries_searched;   // forward sketches produced = getNumberProcessed() (MhapMain.java:537)
       mhap_fasta_free(&fa);
-      sink_flush(sink);
-      seq_processed += nq;
-      fprintf(stderr, "Processed %lld to sequences.\n", (long long)nq);
-      fprintf(stderr, "Time (s) to score, hash to-file, and output: %g\n", now() - t);
     }
+    sink_flush(sink);
+    seq_processed += nq;
+    fprintf(stderr, "Processed %lld to sequences.\n", (long long)nq);
+    fprintf(stderr, "Time (s) to score, hash to-file, and output: %g\n", now() - t);
   }
   sink_flush(sink);
   fprintf(stderr, "Total scoring time (s): %g\n", now() - t_score);
-  if (realign) fprintf(stderr, "Time (s) to realign: %g (%lld overlaps kept, %lld dropped: no alignment or identity below %g)\n", RA.seconds, (long long)RA.kept, (long long)RA.dropped, RA.min_identity);
-  if (RA.select) {   // every read's threshold after the last batch; with --correct the held records that keep a view are realigned again, with paths, and vote
-    const double ts = now();
-    const int64_t nr = (int64_t)RA.ids.size(), nh = (int64_t)RA.held_out.size();
-    int64_t sc[MHAP_SELECT_COUNTS];
-    chk(E.h, mhap_select_finish(RA.select, sc));
-    if (o.isset("--best-table")) {
-      std::vector<int32_t> srows((size_t)std::max<int64_t>(nr, 1) * 4);
-      chk(E.h, mhap_select_copy(RA.select, srows.data()));
-      FILE* f = fopen(o.s("--best-table").c_str(), "wb");
-      if (!f) die("cannot write " + o.s("--best-table"));
-      std::string text;
-      for (int64_t r = 0; r < nr; r++)
-        text += header_of(RA.ids[(size_t)r]) + " " + std::to_string(srows[4 * (size_t)r]) + " " + std::to_string(srows[4 * (size_t)r + 1]) + " " +
-                std::to_string(srows[4 * (size_t)r + 2]) + "\n";
-      fwrite(text.data(), 1, text.size(), f);
-      if (fclose(f) != 0) die("cannot write " + o.s("--best-table"));
-    }
-    std::vector<uint8_t> views((size_t)std::max<int64_t>(nh, 1));
-    if (RA.correct) chk(E.h, mhap_select_apply(RA.select, RA.held_out.data(), nh, views.data()));
-    mhap_select_free(RA.select);
-    RA.select = nullptr;
-    RA.select_seconds += now() - ts;
-    fprintf(stderr, "Best overlaps: %lld reads, %lld with a view, %lld cut; %lld of %lld views kept; %lld eligible overlaps\n", (long long)sc[0],
-            (long long)sc[1], (long long)sc[2], (long long)sc[4], (long long)sc[3], (long long)sc[5]);
-    fprintf(stderr, "Time (s) to select the best overlaps: %g\n", RA.select_seconds);
-    if (RA.correct) {   // the aligner is deterministic: the records as they came give the alignments of the first pass again, now with their paths
-      const double tc = now();
-      std::vector<mhap_record> in, out, kept;
-      std::vector<uint8_t> vb, kv;
-      for (int64_t q = 0; q < nh; q++)
-        if (views[(size_t)q]) { in.push_back(RA.held_in[(size_t)q]); vb.push_back(views[(size_t)q]); }
-      std::vector<mhap_record>().swap(RA.held_in);
-      std::vector<mhap_record>().swap(RA.held_out);
-      const int64_t total = (int64_t)in.size(), step = 1 << 16;
-      for (int64_t q0 = 0; q0 < total; q0 += step) {
-        const int64_t n = std::min(step, total - q0);
-        out.resize((size_t)n);
-        RA.detail.resize((size_t)n * 3);
-        mhap_align_paths* paths = nullptr;
-        chk(E.h, mhap_realign_records_paths(E.h, RA.bases.data(), (int64_t)RA.bases.size(), RA.ids.data(), RA.offsets.data(), RA.lengths.data(),
-                                            (int64_t)RA.ids.size(), in.data() + q0, n, RA.band, out.data(), RA.detail.data(), &paths));
-        int64_t n_ops = 0;
-        mhap_align_paths_info(paths, nullptr, &n_ops);
-        RA.op_offsets.resize((size_t)n + 1); RA.ops.resize((size_t)std::max<int64_t>(n_ops, 1));
-        mhap_align_paths_copy(paths, RA.op_offsets.data(), RA.ops.data());
-        mhap_align_paths_free(paths);
-        kept.clear(); kv.clear();
-        RA.vote_offsets.assign(1, 0); RA.vote_ops.clear();
-        for (int64_t i = 0; i < n; i++) {   // (the first pass's rule once more: nothing is dropped here unless the aligner differs)
-          const mhap_record& r = out[(size_t)i];
-          const bool none = r.score == 0.0 && r.a1 == 0 && r.a2 == 0 && r.b1 == 0 && r.b2 == 0;
-          if (none || r.score < RA.min_identity) continue;
-          kept.push_back(r); kv.push_back(vb[(size_t)(q0 + i)]);
-          RA.vote_ops.insert(RA.vote_ops.end(), RA.ops.begin() + RA.op_offsets[(size_t)i], RA.ops.begin() + RA.op_offsets[(size_t)i + 1]);
-          RA.vote_offsets.push_back((int64_t)RA.vote_ops.size());
-        }
-        mhap_align_paths* kept_paths = nullptr;
-        if (mhap_align_paths_from_runs(RA.vote_offsets.data(), (int64_t)kept.size(), RA.vote_ops.data(), &kept_paths) != MHAP_OK) die("the paths of the selected overlaps");
-        const int rc = mhap_correct_add_views(RA.correct, kept.data(), (int64_t)kept.size(), kept_paths, kv.empty() ? views.data() : kv.data());
-        mhap_align_paths_free(kept_paths);
-        chk(E.h, rc);
-      }
-      RA.correct_seconds += now() - tc;
-    }
-  }
-  if (RA.correct) {   // the call for every read, after the last batch has voted; the FASTA file is all it writes
-    const double tc = now();
-    const int64_t nr = (int64_t)RA.ids.size();
-    std::vector<int64_t> off((size_t)nr + 1);
-    std::vector<int32_t> st((size_t)std::max<int64_t>(nr, 1) * 6);
-    int64_t skipped = 0;
-    chk(E.h, mhap_correct_finish(RA.correct, o.i("--correct-min-coverage"), off.data(), st.data(), &skipped));
-    std::vector<uint8_t> bytes((size_t)std::max<int64_t>(off[(size_t)nr], 1));
-    chk(E.h, mhap_correct_copy(RA.correct, bytes.data()));
-    mhap_correct_free(RA.correct);
-    RA.correct = nullptr;
-    FILE* f = fopen(o.s("--correct").c_str(), "wb");
-    if (!f) die("cannot write " + o.s("--correct"));
-    long long tot[6] = {0, 0, 0, 0, 0, 0};
-    std::string text;
-    for (int64_t r = 0; r < nr; r++) {
-      const int32_t* c = st.data() + 6 * r;
-      for (int u = 0; u < 6; u++) tot[u] += c[u];
-      text += ">" + header_of(RA.ids[(size_t)r]) + " len=" + std::to_string(c[1]) + " sub=" + std::to_string(c[2]) + " del=" + std::to_string(c[3]) +
-              " ins=" + std::to_string(c[4]) + " low=" + std::to_string(c[5]) + "\n";
-      text.append((const char*)bytes.data() + off[(size_t)r], (size_t)(off[(size_t)r + 1] - off[(size_t)r]));
-      text.push_back('\n');
-      if (text.size() > (8u << 20)) { fwrite(text.data(), 1, text.size(), f); text.clear(); }
-    }
-    fwrite(text.data(), 1, text.size(), f);
-    if (fclose(f) != 0) die("cannot write " + o.s("--correct"));
-    RA.correct_seconds += now() - tc;
-    fprintf(stderr, "Corrected %lld reads: %lld bases in, %lld out; %lld substitutions, %lld deletions, %lld insertions, %lld positions of low coverage; skipped_views = %lld\n",
-            (long long)nr, tot[0], tot[1], tot[2], tot[3], tot[4], tot[5], (long long)skipped);
-    fprintf(stderr, "Time (s) to vote and correct: %g\n", RA.correct_seconds);
-  }
-  if (RA.repeat) {   // the intervals of every read and the judgement of every held record, after the last batch; trimming and graph take the survivors
-    const double tr = now();
-    const int64_t nr = (int64_t)RA.ids.size(), nk = (int64_t)RA.held_refined.size();
-    int64_t rcn[MHAP_REPEAT_COUNTS];
-    chk(E.h, mhap_repeat_finish(RA.repeat, rcn));
-    if (o.isset("--repeat-table")) {
-      std::vector<int32_t> rrows((size_t)std::max<int64_t>(nr, 1) * 4), riv((size_t)std::max<int64_t>(rcn[3], 1) * 2);
-      std::vector<uint8_t> rflags((size_t)std::max<int64_t>(nr, 1));
-      std::vector<int64_t> roff((size_t)nr + 1);
-      chk(E.h, mhap_repeat_copy(RA.repeat, rrows.data(), rflags.data(), roff.data(), riv.data()));
-      FILE* f = fopen(o.s("--repeat-table").c_str(), "wb");
-      if (!f) die("cannot write " + o.s("--repeat-table"));
-      for (int64_t r = 0; r < nr; r++)
-        for (int64_t i = roff[(size_t)r]; i < roff[(size_t)r + 1]; i++)
-          fprintf(f, "%lld\t%d\t%d\n", (long long)RA.ids[(size_t)r], riv[(size_t)i * 2], riv[(size_t)i * 2 + 1]);
-      if (fclose(f) != 0) die("cannot write " + o.s("--repeat-table"));
-    }
-    std::vector<uint8_t> keep((size_t)std::max<int64_t>(nk, 1));
-    std::vector<int32_t> unique((size_t)std::max<int64_t>(nk, 1) * 2);
-    chk(E.h, mhap_repeat_apply(RA.repeat, RA.held_refined.data(), nk, keep.data(), unique.data()));
-    mhap_repeat_free(RA.repeat);   // (its device arrays go before the trimming allocates its own)
-    RA.repeat = nullptr;
-    std::vector<mhap_record>& survivors = RA.hold_plain ? RA.held_plain : RA.held_refined;   // the graph: as realigned; the trimming: refined
-    size_t w = 0;
-    for (int64_t q = 0; q < nk; q++) if (keep[(size_t)q]) survivors[w++] = survivors[(size_t)q];
-    survivors.resize(w);
-    RA.repeat_seconds += now() - tr;
-    fprintf(stderr, "Repeats: %lld reads, %lld with a repeat, %lld repeat throughout; %lld intervals, %lld of %lld bases; %lld eligible overlaps, depth %lld, threshold %lld\n",
-            (long long)rcn[0], (long long)rcn[1], (long long)rcn[2], (long long)rcn[3], (long long)rcn[4], (long long)rcn[5], (long long)rcn[6],
-            (long long)rcn[7], (long long)rcn[8]);
-    fprintf(stderr, "Time (s) to mark repeats: %g (%lld of %lld overlaps set aside)\n", RA.repeat_seconds, (long long)(nk - (int64_t)w), (long long)nk);
-    if (trim) {
-      const double tt = now();
-      chk(E.h, mhap_trim_begin(E.h, RA.ids.data(), RA.lengths.data(), nr, &tp, &RA.trim));
-      chk(E.h, mhap_trim_add(RA.trim, survivors.data(), (int64_t)w));
-      RA.trim_seconds += now() - tt;
-    } else if (RA.graph) {
-      const double tg = now();
-      chk(E.h, mhap_graph_add(RA.graph, survivors.data(), (int64_t)w));
-      RA.graph_seconds += now() - tg;
-    }
-    if (RA.keep_records) RA.kept_records.swap(survivors);
-    std::vector<mhap_record>().swap(RA.held_refined);
-    std::vector<mhap_record>().swap(RA.held_plain);
-  }
-  if (RA.trim) {   // every read's clear range, after the last batch has been piled up; with --gfa the graph begins here, on the trimmed reads
-    const double tt = now();
-    const int64_t nr = (int64_t)RA.ids.size();
-    int64_t tc[MHAP_TRIM_COUNTS];
-    chk(E.h, mhap_trim_finish(RA.trim, tc));
-    std::vector<int32_t> trows((size_t)std::max<int64_t>(nr, 1) * 4);
-    std::vector<uint8_t> tflags((size_t)std::max<int64_t>(nr, 1));
-    chk(E.h, mhap_trim_copy(RA.trim, trows.data(), tflags.data()));
-    if (o.isset("--trim-fasta")) {
-      FILE* f = fopen(o.s("--trim-fasta").c_str(), "wb");
-      if (!f) die("cannot write " + o.s("--trim-fasta"));
-      std::string text;
-      for (int64_t r = 0; r < nr; r++) {
-        if (tflags[(size_t)r] & MHAP_TRIM_DELETED) continue;
-        const int32_t* c = trows.data() + 4 * r;
-        text += ">" + header_of(RA.ids[(size_t)r]) + " len=" + std::to_string(c[1] - c[0]) + " begin=" + std::to_string(c[0]) + " end=" + std::to_string(c[1]) +
-                " runs=" + std::to_string(c[2]) + "\n";
-        text.append((const char*)RA.bases.data() + RA.offsets[(size_t)r] + c[0], (size_t)(c[1] - c[0]));
-        text.push_back('\n');
-        if (text.size() > (8u << 20)) { fwrite(text.data(), 1, text.size(), f); text.clear(); }
-      }
-      fwrite(text.data(), 1, text.size(), f);
-      if (fclose(f) != 0) die("cannot write " + o.s("--trim-fasta"));
-    }
-    if (o.isset("--trim-table")) {
-      FILE* f = fopen(o.s("--trim-table").c_str(), "wb");
-      if (!f) die("cannot write " + o.s("--trim-table"));
-      for (int64_t r = 0; r < nr; r++) {
-        const int32_t* c = trows.data() + 4 * r;
-        fprintf(f, "%lld\t%d\t%d\t%d\t%d\t%d\t%d\n", (long long)RA.ids[(size_t)r], RA.lengths[(size_t)r], c[0], c[1], c[2], c[3], (int)tflags[(size_t)r]);
-      }
-      if (fclose(f) != 0) die("cannot write " + o.s("--trim-table"));
-    }
-    if (gfa) {   // the records rewritten and compacted, the table of the surviving reads, and the graph over both
-      const int64_t nk = (int64_t)RA.kept_records.size();
-      std::vector<mhap_record> applied((size_t)std::max<int64_t>(nk, 1));
-      std::vector<uint8_t> keep((size_t)std::max<int64_t>(nk, 1));
-      chk(E.h, mhap_trim_apply(RA.trim, RA.kept_records.data(), nk, applied.data(), keep.data()));
-      size_t w = 0;
-      for (int64_t q = 0; q < nk; q++) if (keep[(size_t)q]) applied[w++] = applied[(size_t)q];
-      applied.resize(w);
-      RA.kept_records.swap(applied);
-      size_t live = 0;
-      for (int64_t r = 0; r < nr; r++) {   // (the bases stay where they are: a trimmed read begins `begin` bytes later)
-        if (tflags[(size_t)r] & MHAP_TRIM_DELETED) continue;
-        RA.ids[live] = RA.ids[(size_t)r];
-        RA.offsets[live] = RA.offsets[(size_t)r] + trows[(size_t)r * 4];
-        RA.lengths[live++] = trows[(size_t)r * 4 + 1] - trows[(size_t)r * 4];
-      }
-      RA.ids.resize(live); RA.offsets.resize(live); RA.lengths.resize(live);
-      const double tg = now();
-      chk(E.h, mhap_graph_begin(E.h, RA.ids.data(), RA.lengths.data(), (int64_t)live, &gp, &RA.graph));
-      chk(E.h, mhap_graph_add(RA.graph, RA.kept_records.data(), (int64_t)RA.kept_records.size()));
-      RA.graph_seconds += now() - tg;
-      if (!o.b("--gfa-consensus")) std::vector<mhap_record>().swap(RA.kept_records);
-    }
-    mhap_trim_free(RA.trim);
-    RA.trim = nullptr;
-    RA.trim_seconds += now() - tt;
-    fprintf(stderr, "Trim: %lld reads, %lld deleted, %lld cut at 5', %lld cut at 3', %lld gapped; %lld of %lld bases kept, %lld eligible overlaps\n",
-            (long long)tc[0], (long long)tc[1], (long long)tc[2], (long long)tc[3], (long long)tc[4], (long long)tc[6], (long long)tc[5], (long long)tc[7]);
-    fprintf(stderr, "Time (s) to pile up and trim: %g\n", RA.trim_seconds);
-  }
-  if (RA.graph) {   // the list and its reduction, after the last batch has been classed; the GFA file is all it writes
-    const double tg = now();
-    const int64_t nr = (int64_t)RA.ids.size();
-    int64_t gc[MHAP_GRAPH_COUNTS];
-    chk(E.h, mhap_graph_finish(RA.graph, gc));
-    const int64_t na = gc[8];
-    std::vector<int32_t> rows((size_t)std::max<int64_t>(na, 1) * 7);
-    std::vector<uint8_t> contained((size_t)std::max<int64_t>(nr, 1));
-    chk(E.h, mhap_graph_copy_arcs(RA.graph, rows.data()));
-    chk(E.h, mhap_graph_copy_read_flags(RA.graph, contained.data()));
-    int64_t uc[MHAP_UNITIG_COUNTS], cc[MHAP_CLEAN_COUNTS], kc[MHAP_CONSENSUS_COUNTS];
-    const bool unitigs = o.isset("--gfa-unitigs"), clean = o.b("--gfa-clean"), consensus = o.b("--gfa-consensus");
-    std::vector<uint8_t> removed((size_t)std::max<int64_t>(na, 1), 0);
-    if (clean) {   // tips and bubbles go before either file is written: a dropped read counts as a contained one does, a removed arc is not final
-      mhap_clean_params cp;
-      cp.tip_reads = o.i("--gfa-tip-reads"); cp.bubble_bases = o.i("--gfa-bubble-bases"); cp.max_rounds = o.i("--gfa-clean-rounds");
-      std::vector<uint8_t> dropped((size_t)std::max<int64_t>(nr, 1));
-      chk(E.h, mhap_graph_clean(RA.graph, &cp, cc));
-      chk(E.h, mhap_graph_copy_dropped(RA.graph, dropped.data()));
-      chk(E.h, mhap_graph_copy_removed(RA.graph, removed.data()));
-      for (int64_t r = 0; r < nr; r++) if (dropped[(size_t)r]) contained[(size_t)r] = 1;
-    }
-    if (unitigs) {   // the chains of the final arcs and their bases, while the graph is on the device; the second file is all it writes
-      if (clean) chk(E.h, mhap_graph_unitigs_counts(RA.graph, uc));   // (the clean has built the unitigs of the cleaned graph)
-      else chk(E.h, mhap_graph_unitigs(RA.graph, uc));
-      const size_t nu = (size_t)uc[0], nm = (size_t)uc[2], nl = (size_t)uc[4];
-      std::vector<int64_t> ustart(nu + 1), ulen(nu + 1), moff(nm + 1);
-      std::vector<uint8_t> circ(nu + 1), seq((size_t)uc[6] + 1);
-      std::vector<int32_t> mv(nm + 1), msp(nm + 1), links(6 * nl + 6);
-      chk(E.h, mhap_graph_copy_unitigs(RA.graph, ustart.data(), ulen.data(), circ.data()));
-      chk(E.h, mhap_graph_copy_layout(RA.graph, mv.data(), moff.data(), msp.data()));
-      chk(E.h, mhap_graph_copy_links(RA.graph, links.data()));
-      std::vector<int64_t> cons_off(nu + 1, 0), cons_map;   // --gfa-consensus: unitig k's bytes in seq, the position map of all unitigs
-      if (!consensus) chk(E.h, mhap_graph_spell(RA.graph, RA.bases.data(), (int64_t)RA.bases.size(), RA.offsets.data(), seq.data()));
-      else {   // the kept records, fed now that the unitigs are served; the consensus takes the place of the spelling
-        mhap_consensus_params kp;
-        mhap_consensus_default_params(&kp);
-        kp.min_cov = o.i("--gfa-consensus-min-cov");
-        mhap_consensus_session* cs = nullptr;
-        chk(E.h, mhap_consensus_begin(RA.graph, (const uint8_t*)RA.bases.data(), (int64_t)RA.bases.size(), RA.offsets.data(), &kp, &cs));
-        chk(E.h, mhap_consensus_add(cs, RA.kept_records.data(), (int64_t)RA.kept_records.size()));
-        chk(E.h, mhap_consensus_run(cs, kc));
-        int64_t n_draft = 0, n_out = 0;
-        chk(E.h, mhap_consensus_info(cs, nullptr, nullptr, &n_draft, &n_out));
-        std::vector<int64_t> stats(6 * nu + 6);
-        seq.assign((size_t)n_out + 1, 0);
-        cons_map.assign((size_t)n_draft + 1, 0);
-        chk(E.h, mhap_consensus_copy(cs, seq.data(), cons_off.data(), stats.data()));
-        chk(E.h, mhap_consensus_copy_map(cs, cons_map.data()));
-        mhap_consensus_free(cs);
-        std::vector<mhap_record>().swap(RA.kept_records);
-      }
-      FILE* f = fopen(o.s("--gfa-unitigs").c_str(), "wb");
-      if (!f) die("cannot write " + o.s("--gfa-unitigs"));
-      std::string text = "H\tVN:Z:1.0\n";
-      char name[32], line[128];
-      size_t at = 0, draft_at = 0;   // unitig k's sequence in seq, its first position in the map
-      for (size_t k = 0; k < nu; k++) {
-        snprintf(name, sizeof name, "utg%06lld%c", (long long)k + 1, circ[k] ? 'c' : 'l');
-        const size_t slen = consensus ? (size_t)(cons_off[k + 1] - cons_off[k]) : (size_t)ulen[k];
-        text += std::string("S\t") + name + "\t";
-        text.append((const char*)seq.data() + at, slen);
-        at += slen;
-        text += "\tLN:i:" + std::to_string(slen) + "\tnr:i:" + std::to_string(ustart[k + 1] - ustart[k]) + "\n";
-        for (int64_t m = ustart[k]; m < ustart[k + 1]; m++) {
-          const std::string sp = std::to_string(msp[(size_t)m]);
-          const int64_t off = consensus ? cons_map[draft_at + (size_t)moff[(size_t)m]] : moff[(size_t)m];
-          text += std::string("a\t") + name + "\t" + std::to_string(off) + "\t" + std::to_string(RA.ids[(size_t)(mv[(size_t)m] >> 1)]) + ":1-" + sp +
-                  "\t" + ((mv[(size_t)m] & 1) ? "-" : "+") + "\t" + sp + "\n";
-        }
-        draft_at += (size_t)ulen[k];
-        if (text.size() > (8u << 20)) { fwrite(text.data(), 1, text.size(), f); text.clear(); }
-      }
-      for (size_t i = 0; i < nl; i++) {
-        const int len = mhap_format_gfa_unitig_link(links.data() + 6 * i, line, sizeof line);
-        if (len < 0 || (size_t)len >= sizeof line) die("mhap_format_gfa_unitig_link failed");
-        text.append(line, (size_t)len);
-        text.push_back('\n');
-        if (text.size() > (8u << 20)) { fwrite(text.data(), 1, text.size(), f); text.clear(); }
-      }
-      fwrite(text.data(), 1, text.size(), f);
-      if (fclose(f) != 0) die("cannot write " + o.s("--gfa-unitigs"));
-      if (consensus && o.isset("--gfa-consensus-fasta")) {
-        FILE* ff = fopen(o.s("--gfa-consensus-fasta").c_str(), "wb");
-        if (!ff) die("cannot write " + o.s("--gfa-consensus-fasta"));
-        for (size_t k = 0; k < nu; k++) {
-          fprintf(ff, ">utg%06lld%c\n", (long long)k + 1, circ[k] ? 'c' : 'l');
-          fwrite(seq.data() + cons_off[k], 1, (size_t)(cons_off[k + 1] - cons_off[k]), ff);
-          fputc('\n', ff);
-        }
-        if (fclose(ff) != 0) die("cannot write " + o.s("--gfa-consensus-fasta"));
-      }
-    }
-    mhap_graph_free(RA.graph);
-    RA.graph = nullptr;
-    FILE* f = fopen(o.s("--gfa").c_str(), "wb");
-    if (!f) die("cannot write " + o.s("--gfa"));
-    std::string text = "H\tVN:Z:1.0\n";
-    char line[128];
-    for (int64_t r = 0; r < nr; r++) {
-      if (contained[(size_t)r]) continue;
-      text += "S\t" + std::to_string(RA.ids[(size_t)r]) + "\t*\tLN:i:" + std::to_string(RA.lengths[(size_t)r]) + "\n";
-      if (text.size() > (8u << 20)) { fwrite(text.data(), 1, text.size(), f); text.clear(); }
-    }
-    for (int64_t i = 0; i < na; i++) {
-      if (!rows[(size_t)i * 7 + 6] || removed[(size_t)i]) continue;
-      const int len = mhap_format_gfa_link(rows.data() + 7 * i, RA.ids.data(), line, sizeof line);
-      if (len < 0 || (size_t)len >= sizeof line) die("mhap_format_gfa_link failed");
-      text.append(line, (size_t)len);
-      text.push_back('\n');
-      if (text.size() > (8u << 20)) { fwrite(text.data(), 1, text.size(), f); text.clear(); }
-    }
-    fwrite(text.data(), 1, text.size(), f);
-    if (fclose(f) != 0) die("cannot write " + o.s("--gfa"));
-    RA.graph_seconds += now() - tg;
-    fprintf(stderr, "String graph of %lld overlaps: %lld none, %lld internal, %lld contained (from), %lld contained (to), %lld short, %lld dovetail; "
-                    "%lld contained reads, %lld arcs, %lld reduced, %lld final\n",
-            (long long)gc[0], (long long)gc[1], (long long)gc[2], (long long)gc[3], (long long)gc[4], (long long)gc[5], (long long)gc[6],
-            (long long)gc[7], (long long)gc[8], (long long)gc[9], (long long)gc[10]);
-    if (clean)
-      fprintf(stderr, "Cleaned in %lld rounds: %lld tips (%lld reads), %lld bubbles (%lld reads), %lld arcs removed\n", (long long)cc[0], (long long)cc[1],
-              (long long)cc[2], (long long)cc[3], (long long)cc[4], (long long)cc[5]);
-    if (unitigs)
-      fprintf(stderr, "Unitigs: %lld unitigs (%lld circular) of %lld reads, %lld joined arcs, %lld links; longest %lld bases, %lld bases in all\n",
-              (long long)uc[0], (long long)uc[1], (long long)uc[2], (long long)uc[3], (long long)uc[4], (long long)uc[5], (long long)uc[6]);
-    if (consensus)
-      fprintf(stderr, "Consensus: %lld members, %lld reads placed by an overlap, %lld unplaced; %lld aligned, %lld without alignment; %lld bases in, "
-                      "%lld out: %lld substitutions, %lld deletions, %lld insertions, %lld low positions\n",
-              (long long)kc[0], (long long)kc[1], (long long)kc[2], (long long)kc[3], (long long)kc[4], (long long)kc[5], (long long)kc[6],
-              (long long)kc[7], (long long)kc[8], (long long)kc[9], (long long)kc[10]);
-    fprintf(stderr, "Time (s) to class, build and reduce the graph: %g\n", RA.graph_seconds);
-  }
-  fprintf(stderr, "Total time (s): %g\n", now() - t_total);
-  // outputFinalStat (MhapMain.java:572-590); the inverted-index counters have no brute-force analogue
+}
+
+// outputFinalStat (MhapMain.java:572-590); the inverted-index counters have no brute-force analogue
+void final_statistics(const Engine& E) {
   const mhap_stats st = E.stats();
   mhap_kernel_times kt; memset(&kt, 0, sizeof kt);
   for (int r = 0; r < E.n; r++) {   // kernel time summed over the ranks (they run concurrently)
@@ -1108,6 +574,47 @@ int main(int argc, char** argv) {
   fprintf(stderr, "GPU kernel time (ms): hash %.3f, weights %.3f, minhash %.3f, ordered %.3f, index build %.3f, index query %.3f, candidates %.3f, overlap %.3f\n",
           kt.ms[MHAP_K_HASH], kt.ms[MHAP_K_WEIGHT], kt.ms[MHAP_K_MINHASH], kt.ms[MHAP_K_ORDERED], kt.ms[MHAP_K_INDEX_BUILD], kt.ms[MHAP_K_INDEX_QUERY],
           kt.ms[MHAP_K_CANDIDATE], kt.ms[MHAP_K_OVERLAP]);
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  Options o;
+  declare_options(o);
+  if (!o.parse(argc, argv)) return 0;
+  std::vector<int32_t> devs = check_options(o);
+  mhap_params P; mhap_default_params(&P);
+  P.kmer_size = o.i("-k"); P.num_hashes = o.i("--num-hashes"); P.ordered_kmer_size = o.i("--ordered-kmer-size");
+  P.ordered_sketch_size = o.i("--ordered-sketch-size"); P.num_min_matches = o.i("--num-min-matches");
+  P.min_store_length = o.i("--min-store-length"); P.min_olap_length = o.i("--min-olap-length"); P.device = o.i("--device");
+  P.threshold = o.d("--threshold"); P.max_shift = o.d("--max-shift"); P.repeat_weight = o.d("--repeat-weight");
+  const bool precompute = !o.s("-p").empty();
+  Engine E = create_engine(o, P, devs, precompute);
+
+  const double t_total = now();
+  if (!o.s("-f").empty()) load_filter(E, o);
+  if (precompute) {
+    precompute_dat(E, o, P);
+    fprintf(stderr, "Total time (s): %g\n", now() - t_total);
+    E.destroy();
+    return 0;
+  }
+
+  fprintf(stderr, "Processing files for storage in reverse index...\n");
+  const double t_proc = now();
+  int64_t strands = 0;
+  const int64_t seq_processed = add_file_to_index(E, o.s("-s"), 0, o, &strands);
+  fprintf(stderr, "Stored %lld sequences in the index.\n", (long long)strands);
+  fprintf(stderr, "Processed %lld unique sequences (fwd and rev).\n", (long long)strands);
+  fprintf(stderr, "Time (s) to read and hash from file: %g\n", now() - t_proc);
+
+  Sink sink;
+  Pipeline pipeline;
+  if (o.b("--realign")) { begin_pipeline(o, E.h, pipeline); sink.pipeline = &pipeline; }
+  search(E, o, P, sink, seq_processed);
+  if (sink.pipeline) pipeline.finish();
+  fprintf(stderr, "Total time (s): %g\n", now() - t_total);
+  final_statistics(E);
   // everything is written: leave without tearing down gigabytes of device and host mappings one by one (the kernel does it faster)
   fflush(nullptr);
   _exit(0);
