@@ -1203,6 +1203,17 @@ int mhap_selftest_transpose32(uint32_t* a32);
 /* the (inter, k) identity table (J/sketch/BottomOverlapSketch.java:391-395; scores[k (k + 1) / 2 + inter], k <= S; may be NULL) and the
  * second stage's early-reject table derived from it: pass_min[k] = smallest inter with score >= threshold for any k' >= k (S + 2 entries) */
 int mhap_selftest_pass_min(int32_t S, int32_t k2, double threshold, double* scores, int32_t* pass_min);
+/* the sketch driver's host rules on n reads of the given lengths and flags (2 = skipped, 1 = raw bytes; fused = 0: every read's hashes are
+ * materialised).  plan8 = {bases per launch group from free_bytes and the override (> 0 wins), groups, max key / 32-bit hash / weight elements,
+ * max reads of a group, longest read, slab entries}; per read group_of[i], layout[6 i ..] = {w_off, key_off, h2_off, key_stride, h2_stride,
+ * flags out} and order[i] = the i-th read (within its group) handed out, or -1 where the group keeps the input order; per group
+ * totals[6 g ..] = {key, hash, weight elements, longest and shortest read not skipped, read bases}.  n = 0: plan8 only. */
+int mhap_selftest_sketch_plan(uint64_t free_bytes, int64_t group_bases_override, const int32_t* lengths, const int32_t* flags, int64_t n,
+                              int32_t k, int32_t k2, int32_t fused, int64_t* plan8, int64_t* group_of, int64_t* layout, int64_t* totals,
+                              int32_t* order);
+/* where the ordered kernel runs around the MinHash launch, under the MHAP_ORDERED_* / MHAP_W1_PREFILL switches of the environment:
+ * out5 = {strands in front of the launch, no wait, idle gap, prefills, all rows in front} */
+int mhap_selftest_ordered_schedule(int64_t group_read_bases, int64_t n_w1, int64_t n_weighted, int64_t nstr, int32_t eager_x, int64_t* out5);
 int mhap_selftest_xorshift_jump(uint64_t key, int32_t nsteps, uint64_t* out);
 int mhap_selftest_xorshift_unjump(uint64_t x, int32_t nsteps, uint64_t* out);   /* the key nsteps steps before chain value x */
 /* the k-mer counter's window values of one read's bytes: out[i] / valid[i] for the window starting at i (len - k + 1 of each) */

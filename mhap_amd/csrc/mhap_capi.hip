@@ -22,14 +22,13 @@ static double hp_now() { return std::chrono::duration<double, std::milli>(std::c
 #include "kernels.hpp"
 #include "mhap_internal.hpp"
 #include "overlap_lane.hpp"
+#include "sketch_plan.hpp"
 
 using namespace mhap;
 
 namespace {
 
 struct TimedLaunch { hipEvent_t a, b; int kind; };
-
-inline int64_t align4(int64_t v) { return (v + 3) & ~(int64_t)3; }
 
 void parallel_for(int64_t n, int nthreads, const std::function<void(int64_t, int64_t)>& fn, int64_t grain = 16384) {
   if (n <= 0) return;
@@ -88,8 +87,6 @@ struct mhap_handle {
   hipStream_t stream = nullptr;
   hipStream_t own_stream = nullptr;
   int oj_per_cu[OJ_LEVELS][3] = {}, oj_per_cu_S = -1;   // resident join-kernel workgroups per CU by level and shape at ordered sketch size oj_per_cu_S (0: not asked yet)
-  int join_mode = 0;                      // MHAP_JOIN_MODE: 0 = by the candidates per query, 1 = alone, 2 = pair, 3 = team
-  int join_wide = 2;                      // MHAP_JOIN_WIDE: further passes of the join kernel (512, then 1 536 joined k-mers) over the pairs handed over: 0, 1 or 2 of them
   hipStream_t mh_stream = nullptr;        // MinHash launch of the weighted strands, next to the launch of the weight-1 strands
   hipEvent_t ev_mh_fork = nullptr, ev_mh_join = nullptr, ev_ix_fork = nullptr, ev_ix_join = nullptr;
   // inverted index state: inv_ends / inv_items hold the index of entries [0, inv_ne) when inv_ready
@@ -320,10 +317,6 @@ int stage_reads(mhap_handle* h, const char* bases, const int64_t* offsets, const
   return MHAP_OK;
 }
 
-// Sketch the staged reads into device rows [0, 2*st_n) of the given tables (kernels only + tiny descriptor uploads).
-// Batches run back to back on the handle's stream.  (A two-stream variant that overlapped hash/weight/ordered of
-// batch b+1 with MinHash of batch b was measured at 358 -> 355..365 ms/step: the kernels compete for the same VALU
-// issue slots and LDS, so it was removed.)
 // (Re)allocate the inverted index for `ne` entries: per MinHash slot an ends table of one bucket per entry (rounded up to a power
 // of two: 0.5-1 postings per bucket), room for ne postings of 8 bytes, and the sort's scratch (as much again + the tile counts).
 static int inv_alloc(mhap_handle* h, int64_t ne) {
@@ -377,257 +370,185 @@ int fill_ids(mhap_handle* h, int64_t first, const int64_t* ids, int64_t n) {
 }
 
 
-// eager_index_entries > 0 (an add that very likely completes the index): the inverted index of entries [0, eager_index_entries) —
-// the tables' rows up to the end of this add — is built as soon as the last batch's MinHash rows and statuses exist, on the side
-// stream, next to the ordered-sketch kernel (which is bound by the LDS pipe and leaves the memory side idle): at C2 3 ms of index
-// build used to follow 4.8 ms of ordered kernel.
+// Strands whose hashes are recomputed from their 2-bit codes wherever they are consumed need no key / 32-bit hash arrays;
+// raw-byte reads, k != 16 / k2 != 12 and reads beyond the weight kernel's LDS path are hashed by hash_kmers_kernel (MHAP_RD_MAT).
+struct MatRule {
+  bool from_codes_ok; int k, k2;   // from_codes_ok: MHAP_FUSED_HASH is not 0
+  bool operator()(const ReadDesc& d) const { return (d.flags & MHAP_RD_RAW) || !from_codes_ok || !strand_hashes_from_codes(d.length, k, k2); }
+};
+// what the launch groups of one sketch_staged call share: the tables they write and the call's decisions
+struct SketchJob {
+  int32_t* d_minhash; int64_t mh_stride; int32_t* d_ordered; int64_t ord_stride; int32_t* d_meta;
+  int64_t eager_index_entries; bool eager_x; MatRule is_mat;
+};
+
+// One launch group as a list of launches: descriptors up, hash (if any strand is materialised), weights, the two list lengths back, the ordered
+// kernel's first part, MinHash with its fork and join, fix status, the eager index build on the side stream, the ordered rest, ids, drain.
+int sketch_group(mhap_handle* h, const SketchJob& J, const LaunchGroup& B, bool last) {
+  Switches sw; sw.read_sketch_group();   // (read at every launch group: tests switch them inside one process)
+  const int k = h->P.kmer_size, k2 = h->P.ordered_kmer_size, H = h->P.num_hashes, S = h->P.ordered_sketch_size;
+  const int64_t nb = B.r1 - B.r0, nstr = 2 * nb;
+  if (h->h_descs_cap < (size_t)nb) {
+    if (h->h_descs) (void)hipHostFree(h->h_descs);
+    h->h_descs = nullptr; h->h_descs_cap = 0;
+    const size_t want = (size_t)nb + (size_t)nb / 4 + 64;
+    HIPCHK(h, hipHostMalloc((void**)&h->h_descs, want * sizeof(ReadDesc), hipHostMallocDefault));
+    h->h_descs_cap = want;
+  }
+  const GroupLayout G = layout_group(h->st_descs.data() + B.r0, nb, k, k2, J.is_mat, h->h_descs);
+  const int32_t* d_order = nullptr;
+  if (!sw.no_length_order && length_order(h->h_descs, nb, G.min_len, B.max_len, h->h_order)) {
+    HIPCHK(h, h->order.ensure((size_t)nb * 4));
+    HIPCHK(h, hipMemcpyAsync(h->order.p, h->h_order.data(), (size_t)nb * 4, hipMemcpyHostToDevice, h->stream));
+    d_order = h->order.as<int32_t>();
+  }
+  int32_t* mh_rows = J.d_minhash + (2 * B.r0) * J.mh_stride;
+  int32_t* ord_rows = J.d_ordered + (2 * B.r0) * J.ord_stride;
+  int32_t* meta_rows = J.d_meta + (2 * B.r0) * META_W;
+  unsigned long long* ctr = h->counters.as<unsigned long long>();
+  const ReadDesc* dd = h->descs.as<ReadDesc>();
+  HIPCHK(h, hipMemcpyAsync(h->descs.p, h->h_descs, (size_t)nb * sizeof(ReadDesc), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemsetAsync(h->counters.p, 0, 256, h->stream));
+  const bool fused = k == 16 && k2 == 12;   // the table path exists: strands without MHAP_RD_MAT are hashed where their hashes are used
+  if (G.any_mat) {
+    time_begin(h, MHAP_K_HASH);
+    launch_hash_kmers(h->stream, dd, nstr, B.max_len, h->store.as<uint8_t>(), h->keys.as<int64_t>(), h->h32.as<int32_t>(), k, k2,
+                      h->hash_luts.as<uint64_t>(), 1);
+    time_end(h);
+    DBGSYNC(h, "hash_kmers");
+  }
+  HPROF("sketch: descriptors up");
+  time_begin(h, MHAP_K_WEIGHT);
+  launch_kmer_weights(h->stream, h->num_cus, dd, nstr, B.max_len, h->keys.as<int64_t>(), h->wts.as<uint32_t>(), h->perm.as<uint32_t>(),
+                      h->slabs.as<uint32_t>(), slab_entries(B.max_len, k), ctr + KC_BASE, k, h->ft, h->P.repeat_weight, h->info.as<StrandInfo>(), fused,
+                      h->store.as<uint8_t>(), h->hash_luts.as<uint64_t>(), d_order, h->slist.as<int32_t>());
+  time_end(h);
+  DBGSYNC(h, "kmer_weights");
+  int per_cu = minhash_wgs_per_cu(H);   // the launch is persistent: exactly the workgroups that can be resident
+  if (sw.minhash_wgs_per_cu) per_cu = sw.minhash_wgs_per_cu;
+  int mblocks = h->num_cus * per_cu;   // (each launch is trimmed to the workgroups its work list can feed)
+  if (J.eager_x) mblocks = std::max(per_cu, mblocks - dist_eager_reserve_wgs(h));   // (room for the all-gather's own kernels: mhap_dist.hip)
+  // (the slack factor only where the workgroups really have fewer than four waves — --num-hashes beyond ~3 000 — instead of 2 GB
+  //  of queue scratch at --num-hashes 2048 and 8.6 GB at 8192 for everybody)
+  HIPCHK(h, h->mhq.ensure(minhash_queue_bytes(2 * std::max(mblocks, 1), H) * (size_t)(minhash_waves_per_workgroup(H) < 4 ? 4 : 1)));
+  HIPCHK(h, h->mhmerge.ensure(minhash_merge_bytes(std::max(mblocks, 1), H)));
+  // The strands with weighted k-mers are a second launch (own instantiation).  On the same stream a handful of such strands (C2:
+  // under 1 %) hold the GPU for one strand's duration (3 ms) after the weight-1 launch has drained.  So the two list lengths are
+  // read back (one 16-byte copy: the weight kernel has to be complete anyway), each launch gets only the workgroups its list
+  // can feed, and the weighted one goes first, on its own stream: its few workgroups take their slots, the weight-1 launch fills
+  // the rest of the GPU.  (Full grids side by side do not work: whichever launch is first in line takes every slot before most of
+  // its workgroups find their list empty, +8 ms; the weighted launch second in line only moves into the draining tail, -1 ms.)
+  unsigned long long lens[KC_LIST_WEIGHTED - KC_LIST_W1 + 1] = {0, 0};
+  HIPCHK(h, hipMemcpyAsync(lens, ctr + KC_LIST_W1, sizeof lens, hipMemcpyDeviceToHost, h->stream));
+  { const int rs = sync_stream(h); if (rs != MHAP_OK) return rs; }
+  HPROF("sketch: list lengths back");
+  const int64_t n_w1 = (int64_t)lens[0], n_weighted = (int64_t)lens[KC_LIST_WEIGHTED - KC_LIST_W1];
+  // (Round 4 measured the ordered-sketch kernel — it only reads the strands — on a side stream next to the MinHash launch, with equal
+  //  and with lowest priority, and next to the weight kernel: 107.4 -> 107.6-108.4 and 108.1 -> 110-111.6 ms at C2.  It trickles
+  //  through the persistent MinHash grid's slots for 60-90 ms and slows that kernel by what it gains; the weight kernel and it both
+  //  live on the LDS pipe.  One stream it is.)
+  auto do_ordered = [&](int64_t first, int64_t count) {
+    time_begin(h, MHAP_K_ORDERED);
+    launch_ordered(h->stream, dd, nstr, G.max_len_codes, B.max_len, h->h32.as<int32_t>(), h->store.as<uint8_t>(), h->hash_luts.as<uint64_t>(), k2, S, h->ord_cap,
+                   ord_rows, J.ord_stride, meta_rows, META_W, first, count);
+    time_end(h);
+  };
+  const OrderedSchedule os = ordered_schedule(sw, G.read_bases, n_w1, n_weighted, nstr, J.eager_x);   // (sketch_plan.hpp: the rule and its measurements)
+  bool ordered_done = false;
+  if (os.pre > 0) {
+    do_ordered(0, os.pre);
+    ordered_done = os.pre >= nstr;
+    if (!os.nowait) {
+      HIPCHK(h, hipEventRecord(h->ev_mh_fork, h->stream));
+      HIPCHK(h, hipStreamWaitEvent(h->mh_stream, h->ev_mh_fork, 0));
+    }
+  }
+  if (J.eager_x) {
+    // eager exchange: the ordered rows first (they do not depend on the MinHash rows), so that their all-gather — 6/7 of the bytes
+    // a rank sends — runs under the MinHash kernel; its copy engines / RCCL workgroups are in place before the persistent grid starts
+    do_ordered(0, nstr);
+    ordered_done = true;
+    const int rxo = dist_eager_ordered(h, h->stream, ord_rows);
+    if (rxo != MHAP_OK) return rxo;
+  }
+  if (os.idle_gap) (void)hipStreamSynchronize(h->stream);
+  for (int i = 0; i < os.prefill; i++) (void)hipMemsetAsync(h->mhq.p, 0, h->mhq.cap, h->stream);
+  const size_t t_mh = time_begin(h, MHAP_K_MINHASH);
+  const bool mh_forked = launch_minhash(h->stream, h->mh_stream, mblocks, n_w1, n_weighted, dd, nstr, h->keys.as<int64_t>(), h->wts.as<uint32_t>(),
+                 h->perm.as<uint32_t>(), h->info.as<StrandInfo>(), h->store.as<uint8_t>(), h->hash_luts.as<uint64_t>(), k, k2, H, ctr + KC_BASE, mh_rows, J.mh_stride,
+                 meta_rows + 3, META_W, h->jump_tbl.as<uint64_t>(), h->jump_na, h->slist.as<int32_t>(), h->mhq.as<uint32_t>(), h->unjump_tbl.as<uint64_t>(), h->jump_w1_tbl.as<uint64_t>(),
+                 h->mhmerge.as<unsigned long long>(), std::max(0, B.max_len - k + 1));
+  if (mh_forked) {   // (the strands with weighted k-mers went to their own stream)
+    HIPCHK(h, hipEventRecord(h->ev_mh_join, h->mh_stream));
+    HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_mh_join, 0));
+  }
+  time_end_at(h, t_mh);
+  DBGSYNC(h, "minhash");
+  launch_fix_status(h->stream, meta_rows, nb);   // statuses are final here (the ordered kernel only writes sizes)
+  if (J.eager_x) { const int rxm = dist_eager_minhash(h, h->stream, mh_rows, meta_rows); if (rxm != MHAP_OK) return rxm; }
+  // eager_index_entries > 0 (an add that very likely completes the index): the inverted index of entries [0, eager_index_entries) —
+  // the tables' rows up to the end of this add — is built as soon as the last group's MinHash rows and statuses exist, on the side
+  // stream, next to the ordered-sketch kernel (which is bound by the LDS pipe and leaves the memory side idle): at C2 3 ms of index
+  // build used to follow 4.8 ms of ordered kernel.
+  bool eager_launched = false;
+  if (J.eager_index_entries > 0 && last && !sw.no_eager_index) {
+    HIPCHK(h, hipEventRecord(h->ev_ix_fork, h->stream));
+    HIPCHK(h, hipStreamWaitEvent(h->mh_stream, h->ev_ix_fork, 0));
+    const int rce = ensure_inverted_index(h, h->mh_stream, J.eager_index_entries);
+    if (rce != MHAP_OK) return rce;   // inv_ready is not reset on this path (a behaviour change: its own pull request)
+    HIPCHK(h, hipEventRecord(h->ev_ix_join, h->mh_stream));
+    eager_launched = true;
+  }
+  if (!ordered_done) do_ordered(os.pre, nstr - os.pre);
+  DBGSYNC(h, "ordered");
+  HIPCHK(h, hipGetLastError());
+  if (eager_launched) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_ix_join, 0));
+  HPROF("sketch: all launched");
+  if (last && h->pend_ids.n > 0 && !h->pend_ids.done) {   // (host work and a copy the kernels do not touch: under the GPU's time)
+    const int rf = fill_ids(h, h->pend_ids.first, h->pend_ids.ids, h->pend_ids.n);
+    if (rf != MHAP_OK) { (void)sync_stream(h); return rf; }
+    h->pend_ids.done = true;
+  }
+  const int rc = sync_stream(h);   // h_descs is reused by the next group
+  if (rc == MHAP_OK) HPROF("sketch: stream drained");
+  return rc;
+}
+
+// Sketch the staged reads into device rows [0, 2*st_n) of the given tables (kernels only + tiny descriptor uploads).
+// Launch groups run back to back on the handle's stream.  (A two-stream variant that overlapped hash/weight/ordered of
+// group b+1 with MinHash of group b was measured at 358 -> 355..365 ms/step: the kernels compete for the same VALU
+// issue slots and LDS, so it was removed.)
 int sketch_staged(mhap_handle* h, int32_t* d_minhash, int64_t mh_stride, int32_t* d_ordered, int64_t ord_stride, int32_t* d_meta,
                   int64_t eager_index_entries = 0, bool eager_exchange = false, bool eager_first = false) {
   const int64_t n = h->st_n;
   if (n <= 0) { if (eager_exchange) { const int rx = dist_eager_begin(h, 0, nullptr, false); if (rx < 0) return rx; } return MHAP_OK; }
   HPROF("sketch_staged begin");
-  const int k = h->P.kmer_size, k2 = h->P.ordered_kmer_size, H = h->P.num_hashes, S = h->P.ordered_sketch_size;
-  int64_t batch_bases = 1LL << 30;   // bases per launch group: 16 B of scratch per base (weights + class lists of both strands) = 16 GB of the 288 GB;
-                                     // fewer, larger launches = fewer drain tails of the persistent MinHash waves (a strand takes ~2 ms)
-  {   // Round 6: larger launch groups where the HBM is there — a job of more than 1 G bases (configs[3]: 15 G) is cut into groups of up to 4 G bases
-      // as long as their scratch stays under a quarter of the memory that is free now: 14 -> 4 groups at C4, 1 469 -> 1 437 ms on one box (fewer
-      // drain tails, fewer launches into an idle GPU).  The groups of one rank of configs[4] at N = 8 (137 GB in use) stay where they were.
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-      const int64_t by_mem = (int64_t)(free_b / 4 / 16);
-      batch_bases = std::max<int64_t>(batch_bases, std::min<int64_t>(4LL << 30, by_mem));
-    }
-  }
-  if (const char* e = getenv("MHAP_BATCH_BASES")) { long long v = atoll(e); if (v > 0) batch_bases = v; }
-  // Strands whose hashes are recomputed from their 2-bit codes wherever they are consumed need no key / 32-bit hash arrays;
-  // raw-byte reads, k != 16 / k2 != 12 and reads beyond the weight kernel's LDS path are hashed by hash_kmers_kernel (MHAP_RD_MAT).
-  const char* fenv = getenv("MHAP_FUSED_HASH");
-  const bool from_codes_ok = !(fenv && atoi(fenv) == 0);
-  auto is_mat = [&](const ReadDesc& d) { return (d.flags & MHAP_RD_RAW) || !from_codes_ok || !strand_hashes_from_codes(d.length, k, k2); };
-  // ---- batch plan + worst-case scratch sizes (allocated once) ----
-  struct Batch { int64_t r0, r1; int max_len; };
-  std::vector<Batch> plan;
-  int64_t max_key = 4, max_h2 = 4, max_w = 4, max_nb = 1;
-  int max_len_all = 0;
-  for (int64_t r0 = 0; r0 < n;) {
-    int64_t r1 = r0, tot = 0;
-    while (r1 < n && (r1 == r0 || tot + h->st_descs[(size_t)r1].length <= batch_bases) && (r1 - r0) < (1 << 22)) { tot += h->st_descs[(size_t)r1].length; r1++; }
-    Batch b{r0, r1, 0};
-    int64_t key_elems = 0, h2_elems = 0, w_elems = 0;
-    for (int64_t i = r0; i < r1; i++) {
-      const ReadDesc& d = h->st_descs[(size_t)i];
-      if (d.flags & MHAP_RD_SKIP) continue;
-      w_elems += 2 * align4(std::max(0, d.length - k + 1));
-      if (is_mat(d)) { key_elems += 2 * align4(std::max(0, d.length - k + 1)); h2_elems += 2 * align4(std::max(0, d.length - k2 + 1)); }
-      b.max_len = std::max(b.max_len, d.length);
-    }
-    max_key = std::max(max_key, key_elems); max_h2 = std::max(max_h2, h2_elems); max_w = std::max(max_w, w_elems); max_nb = std::max(max_nb, r1 - r0);
-    max_len_all = std::max(max_len_all, b.max_len);
-    plan.push_back(b);
-    r0 = r1;
-  }
+  const int k = h->P.kmer_size, k2 = h->P.ordered_kmer_size;
+  Switches sw; sw.read_sketch_call();
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;   // the budget ignores the 40 B/base of materialised reads (its own pull request)
+  SketchJob J{d_minhash, mh_stride, d_ordered, ord_stride, d_meta, eager_index_entries, false, MatRule{sw.fused_hash, k, k2}};
+  const SketchPlan plan = plan_launch_groups(h->st_descs.data(), n, launch_group_bases(free_b, sw.batch_bases), k, k2, J.is_mat);
   // Eager exchange (mhap_dist_set_eager): the rendezvous of the ranks — collective, so every rank of the job gets here — says whether
   // this add gathers its rows while it computes.  Only an add of one launch group can (the rows of earlier groups would have to wait).
-  bool eager_x = false;
   if (eager_exchange) {
-    const int rx = dist_eager_begin(h, n, h->st_ids.data(), plan.size() == 1 && eager_first);
+    const int rx = dist_eager_begin(h, n, h->st_ids.data(), plan.groups.size() == 1 && eager_first);
     if (rx < 0) return rx;
-    eager_x = rx == 1;
+    J.eager_x = rx == 1;
   }
-  HIPCHK(h, h->descs.ensure((size_t)max_nb * sizeof(ReadDesc)));
-  HIPCHK(h, h->keys.ensure((size_t)max_key * 8));
-  HIPCHK(h, h->h32.ensure((size_t)max_h2 * 4));
-  HIPCHK(h, h->wts.ensure((size_t)max_w * 4));
-  HIPCHK(h, h->perm.ensure((size_t)max_w * 4));
-  HIPCHK(h, h->info.ensure((size_t)(2 * max_nb) * sizeof(StrandInfo)));
-  HIPCHK(h, h->slist.ensure((size_t)(4 * max_nb) * 4));
+  HIPCHK(h, h->descs.ensure((size_t)plan.max_nb * sizeof(ReadDesc)));
+  HIPCHK(h, h->keys.ensure((size_t)plan.max_key * 8));
+  HIPCHK(h, h->h32.ensure((size_t)plan.max_h2 * 4));
+  HIPCHK(h, h->wts.ensure((size_t)plan.max_w * 4));
+  HIPCHK(h, h->perm.ensure((size_t)plan.max_w * 4));
+  HIPCHK(h, h->info.ensure((size_t)(2 * plan.max_nb) * sizeof(StrandInfo)));
+  HIPCHK(h, h->slist.ensure((size_t)(4 * plan.max_nb) * 4));
   HIPCHK(h, h->counters.ensure(256));
-  {
-    const int wb = weight_grid(h->num_cus, 2 * max_nb, max_len_all, k);
-    int64_t se = 64;
-    while (3 * se < 4LL * std::max(1, max_len_all - k + 1)) se <<= 1;
-    HIPCHK(h, h->slabs.ensure((size_t)wb * (size_t)se * 4));
-  }
+  HIPCHK(h, h->slabs.ensure((size_t)weight_grid(h->num_cus, 2 * plan.max_nb, plan.max_len_all, k) * (size_t)slab_entries(plan.max_len_all, k) * 4));
   HPROF("sketch: plan + scratch");
-  for (const Batch& B : plan) {
-    const int64_t nb = B.r1 - B.r0, nstr = 2 * nb;
-    if (h->h_descs_cap < (size_t)nb) {
-      if (h->h_descs) (void)hipHostFree(h->h_descs);
-      h->h_descs = nullptr; h->h_descs_cap = 0;
-      const size_t want = (size_t)nb + (size_t)nb / 4 + 64;
-      HIPCHK(h, hipHostMalloc((void**)&h->h_descs, want * sizeof(ReadDesc), hipHostMallocDefault));
-      h->h_descs_cap = want;
-    }
-    int64_t key_elems = 0, h2_elems = 0, w_elems = 0;
-    bool any_mat = false;
-    int min_len_b = INT32_MAX, max_len_codes = 0;
-    for (int64_t i = 0; i < nb; i++) {
-      ReadDesc d = h->st_descs[(size_t)(B.r0 + i)];
-      const bool skip = (d.flags & MHAP_RD_SKIP) != 0;
-      if (!skip) min_len_b = std::min(min_len_b, d.length);
-      const int64_t nk = align4(std::max(0, d.length - k + 1)), nk2 = align4(std::max(0, d.length - k2 + 1));
-      d.key_off = d.h2_off = 0;
-      d.w_off = w_elems; d.key_stride = (int32_t)nk; d.h2_stride = (int32_t)nk2;
-      if (!skip) {
-        w_elems += 2 * nk;
-        if (is_mat(d)) {
-          d.flags |= MHAP_RD_MAT; any_mat = true;
-          d.key_off = key_elems; d.h2_off = h2_elems;
-          key_elems += 2 * nk; h2_elems += 2 * nk2;
-        } else max_len_codes = std::max(max_len_codes, d.length);
-      }
-      h->h_descs[(size_t)i] = d;
-    }
-    // reads of clearly different lengths: hand them out longest first (counting sort on length / 128), so that the persistent
-    // workgroups do not end on a long read while the rest of the GPU idles
-    const int32_t* d_order = nullptr;
-    if (min_len_b * 5 < B.max_len * 4 && nb > 1 && !getenv("MHAP_NO_LENGTH_ORDER")) {
-      const int nbk = B.max_len / 128 + 2;
-      std::vector<int64_t> start((size_t)nbk + 1, 0);
-      for (int64_t i = 0; i < nb; i++) start[(size_t)(nbk - 1 - h->h_descs[(size_t)i].length / 128)]++;
-      int64_t acc = 0;
-      for (int b = 0; b <= nbk; b++) { const int64_t c = start[(size_t)b]; start[(size_t)b] = acc; acc += c; }
-      h->h_order.resize((size_t)nb);
-      for (int64_t i = 0; i < nb; i++) h->h_order[(size_t)start[(size_t)(nbk - 1 - h->h_descs[(size_t)i].length / 128)]++] = (int32_t)i;
-      HIPCHK(h, h->order.ensure((size_t)nb * 4));
-      HIPCHK(h, hipMemcpyAsync(h->order.p, h->h_order.data(), (size_t)nb * 4, hipMemcpyHostToDevice, h->stream));
-      d_order = h->order.as<int32_t>();
-    }
-    int64_t slab_entries = 64;
-    while (3 * slab_entries < 4LL * std::max(1, B.max_len - k + 1)) slab_entries <<= 1;
-    int32_t* mh_rows = d_minhash + (2 * B.r0) * mh_stride;
-    int32_t* ord_rows = d_ordered + (2 * B.r0) * ord_stride;
-    int32_t* meta_rows = d_meta + (2 * B.r0) * META_W;
-    unsigned long long* ctr = h->counters.as<unsigned long long>();
-    const ReadDesc* dd = h->descs.as<ReadDesc>();
-    HIPCHK(h, hipMemcpyAsync(h->descs.p, h->h_descs, (size_t)nb * sizeof(ReadDesc), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemsetAsync(h->counters.p, 0, 256, h->stream));
-    const bool fused = k == 16 && k2 == 12;   // the table path exists: strands without MHAP_RD_MAT are hashed where their hashes are used
-    if (any_mat) {
-      time_begin(h, MHAP_K_HASH);
-      launch_hash_kmers(h->stream, dd, nstr, B.max_len, h->store.as<uint8_t>(), h->keys.as<int64_t>(), h->h32.as<int32_t>(), k, k2,
-                        h->hash_luts.as<uint64_t>(), 1);
-      time_end(h);
-      DBGSYNC(h, "hash_kmers");
-    }
-    HPROF("sketch: descriptors up");
-    time_begin(h, MHAP_K_WEIGHT);
-    launch_kmer_weights(h->stream, h->num_cus, dd, nstr, B.max_len, h->keys.as<int64_t>(), h->wts.as<uint32_t>(), h->perm.as<uint32_t>(),
-                        h->slabs.as<uint32_t>(), slab_entries, ctr + 0, k, h->ft, h->P.repeat_weight, h->info.as<StrandInfo>(), fused,
-                        h->store.as<uint8_t>(), h->hash_luts.as<uint64_t>(), d_order, h->slist.as<int32_t>());
-    time_end(h);
-    DBGSYNC(h, "kmer_weights");
-    int per_cu = minhash_wgs_per_cu(H);   // the launch is persistent: exactly the workgroups that can be resident
-    if (const char* e = getenv("MHAP_MINHASH_WGS_PER_CU")) { int v = atoi(e); if (v >= 1 && v <= 8) per_cu = v; }
-    int mblocks = h->num_cus * per_cu;   // (each launch is trimmed to the workgroups its work list can feed)
-    if (eager_x) mblocks = std::max(per_cu, mblocks - dist_eager_reserve_wgs(h));   // (room for the all-gather's own kernels: mhap_dist.hip)
-    // (the slack factor only where the workgroups really have fewer than four waves — --num-hashes beyond ~3 000 — instead of 2 GB
-    //  of queue scratch at --num-hashes 2048 and 8.6 GB at 8192 for everybody)
-    HIPCHK(h, h->mhq.ensure(minhash_queue_bytes(2 * std::max(mblocks, 1), H) * (size_t)(minhash_waves_per_workgroup(H) < 4 ? 4 : 1)));
-    HIPCHK(h, h->mhmerge.ensure(minhash_merge_bytes(std::max(mblocks, 1), H)));
-    // The strands with weighted k-mers are a second launch (own instantiation).  On the same stream a handful of such strands (C2:
-    // under 1 %) hold the GPU for one strand's duration (3 ms) after the weight-1 launch has drained.  So the two list lengths are
-    // read back (one 16-byte copy: the weight kernel has to be complete anyway), each launch gets only the workgroups its list
-    // can feed, and the weighted one goes first, on its own stream: its few workgroups take their slots, the weight-1 launch fills
-    // the rest of the GPU.  (Full grids side by side do not work: whichever launch is first in line takes every slot before most of
-    // its workgroups find their list empty, +8 ms; the weighted launch second in line only moves into the draining tail, -1 ms.)
-    unsigned long long lens[2] = {0, 0};
-    HIPCHK(h, hipMemcpyAsync(lens, ctr + 4, 16, hipMemcpyDeviceToHost, h->stream));
-    { const int rs = sync_stream(h); if (rs != MHAP_OK) return rs; }
-    HPROF("sketch: list lengths back");
-    // (Round 4 measured the ordered-sketch kernel — it only reads the strands — on a side stream next to the MinHash launch, with equal
-    //  and with lowest priority, and next to the weight kernel: 107.4 -> 107.6-108.4 and 108.1 -> 110-111.6 ms at C2.  It trickles
-    //  through the persistent MinHash grid's slots for 60-90 ms and slows that kernel by what it gains; the weight kernel and it both
-    //  live on the LDS pipe.  One stream it is.)
-    const hipStream_t ost = h->stream;
-    auto do_ordered = [&](int64_t first, int64_t count) -> int {
-      time_begin(h, MHAP_K_ORDERED, ost);
-      launch_ordered(ost, dd, nstr, max_len_codes, B.max_len, h->h32.as<int32_t>(), h->store.as<uint8_t>(), h->hash_luts.as<uint64_t>(), k2, S, h->ord_cap,
-                     ord_rows, ord_stride, meta_rows, META_W, first, count);
-      time_end(h, ost);
-      return MHAP_OK;
-    };
-    // Round 6: PART of the ordered kernel runs between the weight kernel's read-back and the weight-1 MinHash launch, and the weighted strands'
-    // MinHash launch (its own stream) runs NEXT TO THAT PART instead of next to the weight-1 launch's start.  Measured, not derived (EXPERIMENTS.md,
-    // round 6, "the MinHash launch's clock"): the weight-1 launch of C2 — 75 ms at the card's power limit — holds whatever clock the power
-    // management settles on when it starts.  Started into an idle GPU (the read-back is a host round trip) together with the weighted launch it held
-    // 1 820-2 126 MHz from step to step; started alone, right behind a running, moderately busy kernel, 2 164-2 179 MHz every time
-    // (MHAP_MINHASH_PROF): 76.2-76.8 -> 72.1-72.4 ms, the C2 step 93.4-94.6 -> 90.5-91.3 ms on one box.  With the weighted launch made to wait for
-    // the ordered part the gain is gone (76.1-76.3); behind memory fills the clock is 1 800; with an idle gap behind the ordered part 1 850-2 030.
-    // The rest of the strands' ordered rows are made behind the MinHash launch, next to the index build as before (the build takes about as long as
-    // 0.45 of the ordered kernel beside it).  Only where a LONG weight-1 launch is the job: a launch group of 0.9 G bases of reads or more (a
-    // MinHash launch of 60 ms and more: C2 on one GPU, the launch groups of C4) with at most a fifth of the strands weighted.  Shorter launches
-    // lose by it — one rank's share of an N-GPU C2 job, same box, alternating: N = 2 / 4 / 8 rank step 50.5 -> 50.7 / 26.85 -> 27.6 / 14.8 -> 15.2 ms —
-    // and a -f run's strands are all weighted (its MinHash launch would run under the ordered part from the start: c5slice 180.3 -> 180.5 / 184.6).
-    // MHAP_ORDERED_SPLIT = per cent of the strands in the first part (0 = rounds 1-5's order, 100 = all of them); MHAP_ORDERED_NOWAIT=0 makes the
-    // weighted launch wait for the first part; MHAP_ORDERED_FIRST=1 / 2 = all of it first / and an idle gap behind it (the experiments).
-    // (read at every launch group: tests switch them inside one process)
-    const int ord_first_env = []() { const char* e = getenv("MHAP_ORDERED_FIRST"); return e ? atoi(e) : 0; }();
-    const int ord_split_env = []() { const char* e = getenv("MHAP_ORDERED_SPLIT"); const int v = e ? atoi(e) : -1; return v > 100 ? 100 : v; }();
-    int64_t batch_read_bases = 0;
-    for (int64_t i = 0; i < nb; i++) batch_read_bases += h->h_descs[(size_t)i].length;
-    const bool split_pays = batch_read_bases >= 900000000LL && (int64_t)lens[0] >= 4 * (int64_t)lens[1];
-    int64_t ord_pre = ord_first_env ? nstr : (nstr * (int64_t)(ord_split_env >= 0 ? ord_split_env : (split_pays ? 55 : 0))) / 100;
-    ord_pre &= ~(int64_t)1;   // (both strands of a read in one part)
-    bool ordered_done = false;
-    if (ord_pre > 0 && !eager_x) {
-      (void)do_ordered(0, ord_pre);
-      ordered_done = ord_pre >= nstr;
-      const int nowait = []() { const char* e = getenv("MHAP_ORDERED_NOWAIT"); return e ? atoi(e) : 1; }();
-      if (!nowait) {
-        HIPCHK(h, hipEventRecord(h->ev_mh_fork, h->stream));
-        HIPCHK(h, hipStreamWaitEvent(h->mh_stream, h->ev_mh_fork, 0));
-      }
-    } else ord_pre = 0;
-    if (eager_x) {
-      // eager exchange: the ordered rows first (they do not depend on the MinHash rows), so that their all-gather — 6/7 of the bytes
-      // a rank sends — runs under the MinHash kernel; its copy engines / RCCL workgroups are in place before the persistent grid starts
-      (void)do_ordered(0, nstr);
-      ordered_done = true;
-      const int rxo = dist_eager_ordered(h, h->stream, ord_rows);
-      if (rxo != MHAP_OK) return rxo;
-    }
-    {   // experiments (round 6, EXPERIMENTS.md "the MinHash launch's clock"): MHAP_ORDERED_FIRST=2 = an idle gap between the ordered kernel and the
-        // MinHash launch; MHAP_W1_PREFILL=n = n fills of the queue buffer in front of the MinHash launch (it is enqueued behind running work)
-      const int prefill = []() { const char* e = getenv("MHAP_W1_PREFILL"); return e ? atoi(e) : 0; }();   // (read at every launch group)
-      if (ord_first_env == 2) (void)hipStreamSynchronize(h->stream);
-      for (int i = 0; i < prefill; i++) (void)hipMemsetAsync(h->mhq.p, 0, h->mhq.cap, h->stream);
-    }
-    const size_t t_mh = time_begin(h, MHAP_K_MINHASH);
-    const bool mh_forked = launch_minhash(h->stream, h->mh_stream, mblocks, (int64_t)lens[0], (int64_t)lens[1], dd, nstr, h->keys.as<int64_t>(), h->wts.as<uint32_t>(),
-                   h->perm.as<uint32_t>(), h->info.as<StrandInfo>(), h->store.as<uint8_t>(), h->hash_luts.as<uint64_t>(), k, k2, H, ctr, mh_rows, mh_stride,
-                   meta_rows + 3, META_W, h->jump_tbl.as<uint64_t>(), h->jump_na, h->slist.as<int32_t>(), h->mhq.as<uint32_t>(), h->unjump_tbl.as<uint64_t>(), h->jump_w1_tbl.as<uint64_t>(),
-                   h->mhmerge.as<unsigned long long>(), std::max(0, B.max_len - k + 1));
-    if (mh_forked) {   // (the strands with weighted k-mers went to their own stream)
-      HIPCHK(h, hipEventRecord(h->ev_mh_join, h->mh_stream));
-      HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_mh_join, 0));
-    }
-    time_end_at(h, t_mh);
-    DBGSYNC(h, "minhash");
-    launch_fix_status(h->stream, meta_rows, nb);   // statuses are final here (the ordered kernel only writes sizes)
-    if (eager_x) { const int rxm = dist_eager_minhash(h, h->stream, mh_rows, meta_rows); if (rxm != MHAP_OK) return rxm; }
-    bool eager_launched = false;
-    if (eager_index_entries > 0 && &B == &plan.back() && !getenv("MHAP_NO_EAGER_INDEX")) {
-      HIPCHK(h, hipEventRecord(h->ev_ix_fork, h->stream));
-      HIPCHK(h, hipStreamWaitEvent(h->mh_stream, h->ev_ix_fork, 0));
-      const int rce = ensure_inverted_index(h, h->mh_stream, eager_index_entries);
-      if (rce != MHAP_OK) return rce;
-      HIPCHK(h, hipEventRecord(h->ev_ix_join, h->mh_stream));
-      eager_launched = true;
-    }
-    if (!ordered_done) (void)do_ordered(ord_pre, nstr - ord_pre);
-    DBGSYNC(h, "ordered");
-    HIPCHK(h, hipGetLastError());
-    if (eager_launched) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_ix_join, 0));
-    HPROF("sketch: all launched");
-    if (&B == &plan.back() && h->pend_ids.n > 0 && !h->pend_ids.done) {   // (host work and a copy the kernels do not touch: under the GPU's time)
-      const int rf = fill_ids(h, h->pend_ids.first, h->pend_ids.ids, h->pend_ids.n);
-      if (rf != MHAP_OK) { (void)sync_stream(h); return rf; }
-      h->pend_ids.done = true;
-    }
-    int rc = sync_stream(h);   // h_descs is reused by the next batch
+  for (const LaunchGroup& B : plan.groups) {
+    const int rc = sketch_group(h, J, B, &B == &plan.groups.back());
     if (rc != MHAP_OK) return rc;
-    HPROF("sketch: stream drained");
   }
   return MHAP_OK;
 }
@@ -692,7 +613,6 @@ struct QuerySide {
   const uint8_t* h_valid = nullptr;
 };
 
-// Run candidate + second stage for the query entries in `ql` (entry indices into the query side).
 // (re)build the inverted index for the current entries unless the table in place already covers them
 int ensure_inverted_index(mhap_handle* h, hipStream_t st, int64_t ne_override) {
   const int ne = (int)(ne_override >= 0 ? ne_override : h->n_entries), H = h->P.num_hashes;
@@ -705,13 +625,14 @@ int ensure_inverted_index(mhap_handle* h, hipStream_t st, int64_t ne_override) {
   time_end(h, st);
   if (!built) return fail(h, MHAP_E_STATE, "inverted index: its tiles do not cover the entries it was sized for");
   HIPCHK(h, hipGetLastError());
-  if (getenv("MHAP_DEBUG_INDEX")) {   // self-check: every stored (entry, slot) must find its own posting
+  Switches sw; sw.read_index_build();
+  if (sw.debug_index) {   // self-check: every stored (entry, slot) must find its own posting
     HIPCHK(h, h->counters.ensure(256));
-    unsigned long long* ctr = h->counters.as<unsigned long long>();
+    unsigned long long* missing_ctr = h->counters.as<unsigned long long>() + SC_INDEX_MISSING;
     unsigned long long missing = 0;
-    HIPCHK(h, hipMemsetAsync(ctr + 15, 0, 8, st));
-    launch_index_verify(st, h->d_minhash, h->Hrow, h->d_meta, ne, H, h->inv, ctr + 15);
-    HIPCHK(h, hipMemcpyAsync(&missing, ctr + 15, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemsetAsync(missing_ctr, 0, 8, st));
+    launch_index_verify(st, h->d_minhash, h->Hrow, h->d_meta, ne, H, h->inv, missing_ctr);
+    HIPCHK(h, hipMemcpyAsync(&missing, missing_ctr, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));
     fprintf(stderr, "[index] self-check: %llu of %lld postings missing\n", missing, (long long)ne * H);
     if (missing) return fail(h, MHAP_E_STATE, "inverted index self-check failed");
@@ -811,199 +732,232 @@ struct PostStage {
   ~PostStage() { (void)drain(); }
 };
 
-int search_core(mhap_handle* h, QuerySide& qs, const std::vector<int32_t>& ql_in, bool to_self, bool triangular_ok,
-                mhap_record_sink sink, void* user) {
-  // candidate generation: GPU inverted index (default) or brute-force all-pairs (MHAP_CANDIDATES=bruteforce)
-  const char* cmode = getenv("MHAP_CANDIDATES");
-  const bool use_index = !(cmode && strcmp(cmode, "bruteforce") == 0);
-  bool prep_done = !qs.prep;
-  auto run_prep = [&]() -> int { if (prep_done) return MHAP_OK; prep_done = true; return qs.prep(qs); };
-  auto count_valid = [&](int64_t a, int64_t n) { int64_t c = 0; for (int64_t e = a; e < a + n; e++) c += qs.h_valid[(size_t)e] ? 1 : 0; return c; };
-  // the list on the device (identity) unless the brute-force tiles want it sorted out on the host, the index is empty, or MHAP_QUERY_LIST_HOST=1 (A/B, tests)
-  bool ident = qs.identity;
-  std::vector<int32_t> ql_made;
-  if (ident && (!use_index || h->n_entries == 0 || getenv("MHAP_QUERY_LIST_HOST"))) {
-    const int rp = run_prep();
-    if (rp != MHAP_OK) return rp;
-    ql_made.reserve((size_t)qs.n_rows);
-    for (int64_t e = 0; e < qs.n_rows; e++) if (qs.h_valid[(size_t)e]) ql_made.push_back((int32_t)e);
-    ident = false;
+// One chunk of a search: queries qlist[c0, c0 + nq), its triangular row starts (brute force only) and its candidates.
+struct Chunk { int64_t c0; int nq, ntq; const long long* d_rowstart; long long nblocks_tri; unsigned long long ncand; };
+constexpr int CHUNK_DONE = 1;   // a step's "nothing further for this chunk" (error codes are negative)
+
+// The state of one search_core call and its steps.  A step returns MHAP_OK, CHUNK_DONE, or an error that has gone through leave().
+struct Search {
+  mhap_handle* h; QuerySide& qs; SearchParams sp{}; Switches sw;
+  bool use_index = true, triangular_ok = false, ident = false, prep_done = true;
+  bool q_ph_done = false;    // the query side's position histograms exist (second stage, early "below the threshold")
+  std::vector<int32_t> ql_made; const std::vector<int32_t>* ql = nullptr; int64_t nql = 0;
+  int64_t qchunk = 0;        // queries per candidate/overlap launch pair (bounds the candidate buffer)
+  size_t cand_cap = 0;
+  int slot = 0;              // the record buffers (device + host) this chunk's kernels and tail use; flips with every tail handed over
+  unsigned long long* ctr = nullptr;
+  PostStage post;
+  Search(mhap_handle* h_, QuerySide& q) : h(h_), qs(q) {}
+
+  int run_prep() { if (prep_done) return MHAP_OK; prep_done = true; return qs.prep(qs); }
+  // every error return of the steps leaves through here: the worker is drained first (its buffers belong to the handle), the records it has
+  // already delivered are credited, and — if the search itself was fine — the worker's own error is the one reported
+  int leave(int code) {
+    const int pr = post.drain(); h->stats.matches_found += post.matches; post.matches = 0;
+    if (code == MHAP_OK && pr != MHAP_OK) return fail(h, pr, post.err);
+    return code;
   }
-  const std::vector<int32_t>& ql = qs.identity && !ident ? ql_made : ql_in;
-  const int64_t nql = ident ? qs.n_rows : (int64_t)ql.size();
-  if (nql == 0 || h->n_entries == 0) { h->stats.queries_searched += nql; return MHAP_OK; }
-  const int S = h->P.ordered_sketch_size;
-  SearchParams sp;
-  sp.H = h->P.num_hashes; sp.S = S; sp.k2 = h->P.ordered_kmer_size;
-  sp.num_min_matches = h->P.num_min_matches; sp.min_store_length = h->P.min_store_length; sp.to_self = to_self ? 1 : 0;
-  sp.own_queries = (to_self && qs.d_minhash == h->d_minhash && qs.d_meta == h->d_meta && !getenv("MHAP_COUNT_OWN")) ? 1 : 0;
-  sp.max_shift = h->P.max_shift; sp.threshold = h->P.threshold;
-  const int ne = (int)h->n_entries;
-  int64_t qchunk = 262144;   // queries per candidate/overlap launch pair (bounds the candidate buffer)
-  if (const char* e = getenv("MHAP_QUERY_CHUNK")) { long long v = atoll(e); if (v >= CAND_TQ) qchunk = (v / CAND_TQ) * CAND_TQ; }
-  HIPCHK(h, h->qlist.ensure((size_t)nql * 4));
-  if (ident) { launch_query_iota(h->stream, h->qlist.as<int32_t>(), 0, (int)nql); HIPCHK(h, hipGetLastError()); }
-  else HIPCHK(h, hipMemcpyAsync(h->qlist.p, ql.data(), ql.size() * 4, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, h->counters.ensure(256));
-  unsigned long long* ctr = h->counters.as<unsigned long long>();
-  size_t cand_cap = std::max<size_t>(h->cand.cap / sizeof(Candidate), (size_t)4 << 20);
-  // second stage: one lane per candidate; it is latency-bound, so put as many lanes in flight as the candidates allow
-  // (per-lane scratch = 3 int arrays of 2S+2 entries: 37 KB at S=1536; 16 workgroups/CU = 19 GB of the 288 GB HBM)
-  int64_t ovl_max_blocks = (int64_t)h->num_cus * 16;
-  if (const char* e = getenv("MHAP_OVERLAP_BLOCKS")) { long long v = atoll(e); if (v > 0) ovl_max_blocks = v; }
-  const int64_t per_lane = 3LL * (2LL * S + 2);
-  const char* omode = getenv("MHAP_OVERLAP");
-  const bool lane_only = omode && strcmp(omode, "lane") == 0;
-  { const char* jw = getenv("MHAP_JOIN_WIDE"); h->join_wide = !jw ? 2 : (jw[0] == '0' ? 0 : (jw[0] == '1' ? 1 : 2)); }
-  { const char* jm = getenv("MHAP_JOIN_MODE"); h->join_mode = !jm ? 0 : (strcmp(jm, "alone") == 0 ? 1 : (strcmp(jm, "pair") == 0 ? 2 : (strcmp(jm, "team") == 0 ? 3 : 0))); }
-  const int ntu = (ne + CAND_TM - 1) / CAND_TM;
-  if (use_index) {
-    int rcb = ensure_inverted_index(h);
-    if (rcb != MHAP_OK) return rcb;
+#define SCHK(expr) do { const hipError_t _e = (expr); if (_e != hipSuccess) return leave(fail(h, _e == hipErrorOutOfMemory ? MHAP_E_NOMEM : MHAP_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e))); } while (0)
+
+  // the list on the device (identity) unless the brute-force tiles want it sorted out on the host, the index is empty, or MHAP_QUERY_LIST_HOST=1 (A/B, tests)
+  int make_query_list(const std::vector<int32_t>& ql_in) {
+    ident = qs.identity;
+    if (ident && (!use_index || h->n_entries == 0 || sw.query_list_host)) {
+      const int rp = run_prep();
+      if (rp != MHAP_OK) return rp;
+      ql_made.reserve((size_t)qs.n_rows);
+      for (int64_t e = 0; e < qs.n_rows; e++) if (qs.h_valid[(size_t)e]) ql_made.push_back((int32_t)e);
+      ident = false;
+    }
+    ql = qs.identity && !ident ? &ql_made : &ql_in;
+    nql = ident ? qs.n_rows : (int64_t)ql->size();
+    return MHAP_OK;
   }
 
-  h->iq_start_mid = false;   // decided anew by the first chunks of every search
-  bool q_ph_done = false;    // the query side's position histograms exist (second stage, early "below the threshold")
-  PostStage post; post.h = h; post.qs = &qs; post.sink = sink; post.user = user;
-#define SCHK(expr) do { const hipError_t _e = (expr); if (_e != hipSuccess) return leave(fail(h, _e == hipErrorOutOfMemory ? MHAP_E_NOMEM : MHAP_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e))); } while (0)
-  // every error return below leaves through here: the worker is drained first (its buffers belong to the handle), the records it has
-  // already delivered are credited, and — if the search itself was fine — the worker's own error is the one reported
-  auto leave = [&](int code) { const int pr = post.drain(); h->stats.matches_found += post.matches; post.matches = 0;
-                               if (code == MHAP_OK && pr != MHAP_OK) return fail(h, pr, post.err); return code; };
-  int64_t chunk_no = 0;
-  const char* ppe = getenv("MHAP_SEARCH_PIPELINE");   // "0": the tail of every chunk inline (tests / A-B)
-  const bool pipeline = !(ppe && ppe[0] == '0');
-  int slot = 0;   // the record buffers (device + host) this chunk's kernels and tail use; flips with every tail handed over
-  for (int64_t c0 = 0, adv = 0; c0 < nql; c0 += adv, chunk_no++) {
-    const int nq = (int)std::min<int64_t>(qchunk, nql - c0);
-    adv = nq;
-    const int ntq = (nq + CAND_TQ - 1) / CAND_TQ;
-    const long long* d_rowstart = nullptr;
-    long long nblocks_tri = 0;
-    if (triangular_ok && !use_index) {
-      std::vector<long long> rs((size_t)ntq + 1);
-      long long acc = 0;
-      for (int t = 0; t < ntq; t++) {
-        rs[(size_t)t] = acc;
-        const int32_t maxq = ql[(size_t)(c0 + std::min<int64_t>((int64_t)(t + 1) * CAND_TQ, nq) - 1)];
-        acc += std::min<long long>(ntu, ((long long)maxq + CAND_TM - 1) / CAND_TM);
-      }
-      rs[(size_t)ntq] = acc; nblocks_tri = acc;
-      SCHK(h->rowstart.ensure(rs.size() * 8));
-      SCHK(hipMemcpyAsync(h->rowstart.p, rs.data(), rs.size() * 8, hipMemcpyHostToDevice, h->stream));
-      SCHK(hipStreamSynchronize(h->stream));  // rs is a stack vector
-      d_rowstart = h->rowstart.as<long long>();
-      if (nblocks_tri == 0) { h->stats.queries_searched += nq; continue; }   // (never the identity list: that needs the index)
+  // one launch of a query tier over `list`, and the counters it leaves (c5: words 0 .. SC_LAST_TIER)
+  int query_tier(int tier, const int32_t* list, int n, int32_t* out_list, unsigned long long* out_count, unsigned long long* c5) {
+    time_begin(h, MHAP_K_INDEX_QUERY);
+    launch_index_query(h->stream, h->inv, qs.d_minhash, qs.mh_stride, list, n, h->d_ids.as<int64_t>(), qs.d_ids, h->d_meta, qs.d_meta, sp,
+                       h->cand.as<Candidate>(), ctr + SC_CAND, (unsigned long long)cand_cap, ctr + SC_SPLITS, ctr + SC_ELEMENTS, out_list, out_count, tier,
+                       h->iq_espread.as<unsigned long long>());
+    time_end(h);
+    SCHK(hipGetLastError());
+    SCHK(hipMemcpyAsync(c5, ctr, counter_bytes(SC_LAST_TIER), hipMemcpyDeviceToHost, h->stream));
+    if (!prep_done) {   // (the rows' meta words, under the first tier's time)
+      const int rp = run_prep();
+      if (rp != MHAP_OK) { (void)sync_stream(h); return leave(rp); }
+      HPROF("query meta on the host");
     }
-    unsigned long long ncand = 0;
+    const int rc = sync_stream(h);
+    return rc != MHAP_OK ? leave(rc) : MHAP_OK;
+  }
+
+  int candidates_by_index(Chunk& c) {
+    const int nq = c.nq;
+    SCHK(h->inv_big.ensure((size_t)nq * 8));   // two lists: handed on by the first tier / by the middle tier
+    // (the spread words of the "elements processed" count: zeroed once, every launch folds them into the elements word and leaves them zero)
+    if (!h->iq_espread.p) { SCHK(h->iq_espread.ensure((size_t)index_elements_spread_words() * 8)); SCHK(hipMemsetAsync(h->iq_espread.p, 0, (size_t)index_elements_spread_words() * 8, h->stream)); }
+    const bool tiers = index_query_tiers() && !sw.first_tier_only;   // MHAP_INDEX_TIERS=1: first tier only (large hit sets are split right away; tests)
+    // (an index or a numMinMatches the first tier's packed hit-count words cannot hold: every query takes the dense tier; so does MHAP_INDEX_DENSE=1, tests)
+    const bool first_ok = index_query_tier_ok(0, h->n_entries, sp.num_min_matches) && !sw.index_dense;
+    int32_t* listA = h->inv_big.as<int32_t>();
+    int32_t* listB = listA + nq;
+    // MHAP_INDEX_MID=1 / 0: with / without the middle tier whatever the index size (tests)
+    const bool use_mid = tiers && first_ok && (sw.index_mid >= 0 ? sw.index_mid == 1 : index_query_dense_ranges(h->n_entries) > 4) &&
+                         index_query_tier_ok(1, h->n_entries, sp.num_min_matches);
+    // Tiers (search_kernels.hip).  Queries whose hits outgrow the first tier's table: a small index (a few dense ranges) counts them
+    // with dense counters at once; a large one in the middle tier's 8192-entry table first — ordinary reads of a big data set have
+    // thousands of hits, and the dense tier would make a pass per 32 768 stored entries for each of them — and dense counters for
+    // what outgrows that too (repeats).  When more than half of a chunk's queries left the first tier for the middle one (all of
+    // C4), the next chunks START there: the first tier's look at the bucket lengths was their only use of it.
+    const int t0 = !first_ok ? 2 : (use_mid && h->iq_start_mid ? 1 : 0);
+    unsigned long long c5[SC_LAST_TIER + 1] = {};
+    int rc = query_tier(t0, h->qlist.as<int32_t>() + c.c0, nq, tiers && t0 < 2 ? listA : nullptr, ctr + SC_BIG_A, c5);
+    if (rc != MHAP_OK) return rc;
+    HPROF("first query tier done");
+    const int32_t* dense_list = listA;
+    unsigned long long n_dense = c5[SC_BIG_A];
+    if (t0 == 0 && use_mid && c5[SC_CAND] <= cand_cap) {
+      // (a chunk of a few thousand queries at least: one repeat-rich read of a small -q batch must not send every later
+      //  query of this search through the 256-lane tier, which costs ordinary queries about twice the first tier's time)
+      if (nq >= 4096 && 2 * c5[SC_BIG_A] > (unsigned long long)nq) h->iq_start_mid = true;
+      if (c5[SC_BIG_A] > 0) {
+        if ((rc = query_tier(1, listA, (int)c5[SC_BIG_A], listB, ctr + SC_BIG_B, c5)) != MHAP_OK) return rc;
+        dense_list = listB; n_dense = c5[SC_BIG_B];
+      }
+    }
+    if (n_dense > 0 && c5[SC_CAND] <= cand_cap && (rc = query_tier(2, dense_list, (int)n_dense, nullptr, nullptr, c5)) != MHAP_OK) return rc;
+    HPROF("candidates known");
+    c.ncand = c5[SC_CAND];
+    if (c.ncand <= cand_cap) { h->stats.table_elements += (int64_t)c5[SC_ELEMENTS]; h->stats.index_splits += (int64_t)c5[SC_SPLITS]; }
+    return MHAP_OK;
+  }
+
+  // brute force, a self search whose ids rise with the entries: the tiles above the diagonal are skipped (row starts of the tiles that remain)
+  int triangular_row_starts(Chunk& c) {
+    const int ntu = ((int)h->n_entries + CAND_TM - 1) / CAND_TM;
+    std::vector<long long> rs((size_t)c.ntq + 1);
+    long long acc = 0;
+    for (int t = 0; t < c.ntq; t++) {
+      rs[(size_t)t] = acc;
+      const int32_t maxq = (*ql)[(size_t)(c.c0 + std::min<int64_t>((int64_t)(t + 1) * CAND_TQ, c.nq) - 1)];
+      acc += std::min<long long>(ntu, ((long long)maxq + CAND_TM - 1) / CAND_TM);
+    }
+    rs[(size_t)c.ntq] = acc; c.nblocks_tri = acc;
+    SCHK(h->rowstart.ensure(rs.size() * 8));
+    SCHK(hipMemcpyAsync(h->rowstart.p, rs.data(), rs.size() * 8, hipMemcpyHostToDevice, h->stream));
+    SCHK(hipStreamSynchronize(h->stream));  // rs is a stack vector
+    c.d_rowstart = h->rowstart.as<long long>();
+    if (c.nblocks_tri == 0) { h->stats.queries_searched += c.nq; return CHUNK_DONE; }   // (never the identity list: that needs the index)
+    return MHAP_OK;
+  }
+  int candidates_bruteforce(Chunk& c) {
+    const int ne = (int)h->n_entries, ntu = (ne + CAND_TM - 1) / CAND_TM;
+    time_begin(h, MHAP_K_CANDIDATE);
+    launch_candidates(h->stream, h->d_minhash, h->Hrow, qs.d_minhash, qs.mh_stride, h->qlist.as<int32_t>() + c.c0, c.nq, ne,
+                      h->d_ids.as<int64_t>(), qs.d_ids, h->d_meta, qs.d_meta, sp, c.d_rowstart, c.nblocks_tri, h->cand.as<Candidate>(),
+                      ctr + SC_CAND, (unsigned long long)cand_cap);
+    time_end(h);
+    SCHK(hipGetLastError());
+    SCHK(hipMemcpyAsync(&c.ncand, ctr + SC_CAND, counter_bytes(SC_CAND), hipMemcpyDeviceToHost, h->stream));
+    const int rc = sync_stream(h);
+    if (rc != MHAP_OK) return leave(rc);
+    if (c.ncand <= cand_cap) {
+      const long long tiles = c.d_rowstart ? c.nblocks_tri : (long long)c.ntq * ntu;
+      h->stats.slot_compares += tiles * (long long)CAND_TQ * CAND_TM * sp.H;
+    }
+    return MHAP_OK;
+  }
+  // the chunk's candidates; overflow of the candidate buffer: grow and redo this chunk
+  int find_candidates(Chunk& c) {
+    if (triangular_ok && !use_index) { const int rc = triangular_row_starts(c); if (rc != MHAP_OK) return rc; }
     for (;;) {
       SCHK(h->cand.ensure(cand_cap * sizeof(Candidate)));
-      SCHK(hipMemsetAsync(ctr, 0, 160, h->stream));
-      if (use_index) {
-        SCHK(h->inv_big.ensure((size_t)nq * 8));   // two lists: handed on by the first tier / by the middle tier
-        // (the spread words of the "elements processed" count: zeroed once, every launch folds them into ctr[4] and leaves them zero)
-        if (!h->iq_espread.p) { SCHK(h->iq_espread.ensure((size_t)index_elements_spread_words() * 8)); SCHK(hipMemsetAsync(h->iq_espread.p, 0, (size_t)index_elements_spread_words() * 8, h->stream)); }
-        unsigned long long* espread = h->iq_espread.as<unsigned long long>();
-        const char* tv = getenv("MHAP_INDEX_TIERS");   // "1": first tier only (large hit sets are split right away; tests)
-        const bool tiers = index_query_tiers() && !(tv && tv[0] == '1');
-        // (an index or a numMinMatches the first tier's packed hit-count words cannot hold: every query takes the dense tier)
-        const char* dv = getenv("MHAP_INDEX_DENSE");    // "1": every query takes the dense tier (tests)
-        const bool first_ok = index_query_tier_ok(0, h->n_entries, sp.num_min_matches) && !(dv && dv[0] == '1');
-        int32_t* listA = h->inv_big.as<int32_t>();
-        int32_t* listB = listA + nq;
-        const char* midv = getenv("MHAP_INDEX_MID");   // "1" / "0": with / without the middle tier whatever the index size (tests)
-        const bool use_mid = tiers && first_ok && (midv ? midv[0] == '1' : index_query_dense_ranges(h->n_entries) > 4) &&
-                             index_query_tier_ok(1, h->n_entries, sp.num_min_matches);
-        // Tiers (search_kernels.hip).  Queries whose hits outgrow the first tier's table: a small index (a few dense ranges) counts them
-        // with dense counters at once; a large one in the middle tier's 8192-entry table first — ordinary reads of a big data set have
-        // thousands of hits, and the dense tier would make a pass per 32 768 stored entries for each of them — and dense counters for
-        // what outgrows that too (repeats).  When more than half of a chunk's queries left the first tier for the middle one (all of
-        // C4), the next chunks START there: the first tier's look at the bucket lengths was their only use of it.
-        const int t0 = !first_ok ? 2 : (use_mid && h->iq_start_mid ? 1 : 0);
-        time_begin(h, MHAP_K_INDEX_QUERY);
-        launch_index_query(h->stream, h->inv, qs.d_minhash, qs.mh_stride, h->qlist.as<int32_t>() + c0, nq,
-                           h->d_ids.as<int64_t>(), qs.d_ids, h->d_meta, qs.d_meta, sp, h->cand.as<Candidate>(), ctr + 0,
-                           (unsigned long long)cand_cap, ctr + 3, ctr + 4, tiers && t0 < 2 ? listA : nullptr, ctr + 6, t0, espread);
-        time_end(h);
-        SCHK(hipGetLastError());
-        unsigned long long c5[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        SCHK(hipMemcpyAsync(c5, ctr, 72, hipMemcpyDeviceToHost, h->stream));
-        if (!prep_done) {   // (the rows' meta words, under the first tier's time)
-          const int rp = run_prep();
-          if (rp != MHAP_OK) { (void)sync_stream(h); return leave(rp); }
-          HPROF("query meta on the host");
-        }
-        int rc = sync_stream(h);
-        if (rc != MHAP_OK) return leave(rc);
-        HPROF("first query tier done");
-        const int32_t* dense_list = listA;
-        unsigned long long n_dense = c5[6];
-        if (t0 == 0 && use_mid && c5[0] <= cand_cap) {
-          // (a chunk of a few thousand queries at least: one repeat-rich read of a small -q batch must not send every later
-          //  query of this search through the 256-lane tier, which costs ordinary queries about twice the first tier's time)
-          if (nq >= 4096 && 2 * c5[6] > (unsigned long long)nq) h->iq_start_mid = true;
-          if (c5[6] > 0) {
-            time_begin(h, MHAP_K_INDEX_QUERY);
-            launch_index_query(h->stream, h->inv, qs.d_minhash, qs.mh_stride, listA, (int)c5[6], h->d_ids.as<int64_t>(), qs.d_ids, h->d_meta, qs.d_meta, sp,
-                               h->cand.as<Candidate>(), ctr + 0, (unsigned long long)cand_cap, ctr + 3, ctr + 4, listB, ctr + 8, 1, espread);
-            time_end(h);
-            SCHK(hipGetLastError());
-            SCHK(hipMemcpyAsync(c5, ctr, 72, hipMemcpyDeviceToHost, h->stream));
-            rc = sync_stream(h);
-            if (rc != MHAP_OK) return leave(rc);
-            dense_list = listB; n_dense = c5[8];
-          }
-        }
-        if (n_dense > 0 && c5[0] <= cand_cap) {
-          time_begin(h, MHAP_K_INDEX_QUERY);
-          launch_index_query(h->stream, h->inv, qs.d_minhash, qs.mh_stride, dense_list, (int)n_dense,
-                             h->d_ids.as<int64_t>(), qs.d_ids, h->d_meta, qs.d_meta, sp, h->cand.as<Candidate>(), ctr + 0,
-                             (unsigned long long)cand_cap, ctr + 3, ctr + 4, nullptr, nullptr, 2, espread);
-          time_end(h);
-          SCHK(hipGetLastError());
-          SCHK(hipMemcpyAsync(c5, ctr, 72, hipMemcpyDeviceToHost, h->stream));
-          rc = sync_stream(h);
-          if (rc != MHAP_OK) return leave(rc);
-        }
-        HPROF("candidates known");
-        ncand = c5[0];
-        if (ncand <= cand_cap) { h->stats.table_elements += (int64_t)c5[4]; h->stats.index_splits += (int64_t)c5[3]; }
-      } else {
-        time_begin(h, MHAP_K_CANDIDATE);
-        launch_candidates(h->stream, h->d_minhash, h->Hrow, qs.d_minhash, qs.mh_stride, h->qlist.as<int32_t>() + c0, nq, ne,
-                          h->d_ids.as<int64_t>(), qs.d_ids, h->d_meta, qs.d_meta, sp, d_rowstart, nblocks_tri, h->cand.as<Candidate>(),
-                          ctr + 0, (unsigned long long)cand_cap);
-        time_end(h);
-        SCHK(hipGetLastError());
-        SCHK(hipMemcpyAsync(&ncand, ctr + 0, 8, hipMemcpyDeviceToHost, h->stream));
-        int rc = sync_stream(h);
-        if (rc != MHAP_OK) return leave(rc);
-        if (ncand <= cand_cap) {
-          const long long tiles = d_rowstart ? nblocks_tri : (long long)ntq * ntu;
-          h->stats.slot_compares += tiles * (long long)CAND_TQ * CAND_TM * sp.H;
-        }
-      }
-      if (ncand <= cand_cap) break;
-      cand_cap = (size_t)ncand + (size_t)(ncand / 4) + 1024;   // overflow: grow and redo this chunk
+      SCHK(hipMemsetAsync(ctr, 0, counter_bytes(SC_LAST_JOIN), h->stream));
+      const int rc = use_index ? candidates_by_index(c) : candidates_bruteforce(c);
+      if (rc != MHAP_OK) return rc;
+      if (c.ncand <= cand_cap) return MHAP_OK;
+      cand_cap = (size_t)c.ncand + (size_t)(c.ncand / 4) + 1024;
     }
-    h->stats.queries_searched += ident ? count_valid(c0, nq) : (int64_t)nq;
-    if (ncand == 0) continue;
-    // a candidate-rich search (repeats): smaller chunks from here on — smaller candidate / record buffers, and the tail of a chunk
-    // (read-back, conversion, sink: PostStage) hides behind the next chunk's kernels, so less of it is left over at the end
-    if (chunk_no == 0 && (int64_t)ncand >= 64LL * nq && !getenv("MHAP_QUERY_CHUNK")) qchunk = 65536;
+  }
+
+  // a join pass's launch.  Candidates per pull of a wave: 8 amortise the counter and keep a query's hashes staged across its candidates —
+  // unless the pairs are few (a small batch of -q reads, one rank's share of a small job): then every resident wave should get some
+  // (fills the handle's cache of resident workgroups per CU on the first call for a level and shape, and empties it when S changes)
+  struct JoinGrid { int chunk, blocks; };
+  JoinGrid join_grid(int level, int shp, unsigned long long npairs) {
+    if (h->oj_per_cu_S != sp.S) { memset(h->oj_per_cu, 0, sizeof h->oj_per_cu); h->oj_per_cu_S = sp.S; }
+    int& per_cu = h->oj_per_cu[level][shp];
+    if (per_cu == 0) per_cu = overlap_join_blocks_per_cu(sp.S, shp, level);
+    const int wpb = overlap_join_waves_per_block(shp);
+    const int64_t resident_waves = (int64_t)h->num_cus * per_cu * wpb;
+    JoinGrid g;
+    g.chunk = (int)std::max<int64_t>(1, std::min<int64_t>(8, (int64_t)npairs / std::max<int64_t>(resident_waves, 1)));
+    const int64_t want = ((int64_t)npairs + (int64_t)wpb * g.chunk - 1) / ((int64_t)wpb * g.chunk);
+    g.blocks = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)h->num_cus * per_cu, want));
+    return g;
+  }
+  // Early "below the threshold" from position histograms (join_kernels.hip, poshist_kernel): pays when the joined k-mers of a pair
+  // are few next to its windows — repeat-induced candidates, i.e. many candidates per query (sixteen and more); at C2 (40
+  // joined k-mers per pair) it rejects nothing and the histograms would cost a pass over the ordered table.  MHAP_OVERLAP_PRUNE=0|1.
+  int prune_histograms(const uint16_t*& ph, const uint16_t*& qph) {
+    time_begin(h, MHAP_K_OVERLAP);
+    if (!(h->ph_ready && h->ph_ne == h->n_entries)) {
+      SCHK(h->poshist.ensure((size_t)h->n_entries * POSHIST_BINS * 2));
+      launch_poshist(h->stream, h->d_ordered, 2LL * sp.S, h->d_meta, h->n_entries, h->poshist.as<uint16_t>());
+      h->ph_ready = true; h->ph_ne = h->n_entries;
+    }
+    ph = h->poshist.as<uint16_t>();
+    if (qs.d_ordered == h->d_ordered && qs.d_meta == h->d_meta) qph = ph;
+    else {
+      if (!q_ph_done) {      // (after the gate: the query rows of a sharded search have all arrived)
+        SCHK(h->q_poshist.ensure((size_t)qs.n_rows * POSHIST_BINS * 2));
+        launch_poshist(h->stream, qs.d_ordered, qs.ord_stride, qs.d_meta, qs.n_rows, h->q_poshist.as<uint16_t>());
+        q_ph_done = true;
+      }
+      qph = h->q_poshist.as<uint16_t>();
+    }
+    time_end(h);
+    SCHK(hipGetLastError());
+    return MHAP_OK;
+  }
+  // the literal per-lane merge over nslow pairs of `list` (what the join kernel hands over, or every candidate)
+  int per_lane_merge(const Candidate* list, unsigned long long* count, unsigned long long cap, unsigned long long nslow, unsigned long long ncand, DevRecord* recs) {
+    // second stage: one lane per candidate; it is latency-bound, so put as many lanes in flight as the candidates allow
+    // (per-lane scratch = 3 int arrays of 2S+2 entries: 37 KB at S=1536; 16 workgroups/CU = 19 GB of the 288 GB HBM)
+    const int64_t ovl_max_blocks = sw.overlap_blocks > 0 ? sw.overlap_blocks : (int64_t)h->num_cus * 16;
+    const int64_t per_lane = 3LL * (2LL * sp.S + 2);
+    // (few pairs — what the join kernel hands over — are spread over more wavefronts while there is at most one per SIMD: 600 pairs of a
+    //  c5rank chunk, one per wave, 9 -> 3.5 ms; the 76 000 of the C5 slice at sixteen per wave instead of 64: 3 ms SLOWER — four times
+    //  the instructions on a machine that is then full: join_kernels.hip, overlap_kernel)
+    int spread = 1;
+    while (spread < 64 && (int64_t)nslow * spread * 2 <= (int64_t)h->num_cus * 4 * 64) spread *= 2;
+    const int oblocks = (int)std::max<int64_t>(1, std::min<int64_t>(ovl_max_blocks, ((int64_t)nslow * spread + OVL_THREADS - 1) / OVL_THREADS));
+    SCHK(h->ovl_scratch.ensure((size_t)oblocks * OVL_THREADS / (size_t)spread * (size_t)per_lane * 4));
+    time_begin(h, MHAP_K_OVERLAP);
+    launch_overlap(h->stream, oblocks, list, count, cap, h->d_ordered, 2LL * sp.S, h->d_meta, qs.d_ordered, qs.ord_stride, qs.d_meta, sp, h->score_tbl.as<double>(),
+                   h->ovl_scratch.as<int32_t>(), per_lane, recs, ctr + SC_REC, ncand, ctr + SC_COMPARED, spread);
+    time_end(h);
+    SCHK(hipGetLastError());
+    return MHAP_OK;
+  }
+
+  // second stage: one wavefront per candidate from the equal-hash join (MHAP_OVERLAP=lane: the literal per-lane merge for
+  // every pair); pairs the join cannot decide exactly come back in slow_cand and take the per-lane merge.  nrec: the chunk's records.
+  int second_stage(const Chunk& c, unsigned long long& nrec) {
+    const int S = sp.S, nq = c.nq;
+    const unsigned long long ncand = c.ncand;
     DevBuf& recbuf = slot ? h->recs2 : h->recs;
     SCHK(recbuf.ensure((size_t)ncand * sizeof(DevRecord)));
-    // second stage: one wavefront per candidate from the equal-hash join (MHAP_OVERLAP=lane: the literal per-lane merge for
-    // every pair); pairs the join cannot decide exactly come back in slow_cand and take the per-lane merge
     if (h->gate && h->gate(h->gate_user) != 0) return leave(fail(h, MHAP_E_STATE, "second-stage gate aborted the search"));
     // the join kernel's three shapes (join_kernels.hip): every wave alone, pairs of waves or teams of four sharing a staged query and
     // its filter — by the candidates per query.  MHAP_JOIN_MODE=alone|pair|team pins one.
     bool fits[3];
     for (int i = 0; i < 3; i++) fits[i] = overlap_join_lds_bytes(S, i, 0) <= 64 * 1024;
-    const bool use_join = !lane_only && S <= OJ_MAX_S && (fits[0] || fits[1] || fits[2]);
+    const bool use_join = !sw.lane_only && S <= OJ_MAX_S && (fits[0] || fits[1] || fits[2]);
     unsigned long long nslow = use_join ? 0 : ncand;
-    const Candidate* slow_list = nullptr; unsigned long long* slow_count_ptr = nullptr;   // (set when the wide second pass ran)
-    unsigned long long cj[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const Candidate* slow_list = nullptr; unsigned long long* slow_count_ptr = nullptr;   // (set when a wide pass ran: its output)
+    unsigned long long cj[SC_LAST_JOIN + 1] = {};
     bool have_counts = false;
     if (use_join) {
       SCHK(h->slow_cand.ensure((size_t)ncand * sizeof(Candidate)));
@@ -1011,65 +965,27 @@ int search_core(mhap_handle* h, QuerySide& qs, const std::vector<int32_t>& ql_in
       //  team 77; a rank of eight, 0.56 per query: alone 0.86, pair 1.24.  Round 4, the shared shapes with the filter — C2: pair 3.74, team 3.65;
       //  C5 slice: pair 66.8, team 49.8; ranks of two / four / eight: alone 2.29 / 1.19 / 0.69, pair 2.09 / 1.29 / 0.83, team 2.29 / 1.69 / 1.33)
       int shape = (int64_t)ncand >= 4LL * nq ? 2 : ((int64_t)ncand >= 2LL * nq ? 1 : 0);
-      if (h->join_mode > 0) shape = h->join_mode - 1;
+      if (sw.join_mode > 0) shape = sw.join_mode - 1;
       while (!fits[shape]) shape = (shape + 1) % 3;
       // One pass of the join kernel per level: level 0 reads the candidates, every further one what the pass before handed over.
       // {pairs in, pairs handed over, and where among the counters: pairs in, pairs handed over (the kernel counts those handed over for
       // the duplicated-hash group caps OJ_GROUP_BAD words behind that), the work counter}
       struct JoinLevel { DevBuf *in, *out; int in_count, out_count, work; };
-      const JoinLevel levels[OJ_LEVELS] = {{&h->cand, &h->slow_cand, 0, 5, 7}, {&h->slow_cand, &h->slow_cand2, 5, 10, 9}, {&h->slow_cand2, &h->slow_cand3, 10, 11, 12}};
-      // a pass's launch.  Candidates per pull of a wave: 8 amortise the counter and keep a query's hashes staged across its candidates —
-      // unless the pairs are few (a small batch of -q reads, one rank's share of a small job): then every resident wave should get some
-      // (fills the handle's cache of resident workgroups per CU on the first call for a level and shape, and empties it when S changes)
-      struct JoinGrid { int chunk, blocks; };
-      auto join_grid = [&](int level, int shp, unsigned long long npairs) {
-        if (h->oj_per_cu_S != S) { memset(h->oj_per_cu, 0, sizeof h->oj_per_cu); h->oj_per_cu_S = S; }
-        int& per_cu = h->oj_per_cu[level][shp];
-        if (per_cu == 0) per_cu = overlap_join_blocks_per_cu(S, shp, level);
-        const int wpb = overlap_join_waves_per_block(shp);
-        const int64_t resident_waves = (int64_t)h->num_cus * per_cu * wpb;
-        JoinGrid g;
-        g.chunk = (int)std::max<int64_t>(1, std::min<int64_t>(8, (int64_t)npairs / std::max<int64_t>(resident_waves, 1)));
-        const int64_t want = ((int64_t)npairs + (int64_t)wpb * g.chunk - 1) / ((int64_t)wpb * g.chunk);
-        g.blocks = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)h->num_cus * per_cu, want));
-        return g;
-      };
+      const JoinLevel levels[OJ_LEVELS] = {{&h->cand, &h->slow_cand, SC_CAND, SC_SLOW0, SC_WORK0}, {&h->slow_cand, &h->slow_cand2, SC_SLOW0, SC_SLOW1, SC_WORK1},
+                                           {&h->slow_cand2, &h->slow_cand3, SC_SLOW1, SC_SLOW2, SC_WORK2}};
       const JoinGrid jg = join_grid(0, shape, ncand);
-      // Early "below the threshold" from position histograms (join_kernels.hip, poshist_kernel): pays when the joined k-mers of a pair
-      // are few next to its windows — repeat-induced candidates, i.e. many candidates per query (sixteen and more); at C2 (40
-      // joined k-mers per pair) it rejects nothing and the histograms would cost a pass over the ordered table.  MHAP_OVERLAP_PRUNE=0|1.
-      const char* pe = getenv("MHAP_OVERLAP_PRUNE");
-      const bool prune = pe ? pe[0] == '1' : (int64_t)ncand >= 16LL * nq;
+      const bool prune = sw.overlap_prune >= 0 ? sw.overlap_prune == 1 : (int64_t)ncand >= 16LL * nq;
       const uint16_t *ph = nullptr, *qph = nullptr;
-      if (prune) {
-        time_begin(h, MHAP_K_OVERLAP);
-        if (!(h->ph_ready && h->ph_ne == h->n_entries)) {
-          SCHK(h->poshist.ensure((size_t)h->n_entries * POSHIST_BINS * 2));
-          launch_poshist(h->stream, h->d_ordered, 2LL * S, h->d_meta, h->n_entries, h->poshist.as<uint16_t>());
-          h->ph_ready = true; h->ph_ne = h->n_entries;
-        }
-        ph = h->poshist.as<uint16_t>();
-        if (qs.d_ordered == h->d_ordered && qs.d_meta == h->d_meta) qph = ph;
-        else {
-          if (!q_ph_done) {      // (after the gate: the query rows of a sharded search have all arrived)
-            SCHK(h->q_poshist.ensure((size_t)qs.n_rows * POSHIST_BINS * 2));
-            launch_poshist(h->stream, qs.d_ordered, qs.ord_stride, qs.d_meta, qs.n_rows, h->q_poshist.as<uint16_t>());
-            q_ph_done = true;
-          }
-          qph = h->q_poshist.as<uint16_t>();
-        }
-        time_end(h);
-        SCHK(hipGetLastError());
-      }
+      if (prune) { const int rp = prune_histograms(ph, qph); if (rp != MHAP_OK) return rp; }
       time_begin(h, MHAP_K_OVERLAP);
       launch_overlap_join(h->stream, 0, shape, jg.blocks, jg.chunk, h->cand.as<Candidate>(), ctr + levels[0].in_count, (unsigned long long)cand_cap, h->d_ordered, 2LL * S, h->d_meta,
-                          qs.d_ordered, qs.ord_stride, qs.d_meta, sp, h->score_tbl.as<double>(), recbuf.as<DevRecord>(), ctr + 1,
-                          (unsigned long long)ncand, ctr + 2, h->slow_cand.as<Candidate>(), ctr + levels[0].out_count, ctr + levels[0].work, ph, qph, h->pass_min_tbl.as<int32_t>());
+                          qs.d_ordered, qs.ord_stride, qs.d_meta, sp, h->score_tbl.as<double>(), recbuf.as<DevRecord>(), ctr + SC_REC,
+                          ncand, ctr + SC_COMPARED, h->slow_cand.as<Candidate>(), ctr + levels[0].out_count, ctr + levels[0].work, ph, qph, h->pass_min_tbl.as<int32_t>());
       time_end(h);
       SCHK(hipGetLastError());
       // (one read-back for the pairs handed over and for the counts the tail needs: nothing else changes them when none were)
-      SCHK(hipMemcpyAsync(cj, ctr, 160, hipMemcpyDeviceToHost, h->stream));
-      int rcj = sync_stream(h);
+      SCHK(hipMemcpyAsync(cj, ctr, sizeof cj, hipMemcpyDeviceToHost, h->stream));
+      const int rcj = sync_stream(h);
       if (rcj != MHAP_OK) return leave(rcj);
       nslow = cj[levels[0].out_count];
       have_counts = nslow == 0;
@@ -1078,7 +994,7 @@ int search_core(mhap_handle* h, QuerySide& qs, const std::vector<int32_t>& ql_in
       // over through the one with room for 1 536 (join_kernels.hip, oj_dispatch), every wave alone; only what is left then (the
       // duplicated-hash group caps) takes the per-lane merge.  MHAP_JOIN_WIDE=0 switches the passes off, =1 keeps the first of them only.
       unsigned long long group_bad = cj[levels[0].out_count + OJ_GROUP_BAD];   // of the pairs handed over: for the duplicated-hash group caps
-      for (int level = 1; level <= h->join_wide && nslow > 0; level++) {
+      for (int level = 1; level <= sw.join_wide && nslow > 0; level++) {
         // (pairs handed over for their duplicated-hash groups — repeat-rich reads of low error without a -f filter: hundreds of millions of
         //  them — would be handed on by a wider pass too: 1.4 s of 9.6 wasted on 20 000 such reads)
         if (group_bad * 10 > nslow * 9) break;
@@ -1087,16 +1003,16 @@ int search_core(mhap_handle* h, QuerySide& qs, const std::vector<int32_t>& ql_in
         SCHK(lv.out->ensure((size_t)nslow * sizeof(Candidate)));
         const JoinGrid wg = join_grid(level, 0, nslow);
         time_begin(h, MHAP_K_OVERLAP);
-        launch_overlap_join(h->stream, level, 0, wg.blocks, wg.chunk, lv.in->as<Candidate>(), ctr + lv.in_count, (unsigned long long)ncand, h->d_ordered, 2LL * S, h->d_meta,
-                            qs.d_ordered, qs.ord_stride, qs.d_meta, sp, h->score_tbl.as<double>(), recbuf.as<DevRecord>(), ctr + 1, (unsigned long long)ncand, ctr + 2,
+        launch_overlap_join(h->stream, level, 0, wg.blocks, wg.chunk, lv.in->as<Candidate>(), ctr + lv.in_count, ncand, h->d_ordered, 2LL * S, h->d_meta,
+                            qs.d_ordered, qs.ord_stride, qs.d_meta, sp, h->score_tbl.as<double>(), recbuf.as<DevRecord>(), ctr + SC_REC, ncand, ctr + SC_COMPARED,
                             lv.out->as<Candidate>(), ctr + lv.out_count, ctr + lv.work, nullptr, nullptr, h->pass_min_tbl.as<int32_t>());
         time_end(h);
         SCHK(hipGetLastError());
-        unsigned long long cw[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        SCHK(hipMemcpyAsync(cw, ctr, 160, hipMemcpyDeviceToHost, h->stream));
+        unsigned long long cw[SC_LAST_JOIN + 1] = {};
+        SCHK(hipMemcpyAsync(cw, ctr, sizeof cw, hipMemcpyDeviceToHost, h->stream));
         const int rcw = sync_stream(h);
         if (rcw != MHAP_OK) return leave(rcw);
-        for (int i = 0; i < 8; i++) cj[i] = cw[i];
+        for (int i = 0; i <= SC_COMPARED; i++) cj[i] = cw[i];   // (the counts the tail needs)
         const unsigned long long before = nslow;
         nslow = cw[lv.out_count];
         group_bad = cw[lv.out_count + OJ_GROUP_BAD];
@@ -1107,41 +1023,84 @@ int search_core(mhap_handle* h, QuerySide& qs, const std::vector<int32_t>& ql_in
       h->stats.slow_pairs += (int64_t)nslow;
     }
     if (nslow > 0) {
-      // (few pairs — what the join kernel hands over — are spread over more wavefronts while there is at most one per SIMD: 600 pairs of a
-      //  c5rank chunk, one per wave, 9 -> 3.5 ms; the 76 000 of the C5 slice at sixteen per wave instead of 64: 3 ms SLOWER — four times
-      //  the instructions on a machine that is then full: join_kernels.hip, overlap_kernel)
-      int spread = 1;
-      while (spread < 64 && (int64_t)nslow * spread * 2 <= (int64_t)h->num_cus * 4 * 64) spread *= 2;
-      const int oblocks = (int)std::max<int64_t>(1, std::min<int64_t>(ovl_max_blocks, ((int64_t)nslow * spread + OVL_THREADS - 1) / OVL_THREADS));
-      SCHK(h->ovl_scratch.ensure((size_t)oblocks * OVL_THREADS / (size_t)spread * (size_t)per_lane * 4));
-      time_begin(h, MHAP_K_OVERLAP);
-      launch_overlap(h->stream, oblocks, slow_list ? slow_list : (use_join ? h->slow_cand.as<Candidate>() : h->cand.as<Candidate>()), slow_list ? slow_count_ptr : (use_join ? ctr + 5 : ctr + 0),
-                     use_join ? (unsigned long long)ncand : (unsigned long long)cand_cap, h->d_ordered, 2LL * S, h->d_meta,
-                     qs.d_ordered, qs.ord_stride, qs.d_meta, sp, h->score_tbl.as<double>(), h->ovl_scratch.as<int32_t>(), per_lane,
-                     recbuf.as<DevRecord>(), ctr + 1, (unsigned long long)ncand, ctr + 2, spread);
-      time_end(h);
-      SCHK(hipGetLastError());
+      // (the lists' addresses are taken here: slow_cand may have been reallocated above)
+      if (!slow_list) { slow_list = use_join ? h->slow_cand.as<Candidate>() : h->cand.as<Candidate>(); slow_count_ptr = ctr + (use_join ? SC_SLOW0 : SC_CAND); }
+      const int rl = per_lane_merge(slow_list, slow_count_ptr, use_join ? ncand : (unsigned long long)cand_cap, nslow, ncand, recbuf.as<DevRecord>());
+      if (rl != MHAP_OK) return rl;
     }
-    unsigned long long counts[3] = {cj[0], cj[1], cj[2]};
+    unsigned long long counts[SC_COMPARED + 1] = {cj[SC_CAND], cj[SC_REC], cj[SC_COMPARED]};
     if (!have_counts) {
-      SCHK(hipMemcpyAsync(counts, ctr, 24, hipMemcpyDeviceToHost, h->stream));
-      int rc = sync_stream(h);
+      SCHK(hipMemcpyAsync(counts, ctr, sizeof counts, hipMemcpyDeviceToHost, h->stream));
+      const int rc = sync_stream(h);
       if (rc != MHAP_OK) return leave(rc);
     }
     HPROF("overlap done");
     oj_stats_dump();
-    const unsigned long long nrec = counts[1];
-    h->stats.candidates_compared += (int64_t)counts[2];
-    if (nrec == 0) continue;
-    // the chunk's tail: inline when it is the last chunk with no worker running (nothing left to hide it behind), else on the worker
-    const bool last = c0 + nq >= nql;
-    const int rp = post.submit(slot, nrec, !pipeline || last);
-    if (rp != MHAP_OK) return leave(fail(h, rp, post.err));
-    slot ^= 1;
-    HPROF("chunk tail handed over");
+    nrec = counts[SC_REC];
+    h->stats.candidates_compared += (int64_t)counts[SC_COMPARED];
+    return MHAP_OK;
   }
-  return leave(MHAP_OK);
+
+  // the chunks: candidates, second stage, and the hand-over of the chunk's tail to PostStage
+  int run() {
+    auto count_valid = [&](int64_t a, int64_t n) { int64_t v = 0; for (int64_t e = a; e < a + n; e++) v += qs.h_valid[(size_t)e] ? 1 : 0; return v; };
+    int64_t chunk_no = 0;
+    for (int64_t c0 = 0, adv = 0; c0 < nql; c0 += adv, chunk_no++) {
+      const int nq = (int)std::min<int64_t>(qchunk, nql - c0);
+      adv = nq;
+      Chunk c{c0, nq, (nq + CAND_TQ - 1) / CAND_TQ, nullptr, 0, 0};
+      int rc = find_candidates(c);
+      if (rc == CHUNK_DONE) continue;
+      if (rc != MHAP_OK) return rc;
+      h->stats.queries_searched += ident ? count_valid(c0, nq) : (int64_t)nq;
+      if (c.ncand == 0) continue;
+      // a candidate-rich search (repeats): smaller chunks from here on — smaller candidate / record buffers, and the tail of a chunk
+      // (read-back, conversion, sink: PostStage) hides behind the next chunk's kernels, so less of it is left over at the end
+      if (chunk_no == 0 && (int64_t)c.ncand >= 64LL * nq && !sw.query_chunk_set) qchunk = 65536;
+      unsigned long long nrec = 0;
+      if ((rc = second_stage(c, nrec)) != MHAP_OK) return rc;
+      if (nrec == 0) continue;
+      // the chunk's tail: inline when it is the last chunk with no worker running (nothing left to hide it behind), else on the worker
+      const bool last = c0 + nq >= nql;
+      const int rp = post.submit(slot, nrec, !sw.pipeline || last);   // MHAP_SEARCH_PIPELINE=0: the tail of every chunk inline (tests / A-B)
+      if (rp != MHAP_OK) return leave(fail(h, rp, post.err));
+      slot ^= 1;
+      HPROF("chunk tail handed over");
+    }
+    return leave(MHAP_OK);
+  }
 #undef SCHK
+};
+
+// Run candidate + second stage for the query entries in `ql` (entry indices into the query side).
+int search_core(mhap_handle* h, QuerySide& qs, const std::vector<int32_t>& ql_in, bool to_self, bool triangular_ok,
+                mhap_record_sink sink, void* user) {
+  Search s(h, qs);
+  s.sw.read_search();
+  s.use_index = !s.sw.bruteforce;   // candidate generation: GPU inverted index (default) or brute-force all-pairs (MHAP_CANDIDATES=bruteforce)
+  s.triangular_ok = triangular_ok; s.prep_done = !qs.prep;
+  const int rq = s.make_query_list(ql_in);
+  if (rq != MHAP_OK) return rq;
+  if (s.nql == 0 || h->n_entries == 0) { h->stats.queries_searched += s.nql; return MHAP_OK; }
+  SearchParams& sp = s.sp;
+  sp.H = h->P.num_hashes; sp.S = h->P.ordered_sketch_size; sp.k2 = h->P.ordered_kmer_size;
+  sp.num_min_matches = h->P.num_min_matches; sp.min_store_length = h->P.min_store_length; sp.to_self = to_self ? 1 : 0;
+  sp.own_queries = (to_self && qs.d_minhash == h->d_minhash && qs.d_meta == h->d_meta && !s.sw.count_own) ? 1 : 0;
+  sp.max_shift = h->P.max_shift; sp.threshold = h->P.threshold;
+  s.qchunk = s.sw.query_chunk;
+  HIPCHK(h, h->qlist.ensure((size_t)s.nql * 4));
+  if (s.ident) { launch_query_iota(h->stream, h->qlist.as<int32_t>(), 0, (int)s.nql); HIPCHK(h, hipGetLastError()); }
+  else HIPCHK(h, hipMemcpyAsync(h->qlist.p, s.ql->data(), s.ql->size() * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, h->counters.ensure(256));
+  s.ctr = h->counters.as<unsigned long long>();
+  s.cand_cap = std::max<size_t>(h->cand.cap / sizeof(Candidate), (size_t)4 << 20);
+  if (s.use_index) {
+    const int rcb = ensure_inverted_index(h);
+    if (rcb != MHAP_OK) return rcb;
+  }
+  h->iq_start_mid = false;   // decided anew by the first chunks of every search
+  s.post.h = h; s.post.qs = &qs; s.post.sink = sink; s.post.user = user;
+  return s.run();
 }
 
 }  // namespace
@@ -1633,7 +1592,8 @@ static int self_search(mhap_handle* h, int64_t q_first, int64_t q_count, int64_t
   if (h->mono_gen == h->index_gen) mono = h->mono_val;   // (looked at when the ids arrived)
   else for (int64_t e = 1; e < h->n_entries && mono; e++) if (h->ids[(size_t)e] < h->ids[(size_t)(e - 1)]) mono = false;
   // tile skipping needs: ids sorted with entry order, every entry "long" (minStore == 0 -> only m.id < q.id survives)
-  const bool tri = mono && h->P.min_store_length == 0 && !getenv("MHAP_NO_TRIANGULAR");
+  Switches sw; sw.read_self_search();
+  const bool tri = mono && h->P.min_store_length == 0 && !sw.no_triangular;
   QuerySide qs{h->d_minhash, h->Hrow, h->d_ordered, 2LL * h->P.ordered_sketch_size, h->d_meta, h->d_ids.as<int64_t>(), h->ids.data(), h->seqlen.data(), h->n_entries};
   HPROF("search_core begin");
   const int rcs = search_core(h, qs, ql, true, tri, sink, user);
@@ -1894,6 +1854,44 @@ int mhap_selftest_pass_min(int32_t S, int32_t k2, double threshold, double* scor
   build_pass_min(tbl, S, threshold, pm);
   if (scores) memcpy(scores, tbl.data(), tbl.size() * 8);
   memcpy(pass_min, pm.data(), pm.size() * 4);
+  return MHAP_OK;
+}
+
+// sketch_plan.hpp's rules on n reads of the given lengths and flags (MHAP_RD_SKIP / MHAP_RD_RAW), hashed from their codes unless fused == 0
+int mhap_selftest_sketch_plan(uint64_t free_bytes, int64_t group_bases_override, const int32_t* lengths, const int32_t* flags, int64_t n, int32_t k, int32_t k2,
+                              int32_t fused, int64_t* plan8, int64_t* group_of, int64_t* layout, int64_t* totals, int32_t* order) {
+  if (!plan8 || n < 0 || k < 1 || k2 < 1 || (n > 0 && (!lengths || !flags || !group_of || !layout || !totals || !order))) return MHAP_E_INVALID;
+  std::vector<ReadDesc> descs((size_t)n), out((size_t)n);
+  for (int64_t i = 0; i < n; i++) { descs[(size_t)i] = ReadDesc{}; descs[(size_t)i].length = lengths[i]; descs[(size_t)i].flags = flags[i]; }
+  const MatRule is_mat{fused != 0, k, k2};
+  const int64_t group_bases = launch_group_bases((size_t)free_bytes, group_bases_override);
+  const SketchPlan p = plan_launch_groups(descs.data(), n, group_bases, k, k2, is_mat);
+  const int64_t head[8] = {group_bases, (int64_t)p.groups.size(), p.max_key, p.max_h2, p.max_w, p.max_nb, p.max_len_all, slab_entries(p.max_len_all, k)};
+  memcpy(plan8, head, sizeof head);
+  std::vector<int32_t> ord;
+  for (size_t g = 0; g < p.groups.size(); g++) {
+    const LaunchGroup& B = p.groups[g];
+    const GroupLayout G = layout_group(descs.data() + B.r0, B.r1 - B.r0, k, k2, is_mat, out.data() + B.r0);
+    const int64_t t[6] = {G.key_elems, G.h2_elems, G.w_elems, B.max_len, G.min_len, G.read_bases};
+    memcpy(totals + 6 * g, t, sizeof t);
+    const bool ordered = length_order(out.data() + B.r0, B.r1 - B.r0, G.min_len, B.max_len, ord);
+    for (int64_t i = B.r0; i < B.r1; i++) {
+      const ReadDesc& d = out[(size_t)i];
+      const int64_t row[6] = {d.w_off, d.key_off, d.h2_off, d.key_stride, d.h2_stride, d.flags};
+      memcpy(layout + 6 * i, row, sizeof row);
+      group_of[i] = (int64_t)g;
+      order[i] = ordered ? ord[(size_t)(i - B.r0)] : -1;
+    }
+  }
+  return MHAP_OK;
+}
+
+// ordered_schedule under the MHAP_ORDERED_* / MHAP_W1_PREFILL switches of the environment: out5 = {pre, nowait, idle gap, prefill, all rows first}
+int mhap_selftest_ordered_schedule(int64_t group_read_bases, int64_t n_w1, int64_t n_weighted, int64_t nstr, int32_t eager_x, int64_t* out5) {
+  if (!out5 || nstr < 0) return MHAP_E_INVALID;
+  Switches sw; sw.read_sketch_group();
+  const OrderedSchedule os = ordered_schedule(sw, group_read_bases, n_w1, n_weighted, nstr, eager_x != 0);
+  out5[0] = os.pre; out5[1] = os.nowait; out5[2] = os.idle_gap; out5[3] = os.prefill; out5[4] = os.pre > 0 && os.pre >= nstr;
   return MHAP_OK;
 }
 

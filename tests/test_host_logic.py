@@ -552,3 +552,142 @@ def test_build_lists_name_real_files_and_no_unit_includes_another():
     for name in B.SOURCES:
         text = open(os.path.join(B.CSRC, name), encoding="utf-8").read()
         assert not re.search(r'^[ \t]*#[ \t]*include[ \t]*["<][^">]*\.hip[">]', text, re.M), name
+
+
+# ---- the sketch driver's host rules (sketch_plan.hpp): expected values restated here from the rules, not taken from the library ----
+_RD_RAW, _RD_SKIP, _RD_MAT = 1, 2, 8
+_GIB = 1 << 30
+
+
+def _a4(v):
+    return (v + 3) & ~3
+
+
+def _sketch_plan(lengths, flags, k=16, k2=12, fused=1, free=0, override=0):
+    lib = mhap_amd.load_library()
+    n = len(lengths)
+    L, F = np.asarray(lengths, dtype=np.int32), np.asarray(flags, dtype=np.int32)
+    plan8, group_of, order = np.zeros(8, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
+    layout, totals = np.zeros((n, 6), dtype=np.int64), np.zeros((n, 6), dtype=np.int64)
+    assert lib.mhap_selftest_sketch_plan(C.c_uint64(free), C.c_int64(override), api._ptr(L), api._ptr(F), C.c_int64(n), C.c_int32(k), C.c_int32(k2),
+                                         C.c_int32(fused), api._ptr(plan8), api._ptr(group_of), api._ptr(layout), api._ptr(totals), api._ptr(order)) == 0
+    return plan8.tolist(), group_of.tolist(), layout.tolist(), totals[:int(plan8[1])].tolist(), order.tolist()
+
+
+def _expected_sketch_plan(lengths, flags, group_bases, k, k2, fused):
+    n, groups, r0 = len(lengths), [], 0
+    while r0 < n:   # a group is closed before the read that would pass group_bases, but always takes its first read
+        r1, tot = r0 + 1, lengths[r0]
+        while r1 < n and tot + lengths[r1] <= group_bases and r1 - r0 < (1 << 22):
+            tot += lengths[r1]
+            r1 += 1
+        groups.append((r0, r1))
+        r0 = r1
+    group_of, layout, totals, order = [0] * n, [None] * n, [], [-1] * n
+    for g, (a, b) in enumerate(groups):
+        w = key = h2 = 0
+        kept = [lengths[i] for i in range(a, b) if not flags[i] & _RD_SKIP]
+        lo, hi = (min(kept), max(kept)) if kept else (2**31 - 1, 0)
+        for i in range(a, b):
+            ln, nk, nk2 = lengths[i], _a4(max(0, lengths[i] - k + 1)), _a4(max(0, lengths[i] - k2 + 1))
+            group_of[i] = g
+            mat = bool(flags[i] & _RD_RAW) or not fused or not (k == 16 and k2 == 12 and ln - k + 1 <= 24 * 1024)
+            if flags[i] & _RD_SKIP:
+                layout[i] = [w, 0, 0, nk, nk2, flags[i]]
+            elif mat:
+                layout[i] = [w, key, h2, nk, nk2, flags[i] | _RD_MAT]
+                w, key, h2 = w + 2 * nk, key + 2 * nk, h2 + 2 * nk2
+            else:
+                layout[i] = [w, 0, 0, nk, nk2, flags[i]]
+                w += 2 * nk
+        totals.append([key, h2, w, hi, lo, sum(lengths[a:b])])
+        if b - a > 1 and 5 * lo < 4 * hi:   # longest first by length // 128, stable (a read beyond the longest kept one shares its bucket)
+            perm = sorted(range(b - a), key=lambda j: max(0, hi // 128 + 1 - lengths[a + j] // 128))
+            order[a:b] = perm
+    slab = 64
+    while 3 * slab < 4 * max(1, max([t[3] for t in totals], default=0) - k + 1):
+        slab *= 2
+    head = [group_bases, len(groups), max([4] + [t[0] for t in totals]), max([4] + [t[1] for t in totals]), max([4] + [t[2] for t in totals]),
+            max([1] + [b - a for a, b in groups]), max([0] + [t[3] for t in totals]), slab]
+    return head, group_of, layout, totals, order
+
+
+def test_launch_group_size_rule():
+    """max(2^30, min(4 * 2^30, free / 4 / 16)) bases per launch group; MHAP_BATCH_BASES (the override) wins."""
+    for free, want in ((0, _GIB), (64 * _GIB, _GIB), (288 * _GIB, 4 * _GIB), (256 * _GIB, 4 * _GIB), (256 * _GIB - 64, 4 * _GIB - 1), (128 * _GIB, 2 * _GIB)):
+        assert _sketch_plan([], [], free=free)[0][0] == want, free
+        assert _sketch_plan([], [], free=free, override=200000)[0][0] == 200000
+    assert _sketch_plan([], [], free=5)[0][:2] == [_GIB, 0]
+
+
+def test_launch_groups_and_descriptor_layout():
+    lengths = [100, 15, 16, 3000, 100]
+    head, group_of, layout, totals, order = _sketch_plan(lengths, [0] * 5, override=3000)
+    assert group_of == [0, 0, 0, 1, 2] and head[:2] == [3000, 3]        # 3000 does not fit behind 131 bases; the last 100 not behind 3000
+    assert layout[1][0] == layout[2][0] == 2 * _a4(85) and layout[1][3] == 0   # shorter than k: no window, still a descriptor
+    assert _sketch_plan(lengths, [0] * 5, override=2999)[1] == [0, 0, 0, 1, 2]   # a first read beyond the whole budget is taken anyway
+    assert _sketch_plan(lengths, [0] * 5, override=3100)[1] == [0, 0, 0, 1, 1]
+    rnd = random.Random(11)
+    cases = [(lengths, [0] * 5, 3000, 16, 12, 1), (lengths, [0, _RD_SKIP, 0, _RD_RAW, 0], 3000, 16, 12, 1), (lengths, [0] * 5, 10**9, 16, 12, 0),
+             ([400, 5000, 90, 130, 9000, 128, 127, 20000], [0, 0, _RD_SKIP, 0, 0, 0, 0, 0], 10**9, 16, 12, 1), ([30000, 200], [0, 0], 10**9, 16, 12, 1)]
+    for _ in range(40):
+        n = rnd.randrange(1, 60)
+        ls = [rnd.choice((0, 7, 15, 16, 17, 116, 127, 128, 129, 1000, 4000, 24591, 24592)) + rnd.randrange(3) for _ in range(n)]
+        fl = [(_RD_SKIP if x < 116 else 0) | (_RD_RAW if rnd.random() < 0.3 else 0) for x in ls]
+        cases.append((ls, fl, rnd.choice((1, 500, 5000, 40000, 10**9)), rnd.choice((16, 14)), rnd.choice((12, 13)), rnd.randrange(2)))
+    for ls, fl, gb, k, k2, fused in cases:
+        got = _sketch_plan(ls, fl, k=k, k2=k2, fused=fused, override=gb)
+        want = _expected_sketch_plan(ls, fl, gb, k, k2, fused)
+        assert got == tuple(want), (ls, fl, gb, k, k2, fused)
+        head, group_of, layout, totals, order = got
+        for i, row in enumerate(layout):
+            assert row[0] % 4 == 0 and row[1] % 4 == 0 and row[2] % 4 == 0
+            if not fl[i] & _RD_SKIP and i + 1 < len(ls) and group_of[i + 1] == group_of[i]:   # both strands adjacent: the next read starts 2 strides on
+                assert layout[i + 1][0] == row[0] + 2 * row[3]
+        assert head[2:5] == [max([4] + [t[j] for t in totals]) for j in range(3)]           # the plan's maxima = the largest group totals
+        for g in set(group_of):
+            idx = [i for i in range(len(ls)) if group_of[i] == g]
+            perm = [order[i] for i in idx]
+            kept = [ls[i] for i in idx if not fl[i] & _RD_SKIP]
+            if len(idx) == 1 or not kept or 5 * min(kept) >= 4 * max(kept):
+                assert perm == [-1] * len(idx)
+            else:
+                assert sorted(perm) == list(range(len(idx)))
+                b = [ls[idx[j]] // 128 for j in perm]
+                assert all(x >= y for x, y in zip(b, b[1:]))
+                assert all(p < q for p, q, x, y in zip(perm, perm[1:], b, b[1:]) if x == y)   # stable within a bucket
+
+
+def test_ordered_schedule_rule_and_switches(monkeypatch):
+    """The ordered kernel's first part: 55 % of the strands for a launch group of 900 000 000 read bases or more with at least four weight-1
+    strands per weighted one, else none; the MHAP_ORDERED_* switches as sketch_staged reads them at every launch group."""
+    lib = mhap_amd.load_library()
+    names = ("MHAP_ORDERED_SPLIT", "MHAP_ORDERED_FIRST", "MHAP_ORDERED_NOWAIT", "MHAP_W1_PREFILL")
+
+    def sched(env, bases=0, n_w1=800, n_weighted=200, nstr=1000, eager=0):
+        for nm in names:
+            monkeypatch.delenv(nm, raising=False)
+        for nm, v in env.items():
+            monkeypatch.setenv(nm, v)
+        out = np.zeros(5, dtype=np.int64)
+        assert lib.mhap_selftest_ordered_schedule(C.c_int64(bases), C.c_int64(n_w1), C.c_int64(n_weighted), C.c_int64(nstr), C.c_int32(eager), api._ptr(out)) == 0
+        return dict(zip(("pre", "nowait", "gap", "prefill", "done"), out.tolist()))
+
+    assert sched({}, bases=900000000) == {"pre": 550, "nowait": 1, "gap": 0, "prefill": 0, "done": 0}
+    assert sched({}, bases=899999999)["pre"] == 0
+    assert sched({}, bases=900000000, n_w1=799)["pre"] == 0
+    assert sched({"MHAP_ORDERED_SPLIT": "0"}, bases=900000000)["pre"] == 0
+    assert sched({"MHAP_ORDERED_SPLIT": "33"})["pre"] == 330 and sched({"MHAP_ORDERED_SPLIT": "33"}, bases=10**10)["pre"] == 330
+    assert sched({"MHAP_ORDERED_SPLIT": "33"}, nstr=1002)["pre"] == 330      # 330.66: down to a whole, even number of strands
+    assert sched({"MHAP_ORDERED_SPLIT": "33"}, nstr=1010)["pre"] == 332      # 333.3 -> 333 -> 332
+    assert sched({"MHAP_ORDERED_SPLIT": "250"}) == {"pre": 1000, "nowait": 1, "gap": 0, "prefill": 0, "done": 1}
+    assert sched({"MHAP_ORDERED_SPLIT": "100"})["done"] == 1 and sched({"MHAP_ORDERED_SPLIT": "99"})["done"] == 0
+    assert sched({"MHAP_ORDERED_FIRST": "1"}) == {"pre": 1000, "nowait": 1, "gap": 0, "prefill": 0, "done": 1}
+    assert sched({"MHAP_ORDERED_FIRST": "2", "MHAP_ORDERED_SPLIT": "10"}) == {"pre": 1000, "nowait": 1, "gap": 1, "prefill": 0, "done": 1}
+    assert sched({"MHAP_ORDERED_NOWAIT": "0", "MHAP_ORDERED_SPLIT": "33"})["nowait"] == 0
+    assert sched({"MHAP_ORDERED_NOWAIT": "0"}, bases=900000000)["nowait"] == 0
+    assert sched({"MHAP_ORDERED_NOWAIT": "0"}) == {"pre": 0, "nowait": 1, "gap": 0, "prefill": 0, "done": 0}   # nothing to wait for
+    assert sched({"MHAP_W1_PREFILL": "3"})["prefill"] == 3
+    for env in ({}, {"MHAP_ORDERED_SPLIT": "50"}, {"MHAP_ORDERED_FIRST": "1"}, {"MHAP_ORDERED_NOWAIT": "0", "MHAP_ORDERED_SPLIT": "100"}):
+        got = sched(env, bases=900000000, eager=1)
+        assert got["pre"] == 0 and got["done"] == 0 and got["nowait"] == 1, env
