@@ -51,48 +51,200 @@ RECORD_DTYPE = np.dtype([("from_id", "<i8"), ("to_id", "<i8"), ("score", "<f8"),
 _SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p)
 _GATE = C.CFUNCTYPE(C.c_int, C.c_void_p)
 
-# every symbol include/mhap_hip.h declares
-EXPORTED_SYMBOLS = [
-    "mhap_create", "mhap_destroy", "mhap_last_error", "mhap_default_params", "mhap_set_filter", "mhap_index_add_reads",
-    "mhap_sketch_batch", "mhap_index_add_sketches", "mhap_index_size", "mhap_index_export", "mhap_index_clear", "mhap_index_prepare",
-    "mhap_sketch_reads_device", "mhap_index_set_device", "mhap_find_matches_self", "mhap_find_matches_reads",
-    "mhap_get_stats", "mhap_get_kernel_times", "mhap_reset_kernel_times", "mhap_set_stream", "mhap_synchronize",
-    "mhap_format_record", "mhap_fasta_read", "mhap_fasta_free", "mhap_synth_reads", "mhap_hash_kmer",
-    "mhap_selftest_hash_windows", "mhap_selftest_overlap_lane", "mhap_stage_reads", "mhap_index_add_staged",
-    "mhap_sketch_staged_device", "mhap_find_matches_self_shard", "mhap_synth_reads_shard", "mhap_selftest_transpose32", "mhap_selftest_pass_min", "mhap_selftest_sketch_plan", "mhap_selftest_ordered_schedule", "mhap_selftest_xorshift_jump", "mhap_selftest_xorshift_unjump", "mhap_find_matches_sketches",
-    "mhap_synth_reads_repeats", "mhap_synth_reads_genome", "mhap_find_matches_device", "mhap_set_filter_whitelist", "mhap_set_filter_file", "mhap_selftest_bloom", "mhap_set_second_stage_gate",
-    "mhap_dist_unique_id", "mhap_dist_init", "mhap_dist_finalize", "mhap_dist_find_matches_self", "mhap_dist_find_matches_reads", "mhap_dist_last_timing", "mhap_dist_exchange_timing", "mhap_dist_info", "mhap_dist_selftest", "mhap_dist_set_eager", "mhap_dist_eager_searches",
-    "mhap_group_create", "mhap_group_destroy", "mhap_group_size", "mhap_group_rank", "mhap_group_last_error", "mhap_group_add_reads", "mhap_group_clear",
-    "mhap_group_find_matches_self", "mhap_group_find_matches_reads", "mhap_group_get_stats", "mhap_abi_version", "mhap_abi_sizes",
-    "mhap_index_reserve", "mhap_fasta_scan_open", "mhap_fasta_scan_free", "mhap_fasta_scan_reads", "mhap_fasta_scan_bases", "mhap_fasta_scan_info",
-    "mhap_index_add_scan", "mhap_find_matches_scan", "mhap_group_add_scan",
-    "mhap_kmer_count_begin", "mhap_kmer_count_add_reads", "mhap_kmer_count_add_scan", "mhap_kmer_count_finish", "mhap_kmer_counts_info",
-    "mhap_kmer_counts_lines", "mhap_kmer_counts_write", "mhap_kmer_counts_free", "mhap_selftest_kmer_windows",
-    "mhap_kmer_count_finish_flags", "mhap_kmer_counts_histogram_size", "mhap_kmer_counts_histogram", "mhap_kmer_counts_write_histogram",
-    "mhap_histogram_stats",
-    "mhap_synth_truth", "mhap_align_pairs",
-    "mhap_align_pairs_banded", "mhap_realign_plan", "mhap_realign_plan_error", "mhap_realign_records",
-    "mhap_align_pairs_banded_paths", "mhap_realign_records_paths", "mhap_align_paths_info", "mhap_align_paths_copy", "mhap_align_paths_free",
-    "mhap_format_paf", "mhap_align_paths_from_runs",
-    "mhap_correct_begin", "mhap_correct_add", "mhap_correct_finish", "mhap_correct_copy", "mhap_correct_votes", "mhap_correct_free",
-    "mhap_graph_default_params", "mhap_graph_begin", "mhap_graph_add", "mhap_graph_finish", "mhap_graph_info", "mhap_graph_copy_arcs",
-    "mhap_graph_copy_classes", "mhap_graph_copy_read_flags", "mhap_graph_free", "mhap_format_gfa_link",
-    "mhap_graph_unitigs", "mhap_graph_unitigs_info", "mhap_graph_copy_unitigs", "mhap_graph_copy_layout", "mhap_graph_copy_links",
-    "mhap_graph_spell", "mhap_graph_spell_device", "mhap_format_gfa_unitig_link",
-    "mhap_graph_default_clean_params", "mhap_graph_clean", "mhap_graph_copy_dropped", "mhap_graph_copy_removed",
-    "mhap_graph_unitigs_counts",
-    "mhap_consensus_default_params", "mhap_consensus_begin", "mhap_consensus_add", "mhap_consensus_run", "mhap_consensus_info",
-    "mhap_consensus_copy", "mhap_consensus_copy_placements", "mhap_consensus_copy_map", "mhap_consensus_votes", "mhap_consensus_times",
-    "mhap_consensus_free",
-    "mhap_trim_default_params", "mhap_trim_begin", "mhap_trim_add", "mhap_trim_finish", "mhap_trim_copy", "mhap_trim_coverage",
-    "mhap_trim_apply", "mhap_trim_clip_record", "mhap_trim_free", "mhap_trim_refine", "mhap_trim_refine_record",
-    "mhap_repeat_default_params", "mhap_repeat_begin", "mhap_repeat_add", "mhap_repeat_finish", "mhap_repeat_copy", "mhap_repeat_histogram",
-    "mhap_repeat_apply", "mhap_repeat_judge_record", "mhap_repeat_free",
-    "mhap_select_default_params", "mhap_select_begin", "mhap_select_add", "mhap_select_finish", "mhap_select_copy", "mhap_select_apply",
-    "mhap_select_judge_record", "mhap_select_free", "mhap_correct_add_views",
-    "mhap_pair_kmer_stats", "mhap_pair_kmer_stats_paths", "mhap_ksim_create", "mhap_ksim_next", "mhap_ksim_error", "mhap_ksim_destroy",
-    "mhap_ksim_dev_create", "mhap_ksim_dev_destroy", "mhap_ksim_dev_pair_stats", "mhap_ksim_dev_trials",
-]
+# Every symbol include/mhap_hip.h declares, with its prototype as the header has it: "result:parameters", one letter per type.
+# Result: v void, i int, q int64_t, s const char*, p another pointer.  Parameters: p a pointer of any kind (a callback too),
+# i int or int32_t, I uint32_t, q int64_t, Q uint64_t, z size_t, d double.  load_library declares all of them, so that a bare Python int
+# goes down as the 64-bit value the callee reads, and a library without one of the symbols is refused there.
+_CTYPES = {"v": None, "i": C.c_int32, "I": C.c_uint32, "q": C.c_int64, "Q": C.c_uint64, "z": C.c_size_t, "d": C.c_double, "p": C.c_void_p,
+           "s": C.c_char_p}
+_PROTOTYPES = {
+    "mhap_create": "i:pppz",
+    "mhap_destroy": "v:p",
+    "mhap_last_error": "s:p",
+    "mhap_default_params": "v:p",
+    "mhap_set_filter": "i:pppqdddi",
+    "mhap_index_add_reads": "i:pppppq",
+    "mhap_sketch_batch": "i:ppppqpppp",
+    "mhap_index_add_sketches": "i:ppppppppq",
+    "mhap_index_size": "i:pp",
+    "mhap_index_export": "i:pqqpppppppp",
+    "mhap_index_clear": "i:p",
+    "mhap_index_prepare": "i:p",
+    "mhap_sketch_reads_device": "i:ppppqppp",
+    "mhap_index_set_device": "i:ppppppq",
+    "mhap_find_matches_self": "i:pqqpp",
+    "mhap_find_matches_reads": "i:pppppqpp",
+    "mhap_get_stats": "i:pp",
+    "mhap_get_kernel_times": "i:pp",
+    "mhap_reset_kernel_times": "i:p",
+    "mhap_set_stream": "i:pp",
+    "mhap_synchronize": "i:p",
+    "mhap_format_record": "i:ppz",
+    "mhap_fasta_read": "i:pqppz",
+    "mhap_fasta_free": "v:p",
+    "mhap_synth_reads": "i:Qqiddp",
+    "mhap_hash_kmer": "i:piip",
+    "mhap_selftest_hash_windows": "i:piiipp",
+    "mhap_selftest_overlap_lane": "i:piipiidip",
+    "mhap_stage_reads": "i:pppppq",
+    "mhap_index_add_staged": "i:p",
+    "mhap_sketch_staged_device": "i:pppp",
+    "mhap_find_matches_self_shard": "i:pqqpp",
+    "mhap_synth_reads_shard": "i:Qqiddqqp",
+    "mhap_selftest_transpose32": "i:p",
+    "mhap_selftest_pass_min": "i:iidpp",
+    "mhap_selftest_sketch_plan": "i:Qqppqiiippppp",
+    "mhap_selftest_ordered_schedule": "i:qqqqip",
+    "mhap_selftest_xorshift_jump": "i:Qip",
+    "mhap_selftest_xorshift_unjump": "i:Qip",
+    "mhap_find_matches_sketches": "i:pppppppqpp",
+    "mhap_synth_reads_repeats": "i:Qqiddqqiidp",
+    "mhap_synth_reads_genome": "i:Qpqqppdp",
+    "mhap_find_matches_device": "i:pppppqipp",
+    "mhap_set_filter_whitelist": "i:ppqqi",
+    "mhap_set_filter_file": "i:ppddiidipz",
+    "mhap_selftest_bloom": "i:pqqpqpp",
+    "mhap_set_second_stage_gate": "i:ppp",
+    "mhap_dist_unique_id": "i:pz",
+    "mhap_dist_init": "i:piip",
+    "mhap_dist_finalize": "i:p",
+    "mhap_dist_find_matches_self": "i:ppp",
+    "mhap_dist_find_matches_reads": "i:pppppqpp",
+    "mhap_dist_last_timing": "i:pp",
+    "mhap_dist_exchange_timing": "i:pp",
+    "mhap_dist_info": "i:pppz",
+    "mhap_dist_selftest": "i:pzp",
+    "mhap_dist_set_eager": "i:pi",
+    "mhap_dist_eager_searches": "q:p",
+    "mhap_group_create": "i:ppippz",
+    "mhap_group_destroy": "v:p",
+    "mhap_group_size": "i:p",
+    "mhap_group_rank": "p:pi",
+    "mhap_group_last_error": "s:p",
+    "mhap_group_add_reads": "i:pppppq",
+    "mhap_group_clear": "i:p",
+    "mhap_group_find_matches_self": "i:ppp",
+    "mhap_group_find_matches_reads": "i:pppppqpp",
+    "mhap_group_get_stats": "i:pp",
+    "mhap_abi_version": "i:",
+    "mhap_abi_sizes": "i:p",
+    "mhap_index_reserve": "i:pq",
+    "mhap_fasta_scan_open": "i:pqppz",
+    "mhap_fasta_scan_free": "v:p",
+    "mhap_fasta_scan_reads": "q:p",
+    "mhap_fasta_scan_bases": "q:p",
+    "mhap_fasta_scan_info": "i:ppppp",
+    "mhap_index_add_scan": "i:pp",
+    "mhap_find_matches_scan": "i:pppp",
+    "mhap_group_add_scan": "i:pp",
+    "mhap_kmer_count_begin": "i:pii",
+    "mhap_kmer_count_add_reads": "i:ppppq",
+    "mhap_kmer_count_add_scan": "i:pp",
+    "mhap_kmer_count_finish": "i:pdp",
+    "mhap_kmer_counts_info": "i:ppppp",
+    "mhap_kmer_counts_lines": "i:ppp",
+    "mhap_kmer_counts_write": "i:pp",
+    "mhap_kmer_counts_free": "v:p",
+    "mhap_selftest_kmer_windows": "i:piiipp",
+    "mhap_kmer_count_finish_flags": "i:pdIp",
+    "mhap_kmer_counts_histogram_size": "i:pp",
+    "mhap_kmer_counts_histogram": "i:ppp",
+    "mhap_kmer_counts_write_histogram": "i:pp",
+    "mhap_histogram_stats": "i:ppqdppp",
+    "mhap_synth_truth": "i:Qqidqpdqqpppppp",
+    "mhap_align_pairs": "i:ppqpqp",
+    "mhap_align_pairs_banded": "i:ppqpqp",
+    "mhap_realign_plan": "i:pqpppqdip",
+    "mhap_realign_plan_error": "s:",
+    "mhap_realign_records": "i:ppqpppqpqipp",
+    "mhap_align_pairs_banded_paths": "i:ppqpqpp",
+    "mhap_realign_records_paths": "i:ppqpppqpqippp",
+    "mhap_align_paths_info": "i:ppp",
+    "mhap_align_paths_copy": "i:ppp",
+    "mhap_align_paths_free": "v:p",
+    "mhap_format_paf": "i:pppqpppz",
+    "mhap_align_paths_from_runs": "i:pqpp",
+    "mhap_correct_begin": "i:ppqpppqp",
+    "mhap_correct_add": "i:ppqp",
+    "mhap_correct_finish": "i:pippp",
+    "mhap_correct_copy": "i:pp",
+    "mhap_correct_votes": "i:pqp",
+    "mhap_correct_free": "v:p",
+    "mhap_graph_default_params": "v:p",
+    "mhap_graph_begin": "i:pppqpp",
+    "mhap_graph_add": "i:ppq",
+    "mhap_graph_finish": "i:pp",
+    "mhap_graph_info": "i:pppp",
+    "mhap_graph_copy_arcs": "i:pp",
+    "mhap_graph_copy_classes": "i:pp",
+    "mhap_graph_copy_read_flags": "i:pp",
+    "mhap_graph_free": "v:p",
+    "mhap_format_gfa_link": "i:pppz",
+    "mhap_graph_unitigs": "i:pp",
+    "mhap_graph_unitigs_info": "i:ppppp",
+    "mhap_graph_copy_unitigs": "i:pppp",
+    "mhap_graph_copy_layout": "i:pppp",
+    "mhap_graph_copy_links": "i:pp",
+    "mhap_graph_spell": "i:ppqpp",
+    "mhap_graph_spell_device": "i:ppqpp",
+    "mhap_format_gfa_unitig_link": "i:ppz",
+    "mhap_graph_default_clean_params": "v:p",
+    "mhap_graph_clean": "i:ppp",
+    "mhap_graph_copy_dropped": "i:pp",
+    "mhap_graph_copy_removed": "i:pp",
+    "mhap_graph_unitigs_counts": "i:pp",
+    "mhap_consensus_default_params": "v:p",
+    "mhap_consensus_begin": "i:ppqppp",
+    "mhap_consensus_add": "i:ppq",
+    "mhap_consensus_run": "i:pp",
+    "mhap_consensus_info": "i:ppppp",
+    "mhap_consensus_copy": "i:pppp",
+    "mhap_consensus_copy_placements": "i:pp",
+    "mhap_consensus_copy_map": "i:pp",
+    "mhap_consensus_votes": "i:pqp",
+    "mhap_consensus_times": "i:pp",
+    "mhap_consensus_free": "v:p",
+    "mhap_trim_default_params": "v:p",
+    "mhap_trim_begin": "i:pppqpp",
+    "mhap_trim_add": "i:ppq",
+    "mhap_trim_finish": "i:pp",
+    "mhap_trim_copy": "i:ppp",
+    "mhap_trim_coverage": "i:pqp",
+    "mhap_trim_apply": "i:ppqpp",
+    "mhap_trim_clip_record": "i:ppppp",
+    "mhap_trim_free": "v:p",
+    "mhap_trim_refine": "i:ppqpip",
+    "mhap_trim_refine_record": "i:ppqip",
+    "mhap_repeat_default_params": "v:p",
+    "mhap_repeat_begin": "i:pppqpp",
+    "mhap_repeat_add": "i:ppq",
+    "mhap_repeat_finish": "i:pp",
+    "mhap_repeat_copy": "i:ppppp",
+    "mhap_repeat_histogram": "i:pp",
+    "mhap_repeat_apply": "i:ppqpp",
+    "mhap_repeat_judge_record": "i:ppqpqpp",
+    "mhap_repeat_free": "v:p",
+    "mhap_select_default_params": "v:p",
+    "mhap_select_begin": "i:pppqpp",
+    "mhap_select_add": "i:ppq",
+    "mhap_select_finish": "i:pp",
+    "mhap_select_copy": "i:pp",
+    "mhap_select_apply": "i:ppqp",
+    "mhap_select_judge_record": "i:ppp",
+    "mhap_select_free": "v:p",
+    "mhap_correct_add_views": "i:ppqpp",
+    "mhap_pair_kmer_stats": "i:ppqpqiipqpp",
+    "mhap_pair_kmer_stats_paths": "i:pqiqip",
+    "mhap_ksim_create": "p:qiiddddipppq",
+    "mhap_ksim_next": "q:pqpp",
+    "mhap_ksim_error": "s:pp",
+    "mhap_ksim_destroy": "v:p",
+    "mhap_ksim_dev_create": "p:p",
+    "mhap_ksim_dev_destroy": "v:p",
+    "mhap_ksim_dev_pair_stats": "i:ppqpqiipqpp",
+    "mhap_ksim_dev_trials": "i:pQqqiiddddipppqiipqppppp",
+}
+EXPORTED_SYMBOLS = list(_PROTOTYPES)
 MHAP_KMER_HISTOGRAM = 1   # mhap_kmer_count_finish_flags
 ABI_VERSION = 4   # MHAP_ABI_VERSION of include/mhap_hip.h this binding was written against
 
@@ -117,120 +269,10 @@ def load_library(build_if_missing=True):
         lib = C.CDLL(_LIB_PATH)
     except OSError as e:
         raise MhapError(f"cannot load the HIP extension {_LIB_PATH}: {e}") from e
-    lib.mhap_last_error.restype = C.c_char_p
-    lib.mhap_last_error.argtypes = [C.c_void_p]
-    lib.mhap_destroy.restype = None
-    lib.mhap_destroy.argtypes = [C.c_void_p]
-    lib.mhap_fasta_free.restype = None
-    lib.mhap_default_params.restype = None
-    lib.mhap_group_destroy.restype = None
-    lib.mhap_group_destroy.argtypes = [C.c_void_p]
-    lib.mhap_group_rank.restype = C.c_void_p
-    lib.mhap_group_rank.argtypes = [C.c_void_p, C.c_int32]
-    lib.mhap_group_last_error.restype = C.c_char_p
-    lib.mhap_group_last_error.argtypes = [C.c_void_p]
-    lib.mhap_group_size.argtypes = [C.c_void_p]
-    lib.mhap_fasta_scan_free.restype = None
-    lib.mhap_fasta_scan_free.argtypes = [C.c_void_p]
-    lib.mhap_fasta_scan_reads.restype = C.c_int64
-    lib.mhap_fasta_scan_reads.argtypes = [C.c_void_p]
-    lib.mhap_fasta_scan_bases.restype = C.c_int64
-    lib.mhap_fasta_scan_bases.argtypes = [C.c_void_p]
-    lib.mhap_kmer_counts_free.restype = None
-    lib.mhap_kmer_counts_free.argtypes = [C.c_void_p]
-    for name, nargs in (("mhap_kmer_counts_info", 4), ("mhap_kmer_counts_lines", 2), ("mhap_kmer_counts_write", 1),
-                        ("mhap_kmer_counts_histogram_size", 1), ("mhap_kmer_counts_histogram", 2), ("mhap_kmer_counts_write_histogram", 1)):
-        getattr(lib, name).argtypes = [C.c_void_p] + [C.c_void_p] * nargs
-    lib.mhap_histogram_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mhap_ksim_create.restype = C.c_void_p
-    lib.mhap_ksim_create.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32,
-                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
-    lib.mhap_ksim_next.restype = C.c_int64
-    lib.mhap_ksim_next.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-    lib.mhap_ksim_error.restype = C.c_char_p
-    lib.mhap_ksim_error.argtypes = [C.c_void_p, C.c_void_p]
-    lib.mhap_ksim_destroy.restype = None
-    lib.mhap_ksim_destroy.argtypes = [C.c_void_p]
-    lib.mhap_ksim_dev_create.restype = C.c_void_p
-    lib.mhap_ksim_dev_create.argtypes = [C.c_void_p]
-    lib.mhap_ksim_dev_destroy.restype = None
-    lib.mhap_ksim_dev_destroy.argtypes = [C.c_void_p]
-    lib.mhap_ksim_dev_pair_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
-                                             C.c_int64, C.c_void_p, C.c_void_p]
-    lib.mhap_ksim_dev_trials.argtypes = [C.c_void_p, C.c_uint64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double,
-                                         C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
-                                         C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mhap_realign_plan_error.restype = C.c_char_p
-    lib.mhap_realign_plan_error.argtypes = []
-    lib.mhap_realign_plan.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int32, C.c_void_p]
-    lib.mhap_realign_records.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                         C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.mhap_align_pairs_banded_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-    lib.mhap_realign_records_paths.argtypes = lib.mhap_realign_records.argtypes + [C.c_void_p]
-    lib.mhap_align_paths_info.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mhap_align_paths_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mhap_align_paths_free.restype = None
-    lib.mhap_align_paths_free.argtypes = [C.c_void_p]
-    lib.mhap_format_paf.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t]
-    lib.mhap_align_paths_from_runs.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-    lib.mhap_correct_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-    lib.mhap_correct_add.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-    lib.mhap_correct_add_views.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-    lib.mhap_select_default_params.restype = None
-    lib.mhap_select_default_params.argtypes = [C.c_void_p]
-    lib.mhap_select_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-    lib.mhap_select_add.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
-    lib.mhap_select_finish.argtypes = [C.c_void_p, C.c_void_p]
-    lib.mhap_select_copy.argtypes = [C.c_void_p, C.c_void_p]
-    lib.mhap_select_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-    lib.mhap_select_judge_record.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mhap_select_free.restype = None
-    lib.mhap_select_free.argtypes = [C.c_void_p]
-    lib.mhap_correct_finish.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mhap_correct_copy.argtypes = [C.c_void_p, C.c_void_p]
-    lib.mhap_correct_votes.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
-    lib.mhap_correct_free.restype = None
-    lib.mhap_correct_free.argtypes = [C.c_void_p]
-    lib.mhap_graph_default_params.restype = None
-    lib.mhap_graph_default_params.argtypes = [C.c_void_p]
-    lib.mhap_graph_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-    lib.mhap_graph_add.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
-    lib.mhap_graph_finish.argtypes = [C.c_void_p, C.c_void_p]
-    lib.mhap_graph_info.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    for name in ("mhap_graph_copy_arcs", "mhap_graph_copy_classes", "mhap_graph_copy_read_flags"):
-        getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p]
-    lib.mhap_graph_free.restype = None
-    lib.mhap_graph_free.argtypes = [C.c_void_p]
-    lib.mhap_format_gfa_link.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
-    lib.mhap_graph_unitigs.argtypes = [C.c_void_p, C.c_void_p]
-    lib.mhap_graph_unitigs_info.argtypes = [C.c_void_p] + [C.c_void_p] * 4
-    lib.mhap_graph_copy_unitigs.argtypes = [C.c_void_p] + [C.c_void_p] * 3
-    lib.mhap_graph_copy_layout.argtypes = [C.c_void_p] + [C.c_void_p] * 3
-    lib.mhap_graph_copy_links.argtypes = [C.c_void_p, C.c_void_p]
-    for name in ("mhap_graph_spell", "mhap_graph_spell_device"):
-        getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-    lib.mhap_format_gfa_unitig_link.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    lib.mhap_graph_default_clean_params.restype = None
-    lib.mhap_graph_default_clean_params.argtypes = [C.c_void_p]
-    lib.mhap_graph_clean.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mhap_graph_copy_dropped.argtypes = [C.c_void_p, C.c_void_p]
-    lib.mhap_graph_copy_removed.argtypes = [C.c_void_p, C.c_void_p]
-    lib.mhap_graph_unitigs_counts.argtypes = [C.c_void_p, C.c_void_p]
-    lib.mhap_consensus_default_params.restype = None
-    lib.mhap_consensus_default_params.argtypes = [C.c_void_p]
-    lib.mhap_consensus_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mhap_consensus_add.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
-    lib.mhap_consensus_run.argtypes = [C.c_void_p, C.c_void_p]
-    lib.mhap_consensus_info.argtypes = [C.c_void_p] + [C.c_void_p] * 4
-    lib.mhap_consensus_copy.argtypes = [C.c_void_p] + [C.c_void_p] * 3
-    lib.mhap_consensus_copy_placements.argtypes = [C.c_void_p, C.c_void_p]
-    lib.mhap_consensus_copy_map.argtypes = [C.c_void_p, C.c_void_p]
-    lib.mhap_consensus_votes.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
-    lib.mhap_consensus_times.argtypes = [C.c_void_p, C.c_void_p]
-    lib.mhap_consensus_free.restype = None
-    lib.mhap_consensus_free.argtypes = [C.c_void_p]
-    for name in EXPORTED_SYMBOLS:
-        getattr(lib, name)  # AttributeError here = header/library mismatch
+    for name, proto in _PROTOTYPES.items():
+        fn = getattr(lib, name)  # AttributeError here = header/library mismatch
+        result, params = proto.split(":")
+        fn.restype, fn.argtypes = _CTYPES[result], [_CTYPES[c] for c in params]
     # a stale library next to newer host code (or the reverse) must not get as far as a struct copy
     sizes = (C.c_int32 * 4)()
     lib.mhap_abi_sizes(sizes)
@@ -244,6 +286,11 @@ def load_library(build_if_missing=True):
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def _opt(a):
+    """The pointer of an array that may be empty: an empty one goes down as NULL."""
+    return _ptr(a) if len(a) else None
 
 
 class MhapParams:
@@ -577,7 +624,7 @@ def format_paf(record, detail, ops, qname=None, tname=None):
     tname = str(int(arr[0]["to_id"]) if tname is None else tname).encode()
     cap = 256 + len(qname) + len(tname) + 12 * len(ops)
     buf = C.create_string_buffer(cap)
-    n = lib.mhap_format_paf(_ptr(arr), _ptr(detail), _ptr(ops) if len(ops) else None, C.c_int64(len(ops)), qname, tname, buf, C.c_size_t(cap))
+    n = lib.mhap_format_paf(_ptr(arr), _ptr(detail), _opt(ops), C.c_int64(len(ops)), qname, tname, buf, C.c_size_t(cap))
     if n < 0 or n >= cap:
         raise MhapError("mhap_format_paf failed")
     return buf.value.decode()
@@ -587,7 +634,78 @@ CORRECT_STATS = ("len_in", "len_out", "n_sub", "n_del", "n_ins", "n_low")   # th
 CORRECT_COUNTERS = 24   # per position: base A C G T, del, span, ins[k][A C G T] for k = 0 .. 3, two spare
 
 
-class CorrectSession:
+class _Session:
+    """What every session class shares: the MinHashSearch whose device and stream it uses, the caller's (handle=...) or one made here
+    and closed with the session; the C session in `_s`; close(), `with` and the close of a session that is dropped.  A subclass names
+    the prefix of its C entry points in `_prefix`: close() calls `<prefix>_free`."""
+
+    _prefix = None
+
+    def __init__(self, handle, device, begin):
+        """begin(): the C begin, which fills `_s`.  Whatever it raises closes a handle made here."""
+        self._own = handle is None
+        self._ms = MinHashSearch(MhapParams(num_hashes=1, ordered_sketch_size=1, device=device)) if self._own else handle
+        self._lib = self._ms._lib
+        self._s = C.c_void_p()
+        try:
+            begin()
+        except Exception:
+            if self._own:
+                self._ms.close()
+            raise
+
+    def _c(self, name):
+        return getattr(self._lib, f"{self._prefix}_{name}")
+
+    def close(self):
+        if self._s:
+            self._c("free")(self._s)
+            self._s = C.c_void_p()
+            if self._own:
+                self._ms.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _ReadsSession(_Session):
+    """A session over a table of reads: (read_ids, lengths) and a struct of parameters go to `<prefix>_begin`, records to
+    `<prefix>_add`, and `<prefix>_finish` fills the counts that `_counts` names."""
+
+    _counts = ()
+
+    def __init__(self, read_ids, lengths, params, handle, device):
+        self.ids = np.ascontiguousarray(read_ids, np.int64)
+        self.lengths = np.ascontiguousarray(lengths, np.int32)
+        super().__init__(handle, device, lambda: self._begin(params))
+
+    def _begin(self, params):
+        if len(self.ids) != len(self.lengths):
+            raise MhapError(f"{type(self).__name__}: {len(self.ids)} ids and {len(self.lengths)} lengths")
+        self._ms._chk(self._c("begin")(self._ms._h, _opt(self.ids), _opt(self.lengths), len(self.ids), C.byref(params), C.byref(self._s)))
+
+    def add(self, records):
+        """Take realigned records: piled up, classed or entered, as the session does (nothing waits for the device)."""
+        records = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
+        self._ms._chk(self._c("add")(self._s, _opt(records), len(records)))
+
+    def _finish(self):
+        """`<prefix>_finish`: the dict of `_counts`."""
+        counts = np.zeros(len(self._counts), np.int64)
+        self._ms._chk(self._c("finish")(self._s, _ptr(counts)))
+        return dict(zip(self._counts, counts.tolist()))
+
+
+class CorrectSession(_Session):
     """Read correction on the GPU (mhap_correct_begin / _add / _finish / _votes; the contract is the "read correction" section of
     include/mhap_hip.h): every realigned overlap votes column by column on both of its reads, and each position takes the majority.
     The vote table (48 bytes per base) stays on the device from begin to close.
@@ -598,22 +716,16 @@ class CorrectSession:
 
     handle: a MinHashSearch whose device and stream to use (else one is made and closed with the session)."""
 
+    _prefix = "mhap_correct"
+
     def __init__(self, fasta, query_fasta=None, handle=None, device=0):
-        self._own = handle is None
-        self._ms = MinHashSearch(MhapParams(num_hashes=1, ordered_sketch_size=1, device=device)) if self._own else handle
-        self._lib = self._ms._lib
-        self._s = C.c_void_p()
         bases, ids, offsets, lengths = _all_reads(fasta, query_fasta)
         self._bases = np.ascontiguousarray(bases, np.uint8)
         self.ids, self._offsets = np.ascontiguousarray(ids, np.int64), np.ascontiguousarray(offsets, np.int64)
         self.lengths = np.ascontiguousarray(lengths, np.int32)
-        try:
-            self._ms._chk(self._lib.mhap_correct_begin(self._ms._h, _ptr(self._bases), C.c_int64(len(self._bases)), _ptr(self.ids),
-                                                       _ptr(self._offsets), _ptr(self.lengths), C.c_int64(len(self.ids)), C.byref(self._s)))
-        except Exception:
-            if self._own:
-                self._ms.close()
-            raise
+        super().__init__(handle, device, lambda: self._ms._chk(self._lib.mhap_correct_begin(
+            self._ms._h, _ptr(self._bases), len(self._bases), _ptr(self.ids), _ptr(self._offsets), _ptr(self.lengths), len(self.ids),
+            C.byref(self._s))))
 
     @classmethod
     def begin(cls, fasta, query_fasta=None, handle=None, device=0):
@@ -633,10 +745,10 @@ class CorrectSession:
         if len(op_offsets) != len(records) + 1:
             raise MhapError(f"CorrectSession.add: {len(records)} records need {len(records) + 1} run offsets, not {len(op_offsets)}")
         obj = C.c_void_p()
-        if self._lib.mhap_align_paths_from_runs(_ptr(op_offsets), C.c_int64(len(records)), _ptr(ops) if len(ops) else None, C.byref(obj)) != 0:
+        if self._lib.mhap_align_paths_from_runs(_ptr(op_offsets), C.c_int64(len(records)), _opt(ops), C.byref(obj)) != 0:
             raise MhapError("CorrectSession.add: op_offsets is not a list of run offsets over ops")
         try:
-            recs = _ptr(records) if len(records) else None
+            recs = _opt(records)
             if views is None:
                 self._ms._chk(self._lib.mhap_correct_add(self._s, recs, C.c_int64(len(records)), obj))
             else:   # (an empty array has no bytes to point at, and NULL would mean "both")
@@ -654,7 +766,7 @@ class CorrectSession:
         skipped = C.c_int64(0)
         self._ms._chk(self._lib.mhap_correct_finish(self._s, C.c_int32(min_cov), _ptr(self.offsets), _ptr(stats) if n else None, C.byref(skipped)))
         self.bytes = np.zeros(int(self.offsets[n]), np.uint8)
-        self._ms._chk(self._lib.mhap_correct_copy(self._s, _ptr(self.bytes) if len(self.bytes) else None))
+        self._ms._chk(self._lib.mhap_correct_copy(self._s, _opt(self.bytes)))
         raw = self.bytes.tobytes()
         return [raw[int(self.offsets[r]):int(self.offsets[r + 1])] for r in range(n)], stats, int(skipped.value)
 
@@ -663,30 +775,11 @@ class CorrectSession:
         if not 0 <= read_index < len(self.ids):
             raise MhapError(f"CorrectSession.votes: read {read_index} is not among the {len(self.ids)} reads")
         out = np.zeros((int(self.lengths[read_index]), CORRECT_COUNTERS), np.uint16)
-        self._ms._chk(self._lib.mhap_correct_votes(self._s, C.c_int64(read_index), _ptr(out) if len(out) else None))
+        self._ms._chk(self._lib.mhap_correct_votes(self._s, C.c_int64(read_index), _opt(out)))
         return out
 
     def table_bytes(self):
         return 48 * int(self.lengths.astype(np.int64).sum())
-
-    def close(self):
-        if self._s:
-            self._lib.mhap_correct_free(self._s)
-            self._s = C.c_void_p()
-            if self._own:
-                self._ms.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def correct_reads(records, fasta, op_offsets, ops, min_cov=4, query_fasta=None, handle=None, device=0):
@@ -787,7 +880,7 @@ def format_unitig_gfa(read_ids, unitigs, sequences):
     return "".join(out)
 
 
-class GraphSession:
+class GraphSession(_ReadsSession):
     """The string graph of realigned overlaps on the GPU (mhap_graph_begin / _add / _finish / _copy_*; the contract is the "string
     graph" section of include/mhap_hip.h): every record is classed, contained reads are set aside, the dovetails become arcs and
     the arcs a two-arc path explains are reduced.
@@ -803,43 +896,23 @@ class GraphSession:
 
     handle: a MinHashSearch whose device and stream to use (else one is made and closed with the session)."""
 
+    _prefix, _counts = "mhap_graph", GRAPH_COUNTS
+
     def __init__(self, read_ids, lengths, max_hang=1000, int_frac_permille=800, min_ovlp=2000, fuzz=1000, min_identity=0.0, handle=None,
                  device=0):
-        self._own = handle is None
-        self._ms = MinHashSearch(MhapParams(num_hashes=1, ordered_sketch_size=1, device=device)) if self._own else handle
-        self._lib = self._ms._lib
-        self._s = C.c_void_p()
-        self.ids = np.ascontiguousarray(read_ids, np.int64)
-        self.lengths = np.ascontiguousarray(lengths, np.int32)
-        if len(self.ids) != len(self.lengths):
-            raise MhapError(f"GraphSession: {len(self.ids)} ids and {len(self.lengths)} lengths")
-        p = _GraphParams(max_hang, int_frac_permille, min_ovlp, fuzz, min_identity)
         self.arcs = np.zeros((0, 7), np.int32)
         self.unitigs_table = None
         self.cleaned_table = None
-        try:
-            self._ms._chk(self._lib.mhap_graph_begin(self._ms._h, _ptr(self.ids) if len(self.ids) else None,
-                                                     _ptr(self.lengths) if len(self.ids) else None, C.c_int64(len(self.ids)), C.byref(p),
-                                                     C.byref(self._s)))
-        except Exception:
-            if self._own:
-                self._ms.close()
-            raise
-
-    def add(self, records):
-        """Class realigned records (nothing waits for the device)."""
-        records = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
-        self._ms._chk(self._lib.mhap_graph_add(self._s, _ptr(records) if len(records) else None, C.c_int64(len(records))))
+        super().__init__(read_ids, lengths, _GraphParams(max_hang, int_frac_permille, min_ovlp, fuzz, min_identity), handle, device)
 
     def finish(self):
         """(arcs, counts): the de-duplicated arc list as an int32 array (n, 7) of GRAPH_ARC_FIELDS and a dict of GRAPH_COUNTS."""
-        counts = np.zeros(len(GRAPH_COUNTS), np.int64)
         self.unitigs_table = None
         self.cleaned_table = None
-        self._ms._chk(self._lib.mhap_graph_finish(self._s, _ptr(counts)))
-        self.arcs = np.zeros((int(counts[GRAPH_COUNTS.index("arcs")]), 7), np.int32)
-        self._ms._chk(self._lib.mhap_graph_copy_arcs(self._s, _ptr(self.arcs) if len(self.arcs) else None))
-        self.counts = dict(zip(GRAPH_COUNTS, counts.tolist()))
+        counts = self._finish()
+        self.arcs = np.zeros((counts["arcs"], 7), np.int32)
+        self._ms._chk(self._lib.mhap_graph_copy_arcs(self._s, _opt(self.arcs)))
+        self.counts = counts
         return self.arcs, self.counts
 
     def info(self):
@@ -851,13 +924,13 @@ class GraphSession:
     def classes(self):
         """The class code of every record added so far, in arrival order (uint8; GRAPH_CLASSES names them)."""
         out = np.zeros(self.info()[1], np.uint8)
-        self._ms._chk(self._lib.mhap_graph_copy_classes(self._s, _ptr(out) if len(out) else None))
+        self._ms._chk(self._lib.mhap_graph_copy_classes(self._s, _opt(out)))
         return out
 
     def contained(self):
         """One byte per read: 1 when some record classes it contained."""
         out = np.zeros(len(self.ids), np.uint8)
-        self._ms._chk(self._lib.mhap_graph_copy_read_flags(self._s, _ptr(out) if len(out) else None))
+        self._ms._chk(self._lib.mhap_graph_copy_read_flags(self._s, _opt(out)))
         return out
 
     def gfa(self, cleaned=False):
@@ -872,10 +945,9 @@ class GraphSession:
         u = dict(unitig_start=np.zeros(n + 1, np.int64), unitig_len=np.zeros(n, np.int64), circular=np.zeros(n, np.uint8),
                  vertex=np.zeros(members, np.int32), offset=np.zeros(members, np.int64), span=np.zeros(members, np.int32),
                  links=np.zeros((links, 6), np.int32))
-        opt = lambda a: _ptr(a) if len(a) else None
-        self._ms._chk(self._lib.mhap_graph_copy_unitigs(self._s, _ptr(u["unitig_start"]), opt(u["unitig_len"]), opt(u["circular"])))
-        self._ms._chk(self._lib.mhap_graph_copy_layout(self._s, opt(u["vertex"]), opt(u["offset"]), opt(u["span"])))
-        self._ms._chk(self._lib.mhap_graph_copy_links(self._s, opt(u["links"])))
+        self._ms._chk(self._lib.mhap_graph_copy_unitigs(self._s, _ptr(u["unitig_start"]), _opt(u["unitig_len"]), _opt(u["circular"])))
+        self._ms._chk(self._lib.mhap_graph_copy_layout(self._s, _opt(u["vertex"]), _opt(u["offset"]), _opt(u["span"])))
+        self._ms._chk(self._lib.mhap_graph_copy_links(self._s, _opt(u["links"])))
         return u
 
     def unitigs(self):
@@ -915,13 +987,13 @@ class GraphSession:
     def dropped(self):
         """One byte per read after a clean(): 0 in play, 1 dropped as a tip, 2 as a bubble."""
         out = np.zeros(len(self.ids), np.uint8)
-        self._ms._chk(self._lib.mhap_graph_copy_dropped(self._s, _ptr(out) if len(out) else None))
+        self._ms._chk(self._lib.mhap_graph_copy_dropped(self._s, _opt(out)))
         return out
 
     def removed(self):
         """One byte per arc of the list after a clean(): 1 when the arc is final and one of its reads is dropped."""
         out = np.zeros(len(self.arcs), np.uint8)
-        self._ms._chk(self._lib.mhap_graph_copy_removed(self._s, _ptr(out) if len(out) else None))
+        self._ms._chk(self._lib.mhap_graph_copy_removed(self._s, _opt(out)))
         return out
 
     def spell_into(self, bases, offsets, out):
@@ -933,8 +1005,7 @@ class GraphSession:
             raise MhapError(f"GraphSession: {len(offsets)} offsets for {len(self.ids)} reads")
         if out.dtype != np.uint8 or not out.flags.c_contiguous or (self.unitigs_table is not None and len(out) != self.unitigs_table["counts"]["total_bases"]):
             raise MhapError("GraphSession.spell_into: out must be a contiguous uint8 array of total_bases bytes")
-        self._ms._chk(self._lib.mhap_graph_spell(self._s, _ptr(bases) if len(bases) else None, C.c_int64(len(bases)),
-                                                 _ptr(offsets) if len(offsets) else None, _ptr(out) if len(out) else None))
+        self._ms._chk(self._lib.mhap_graph_spell(self._s, _opt(bases), C.c_int64(len(bases)), _opt(offsets), _opt(out)))
         return out
 
     def unitig_sequences(self, fasta, query_fasta=None):
@@ -956,25 +1027,6 @@ class GraphSession:
         a, b, c, d = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
         self._ms._chk(self._lib.mhap_graph_unitigs_info(self._s, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
         return a.value, b.value, c.value, d.value
-
-    def close(self):
-        if self._s:
-            self._lib.mhap_graph_free(self._s)
-            self._s = C.c_void_p()
-            if self._own:
-                self._ms.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 TRIM_COUNTS = ("reads", "deleted", "cut5", "cut3", "gapped", "bases_in", "bases_kept", "eligible_records")   # mhap_trim_finish's counts
@@ -1016,7 +1068,7 @@ def trim_refine_record(record, ops, penalty=TRIM_PENALTY):
     rec = np.ascontiguousarray(record, dtype=RECORD_DTYPE).reshape(1)
     ops = np.ascontiguousarray(ops, dtype=np.uint32)
     out = np.zeros(1, RECORD_DTYPE)
-    rc = lib.mhap_trim_refine_record(_ptr(rec), _ptr(ops) if len(ops) else None, C.c_int64(len(ops)), C.c_int32(penalty), _ptr(out))
+    rc = lib.mhap_trim_refine_record(_ptr(rec), _opt(ops), C.c_int64(len(ops)), C.c_int32(penalty), _ptr(out))
     if rc < 0:
         raise MhapError("mhap_trim_refine_record: bad argument")
     return bool(rc), out[0]
@@ -1033,12 +1085,11 @@ def trim_refine(records, op_offsets, ops, penalty=TRIM_PENALTY, handle=None, dev
     ms = handle or MinHashSearch(MhapParams(num_hashes=1, ordered_sketch_size=1, device=device))
     try:
         obj = C.c_void_p()
-        if ms._lib.mhap_align_paths_from_runs(_ptr(op_offsets), C.c_int64(len(records)), _ptr(ops) if len(ops) else None, C.byref(obj)) != 0:
+        if ms._lib.mhap_align_paths_from_runs(_ptr(op_offsets), C.c_int64(len(records)), _opt(ops), C.byref(obj)) != 0:
             raise MhapError("trim_refine: op_offsets is not a list of run offsets over ops")
         out = np.zeros(len(records), RECORD_DTYPE)
         try:
-            ms._chk(ms._lib.mhap_trim_refine(ms._h, _ptr(records) if len(records) else None, C.c_int64(len(records)), obj, C.c_int32(penalty),
-                                             _ptr(out) if len(out) else None))
+            ms._chk(ms._lib.mhap_trim_refine(ms._h, _opt(records), C.c_int64(len(records)), obj, C.c_int32(penalty), _opt(out)))
         finally:
             ms._lib.mhap_align_paths_free(obj)
         return out
@@ -1047,7 +1098,7 @@ def trim_refine(records, op_offsets, ops, penalty=TRIM_PENALTY, handle=None, dev
             ms.close()
 
 
-class TrimSession:
+class TrimSession(_ReadsSession):
     """Reads cut to the stretch that other reads support (mhap_trim_begin / _add / _finish / _copy / _apply; the contract is the
     "read trimming" section of include/mhap_hip.h).
 
@@ -1060,44 +1111,23 @@ class TrimSession:
 
     handle: a MinHashSearch whose device and stream to use (else one is made and closed with the session)."""
 
-    def __init__(self, read_ids, lengths, min_cov=3, end_clip=500, min_span=2000, min_identity=0.0, handle=None, device=0):
-        self._own = handle is None
-        self._ms = MinHashSearch(MhapParams(num_hashes=1, ordered_sketch_size=1, device=device)) if self._own else handle
-        self._lib = self._ms._lib
-        self._s = C.c_void_p()
-        self.ids = np.ascontiguousarray(read_ids, np.int64)
-        self.lengths = np.ascontiguousarray(lengths, np.int32)
-        self.rows = self.flags = None
-        try:
-            if len(self.ids) != len(self.lengths):
-                raise MhapError(f"TrimSession: {len(self.ids)} ids and {len(self.lengths)} lengths")
-            p = _TrimParams(min_cov, end_clip, min_span, min_identity)
-            self._ms._chk(self._lib.mhap_trim_begin(self._ms._h, _ptr(self.ids) if len(self.ids) else None,
-                                                    _ptr(self.lengths) if len(self.ids) else None, C.c_int64(len(self.ids)), C.byref(p),
-                                                    C.byref(self._s)))
-        except Exception:
-            if self._own:
-                self._ms.close()
-            raise
+    _prefix, _counts = "mhap_trim", TRIM_COUNTS
+    rows = flags = None
 
-    def add(self, records):
-        """Pile realigned records up (nothing waits for the device)."""
-        records = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
-        self._ms._chk(self._lib.mhap_trim_add(self._s, _ptr(records) if len(records) else None, C.c_int64(len(records))))
+    def __init__(self, read_ids, lengths, min_cov=3, end_clip=500, min_span=2000, min_identity=0.0, handle=None, device=0):
+        super().__init__(read_ids, lengths, _TrimParams(min_cov, end_clip, min_span, min_identity), handle, device)
 
     def finish(self):
         """Make every read's row and flags; returns a dict of TRIM_COUNTS."""
-        counts = np.zeros(len(TRIM_COUNTS), np.int64)
         self.rows = self.flags = None
-        self._ms._chk(self._lib.mhap_trim_finish(self._s, _ptr(counts)))
-        self.counts = dict(zip(TRIM_COUNTS, counts.tolist()))
+        self.counts = self._finish()
         return self.counts
 
     def table(self):
         """(rows, flags) of the last finish: int32 (n, 4) of TRIM_ROW_FIELDS and one byte of TRIM_* bits per read."""
         if self.rows is None:
             rows, flags = np.zeros((len(self.ids), 4), np.int32), np.zeros(len(self.ids), np.uint8)
-            self._ms._chk(self._lib.mhap_trim_copy(self._s, _ptr(rows) if len(rows) else None, _ptr(flags) if len(flags) else None))
+            self._ms._chk(self._lib.mhap_trim_copy(self._s, _opt(rows), _opt(flags)))
             self.rows, self.flags = rows, flags
         return self.rows, self.flags
 
@@ -1106,7 +1136,7 @@ class TrimSession:
         if not 0 <= read_index < len(self.ids):
             raise MhapError("TrimSession.coverage: no such read")
         out = np.zeros(int(self.lengths[read_index]), np.int32)
-        self._ms._chk(self._lib.mhap_trim_coverage(self._s, C.c_int64(read_index), _ptr(out) if len(out) else None))
+        self._ms._chk(self._lib.mhap_trim_coverage(self._s, C.c_int64(read_index), _opt(out)))
         return out
 
     def apply(self, records):
@@ -1114,8 +1144,7 @@ class TrimSession:
         (which comes back as it went in); out[keep != 0] is the compacted list."""
         records = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
         out, keep = np.zeros(len(records), RECORD_DTYPE), np.zeros(len(records), np.uint8)
-        opt = lambda a: _ptr(a) if len(a) else None
-        self._ms._chk(self._lib.mhap_trim_apply(self._s, opt(records), C.c_int64(len(records)), opt(out), opt(keep)))
+        self._ms._chk(self._lib.mhap_trim_apply(self._s, _opt(records), C.c_int64(len(records)), _opt(out), _opt(keep)))
         return out, keep
 
     def trimmed(self, fasta):
@@ -1126,25 +1155,6 @@ class TrimSession:
         rows, flags = self.table()
         live = np.flatnonzero((flags & TRIM_DELETED) == 0)
         return FastaData(fasta.bases, fasta.offsets[live] + rows[live, 0], rows[live, 1] - rows[live, 0], self.ids[live])
-
-    def close(self):
-        if self._s:
-            self._lib.mhap_trim_free(self._s)
-            self._s = C.c_void_p()
-            if self._own:
-                self._ms.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 REPEAT_COUNTS = ("reads", "reads_with_interval", "whole_reads", "intervals", "repeat_bases", "bases", "eligible_records", "depth",
@@ -1175,14 +1185,14 @@ def repeat_judge_record(record, intervals_a, intervals_b, factor_pct=200, max_co
     ia, ib = (np.ascontiguousarray(x, np.int32).reshape(-1, 2) for x in (intervals_a, intervals_b))
     u = np.zeros(2, np.int32)
     p = _RepeatParams(factor_pct, max_cov, min_run, min_unique, min_identity)
-    rc = lib.mhap_repeat_judge_record(_ptr(rec), _ptr(ia) if len(ia) else None, C.c_int64(len(ia)), _ptr(ib) if len(ib) else None,
+    rc = lib.mhap_repeat_judge_record(_ptr(rec), _opt(ia), C.c_int64(len(ia)), _opt(ib),
                                       C.c_int64(len(ib)), C.byref(p), _ptr(u))
     if rc < 0:
         raise MhapError("mhap_repeat_judge_record: bad parameters, interval list or record")
     return bool(rc), int(u[0]), int(u[1])
 
 
-class RepeatSession:
+class RepeatSession(_ReadsSession):
     """Repeats marked from the overlap pile-up (mhap_repeat_begin / _add / _finish / _copy / _histogram / _apply; the contract is the
     "repeat marking" section of include/mhap_hip.h).
 
@@ -1195,37 +1205,16 @@ class RepeatSession:
 
     handle: a MinHashSearch whose device and stream to use (else one is made and closed with the session)."""
 
-    def __init__(self, read_ids, lengths, factor_pct=200, max_cov=0, min_run=500, min_unique=500, min_identity=0.0, handle=None, device=0):
-        self._own = handle is None
-        self._ms = MinHashSearch(MhapParams(num_hashes=1, ordered_sketch_size=1, device=device)) if self._own else handle
-        self._lib = self._ms._lib
-        self._s = C.c_void_p()
-        self.ids = np.ascontiguousarray(read_ids, np.int64)
-        self.lengths = np.ascontiguousarray(lengths, np.int32)
-        self._table = self.counts = None
-        try:
-            if len(self.ids) != len(self.lengths):
-                raise MhapError(f"RepeatSession: {len(self.ids)} ids and {len(self.lengths)} lengths")
-            p = _RepeatParams(factor_pct, max_cov, min_run, min_unique, min_identity)
-            self._ms._chk(self._lib.mhap_repeat_begin(self._ms._h, _ptr(self.ids) if len(self.ids) else None,
-                                                      _ptr(self.lengths) if len(self.ids) else None, C.c_int64(len(self.ids)), C.byref(p),
-                                                      C.byref(self._s)))
-        except Exception:
-            if self._own:
-                self._ms.close()
-            raise
+    _prefix, _counts = "mhap_repeat", REPEAT_COUNTS
+    _table = counts = None
 
-    def add(self, records):
-        """Pile realigned records up (nothing waits for the device)."""
-        records = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
-        self._ms._chk(self._lib.mhap_repeat_add(self._s, _ptr(records) if len(records) else None, C.c_int64(len(records))))
+    def __init__(self, read_ids, lengths, factor_pct=200, max_cov=0, min_run=500, min_unique=500, min_identity=0.0, handle=None, device=0):
+        super().__init__(read_ids, lengths, _RepeatParams(factor_pct, max_cov, min_run, min_unique, min_identity), handle, device)
 
     def finish(self):
         """Make the histogram, the depth and threshold and every read's intervals; returns a dict of REPEAT_COUNTS."""
-        counts = np.zeros(len(REPEAT_COUNTS), np.int64)
         self._table = self.counts = None
-        self._ms._chk(self._lib.mhap_repeat_finish(self._s, _ptr(counts)))
-        self.counts = dict(zip(REPEAT_COUNTS, counts.tolist()))
+        self.counts = self._finish()
         return self.counts
 
     def table(self):
@@ -1235,8 +1224,7 @@ class RepeatSession:
             n = len(self.ids)
             rows, flags, offsets = np.zeros((n, 4), np.int32), np.zeros(n, np.uint8), np.zeros(n + 1, np.int64)
             iv = np.zeros((self.counts["intervals"] if self.counts else 0, 2), np.int32)   # (without a finish the copy refuses)
-            opt = lambda a: _ptr(a) if len(a) else None
-            self._ms._chk(self._lib.mhap_repeat_copy(self._s, opt(rows), opt(flags), _ptr(offsets), opt(iv)))
+            self._ms._chk(self._lib.mhap_repeat_copy(self._s, _opt(rows), _opt(flags), _ptr(offsets), _opt(iv)))
             self._table = (rows, flags, offsets, iv)
         return self._table
 
@@ -1250,28 +1238,8 @@ class RepeatSession:
         """(keep, unique): one byte per record, 0 for a void one, and int32 (n, 2) of uA, uB (-1, -1 for an ineligible record)."""
         records = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
         keep, unique = np.zeros(len(records), np.uint8), np.zeros((len(records), 2), np.int32)
-        opt = lambda a: _ptr(a) if len(a) else None
-        self._ms._chk(self._lib.mhap_repeat_apply(self._s, opt(records), C.c_int64(len(records)), opt(keep), opt(unique)))
+        self._ms._chk(self._lib.mhap_repeat_apply(self._s, _opt(records), C.c_int64(len(records)), _opt(keep), _opt(unique)))
         return keep, unique
-
-    def close(self):
-        if self._s:
-            self._lib.mhap_repeat_free(self._s)
-            self._s = C.c_void_p()
-            if self._own:
-                self._ms.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 SELECT_COUNTS = ("reads", "reads_with_entry", "reads_over", "entries", "kept", "eligible_records")   # mhap_select_finish's counts
@@ -1308,7 +1276,7 @@ def select_judge_record(record, best_n=40, min_span=500, min_identity=0.0):
     return bool(rc), int(keys[0]), int(keys[1])
 
 
-class SelectSession:
+class SelectSession(_ReadsSession):
     """Each read's best overlaps (mhap_select_begin / _add / _finish / _copy / _apply; the contract is the "overlap selection" section
     of include/mhap_hip.h).
 
@@ -1319,67 +1287,27 @@ class SelectSession:
 
     handle: a MinHashSearch whose device and stream to use (else one is made and closed with the session)."""
 
-    def __init__(self, read_ids, lengths, best_n=40, min_span=500, min_identity=0.0, handle=None, device=0):
-        self._own = handle is None
-        self._ms = MinHashSearch(MhapParams(num_hashes=1, ordered_sketch_size=1, device=device)) if self._own else handle
-        self._lib = self._ms._lib
-        self._s = C.c_void_p()
-        self.ids = np.ascontiguousarray(read_ids, np.int64)
-        self.lengths = np.ascontiguousarray(lengths, np.int32)
-        self.rows = self.counts = None
-        try:
-            if len(self.ids) != len(self.lengths):
-                raise MhapError(f"SelectSession: {len(self.ids)} ids and {len(self.lengths)} lengths")
-            p = _SelectParams(best_n, min_span, min_identity)
-            self._ms._chk(self._lib.mhap_select_begin(self._ms._h, _ptr(self.ids) if len(self.ids) else None,
-                                                      _ptr(self.lengths) if len(self.ids) else None, C.c_int64(len(self.ids)), C.byref(p),
-                                                      C.byref(self._s)))
-        except Exception:
-            if self._own:
-                self._ms.close()
-            raise
+    _prefix, _counts = "mhap_select", SELECT_COUNTS
+    rows = counts = None
 
-    def add(self, records):
-        """The entries of realigned records (nothing waits for the device)."""
-        records = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
-        self._ms._chk(self._lib.mhap_select_add(self._s, _ptr(records) if len(records) else None, C.c_int64(len(records))))
+    def __init__(self, read_ids, lengths, best_n=40, min_span=500, min_identity=0.0, handle=None, device=0):
+        super().__init__(read_ids, lengths, _SelectParams(best_n, min_span, min_identity), handle, device)
 
     def finish(self):
         """Make every read's threshold: (rows, counts), int32 (n, 4) of SELECT_ROW_FIELDS and a dict of SELECT_COUNTS."""
-        counts = np.zeros(len(SELECT_COUNTS), np.int64)
         self.rows = self.counts = None
-        self._ms._chk(self._lib.mhap_select_finish(self._s, _ptr(counts)))
+        counts = self._finish()
         rows = np.zeros((len(self.ids), 4), np.int32)
-        self._ms._chk(self._lib.mhap_select_copy(self._s, _ptr(rows) if len(rows) else None))
-        self.rows, self.counts = rows, dict(zip(SELECT_COUNTS, counts.tolist()))
+        self._ms._chk(self._lib.mhap_select_copy(self._s, _opt(rows)))
+        self.rows, self.counts = rows, counts
         return self.rows, self.counts
 
     def apply(self, records):
         """One byte per record against the thresholds of the last finish: bit 0 SELECT_A (view A kept), bit 1 SELECT_B."""
         records = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
         views = np.zeros(len(records), np.uint8)
-        opt = lambda a: _ptr(a) if len(a) else None
-        self._ms._chk(self._lib.mhap_select_apply(self._s, opt(records), C.c_int64(len(records)), opt(views)))
+        self._ms._chk(self._lib.mhap_select_apply(self._s, _opt(records), C.c_int64(len(records)), _opt(views)))
         return views
-
-    def close(self):
-        if self._s:
-            self._lib.mhap_select_free(self._s)
-            self._s = C.c_void_p()
-            if self._own:
-                self._ms.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def select_overlaps(records, fasta, best_n=40, min_span=500, min_identity=0.0, query_fasta=None, handle=None, device=0):
@@ -1427,7 +1355,7 @@ def format_consensus_gfa(read_ids, unitigs, sequences, position_maps):
     return "".join(out)
 
 
-class ConsensusSession:
+class ConsensusSession(_Session):
     """The consensus of the unitigs a GraphSession serves (mhap_consensus_begin / _add / _run / _copy*; the contract is the "unitig
     consensus" section of include/mhap_hip.h): every read is placed on a unitig — members exactly, the others through their best
     overlap with a member — aligned to the draft, and every draft position takes the majority of the pile.
@@ -1441,24 +1369,23 @@ class ConsensusSession:
 
     A later finish(), unitigs() or clean() of the graph session invalidates this one."""
 
+    _prefix = "mhap_consensus"
+
     def __init__(self, graph_session, fasta, band=0, min_cov=4, query_fasta=None):
         self._gs = graph_session
-        self._ms = graph_session._ms
-        self._lib = self._ms._lib
-        self._s = C.c_void_p()
         bases, ids, offsets, lengths = _all_reads(fasta, query_fasta)
         if len(ids) != len(graph_session.ids):
             raise MhapError(f"ConsensusSession: {len(ids)} reads for a graph of {len(graph_session.ids)}")
         self._bases = np.ascontiguousarray(bases, np.uint8)
         self._offsets = np.ascontiguousarray(offsets, np.int64)
         p = _ConsensusParams(band, min_cov)
-        self._ms._chk(self._lib.mhap_consensus_begin(graph_session._s, _ptr(self._bases) if len(self._bases) else None, C.c_int64(len(self._bases)),
-                                                     _ptr(self._offsets) if len(self._offsets) else None, C.byref(p), C.byref(self._s)))
+        super().__init__(graph_session._ms, None, lambda: self._ms._chk(self._lib.mhap_consensus_begin(   # (the graph session's handle)
+            graph_session._s, _opt(self._bases), len(self._bases), _opt(self._offsets), C.byref(p), C.byref(self._s))))
 
     def add(self, records):
         """The realigned records the graph was given (they stay on the device, 32 bytes each)."""
         records = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
-        self._ms._chk(self._lib.mhap_consensus_add(self._s, _ptr(records) if len(records) else None, C.c_int64(len(records))))
+        self._ms._chk(self._lib.mhap_consensus_add(self._s, _opt(records), C.c_int64(len(records))))
 
     def run(self):
         """Place, align, vote and call: a dict of CONSENSUS_COUNTS.  Afterwards `bytes`, `out_offsets` (n + 1), `stats` (n, 6)."""
@@ -1488,7 +1415,7 @@ class ConsensusSession:
     def placements(self):
         """The placement table: int64 (reads, 5) of CONSENSUS_PLACEMENT_FIELDS."""
         out = np.zeros((self.info()[1], 5), np.int64)
-        self._ms._chk(self._lib.mhap_consensus_copy_placements(self._s, _ptr(out) if len(out) else None))
+        self._ms._chk(self._lib.mhap_consensus_copy_placements(self._s, _opt(out)))
         return out
 
     def position_maps(self):
@@ -1505,7 +1432,7 @@ class ConsensusSession:
         if not 0 <= k < n:
             raise MhapError(f"ConsensusSession.votes: unitig {k} is not among the {n} unitigs")
         out = np.zeros((int(self.stats[k, 0]), CORRECT_COUNTERS), np.uint16)
-        self._ms._chk(self._lib.mhap_consensus_votes(self._s, C.c_int64(k), _ptr(out) if len(out) else None))
+        self._ms._chk(self._lib.mhap_consensus_votes(self._s, C.c_int64(k), _opt(out)))
         return out
 
     def times(self):
@@ -1522,22 +1449,9 @@ class ConsensusSession:
         return format_consensus_gfa(self._gs.ids, u, self.sequences(), self.position_maps())
 
     def close(self):
-        if self._s:
-            if self._gs._s:   # (the graph session's handle may be gone with it)
-                self._lib.mhap_consensus_free(self._s)
+        if not self._gs._s:   # (the graph session's handle may be gone with it: nothing is left to free through)
             self._s = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
 
 
 def string_graph(records, fasta, query_fasta=None, handle=None, device=0, **params):

@@ -300,27 +300,8 @@ extern "C" int mhap_consensus_add(mhap_consensus_session* s, const mhap_record* 
   if (n < 0 || (n > 0 && !recs)) { *v.err = std::string(who) + ": null or negative argument"; return MHAP_E_INVALID; }
   if (s->n_items + n > INT32_MAX) { *v.err = std::string(who) + ": more than 2^31 - 1 records"; return MHAP_E_INVALID; }
   if (n == 0) return MHAP_OK;
-  const GraphView gv = graph_view(s->g);
-  std::vector<GItem> items((size_t)n);
-  for (int64_t q = 0; q < n; q++) {
-    const mhap_record& r = recs[q];
-    int64_t idx[2];
-    const int64_t ids[2] = {r.from_id, r.to_id};
-    const int32_t lens[2] = {r.alen, r.blen};
-    for (int f = 0; f < 2; f++) {
-      idx[f] = graph_find_read(s->g, ids[f]);
-      if (idx[f] < 0) {
-        *v.err = std::string(who) + ": record " + std::to_string(q) + " names read " + std::to_string(ids[f]) + ", which is not among the reads";
-        return MHAP_E_INVALID;
-      }
-      if (gv.lengths[idx[f]] != lens[f]) {
-        *v.err = std::string(who) + ": record " + std::to_string(q) + " gives read " + std::to_string(ids[f]) + " the length " + std::to_string(lens[f]) +
-                 ", the reads say " + std::to_string(gv.lengths[idx[f]]);
-        return MHAP_E_INVALID;
-      }
-    }
-    items[(size_t)q] = GItem{(int32_t)idx[0], 2 * (int32_t)idx[1] + (r.to_rc != 0 ? 1 : 0), r.a1, r.a2, r.b1, r.b2, r.score};
-  }
+  std::vector<GItem> items;
+  if (!graph_pack_records(s->g, who, recs, n, items, *v.err)) return MHAP_E_INVALID;
   (void)hipSetDevice(v.device);
   hipError_t e = s->items.ensure(sizeof(GItem) * (size_t)(s->n_items + n), true, v.stream);
   if (e != hipSuccess) return hip_fail(v, who, "hipMalloc of the records (32 bytes each)", e);

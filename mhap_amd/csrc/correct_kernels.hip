@@ -31,6 +31,7 @@
 
 #include "device_common.hpp"
 #include "mhap_internal.hpp"
+#include "read_table.hpp"
 #include "vote_common.hpp"
 
 namespace mhap {
@@ -183,18 +184,7 @@ static int correct_add(const char* who, mhap_correct_session* s, const mhap_reco
     const int64_t o0 = paths->offsets[(size_t)q], o1 = paths->offsets[(size_t)q + 1];
     if (o1 == o0 || r.from_id == r.to_id) continue;
     int64_t idx[2];
-    const int64_t ids[2] = {r.from_id, r.to_id};
-    const int32_t lens[2] = {r.alen, r.blen};
-    for (int f = 0; f < 2; f++) {
-      const auto it = s->by_id.find(ids[f]);
-      if (it == s->by_id.end()) { undo(); return bad(q, "names read " + std::to_string(ids[f]) + ", which is not among the reads"); }
-      idx[f] = it->second;
-      if (s->lengths[(size_t)idx[f]] != lens[f]) {
-        undo();
-        return bad(q, "gives read " + std::to_string(ids[f]) + " the length " + std::to_string(lens[f]) + ", the reads say " +
-                          std::to_string(s->lengths[(size_t)idx[f]]));
-      }
-    }
+    if (!find_record_reads(s->by_id, s->lengths.data(), who, q, r, idx, *v.err)) { undo(); return MHAP_E_INVALID; }
     // the runs are a path from (a1, j0) to (a2, j1), '=' at both ends
     const bool rc = r.to_rc != 0;
     const int64_t i0 = r.a1, j0 = rc ? (int64_t)r.blen - r.b2 - 1 : r.b1, j1 = rc ? (int64_t)r.blen - r.b1 - 1 : r.b2;

@@ -22,12 +22,12 @@
 
 #include <deque>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "device_common.hpp"
 #include "graph_class.hpp"
 #include "mhap_internal.hpp"
+#include "read_table.hpp"
 
 namespace mhap {
 namespace {
@@ -635,18 +635,15 @@ __global__ __launch_bounds__(256) void removed_kernel(int64_t n, const int32_t* 
 
 using namespace mhap;
 
-struct mhap_graph_session {
-  mhap_handle* h = nullptr;
+// The table of reads, the lookup of a record's reads and the queued uploads are read_table.hpp's ReadTable.  An add keeps a chunk of its
+// own (the records stay on the device until the session goes), so the table's one `items` buffer, and with it queue_add / commit_add,
+// are not used here.
+struct mhap_graph_session : ReadTable {
   GParams P{};
-  int64_t n_reads = 0, n_records = 0, n_arcs = -1;        // n_arcs < 0: no finish yet
-  std::vector<int64_t> ids;
-  std::vector<int32_t> lengths;
-  std::unordered_map<int64_t, int32_t> by_id;
+  int64_t n_arcs = -1;                                    // n_arcs < 0: no finish yet
   struct Chunk { DevBuf items, cls; int64_t n = 0; };     // items: the add's records, then its arc slots
   std::deque<Chunk> chunks;
-  struct Pending { std::vector<GItem> host; hipEvent_t ev = nullptr; };   // packed records an upload may still be reading
-  std::deque<Pending> pending;
-  DevBuf d_lengths, contained, counts;                    // counts: MHAP_GRAPH_COUNTS x uint64, the classes summed over the adds
+  DevBuf contained, counts;                               // counts: MHAP_GRAPH_COUNTS x uint64, the classes summed over the adds
   DevBuf deg, fill, start, fstart, tmp, keep, U, V, LEN, Q, bt_v, bt_pos, mark, rows;
   // unitigs: rebuilt by every mhap_graph_unitigs, invalid (n_unitigs < 0) from the next finish on
   int64_t n_contained = 0, finish_records = 0, n_unitigs = -1, n_members = 0, n_links = 0, n_ubases = 0;
@@ -658,28 +655,16 @@ struct mhap_graph_session {
   bool cleaned = false;
   uint64_t unitig_gen = 0;                                // bumped whenever the served unitigs go or change: a consensus session's key
   DevBuf dropped, removed, ccounts, o_lo, o_hi, o_cand, verdict;
-  void reap(bool all) {
-    while (!pending.empty() && (all || hipEventQuery(pending.front().ev) == hipSuccess)) {
-      (void)hipEventDestroy(pending.front().ev);
-      pending.pop_front();
-    }
-    (void)hipGetLastError();   // (an event that has not passed is no error of the call that looked)
-  }
   void release() {
+    release_table();
     for (auto& c : chunks) { c.items.release(); c.cls.release(); }
     chunks.clear();
-    for (DevBuf* b : {&d_lengths, &contained, &counts, &deg, &fill, &start, &fstart, &tmp, &keep, &U, &V, &LEN, &Q, &bt_v, &bt_pos, &mark, &rows,
+    for (DevBuf* b : {&contained, &counts, &deg, &fill, &start, &fstart, &tmp, &keep, &U, &V, &LEN, &Q, &bt_v, &bt_pos, &mark, &rows,
                        &fout, &cand, &carc, &unext, &uprev, &uspan, &uP[0], &uP[1], &uR[0], &uR[1], &uO[0], &uO[1], &uQ[0], &uQ[1], &uM[0], &uM[1], &cyc,
                        &tail, &cnt, &ulen, &kept, &unum, &mstart, &bstart, &islink, &lstart, &ucounts, &u_start, &u_len, &u_circ, &m_vertex, &m_offset,
                        &m_span, &m_dst, &links, &d_roff, &d_bases, &spelled, &dropped, &removed, &ccounts, &o_lo, &o_hi, &o_cand, &verdict}) b->release();
   }
 };
-
-namespace {
-
-unsigned blocks256(int64_t n) { return (unsigned)((n + 255) / 256); }
-
-}  // namespace
 
 extern "C" void mhap_graph_default_params(mhap_graph_params* p) {
   if (!p) return;
@@ -704,18 +689,12 @@ extern "C" int mhap_graph_begin(mhap_handle* h, const int64_t* read_ids, const i
   for (int64_t i = 0; i < n_reads; i++)
     if (lengths[i] < 0) { *v.err = std::string(who) + ": read " + std::to_string(i) + " has a negative length"; return MHAP_E_INVALID; }
   mhap_graph_session* s = new mhap_graph_session();
-  s->h = h; s->n_reads = n_reads;
   s->P = GParams{p.max_hang, p.int_frac_permille, p.min_ovlp, p.fuzz, p.min_identity};
-  s->ids.assign(read_ids, read_ids + n_reads);
-  s->lengths.assign(lengths, lengths + n_reads);
-  s->by_id.reserve((size_t)n_reads * 2);
-  for (int64_t i = 0; i < n_reads; i++) s->by_id.emplace(read_ids[i], (int32_t)i);   // (the first read of an id wins, as in mhap_realign_plan)
   (void)hipSetDevice(v.device);
   const size_t rb = 4 * (size_t)std::max<int64_t>(n_reads, 1);
-  hipError_t e = s->d_lengths.ensure(rb);
+  hipError_t e = s->begin_table(v, h, read_ids, lengths, n_reads);
   if (e == hipSuccess) e = s->contained.ensure(rb);
   if (e == hipSuccess) e = s->counts.ensure(8 * MHAP_GRAPH_COUNTS);
-  if (e == hipSuccess && n_reads > 0) e = hipMemcpyAsync(s->d_lengths.p, s->lengths.data(), 4 * (size_t)n_reads, hipMemcpyHostToDevice, v.stream);
   if (e == hipSuccess) e = hipMemsetAsync(s->contained.p, 0, rb, v.stream);
   if (e == hipSuccess) e = hipMemsetAsync(s->counts.p, 0, 8 * MHAP_GRAPH_COUNTS, v.stream);
   if (e == hipSuccess) e = hipStreamSynchronize(v.stream);
@@ -736,35 +715,14 @@ extern "C" int mhap_graph_add(mhap_graph_session* s, const mhap_record* recs, in
   if (s->n_records + n > INT32_MAX) { *v.err = std::string(who) + ": more than 2^31 - 1 records"; return MHAP_E_INVALID; }
   s->reap(false);
   if (n == 0) return MHAP_OK;
-  std::vector<GItem> items((size_t)n);
-  for (int64_t q = 0; q < n; q++) {
-    const mhap_record& r = recs[q];
-    int32_t idx[2];
-    const int64_t ids[2] = {r.from_id, r.to_id};
-    const int32_t lens[2] = {r.alen, r.blen};
-    for (int f = 0; f < 2; f++) {
-      const auto it = s->by_id.find(ids[f]);
-      if (it == s->by_id.end()) {
-        *v.err = std::string(who) + ": record " + std::to_string(q) + " names read " + std::to_string(ids[f]) + ", which is not among the reads";
-        return MHAP_E_INVALID;
-      }
-      idx[f] = it->second;
-      if (s->lengths[(size_t)idx[f]] != lens[f]) {
-        *v.err = std::string(who) + ": record " + std::to_string(q) + " gives read " + std::to_string(ids[f]) + " the length " + std::to_string(lens[f]) +
-                 ", the reads say " + std::to_string(s->lengths[(size_t)idx[f]]);
-        return MHAP_E_INVALID;
-      }
-    }
-    items[(size_t)q] = GItem{idx[0], 2 * idx[1] + (r.to_rc != 0 ? 1 : 0), r.a1, r.a2, r.b1, r.b2, r.score};
-  }
+  mhap_graph_session::Pending p;
+  if (!graph_pack_records(s, who, recs, n, p.host, *v.err)) return MHAP_E_INVALID;
   (void)hipSetDevice(v.device);
   mhap_graph_session::Chunk c;
-  mhap_graph_session::Pending p;
   hipError_t e = c.items.ensure(sizeof(GItem) * (size_t)n);
   if (e == hipSuccess) e = c.cls.ensure((size_t)n);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&p.ev, hipEventDisableTiming);
   if (e != hipSuccess) { c.items.release(); c.cls.release(); return hip_fail(v, who, "hipMalloc of the records", e); }
-  p.host = std::move(items);
   e = hipMemcpyAsync(c.items.p, p.host.data(), sizeof(GItem) * (size_t)n, hipMemcpyHostToDevice, v.stream);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(classify_kernel, dim3(blocks256(n)), dim3(256), 0, v.stream, c.items.as<int4>(), n, (int32_t)s->n_records,
@@ -863,19 +821,6 @@ extern "C" int mhap_graph_info(const mhap_graph_session* s, int64_t* n_reads, in
   return MHAP_OK;
 }
 
-namespace {
-
-int download(mhap_graph_session* s, const char* who, void* dst, const void* src, size_t bytes) {
-  HandleView v = handle_view(s->h);
-  (void)hipSetDevice(v.device);
-  hipError_t e;
-  if ((e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return hip_fail(v, who, "download", e);
-  if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return hip_fail(v, who, "download", e);
-  return MHAP_OK;
-}
-
-}  // namespace
-
 extern "C" int mhap_graph_copy_arcs(mhap_graph_session* s, int32_t* rows) {
   const char* who = "mhap_graph_copy_arcs";
   if (!s) return MHAP_E_INVALID;
@@ -883,7 +828,7 @@ extern "C" int mhap_graph_copy_arcs(mhap_graph_session* s, int32_t* rows) {
   if (s->n_arcs < 0) { *v.err = std::string(who) + ": no mhap_graph_finish has completed"; return MHAP_E_INVALID; }
   if (s->n_arcs == 0) return MHAP_OK;
   if (!rows) { *v.err = std::string(who) + ": null argument"; return MHAP_E_INVALID; }
-  return download(s, who, rows, s->rows.p, 28 * (size_t)s->n_arcs);
+  return s->download(who, rows, s->rows.p, 28 * (size_t)s->n_arcs);
 }
 
 extern "C" int mhap_graph_copy_classes(mhap_graph_session* s, uint8_t* classes) {
@@ -894,7 +839,7 @@ extern "C" int mhap_graph_copy_classes(mhap_graph_session* s, uint8_t* classes) 
   if (!classes) { *v.err = std::string(who) + ": null argument"; return MHAP_E_INVALID; }
   int64_t at = 0;
   for (auto& c : s->chunks) {
-    const int rc = download(s, who, classes + at, c.cls.p, (size_t)c.n);
+    const int rc = s->download(who, classes + at, c.cls.p, (size_t)c.n);
     if (rc != MHAP_OK) return rc;
     at += c.n;
   }
@@ -908,7 +853,7 @@ extern "C" int mhap_graph_copy_read_flags(mhap_graph_session* s, uint8_t* flags)
   if (s->n_reads == 0) return MHAP_OK;
   if (!flags) { *v.err = std::string(who) + ": null argument"; return MHAP_E_INVALID; }
   std::vector<uint32_t> w((size_t)s->n_reads);
-  const int rc = download(s, who, w.data(), s->contained.p, 4 * w.size());
+  const int rc = s->download(who, w.data(), s->contained.p, 4 * w.size());
   if (rc != MHAP_OK) return rc;
   for (int64_t r = 0; r < s->n_reads; r++) flags[r] = w[(size_t)r] ? 1 : 0;
   return MHAP_OK;
@@ -1141,7 +1086,7 @@ extern "C" int mhap_graph_copy_dropped(mhap_graph_session* s, uint8_t* per_read)
   if (!s->cleaned) { *v.err = std::string(who) + ": no mhap_graph_clean has completed since the last mhap_graph_finish"; return MHAP_E_INVALID; }
   if (s->n_reads == 0) return MHAP_OK;
   if (!per_read) { *v.err = std::string(who) + ": null argument"; return MHAP_E_INVALID; }
-  return download(s, who, per_read, s->dropped.p, (size_t)s->n_reads);
+  return s->download(who, per_read, s->dropped.p, (size_t)s->n_reads);
 }
 
 extern "C" int mhap_graph_copy_removed(mhap_graph_session* s, uint8_t* per_arc) {
@@ -1151,7 +1096,7 @@ extern "C" int mhap_graph_copy_removed(mhap_graph_session* s, uint8_t* per_arc) 
   if (!s->cleaned) { *v.err = std::string(who) + ": no mhap_graph_clean has completed since the last mhap_graph_finish"; return MHAP_E_INVALID; }
   if (s->n_arcs == 0) return MHAP_OK;
   if (!per_arc) { *v.err = std::string(who) + ": null argument"; return MHAP_E_INVALID; }
-  return download(s, who, per_arc, s->removed.p, (size_t)s->n_arcs);
+  return s->download(who, per_arc, s->removed.p, (size_t)s->n_arcs);
 }
 
 namespace {
@@ -1198,9 +1143,9 @@ extern "C" int mhap_graph_copy_unitigs(mhap_graph_session* s, int64_t* unitig_st
   unitig_start[s->n_unitigs] = s->n_members;
   if (s->n_unitigs == 0) return MHAP_OK;
   if (!unitig_len || !circular) return null_arg(s, who);
-  if ((rc = download(s, who, unitig_start, s->u_start.p, 8 * (size_t)s->n_unitigs)) != MHAP_OK) return rc;
-  if ((rc = download(s, who, unitig_len, s->u_len.p, 8 * (size_t)s->n_unitigs)) != MHAP_OK) return rc;
-  return download(s, who, circular, s->u_circ.p, (size_t)s->n_unitigs);
+  if ((rc = s->download(who, unitig_start, s->u_start.p, 8 * (size_t)s->n_unitigs)) != MHAP_OK) return rc;
+  if ((rc = s->download(who, unitig_len, s->u_len.p, 8 * (size_t)s->n_unitigs)) != MHAP_OK) return rc;
+  return s->download(who, circular, s->u_circ.p, (size_t)s->n_unitigs);
 }
 
 extern "C" int mhap_graph_copy_layout(mhap_graph_session* s, int32_t* vertex, int64_t* offset, int32_t* span) {
@@ -1210,9 +1155,9 @@ extern "C" int mhap_graph_copy_layout(mhap_graph_session* s, int32_t* vertex, in
   if (rc != MHAP_OK) return rc;
   if (s->n_members == 0) return MHAP_OK;
   if (!vertex || !offset || !span) return null_arg(s, who);
-  if ((rc = download(s, who, vertex, s->m_vertex.p, 4 * (size_t)s->n_members)) != MHAP_OK) return rc;
-  if ((rc = download(s, who, offset, s->m_offset.p, 8 * (size_t)s->n_members)) != MHAP_OK) return rc;
-  return download(s, who, span, s->m_span.p, 4 * (size_t)s->n_members);
+  if ((rc = s->download(who, vertex, s->m_vertex.p, 4 * (size_t)s->n_members)) != MHAP_OK) return rc;
+  if ((rc = s->download(who, offset, s->m_offset.p, 8 * (size_t)s->n_members)) != MHAP_OK) return rc;
+  return s->download(who, span, s->m_span.p, 4 * (size_t)s->n_members);
 }
 
 extern "C" int mhap_graph_copy_links(mhap_graph_session* s, int32_t* rows) {
@@ -1222,7 +1167,7 @@ extern "C" int mhap_graph_copy_links(mhap_graph_session* s, int32_t* rows) {
   if (rc != MHAP_OK) return rc;
   if (s->n_links == 0) return MHAP_OK;
   if (!rows) return null_arg(s, who);
-  return download(s, who, rows, s->links.p, 24 * (size_t)s->n_links);
+  return s->download(who, rows, s->links.p, 24 * (size_t)s->n_links);
 }
 
 extern "C" int mhap_graph_spell_device(mhap_graph_session* s, const uint8_t* d_bases, int64_t n_bases, const int64_t* offsets, uint8_t* out) {
@@ -1289,9 +1234,14 @@ extern "C" void mhap_graph_free(mhap_graph_session* s) {
 mhap::GraphView mhap::graph_view(const mhap_graph_session* s) {
   return GraphView{s->h, s->P, s->n_reads, s->ids.data(), s->lengths.data(), s->unitig_gen, s->n_unitigs};
 }
-int64_t mhap::graph_find_read(const mhap_graph_session* s, int64_t id) {
-  const auto it = s->by_id.find(id);
-  return it == s->by_id.end() ? -1 : (int64_t)it->second;
+bool mhap::graph_pack_records(const mhap_graph_session* s, const char* who, const mhap_record* recs, int64_t n, std::vector<GItem>& out, std::string& err) {
+  out.resize((size_t)n);
+  for (int64_t q = 0; q < n; q++) {   // (the lookup alone: a record's aligned ends index nothing here)
+    int32_t idx[2];
+    if (!s->find_reads(who, q, recs[q], idx, err)) return false;
+    out[(size_t)q] = pack_item(idx, recs[q]);
+  }
+  return true;
 }
 
 extern "C" int mhap_format_gfa_link(const int32_t* row7, const int64_t* read_ids, char* out, size_t cap) {

@@ -106,7 +106,9 @@ struct GraphView {
   mhap_handle* h; GParams P; int64_t n_reads; const int64_t* ids; const int32_t* lengths; uint64_t unitig_gen; int64_t n_unitigs;
 };
 GraphView graph_view(const mhap_graph_session* s);
-int64_t graph_find_read(const mhap_graph_session* s, int64_t id);   // the read's position in read_ids (the first of an id), or -1
+// records against the session's table of reads, as mhap_graph_add takes them: both reads looked up and their lengths checked (no
+// check of the aligned ends), packed as items; false with the refused record's message in err
+bool graph_pack_records(const mhap_graph_session* s, const char* who, const mhap_record* recs, int64_t n, std::vector<GItem>& out, std::string& err);
 // Eager exchange (mhap_dist.hip; mhap_dist_set_eager): an add on a rank of a multi-GPU job gathers its forward rows while the add is
 // still computing — the ordered rows (6/7 of the bytes) as soon as the ordered-sketch kernel has written them, under the MinHash
 // kernel; the MinHash rows, meta and ids right behind the MinHash kernel, under the index build — so that the collective search

@@ -1,7 +1,7 @@
 // pileup_common.hpp — what "read trimming" (trim_kernels.hip) and "repeat marking" (repeat_kernels.hip) share, written once: the
 // per-base difference array of a table of reads, the kernel that piles records up on it, the tile step that turns differences into
-// coverage, and the host side of a session up to the add (the table of reads, the packed records, the queued uploads).  The table
-// and the records without the difference array (ReadTable) are what "overlap selection" (select_kernels.hip) takes from here.
+// coverage, and the host side of a pile up to the add.  The table of reads, the packed records and the queued uploads underneath
+// are read_table.hpp's ReadTable, which needs no pile.
 //
 // Layout: read r owns lengths[r] + 1 int32 slots at an offset rounded up to four slots, so that a read's slots begin on a 16-byte
 // word; the array is zeroed once.  A tile is PILE_TILE positions: four 16-byte loads per lane of a workgroup of 256, each contiguous
@@ -9,22 +9,16 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <deque>
 #include <numeric>
-#include <string>
-#include <unordered_map>
 #include <vector>
 
-#include "graph_class.hpp"
-#include "mhap_internal.hpp"
+#include "read_table.hpp"
 #include "trim_common.hpp"
 
 namespace mhap {
 namespace {
 
 enum { PILE_T = 256, PILE_WAVES = PILE_T / 64, PILE_LOADS = 4, PILE_TILE = PILE_T * PILE_LOADS * 4 };
-
-typedef unsigned long long u64;
 
 // one lane per record: +1 at an interval's begin, -1 at its end, up to four atomicAdd(int32); the eligible records are counted once
 // per wave.  The intervals are trim_interval's: P.end_clip = P.min_span = 0 gives the aligned intervals as they are.
@@ -121,146 +115,6 @@ __device__ inline void pile_scan_tile(const T (&v)[PILE_LOADS], int lane, int wa
   }
   carry = acc;
 }
-
-inline unsigned blocks256(int64_t n) { return (unsigned)((n + 255) / 256); }
-
-// The host side that every session over a table of reads begins with ("read trimming", "repeat marking", "overlap selection"): the
-// table, the records of a call checked and packed as items, and the uploads an add has queued.
-struct ReadTable {
-  mhap_handle* h = nullptr;
-  int64_t n_reads = 0, n_records = 0;
-  std::vector<int64_t> ids;
-  std::vector<int32_t> lengths;
-  std::unordered_map<int64_t, int32_t> by_id;
-  struct Pending { std::vector<GItem> host; hipEvent_t ev = nullptr; };   // packed records an upload may still be reading
-  std::deque<Pending> pending;
-  DevBuf d_lengths, items;
-
-  void reap(bool all) {
-    while (!pending.empty() && (all || hipEventQuery(pending.front().ev) == hipSuccess)) {
-      (void)hipEventDestroy(pending.front().ev);
-      pending.pop_front();
-    }
-    (void)hipGetLastError();   // (an event that has not passed is no error of the call that looked)
-  }
-  void release_table() {
-    for (DevBuf* b : {&d_lengths, &items}) b->release();
-  }
-
-  // the arguments every begin refuses; false with the handle's message set
-  static bool table_ok(const HandleView& v, const char* who, const void* session, const int64_t* read_ids, const int32_t* lens, int64_t n) {
-    if (!session || n < 0 || (n > 0 && (!read_ids || !lens))) { *v.err = std::string(who) + ": null or negative argument"; return false; }
-    if (n >= ((int64_t)1 << 30)) { *v.err = std::string(who) + ": 2^30 reads or more"; return false; }
-    for (int64_t i = 0; i < n; i++)
-      if (lens[i] < 0 || lens[i] > INT32_MAX - 8) {
-        *v.err = std::string(who) + ": read " + std::to_string(i) + " has a negative length or one above 2^31 - 9";
-        return false;
-      }
-    return true;
-  }
-
-  // the table on the host and the lengths on the device; queued on the handle's stream, not waited for
-  hipError_t begin_table(const HandleView& v, mhap_handle* handle, const int64_t* read_ids, const int32_t* lens, int64_t n) {
-    h = handle; n_reads = n;
-    ids.assign(read_ids, read_ids + n);
-    lengths.assign(lens, lens + n);
-    by_id.reserve((size_t)n * 2);
-    for (int64_t i = 0; i < n; i++) by_id.emplace(read_ids[i], (int32_t)i);   // (the first read of an id wins, as in mhap_realign_plan)
-    hipError_t e = d_lengths.ensure(4 * (size_t)std::max<int64_t>(n, 1));
-    if (e == hipSuccess && n > 0) e = hipMemcpyAsync(d_lengths.p, lengths.data(), 4 * (size_t)n, hipMemcpyHostToDevice, v.stream);
-    return e;
-  }
-  // the records of a call as items; a refused record leaves its message in err
-  bool pack_records(const char* who, const mhap_record* recs, int64_t n, std::vector<GItem>& out, std::string& err) const {
-    out.resize((size_t)n);
-    for (int64_t q = 0; q < n; q++) {
-      const mhap_record& r = recs[q];
-      int32_t idx[2];
-      const int64_t rid[2] = {r.from_id, r.to_id};
-      const int32_t lens[2] = {r.alen, r.blen}, x1[2] = {r.a1, r.b1}, x2[2] = {r.a2, r.b2};
-      for (int f = 0; f < 2; f++) {
-        const auto it = by_id.find(rid[f]);
-        if (it == by_id.end()) {
-          err = std::string(who) + ": record " + std::to_string(q) + " names read " + std::to_string(rid[f]) + ", which is not among the reads";
-          return false;
-        }
-        idx[f] = it->second;
-        if (lengths[(size_t)idx[f]] != lens[f]) {
-          err = std::string(who) + ": record " + std::to_string(q) + " gives read " + std::to_string(rid[f]) + " the length " + std::to_string(lens[f]) +
-                ", the reads say " + std::to_string(lengths[(size_t)idx[f]]);
-          return false;
-        }
-        if (r.score != 0.0 && (x1[f] < 0 || x2[f] < x1[f] || x2[f] >= lens[f])) {
-          err = std::string(who) + ": record " + std::to_string(q) + " aligns " + std::to_string(x1[f]) + " .. " + std::to_string(x2[f]) + " of read " +
-                std::to_string(rid[f]) + ", which has " + std::to_string(lens[f]) + " bases";
-          return false;
-        }
-      }
-      out[(size_t)q] = GItem{idx[0], 2 * idx[1] + (r.to_rc != 0 ? 1 : 0), r.a1, r.a2, r.b1, r.b2, r.score};
-    }
-    return true;
-  }
-
-  // The front of an add: the records are checked (a refused call queues nothing), packed into p and their upload into `items` is
-  // queued.  MHAP_OK with p.ev == nullptr: n == 0, nothing to do.  The caller launches its kernel on the stream and calls commit_add.
-  int queue_add(const HandleView& v, const char* who, const mhap_record* recs, int64_t n, Pending& p) {
-    if (n < 0 || (n > 0 && !recs)) { *v.err = std::string(who) + ": null or negative argument"; return MHAP_E_INVALID; }
-    if (n > INT32_MAX) { *v.err = std::string(who) + ": more than 2^31 - 1 records in one call"; return MHAP_E_INVALID; }
-    reap(false);
-    if (n == 0) return MHAP_OK;
-    if (!pack_records(who, recs, n, p.host, *v.err)) return MHAP_E_INVALID;
-    (void)hipSetDevice(v.device);
-    hipError_t e = items.ensure(sizeof(GItem) * (size_t)n);   // (a larger buffer frees the old one, which waits for the device)
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&p.ev, hipEventDisableTiming);
-    if (e != hipSuccess) { p.ev = nullptr; return hip_fail(v, who, "hipMalloc of the records", e); }
-    e = hipMemcpyAsync(items.p, p.host.data(), sizeof(GItem) * (size_t)n, hipMemcpyHostToDevice, v.stream);
-    if (e != hipSuccess) {   // nothing was queued behind the upload: nothing of this call stays
-      (void)hipStreamSynchronize(v.stream);
-      (void)hipEventDestroy(p.ev);
-      p.ev = nullptr;
-      return hip_fail(v, who, "upload", e);
-    }
-    return MHAP_OK;
-  }
-  // The back of an add, behind the caller's launch: the launch's error is looked at, the event recorded and the records counted.
-  int commit_add(const HandleView& v, const char* who, Pending& p, int64_t n) {
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipEventRecord(p.ev, v.stream);
-    if (e != hipSuccess) {
-      (void)hipStreamSynchronize(v.stream);
-      (void)hipEventDestroy(p.ev);
-      return hip_fail(v, who, "launch", e);
-    }
-    pending.push_back(std::move(p));
-    n_records += n;
-    return MHAP_OK;
-  }
-
-  // the packed records of an apply queued into `items`, behind everything an add may still read; `packed` must live until the
-  // caller has waited for the stream.  False with rc set.
-  bool upload_for_apply(const HandleView& v, const char* who, const mhap_record* in, int64_t n, std::vector<GItem>& packed, int& rc) {
-    if (!pack_records(who, in, n, packed, *v.err)) { rc = MHAP_E_INVALID; return false; }
-    (void)hipSetDevice(v.device);
-    hipError_t e;
-    if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) { rc = hip_fail(v, who, "the stream", e); return false; }   // (an add may still read the items' buffer)
-    reap(true);
-    if ((e = items.ensure(sizeof(GItem) * (size_t)n)) != hipSuccess) { rc = hip_fail(v, who, "hipMalloc of the records", e); return false; }
-    if ((e = hipMemcpyAsync(items.p, packed.data(), sizeof(GItem) * (size_t)n, hipMemcpyHostToDevice, v.stream)) != hipSuccess) {
-      rc = hip_fail(v, who, "upload", e);
-      return false;
-    }
-    return true;
-  }
-
-  int download(const char* who, void* dst, const void* src, size_t bytes) {
-    HandleView v = handle_view(h);
-    (void)hipSetDevice(v.device);
-    hipError_t e;
-    if ((e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return hip_fail(v, who, "download", e);
-    if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return hip_fail(v, who, "download", e);
-    return MHAP_OK;
-  }
-};
 
 // The table with the per-base difference array of the trimming and the repeat marking on top.
 struct Pile : ReadTable {

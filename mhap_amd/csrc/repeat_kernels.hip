@@ -271,6 +271,8 @@ bool params_ok(const mhap_repeat_params& p) { return p.factor_pct >= 100 && p.ma
 using namespace mhap;
 
 struct mhap_repeat_session : Pile {
+  static constexpr const char* finish_name = "mhap_repeat_finish";
+  static constexpr int unfinished_rc = MHAP_E_INVALID;
   RParams P{};
   TParams E{};   // the add's parameters: eligibility, and the aligned intervals as they are
   bool finished = false;
@@ -290,41 +292,27 @@ extern "C" void mhap_repeat_default_params(mhap_repeat_params* p) {
 
 extern "C" int mhap_repeat_begin(mhap_handle* h, const int64_t* read_ids, const int32_t* lengths, int64_t n_reads, const mhap_repeat_params* params,
                                  mhap_repeat_session** session) {
-  const char* who = "mhap_repeat_begin";
-  if (session) *session = nullptr;
-  if (!h) return MHAP_E_INVALID;
-  HandleView v = handle_view(h);
-  if (!Pile::table_ok(v, who, session, read_ids, lengths, n_reads)) return MHAP_E_INVALID;
-  mhap_repeat_params p;
-  mhap_repeat_default_params(&p);
-  if (params) p = *params;
-  if (!params_ok(p)) { *v.err = std::string(who) + ": factor_pct must be >= 100, max_cov >= 0, min_run >= 1 and min_unique >= 0"; return MHAP_E_INVALID; }
-  mhap_repeat_session* s = new mhap_repeat_session();
-  s->P = RParams{p.factor_pct, p.max_cov, p.min_run, p.min_unique};
-  s->E = TParams{1, 0, 0, p.min_identity};
-  for (int64_t i = 0; i < n_reads; i++) s->cap += ((int64_t)lengths[i] + 1) / ((int64_t)p.min_run + 1);   // a run and the position behind it
-  (void)hipSetDevice(v.device);
-  const size_t nr = (size_t)std::max<int64_t>(n_reads, 1), ni = (size_t)std::max<int64_t>(s->cap, 1);
-  hipError_t e = s->begin_pile(v, h, read_ids, lengths, n_reads);
-  if (e == hipSuccess) e = s->d_hist.ensure(8 * MHAP_REPEAT_BINS);
-  if (e == hipSuccess) e = s->dt.ensure(8);
-  if (e == hipSuccess) e = s->cnt.ensure(4 * nr);
-  if (e == hipSuccess) e = s->offsets.ensure(8 * (nr + 1));
-  if (e == hipSuccess) e = s->iv.ensure(8 * ni);
-  if (e == hipSuccess) e = s->cum.ensure(4 * ni);
-  if (e == hipSuccess) e = s->rows.ensure(16 * nr);
-  if (e == hipSuccess) e = s->flags.ensure(nr);
-  if (e == hipSuccess) e = s->counts.ensure(8 * MHAP_REPEAT_COUNTS);
-  if (e == hipSuccess) e = hipMemsetAsync(s->counts.p, 0, 8 * MHAP_REPEAT_COUNTS, v.stream);
-  if (e == hipSuccess) e = hipMemsetAsync(s->offsets.p, 0, 8 * (nr + 1), v.stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(v.stream);
-  if (e != hipSuccess) {
-    s->release();
-    delete s;
-    return hip_fail(v, who, "the table of reads", e);
-  }
-  *session = s;
-  return MHAP_OK;
+  return session_begin("mhap_repeat_begin", h, read_ids, lengths, n_reads, params, mhap_repeat_default_params, params_ok,
+                       "factor_pct must be >= 100, max_cov >= 0, min_run >= 1 and min_unique >= 0", session,
+                       [&](mhap_repeat_session& s, const mhap_repeat_params& p, const HandleView& v) {
+    s.P = RParams{p.factor_pct, p.max_cov, p.min_run, p.min_unique};
+    s.E = TParams{1, 0, 0, p.min_identity};
+    for (int64_t i = 0; i < n_reads; i++) s.cap += ((int64_t)lengths[i] + 1) / ((int64_t)p.min_run + 1);   // a run and the position behind it
+    const size_t nr = (size_t)std::max<int64_t>(n_reads, 1), ni = (size_t)std::max<int64_t>(s.cap, 1);
+    Steps q{s.begin_pile(v, h, read_ids, lengths, n_reads), v.stream};
+    q.ensure(s.d_hist, 8 * MHAP_REPEAT_BINS);
+    q.ensure(s.dt, 8);
+    q.ensure(s.cnt, 4 * nr);
+    q.ensure(s.offsets, 8 * (nr + 1));
+    q.ensure(s.iv, 8 * ni);
+    q.ensure(s.cum, 4 * ni);
+    q.ensure(s.rows, 16 * nr);
+    q.ensure(s.flags, nr);
+    q.ensure(s.counts, 8 * MHAP_REPEAT_COUNTS);
+    q.zero(s.counts, 8 * MHAP_REPEAT_COUNTS);
+    q.zero(s.offsets, 8 * (nr + 1));
+    return q.e;
+  });
 }
 
 extern "C" int mhap_repeat_add(mhap_repeat_session* s, const mhap_record* recs, int64_t n) {
@@ -386,9 +374,10 @@ extern "C" int mhap_repeat_copy(mhap_repeat_session* s, int32_t* rows, uint8_t* 
   const char* who = "mhap_repeat_copy";
   if (!s) return MHAP_E_INVALID;
   HandleView v = handle_view(s->h);
-  if (!s->finished) { *v.err = std::string(who) + ": no mhap_repeat_finish has completed"; return MHAP_E_INVALID; }
+  int rc = check_finished(s, v, who);
+  if (rc != MHAP_OK) return rc;
   if (!offsets || (s->n_reads > 0 && (!rows || !flags)) || (s->n_intervals > 0 && !intervals)) { *v.err = std::string(who) + ": null argument"; return MHAP_E_INVALID; }
-  int rc = s->download(who, offsets, s->offsets.p, 8 * ((size_t)s->n_reads + 1));
+  rc = s->download(who, offsets, s->offsets.p, 8 * ((size_t)s->n_reads + 1));
   if (rc == MHAP_OK && s->n_reads > 0) rc = s->download(who, rows, s->rows.p, 16 * (size_t)s->n_reads);
   if (rc == MHAP_OK && s->n_reads > 0) rc = s->download(who, flags, s->flags.p, (size_t)s->n_reads);
   if (rc == MHAP_OK && s->n_intervals > 0) rc = s->download(who, intervals, s->iv.p, 8 * (size_t)s->n_intervals);
@@ -399,7 +388,8 @@ extern "C" int mhap_repeat_histogram(mhap_repeat_session* s, int64_t* bins) {
   const char* who = "mhap_repeat_histogram";
   if (!s) return MHAP_E_INVALID;
   HandleView v = handle_view(s->h);
-  if (!s->finished) { *v.err = std::string(who) + ": no mhap_repeat_finish has completed"; return MHAP_E_INVALID; }
+  const int rc = check_finished(s, v, who);
+  if (rc != MHAP_OK) return rc;
   if (!bins) { *v.err = std::string(who) + ": null argument"; return MHAP_E_INVALID; }
   for (int c = 0; c < MHAP_REPEAT_BINS; c++) bins[c] = (int64_t)s->hist[c];
   return MHAP_OK;
@@ -409,24 +399,13 @@ extern "C" int mhap_repeat_apply(mhap_repeat_session* s, const mhap_record* in, 
   const char* who = "mhap_repeat_apply";
   if (!s) return MHAP_E_INVALID;
   HandleView v = handle_view(s->h);
-  if (!s->finished) { *v.err = std::string(who) + ": no mhap_repeat_finish has completed"; return MHAP_E_INVALID; }
-  if (n < 0 || (n > 0 && (!in || !keep || !unique))) { *v.err = std::string(who) + ": null or negative argument"; return MHAP_E_INVALID; }
-  if (n > INT32_MAX) { *v.err = std::string(who) + ": more than 2^31 - 1 records in one call"; return MHAP_E_INVALID; }
-  if (n == 0) return MHAP_OK;
   std::vector<GItem> items;
-  int rc = MHAP_OK;
-  if (!s->upload_for_apply(v, who, in, n, items, rc)) return rc;
-  hipError_t e;
-  if ((e = s->judged.ensure(16 * (size_t)n)) != hipSuccess) { (void)hipStreamSynchronize(v.stream); return hip_fail(v, who, "hipMalloc of the records", e); }
+  int rc = apply_begin(s, v, who, in, n, keep && unique, items, s->judged, 16 * (size_t)n, "hipMalloc of the records");
+  if (rc != MHAP_OK || n == 0) return rc;
   hipLaunchKernelGGL(judge_kernel, dim3(blocks256(n)), dim3(256), 0, v.stream, s->items.as<int4>(), n, s->offsets.as<int64_t>(), s->iv.as<int2>(),
                      s->cum.as<int32_t>(), s->E, s->P.min_unique, s->judged.as<int4>());
-  if ((e = hipGetLastError()) != hipSuccess) { (void)hipStreamSynchronize(v.stream); return hip_fail(v, who, "launch", e); }
   std::vector<int32_t> got(4 * (size_t)n);
-  if ((e = hipMemcpyAsync(got.data(), s->judged.p, 16 * (size_t)n, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) {
-    (void)hipStreamSynchronize(v.stream);
-    return hip_fail(v, who, "download", e);
-  }
-  if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return hip_fail(v, who, "kernel", e);
+  if ((rc = apply_end(v, who, got.data(), s->judged, 16 * (size_t)n)) != MHAP_OK) return rc;
   for (int64_t q = 0; q < n; q++) {
     keep[q] = (uint8_t)got[4 * (size_t)q];
     unique[2 * q] = got[4 * (size_t)q + 1];
@@ -466,12 +445,4 @@ extern "C" int mhap_repeat_judge_record(const mhap_record* in, const int32_t* in
   return !el || (u[0] >= p.min_unique && u[1] >= p.min_unique) ? 1 : 0;
 }
 
-extern "C" void mhap_repeat_free(mhap_repeat_session* s) {
-  if (!s) return;
-  HandleView v = handle_view(s->h);
-  (void)hipSetDevice(v.device);
-  (void)hipStreamSynchronize(v.stream);
-  s->reap(true);
-  s->release();
-  delete s;
-}
+extern "C" void mhap_repeat_free(mhap_repeat_session* s) { session_free(s); }

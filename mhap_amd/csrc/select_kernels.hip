@@ -1,8 +1,8 @@
 // select_kernels.hip — overlap selection: every read keeps the best_n views with the greatest keys (mhap_select_begin / _add / _finish /
 // _copy / _apply / _judge_record / _free).  The contract — eligible records, the two views of a record, the key, the threshold and
 // the per-read row — is the prose of include/mhap_hip.h ("overlap selection"); tests/select_ref.py restates it.  The key is
-// select_common.hpp's, the table of reads and the record checks are pileup_common.hpp's ReadTable, shared with the trimming and the
-// repeat marking; no per-base array exists here.
+// select_common.hpp's; the table of reads, the record checks and the begin / apply / free of a session are read_table.hpp's, shared
+// with the trimming and the repeat marking; no per-base array exists here.
 //
 // add:    entry_kernel, one lane per record: the record's two entries {read or -1, key} go to the fixed slots 2 (records so far + q)
 //         and + 1 in one 16-byte store, and count[read] takes an atomicAdd of 1 per entry.  Nothing waits (but the entries' buffer
@@ -26,7 +26,7 @@
 #include "device_common.hpp"
 #include "graph_class.hpp"
 #include "mhap_internal.hpp"
-#include "pileup_common.hpp"
+#include "read_table.hpp"
 #include "select_common.hpp"
 
 namespace mhap {
@@ -205,6 +205,8 @@ bool params_ok(const mhap_select_params& p) { return p.best_n >= 1 && p.min_span
 using namespace mhap;
 
 struct mhap_select_session : ReadTable {
+  static constexpr const char* finish_name = "mhap_select_finish";
+  static constexpr int unfinished_rc = MHAP_E_STATE;
   SParams P{};
   bool finished = false;
   int grid = 1;   // the workgroups of select_kernel
@@ -222,39 +224,25 @@ extern "C" void mhap_select_default_params(mhap_select_params* p) {
 
 extern "C" int mhap_select_begin(mhap_handle* h, const int64_t* read_ids, const int32_t* lengths, int64_t n_reads, const mhap_select_params* params,
                                  mhap_select_session** session) {
-  const char* who = "mhap_select_begin";
-  if (session) *session = nullptr;
-  if (!h) return MHAP_E_INVALID;
-  HandleView v = handle_view(h);
-  if (!ReadTable::table_ok(v, who, session, read_ids, lengths, n_reads)) return MHAP_E_INVALID;
-  mhap_select_params p;
-  mhap_select_default_params(&p);
-  if (params) p = *params;
-  if (!params_ok(p)) { *v.err = std::string(who) + ": best_n must be >= 1 and min_span >= 0"; return MHAP_E_INVALID; }
-  mhap_select_session* s = new mhap_select_session();
-  s->P = SParams{p.best_n, p.min_span, p.min_identity};
-  s->grid = std::max(1, v.num_cus) * 4;
-  (void)hipSetDevice(v.device);
-  const size_t nr = (size_t)std::max<int64_t>(n_reads, 1);
-  hipError_t e = s->begin_table(v, h, read_ids, lengths, n_reads);
-  if (e == hipSuccess) e = s->count.ensure(4 * nr);
-  if (e == hipSuccess) e = s->offsets.ensure(8 * (nr + 1));
-  if (e == hipSuccess) e = s->cursor.ensure(4 * nr);
-  if (e == hipSuccess) e = s->rows.ensure(16 * nr);
-  if (e == hipSuccess) e = s->work.ensure(4 * nr);
-  if (e == hipSuccess) e = s->n_work.ensure(4);
-  if (e == hipSuccess) e = s->counts.ensure(8 * MHAP_SELECT_COUNTS);
-  if (e == hipSuccess) e = hipMemsetAsync(s->counts.p, 0, 8 * MHAP_SELECT_COUNTS, v.stream);
-  if (e == hipSuccess) e = hipMemsetAsync(s->count.p, 0, 4 * nr, v.stream);
-  if (e == hipSuccess) e = hipMemsetAsync(s->offsets.p, 0, 8 * (nr + 1), v.stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(v.stream);
-  if (e != hipSuccess) {
-    s->release();
-    delete s;
-    return hip_fail(v, who, "the table of reads", e);
-  }
-  *session = s;
-  return MHAP_OK;
+  return session_begin("mhap_select_begin", h, read_ids, lengths, n_reads, params, mhap_select_default_params, params_ok,
+                       "best_n must be >= 1 and min_span >= 0", session,
+                       [&](mhap_select_session& s, const mhap_select_params& p, const HandleView& v) {
+    s.P = SParams{p.best_n, p.min_span, p.min_identity};
+    s.grid = std::max(1, v.num_cus) * 4;
+    const size_t nr = (size_t)std::max<int64_t>(n_reads, 1);
+    Steps q{s.begin_table(v, h, read_ids, lengths, n_reads), v.stream};
+    q.ensure(s.count, 4 * nr);
+    q.ensure(s.offsets, 8 * (nr + 1));
+    q.ensure(s.cursor, 4 * nr);
+    q.ensure(s.rows, 16 * nr);
+    q.ensure(s.work, 4 * nr);
+    q.ensure(s.n_work, 4);
+    q.ensure(s.counts, 8 * MHAP_SELECT_COUNTS);
+    q.zero(s.counts, 8 * MHAP_SELECT_COUNTS);
+    q.zero(s.count, 4 * nr);
+    q.zero(s.offsets, 8 * (nr + 1));
+    return q.e;
+  });
 }
 
 extern "C" int mhap_select_add(mhap_select_session* s, const mhap_record* recs, int64_t n) {
@@ -321,8 +309,8 @@ extern "C" int mhap_select_copy(mhap_select_session* s, int32_t* rows) {
   const char* who = "mhap_select_copy";
   if (!s) return MHAP_E_INVALID;
   HandleView v = handle_view(s->h);
-  if (!s->finished) { *v.err = std::string(who) + ": no mhap_select_finish has completed"; return MHAP_E_STATE; }
-  if (s->n_reads == 0) return MHAP_OK;
+  const int rc = check_finished(s, v, who);
+  if (rc != MHAP_OK || s->n_reads == 0) return rc;
   if (!rows) { *v.err = std::string(who) + ": null argument"; return MHAP_E_INVALID; }
   return s->download(who, rows, s->rows.p, 16 * (size_t)s->n_reads);
 }
@@ -331,24 +319,12 @@ extern "C" int mhap_select_apply(mhap_select_session* s, const mhap_record* in, 
   const char* who = "mhap_select_apply";
   if (!s) return MHAP_E_INVALID;
   HandleView v = handle_view(s->h);
-  if (!s->finished) { *v.err = std::string(who) + ": no mhap_select_finish has completed"; return MHAP_E_STATE; }
-  if (n < 0 || (n > 0 && (!in || !views))) { *v.err = std::string(who) + ": null or negative argument"; return MHAP_E_INVALID; }
-  if (n > INT32_MAX) { *v.err = std::string(who) + ": more than 2^31 - 1 records in one call"; return MHAP_E_INVALID; }
-  if (n == 0) return MHAP_OK;
   std::vector<GItem> items;
-  int rc = MHAP_OK;
-  if (!s->upload_for_apply(v, who, in, n, items, rc)) return rc;
-  hipError_t e;
-  if ((e = s->views.ensure((size_t)n)) != hipSuccess) { (void)hipStreamSynchronize(v.stream); return hip_fail(v, who, "hipMalloc of the views", e); }
+  const int rc = apply_begin(s, v, who, in, n, views != nullptr, items, s->views, (size_t)n, "hipMalloc of the views");
+  if (rc != MHAP_OK || n == 0) return rc;
   hipLaunchKernelGGL(view_kernel, dim3(blocks256(n)), dim3(256), 0, v.stream, s->items.as<int4>(), n, s->n_reads, s->P, s->rows.as<int32_t>(),
                      s->views.as<uint8_t>());
-  if ((e = hipGetLastError()) != hipSuccess) { (void)hipStreamSynchronize(v.stream); return hip_fail(v, who, "launch", e); }
-  if ((e = hipMemcpyAsync(views, s->views.p, (size_t)n, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) {
-    (void)hipStreamSynchronize(v.stream);
-    return hip_fail(v, who, "download", e);
-  }
-  if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return hip_fail(v, who, "kernel", e);
-  return MHAP_OK;
+  return apply_end(v, who, views, s->views, (size_t)n);   // (a view byte is what the kernel wrote: nothing to unpack)
 }
 
 extern "C" int mhap_select_judge_record(const mhap_record* in, const mhap_select_params* params, uint32_t* keys) {
@@ -365,12 +341,4 @@ extern "C" int mhap_select_judge_record(const mhap_record* in, const mhap_select
   return 1;
 }
 
-extern "C" void mhap_select_free(mhap_select_session* s) {
-  if (!s) return;
-  HandleView v = handle_view(s->h);
-  (void)hipSetDevice(v.device);
-  (void)hipStreamSynchronize(v.stream);
-  s->reap(true);
-  s->release();
-  delete s;
-}
+extern "C" void mhap_select_free(mhap_select_session* s) { session_free(s); }

@@ -190,6 +190,8 @@ __global__ __launch_bounds__(256) void refine_kernel(const RItem* __restrict__ i
 using namespace mhap;
 
 struct mhap_trim_session : Pile {
+  static constexpr const char* finish_name = "mhap_trim_finish";
+  static constexpr int unfinished_rc = MHAP_E_INVALID;
   TParams P{};
   bool finished = false;
   DevBuf rows, flags, counts, applied;   // counts: MHAP_TRIM_COUNTS x uint64
@@ -212,32 +214,18 @@ extern "C" void mhap_trim_default_params(mhap_trim_params* p) {
 
 extern "C" int mhap_trim_begin(mhap_handle* h, const int64_t* read_ids, const int32_t* lengths, int64_t n_reads, const mhap_trim_params* params,
                                mhap_trim_session** session) {
-  const char* who = "mhap_trim_begin";
-  if (session) *session = nullptr;
-  if (!h) return MHAP_E_INVALID;
-  HandleView v = handle_view(h);
-  if (!Pile::table_ok(v, who, session, read_ids, lengths, n_reads)) return MHAP_E_INVALID;
-  mhap_trim_params p;
-  mhap_trim_default_params(&p);
-  if (params) p = *params;
-  if (!params_ok(p)) { *v.err = std::string(who) + ": min_cov must be >= 1, end_clip and min_span >= 0"; return MHAP_E_INVALID; }
-  mhap_trim_session* s = new mhap_trim_session();
-  s->P = TParams{p.min_cov, p.end_clip, p.min_span, p.min_identity};
-  (void)hipSetDevice(v.device);
-  const size_t nr = (size_t)std::max<int64_t>(n_reads, 1);
-  hipError_t e = s->begin_pile(v, h, read_ids, lengths, n_reads);
-  if (e == hipSuccess) e = s->rows.ensure(16 * nr);
-  if (e == hipSuccess) e = s->flags.ensure(nr);
-  if (e == hipSuccess) e = s->counts.ensure(8 * MHAP_TRIM_COUNTS);
-  if (e == hipSuccess) e = hipMemsetAsync(s->counts.p, 0, 8 * MHAP_TRIM_COUNTS, v.stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(v.stream);
-  if (e != hipSuccess) {
-    s->release();
-    delete s;
-    return hip_fail(v, who, "the table of reads", e);
-  }
-  *session = s;
-  return MHAP_OK;
+  return session_begin("mhap_trim_begin", h, read_ids, lengths, n_reads, params, mhap_trim_default_params, params_ok,
+                       "min_cov must be >= 1, end_clip and min_span >= 0", session,
+                       [&](mhap_trim_session& s, const mhap_trim_params& p, const HandleView& v) {
+    s.P = TParams{p.min_cov, p.end_clip, p.min_span, p.min_identity};
+    const size_t nr = (size_t)std::max<int64_t>(n_reads, 1);
+    Steps q{s.begin_pile(v, h, read_ids, lengths, n_reads), v.stream};
+    q.ensure(s.rows, 16 * nr);
+    q.ensure(s.flags, nr);
+    q.ensure(s.counts, 8 * MHAP_TRIM_COUNTS);
+    q.zero(s.counts, 8 * MHAP_TRIM_COUNTS);
+    return q.e;
+  });
 }
 
 extern "C" int mhap_trim_add(mhap_trim_session* s, const mhap_record* recs, int64_t n) {
@@ -277,10 +265,10 @@ extern "C" int mhap_trim_copy(mhap_trim_session* s, int32_t* rows, uint8_t* flag
   const char* who = "mhap_trim_copy";
   if (!s) return MHAP_E_INVALID;
   HandleView v = handle_view(s->h);
-  if (!s->finished) { *v.err = std::string(who) + ": no mhap_trim_finish has completed"; return MHAP_E_INVALID; }
-  if (s->n_reads == 0) return MHAP_OK;
+  int rc = check_finished(s, v, who);
+  if (rc != MHAP_OK || s->n_reads == 0) return rc;
   if (!rows || !flags) { *v.err = std::string(who) + ": null argument"; return MHAP_E_INVALID; }
-  const int rc = s->download(who, rows, s->rows.p, 16 * (size_t)s->n_reads);
+  rc = s->download(who, rows, s->rows.p, 16 * (size_t)s->n_reads);
   return rc != MHAP_OK ? rc : s->download(who, flags, s->flags.p, (size_t)s->n_reads);
 }
 
@@ -302,24 +290,13 @@ extern "C" int mhap_trim_apply(mhap_trim_session* s, const mhap_record* in, int6
   const char* who = "mhap_trim_apply";
   if (!s) return MHAP_E_INVALID;
   HandleView v = handle_view(s->h);
-  if (!s->finished) { *v.err = std::string(who) + ": no mhap_trim_finish has completed"; return MHAP_E_INVALID; }
-  if (n < 0 || (n > 0 && (!in || !out || !keep))) { *v.err = std::string(who) + ": null or negative argument"; return MHAP_E_INVALID; }
-  if (n > INT32_MAX) { *v.err = std::string(who) + ": more than 2^31 - 1 records in one call"; return MHAP_E_INVALID; }
-  if (n == 0) return MHAP_OK;
   std::vector<GItem> items;
-  int rc = MHAP_OK;
-  if (!s->upload_for_apply(v, who, in, n, items, rc)) return rc;
-  hipError_t e;
-  if ((e = s->applied.ensure(32 * (size_t)n)) != hipSuccess) { (void)hipStreamSynchronize(v.stream); return hip_fail(v, who, "hipMalloc of the records", e); }
+  int rc = apply_begin(s, v, who, in, n, out && keep, items, s->applied, 32 * (size_t)n, "hipMalloc of the records");
+  if (rc != MHAP_OK || n == 0) return rc;
   hipLaunchKernelGGL(apply_kernel, dim3(blocks256(n)), dim3(256), 0, v.stream, s->items.as<int4>(), n, s->d_lengths.as<int32_t>(),
                      s->rows.as<int32_t>(), s->flags.as<uint8_t>(), s->P, s->applied.as<int4>());
-  if ((e = hipGetLastError()) != hipSuccess) { (void)hipStreamSynchronize(v.stream); return hip_fail(v, who, "launch", e); }
   std::vector<int32_t> got(8 * (size_t)n);
-  if ((e = hipMemcpyAsync(got.data(), s->applied.p, 32 * (size_t)n, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) {
-    (void)hipStreamSynchronize(v.stream);
-    return hip_fail(v, who, "download", e);
-  }
-  if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return hip_fail(v, who, "kernel", e);
+  if ((rc = apply_end(v, who, got.data(), s->applied, 32 * (size_t)n)) != MHAP_OK) return rc;
   for (int64_t q = 0; q < n; q++) {
     const int32_t* g = got.data() + 8 * (size_t)q;
     out[q] = in[q];
@@ -409,12 +386,4 @@ extern "C" int mhap_trim_refine(mhap_handle* h, const mhap_record* recs, int64_t
   return MHAP_OK;
 }
 
-extern "C" void mhap_trim_free(mhap_trim_session* s) {
-  if (!s) return;
-  HandleView v = handle_view(s->h);
-  (void)hipSetDevice(v.device);
-  (void)hipStreamSynchronize(v.stream);
-  s->reap(true);
-  s->release();
-  delete s;
-}
+extern "C" void mhap_trim_free(mhap_trim_session* s) { session_free(s); }
