@@ -1539,7 +1539,7 @@ struct W1Args {
   const uint64_t* jump; const uint64_t* unjump; int jump_na;
   uint32_t* qbuf; int qcap;          // the waves' candidate queues: qcap words each (minhash_queue_words)
   unsigned long long* merge;         // n_tail x H words, filled with 0xFF: minima of the row items, sign bit flipped (unsigned order)
-  unsigned long long* prof;          // MHAP_MINHASH_PROF: wave-clock sums {key load + transpose, first-row slots, later-row slots, drains, rows, first rows, candidates}
+  unsigned long long* prof;          // MHAP_MINHASH_PROF: wave-clock sums {key load + transpose, first-row slots, later-row slots, drains, rows, first rows, sub-block entries}
   int stagger;                       // clocks a wave waits before its first item, times its slot number on its SIMD (mod 4): minhash_w1_kernel
 };
 
@@ -1581,13 +1581,27 @@ __device__ __forceinline__ uint64_t w1_key_of(uint64_t x, int n, const uint64_t*
 //     chains carry key 0 = chain value 0 for ever = never negative, so no mask of active chains is needed), and a scalar switch on the
 //     slot's depth class (one v_readlane per step) adds the planes 9..13 its depth allows with one to three more VGPR-only ops;
 //     a slot without a usable minimum (fewer than eight leading zero bits) takes the exact masked filter — rare;
-//   * a triggered step appends ONE 8-byte entry per lane that has candidates — its whole 32-chain candidate mask + (slot, lane) —
-//     at the position the trigger's own ballot gives it (two v_mbcnt on the scalar fill count); no per-bit loop, no v_ffbl, no
+//   * an append writes ONE 8-byte entry per lane that has candidates — its whole 32-chain candidate mask + (slot, lane) —
+//     at the position the append's own ballot gives it (two v_mbcnt on the scalar fill count); no per-bit loop, no v_ffbl, no
 //     second ballot, no bounds branch (the index is clamped to a spare last entry and the running count says "overflow");
-//   * the drain takes the lowest chain of every entry and re-queues what is left of a multi-chain mask (one entry in a hundred).
+//   * the drain takes the lowest chain of every entry and re-queues what is left of a multi-chain mask.
 // (The round-3/4 loop this replaced is in the history of this file: commit e70836d keeps both.)
+// Block-deferred candidates: per entry the drain (64 entries side by side, one per lane) is an order of magnitude cheaper than the append (a
+// wave-wide sequence — two v_mbcnt for the position, two for the lane id, clamp, assembly, a global store, the scalar count — that serves 1.4
+// entries), so a step no longer appends.  The slots are cut into sub-blocks of W1_DEFER (never across a 64-slot class block); a step folds its
+// filter word into a per-lane accumulator with one VALU op, and the sub-block's end does ONE ballot and one append of (accumulated chain mask,
+// the sub-block's first slot, lane).  The drain steps the entry's chain through the sub-block's slots and offers it to each.  Exact all the
+// same: whatever is offered to a slot is a chain value of one of the strand's own k-mers AT that slot, and every true minimum still passes
+// the unchanged filter at its own slot, so its chain is in the sub-block's mask.  (Sub-blocks of 4 / 8 / 16 slots measured 71.7 / 72.1 / 73.0 ms
+// at C2 against 73.9 with an append per step: the drain's walk, not the appends saved, decides — EXPERIMENTS, profiles/blockdefer_ab.txt.)
+#ifndef MH_W1_DEFER_BLOCK
+#define MH_W1_DEFER_BLOCK 4
+#endif
+constexpr int W1_DEFER = MH_W1_DEFER_BLOCK;
+static_assert(W1_DEFER >= 1 && 64 % W1_DEFER == 0, "sub-blocks never straddle a 64-slot class block");
+static_assert(W1_DEFER % (1 << XS_JUMP_LOG2) == 0, "a sub-block starts where the jump tables land (w1_flush2)");
 // (8-byte entries in the wave's window of qcap words: wcap = qcap / 2 - 1 of them, entry wcap — the window's last — is the spare one overflowing appends land in)
-// append the lanes' candidate masks (cand != 0 somewhere in the wave, m = its ballot)
+// append the lanes' candidate masks of one sub-block (cand != 0 somewhere in the wave, m = its ballot; head = the sub-block's first slot)
 __device__ __forceinline__ void w1_enqueue(uint2* __restrict__ q, int& qn, int wcap, uint32_t head, uint32_t cand, unsigned long long m) {
   if (cand) {
     uint32_t idx = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, (uint32_t)qn));
@@ -1599,11 +1613,11 @@ __device__ __forceinline__ void w1_enqueue(uint2* __restrict__ q, int& qn, int w
   qn += __popcll(m);
 }
 
-// drain: entry = (candidate mask of one lane, slot | lane << 16); chain value recomputed from the key, slot minimum lowered
+// drain: entry = (candidate mask of one lane, first slot of the sub-block | lane << 16); chain value recomputed from the key, the sub-block's slot minima lowered
 // Returns false when the re-queued rests of multi-chain masks did not fit the queue: the row's own count fitted (the caller checked it), but a
 // rest is appended BEHIND it — with the count close to the capacity (a first row at --num-hashes 1024 queues about 2 048 entries) rests were
 // dropped silently; found by the fuzz sweep on the 31-entry variant build (round 5).  The caller redoes the strand exactly.
-__device__ __forceinline__ bool w1_flush2(int64_t* best, uint2* __restrict__ q, int qn, int wcap, int rb, const KeySrc& ks,
+__device__ __forceinline__ bool w1_flush2(int64_t* best, uint2* __restrict__ q, int qn, int wcap, int rb, int H, const KeySrc& ks,
                                           const uint64_t* __restrict__ jump, int lane) {
   bool fits = true;
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");   // the queue stores have left the wave before its lanes read each other's entries
@@ -1617,9 +1631,8 @@ __device__ __forceinline__ bool w1_flush2(int64_t* best, uint2* __restrict__ q, 
       ehi = e.y;
       const int j = __builtin_ctz(e.x), l = (int)(e.y >> 16), s = (int)(e.y & 0xFFFFu);
       rest = e.x & (e.x - 1u);
-      const int nsteps = s + 1;
-      int a = nsteps >> XS_JUMP_LOG2;
-      const int r = nsteps & ((1 << XS_JUMP_LOG2) - 1);
+      // s is a multiple of W1_DEFER and so of the tables' stride: the tables take the chain to step s, ONE single step to the first slot's value
+      int a = s >> XS_JUMP_LOG2;
       const int qa = a > W1_JUMP_NA ? (a - 1) / W1_JUMP_NA : 0;      // two levels of tables, as in w1_flush
       a -= qa * W1_JUMP_NA;
       uint64_t x = ks_key(ks, rb + j * 64 + l);
@@ -1637,11 +1650,27 @@ __device__ __forceinline__ bool w1_flush2(int64_t* best, uint2* __restrict__ q, 
         for (int i = 0; i < 8; i++) y ^= jump[tb + (uint32_t)(i * 256) + ((uint32_t)(x >> (8 * i)) & 255u)];
         x = y;
       }
+      x = xorshift_step(x);
+      // x is the chain's value at the sub-block's first slot; offered to every slot of the sub-block, one more step each.  The atomic runs
+      // only where the high dword is not above the slot's current one (a stale read is never too low: minima only fall, so it costs an
+      // atomic, not a minimum)
+      const int32_t* besthi = (const int32_t*)best + 2 * s + 1;
+      if (s + W1_DEFER <= H) {   // a whole sub-block: its minima's high dwords in one go, then the steps
+        int32_t bh[W1_DEFER];
 #pragma unroll
-      for (int t = 0; t < (1 << XS_JUMP_LOG2) - 1; t++) { const uint64_t nx = xorshift_step(x); x = (t < r) ? nx : x; }
-      atomicMin((long long*)&best[s], (long long)x);
+        for (int i = 0; i < W1_DEFER; i++) bh[i] = besthi[2 * i];
+#pragma unroll
+        for (int i = 0; i < W1_DEFER; i++) {
+          if ((int32_t)(x >> 32) <= bh[i]) atomicMin((long long*)&best[s + i], (long long)x);
+          if (i + 1 < W1_DEFER) x = xorshift_step(x);
+        }
+      } else                     // the row's last sub-block, cut by H
+        for (int i = 0; i < H - s; i++) {
+          if ((int32_t)(x >> 32) <= besthi[2 * i]) atomicMin((long long*)&best[s + i], (long long)x);
+          x = xorshift_step(x);
+        }
     }
-    // what is left of a multi-chain mask goes to the end of the queue (rare: two candidates of one step in one lane)
+    // what is left of a multi-chain mask goes to the end of the queue (two candidate chains of one sub-block in one lane)
     const unsigned long long m2 = __ballot(rest != 0u);
     if (m2) {
       // (behind the entries this trip covers: an append into the last, partly filled trip would land on lanes that have already run)
@@ -1699,14 +1728,20 @@ __device__ __forceinline__ void w1_row2(int64_t* best, uint2* __restrict__ q, in
   int qn = 0;   // queue fill (wave-uniform)
   const unsigned long long t1 = MHAP_TICK();
   if (first) {
-    for (int s = 0; s < H; s++) {
-      bs_step(P);
-      // the nine-plane shortcut of bs_argmin in line, its ballot serving both the "anyone?" test and the enqueue; the plane walk (one
-      // step in seven) is the out-of-line side
-      uint32_t cand = bs_argmin_pre(P, ACT);
-      unsigned long long m = __ballot(cand != 0u);
-      if (__builtin_expect(m == 0ULL, 0)) { cand = bs_argmin_walk(P, ACT); m = __ballot(cand != 0u); }
-      w1_enqueue(q, qn, wcap, (uint32_t)s, cand, m);
+    for (int sb = 0; sb < H; sb += W1_DEFER) {
+      int se = sb + W1_DEFER;
+      if (se > H) se = H;
+      se = __builtin_amdgcn_readfirstlane(se);
+      uint32_t acc = 0u;   // the sub-block's candidate chains of this lane (alive inside the sub-block only)
+      for (int s = sb; s < se; s++) {
+        bs_step(P);
+        // the nine-plane shortcut of bs_argmin in line, its ballot only deciding whether the plane walk (one step in seven, the out-of-line
+        // side) runs
+        uint32_t cand = bs_argmin_pre(P, ACT);
+        if (__builtin_expect(__ballot(cand != 0u) == 0ULL, 0)) cand = bs_argmin_walk(P, ACT);
+        acc |= cand;
+      }
+      w1_enqueue(q, qn, wcap, (uint32_t)sb, acc, __ballot(acc != 0u));
     }
   } else {
     const int32_t* besthi = (const int32_t*)best;
@@ -1720,101 +1755,108 @@ __device__ __forceinline__ void w1_row2(int64_t* best, uint2* __restrict__ q, in
       int send = s0 + 64;   // (scalar loop bound: written as a select it became v_med3 and a VALU compare per step)
       if (send > H) send = H;
       send = __builtin_amdgcn_readfirstlane(send);
-      for (int sl = s0; sl < send; sl++) {
-        const int t = sl - s0;
-        const int cls = __builtin_amdgcn_readlane(vcls, t);
-        bs_step(P);
-        uint32_t n = w1_base_filter(P);
+      for (int sb = s0; sb < send; sb += W1_DEFER) {
+        int se = sb + W1_DEFER;
+        if (se > send) se = send;
+        se = __builtin_amdgcn_readfirstlane(se);
+        uint32_t nacc = 0xFFFFFFFFu;   // AND of the sub-block's filter words: a zero bit = the chain passed a slot's filter (alive inside the sub-block only)
+        for (int sl = sb; sl < se; sl++) {
+          const int t = sl - s0;
+          const int cls = __builtin_amdgcn_readlane(vcls, t);
+          bs_step(P);
+          uint32_t n = w1_base_filter(P);
 #if MH_W1_CLS == 0
-        switch (cls) {
-          case 1: break;
-          case 2: n |= P[54]; break;
-          case 3: n = __builtin_amdgcn_bitop3_b32(n, P[54], P[53], BS_TT_OR3); break;
-          case 4: n = __builtin_amdgcn_bitop3_b32(n, P[54], P[53], BS_TT_OR3) | P[52]; break;
-          case 5: n = __builtin_amdgcn_bitop3_b32(__builtin_amdgcn_bitop3_b32(n, P[54], P[53], BS_TT_OR3), P[52], P[51], BS_TT_OR3); break;
-          case 6: n = __builtin_amdgcn_bitop3_b32(__builtin_amdgcn_bitop3_b32(n, P[54], P[53], BS_TT_OR3), P[52], P[51], BS_TT_OR3) | P[50]; break;
-          default: n = w1_exact_filter(P, besthi[2 * sl + 1], nk - rb); break;
-        }
-#elif MH_W1_CLS == 1
-        if (__builtin_expect(cls >= 3, 1)) {
-          n = __builtin_amdgcn_bitop3_b32(n, P[54], P[53], BS_TT_OR3);
-          if (cls >= 5) {
-            n = __builtin_amdgcn_bitop3_b32(n, P[52], P[51], BS_TT_OR3);
-            if (cls >= 6) n |= P[50];
-          } else if (cls == 4) n |= P[52];
-        } else if (cls == 2) n |= P[54];
-        else if (__builtin_expect(cls == 0, 0)) n = w1_exact_filter(P, besthi[2 * sl + 1], nk - rb);   // no usable minimum yet: the exact filter of the slot's depth
-#elif MH_W1_CLS == 2
-        // The class selects code through a short chain of scalar compares, deepest classes first (the common ones from the third row on),
-        // written out in assembly: the compiler lowers the equivalent `switch` / if-chain through its control-flow structurizer — a compare
-        // tree with "which way did I come" flags in SGPR pairs, 11 to 16 scalar instructions a step (and selects in place of the
-        // innermost branches); this is 6 or 7.  (One asm statement, branches local to it; classes 1..6 add the planes 9..13.)
-        asm volatile(
-            "s_cmp_lt_i32 %[c], 3\n\t"
-            "s_cbranch_scc1 1f\n\t"
-            "v_bitop3_b32 %[n], %[n], %[p54], %[p53] bitop3:0xfe\n\t"
-            "s_cmp_lt_i32 %[c], 5\n\t"
-            "s_cbranch_scc1 2f\n\t"
-            "v_bitop3_b32 %[n], %[n], %[p52], %[p51] bitop3:0xfe\n\t"
-            "s_cmp_lt_i32 %[c], 6\n\t"
-            "s_cbranch_scc1 3f\n\t"
-            "v_or_b32 %[n], %[n], %[p50]\n\t"
-            "s_branch 3f\n"
-            "2:\n\t"
-            "s_cmp_lt_i32 %[c], 4\n\t"
-            "s_cbranch_scc1 3f\n\t"
-            "v_or_b32 %[n], %[n], %[p52]\n\t"
-            "s_branch 3f\n"
-            "1:\n\t"
-            "s_cmp_lt_i32 %[c], 2\n\t"
-            "s_cbranch_scc1 3f\n\t"
-            "v_or_b32 %[n], %[n], %[p54]\n"
-            "3:\n"
-            : [n] "+v"(n)
-            : [c] "s"(cls), [p54] "v"(P[54]), [p53] "v"(P[53]), [p52] "v"(P[52]), [p51] "v"(P[51]), [p50] "v"(P[50])
-            : "scc");
-        if (__builtin_expect(cls == 0, 0)) n = w1_exact_filter(P, besthi[2 * sl + 1], nk - rb);   // no usable minimum yet: the exact filter of the slot's depth
-#else
-        // as 2, with the deepest classes (from the third row on the most frequent) on the straightest path: one C branch sends the
-        // classes 0..2 out of line, the assembly takes 3..6 in four scalar instructions
-        if (__builtin_expect(cls < 3, 0)) {
-          if (cls == 2) n |= P[54];
-          else if (cls == 0) {   // no usable minimum yet: the exact filter of the slot's depth
-            int so;   // (the slot index through an opaque copy: otherwise the address of its minimum is strength-reduced into one more
-                      //  scalar add in EVERY step of the loop, for a path one step in a thousand takes)
-            asm volatile("s_mov_b32 %0, %1" : "=s"(so) : "s"(sl));
-            n = w1_exact_filter(P, besthi[2 * so + 1], nk - rb);
+          switch (cls) {
+            case 1: break;
+            case 2: n |= P[54]; break;
+            case 3: n = __builtin_amdgcn_bitop3_b32(n, P[54], P[53], BS_TT_OR3); break;
+            case 4: n = __builtin_amdgcn_bitop3_b32(n, P[54], P[53], BS_TT_OR3) | P[52]; break;
+            case 5: n = __builtin_amdgcn_bitop3_b32(__builtin_amdgcn_bitop3_b32(n, P[54], P[53], BS_TT_OR3), P[52], P[51], BS_TT_OR3); break;
+            case 6: n = __builtin_amdgcn_bitop3_b32(__builtin_amdgcn_bitop3_b32(n, P[54], P[53], BS_TT_OR3), P[52], P[51], BS_TT_OR3) | P[50]; break;
+            default: n = w1_exact_filter(P, besthi[2 * sl + 1], nk - rb); break;
           }
-        } else {
-          uint32_t o;   // (a result register of its own: tied to n the compiler copies n first, for the other path's sake)
+#elif MH_W1_CLS == 1
+          if (__builtin_expect(cls >= 3, 1)) {
+            n = __builtin_amdgcn_bitop3_b32(n, P[54], P[53], BS_TT_OR3);
+            if (cls >= 5) {
+              n = __builtin_amdgcn_bitop3_b32(n, P[52], P[51], BS_TT_OR3);
+              if (cls >= 6) n |= P[50];
+            } else if (cls == 4) n |= P[52];
+          } else if (cls == 2) n |= P[54];
+          else if (__builtin_expect(cls == 0, 0)) n = w1_exact_filter(P, besthi[2 * sl + 1], nk - rb);   // no usable minimum yet: the exact filter of the slot's depth
+#elif MH_W1_CLS == 2
+          // The class selects code through a short chain of scalar compares, deepest classes first (the common ones from the third row on),
+          // written out in assembly: the compiler lowers the equivalent `switch` / if-chain through its control-flow structurizer — a compare
+          // tree with "which way did I come" flags in SGPR pairs, 11 to 16 scalar instructions a step (and selects in place of the
+          // innermost branches); this is 6 or 7.  (One asm statement, branches local to it; classes 1..6 add the planes 9..13.)
           asm volatile(
-              "v_bitop3_b32 %[o], %[n], %[p54], %[p53] bitop3:0xfe\n\t"
+              "s_cmp_lt_i32 %[c], 3\n\t"
+              "s_cbranch_scc1 1f\n\t"
+              "v_bitop3_b32 %[n], %[n], %[p54], %[p53] bitop3:0xfe\n\t"
               "s_cmp_lt_i32 %[c], 5\n\t"
-              "s_cbranch_scc0 4f\n\t"
-              "s_cmp_lt_i32 %[c], 4\n\t"
-              "s_cbranch_scc1 3f\n\t"
-              "v_or_b32 %[o], %[o], %[p52]\n\t"
-              "s_branch 3f\n"
-              "4:\n\t"
-              "v_bitop3_b32 %[o], %[o], %[p52], %[p51] bitop3:0xfe\n\t"
+              "s_cbranch_scc1 2f\n\t"
+              "v_bitop3_b32 %[n], %[n], %[p52], %[p51] bitop3:0xfe\n\t"
               "s_cmp_lt_i32 %[c], 6\n\t"
               "s_cbranch_scc1 3f\n\t"
-              "v_or_b32 %[o], %[o], %[p50]\n"
+              "v_or_b32 %[n], %[n], %[p50]\n\t"
+              "s_branch 3f\n"
+              "2:\n\t"
+              "s_cmp_lt_i32 %[c], 4\n\t"
+              "s_cbranch_scc1 3f\n\t"
+              "v_or_b32 %[n], %[n], %[p52]\n\t"
+              "s_branch 3f\n"
+              "1:\n\t"
+              "s_cmp_lt_i32 %[c], 2\n\t"
+              "s_cbranch_scc1 3f\n\t"
+              "v_or_b32 %[n], %[n], %[p54]\n"
               "3:\n"
-              : [o] "=&v"(o)
-              : [n] "v"(n), [c] "s"(cls), [p54] "v"(P[54]), [p53] "v"(P[53]), [p52] "v"(P[52]), [p51] "v"(P[51]), [p50] "v"(P[50])
+              : [n] "+v"(n)
+              : [c] "s"(cls), [p54] "v"(P[54]), [p53] "v"(P[53]), [p52] "v"(P[52]), [p51] "v"(P[51]), [p50] "v"(P[50])
               : "scc");
-          n = o;
-        }
+          if (__builtin_expect(cls == 0, 0)) n = w1_exact_filter(P, besthi[2 * sl + 1], nk - rb);   // no usable minimum yet: the exact filter of the slot's depth
+#else
+          // as 2, with the deepest classes (from the third row on the most frequent) on the straightest path: one C branch sends the
+          // classes 0..2 out of line, the assembly takes 3..6 in four scalar instructions
+          if (__builtin_expect(cls < 3, 0)) {
+            if (cls == 2) n |= P[54];
+            else if (cls == 0) {   // no usable minimum yet: the exact filter of the slot's depth
+              int so;   // (the slot index through an opaque copy: otherwise the address of its minimum is strength-reduced into one more
+                        //  scalar add in EVERY step of the loop, for a path one step in a thousand takes)
+              asm volatile("s_mov_b32 %0, %1" : "=s"(so) : "s"(sl));
+              n = w1_exact_filter(P, besthi[2 * so + 1], nk - rb);
+            }
+          } else {
+            uint32_t o;   // (a result register of its own: tied to n the compiler copies n first, for the other path's sake)
+            asm volatile(
+                "v_bitop3_b32 %[o], %[n], %[p54], %[p53] bitop3:0xfe\n\t"
+                "s_cmp_lt_i32 %[c], 5\n\t"
+                "s_cbranch_scc0 4f\n\t"
+                "s_cmp_lt_i32 %[c], 4\n\t"
+                "s_cbranch_scc1 3f\n\t"
+                "v_or_b32 %[o], %[o], %[p52]\n\t"
+                "s_branch 3f\n"
+                "4:\n\t"
+                "v_bitop3_b32 %[o], %[o], %[p52], %[p51] bitop3:0xfe\n\t"
+                "s_cmp_lt_i32 %[c], 6\n\t"
+                "s_cbranch_scc1 3f\n\t"
+                "v_or_b32 %[o], %[o], %[p50]\n"
+                "3:\n"
+                : [o] "=&v"(o)
+                : [n] "v"(n), [c] "s"(cls), [p54] "v"(P[54]), [p53] "v"(P[53]), [p52] "v"(P[52]), [p51] "v"(P[51]), [p50] "v"(P[50])
+                : "scc");
+            n = o;
+          }
 #endif
-        const unsigned long long m = __ballot(n != 0xFFFFFFFFu);
-        if (__builtin_expect(m != 0ULL, 1)) w1_enqueue(q, qn, wcap, (uint32_t)sl, ~n, m);   // (two steps in three trigger: the enqueue is the fall-through side)
+          nacc &= n;   // no ballot, compare or branch per step
+        }
+        const unsigned long long m = __ballot(nacc != 0xFFFFFFFFu);
+        if (__builtin_expect(m != 0ULL, 1)) w1_enqueue(q, qn, wcap, (uint32_t)sb, ~nacc, m);   // (nearly every sub-block has a candidate: the enqueue is the fall-through side)
       }
     }
   }
   if (qn > wcap) ok = false;
   const unsigned long long t2 = MHAP_TICK();
-  if (!w1_flush2(best, q, qn, wcap, rb, ks, jump, lane)) ok = false;
+  if (!w1_flush2(best, q, qn, wcap, rb, H, ks, jump, lane)) ok = false;
   if (PROF) { tp[0] += t1 - t0; tp[first ? 1 : 2] += t2 - t1; tp[3] += MHAP_TICK() - t2; tp[4]++; tp[5] += first ? 1 : 0; tp[6] += (unsigned long long)qn; }
 }
 
@@ -2032,7 +2074,7 @@ int minhash_queue_words(int H) {
   return want > BS_QCAP ? want : BS_QCAP;
 }
 size_t minhash_queue_bytes(int nblocks_total, int H) { return (size_t)nblocks_total * 4 * (size_t)minhash_queue_words(H) * 4; }
-static_assert(MHAP_MAX_NUM_HASHES < 65536, "a weight-1 queue entry is slot | lane << 16 (w1_enqueue)");
+static_assert(MHAP_MAX_NUM_HASHES < 65536, "a weight-1 queue entry is first slot | lane << 16 (w1_enqueue)");
 // waves (= strands in flight) of one MinHash workgroup: launch_minhash's own rule, for whoever sizes per-wave scratch
 int minhash_waves_per_workgroup(int H) {
   const size_t per_wave = (((size_t)H * 12 + 8) + 15) & ~(size_t)15, lut_bytes = (size_t)MH_LUT_WORDS * 8;
@@ -2170,7 +2212,7 @@ bool launch_minhash(hipStream_t st, hipStream_t st_weighted, int nblocks, int64_
         fprintf(stderr, "[minhash w1 prof] launch %.3f ms, %d waves: mean shader clock %.0f MHz (wave-clocks / waves / time)\n", pms, nb * 4,
                 pms > 0.f ? tot / ((double)nb * 4.0) / ((double)pms * 1e3) : 0.0);
         fprintf(stderr, "[minhash w1 prof] rows %llu (first-type %llu)  wave-clocks: total %.3g  key load+transpose %.1f%%  first-row slots %.1f%% (%.0f clocks/step)  "
-                        "later-row slots %.1f%% (%.0f clocks/step)  drains %.1f%%  candidates/row %.0f\n", hp[4], hp[5], tot, 100.0 * hp[0] / tot, 100.0 * hp[1] / tot,
+                        "later-row slots %.1f%% (%.0f clocks/step)  drains %.1f%%  sub-block entries/row %.0f\n", hp[4], hp[5], tot, 100.0 * hp[0] / tot, 100.0 * hp[1] / tot,
                 hp[5] ? (double)hp[1] / ((double)hp[5] * H) : 0.0, 100.0 * hp[2] / tot, hp[4] > hp[5] ? (double)hp[2] / ((double)(hp[4] - hp[5]) * H) : 0.0,
                 100.0 * hp[3] / tot, hp[4] ? (double)hp[6] / (double)hp[4] : 0.0);
       } else
