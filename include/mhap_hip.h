@@ -209,6 +209,67 @@ int mhap_kmer_counts_histogram_size(const mhap_kmer_counts* c, int64_t* n);
 int mhap_kmer_counts_histogram(const mhap_kmer_counts* c, uint32_t* counts, uint64_t* numbers);
 int mhap_kmer_counts_write_histogram(const mhap_kmer_counts* c, const char* path);
 void mhap_kmer_counts_free(mhap_kmer_counts* c);
+/* MHAP_KMER_KEEP_OPEN in the flags of mhap_kmer_count_finish_flags: the counts are made as usual and the count stays open on the
+ * handle (the finish reads the open state and leaves it as it is), so that one count of the reads gives the `-f` file and, from
+ * mhap_kmer_count_finish_set after it, the set below.  A failed finish closes the count with or without it. */
+#define MHAP_KMER_KEEP_OPEN 2
+
+/* Sequence assessment without a reference: sequences (corrected reads, unitigs, a consensus) against the k-mers of the reads they
+ * came from.  A k-mer of a sequence that the reads do not support is an error (from these a consensus QV); a solid k-mer of the
+ * reads that the sequences lack is lost sequence (from these completeness).  Windows, values and canonical are the counter's.
+ *
+ * The set.  mhap_kmer_count_finish_set ends an open count as mhap_kmer_count_finish does and leaves on the device a bitmap of 4^k
+ * bits (512 MiB at k = 16, sized by k alone): bit v is set iff the final count of value v is >= min_count.  min_count 0: the
+ * valley of the count histogram, the smallest c >= 1 with n[c + 1] >= n[c], where n[c] is the number of distinct values counted c
+ * times (0 where absent) - below it lie the k-mers that the reads' errors made.  mhap_kmer_histogram_valley is that rule on the
+ * arrays mhap_kmer_counts_histogram returns (host only; counts ascending and >= 1, else MHAP_E_INVALID).  The set owns its memory,
+ * outlives the count and is used with handles on the device it was made on.  _info: windows counted, distinct values, members (set
+ * bits), k, canonical, the min_count used.  _contains: out[i] = 1 when the set holds values[i].
+ *
+ * Sequences against a set.  For a sequence of n bases and window starts i in [0, n - k]: valid_i as the counter defines it (a
+ * scanned file is upper-cased by the ingest, mhap_kmer_eval_reads takes its bytes as they are), present_i = valid_i and the set holds
+ * the window's value, missing_i = valid_i and it does not.  Every sequence gets a row of five int64: bases = n; windows = the valid
+ * ones; missing = the missing ones; runs = the i with missing_i and (i = 0 or not missing_{i-1}), so an invalid or a present window
+ * ends a run; unsupported = the positions p that some valid window contains and no present window contains.  The intervals are the
+ * maximal stretches [begin, end) of consecutive unsupported positions, as (sequence index, begin, end), ordered by sequence, then
+ * begin.  A sequence shorter than k, or without a valid window, has zeros after `bases`.  Integers only: the results are a function
+ * of the input.  mhap_kmer_eval_scan takes the groups of a scanned file through the streamed ingest and accumulates over them.
+ * _info: sequences, intervals, k and totals[5], the column sums of the rows.  _rows: sequences x 5, _intervals: intervals x 3.
+ *
+ * mhap_kmer_qv: error = 1 - (1 - missing / windows)^(1 / k) per base, qv = -10 log10 of it; windows = 0: NaN for both; missing = 0:
+ * error 0, qv +inf.  mhap_kmer_eval_write_table writes "name\tbases\twindows\tmissing\truns\tunsupported\terror\tqv" per sequence
+ * (error as %.6e, qv as %.2f) and a last line named total; names are NUL-terminated and back to back, as mhap_fasta_scan_info hands
+ * them (NULL: seq1, seq2, ...).  mhap_kmer_eval_write_bed writes "name\tbegin\tend" per interval.  MHAP_E_IO when a file cannot be
+ * written.  mhap_kmer_eval_summary writes the one line both tools print: the totals, the QV and, with the set of the sequences' own
+ * k-mers (own, may be NULL) and `both` from mhap_kmer_set_compare, completeness = both / members of the reads' set.
+ *
+ * Set against set.  mhap_kmer_set_compare counts the members of a, of b and of both; sets that differ in k or canonical are refused
+ * (MHAP_E_INVALID).  Completeness of an assembly: a = the reads' solid set, b = the set of the assembly's own k-mers (count the
+ * assembly, min_count 1).
+ *
+ * Limits: k <= 16 is the counter's; at k = 16 a genome of some hundred megabases fills much of the 4^16 values with its own k-mers, an
+ * erroneous k-mer is then present by chance and the QV saturates - bacterial genomes are the intended use.  Sequences are below 2^31
+ * bases.  With reads at 10 % error a min_count of 1 is nearly useless (the reads' error k-mers excuse the sequences' errors): hence
+ * the valley. */
+typedef struct mhap_kmer_set mhap_kmer_set;
+typedef struct mhap_kmer_eval mhap_kmer_eval;
+int mhap_kmer_histogram_valley(const uint32_t* counts, const uint64_t* numbers, int64_t n, uint64_t* valley);
+int mhap_kmer_qv(int64_t windows, int64_t missing, int32_t k, double* error, double* qv);
+int mhap_kmer_count_finish_set(mhap_handle* h, uint64_t min_count, mhap_kmer_set** out);
+void mhap_kmer_set_free(mhap_kmer_set* s);
+int mhap_kmer_set_info(const mhap_kmer_set* s, int64_t* total, int64_t* distinct, int64_t* members, int32_t* k, int32_t* canonical, uint64_t* min_count);
+int mhap_kmer_set_contains(mhap_handle* h, const mhap_kmer_set* s, const uint64_t* values, int64_t n, uint8_t* out);
+int mhap_kmer_set_compare(mhap_handle* h, const mhap_kmer_set* a, const mhap_kmer_set* b, int64_t* a_members, int64_t* b_members, int64_t* both);
+int mhap_kmer_eval_reads(mhap_handle* h, const mhap_kmer_set* s, const char* bases, const int64_t* offsets, const int32_t* lengths, int64_t n,
+                         mhap_kmer_eval** out);
+int mhap_kmer_eval_scan(mhap_handle* h, const mhap_kmer_set* s, const mhap_fasta_scan* scan, mhap_kmer_eval** out);
+void mhap_kmer_eval_free(mhap_kmer_eval* e);
+int mhap_kmer_eval_info(const mhap_kmer_eval* e, int64_t* sequences, int64_t* intervals, int32_t* k, int64_t* totals);
+int mhap_kmer_eval_rows(const mhap_kmer_eval* e, int64_t* rows);
+int mhap_kmer_eval_intervals(const mhap_kmer_eval* e, int64_t* intervals);
+int mhap_kmer_eval_write_table(const mhap_kmer_eval* e, const char* names, const char* path);
+int mhap_kmer_eval_write_bed(const mhap_kmer_eval* e, const char* names, const char* path);
+int mhap_kmer_eval_summary(const mhap_kmer_eval* e, const mhap_kmer_set* reads, const mhap_kmer_set* own, int64_t both, char* line, size_t cap);
 
 /* Sketch only (no index change); outputs to caller-allocated HOST arrays, any may be NULL:
  * minhash[2n][max(1,H)], ordered[2n][S][2] (hash,pos), ordered_size[2n], status[2n].
@@ -1218,6 +1279,9 @@ int mhap_selftest_xorshift_jump(uint64_t key, int32_t nsteps, uint64_t* out);
 int mhap_selftest_xorshift_unjump(uint64_t x, int32_t nsteps, uint64_t* out);   /* the key nsteps steps before chain value x */
 /* the k-mer counter's window values of one read's bytes: out[i] / valid[i] for the window starting at i (len - k + 1 of each) */
 int mhap_selftest_kmer_windows(const char* seq, int32_t len, int32_t k, int32_t canonical, uint64_t* out, uint8_t* valid);
+/* the lane arithmetic of the sequence evaluation on the host, against a bitmap of 4^k bits in host memory (at least 16 bytes): row[4] =
+ * windows, missing, runs, unsupported; umask (may be NULL): 63 words for every 4032 positions, a bit per unsupported position */
+int mhap_selftest_kmer_eval(const char* seq, int32_t len, int32_t k, int32_t canonical, const uint32_t* bits, int64_t* row, uint64_t* umask);
 /* out8 = {empty, valid(rawScore), a1, a2, b1, b2, inter, k} */
 int mhap_selftest_overlap_lane(const int32_t* A, int32_t nA, int32_t lenA, const int32_t* B, int32_t nB, int32_t lenB,
                                double max_shift, int32_t stride, int32_t* out8);

@@ -15,6 +15,9 @@ from .api import (  # noqa: F401
     FrequencyCounts,
     KmerCounts,
     count_kmers,
+    KmerSet,
+    KmerEval,
+    kmer_histogram_valley,
     MatchResult,
     format_record,
     synth_reads,
@@ -64,4 +67,7 @@ def __getattr__(name):
     if name in ("simulate_pairs", "simulate_reads"):
         from . import kmer_sim
         return getattr(kmer_sim, name)
+    if name == "assess":   # sequence assessment, the same way (`python -m mhap_amd.kmer_qv`)
+        from . import kmer_qv
+        return kmer_qv.assess
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -150,6 +150,23 @@ _PROTOTYPES = {
     "mhap_kmer_counts_histogram_size": "i:pp",
     "mhap_kmer_counts_histogram": "i:ppp",
     "mhap_kmer_counts_write_histogram": "i:pp",
+    "mhap_kmer_histogram_valley": "i:ppqp",
+    "mhap_kmer_qv": "i:qqipp",
+    "mhap_kmer_count_finish_set": "i:pQp",
+    "mhap_kmer_set_free": "v:p",
+    "mhap_kmer_set_info": "i:ppppppp",
+    "mhap_kmer_set_contains": "i:pppqp",
+    "mhap_kmer_set_compare": "i:pppppp",
+    "mhap_kmer_eval_reads": "i:pppppqp",
+    "mhap_kmer_eval_scan": "i:pppp",
+    "mhap_kmer_eval_free": "v:p",
+    "mhap_kmer_eval_info": "i:ppppp",
+    "mhap_kmer_eval_rows": "i:pp",
+    "mhap_kmer_eval_intervals": "i:pp",
+    "mhap_kmer_eval_write_table": "i:ppp",
+    "mhap_kmer_eval_write_bed": "i:ppp",
+    "mhap_kmer_eval_summary": "i:pppqpz",
+    "mhap_selftest_kmer_eval": "i:piiippp",
     "mhap_histogram_stats": "i:ppqdppp",
     "mhap_synth_truth": "i:Qqidqpdqqpppppp",
     "mhap_align_pairs": "i:ppqpqp",
@@ -246,6 +263,7 @@ _PROTOTYPES = {
 }
 EXPORTED_SYMBOLS = list(_PROTOTYPES)
 MHAP_KMER_HISTOGRAM = 1   # mhap_kmer_count_finish_flags
+MHAP_KMER_KEEP_OPEN = 2   # (the count stays open: mhap_kmer_count_finish_set may follow)
 ABI_VERSION = 4   # MHAP_ABI_VERSION of include/mhap_hip.h this binding was written against
 
 
@@ -1737,6 +1755,119 @@ class KmerCounts:
             pass
 
 
+class KmerSet:
+    """The k-mers of a count whose final count is at least `min_count`, as a bitmap of 4^k bits on the device (mhap_kmer_set_*): what
+    sequences are assessed against.  total: windows counted; distinct: values seen; members: values in the set; min_count: the
+    threshold used (the valley of the count histogram when it was made with min_count=0)."""
+
+    def __init__(self, lib, ptr):
+        self._lib, self._s = lib, ptr
+        total, distinct, members, k, canonical, mc = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int32(), C.c_int32(), C.c_uint64()
+        lib.mhap_kmer_set_info(ptr, C.byref(total), C.byref(distinct), C.byref(members), C.byref(k), C.byref(canonical), C.byref(mc))
+        self.total, self.distinct, self.members = total.value, distinct.value, members.value
+        self.k, self.canonical, self.min_count = k.value, bool(canonical.value), mc.value
+
+    def close(self):
+        if getattr(self, "_s", None):
+            self._lib.mhap_kmer_set_free(self._s)
+            self._s = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class KmerEval:
+    """Sequences walked against a KmerSet (mhap_kmer_eval_*).  rows: int64 (sequences, 5) = bases, windows, missing, runs, unsupported;
+    intervals: int64 (intervals, 3) = sequence index, begin, end of every maximal stretch of unsupported positions; totals: the
+    column sums of the rows; error, qv: mhap_kmer_qv of the totals.  `names` (when the sequences had names) go into the files."""
+    COLUMNS = ("bases", "windows", "missing", "runs", "unsupported")
+
+    def __init__(self, lib, ptr, names=None):
+        self._lib, self._e, self.names = lib, ptr, names
+        n, ni, k = C.c_int64(), C.c_int64(), C.c_int32()
+        self.totals = np.zeros(5, dtype=np.int64)
+        lib.mhap_kmer_eval_info(ptr, C.byref(n), C.byref(ni), C.byref(k), _ptr(self.totals))
+        self.k = k.value
+        self.rows = np.zeros((n.value, 5), dtype=np.int64)
+        self.intervals = np.zeros((ni.value, 3), dtype=np.int64)
+        if n.value:
+            lib.mhap_kmer_eval_rows(ptr, _ptr(self.rows))
+        if ni.value:
+            lib.mhap_kmer_eval_intervals(ptr, _ptr(self.intervals))
+        self.error, self.qv = kmer_qv(int(self.totals[1]), int(self.totals[2]), self.k)
+
+    def __len__(self):
+        return int(self.rows.shape[0])
+
+    def _names(self):
+        if self.names is None:
+            return None
+        if len(self.names) != len(self):
+            raise MhapError(f"{len(self.names)} names for {len(self)} sequences")
+        return b"".join(n.encode("latin-1") + b"\0" for n in self.names)
+
+    def write_table(self, path):
+        """"name\tbases\twindows\tmissing\truns\tunsupported\terror\tqv" per sequence, then a `total` line (mhap_kmer_eval_write_table)."""
+        if not self._e:
+            raise MhapError("KmerEval already freed")
+        if self._lib.mhap_kmer_eval_write_table(self._e, self._names(), os.fspath(path).encode()) != 0:
+            raise MhapError(f"cannot write the assessment table {path}")
+
+    def write_bed(self, path):
+        """"name\tbegin\tend" per interval of unsupported positions (mhap_kmer_eval_write_bed)."""
+        if not self._e:
+            raise MhapError("KmerEval already freed")
+        if self._lib.mhap_kmer_eval_write_bed(self._e, self._names(), os.fspath(path).encode()) != 0:
+            raise MhapError(f"cannot write the interval file {path}")
+
+    def summary(self, reads_set, own_set=None, both=0):
+        """The line both tools print (mhap_kmer_eval_summary)."""
+        buf = C.create_string_buffer(1024)
+        if self._lib.mhap_kmer_eval_summary(self._e, reads_set._s, own_set._s if own_set is not None else None, C.c_int64(both), buf, C.c_size_t(1024)) != 0:
+            raise MhapError("mhap_kmer_eval_summary failed")
+        return buf.value.decode()
+
+    def close(self):
+        if getattr(self, "_e", None):
+            self._lib.mhap_kmer_eval_free(self._e)
+            self._e = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def kmer_histogram_valley(counts, numbers):
+    """The smallest c >= 1 with n[c + 1] >= n[c] of a count histogram given as KmerCounts.histogram gives it (mhap_kmer_histogram_valley)."""
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    numbers = np.ascontiguousarray(numbers, dtype=np.uint64)
+    if counts.shape != numbers.shape or counts.ndim != 1:
+        raise MhapError("counts and numbers must be one-dimensional and of one length")
+    out = C.c_uint64()
+    if load_library().mhap_kmer_histogram_valley(_opt(counts), _opt(numbers), C.c_int64(len(counts)), C.byref(out)) != 0:
+        raise MhapError("the histogram's counts must be ascending and at least 1")
+    return out.value
+
+
+def kmer_qv(windows, missing, k):
+    """(error per base, QV) from the missing windows of `windows` valid ones (mhap_kmer_qv): NaN without windows, (0, inf) without missing ones."""
+    err, qv = C.c_double(), C.c_double()
+    if load_library().mhap_kmer_qv(C.c_int64(windows), C.c_int64(missing), C.c_int32(k), C.byref(err), C.byref(qv)) != 0:
+        raise MhapError(f"mhap_kmer_qv: bad arguments (windows {windows}, missing {missing}, k {k})")
+    return err.value, qv.value
+
+
 def count_kmers(source, k=16, canonical=True, min_fraction=2.5e-6, device=0, histogram=False):
     """Count the k-mers (k = 1..16) of a FastaData or a FASTA file (plain, gz or bz2; a path goes through the streamed ingest) on the GPU
     and return the KmerCounts of the `-f` repeat filter file.  Windows with a byte other than A/C/G/T are skipped; only the forward
@@ -1885,13 +2016,43 @@ class MinHashSearch:
     def kmer_count_add_scan(self, scan):
         self._chk(self._lib.mhap_kmer_count_add_scan(self._h, scan._s))
 
-    def kmer_count_finish(self, min_fraction=2.5e-6, histogram=False):
+    def kmer_count_finish(self, min_fraction=2.5e-6, histogram=False, keep_open=False):
         out = C.c_void_p()
-        if histogram:
-            self._chk(self._lib.mhap_kmer_count_finish_flags(self._h, C.c_double(min_fraction), C.c_uint32(MHAP_KMER_HISTOGRAM), C.byref(out)))
+        if histogram or keep_open:
+            flags = (MHAP_KMER_HISTOGRAM if histogram else 0) | (MHAP_KMER_KEEP_OPEN if keep_open else 0)
+            self._chk(self._lib.mhap_kmer_count_finish_flags(self._h, C.c_double(min_fraction), C.c_uint32(flags), C.byref(out)))
         else:
             self._chk(self._lib.mhap_kmer_count_finish(self._h, C.c_double(min_fraction), C.byref(out)))
         return KmerCounts(self._lib, out)
+
+    # -- sequence assessment (mhap_amd.kmer_qv) ------------------------------------------------
+    def kmer_count_finish_set(self, min_count=0):
+        """End the open count as a KmerSet of the k-mers counted at least min_count times (0: the valley of the count histogram)."""
+        out = C.c_void_p()
+        self._chk(self._lib.mhap_kmer_count_finish_set(self._h, C.c_uint64(min_count), C.byref(out)))
+        return KmerSet(self._lib, out)
+
+    def kmer_set_contains(self, kset, values):
+        values = np.ascontiguousarray(values, dtype=np.uint64)
+        out = np.zeros(len(values), dtype=np.uint8)
+        self._chk(self._lib.mhap_kmer_set_contains(self._h, kset._s, _opt(values), C.c_int64(len(values)), _opt(out)))
+        return out
+
+    def kmer_set_eval(self, kset, source):
+        """The sequences of a FastaData (bytes as they are) or of a FastaScan (through the streamed ingest) against the set: a KmerEval."""
+        out = C.c_void_p()
+        if isinstance(source, FastaScan):
+            self._chk(self._lib.mhap_kmer_eval_scan(self._h, kset._s, source._s, C.byref(out)))
+            return KmerEval(self._lib, out, source.info()[2])
+        self._chk(self._lib.mhap_kmer_eval_reads(self._h, kset._s, _ptr(source.bases), _ptr(source.offsets), _ptr(source.lengths),
+                                                 C.c_int64(len(source)), C.byref(out)))
+        return KmerEval(self._lib, out, getattr(source, "names", None))
+
+    def kmer_set_compare(self, a, b):
+        """(members of a, members of b, members of both); sets that differ in k or canonical are refused."""
+        na, nb, both = C.c_int64(), C.c_int64(), C.c_int64()
+        self._chk(self._lib.mhap_kmer_set_compare(self._h, a._s, b._s, C.byref(na), C.byref(nb), C.byref(both)))
+        return na.value, nb.value, both.value
 
     # -- index ----------------------------------------------------------------------------------
     def add_data(self, fasta):

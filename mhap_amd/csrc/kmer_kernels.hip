@@ -15,9 +15,15 @@
 //                           a global histogram by nonzero bin, larger counts to a tail list (one entry per value)
 // Each bucket is owned by one workgroup, so the counts need no global atomics.  Staging is 2 bytes per window; it is flushed into the
 // kept counts when the next group would pass a budget (a quarter of the free HBM), so every allocation is sized by the input.
+//
+// Sequence assessment sits on the same counts (the second half of this file): kmer_set_kernel ends a count as a bitmap of 4^k bits (step
+// 4's fold, then the values counted often enough, a ballot per word), kmer_eval_kernel walks arbitrary sequences against such a bitmap
+// (a wave per tile of 4 032 positions: windows valid, present or missing, runs of missing ones, bases no present window covers),
+// kmer_eval_intervals_kernel turns the uncovered bases into intervals, kmer_set_compare_kernel counts two bitmaps and their intersection.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -162,6 +168,22 @@ struct KcCountArgs {
   unsigned long long* dense; uint32_t* tail; unsigned long long* ntail; uint64_t tail_cap;
 };
 
+// The fold of step 4 into bucket b's zeroed LDS counters: the counts kept from earlier flushes, then the bucket's segment of every
+// staged group.  True in a thread that saw a counter wrap.
+__device__ inline bool kc_fold(const KcCountArgs& a, uint32_t* cnt, int b, int t) {
+  const uint64_t k0 = a.kept_off[b];
+  const uint32_t kn = a.kept_n[b];
+  for (uint32_t i = t; i < kn; i += KC_COUNT_THREADS) { const uint2 e = a.kept[k0 + i]; cnt[e.x] = e.y; }   // (distinct low bits: no two threads meet)
+  __syncthreads();
+  bool over = false;
+  for (int g = 0; g < a.ngroups; g++) {
+    const uint64_t* row = a.segs + (size_t)g * (a.NB + 1);
+    const uint64_t s = row[b], e = row[b + 1];
+    for (uint64_t i = s + t; i < e; i += KC_COUNT_THREADS) over |= atomicAdd(&cnt[a.stage[i]], 1u) == 0xFFFFFFFFu;
+  }
+  return over;
+}
+
 // Step 4: one workgroup per bucket.  FINISH = 0: a flush, 1: the finish, 2: the finish with the histogram.
 template <int FINISH>
 __global__ __launch_bounds__(KC_COUNT_THREADS) void kmer_count_kernel(KcCountArgs a) {
@@ -176,17 +198,7 @@ __global__ __launch_bounds__(KC_COUNT_THREADS) void kmer_count_kernel(KcCountArg
   }
   if (t == 0) cursor = 0u;
   __syncthreads();
-  const uint64_t k0 = a.kept_off[b];
-  const uint32_t kn = a.kept_n[b];
-  for (uint32_t i = t; i < kn; i += KC_COUNT_THREADS) { const uint2 e = a.kept[k0 + i]; cnt[e.x] = e.y; }   // (distinct low bits: no two threads meet)
-  __syncthreads();
-  bool over = false;
-  for (int g = 0; g < a.ngroups; g++) {
-    const uint64_t* row = a.segs + (size_t)g * (a.NB + 1);
-    const uint64_t s = row[b], e = row[b + 1];
-    for (uint64_t i = s + t; i < e; i += KC_COUNT_THREADS) over |= atomicAdd(&cnt[a.stage[i]], 1u) == 0xFFFFFFFFu;
-  }
-  if (over) *a.overflow = 1;
+  if (kc_fold(a, cnt, b, t)) *a.overflow = 1;
   __syncthreads();
   for (int i0 = 0; i0 < nv; i0 += KC_COUNT_THREADS) {
     const int i = i0 + t;
@@ -234,6 +246,214 @@ __global__ __launch_bounds__(KC_COUNT_THREADS) void kmer_count_kernel(KcCountArg
     if (FINISH) a.distinct[b] = cursor;
     else a.kept_out_n[b] = cursor;
   }
+}
+
+// ---- the set of the solid k-mers and sequences walked against it (sequence assessment) --------------------------------------------
+// The set finish: step 4's fold, then bit v of a bitmap of 4^k bits = (final count of v >= thr).  Value v = (b << L) | i sits in 64-bit
+// word v >> 6 at bit v & 63, so a wave's ballot over 64 consecutive i is one whole word with one writer; a bucket narrower than a word
+// (L < 6) ORs its bits into the zeroed word it shares with its neighbours.  distinct[b] as at the finish; *members += the bucket's bits.
+__global__ __launch_bounds__(KC_COUNT_THREADS) void kmer_set_kernel(KcCountArgs a, uint64_t thr, unsigned long long* __restrict__ bits,
+                                                                    unsigned long long* __restrict__ members) {
+  __shared__ uint32_t cnt[KC_LDS];
+  __shared__ uint32_t ndistinct, nmembers;
+  const int b = blockIdx.x, t = threadIdx.x, lane = t & (MHAP_WAVE - 1);
+  const int nv = 1 << a.L;
+  for (int i = t; i < nv; i += KC_COUNT_THREADS) cnt[i] = 0u;
+  if (t == 0) { ndistinct = 0u; nmembers = 0u; }
+  __syncthreads();
+  if (kc_fold(a, cnt, b, t)) *a.overflow = 1;
+  __syncthreads();
+  for (int i0 = 0; i0 < nv; i0 += KC_COUNT_THREADS) {
+    const int i = i0 + t;
+    const uint32_t c = i < nv ? cnt[i] : 0u;
+    const unsigned long long in = __ballot(c > 0u && (uint64_t)c >= thr), nz = __ballot(c > 0u);
+    if (lane == 0 && i < nv) {
+      if (nz) atomicAdd(&ndistinct, (uint32_t)__popcll(nz));
+      if (in) atomicAdd(&nmembers, (uint32_t)__popcll(in));
+      const uint64_t v0 = ((uint64_t)b << a.L) | (uint64_t)i;   // the value of this wave's first counter
+      if (nv >= MHAP_WAVE) bits[v0 >> 6] = in;
+      else if (in) atomicOr(bits + (v0 >> 6), in << (v0 & 63u));
+    }
+  }
+  __syncthreads();
+  if (t == 0) {
+    a.distinct[b] = ndistinct;
+    if (nmembers) atomicAdd(members, (unsigned long long)nmembers);
+  }
+}
+
+// out[i] = 1 when the set holds values[i] (a value outside the 4^k values of the set: 0)
+__global__ __launch_bounds__(KC_THREADS) void kmer_set_contains_kernel(const uint32_t* __restrict__ bits, int k, const uint64_t* __restrict__ values, int64_t n,
+                                                                       uint8_t* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * KC_THREADS + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t v = values[i];
+  out[i] = v < (1ULL << (2 * k)) ? (uint8_t)((bits[v >> 5] >> (v & 31u)) & 1u) : (uint8_t)0;
+}
+
+// out[0], out[1], out[2] += the bits of a, of b and of a & b over n16 16-byte pieces of the two bitmaps
+__global__ __launch_bounds__(KC_THREADS) void kmer_set_compare_kernel(const uint4* __restrict__ a, const uint4* __restrict__ b, int64_t n16,
+                                                                      unsigned long long* __restrict__ out) {
+  unsigned long long ca = 0, cb = 0, cab = 0;
+  const int64_t step = (int64_t)gridDim.x * KC_THREADS;
+  for (int64_t i = (int64_t)blockIdx.x * KC_THREADS + threadIdx.x; i < n16; i += step) {
+    const uint4 x = a[i], y = b[i];
+    ca += (unsigned)(__popc(x.x) + __popc(x.y) + __popc(x.z) + __popc(x.w));
+    cb += (unsigned)(__popc(y.x) + __popc(y.y) + __popc(y.z) + __popc(y.w));
+    cab += (unsigned)(__popc(x.x & y.x) + __popc(x.y & y.y) + __popc(x.z & y.z) + __popc(x.w & y.w));
+  }
+#pragma unroll
+  for (int off = MHAP_WAVE / 2; off > 0; off >>= 1) { ca += __shfl_xor(ca, off); cb += __shfl_xor(cb, off); cab += __shfl_xor(cab, off); }
+  if ((threadIdx.x & (MHAP_WAVE - 1)) == 0) {
+    if (ca) atomicAdd(out, ca);
+    if (cb) atomicAdd(out + 1, cb);
+    if (cab) atomicAdd(out + 2, cab);
+  }
+}
+
+// Sequences against a set.  A window is named by its LAST base j (it starts at j - k + 1), so bit b of a lane's masks is both the
+// window that ends at base s + b and the position s + b.  One wave takes a tile of KE_TILE positions of one sequence: lane l walks
+// the KE_LANE positions from s = tile start + 64 l after a warm-up of KE_WARM bases (>= k - 1, so no lane needs a state of the lane
+// before it) and keeps two masks, V (valid windows) and P (valid windows the set holds).  Everything a position needs from elsewhere
+// lies AFTER it — the k - 1 windows that also contain it, the window that would continue a missing run — and comes from the next lane
+// by one shuffle; lane 63 walks the first 64 positions of the next tile for that purpose alone and counts nothing, so no pass
+// stitches tiles.  Bases before the sequence or past its end are invalid, which makes their windows invalid and their positions uncovered.
+constexpr int KE_LANE = 64;
+constexpr int KE_TILE = 63 * KE_LANE;
+constexpr int KE_WARM = 16;
+constexpr int KE_BATCH = 32;    // bitmap lookups issued together (dependent random loads: all of a batch are in flight before the first use)
+constexpr int KE_THREADS = 256;
+
+// OR over d in [0, k) of (hi:lo >> d), low 64 bits: position p is covered when a window that ends in [p, p + k) is set (k <= 16)
+__host__ __device__ inline unsigned long long ke_cover(unsigned long long lo, unsigned long long hi, int k) {
+  int w = 1;   // lo and hi hold the OR over d in [0, w)
+  while (2 * w <= k) { lo |= (lo >> w) | (hi << (64 - w)); hi |= hi >> w; w *= 2; }
+  const int r = k - w;
+  if (r > 0) lo |= (lo >> r) | (hi << (64 - r));
+  return lo;
+}
+
+// V and P of the windows that end at bases [s, s + 64) of a sequence of n bases stored at W (s a multiple of 64)
+template <bool RAW>
+__host__ __device__ inline void ke_lane_states(const uint32_t* __restrict__ W, int64_t s, int n, int k, bool canonical, const uint32_t* __restrict__ bits,
+                                      unsigned long long& V, unsigned long long& P) {
+  constexpr int PER = RAW ? 4 : 16, NW = (KE_WARM + KE_LANE) / PER;   // bases per dword; dwords of the bases [s - 16, s + 64)
+  const int64_t w0 = (s - KE_WARM) / PER, nwords = ((int64_t)n + PER - 1) / PER;
+  uint32_t bw[NW];
+#pragma unroll
+  for (int i = 0; i < NW; i++) { const int64_t d = w0 + i; bw[i] = d >= 0 && d < nwords ? W[d] : 0u; }
+  // base s + rel is in the sequence for rel in [lo, hi) (s = 0: nothing before it; a packed dword's padding decodes as A)
+  const int lo = s == 0 ? 0 : -KE_WARM, hi = (int64_t)n - s < KE_LANE ? (int)((int64_t)n - s) : KE_LANE;
+  const uint32_t mask = kmer_mask(k);
+  KmerRoll r;
+  auto push = [&](int q) {   // base s - 16 + q
+    uint32_t code;
+    bool ok = true;
+    if (RAW) ok = kmer_code((bw[q >> 2] >> (8 * (q & 3))) & 0xFFu, code);
+    else code = (bw[q >> 4] >> (2 * (q & 15))) & 3u;
+    kmer_push(r, code, ok && q - KE_WARM >= lo && q - KE_WARM < hi, k, mask);
+  };
+#pragma unroll
+  for (int q = 0; q < KE_WARM; q++) push(q);
+  V = 0; P = 0;
+#pragma unroll
+  for (int h = 0; h < KE_LANE / KE_BATCH; h++) {
+    uint32_t val[KE_BATCH], word[KE_BATCH], vm = 0, pm = 0;
+#pragma unroll
+    for (int j = 0; j < KE_BATCH; j++) {
+      push(KE_WARM + h * KE_BATCH + j);
+      const bool ok = r.run >= k;
+      val[j] = ok ? kmer_value(r, canonical) : 0u;
+      vm |= (ok ? 1u : 0u) << j;
+    }
+#pragma unroll
+    for (int j = 0; j < KE_BATCH; j++) word[j] = bits[val[j] >> 5];
+#pragma unroll
+    for (int j = 0; j < KE_BATCH; j++) pm |= ((word[j] >> (val[j] & 31u)) & 1u) << j;
+    V |= (unsigned long long)vm << (h * KE_BATCH);
+    P |= (unsigned long long)(pm & vm) << (h * KE_BATCH);
+  }
+}
+
+// What a lane counts from its masks and the next lane's: packed as windows | missing << 16 | runs << 32 | unsupported << 48 (a wave's
+// sums are at most KE_TILE each), and U, the unsupported ones of its 64 positions.
+__host__ __device__ inline unsigned long long ke_lane_counts(unsigned long long V, unsigned long long P, unsigned long long nV, unsigned long long nP, int k,
+                                                             unsigned long long& U) {
+  const unsigned long long M = V & ~P, nM = nV & ~nP;
+  const unsigned long long ends = M & ~((M >> 1) | (nM << 63));   // a missing run ends where the next window is not missing
+  U = ke_cover(V, nV, k) & ~ke_cover(P, nP, k);
+  return (unsigned long long)__builtin_popcountll(V) | ((unsigned long long)__builtin_popcountll(M) << 16) |
+         ((unsigned long long)__builtin_popcountll(ends) << 32) | ((unsigned long long)__builtin_popcountll(U) << 48);
+}
+
+struct KeArgs {
+  const uint8_t* store; const ReadDesc* descs;
+  const int32_t* tile_seq; const int64_t* tile_first; int64_t ntiles;   // tile w belongs to sequence tile_seq[w], whose tiles start at tile_first[]
+  const uint32_t* bits; int k; int canonical;
+  unsigned long long* rows;    // [sequence][4]: windows, missing, runs, unsupported
+  unsigned long long* umask;   // [tile][63]: the unsupported positions, a bit each (the tiles of a sequence are in a row: its positions in order)
+};
+
+__global__ __launch_bounds__(KE_THREADS) void kmer_eval_kernel(KeArgs a) {
+  const int lane = threadIdx.x & (MHAP_WAVE - 1);
+  const int64_t w = ((int64_t)blockIdx.x * KE_THREADS + threadIdx.x) / MHAP_WAVE;
+  if (w >= a.ntiles) return;
+  const int seq = a.tile_seq[w];
+  const ReadDesc rd = a.descs[seq];
+  const int64_t s = (w - a.tile_first[seq]) * KE_TILE + (int64_t)lane * KE_LANE;
+  const uint32_t* __restrict__ W = (const uint32_t*)(a.store + rd.base_off);
+  unsigned long long V, P;
+  if (rd.flags & MHAP_RD_RAW) ke_lane_states<true>(W, s, rd.length, a.k, a.canonical != 0, a.bits, V, P);
+  else ke_lane_states<false>(W, s, rd.length, a.k, a.canonical != 0, a.bits, V, P);
+  const unsigned long long nV = __shfl_down(V, 1), nP = __shfl_down(P, 1);   // (lane 63 gets its own: it counts nothing)
+  unsigned long long U;
+  unsigned long long sum = ke_lane_counts(V, P, nV, nP, a.k, U);
+  if (lane == MHAP_WAVE - 1) sum = 0;
+#pragma unroll
+  for (int off = MHAP_WAVE / 2; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+  if (lane < MHAP_WAVE - 1) a.umask[w * (MHAP_WAVE - 1) + lane] = U;
+  if (lane == 0) {
+    unsigned long long* row = a.rows + (size_t)seq * 4;
+#pragma unroll
+    for (int f = 0; f < 4; f++) { const unsigned long long c = (sum >> (16 * f)) & 0xFFFFu; if (c) atomicAdd(row + f, c); }
+  }
+}
+
+// The intervals of unsupported positions from the bit per position: a wave per tile.  FILL = 0 counts the tile's interval begins and
+// ends; after a prefix sum of each, FILL = 1 writes them: begins and ends are both in position order, so the i-th begin and the i-th
+// end are one interval, whichever tiles they lie in.  iv: (seq0 + sequence, begin, end) per interval, as the host hands them out.
+template <int FILL>
+__global__ __launch_bounds__(KE_THREADS) void kmer_eval_intervals_kernel(const unsigned long long* __restrict__ umask, const int32_t* __restrict__ tile_seq,
+                                                                         const int64_t* __restrict__ tile_first, int64_t ntiles, int32_t* __restrict__ nbegin,
+                                                                         int32_t* __restrict__ nend, const int64_t* __restrict__ at_begin,
+                                                                         const int64_t* __restrict__ at_end, int64_t seq0, int64_t* __restrict__ iv) {
+  constexpr int WORDS = MHAP_WAVE - 1;
+  const int lane = threadIdx.x & (MHAP_WAVE - 1);
+  const int64_t w = ((int64_t)blockIdx.x * KE_THREADS + threadIdx.x) / MHAP_WAVE;
+  if (w >= ntiles) return;
+  const int seq = tile_seq[w];
+  const int64_t first = tile_first[seq] * WORDS, last = tile_first[seq + 1] * WORDS, g = w * WORDS + lane;   // the sequence's words
+  unsigned long long U = 0, before = 0, after = 0;
+  if (lane < WORDS) {
+    U = umask[g];
+    if (g > first) before = umask[g - 1];
+    if (g + 1 < last) after = umask[g + 1];
+  }
+  const unsigned long long B = U & ~((U << 1) | (before >> 63)), E = U & ~((U >> 1) | (after << 63));
+  const uint32_t mine = (uint32_t)__popcll(B) | ((uint32_t)__popcll(E) << 16);   // (at most 32 of each per word)
+  uint32_t incl = mine;
+#pragma unroll
+  for (int off = 1; off < MHAP_WAVE; off <<= 1) { const uint32_t u = __shfl_up(incl, off); if (lane >= off) incl += u; }
+  if (!FILL) {
+    if (lane == MHAP_WAVE - 1) { nbegin[w] = (int32_t)(incl & 0xFFFFu); nend[w] = (int32_t)(incl >> 16); }
+    return;
+  }
+  const uint32_t ex = incl - mine;
+  const int32_t p0 = (int32_t)((g - first) * KE_LANE);   // the position of bit 0
+  int64_t o = at_begin[w] + (ex & 0xFFFFu);
+  for (unsigned long long m = B; m; m &= m - 1) { iv[3 * o] = seq0 + seq; iv[3 * o + 1] = p0 + (__ffsll((long long)m) - 1); o++; }
+  o = at_end[w] + (ex >> 16);
+  for (unsigned long long m = E; m; m &= m - 1) { iv[3 * o + 2] = p0 + __ffsll((long long)m); o++; }
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
@@ -456,7 +676,207 @@ int kmer_count_finish(KmerCountState& S, const HandleView& v, double min_fractio
   return MHAP_OK;
 }
 
+// ---- sequence assessment: the drivers ------------------------------------------------------------------------------------------------
+int kmer_count_finish_set(KmerCountState& S, const HandleView& v, uint64_t min_count, KmerSet& out) {
+  (void)hipSetDevice(v.device);
+  hipStream_t st = v.stream;
+  const uint64_t space = 1ULL << (2 * S.k);
+  out.k = S.k; out.canonical = S.canonical; out.device = v.device; out.total = S.total; out.min_count = min_count;
+  out.bytes = (size_t)std::max<uint64_t>((space / 8 + 15) & ~15ULL, 16);
+  KCHK(v, hipMalloc(&out.bits, out.bytes));
+  // a bucket of 64 values or more writes every one of its words; narrower ones OR into zeroed words, and so does the padding stay zero
+  if (S.L < 6 || space / 8 < out.bytes) KCHK(v, hipMemsetAsync(out.bits, 0, out.bytes, st));
+  KCHK(v, S.distinct.ensure((size_t)S.NB * 4));
+  unsigned long long* sc = S.scalars.as<unsigned long long>();
+  KCHK(v, hipMemsetAsync(sc + 2, 0, 16, st));   // [2] the members here, [3] the overflow flag
+  KcCountArgs a{};
+  a.stage = S.arena.as<uint16_t>(); a.segs = S.segs.as<uint64_t>(); a.ngroups = S.ngroups; a.NB = S.NB; a.L = S.L;
+  a.kept = S.kept.as<uint2>(); a.kept_off = S.kept_off.as<uint64_t>(); a.kept_n = S.kept_n.as<uint32_t>();
+  a.distinct = S.distinct.as<uint32_t>(); a.overflow = (int*)(sc + 3);
+  kmer_set_kernel<<<S.NB, KC_COUNT_THREADS, 0, st>>>(a, min_count, (unsigned long long*)out.bits, sc + 2);
+  KCHK(v, hipGetLastError());
+  unsigned long long tail[2] = {0, 0};
+  KCHK(v, hipMemcpyAsync(tail, sc + 2, 16, hipMemcpyDeviceToHost, st));
+  std::vector<uint32_t> dist((size_t)S.NB);
+  KCHK(v, hipMemcpyAsync(dist.data(), S.distinct.p, (size_t)S.NB * 4, hipMemcpyDeviceToHost, st));
+  KCHK(v, hipStreamSynchronize(st));
+  if ((int)tail[1]) { *v.err = "a k-mer occurs more than 4294967295 times: its count would overflow the counter"; return MHAP_E_INVALID; }
+  out.members = (int64_t)tail[0];
+  out.distinct = 0;
+  for (uint32_t d : dist) out.distinct += d;
+  if (kc_prof()) fprintf(stderr, "[kmer] set: %lld of %lld distinct %d-mers at count >= %llu, %zu bytes\n", (long long)out.members, (long long)out.distinct, S.k,
+                         (unsigned long long)min_count, out.bytes);
+  return MHAP_OK;
+}
+
+void kmer_set_release(KmerSet& s) {
+  if (s.bits) { (void)hipSetDevice(s.device); (void)hipFree(s.bits); }
+  s.bits = nullptr; s.bytes = 0;
+}
+
+int kmer_set_contains(const HandleView& v, const KmerSet& s, const uint64_t* values, int64_t n, uint8_t* out) {
+  if (n <= 0) return MHAP_OK;
+  (void)hipSetDevice(v.device);
+  hipStream_t st = v.stream;
+  DevBuf dv, dout;
+  auto run = [&]() -> int {
+    KCHK(v, dv.ensure((size_t)n * 8));
+    KCHK(v, dout.ensure((size_t)n));
+    KCHK(v, hipMemcpyAsync(dv.p, values, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    kmer_set_contains_kernel<<<(unsigned)((n + KC_THREADS - 1) / KC_THREADS), KC_THREADS, 0, st>>>((const uint32_t*)s.bits, s.k, dv.as<uint64_t>(), n, dout.as<uint8_t>());
+    KCHK(v, hipGetLastError());
+    KCHK(v, hipMemcpyAsync(out, dout.p, (size_t)n, hipMemcpyDeviceToHost, st));
+    KCHK(v, hipStreamSynchronize(st));
+    return MHAP_OK;
+  };
+  const int rc = run();
+  dv.release(); dout.release();
+  return rc;
+}
+
+int kmer_set_compare(const HandleView& v, const KmerSet& a, const KmerSet& b, int64_t counts[3]) {
+  (void)hipSetDevice(v.device);
+  hipStream_t st = v.stream;
+  DevBuf dc;
+  auto run = [&]() -> int {
+    KCHK(v, dc.ensure(24));
+    KCHK(v, hipMemsetAsync(dc.p, 0, 24, st));
+    const int64_t n16 = (int64_t)(a.bytes / 16);
+    const int grid = (int)std::min<int64_t>((n16 + KC_THREADS - 1) / KC_THREADS, 8 * (int64_t)std::max(1, v.num_cus));
+    kmer_set_compare_kernel<<<grid, KC_THREADS, 0, st>>>((const uint4*)a.bits, (const uint4*)b.bits, n16, dc.as<unsigned long long>());
+    KCHK(v, hipGetLastError());
+    unsigned long long got[3] = {0, 0, 0};
+    KCHK(v, hipMemcpyAsync(got, dc.p, 24, hipMemcpyDeviceToHost, st));
+    KCHK(v, hipStreamSynchronize(st));
+    for (int i = 0; i < 3; i++) counts[i] = (int64_t)got[i];
+    return MHAP_OK;
+  };
+  const int rc = run();
+  dc.release();
+  return rc;
+}
+
+int kmer_eval_group(const HandleView& v, const KmerSet& s, const ReadDesc* descs, int64_t n, const void* packed, size_t bytes, KmerEval& out) {
+  if (n <= 0) return MHAP_OK;
+  (void)hipSetDevice(v.device);
+  hipStream_t st = v.stream;
+  // the work items: (sequence, tile of KE_TILE positions), the tiles of a sequence in a row; a sequence shorter than k has no window and no tile
+  std::vector<int64_t> tile_first((size_t)n + 1, 0);
+  for (int64_t i = 0; i < n; i++)
+    tile_first[(size_t)i + 1] = tile_first[(size_t)i] + (descs[i].length >= s.k ? ((int64_t)descs[i].length + KE_TILE - 1) / KE_TILE : 0);
+  const int64_t ntiles = tile_first[(size_t)n];
+  std::vector<int32_t> tile_seq((size_t)ntiles);
+  for (int64_t i = 0; i < n; i++) std::fill(tile_seq.begin() + tile_first[(size_t)i], tile_seq.begin() + tile_first[(size_t)i + 1], (int32_t)i);
+  const size_t row0 = out.rows.size(), iv_before = out.intervals.size();
+  out.rows.resize(row0 + (size_t)n * 5, 0);
+  for (int64_t i = 0; i < n; i++) out.rows[row0 + (size_t)i * 5] = descs[i].length;
+  if (ntiles == 0) return MHAP_OK;
+  const int64_t seq0 = (int64_t)(row0 / 5);
+  DevBuf &store = out.scratch[0], &ddescs = out.scratch[1], &dseq = out.scratch[2], &dfirst = out.scratch[3], &rows = out.scratch[4], &umask = out.scratch[5],
+         &counts = out.scratch[6], &at = out.scratch[7], &iv = out.scratch[8];   // (kept from group to group; kmer_eval_done frees them)
+  auto run = [&]() -> int {
+    KCHK(v, store.ensure(std::max<size_t>(bytes, 4)));
+    KCHK(v, ddescs.ensure((size_t)n * sizeof(ReadDesc)));
+    KCHK(v, dseq.ensure((size_t)ntiles * 4));
+    KCHK(v, dfirst.ensure(((size_t)n + 1) * 8));
+    KCHK(v, rows.ensure((size_t)n * 32));
+    KCHK(v, umask.ensure((size_t)ntiles * (MHAP_WAVE - 1) * 8));
+    KCHK(v, counts.ensure((size_t)ntiles * 8));            // begins per tile, then ends per tile
+    KCHK(v, at.ensure(((size_t)ntiles + 1) * 16));         // their prefix sums
+    KCHK(v, hipMemcpyAsync(store.p, packed, bytes, hipMemcpyHostToDevice, st));
+    KCHK(v, hipMemcpyAsync(ddescs.p, descs, (size_t)n * sizeof(ReadDesc), hipMemcpyHostToDevice, st));
+    KCHK(v, hipMemcpyAsync(dseq.p, tile_seq.data(), (size_t)ntiles * 4, hipMemcpyHostToDevice, st));
+    KCHK(v, hipMemcpyAsync(dfirst.p, tile_first.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
+    KCHK(v, hipMemsetAsync(rows.p, 0, (size_t)n * 32, st));
+    KeArgs a{};
+    a.store = store.as<uint8_t>(); a.descs = ddescs.as<ReadDesc>(); a.tile_seq = dseq.as<int32_t>(); a.tile_first = dfirst.as<int64_t>(); a.ntiles = ntiles;
+    a.bits = (const uint32_t*)s.bits; a.k = s.k; a.canonical = s.canonical;
+    a.rows = rows.as<unsigned long long>(); a.umask = umask.as<unsigned long long>();
+    const unsigned grid = (unsigned)((ntiles + KE_THREADS / MHAP_WAVE - 1) / (KE_THREADS / MHAP_WAVE));
+    const bool prof = kc_prof();
+    auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    if (prof) KCHK(v, hipStreamSynchronize(st));   // (the uploads end here, so that the line below times the kernel alone)
+    const double t0 = now();
+    kmer_eval_kernel<<<grid, KE_THREADS, 0, st>>>(a);
+    KCHK(v, hipGetLastError());
+    if (prof) KCHK(v, hipStreamSynchronize(st));
+    const double t1 = now();
+    int32_t *nbegin = counts.as<int32_t>(), *nend = nbegin + ntiles;
+    int64_t *at_begin = at.as<int64_t>(), *at_end = at_begin + ntiles + 1;
+    kmer_eval_intervals_kernel<0><<<grid, KE_THREADS, 0, st>>>(a.umask, a.tile_seq, a.tile_first, ntiles, nbegin, nend, nullptr, nullptr, 0, nullptr);
+    KCHK(v, hipGetLastError());
+    scan_kernel<int32_t><<<1, 1024, 0, st>>>(nbegin, ntiles, at_begin);
+    KCHK(v, hipGetLastError());
+    scan_kernel<int32_t><<<1, 1024, 0, st>>>(nend, ntiles, at_end);
+    KCHK(v, hipGetLastError());
+    int64_t nb = 0, ne = 0;
+    KCHK(v, hipMemcpyAsync(&nb, at_begin + ntiles, 8, hipMemcpyDeviceToHost, st));
+    KCHK(v, hipMemcpyAsync(&ne, at_end + ntiles, 8, hipMemcpyDeviceToHost, st));
+    const size_t r0 = out.rows.size() - (size_t)n * 5;
+    std::vector<unsigned long long> got((size_t)n * 4);
+    KCHK(v, hipMemcpyAsync(got.data(), rows.p, (size_t)n * 32, hipMemcpyDeviceToHost, st));
+    KCHK(v, hipStreamSynchronize(st));
+    if (nb != ne) { *v.err = "k-mer evaluation: interval begins and ends differ in number (internal error)"; return MHAP_E_HIP; }
+    for (int64_t i = 0; i < n; i++)
+      for (int f = 0; f < 4; f++) out.rows[r0 + (size_t)i * 5 + 1 + (size_t)f] = (int64_t)got[(size_t)i * 4 + (size_t)f];
+    const double t2 = now();
+    if (prof) fprintf(stderr, "[kmer] eval group: %lld sequences, %lld tiles, %lld intervals; walk %.2f ms, rows and interval counts %.2f ms\n", (long long)n,
+                      (long long)ntiles, (long long)nb, (t1 - t0) * 1e3, (t2 - t1) * 1e3);
+    if (nb == 0) return MHAP_OK;
+    KCHK(v, iv.ensure((size_t)nb * 24));
+    kmer_eval_intervals_kernel<1><<<grid, KE_THREADS, 0, st>>>(a.umask, a.tile_seq, a.tile_first, ntiles, nullptr, nullptr, at_begin, at_end, seq0, iv.as<int64_t>());
+    KCHK(v, hipGetLastError());
+    const size_t iv0 = out.intervals.size();
+    out.intervals.resize(iv0 + (size_t)nb * 3);
+    KCHK(v, hipMemcpyAsync(out.intervals.data() + iv0, iv.p, (size_t)nb * 24, hipMemcpyDeviceToHost, st));
+    KCHK(v, hipStreamSynchronize(st));
+    if (prof) fprintf(stderr, "[kmer] eval group: intervals filled and copied in %.2f ms\n", (now() - t2) * 1e3);
+    return MHAP_OK;
+  };
+  const int rc = run();
+  if (rc != MHAP_OK) { out.rows.resize(row0); out.intervals.resize(iv_before); }
+  return rc;
+}
+
+void kmer_eval_done(const HandleView& v, KmerEval& e) {
+  (void)hipSetDevice(v.device);
+  (void)hipStreamSynchronize(v.stream);
+  for (DevBuf& b : e.scratch) b.release();
+}
+
 }  // namespace mhap
+
+// The lane arithmetic of kmer_eval_kernel on the host: the sequence stored as the ingest stores it, every tile's 64 lanes walked in
+// turn against a bitmap in host memory.  row: windows, missing, runs, unsupported; umask: 63 words per tile.
+extern "C" int mhap_selftest_kmer_eval(const char* seq, int32_t len, int32_t k, int32_t canonical, const uint32_t* bits, int64_t* row, uint64_t* umask) {
+  using namespace mhap;
+  if (k < 1 || k > 16 || len < 0 || (len > 0 && !seq) || !bits || !row) return MHAP_E_INVALID;
+  bool raw = false;
+  for (int p = 0; p < len; p++) { uint32_t code; raw = raw || !kmer_code((uint8_t)seq[p], code); }
+  std::vector<uint32_t> W((size_t)(raw ? (len + 3) / 4 : (len + 15) / 16) + 1, 0u);
+  for (int p = 0; p < len; p++) {
+    uint32_t code = 0;
+    if (raw) W[(size_t)p >> 2] |= (uint32_t)(uint8_t)seq[p] << (8 * (p & 3));
+    else { kmer_code((uint8_t)seq[p], code); W[(size_t)p >> 4] |= code << (2 * (p & 15)); }
+  }
+  for (int f = 0; f < 4; f++) row[f] = 0;
+  const int64_t ntiles = len >= k ? ((int64_t)len + KE_TILE - 1) / KE_TILE : 0;
+  for (int64_t t = 0; t < ntiles; t++) {
+    unsigned long long V[MHAP_WAVE], P[MHAP_WAVE];
+    for (int l = 0; l < MHAP_WAVE; l++) {
+      const int64_t s = t * KE_TILE + (int64_t)l * KE_LANE;
+      if (raw) ke_lane_states<true>(W.data(), s, len, k, canonical != 0, bits, V[l], P[l]);
+      else ke_lane_states<false>(W.data(), s, len, k, canonical != 0, bits, V[l], P[l]);
+    }
+    for (int l = 0; l < MHAP_WAVE - 1; l++) {
+      unsigned long long U;
+      const unsigned long long c = ke_lane_counts(V[l], P[l], V[l + 1], P[l + 1], k, U);
+      for (int f = 0; f < 4; f++) row[f] += (int64_t)((c >> (16 * f)) & 0xFFFFu);
+      if (umask) umask[t * (MHAP_WAVE - 1) + l] = U;
+    }
+  }
+  return MHAP_OK;
+}
 
 extern "C" int mhap_selftest_kmer_windows(const char* seq, int32_t len, int32_t k, int32_t canonical, uint64_t* out, uint8_t* valid) {
   using namespace mhap;

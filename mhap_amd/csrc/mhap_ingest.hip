@@ -16,11 +16,13 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <limits>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -421,6 +423,8 @@ int mhap_find_matches_scan(mhap_handle* h, const mhap_fasta_scan* s, mhap_record
 }  // extern "C"
 
 // ---- exact k-mer counting: the C ABI (kernels and their driver: kmer_kernels.hip) ---------------------------------------------
+struct mhap_kmer_set { KmerSet set; };
+struct mhap_kmer_eval { KmerEval eval; };
 struct mhap_kmer_counts {
   int32_t k = 0;
   int64_t total = 0, distinct = 0;
@@ -449,30 +453,10 @@ int kc_close_on_error(const HandleView& v, int rc) {
 }
 inline bool is_upper_base(uint8_t c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T'; }
 
-}  // namespace
-
-extern "C" {
-
-int mhap_kmer_count_begin(mhap_handle* h, int32_t k, int32_t canonical) {
-  if (!h) return MHAP_E_INVALID;
-  HandleView v = handle_view(h);
-  if (k < 1 || k > 16) { *v.err = "k-mer counting supports k from 1 to 16 (got " + std::to_string(k) + ")"; return MHAP_E_INVALID; }
-  if (*v.kmer) { *v.err = "mhap_kmer_count_begin: a k-mer count is already open on this handle (mhap_kmer_count_finish ends it)"; return MHAP_E_STATE; }
-  KmerCountState* S = nullptr;
-  const int rc = kmer_count_begin(S, v, k, canonical);
-  if (rc == MHAP_OK) *v.kmer = S;
-  return rc;
-}
-
-int mhap_kmer_count_add_reads(mhap_handle* h, const char* bases, const int64_t* offsets, const int32_t* lengths, int64_t n) {
-  if (!h) return MHAP_E_INVALID;
-  HandleView v = handle_view(h);
-  int rc;
-  KmerCountState* S = kc_state(v, "mhap_kmer_count_add_reads", rc);
-  if (!S) return rc;
-  if (n < 0 || (n > 0 && (!bases || !offsets || !lengths))) { *v.err = "mhap_kmer_count_add_reads: null argument"; return MHAP_E_INVALID; }
-  for (int64_t i = 0; i < n; i++) if (lengths[i] < 0 || offsets[i] < 0) { *v.err = "mhap_kmer_count_add_reads: negative read length or offset"; return MHAP_E_INVALID; }
-  // groups of <= 256 Mbase (and <= 2^21 reads), packed like the ingest packs them: 2 bits per base when every byte is A/C/G/T, else the bytes
+// reads given as bytes, in groups of <= 256 Mbase (and <= 2^21 reads), packed like the ingest packs them: 2 bits per base when every
+// byte is A/C/G/T, else the bytes as they are; each group goes to consume(descs, reads, packed, bytes), whose first error ends the walk
+int pack_read_groups(const char* bases, const int64_t* offsets, const int32_t* lengths, int64_t n,
+                     const std::function<int(const ReadDesc*, int64_t, const void*, size_t)>& consume) {
   const int nthreads = host_threads();
   std::vector<ReadDesc> descs;
   std::vector<uint8_t> packed;
@@ -506,11 +490,40 @@ int mhap_kmer_count_add_reads(mhap_handle* h, const char* bases, const int64_t* 
         else pack_bases(s, d.length, packed.data() + d.base_off);
       }
     });
-    rc = kmer_count_add_group(*S, v, descs.data(), hi - lo, packed.data(), (size_t)store);
-    if (rc != MHAP_OK) return kc_close_on_error(v, rc);
+    const int rc = consume(descs.data(), hi - lo, packed.data(), (size_t)store);
+    if (rc != MHAP_OK) return rc;
     lo = hi;
   }
   return MHAP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mhap_kmer_count_begin(mhap_handle* h, int32_t k, int32_t canonical) {
+  if (!h) return MHAP_E_INVALID;
+  HandleView v = handle_view(h);
+  if (k < 1 || k > 16) { *v.err = "k-mer counting supports k from 1 to 16 (got " + std::to_string(k) + ")"; return MHAP_E_INVALID; }
+  if (*v.kmer) { *v.err = "mhap_kmer_count_begin: a k-mer count is already open on this handle (mhap_kmer_count_finish ends it)"; return MHAP_E_STATE; }
+  KmerCountState* S = nullptr;
+  const int rc = kmer_count_begin(S, v, k, canonical);
+  if (rc == MHAP_OK) *v.kmer = S;
+  return rc;
+}
+
+int mhap_kmer_count_add_reads(mhap_handle* h, const char* bases, const int64_t* offsets, const int32_t* lengths, int64_t n) {
+  if (!h) return MHAP_E_INVALID;
+  HandleView v = handle_view(h);
+  int rc;
+  KmerCountState* S = kc_state(v, "mhap_kmer_count_add_reads", rc);
+  if (!S) return rc;
+  if (n < 0 || (n > 0 && (!bases || !offsets || !lengths))) { *v.err = "mhap_kmer_count_add_reads: null argument"; return MHAP_E_INVALID; }
+  for (int64_t i = 0; i < n; i++) if (lengths[i] < 0 || offsets[i] < 0) { *v.err = "mhap_kmer_count_add_reads: negative read length or offset"; return MHAP_E_INVALID; }
+  rc = pack_read_groups(bases, offsets, lengths, n, [&](const ReadDesc* descs, int64_t count, const void* packed, size_t bytes) {
+    return kmer_count_add_group(*S, v, descs, count, packed, bytes);
+  });
+  return kc_close_on_error(v, rc);
 }
 
 int mhap_kmer_count_add_scan(mhap_handle* h, const mhap_fasta_scan* s) {
@@ -547,13 +560,13 @@ int mhap_kmer_count_finish_flags(mhap_handle* h, double min_fraction, uint32_t f
   if (!S) return rc;
   if (!out) { *v.err = "mhap_kmer_count_finish: null output"; return MHAP_E_INVALID; }
   if (!(min_fraction == min_fraction)) { *v.err = "mhap_kmer_count_finish: min_fraction is NaN"; return MHAP_E_INVALID; }
-  if (flags & ~(uint32_t)MHAP_KMER_HISTOGRAM) { *v.err = "mhap_kmer_count_finish_flags: unknown flags " + std::to_string(flags); return MHAP_E_INVALID; }
+  if (flags & ~(uint32_t)(MHAP_KMER_HISTOGRAM | MHAP_KMER_KEEP_OPEN)) { *v.err = "mhap_kmer_count_finish_flags: unknown flags " + std::to_string(flags); return MHAP_E_INVALID; }
   mhap_kmer_counts* c = new mhap_kmer_counts();
   c->has_histogram = (flags & MHAP_KMER_HISTOGRAM) != 0;
   rc = kmer_count_finish(*S, v, min_fraction, c->values, c->counts, c->distinct, c->has_histogram ? &c->histogram : nullptr);
   c->k = kmer_count_k(*S);
   c->total = kmer_count_total(*S);
-  kmer_count_release(S); *v.kmer = nullptr;
+  if (rc != MHAP_OK || !(flags & MHAP_KMER_KEEP_OPEN)) { kmer_count_release(S); *v.kmer = nullptr; }
   if (rc != MHAP_OK) { delete c; return rc; }
   *out = c;
   return MHAP_OK;
@@ -626,5 +639,255 @@ int mhap_kmer_counts_write_histogram(const mhap_kmer_counts* c, const char* path
 }
 
 void mhap_kmer_counts_free(mhap_kmer_counts* c) { delete c; }
+
+// ---- sequence assessment: the set of the solid k-mers, sequences against it, set against set ----------------------------------------
+int mhap_kmer_histogram_valley(const uint32_t* counts, const uint64_t* numbers, int64_t n, uint64_t* valley) {
+  if (!valley || n < 0 || (n > 0 && (!counts || !numbers))) return MHAP_E_INVALID;
+  for (int64_t i = 0; i < n; i++) if (counts[i] < 1 || (i > 0 && counts[i] <= counts[i - 1])) return MHAP_E_INVALID;
+  // the smallest c >= 1 with n[c + 1] >= n[c]: a count that is absent (n[c] = 0) ends the walk, so it only steps over entries in a row
+  uint64_t c = 1;
+  for (int64_t i = 0; i < n && counts[i] == c && numbers[i] > 0; i++, c++) {
+    const uint64_t next = i + 1 < n && counts[i + 1] == c + 1 ? numbers[i + 1] : 0;
+    if (next >= numbers[i]) break;
+  }
+  *valley = c;
+  return MHAP_OK;
+}
+
+int mhap_kmer_qv(int64_t windows, int64_t missing, int32_t k, double* error, double* qv) {
+  if (windows < 0 || missing < 0 || missing > windows || k < 1) return MHAP_E_INVALID;
+  double e, q;
+  if (windows == 0) e = q = std::numeric_limits<double>::quiet_NaN();
+  else if (missing == 0) { e = 0.0; q = std::numeric_limits<double>::infinity(); }
+  else {
+    e = 1.0 - std::pow(1.0 - (double)missing / (double)windows, 1.0 / (double)k);
+    q = 0.0 - 10.0 * std::log10(e);   // (0.0 -: an error of 1 gives +0)
+  }
+  if (error) *error = e;
+  if (qv) *qv = q;
+  return MHAP_OK;
+}
+
+int mhap_kmer_count_finish_set(mhap_handle* h, uint64_t min_count, mhap_kmer_set** out) {
+  if (!h) return MHAP_E_INVALID;
+  HandleView v = handle_view(h);
+  int rc;
+  KmerCountState* S = kc_state(v, "mhap_kmer_count_finish_set", rc);
+  if (!S) return rc;
+  if (!out) { *v.err = "mhap_kmer_count_finish_set: null output"; return MHAP_E_INVALID; }
+  if (min_count == 0) {   // the valley of the count histogram: the histogram finish reads the open state and leaves it as it is
+    std::vector<uint32_t> values, counts;
+    int64_t distinct = 0;
+    KmerHistogram hist;
+    rc = kmer_count_finish(*S, v, 2.0, values, counts, distinct, &hist);   // (a fraction above 1: no lines)
+    if (rc == MHAP_OK) rc = mhap_kmer_histogram_valley(hist.counts.data(), hist.numbers.data(), (int64_t)hist.counts.size(), &min_count);
+  }
+  mhap_kmer_set* s = new mhap_kmer_set();
+  if (rc == MHAP_OK) rc = kmer_count_finish_set(*S, v, min_count, s->set);
+  kmer_count_release(S); *v.kmer = nullptr;
+  if (rc != MHAP_OK) { kmer_set_release(s->set); delete s; return rc; }
+  *out = s;
+  return MHAP_OK;
+}
+
+void mhap_kmer_set_free(mhap_kmer_set* s) {
+  if (!s) return;
+  kmer_set_release(s->set);
+  delete s;
+}
+
+int mhap_kmer_set_info(const mhap_kmer_set* s, int64_t* total, int64_t* distinct, int64_t* members, int32_t* k, int32_t* canonical, uint64_t* min_count) {
+  if (!s) return MHAP_E_INVALID;
+  if (total) *total = s->set.total;
+  if (distinct) *distinct = s->set.distinct;
+  if (members) *members = s->set.members;
+  if (k) *k = s->set.k;
+  if (canonical) *canonical = s->set.canonical;
+  if (min_count) *min_count = s->set.min_count;
+  return MHAP_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// the set as an entry point may use it: made on the handle's device
+bool ks_usable(const HandleView& v, const mhap_kmer_set* s, const char* who) {
+  if (!s || !s->set.bits) { *v.err = std::string(who) + ": null set"; return false; }
+  if (s->set.device != v.device) { *v.err = std::string(who) + ": the set was made on device " + std::to_string(s->set.device) + ", the handle is on " + std::to_string(v.device); return false; }
+  return true;
+}
+}  // namespace
+
+extern "C" {
+
+int mhap_kmer_set_contains(mhap_handle* h, const mhap_kmer_set* s, const uint64_t* values, int64_t n, uint8_t* out) {
+  if (!h) return MHAP_E_INVALID;
+  HandleView v = handle_view(h);
+  if (!ks_usable(v, s, "mhap_kmer_set_contains")) return MHAP_E_INVALID;
+  if (n < 0 || (n > 0 && (!values || !out))) { *v.err = "mhap_kmer_set_contains: null argument"; return MHAP_E_INVALID; }
+  return kmer_set_contains(v, s->set, values, n, out);
+}
+
+int mhap_kmer_set_compare(mhap_handle* h, const mhap_kmer_set* a, const mhap_kmer_set* b, int64_t* a_members, int64_t* b_members, int64_t* both) {
+  if (!h) return MHAP_E_INVALID;
+  HandleView v = handle_view(h);
+  if (!ks_usable(v, a, "mhap_kmer_set_compare") || !ks_usable(v, b, "mhap_kmer_set_compare")) return MHAP_E_INVALID;
+  if (a->set.k != b->set.k || a->set.canonical != b->set.canonical) {
+    *v.err = "mhap_kmer_set_compare: the sets differ in k or in canonical (" + std::to_string(a->set.k) + "/" + std::to_string(a->set.canonical) + " against " +
+             std::to_string(b->set.k) + "/" + std::to_string(b->set.canonical) + ")";
+    return MHAP_E_INVALID;
+  }
+  int64_t c[3] = {0, 0, 0};
+  const int rc = kmer_set_compare(v, a->set, b->set, c);
+  if (rc != MHAP_OK) return rc;
+  if (a_members) *a_members = c[0];
+  if (b_members) *b_members = c[1];
+  if (both) *both = c[2];
+  return MHAP_OK;
+}
+
+int mhap_kmer_eval_reads(mhap_handle* h, const mhap_kmer_set* s, const char* bases, const int64_t* offsets, const int32_t* lengths, int64_t n, mhap_kmer_eval** out) {
+  if (!h) return MHAP_E_INVALID;
+  HandleView v = handle_view(h);
+  if (!ks_usable(v, s, "mhap_kmer_eval_reads")) return MHAP_E_INVALID;
+  if (!out || n < 0 || (n > 0 && (!bases || !offsets || !lengths))) { *v.err = "mhap_kmer_eval_reads: null argument"; return MHAP_E_INVALID; }
+  for (int64_t i = 0; i < n; i++) if (lengths[i] < 0 || offsets[i] < 0) { *v.err = "mhap_kmer_eval_reads: negative sequence length or offset"; return MHAP_E_INVALID; }
+  mhap_kmer_eval* e = new mhap_kmer_eval();
+  e->eval.k = s->set.k;
+  const int rc = pack_read_groups(bases, offsets, lengths, n, [&](const ReadDesc* descs, int64_t count, const void* packed, size_t bytes) {
+    return kmer_eval_group(v, s->set, descs, count, packed, bytes, e->eval);
+  });
+  kmer_eval_done(v, e->eval);
+  if (rc != MHAP_OK) { delete e; return rc; }
+  *out = e;
+  return MHAP_OK;
+}
+
+int mhap_kmer_eval_scan(mhap_handle* h, const mhap_kmer_set* s, const mhap_fasta_scan* scan, mhap_kmer_eval** out) {
+  if (!h) return MHAP_E_INVALID;
+  HandleView v = handle_view(h);
+  if (!ks_usable(v, s, "mhap_kmer_eval_scan")) return MHAP_E_INVALID;
+  if (!out || !scan) { *v.err = "mhap_kmer_eval_scan: null argument"; return MHAP_E_INVALID; }
+  (void)hipSetDevice(v.device);
+  mhap_kmer_eval* e = new mhap_kmer_eval();
+  e->eval.k = s->set.k;
+  std::string err;
+  const int rc = ingest_pipeline(scan->impl, 0, 1, 0, false, [&](Slot& sl) {
+    return kmer_eval_group(v, s->set, sl.descs.data(), (int64_t)sl.descs.size(), sl.pin, sl.bytes, e->eval);
+  }, err);
+  kmer_eval_done(v, e->eval);
+  if (rc != MHAP_OK) { if (!err.empty()) *v.err = err; delete e; return rc; }
+  *out = e;
+  return MHAP_OK;
+}
+
+void mhap_kmer_eval_free(mhap_kmer_eval* e) { delete e; }
+
+int mhap_kmer_eval_info(const mhap_kmer_eval* e, int64_t* sequences, int64_t* intervals, int32_t* k, int64_t* totals) {
+  if (!e) return MHAP_E_INVALID;
+  const KmerEval& E = e->eval;
+  if (sequences) *sequences = (int64_t)(E.rows.size() / 5);
+  if (intervals) *intervals = (int64_t)(E.intervals.size() / 3);
+  if (k) *k = E.k;
+  if (totals) {
+    for (int f = 0; f < 5; f++) totals[f] = 0;
+    for (size_t i = 0; i < E.rows.size(); i++) totals[i % 5] += E.rows[i];
+  }
+  return MHAP_OK;
+}
+
+int mhap_kmer_eval_rows(const mhap_kmer_eval* e, int64_t* rows) {
+  if (!e) return MHAP_E_INVALID;
+  if (rows && !e->eval.rows.empty()) memcpy(rows, e->eval.rows.data(), e->eval.rows.size() * 8);
+  return MHAP_OK;
+}
+
+int mhap_kmer_eval_intervals(const mhap_kmer_eval* e, int64_t* intervals) {
+  if (!e) return MHAP_E_INVALID;
+  if (intervals && !e->eval.intervals.empty()) memcpy(intervals, e->eval.intervals.data(), e->eval.intervals.size() * 8);
+  return MHAP_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// name i of `names` (NUL-terminated, back to back), or seq<i + 1> without names; `at` walks the names
+std::string ke_name(const char*& at, int64_t i) {
+  if (!at) return "seq" + std::to_string(i + 1);
+  std::string s(at);
+  at += s.size() + 1;
+  return s;
+}
+bool ke_table_line(FILE* f, const std::string& name, const int64_t* r, int k) {
+  double err = 0.0, qv = 0.0;
+  (void)mhap_kmer_qv(r[1], r[2], k, &err, &qv);
+  return fprintf(f, "%s\t%lld\t%lld\t%lld\t%lld\t%lld\t%.6e\t%.2f\n", name.c_str(), (long long)r[0], (long long)r[1], (long long)r[2], (long long)r[3],
+                 (long long)r[4], err, qv) > 0;
+}
+}  // namespace
+
+extern "C" {
+
+int mhap_kmer_eval_write_table(const mhap_kmer_eval* e, const char* names, const char* path) {
+  if (!e || !path) return MHAP_E_INVALID;
+  FILE* f = fopen(path, "w");
+  if (!f) return MHAP_E_IO;
+  std::vector<char> buf(1 << 20);
+  setvbuf(f, buf.data(), _IOFBF, buf.size());
+  const KmerEval& E = e->eval;
+  int64_t tot[5] = {0, 0, 0, 0, 0};
+  bool ok = true;
+  const char* at = names;
+  for (size_t i = 0; i * 5 < E.rows.size() && ok; i++) {
+    const int64_t* r = E.rows.data() + i * 5;
+    for (int j = 0; j < 5; j++) tot[j] += r[j];
+    ok = ke_table_line(f, ke_name(at, (int64_t)i), r, E.k);
+  }
+  ok = ok && ke_table_line(f, "total", tot, E.k);
+  ok = (fclose(f) == 0) && ok;
+  return ok ? MHAP_OK : MHAP_E_IO;
+}
+
+int mhap_kmer_eval_write_bed(const mhap_kmer_eval* e, const char* names, const char* path) {
+  if (!e || !path) return MHAP_E_INVALID;
+  FILE* f = fopen(path, "w");
+  if (!f) return MHAP_E_IO;
+  std::vector<char> buf(1 << 20);
+  setvbuf(f, buf.data(), _IOFBF, buf.size());
+  const KmerEval& E = e->eval;
+  bool ok = true;
+  const char* at = names;
+  int64_t named = -1;   // the sequence `name` belongs to (intervals are in sequence order)
+  std::string name;
+  for (size_t i = 0; i * 3 < E.intervals.size() && ok; i++) {
+    const int64_t* iv = E.intervals.data() + i * 3;
+    while (named < iv[0]) name = ke_name(at, ++named);
+    ok = fprintf(f, "%s\t%lld\t%lld\n", name.c_str(), (long long)iv[1], (long long)iv[2]) > 0;
+  }
+  ok = (fclose(f) == 0) && ok;
+  return ok ? MHAP_OK : MHAP_E_IO;
+}
+
+int mhap_kmer_eval_summary(const mhap_kmer_eval* e, const mhap_kmer_set* reads, const mhap_kmer_set* own, int64_t both, char* line, size_t cap) {
+  if (!e || !reads || !line || cap == 0) return MHAP_E_INVALID;
+  int64_t n = 0, t[5];
+  (void)mhap_kmer_eval_info(e, &n, nullptr, nullptr, t);
+  double err = 0.0, qv = 0.0;
+  (void)mhap_kmer_qv(t[1], t[2], e->eval.k, &err, &qv);
+  std::string s(512, 0);
+  int w = snprintf(&s[0], s.size(), "Assessed %lld sequences, %lld bases against %lld solid %d-mers (count >= %llu): %lld windows, %lld missing in %lld runs, "
+                   "%lld unsupported bases, QV %.2f", (long long)n, (long long)t[0], (long long)reads->set.members, (int)reads->set.k,
+                   (unsigned long long)reads->set.min_count, (long long)t[1], (long long)t[2], (long long)t[3], (long long)t[4], qv);
+  s.resize((size_t)std::max(w, 0));
+  if (own) {
+    char c[160];
+    const double comp = reads->set.members > 0 ? (double)both / (double)reads->set.members : std::numeric_limits<double>::quiet_NaN();
+    snprintf(c, sizeof c, "; completeness %.6f (%lld of the solid %d-mers are among the sequences' %lld)", comp, (long long)both, (int)reads->set.k,
+             (long long)own->set.members);
+    s += c;
+  }
+  snprintf(line, cap, "%s", s.c_str());
+  return MHAP_OK;
+}
 
 }  // extern "C"

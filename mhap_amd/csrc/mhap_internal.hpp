@@ -153,6 +153,26 @@ int kmer_count_k(const KmerCountState& S);
 uint64_t kmer_count_index_gen(const KmerCountState& S);
 uint64_t kmer_count_budget(const KmerCountState& S);   // windows staged before a flush
 void kmer_count_release(KmerCountState* S);
+// Sequence assessment (kmer_kernels.hip).  The set made from an open count: a bitmap of 4^k bits on `device`, bit v = (count of v >= min_count).
+struct KmerSet {
+  int k = 0, canonical = 0, device = 0;
+  void* bits = nullptr; size_t bytes = 0;   // (a multiple of 16 bytes, zero past 4^k bits)
+  int64_t total = 0, distinct = 0, members = 0;
+  uint64_t min_count = 0;
+};
+// sequences walked against a set: rows of 5 (bases, windows, missing, runs, unsupported) and intervals of 3 (sequence, begin, end)
+struct KmerEval {
+  int k = 0;
+  std::vector<int64_t> rows, intervals;
+  DevBuf scratch[9];   // device buffers of kmer_eval_group, kept from group to group of one call
+};
+int kmer_count_finish_set(KmerCountState& S, const HandleView& v, uint64_t min_count, KmerSet& out);   // (the count itself is left as it was)
+void kmer_set_release(KmerSet& s);
+int kmer_set_contains(const HandleView& v, const KmerSet& s, const uint64_t* values, int64_t n, uint8_t* out);
+int kmer_set_compare(const HandleView& v, const KmerSet& a, const KmerSet& b, int64_t counts[3]);
+// one group of sequences, packed as kmer_count_add_group takes them; its rows and intervals are appended to out
+int kmer_eval_group(const HandleView& v, const KmerSet& s, const ReadDesc* descs, int64_t n, const void* packed, size_t bytes, KmerEval& out);
+void kmer_eval_done(const HandleView& v, KmerEval& e);   // after the last group of a call, failed or not: frees the device buffers
 int internal_sketch_queries(mhap_handle* h, const char* bases, const int64_t* offsets, const int32_t* lengths, int64_t n, void* d_mh, void* d_od, void* d_mt);
 
 }  // namespace mhap

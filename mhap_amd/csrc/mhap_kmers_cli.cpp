@@ -20,12 +20,18 @@ namespace {
 
 const char* USAGE =
     "Usage: mhap-hip-kmers -o <output file> [-k 16] [--no-rc] [--min-fraction 2.5e-6] [--histogram <file>] [--device 0] <FASTA file or directory> ...\n"
-    "  -o               the k-mer filter file to write (the -f file of mhap-hip)\n"
+    "       mhap-hip-kmers --assess <FASTA> [--assess-min-count 0] [--assess-table <file>] [--assess-bed <file>] [-o ...] [-k 16] [--no-rc] <FASTA file or directory> ...\n"
+    "  -o               the k-mer filter file to write (the -f file of mhap-hip; optional with --assess)\n"
     "  -k               k-mer size, 1 to 16 (default 16)\n"
     "  --no-rc          count k-mers as they are read instead of canonical (the smaller of a k-mer and its reverse complement)\n"
     "  --min-fraction   write the k-mers whose share of all counted k-mers is at least this (default 2.5e-6)\n"
     "  --histogram      also write the k-mer count histogram, \"<count>\\t<number of k-mers>\" per line in ascending count\n"
     "                   (what `python -m mhap_amd.histogram_stats <file> <percent>` reads to help choose --min-fraction)\n"
+    "  --assess         assess the sequences of this FASTA file against the k-mers of the inputs: k-mers of the sequences that the reads\n"
+    "                   do not support (a consensus QV) and solid k-mers of the reads that the sequences lack (completeness)\n"
+    "  --assess-min-count  a k-mer of the reads is solid when it is counted at least this often (default 0: the valley of the count histogram)\n"
+    "  --assess-table   write \"name\\tbases\\twindows\\tmissing\\truns\\tunsupported\\terror\\tqv\" per sequence and a total line\n"
+    "  --assess-bed     write \"name\\tbegin\\tend\" per stretch of bases that no supported k-mer covers\n"
     "  --device         HIP device ordinal (default 0)\n";
 
 [[noreturn]] void die(const std::string& m) {
@@ -53,8 +59,9 @@ bool parse_double(const char* s, double& v) { char* e = nullptr; v = strtod(s, &
 }  // namespace
 
 int main(int argc, char** argv) {
-  std::string out, histogram;
-  long k = 16, device = 0;
+  std::string out, histogram, assess, assess_table, assess_bed;
+  long k = 16, device = 0, assess_min_count = 0;
+  bool assess_options = false;
   double min_fraction = 2.5e-6;
   bool rc = true;
   std::vector<std::string> inputs;
@@ -67,11 +74,17 @@ int main(int argc, char** argv) {
     else if (s == "--no-rc") rc = false;
     else if (s == "--histogram") histogram = value();
     else if (s == "--min-fraction") { if (!parse_double(value(), min_fraction)) die("--min-fraction takes a number"); }
+    else if (s == "--assess") assess = value();
+    else if (s == "--assess-min-count") { assess_options = true; if (!parse_int(value(), assess_min_count) || assess_min_count < 0) die("--assess-min-count takes an integer that is not negative"); }
+    else if (s == "--assess-table") { assess_options = true; assess_table = value(); }
+    else if (s == "--assess-bed") { assess_options = true; assess_bed = value(); }
     else if (s == "--device") { if (!parse_int(value(), device) || device < 0) die("--device takes a device ordinal"); }
     else if (!s.empty() && s[0] == '-') die("unknown option " + s);
     else inputs.push_back(s);
   }
-  if (out.empty()) die("no output file (-o)");
+  if (assess_options && assess.empty()) die("--assess-min-count, --assess-table and --assess-bed go with --assess <FASTA>");
+  if (out.empty() && assess.empty()) die("no output file (-o)");
+  if (out.empty() && !histogram.empty()) die("--histogram goes with -o");
   if (inputs.empty()) die("no input file");
   if (k < 1 || k > 16) die("k-mer size must be from 1 to 16 (got " + std::to_string(k) + ")");
   const double t0 = now();
@@ -99,19 +112,60 @@ int main(int argc, char** argv) {
       t_scan += b - a; t_count += now() - b;
     }
   }
-  mhap_kmer_counts* c = nullptr;
-  chk(mhap_kmer_count_finish_flags(h, min_fraction, histogram.empty() ? 0u : (uint32_t)MHAP_KMER_HISTOGRAM, &c));
   int64_t total = 0, distinct = 0, lines = 0;
   int32_t kk = 0;
-  mhap_kmer_counts_info(c, &total, &distinct, &lines, &kk);
-  const double tw = now();
-  const int w = mhap_kmer_counts_write(c, out.c_str());
-  const int wh = w != MHAP_OK || histogram.empty() ? MHAP_OK : mhap_kmer_counts_write_histogram(c, histogram.c_str());
-  mhap_kmer_counts_free(c);
+  double tw = 0.0, tw1 = 0.0;
+  if (!out.empty()) {   // with --assess the count stays open: the set is made from the same count of the reads
+    mhap_kmer_counts* c = nullptr;
+    chk(mhap_kmer_count_finish_flags(h, min_fraction, (histogram.empty() ? 0u : (uint32_t)MHAP_KMER_HISTOGRAM) | (assess.empty() ? 0u : (uint32_t)MHAP_KMER_KEEP_OPEN), &c));
+    mhap_kmer_counts_info(c, &total, &distinct, &lines, &kk);
+    tw = now();
+    const int w = mhap_kmer_counts_write(c, out.c_str());
+    const int wh = w != MHAP_OK || histogram.empty() ? MHAP_OK : mhap_kmer_counts_write_histogram(c, histogram.c_str());
+    mhap_kmer_counts_free(c);
+    tw1 = now();
+    if (w != MHAP_OK) { fprintf(stderr, "mhap-hip-kmers: cannot write %s\n", out.c_str()); mhap_destroy(h); return 1; }
+    if (wh != MHAP_OK) { fprintf(stderr, "mhap-hip-kmers: cannot write %s\n", histogram.c_str()); mhap_destroy(h); return 1; }
+  }
+  char line[1024] = {0};
+  if (!assess.empty()) {
+    mhap_kmer_set *solid = nullptr, *own = nullptr;
+    chk(mhap_kmer_count_finish_set(h, (uint64_t)assess_min_count, &solid));
+    if (out.empty()) {
+      int64_t members = 0; int32_t canonical = 0; uint64_t mc = 0;
+      mhap_kmer_set_info(solid, &total, &distinct, &members, &kk, &canonical, &mc);
+    }
+    mhap_fasta_scan* s = nullptr;
+    if (mhap_fasta_scan_open(assess.c_str(), 0, &s, err, sizeof err) != MHAP_OK) { fprintf(stderr, "mhap-hip-kmers: %s\n", err); mhap_kmer_set_free(solid); mhap_destroy(h); return 1; }
+    mhap_kmer_eval* ev = nullptr;
+    int64_t both = 0;
+    int r = mhap_kmer_eval_scan(h, solid, s, &ev);
+    // completeness: the set of the sequences' own k-mers (every one of them: count >= 1) against the solid set
+    if (r == MHAP_OK) r = mhap_kmer_count_begin(h, (int32_t)k, rc ? 1 : 0);
+    if (r == MHAP_OK) r = mhap_kmer_count_add_scan(h, s);
+    if (r == MHAP_OK) r = mhap_kmer_count_finish_set(h, 1, &own);
+    if (r == MHAP_OK) r = mhap_kmer_set_compare(h, solid, own, nullptr, nullptr, &both);
+    const char* names = nullptr;
+    if (r == MHAP_OK) r = mhap_fasta_scan_info(s, nullptr, nullptr, &names, nullptr);
+    std::string failed;
+    if (r == MHAP_OK && !assess_table.empty() && mhap_kmer_eval_write_table(ev, names, assess_table.c_str()) != MHAP_OK) failed = assess_table;
+    if (r == MHAP_OK && failed.empty() && !assess_bed.empty() && mhap_kmer_eval_write_bed(ev, names, assess_bed.c_str()) != MHAP_OK) failed = assess_bed;
+    if (r == MHAP_OK) (void)mhap_kmer_eval_summary(ev, solid, own, both, line, sizeof line);
+    if (r != MHAP_OK) fprintf(stderr, "mhap-hip-kmers: %s (code %d)\n", mhap_last_error(h), r);
+    if (!failed.empty()) fprintf(stderr, "mhap-hip-kmers: cannot write %s\n", failed.c_str());
+    mhap_kmer_eval_free(ev);
+    mhap_fasta_scan_free(s);
+    mhap_kmer_set_free(own);
+    mhap_kmer_set_free(solid);
+    if (r != MHAP_OK || !failed.empty()) { mhap_destroy(h); return 1; }
+  }
   mhap_destroy(h);
-  if (w != MHAP_OK) { fprintf(stderr, "mhap-hip-kmers: cannot write %s\n", out.c_str()); return 1; }
-  if (wh != MHAP_OK) { fprintf(stderr, "mhap-hip-kmers: cannot write %s\n", histogram.c_str()); return 1; }
-  fprintf(stderr, "Counted %lld %d-mers (%lld distinct) in %lld reads, %.1f Mbase; wrote %lld lines to %s; total %.3f s (scan %.3f s, count %.3f s, write %.3f s)\n",
-          (long long)total, (int)kk, (long long)distinct, (long long)reads, bases / 1e6, (long long)lines, out.c_str(), now() - t0, t_scan, t_count, now() - tw);
+  if (!out.empty())
+    fprintf(stderr, "Counted %lld %d-mers (%lld distinct) in %lld reads, %.1f Mbase; wrote %lld lines to %s; total %.3f s (scan %.3f s, count %.3f s, write %.3f s)\n",
+            (long long)total, (int)kk, (long long)distinct, (long long)reads, bases / 1e6, (long long)lines, out.c_str(), now() - t0, t_scan, t_count, tw1 - tw);
+  else
+    fprintf(stderr, "Counted %lld %d-mers (%lld distinct) in %lld reads, %.1f Mbase; total %.3f s (scan %.3f s, count %.3f s)\n", (long long)total, (int)kk,
+            (long long)distinct, (long long)reads, bases / 1e6, now() - t0, t_scan, t_count);
+  if (!assess.empty()) fprintf(stderr, "%s\n", line);
   return 0;
 }
