@@ -490,37 +490,42 @@ def test_bench_dump_outputs_is_canonical_and_capped(tmp_path):
         assert got <= set(zip(*(recs[f].astype(np.float64).tolist() for f in bench.DUMP_FIELDS))) and len(got) == want
 
 
-def test_early_reject_table_of_the_second_stage_is_exact():
-    """The join kernel ends a pair early when its joined k-mers inside both windows (an upper bound of the intersection) are fewer than
-    pass_min[lower bound of its k]: pass_min[k] must be the smallest intersection that reaches --threshold for ANY k' >= k, read off the
-    identity table the kernel scores with — and that table must be the oracle's jaccardToIdentity bit for bit (BottomOverlapSketch.java:391-395)."""
+def _assert_early_reject_table(S, k2, rows, thresholds=(0.0, 0.3, 0.78, 0.95, 1.0)):
+    """mhap_selftest_pass_min at sketch size S and ordered k-mer size k2: the identity table's `rows` equal the oracle's jaccardToIdentity bit for
+    bit, pass_min equals the brute-force suffix minimum at every threshold, and the acceptance property the join kernel relies on holds."""
     lib = api.load_library()
-    S, k2 = 200, 12
     f = O.lib().orc_jaccard_to_identity
     f.restype = C.c_double
-    for thr in (0.0, 0.3, 0.78, 0.95, 1.0):
+    for thr in thresholds:
         scores = np.zeros((S + 1) * (S + 2) // 2, dtype=np.float64)
         pm = np.zeros(S + 2, dtype=np.int32)
         assert lib.mhap_selftest_pass_min(C.c_int32(S), C.c_int32(k2), C.c_double(thr), scores.ctypes.data_as(C.c_void_p), pm.ctypes.data_as(C.c_void_p)) == 0
         first = np.full(S + 1, np.iinfo(np.int32).max, dtype=np.int64)         # per k: the smallest inter with score >= thr (brute force)
         for k in range(S + 1):
             row = scores[k * (k + 1) // 2:k * (k + 1) // 2 + k + 1]
-            if k in (0, 1, 7, 64, S):
+            if k in rows:
                 want = [f(C.c_double(0.0 if k == 0 else i / k), C.c_int(k2)) for i in range(k + 1)]
-                assert np.array_equal(row.view(np.uint64), np.array(want, dtype=np.float64).view(np.uint64)), k
+                assert np.array_equal(row.view(np.uint64), np.array(want, dtype=np.float64).view(np.uint64)), (S, k2, k)
             ok = np.nonzero(row >= thr)[0]
             if len(ok):
                 first[k] = ok[0]
         suffix = np.minimum.accumulate(first[::-1])[::-1]                      # min over k' >= k
-        assert np.array_equal(pm[:S + 1].astype(np.int64), suffix), thr
+        assert np.array_equal(pm[:S + 1].astype(np.int64), suffix), (S, k2, thr)
         # the property the kernel relies on: an accepted (inter, k) is never below pass_min of any lower bound of k
         for k in range(S + 1):
             row = scores[k * (k + 1) // 2:k * (k + 1) // 2 + k + 1]
             acc = np.nonzero(row >= thr)[0]
             if len(acc):
-                assert acc.min() >= pm[:k + 1].max() or acc.min() >= pm[k], (thr, k)
+                assert acc.min() >= pm[:k + 1].max() or acc.min() >= pm[k], (S, k2, thr, k)
                 assert all(acc.min() >= pm[kl] for kl in range(0, k + 1, max(1, k // 7)))
-    assert pm[S + 1] == np.iinfo(np.int32).max
+        assert pm[S + 1] == np.iinfo(np.int32).max
+
+
+def test_early_reject_table_of_the_second_stage_is_exact():
+    """The join kernel ends a pair early when its joined k-mers inside both windows (an upper bound of the intersection) are fewer than
+    pass_min[lower bound of its k]: pass_min[k] must be the smallest intersection that reaches --threshold for ANY k' >= k, read off the
+    identity table the kernel scores with — and that table must be the oracle's jaccardToIdentity bit for bit (BottomOverlapSketch.java:391-395)."""
+    _assert_early_reject_table(200, 12, rows=(0, 1, 7, 64, 200))
 
 
 def test_second_stage_lane_on_error_free_overlaps_takes_the_bounded_selection():
