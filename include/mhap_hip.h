@@ -1150,6 +1150,64 @@ int mhap_select_apply(mhap_select_session* s, const mhap_record* in, int64_t n, 
 int mhap_select_judge_record(const mhap_record* in, const mhap_select_params* params, uint32_t* keys /* 2 */);
 void mhap_select_free(mhap_select_session* s);
 
+/* ---- homopolymer compression: every run of equal bytes collapsed to one, the map back kept, records carried to raw coordinates ---- */
+
+/* The step in front of the search for reads whose commonest error is the wrong length of a homopolymer run (what minimap2 -H, Canu's
+ * HiFi mode, Flye and hifiasm do): the reads are sketched and searched with every run collapsed to one base, and what is found is
+ * carried back through the map, so that the realignment and every stage behind it see raw reads and raw coordinates.
+ *
+ * The reads.  Read r is its lengths[r] bytes at bases + offsets[r], taken as they are: offsets in any order, overlapping, unaligned
+ * (the table of trimmed reads is such a table).  MHAP_E_INVALID, the read named in the message, for a negative length or a read that
+ * does not lie in [0, n_bases); lengths above 2^31 - 9 and 2^30 reads or more are refused as every table of reads refuses them.
+ *
+ * Heads.  Position p of a read is a head iff p = 0 or byte[p] != byte[p - 1].  Equality is equality of bytes: runs of N collapse, a and
+ * A differ.  The byte in front of a read's first base never matters (it belongs to another read, or to nobody).
+ *
+ * Result.  The compressed read is its head bytes in order; clen is their number.  The map start[0 .. clen] holds the raw position of
+ * every head, and start[clen] = L, the raw length: compressed position p stands for the raw run [start[p], start[p + 1]).  An empty
+ * read compresses to an empty read with start = {0}.  The compressed reads lie back to back in read order, coff[r + 1] = coff[r] +
+ * clen[r] with coff[0] = 0, and the map of read r is the clen[r] + 1 int32 at starts + coff[r] + r.  MHAP_HPC_COUNTS int64 counts:
+ * reads, raw bases, compressed bases, runs longer than 1, the longest run, empty reads.
+ *
+ * Records.  Two functions of a read's map, for any int32 p:
+ *     p < 0: lo(p) = hi(p) = -1        0 <= p < clen: lo(p) = start[p], hi(p) = start[p + 1] - 1        p >= clen: lo(p) = hi(p) = L
+ * A record in compressed coordinates expands to a1' = lo_from(a1), a2' = hi_from(a2), b1' = lo_to(b1), b2' = hi_to(b2), alen' and blen'
+ * the raw lengths; ids, score, raw and to_rc are copied.  b1 and b2 are taken as the record holds them, that is after MatchResult's
+ * flip (J/impl/MatchResult.java:54-57: b1 = blen - b2 - 1, b2 = blen - b1 - 1 when to_rc), and no case is made of to_rc, because the
+ * rule is symmetric under the flip: compression commutes with the reverse complement (a run stays a run), so position p of the
+ * reversed compressed read is position clen - p - 1 of the forward one and stands for the raw run [L - hi(p) - 1, L - lo(p) - 1] of the
+ * forward read, which reads  L - hi_rc(p) - 1 = lo(clen - p - 1)  and  L - lo_rc(p) - 1 = hi(clen - p - 1).  Expanding the flipped ends
+ * on the forward map therefore gives the flip of the ends expanded on the reversed map.  The edge values obey the same equations: the
+ * second stage may give a2 or b2 = clen (J/sketch/BottomOverlapSketch.java:131-134), which the flip turns into -1, and lo(-1) = -1 =
+ * L - hi(clen) - 1, hi(clen) = L = L - lo(-1) - 1.  tests/hpc_ref.py restates all of it.
+ *
+ * The calls.  mhap_hpc_compress does it on the GPU (hpc_kernels.hip: two passes over tiles of MHAP_HPC_TILE positions and a scan of the
+ * tiles' head counts in blocks of MHAP_HPC_SCAN_BLOCK, for groups of whole reads of at most group_bases raw bases each; 0: 2^28, at
+ * most 2^30; a longer read is a group of its own; the result does not depend on it) and leaves the compressed reads and the maps on
+ * the device with the object; the handle must outlive the object, whose errors are the handle's (mhap_last_error).  mhap_hpc_info
+ * gives the counts, mhap_hpc_copy the arrays (any pointer may be NULL).  mhap_hpc_expand_records expands n records on the device, one
+ * lane per record: the `from` reads are looked up by id in from_side, the `to` reads in to_side (NULL: from_side; another object must be
+ * of the same device); MHAP_E_INVALID, the record named in the message, for an id that its side does not have or an alen / blen that
+ * is not that read's clen; a refused call writes nothing.  mhap_hpc_expand_record is the rule on the host for one record and explicit
+ * maps: 0, or -1 for a null pointer or a negative clen.  Device memory of an object: 5 bytes per compressed base and 24 per read;
+ * during the compression also the raw bytes, 8 bytes per read and 40 per tile. */
+#define MHAP_HPC_TILE 4096         /* positions per workgroup of the two passes: 256 lanes x 16 bytes */
+#define MHAP_HPC_SCAN_BLOCK 4096   /* tile counts the scan takes at once: 1024 lanes x 4, a carry from block to block */
+#define MHAP_HPC_COUNTS 6
+typedef struct mhap_hpc mhap_hpc;
+int mhap_hpc_compress(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const int64_t* read_ids, const int64_t* offsets,
+                      const int32_t* lengths, int64_t n_reads, int64_t group_bases /* 0: default */, mhap_hpc** out);
+int mhap_hpc_info(const mhap_hpc* c, int64_t* counts /* MHAP_HPC_COUNTS */);
+int mhap_hpc_copy(const mhap_hpc* c, uint8_t* cbases, int64_t* coff /* n + 1 */, int32_t* clen /* n */, int32_t* starts /* compressed + n */);
+int mhap_hpc_expand_records(const mhap_hpc* from_side, const mhap_hpc* to_side /* NULL: the same */, const mhap_record* in, int64_t n,
+                            mhap_record* out);
+int mhap_hpc_expand_record(const mhap_record* in, const int32_t* start_from, int32_t clen_from, const int32_t* start_to, int32_t clen_to,
+                           mhap_record* out);   /* host, no GPU */
+/* milliseconds of the compression that made the object: the upload of the reads, the two passes with the scan, the kernel that sums the run counts up (all
+ * three between HIP events on the handle's stream), and the whole call on the host's clock (tools/hpc_bench.py) */
+int mhap_hpc_times(const mhap_hpc* c, double* ms /* 4 */);
+void mhap_hpc_free(mhap_hpc* c);
+
 /* KmerStatSimulator's pair statistics on the GPU (J/main/KmerStatSimulator.java:163-196).  pairs: n rows of 4 int64 {a_off, a_len,
  * b_off, b_len}; a = bases[a_off, a_off + a_len) is the first read, b the second.  skip: n_skip k-mers of k bytes each, back to back, in
  * any order (the skip set of loadSkipMers; entries of another length never match and are left out by the caller).  For each pair,

@@ -67,6 +67,10 @@ def __getattr__(name):
     if name in ("simulate_pairs", "simulate_reads"):
         from . import kmer_sim
         return getattr(kmer_sim, name)
+    if name in ("hpc", "HpcReads"):   # homopolymer compression, the same way (`python -m mhap_amd.hpc`): hpc.compress, hpc.HpcReads
+        import importlib
+        hpc = importlib.import_module(".hpc", __name__)
+        return hpc if name == "hpc" else hpc.HpcReads
     if name == "assess":   # sequence assessment, the same way (`python -m mhap_amd.kmer_qv`)
         from . import kmer_qv
         return kmer_qv.assess

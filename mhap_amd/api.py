@@ -249,6 +249,13 @@ _PROTOTYPES = {
     "mhap_select_apply": "i:ppqp",
     "mhap_select_judge_record": "i:ppp",
     "mhap_select_free": "v:p",
+    "mhap_hpc_compress": "i:ppqpppqqp",
+    "mhap_hpc_info": "i:pp",
+    "mhap_hpc_copy": "i:ppppp",
+    "mhap_hpc_expand_records": "i:pppqp",
+    "mhap_hpc_expand_record": "i:ppipip",
+    "mhap_hpc_times": "i:pp",
+    "mhap_hpc_free": "v:p",
     "mhap_correct_add_views": "i:ppqpp",
     "mhap_pair_kmer_stats": "i:ppqpqiipqpp",
     "mhap_pair_kmer_stats_paths": "i:pqiqip",
@@ -1045,6 +1052,31 @@ class GraphSession(_ReadsSession):
         a, b, c, d = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
         self._ms._chk(self._lib.mhap_graph_unitigs_info(self._s, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
         return a.value, b.value, c.value, d.value
+
+
+HPC_TILE = 4096         # MHAP_HPC_TILE: the positions a workgroup of the two compression passes takes
+HPC_SCAN_BLOCK = 4096   # MHAP_HPC_SCAN_BLOCK: the tile counts the scan takes at once
+HPC_COUNTS = ("reads", "raw_bases", "compressed_bases", "long_runs", "longest_run", "empty_reads")   # mhap_hpc_info's counts, in order
+
+
+def hpc_counts_line(counts):
+    """The one stderr line of a homopolymer compression (the drivers print the same); counts: the MHAP_HPC_COUNTS values in order."""
+    c = [int(x) for x in counts]
+    return (f"Homopolymer compression: {c[0]} reads ({c[5]} empty), {c[1]} bases compressed to {c[2]}; {c[3]} runs longer than 1, "
+            f"the longest of {c[4]}")
+
+
+def hpc_expand_record(record, start_from, start_to=None):
+    """One record in compressed coordinates carried to raw ones through explicit maps (mhap_hpc_expand_record, no GPU; "homopolymer
+    compression" in include/mhap_hip.h).  start_from, start_to: the clen + 1 entries of the two reads' maps (None: the same read's)."""
+    lib = load_library()
+    rec = np.ascontiguousarray(record, dtype=RECORD_DTYPE).reshape(1)
+    out = np.zeros(1, RECORD_DTYPE)
+    sf = np.ascontiguousarray(start_from, np.int32)
+    st = sf if start_to is None else np.ascontiguousarray(start_to, np.int32)
+    if len(sf) < 1 or len(st) < 1 or lib.mhap_hpc_expand_record(_ptr(rec), _ptr(sf), C.c_int32(len(sf) - 1), _ptr(st), C.c_int32(len(st) - 1), _ptr(out)) != 0:
+        raise MhapError("mhap_hpc_expand_record: a map has at least one entry")
+    return out[0]
 
 
 TRIM_COUNTS = ("reads", "deleted", "cut5", "cut3", "gapped", "bases_in", "bases_kept", "eligible_records")   # mhap_trim_finish's counts

@@ -136,6 +136,52 @@ struct Realigner {
 
 struct Stage { mhap_handle* h = nullptr; bool on = false; double seconds = 0.0; };   // what every stage has: the handle, its flag, its own seconds
 
+// --hpc, in front of the search and of everything behind it: the reads of one side (the index's, or one -q file's) homopolymer-compressed
+// on the GPU and copied back for the sketching under the same ids; the object keeps the maps on the device for the records' way back
+struct HpcSide {
+  mhap_hpc* c = nullptr; int64_t first = 0, n = 0;   // reads [first, first + n) of the table
+  std::vector<uint8_t> bases; std::vector<int64_t> offsets; std::vector<int32_t> lengths;
+};
+struct HpcStage : Stage {
+  Reads own;                      // the raw reads when no pipeline keeps them
+  Reads* reads = &own;
+  HpcSide index, query;
+  bool querying = false;          // the records coming are a -q file's against the index
+  int64_t counts[MHAP_HPC_COUNTS] = {0, 0, 0, 0, 0, 0}, records = 0;
+  std::vector<mhap_record> raw;
+  // reads first .. of the table compressed into s (what s held is freed)
+  void compress(int64_t first, HpcSide& s) {
+    Tick t{seconds};
+    const Reads& R = *reads;
+    mhap_hpc_free(s.c);
+    s.c = nullptr; s.first = first; s.n = R.n() - first;
+    chk(h, mhap_hpc_compress(h, R.bases.data(), (int64_t)R.bases.size(), R.ids.data() + first, R.offsets.data() + first, R.lengths.data() + first, s.n, 0, &s.c));
+    int64_t c[MHAP_HPC_COUNTS];
+    mhap_hpc_info(s.c, c);
+    for (int k = 0; k < MHAP_HPC_COUNTS; k++) counts[k] = k == 4 ? std::max(counts[k], c[k]) : counts[k] + c[k];   // (4: the longest run)
+    s.bases = room<uint8_t>(c[2]); s.offsets = room<int64_t>(s.n + 1); s.lengths = room<int32_t>(s.n);
+    chk(h, mhap_hpc_copy(s.c, s.bases.data(), s.offsets.data(), s.lengths.data(), nullptr));
+  }
+  const int64_t* ids(const HpcSide& s) const { return reads->ids.data() + s.first; }
+  // a batch of found records onto the raw reads, before anything else sees it
+  int expand(const mhap_record*& r, int64_t n) {
+    Tick t{seconds};
+    raw.resize((size_t)n);
+    const int rc = querying ? mhap_hpc_expand_records(query.c, index.c, r, n, raw.data()) : mhap_hpc_expand_records(index.c, nullptr, r, n, raw.data());
+    if (rc != MHAP_OK) { fprintf(stderr, "Exception in mhap-hip: %s (code %d)\n", mhap_last_error(h), rc); return rc; }
+    records += n;
+    r = raw.data();
+    return MHAP_OK;
+  }
+  void finish() {
+    mhap_hpc_free(index.c); mhap_hpc_free(query.c);
+    index.c = query.c = nullptr;
+    fprintf(stderr, "Homopolymer compression: %lld reads (%lld empty), %lld bases compressed to %lld; %lld runs longer than 1, the longest of %lld\n", ll(counts[0]),
+            ll(counts[5]), ll(counts[1]), ll(counts[2]), ll(counts[3]), ll(counts[4]));
+    fprintf(stderr, "Time (s) to compress the reads and expand %lld overlaps: %g\n", ll(records), seconds);
+  }
+};
+
 // --correct: every kept record votes on both of its reads, or (add_selected) with the views the selection kept
 struct CorrectStage : Stage {
   std::string fasta; int32_t min_cov = 0; mhap_correct_session* s = nullptr;

@@ -180,4 +180,12 @@ void launch_overlap_join(hipStream_t st, int level, int shape, int nblocks, int 
 void launch_poshist(hipStream_t st, const int32_t* ordered, int64_t stride, const int32_t* meta, int64_t n, uint16_t* out);
 constexpr int POSHIST_BINS = 64;
 
+// ---- hpc_kernels.hip ----
+// Homopolymer compression ("homopolymer compression" in include/mhap_hip.h).  Its kernels — count_kernel and write_kernel over tiles of
+// MHAP_HPC_TILE positions, scan_kernel over MHAP_HPC_SCAN_BLOCK tile counts at a time, reads_kernel, stats_kernel and expand_kernel —
+// are launched by the mhap_hpc_* entry points of the same file on the handle's stream, as the sessions' kernels are; the rules they
+// share with the host are hpc_common.hpp's.
+constexpr int HPC_TILE_THREADS = 256;    // one 16-byte load per lane and tile
+constexpr int HPC_SCAN_THREADS = 1024;   // four tile counts per lane and scan block
+
 }  // namespace mhap

@@ -47,6 +47,7 @@ struct Options {
       if (n.compare(0, 6, "--trim") == 0 && !b("--trim")) continue;
       if (n.compare(0, 8, "--repeat") == 0 && !b("--repeat-filter")) continue;
       if (n.compare(0, 6, "--best") == 0 && !isset("--best-overlaps")) continue;
+      if (n == "--hpc" && !b("--hpc")) continue;
       t += n + " = " + m.at(n).value + "\n";
     }
     return t;
@@ -138,10 +139,12 @@ void collect_headers(mhap_fasta_scan* sc) {
 // the file the index is built from is mapped and scanned while the HIP runtime comes up
 struct Preload { std::string path; mhap_fasta_scan* scan = nullptr; } g_preload;
 // stdout: with --realign every batch goes through the pipeline first and what it keeps is printed, as 12 columns or as PAF
-struct Sink { Writer out{stdout}; Pipeline* pipeline = nullptr; };
+// with --hpc every batch is first carried from compressed to raw coordinates
+struct Sink { Writer out{stdout}; Pipeline* pipeline = nullptr; HpcStage* hpc = nullptr; };
 int sink_cb(const mhap_record* r, int64_t n, void* user) {
   Sink* s = (Sink*)user;
   const Batch* b = nullptr;
+  if (s->hpc && n > 0 && s->hpc->expand(r, n) != MHAP_OK) return 1;
   if (s->pipeline && n > 0) {
     if (!(b = s->pipeline->batch(r, n))) return 1;
     r = b->out.data(); n = b->k;
@@ -338,6 +341,7 @@ void declare_options(Options& o) {
   o.add("--best-overlaps", "[int] With --realign: select each read's N best overlaps on the GPU, by the matches counted on that read, ties at the last place included; with --correct only the selected views of an overlap vote. The overlaps printed, --realign-paf, --gfa and --trim stay on all overlaps. 0) off. Self overlaps only (no -q), one GPU.", "0");
   o.add("--best-min-span", "[int] With --best-overlaps, the shortest aligned interval on a read that counts as evidence for it.", "500");
   o.add("--best-table", "With --best-overlaps, write one line per read to this file: read_id entries kept threshold.", "");
+  o.add("--hpc", "Search with homopolymer-compressed reads: every read of -s and -q is read whole, each run of equal bases is collapsed to one on the GPU, the compressed reads are sketched and searched, and every overlap found is carried back to the raw reads before it is printed or handed to --realign. Columns 5 to 12 are raw coordinates and raw lengths; columns 3 and 4 are the compressed sketches'. -k, --min-olap-length, --min-store-length and the -f file apply to the compressed reads: make the -f file with mhap-hip-kmers --hpc. FASTA input, one GPU.", "false", true);
   o.add("--trim-fasta", "With --trim, write the trimmed reads to this FASTA file; deleted reads are left out.", "");
   o.add("--trim-table", "With --trim, write one line per read to this file: id length begin end runs covered flags.", "");
 }
@@ -434,6 +438,13 @@ std::vector<int32_t> check_options(Options& o) {
     for (const char* n : {"--trim-fasta", "--trim-table"})
       if (o.isset(n) && o.s(n).empty()) bad(std::string(n) + " needs the name of the file to write.");
   }
+  if (o.b("--hpc")) {
+    if (!o.s("-p").empty()) bad("--hpc compresses the reads of a search: it does not go with -p.");
+    bool dat = ends_with(o.s("-s"), ".dat");
+    if (!o.s("-q").empty()) for (const std::string& cf : list_files(o.s("-q"))) dat = dat || ends_with(cf, ".dat");
+    if (dat) bad("--hpc needs the reads' bases: give FASTA files, not .dat sketches.");
+    if (n_devs > 1) bad("--hpc runs on one GPU: give one device (--gpus 1).");
+  }
   if (o.b("--realign") && o.s("-p").empty()) {
     if (o.i("--realign-band") < 0) bad("The realignment band must be >=0.");
     if (n_devs > 1) bad("--realign runs on one GPU: give one device (--gpus 1).");
@@ -455,7 +466,7 @@ Engine create_engine(const Options& o, mhap_params& P, std::vector<int32_t>& dev
     if (devs.size() == 1) { P.device = devs[0]; rc_create = mhap_create(&P, &E.h, err, sizeof err); }
     else rc_create = mhap_group_create(&P, devs.data(), (int32_t)devs.size(), &E.g, err, sizeof err);
   });
-  if (!precompute && !is_dir(o.s("-s")) && !ends_with(o.s("-s"), ".dat")) {
+  if (!precompute && !o.b("--hpc") && !is_dir(o.s("-s")) && !ends_with(o.s("-s"), ".dat")) {
     char perr[512] = {0};
     if (mhap_fasta_scan_open(o.s("-s").c_str(), 0, &g_preload.scan, perr, sizeof perr) == MHAP_OK) g_preload.path = o.s("-s");
     else g_preload.scan = nullptr;
@@ -490,7 +501,7 @@ void precompute_dat(const Engine& E, const Options& o, const mhap_params& P) {
 // --realign: the reads of -s (ids as the index assigned them: FastaData's running count), every stage's parameters from its flags, and the sessions that begin before the search
 void begin_pipeline(const Options& o, mhap_handle* h, Pipeline& p) {
   char err[512] = {0};
-  for (const std::string& sf : list_files(o.s("-s"))) {
+  for (const std::string& sf : p.reads.n() > 0 ? std::vector<std::string>() : list_files(o.s("-s"))) {   // (--hpc has read them already)
     mhap_fasta fa;
     if (mhap_fasta_read(sf.c_str(), p.reads.n(), &fa, err, sizeof err) != MHAP_OK) die(err);
     p.reads.add(fa);
@@ -515,6 +526,26 @@ void begin_pipeline(const Options& o, mhap_handle* h, Pipeline& p) {
   p.graph.clean = o.b("--gfa-clean"); p.graph.cp.tip_reads = o.i("--gfa-tip-reads"); p.graph.cp.bubble_bases = o.i("--gfa-bubble-bases"); p.graph.cp.max_rounds = o.i("--gfa-clean-rounds");
   p.graph.consensus = o.b("--gfa-consensus"); p.graph.consensus_fasta = o.s("--gfa-consensus-fasta"); mhap_consensus_default_params(&p.graph.kp); p.graph.kp.min_cov = o.i("--gfa-consensus-min-cov");
   p.begin();
+}
+
+// --hpc: the files of -s read whole into the table of reads (ids as the index assigns them), compressed on the GPU, and the compressed
+// reads sketched and indexed under those ids; the reads the index took, as add_file_to_index counts them
+int64_t add_compressed_to_index(const Engine& E, const Options& o, HpcStage& hpc, int64_t* strands) {
+  char err[512] = {0};
+  Reads& R = *hpc.reads;
+  for (const std::string& sf : list_files(o.s("-s"))) {
+    mhap_fasta fa;
+    if (mhap_fasta_read(sf.c_str(), R.n(), &fa, err, sizeof err) != MHAP_OK) die(err);
+    if (g_headers.full) collect_headers(fa);
+    R.add(fa);
+    mhap_fasta_free(&fa);
+  }
+  hpc.compress(0, hpc.index);
+  const HpcSide& s = hpc.index;
+  if (s.n > 0) chk(E.h, mhap_index_add_reads(E.h, (const char*)s.bases.data(), s.offsets.data(), s.lengths.data(), hpc.ids(s), s.n));
+  const mhap_stats st = E.stats();
+  *strands = st.strands_indexed;
+  return st.strands_indexed / 2;
 }
 
 // Usage 1: the index against itself, then every -q file against it (MhapMain.java:453-570)
@@ -544,9 +575,19 @@ void search(const Engine& E, const Options& o, const mhap_params& P, Sink& sink,
       mhap_fasta fa;
       if (mhap_fasta_read(cf.c_str(), seq_processed, &fa, err, sizeof err) != MHAP_OK) die(err);   // id offset = reads so far (MhapMain.java:527)
       if (g_headers.full) collect_headers(fa);
+      const int64_t first = sink.hpc ? sink.hpc->reads->n() : 0;
       if (sink.pipeline) sink.pipeline->reads.add(fa);
+      else if (sink.hpc) sink.hpc->own.add(fa);
       const mhap_stats s0 = E.stats();
-      E.find_reads(fa, sink_cb, &sink);
+      if (sink.hpc) {   // the file's reads compressed, searched as they are then, and every record expanded from this file's maps to the index's
+        HpcStage& H = *sink.hpc;
+        H.compress(first, H.query);
+        H.querying = true;
+        const HpcSide& q = H.query;
+        if (q.n > 0) chk(E.h, mhap_find_matches_reads(E.h, (const char*)q.bases.data(), q.offsets.data(), q.lengths.data(), H.ids(q), q.n, sink_cb, &sink));
+        H.querying = false;
+      } else
+        E.find_reads(fa, sink_cb, &sink);
       nq = E.stats().queries_searched - s0.queries_searched;   // forward sketches produced = getNumberProcessed() (MhapMain.java:537)
       mhap_fasta_free(&fa);
     }
@@ -603,15 +644,22 @@ int main(int argc, char** argv) {
   fprintf(stderr, "Processing files for storage in reverse index...\n");
   const double t_proc = now();
   int64_t strands = 0;
-  const int64_t seq_processed = add_file_to_index(E, o.s("-s"), 0, o, &strands);
+  Sink sink;
+  Pipeline pipeline;
+  HpcStage hpc;
+  if (o.b("--hpc")) {
+    hpc.on = true; hpc.h = E.h;
+    if (o.b("--realign")) hpc.reads = &pipeline.reads;   // the raw reads are kept once
+    sink.hpc = &hpc;
+  }
+  const int64_t seq_processed = hpc.on ? add_compressed_to_index(E, o, hpc, &strands) : add_file_to_index(E, o.s("-s"), 0, o, &strands);
   fprintf(stderr, "Stored %lld sequences in the index.\n", (long long)strands);
   fprintf(stderr, "Processed %lld unique sequences (fwd and rev).\n", (long long)strands);
   fprintf(stderr, "Time (s) to read and hash from file: %g\n", now() - t_proc);
 
-  Sink sink;
-  Pipeline pipeline;
   if (o.b("--realign")) { begin_pipeline(o, E.h, pipeline); sink.pipeline = &pipeline; }
   search(E, o, P, sink, seq_processed);
+  if (hpc.on) hpc.finish();
   if (sink.pipeline) pipeline.finish();
   fprintf(stderr, "Total time (s): %g\n", now() - t_total);
   final_statistics(E);

@@ -19,11 +19,13 @@
 namespace {
 
 const char* USAGE =
-    "Usage: mhap-hip-kmers -o <output file> [-k 16] [--no-rc] [--min-fraction 2.5e-6] [--histogram <file>] [--device 0] <FASTA file or directory> ...\n"
+    "Usage: mhap-hip-kmers -o <output file> [-k 16] [--no-rc] [--hpc] [--min-fraction 2.5e-6] [--histogram <file>] [--device 0] <FASTA file or directory> ...\n"
     "       mhap-hip-kmers --assess <FASTA> [--assess-min-count 0] [--assess-table <file>] [--assess-bed <file>] [-o ...] [-k 16] [--no-rc] <FASTA file or directory> ...\n"
     "  -o               the k-mer filter file to write (the -f file of mhap-hip; optional with --assess)\n"
     "  -k               k-mer size, 1 to 16 (default 16)\n"
     "  --no-rc          count k-mers as they are read instead of canonical (the smaller of a k-mer and its reverse complement)\n"
+    "  --hpc            count the k-mers of the homopolymer-compressed reads (every run of equal bases collapsed to one, on the GPU):\n"
+    "                   the -f file of a `mhap-hip --hpc` search, which sketches the compressed reads, has to be made this way\n"
     "  --min-fraction   write the k-mers whose share of all counted k-mers is at least this (default 2.5e-6)\n"
     "  --histogram      also write the k-mer count histogram, \"<count>\\t<number of k-mers>\" per line in ascending count\n"
     "                   (what `python -m mhap_amd.histogram_stats <file> <percent>` reads to help choose --min-fraction)\n"
@@ -63,7 +65,7 @@ int main(int argc, char** argv) {
   long k = 16, device = 0, assess_min_count = 0;
   bool assess_options = false;
   double min_fraction = 2.5e-6;
-  bool rc = true;
+  bool rc = true, hpc = false;
   std::vector<std::string> inputs;
   for (int a = 1; a < argc; a++) {
     const std::string s = argv[a];
@@ -72,6 +74,7 @@ int main(int argc, char** argv) {
     else if (s == "-o") out = value();
     else if (s == "-k") { if (!parse_int(value(), k)) die("-k takes an integer"); }
     else if (s == "--no-rc") rc = false;
+    else if (s == "--hpc") hpc = true;
     else if (s == "--histogram") histogram = value();
     else if (s == "--min-fraction") { if (!parse_double(value(), min_fraction)) die("--min-fraction takes a number"); }
     else if (s == "--assess") assess = value();
@@ -83,6 +86,7 @@ int main(int argc, char** argv) {
     else inputs.push_back(s);
   }
   if (assess_options && assess.empty()) die("--assess-min-count, --assess-table and --assess-bed go with --assess <FASTA>");
+  if (hpc && !assess.empty()) die("--hpc makes the -f file of a compressed search: it does not go with --assess");
   if (out.empty() && assess.empty()) die("no output file (-o)");
   if (out.empty() && !histogram.empty()) die("--histogram goes with -o");
   if (inputs.empty()) die("no input file");
@@ -97,11 +101,33 @@ int main(int argc, char** argv) {
   if (mhap_create(&p, &h, err, sizeof err) != MHAP_OK) { fprintf(stderr, "mhap-hip-kmers: %s\n", err); return 1; }
   auto chk = [&](int r) { if (r != MHAP_OK) { fprintf(stderr, "mhap-hip-kmers: %s (code %d)\n", mhap_last_error(h), r); mhap_destroy(h); exit(1); } };
   chk(mhap_kmer_count_begin(h, (int32_t)k, rc ? 1 : 0));
-  int64_t reads = 0, bases = 0;
+  int64_t reads = 0, bases = 0, hpc_counts[MHAP_HPC_COUNTS] = {0, 0, 0, 0, 0, 0};
   double t_scan = 0.0, t_count = 0.0;
   for (const std::string& in : inputs) {
     for (const std::string& f : list_files(in)) {
       const double a = now();
+      if (hpc) {   // the file read whole, compressed on the GPU, and the compressed reads counted as they are
+        mhap_fasta fa;
+        if (mhap_fasta_read(f.c_str(), 0, &fa, err, sizeof err) != MHAP_OK) { fprintf(stderr, "mhap-hip-kmers: %s\n", err); mhap_destroy(h); return 1; }
+        const double b = now();
+        reads += fa.n; bases += fa.total_bases;
+        mhap_hpc* c = nullptr;
+        int r = mhap_hpc_compress(h, (const uint8_t*)fa.bases, fa.total_bases, fa.ids, fa.offsets, fa.lengths, fa.n, 0, &c);
+        mhap_fasta_free(&fa);
+        chk(r);
+        int64_t cc[MHAP_HPC_COUNTS];
+        mhap_hpc_info(c, cc);
+        for (int i = 0; i < MHAP_HPC_COUNTS; i++) hpc_counts[i] = i == 4 ? std::max(hpc_counts[i], cc[i]) : hpc_counts[i] + cc[i];
+        std::vector<uint8_t> cb((size_t)std::max<int64_t>(cc[2], 1));
+        std::vector<int64_t> coff((size_t)cc[0] + 1);
+        std::vector<int32_t> clen((size_t)std::max<int64_t>(cc[0], 1));
+        r = mhap_hpc_copy(c, cb.data(), coff.data(), clen.data(), nullptr);
+        mhap_hpc_free(c);
+        chk(r);
+        if (cc[0] > 0) chk(mhap_kmer_count_add_reads(h, (const char*)cb.data(), coff.data(), clen.data(), cc[0]));
+        t_scan += b - a; t_count += now() - b;
+        continue;
+      }
       mhap_fasta_scan* s = nullptr;
       if (mhap_fasta_scan_open(f.c_str(), 0, &s, err, sizeof err) != MHAP_OK) { fprintf(stderr, "mhap-hip-kmers: %s\n", err); mhap_destroy(h); return 1; }
       const double b = now();
@@ -166,6 +192,9 @@ int main(int argc, char** argv) {
   else
     fprintf(stderr, "Counted %lld %d-mers (%lld distinct) in %lld reads, %.1f Mbase; total %.3f s (scan %.3f s, count %.3f s)\n", (long long)total, (int)kk,
             (long long)distinct, (long long)reads, bases / 1e6, now() - t0, t_scan, t_count);
+  if (hpc)
+    fprintf(stderr, "Homopolymer compression: %lld reads (%lld empty), %lld bases compressed to %lld; %lld runs longer than 1, the longest of %lld\n", (long long)hpc_counts[0],
+            (long long)hpc_counts[5], (long long)hpc_counts[1], (long long)hpc_counts[2], (long long)hpc_counts[3], (long long)hpc_counts[4]);
   if (!assess.empty()) fprintf(stderr, "%s\n", line);
   return 0;
 }
