@@ -826,7 +826,8 @@ int mhap_graph_unitigs_counts(mhap_graph_session* s, int64_t* counts /* MHAP_UNI
 /* A unitig as spelled carries the error rate of one read at every position, and the contained reads, which hold most of the coverage,
  * contribute nothing.  This stage places every read it can on a served unitig, aligns it to the draft in a band round its place with
  * the banded aligner above, lets every alignment vote as view A of the correction contract ("read correction"), and calls every draft
- * position as that contract calls a read position.  One round; no quality values, no chimera detection, no read trimming.
+ * position as that contract calls a read position.  One round; no chimera detection, no read trimming.  Every consensus byte has a
+ * quality from its counters ("base qualities" below); the reads' own qualities are not read, and a called deletion reports none.
  *
  * Draft.  The spelling of the unitigs the graph session serves (of the last mhap_graph_unitigs or mhap_graph_clean), exactly what
  * mhap_graph_spell writes; unitig k has the length ulen[k].  A unitig of 2^31 bases or more refuses the run and is named.
@@ -906,6 +907,44 @@ int mhap_consensus_copy_map(mhap_consensus_session* s, int64_t* map /* n_draft_b
 int mhap_consensus_votes(mhap_consensus_session* s, int64_t unitig, uint16_t* counters /* length x 24 */);
 int mhap_consensus_times(mhap_consensus_session* s, double* seconds /* 4: placement, alignment, vote, call */);
 void mhap_consensus_free(mhap_consensus_session* s);
+
+/* ---- base qualities: how far each corrected or consensus byte can be trusted, from the counters that decided it --------------------- */
+
+/* One quality byte, 0 .. 93, goes with every byte that the call of "read correction" or of "unitig consensus" emits, at the offset of
+ * that byte.  It is a function of the position's 24 counters, own, min_cov and the two parameters below, in integer arithmetic only,
+ * so it is the same from run to run; tests/quality_ref.py restates it.
+ *
+ * Parameters.  per_vote: tenths of a Phred unit per net vote, 1 .. 1000; cap: 1 .. 93.  The defaults are {15, 60}: the slope is the
+ * one tools/quality_calibration.py measured against a truth genome (12.9, to the nearest 5; EXPERIMENTS.md, "Base qualities"), the cap
+ * a convention.
+ *
+ * Rule.  Q(m) = min(cap, per_vote * max(m, 0) / 10), C integer division.  At position t with the raw counters base[4], del, span,
+ * ins[k][4] as the call reads them, d = base[A] + base[C] + base[G] + base[T] + del and n = d + 1 (own counts once):
+ *   The base byte, the first byte of a position that is not called deleted, e: not A, C, G or T: quality 0, fixed.  Otherwise
+ *     s = base[e] + (own == e ? 1 : 0) and the margin is m = 2 s - n: the votes for e less everything else.  The same in the
+ *     low-coverage branch (d < min_cov), where e = own and s = base[own] + 1.
+ *   Inserted byte k, e: m = 2 ins[k][e] - (span + 1), positive because the call emitted it.
+ *   The stop margin.  The last byte emitted at t also answers for the junction not going on: when t < L - 1 and the position emitted
+ *     n_ins < 4 inserted bytes, m_stop = (span + 1) - 2 max over b of ins[n_ins][b], and the last byte's margin becomes min(m, m_stop)
+ *     unless its quality is the fixed 0.  This holds whether or not span >= min_cov: a junction with an insertion majority that the
+ *     call did not make for lack of span gives its base byte quality 0.
+ *   No byte, no quality: a position called deleted without an insertion emits nothing and its evidence is not reported.
+ * The same pass counts a histogram of 94 int64 bins over all quality bytes of the call.
+ *
+ * mhap_correct_quality needs a completed mhap_correct_finish with no record added since and uses that finish's min_cov, which the
+ * session remembers; quals takes out_offsets[n_reads] bytes.  mhap_consensus_quality is the same against the last completed
+ * mhap_consensus_run (n_out_bytes bytes); a run the guard refused, or a graph session that has moved on, leaves nothing to ask for.
+ * MHAP_E_INVALID with a message otherwise, and for per_vote or cap out of range; params == NULL: the defaults; hist may be NULL.  They
+ * may be repeated with other parameters.  The pass is a kernel of its own next to each call kernel (correct_kernels.hip,
+ * consensus_kernels.hip) over one shared device function (vote_common.hpp); device memory: 1 byte per output byte from the first call.
+ * Left out: reading FASTQ and weighing votes by the reads' own qualities; qualities for called deletions; qualities in the GFA. */
+typedef struct mhap_quality_params { int32_t per_vote, cap; } mhap_quality_params;
+#define MHAP_QUALITY_BINS 94
+void mhap_quality_default_params(mhap_quality_params* p);
+int mhap_correct_quality(mhap_correct_session* s, const mhap_quality_params* params /* NULL: the defaults */,
+                         uint8_t* quals /* out_offsets[n_reads] */, int64_t* hist /* MHAP_QUALITY_BINS, or NULL */);
+int mhap_consensus_quality(mhap_consensus_session* s, const mhap_quality_params* params /* NULL: the defaults */,
+                           uint8_t* quals /* n_out_bytes */, int64_t* hist /* MHAP_QUALITY_BINS, or NULL */);
 
 /* ---- read trimming: every read cut to the stretch that other reads support, chimeras split, records rewritten onto the cut reads ---- */
 

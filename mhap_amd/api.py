@@ -267,6 +267,9 @@ _PROTOTYPES = {
     "mhap_ksim_dev_destroy": "v:p",
     "mhap_ksim_dev_pair_stats": "i:ppqpqiipqpp",
     "mhap_ksim_dev_trials": "i:pQqqiiddddipppqiipqppppp",
+    "mhap_quality_default_params": "v:p",
+    "mhap_correct_quality": "i:pppp",
+    "mhap_consensus_quality": "i:pppp",
 }
 EXPORTED_SYMBOLS = list(_PROTOTYPES)
 MHAP_KMER_HISTOGRAM = 1   # mhap_kmer_count_finish_flags
@@ -730,6 +733,32 @@ class _ReadsSession(_Session):
         return dict(zip(self._counts, counts.tolist()))
 
 
+QUALITY_BINS = 94   # MHAP_QUALITY_BINS: Phred 0 .. 93
+
+
+class QualityParams(C.Structure):
+    """mhap_quality_params: per_vote, tenths of a Phred unit per net vote (1 .. 1000), and cap (1 .. 93)."""
+    _fields_ = [("per_vote", C.c_int32), ("cap", C.c_int32)]
+
+    def __init__(self, per_vote=15, cap=60):
+        super().__init__(int(per_vote), int(cap))
+
+
+def quality_counts_line(hist):
+    """The one stderr line of a run that was asked for qualities (the driver prints the same), from the histogram."""
+    h = [int(x) for x in hist]
+    n = sum(h)
+    mean = f"{sum(q * c for q, c in enumerate(h)) / n:.1f}" if n else "0.0"
+    return f"Qualities: {n} bytes, {sum(h[:10])} below Q10, {sum(h[:20])} below Q20, mean {mean}"
+
+
+def _qualities(ms, call, session, params, offsets):
+    """What both quality() methods do: (one uint8 array per sequence of `offsets`, the histogram)."""
+    flat, hist = np.zeros(int(offsets[-1]), np.uint8), np.zeros(QUALITY_BINS, np.int64)
+    ms._chk(call(session, C.byref(params), _opt(flat), _ptr(hist)))
+    return [flat[int(offsets[k]):int(offsets[k + 1])] for k in range(len(offsets) - 1)], hist
+
+
 class CorrectSession(_Session):
     """Read correction on the GPU (mhap_correct_begin / _add / _finish / _votes; the contract is the "read correction" section of
     include/mhap_hip.h): every realigned overlap votes column by column on both of its reads, and each position takes the majority.
@@ -802,6 +831,12 @@ class CorrectSession(_Session):
         out = np.zeros((int(self.lengths[read_index]), CORRECT_COUNTERS), np.uint16)
         self._ms._chk(self._lib.mhap_correct_votes(self._s, C.c_int64(read_index), _opt(out)))
         return out
+
+    def quality(self, per_vote=15, cap=60):
+        """(quals, hist) of the last finish (mhap_correct_quality; "base qualities" in include/mhap_hip.h): a uint8 array per read, as
+        long as its corrected bytes, and the int64 histogram of QUALITY_BINS bins over all of them."""
+        off = getattr(self, "offsets", np.zeros(1, np.int64))   # (no finish yet: the library refuses)
+        return _qualities(self._ms, self._lib.mhap_correct_quality, self._s, QualityParams(per_vote, cap), off)
 
     def table_bytes(self):
         return 48 * int(self.lengths.astype(np.int64).sum())
@@ -1484,6 +1519,13 @@ class ConsensusSession(_Session):
         out = np.zeros((int(self.stats[k, 0]), CORRECT_COUNTERS), np.uint16)
         self._ms._chk(self._lib.mhap_consensus_votes(self._s, C.c_int64(k), _opt(out)))
         return out
+
+    def quality(self, per_vote=15, cap=60):
+        """(quals, hist) of the last run (mhap_consensus_quality; "base qualities" in include/mhap_hip.h): a uint8 array per unitig,
+        as long as its consensus, and the int64 histogram of QUALITY_BINS bins over all of them."""
+        n = self.info()[0]
+        off = self.out_offsets if n >= 0 and hasattr(self, "out_offsets") else np.zeros(1, np.int64)   # (no run: the library refuses)
+        return _qualities(self._ms, self._lib.mhap_consensus_quality, self._s, QualityParams(per_vote, cap), off)
 
     def times(self):
         """The host's wall time of the last run's stages in seconds: a dict of placement, alignment, vote, call."""

@@ -1,12 +1,15 @@
 """Correct reads on the GPU from a file of MHAP overlaps: `python -m mhap_amd.correct overlaps.txt reads.fasta [queries.fasta] [--band W]
-[--min-identity X] [--min-coverage N] [--best-overlaps N [--best-min-span S]] [-o out.fasta]` writes what `mhap-hip --realign --correct
-out.fasta` (with the same --best-overlaps flags) writes for the same overlaps.
+[--min-identity X] [--min-coverage N] [--best-overlaps N [--best-min-span S]] [-o out.fasta] [--fastq out.fastq [--quality-per-vote N]
+[--quality-cap N]]` writes what `mhap-hip --realign --correct out.fasta` (with the same --best-overlaps flags, and --correct-fastq)
+writes for the same overlaps.
 
 The overlaps are parsed and realigned as `python -m mhap_amd.realign` does, with every alignment's path; the records that tool would
 drop (no alignment, or an identity below --min-identity) cast no vote.  Every other record votes column by column on both of its reads
 (api.CorrectSession; the contract is the "read correction" section of include/mhap_hip.h) and each read position takes the majority.
 Output is FASTA, one unwrapped line per read: `>ID len=<corrected length> sub=<substitutions> del=<deletions> ins=<insertions>
 low=<positions below --min-coverage>`, the ids numeric as the records print them; one line on stderr gives the totals.
+--fastq also writes the corrected reads as FASTQ, the same header fields behind `@`, with one quality per base from the votes that
+decided it ("base qualities" of include/mhap_hip.h; Phred+33), and one more stderr line counts them.
 
 --best-overlaps N makes two passes ("overlap selection" of include/mhap_hip.h): the first realigns without paths and selects each
 read's N best views over the records that would vote (api.SelectSession), the second realigns only the records that keep a view, with
@@ -17,7 +20,7 @@ import sys
 
 import numpy as np
 
-from . import api
+from . import api, fastq
 from .realign import kept_rows, read_overlaps
 
 BATCH = 1 << 16   # records realigned and voted per call
@@ -33,12 +36,14 @@ def select_paths(op_offsets, ops, rows):
     return out, (np.concatenate(parts).astype(np.uint32) if parts else np.zeros(0, np.uint32))
 
 
+def header_fields(names, stats):
+    """What follows `>` (FASTA) or `@` (FASTQ) per read: `NAME len= sub= del= ins= low=`."""
+    return [f"{name} len={st[1]} sub={st[2]} del={st[3]} ins={st[4]} low={st[5]}" for name, st in zip(names, np.asarray(stats).tolist())]
+
+
 def format_fasta(names, seqs, stats):
     """The corrected reads as FASTA text: `>NAME len= sub= del= ins= low=` and the bases on one line, per read."""
-    out = []
-    for name, seq, st in zip(names, seqs, np.asarray(stats).tolist()):
-        out.append(f">{name} len={st[1]} sub={st[2]} del={st[3]} ins={st[4]} low={st[5]}\n{bytes(seq).decode('latin-1')}\n")
-    return "".join(out)
+    return "".join(f">{h}\n{bytes(seq).decode('latin-1')}\n" for h, seq in zip(header_fields(names, stats), seqs))
 
 
 def totals_line(stats, skipped_views):
@@ -69,9 +74,10 @@ def select_pass(recs, fasta, queries, ms, band, min_identity, best_n, best_min_s
 
 
 def correct_overlaps(recs, fasta, queries=None, band=0, max_shift=0.2, min_identity=0.0, min_cov=4, device=0, batch=BATCH, best_n=0,
-                     best_min_span=500, selection=None):
+                     best_min_span=500, selection=None, quality=None):
     """Realign `recs` with paths in batches and vote: (seqs, stats, skipped_views, records that voted).  best_n > 0: only each read's
-    best_n best views vote; `selection` (a dict) then takes the selection's rows, counts and ids."""
+    best_n best views vote; `selection` (a dict) then takes the selection's rows, counts and ids.  quality: None, or a dict of per_vote and
+    cap, which then takes `quals` (a uint8 array per read) and `hist` of CorrectSession.quality."""
     voted = 0
     with api.MinHashSearch(api.MhapParams(num_hashes=1, ordered_sketch_size=1, max_shift=max_shift, device=device)) as ms:
         views = None
@@ -88,6 +94,8 @@ def correct_overlaps(recs, fasta, queries=None, band=0, max_shift=0.2, min_ident
                 cs.add(out[rows], ko, kops, views=None if views is None else views[q0:q0 + batch][rows])
                 voted += len(rows)
             seqs, stats, skipped = cs.finish(min_cov)
+            if quality is not None:
+                quality["quals"], quality["hist"] = cs.quality(quality.get("per_vote", 15), quality.get("cap", 60))
             ids = cs.ids.tolist()
     return ids, seqs, stats, skipped, voted
 
@@ -106,7 +114,12 @@ def main(argv=None):
     ap.add_argument("--query-id-offset", type=int, default=None)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("-o", "--output", default=None, help="the FASTA file to write (default: stdout)")
+    ap.add_argument("--fastq", default=None, help="also write the corrected reads with base qualities to this FASTQ file")
+    fastq.add_arguments(ap)
     a = ap.parse_args(argv)
+    quality, message = fastq.parameters(a, a.fastq is not None, "--fastq")
+    if message:
+        ap.error(message)
     if a.best_overlaps < 0:
         ap.error("--best-overlaps must be >= 0")
     if a.best_min_span is not None and a.best_overlaps == 0:
@@ -124,7 +137,7 @@ def main(argv=None):
     ids, seqs, stats, skipped, voted = correct_overlaps(recs, fasta, queries, band=a.band, max_shift=a.max_shift, min_identity=a.min_identity,
                                                         min_cov=a.min_coverage, device=a.device, best_n=a.best_overlaps,
                                                         best_min_span=500 if a.best_min_span is None else a.best_min_span,
-                                                        selection=selection)
+                                                        selection=selection, quality=quality if a.fastq else None)
     text = format_fasta(ids, seqs, stats)
     if a.output:
         with open(a.output, "w") as fh:
@@ -136,6 +149,10 @@ def main(argv=None):
     if selection:
         print(api.select_counts_line([selection["counts"][k] for k in api.SELECT_COUNTS]), file=sys.stderr)
     print(totals_line(stats, skipped), file=sys.stderr)
+    if a.fastq:
+        with open(a.fastq, "w") as fh:
+            fh.write(fastq.format_fastq(header_fields(ids, stats), seqs, quality["quals"]))
+        print(api.quality_counts_line(quality["hist"]), file=sys.stderr)
     return 0
 
 

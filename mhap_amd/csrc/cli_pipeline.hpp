@@ -53,6 +53,25 @@ inline void hold_records(std::vector<mhap_record>& held, const mhap_record* r, i
   else held.insert(held.end(), r, r + n);
 }
 
+// --correct-fastq, --gfa-consensus-fastq: the file, the two parameters, and the one formatter and the one stderr line both stages use
+struct Quality {
+  std::string fastq; mhap_quality_params p;
+  bool on() const { return !fastq.empty(); }
+  static void record(Writer& w, const std::string& header, const uint8_t* seq, const uint8_t* quals, size_t n) {   // @header, the bases, +, Phred+33
+    w.put("@" + header + "\n");
+    w.put((const char*)seq, n);
+    w.put("\n+\n", 3);
+    std::string q(n, '!');
+    for (size_t i = 0; i < n; i++) q[i] = (char)(33 + quals[i]);
+    w.put(q + "\n");
+  }
+  static void line(const int64_t* hist) {
+    long long n = 0, below10 = 0, below20 = 0, sum = 0;
+    for (int q = 0; q < MHAP_QUALITY_BINS; q++) { n += hist[q]; sum += (long long)q * hist[q]; if (q < 10) below10 += hist[q]; if (q < 20) below20 += hist[q]; }
+    fprintf(stderr, "Qualities: %lld bytes, %lld below Q10, %lld below Q20, mean %.1f\n", n, below10, below20, n ? (double)sum / (double)n : 0.0);
+  }
+};
+
 // A one-byte-per-base copy of every read the search has seen (the index's, then each -q file's) and the table of their ids, places and lengths.
 struct Reads {
   std::vector<uint8_t> bases; std::vector<int64_t> ids, offsets; std::vector<int32_t> lengths;
@@ -184,7 +203,7 @@ struct HpcStage : Stage {
 
 // --correct: every kept record votes on both of its reads, or (add_selected) with the views the selection kept
 struct CorrectStage : Stage {
-  std::string fasta; int32_t min_cov = 0; mhap_correct_session* s = nullptr;
+  std::string fasta; int32_t min_cov = 0; mhap_correct_session* s = nullptr; Quality quality;
   void begin(const Reads& R) { chk(h, mhap_correct_begin(h, R.bases.data(), (int64_t)R.bases.size(), R.ids.data(), R.offsets.data(), R.lengths.data(), R.n(), &s)); }
   int add(const Batch& b) { Tick t{seconds}; return mhap_correct_add(s, b.out.data(), b.k, b.paths); }
   // the records as they came give the alignments of the first pass again (the aligner is deterministic), now with their paths, 65 536 at a time
@@ -201,7 +220,7 @@ struct CorrectStage : Stage {
       chk(h, mhap_correct_add_views(s, b.out.data(), b.k, b.paths, kv.data()));
     }
   }
-  void finish(const Reads& R) {   // the call for every read, after the last vote; the FASTA file is all it writes
+  void finish(const Reads& R) {   // the call for every read, after the last vote; the FASTA file, and with --correct-fastq the FASTQ file, is all it writes
     const double t0 = now();
     const int64_t nr = R.n();
     std::vector<int64_t> off((size_t)nr + 1); std::vector<int32_t> st = room<int32_t>(nr, 6);
@@ -209,21 +228,32 @@ struct CorrectStage : Stage {
     chk(h, mhap_correct_finish(s, min_cov, off.data(), st.data(), &skipped));
     std::vector<uint8_t> bytes = room<uint8_t>(off[(size_t)nr]);
     chk(h, mhap_correct_copy(s, bytes.data()));
+    std::vector<uint8_t> quals = room<uint8_t>(quality.on() ? off[(size_t)nr] : 0);
+    int64_t hist[MHAP_QUALITY_BINS];
+    if (quality.on()) chk(h, mhap_correct_quality(s, &quality.p, quals.data(), hist));
     mhap_correct_free(s);
     Writer w(fasta);
     long long tot[6] = {0, 0, 0, 0, 0, 0};
+    std::vector<std::string> fields((size_t)nr);   // what follows '>' and, in the FASTQ file, '@'
     for (int64_t r = 0; r < nr; r++) {
       const int32_t* c = st.data() + 6 * r;
       for (int u = 0; u < 6; u++) tot[u] += c[u];
-      w.put(">" + header_of(R.ids[(size_t)r]) + " len=" + std::to_string(c[1]) + " sub=" + std::to_string(c[2]) + " del=" + std::to_string(c[3]) + " ins=" + std::to_string(c[4]) +
-            " low=" + std::to_string(c[5]) + "\n");
+      fields[(size_t)r] = header_of(R.ids[(size_t)r]) + " len=" + std::to_string(c[1]) + " sub=" + std::to_string(c[2]) + " del=" + std::to_string(c[3]) + " ins=" + std::to_string(c[4]) +
+                          " low=" + std::to_string(c[5]);
+      w.put(">" + fields[(size_t)r] + "\n");
       w.put((const char*)bytes.data() + off[(size_t)r], (size_t)(off[(size_t)r + 1] - off[(size_t)r]));
       w.put("\n", 1);
     }
     w.close();
+    if (quality.on()) {
+      Writer wq(quality.fastq);
+      for (int64_t r = 0; r < nr; r++) Quality::record(wq, fields[(size_t)r], bytes.data() + off[(size_t)r], quals.data() + off[(size_t)r], (size_t)(off[(size_t)r + 1] - off[(size_t)r]));
+      wq.close();
+    }
     seconds += now() - t0;
     fprintf(stderr, "Corrected %lld reads: %lld bases in, %lld out; %lld substitutions, %lld deletions, %lld insertions, %lld positions of low coverage; skipped_views = %lld\n",
             ll(nr), tot[0], tot[1], tot[2], tot[3], tot[4], tot[5], ll(skipped));
+    if (quality.on()) Quality::line(hist);
     fprintf(stderr, "Time (s) to vote and correct: %g\n", seconds);
   }
 };
@@ -307,7 +337,7 @@ struct RepeatStage : Stage {
 // --gfa: every record it is given is classed for the string graph (queued: nothing waits); finish cleans, compacts into unitigs, spells them or calls their consensus
 struct GraphStage : Stage {
   mhap_graph_params p; std::string gfa, unitigs, consensus_fasta; mhap_graph_session* s = nullptr;
-  bool clean = false, consensus = false; mhap_clean_params cp; mhap_consensus_params kp;
+  bool clean = false, consensus = false; mhap_clean_params cp; mhap_consensus_params kp; Quality quality; int64_t qhist[MHAP_QUALITY_BINS];
   std::vector<mhap_record> held;              // --gfa-consensus: the consensus takes what the graph took
   int64_t uc[MHAP_UNITIG_COUNTS], kc[MHAP_CONSENSUS_COUNTS];
   void begin(const Reads& R) { Tick t{seconds}; chk(h, mhap_graph_begin(h, R.ids.data(), R.lengths.data(), R.n(), &p, &s)); }
@@ -328,6 +358,7 @@ struct GraphStage : Stage {
     chk(h, mhap_graph_copy_layout(s, mv.data(), moff.data(), msp.data()));
     chk(h, mhap_graph_copy_links(s, links.data()));
     std::vector<int64_t> cons_off(nu + 1, 0), cons_map;   // --gfa-consensus: unitig k's bytes in seq, the position map of all unitigs
+    std::vector<uint8_t> cons_quals;                       // --gfa-consensus-fastq: one quality per byte of seq
     if (!consensus) chk(h, mhap_graph_spell(s, R.bases.data(), (int64_t)R.bases.size(), R.offsets.data(), seq.data()));
     else {   // the held records, fed now that the unitigs are served; the consensus takes the place of the spelling
       mhap_consensus_session* cs = nullptr;
@@ -341,6 +372,7 @@ struct GraphStage : Stage {
       cons_map.assign((size_t)n_draft + 1, 0);
       chk(h, mhap_consensus_copy(cs, seq.data(), cons_off.data(), stats.data()));
       chk(h, mhap_consensus_copy_map(cs, cons_map.data()));
+      if (quality.on()) { cons_quals.assign((size_t)n_out + 1, 0); chk(h, mhap_consensus_quality(cs, &quality.p, cons_quals.data(), qhist)); }
       mhap_consensus_free(cs);
       std::vector<mhap_record>().swap(held);
     }
@@ -369,6 +401,14 @@ struct GraphStage : Stage {
       w.put(std::string(line, (size_t)len) + "\n");
     }
     w.close();
+    if (consensus && quality.on()) {
+      Writer wq(quality.fastq);
+      for (size_t k = 0; k < nu; k++) {
+        snprintf(name, sizeof name, "utg%06lld%c", (long long)k + 1, circ[k] ? 'c' : 'l');
+        Quality::record(wq, name, seq.data() + cons_off[k], cons_quals.data() + cons_off[k], (size_t)(cons_off[k + 1] - cons_off[k]));
+      }
+      wq.close();
+    }
     if (!consensus || consensus_fasta.empty()) return;
     Writer wf(consensus_fasta);
     for (size_t k = 0; k < nu; k++) {
@@ -419,6 +459,7 @@ struct GraphStage : Stage {
     if (consensus)
       fprintf(stderr, "Consensus: %lld members, %lld reads placed by an overlap, %lld unplaced; %lld aligned, %lld without alignment; %lld bases in, %lld out: %lld substitutions, %lld deletions, %lld insertions, %lld low positions\n",
               ll(kc[0]), ll(kc[1]), ll(kc[2]), ll(kc[3]), ll(kc[4]), ll(kc[5]), ll(kc[6]), ll(kc[7]), ll(kc[8]), ll(kc[9]), ll(kc[10]));
+    if (consensus && quality.on()) Quality::line(qhist);
     fprintf(stderr, "Time (s) to class, build and reduce the graph: %g\n", seconds);
   }
 };

@@ -1,4 +1,4 @@
-// consensus_kernels.hip — the consensus of the served unitigs (mhap_consensus_begin / _add / _run / _copy* / _votes / _free): every read
+// consensus_kernels.hip — the consensus of the served unitigs (mhap_consensus_begin / _add / _run / _copy* / _quality / _votes / _free): every read
 // is placed on a unitig, aligned to the draft in a band round its place, votes as view A of the correction contract, and every draft
 // position takes the majority.  The contract is the "unitig consensus" section of include/mhap_hip.h; tests/unitig_consensus_ref.py
 // restates it.  The class rule is graph_class.hpp's (classify_kernel's), the column walk and the decision vote_common.hpp's
@@ -21,6 +21,8 @@
 //   ccall_kernel     one workgroup per tile, 256 positions at a time: decide() per thread, a workgroup scan of the emitted lengths; the
 //                    first launch leaves every tile's length and four counts, the host prefix-sums the lengths, the second launch writes
 //                    the bytes and the position map.  The junction after t belongs to t's tile; t < L - 1 is the unitig's L.
+// quality, on request after a run:
+//   cqual_kernel     one workgroup per tile: decide() and decide_quality() per position, the bytes' places from the position map
 // Integer atomic rates behind the vote layout are not measured here either (correct_kernels.hip).
 #include <hip/hip_runtime.h>
 
@@ -199,6 +201,40 @@ __global__ __launch_bounds__(CK_T) void ccall_kernel(const uint8_t* __restrict__
   }
 }
 
+// The quality pass of mhap_consensus_quality, over the table, the offsets and the position map of a completed run: one workgroup per
+// tile as in ccall_kernel, decide() and decide_quality() per position.  A kernel of its own, so that ccall_kernel stays the code it is;
+// it needs no scan, because the run's position map already says where a position's bytes lie.  One writer per quality byte; the
+// workgroup's histogram lives in LDS and leaves by one 64-bit atomic per non-empty bin.
+__global__ __launch_bounds__(CK_T) void cqual_kernel(const uint8_t* __restrict__ draft, int64_t nu, const int64_t* __restrict__ u_len,
+                                                     const int64_t* __restrict__ ubase, const int64_t* __restrict__ utile,
+                                                     const uint32_t* __restrict__ table, int min_cov, int per_vote, int cap,
+                                                     const int64_t* __restrict__ out_offsets, const int64_t* __restrict__ posmap,
+                                                     uint8_t* __restrict__ quals, unsigned long long* __restrict__ hist) {
+  __shared__ unsigned long long bins[QUAL_BINS];
+  const int64_t tile = blockIdx.x;
+  const int64_t k = last_at_or_before(utile, nu, tile);
+  const int64_t L = u_len[k], t_begin = (tile - utile[k]) * CT, t_end = min64(L, t_begin + CT);
+  const uint8_t* own = draft + ubase[k];
+  const uint32_t* w = table + (int64_t)CK_WORDS * ubase[k];
+  const int64_t o_end = out_offsets[k + 1];
+  const int tid = threadIdx.x;
+  if (tid < QUAL_BINS) bins[tid] = 0ull;
+  __syncthreads();
+  for (int64_t t = t_begin + tid; t < t_end; t += CK_T) {
+    const Decision D = decide(w, L, t, own[t], min_cov);
+    uint8_t q[1 + CK_KI] = {0, 0, 0, 0, 0};
+    decide_quality(w, L, t, own[t], D, per_vote, cap, q);
+    const int64_t at = out_offsets[k] + posmap[ubase[k] + t];
+    for (int u = 0; u < D.n; u++)
+      if (at + u < o_end) {   // (the map is that of this table and this min_cov: always)
+        quals[at + u] = q[u];
+        atomicAdd(&bins[q[u]], 1ull);
+      }
+  }
+  __syncthreads();
+  if (tid < QUAL_BINS && bins[tid]) atomicAdd(hist + tid, bins[tid]);
+}
+
 // the cap on reads per tile: 65 535, lowered by MHAP_CONSENSUS_TILE_CAP (tests), read at each run
 uint32_t tile_cap() {
   if (const char* e = getenv("MHAP_CONSENSUS_TILE_CAP")) {
@@ -227,11 +263,11 @@ struct mhap_consensus_session {
   double seconds[4] = {0, 0, 0, 0};                       // the host's wall time of the last run: placement, alignment, vote, call
   std::vector<int64_t> u_len, ubase, out_offsets, stats, place;
   DevBuf bases, roff, items, rlen, mem_vertex, mem_unitig, mem_off, key1, key2, d_place, d_pairs, d_ustart, d_ulen, d_ucirc, d_ubase,
-      d_utile, m_vertex, m_offset, tile_reads, table, vitems, ops, tile_len, tile_counts, tile_off, d_outoff, out, posmap;
+      d_utile, m_vertex, m_offset, tile_reads, table, vitems, ops, tile_len, tile_counts, tile_off, d_outoff, out, posmap, quals, hist;
   void release() {
     for (DevBuf* b : {&bases, &roff, &items, &rlen, &mem_vertex, &mem_unitig, &mem_off, &key1, &key2, &d_place, &d_pairs, &d_ustart, &d_ulen,
                        &d_ucirc, &d_ubase, &d_utile, &m_vertex, &m_offset, &tile_reads, &table, &vitems, &ops, &tile_len, &tile_counts, &tile_off,
-                       &d_outoff, &out, &posmap}) b->release();
+                       &d_outoff, &out, &posmap, &quals, &hist}) b->release();
   }
 };
 
@@ -555,6 +591,36 @@ extern "C" int mhap_consensus_copy_map(mhap_consensus_session* s, int64_t* map) 
   hipError_t e;
   if ((e = hipMemcpyAsync(map, s->posmap.p, 8 * (size_t)s->n_draft, hipMemcpyDeviceToHost, v.stream)) != hipSuccess ||
       (e = hipStreamSynchronize(v.stream)) != hipSuccess) return hip_fail(v, who, "download", e);
+  return MHAP_OK;
+}
+
+extern "C" int mhap_consensus_quality(mhap_consensus_session* s, const mhap_quality_params* params, uint8_t* quals, int64_t* hist) {
+  const char* who = "mhap_consensus_quality";
+  if (!s) return MHAP_E_INVALID;
+  HandleView v = handle_view(s->h);
+  mhap_quality_params p;
+  mhap_quality_default_params(&p);
+  if (params) p = *params;
+  if (!quality_params_ok(p.per_vote, p.cap, who, *v.err)) return MHAP_E_INVALID;
+  const int rc = need_run(s, v, who);
+  if (rc != MHAP_OK) return rc;
+  if (hist) for (int b = 0; b < QUAL_BINS; b++) hist[b] = 0;
+  if (s->out_bytes == 0) return MHAP_OK;
+  if (!quals) { *v.err = std::string(who) + ": null argument"; return MHAP_E_INVALID; }
+  int64_t n_tiles = 0;
+  for (int64_t k = 0; k < s->n_unitigs; k++) n_tiles += (s->u_len[(size_t)k] + CT - 1) / CT;
+  (void)hipSetDevice(v.device);
+  hipError_t e;
+  if ((e = s->quals.ensure((size_t)s->out_bytes)) != hipSuccess || (e = s->hist.ensure(8 * QUAL_BINS)) != hipSuccess) return hip_fail(v, who, "hipMalloc of the quality bytes", e);
+  if ((e = hipMemsetAsync(s->hist.p, 0, 8 * QUAL_BINS, v.stream)) != hipSuccess) return hip_fail(v, who, "memset", e);
+  hipLaunchKernelGGL(cqual_kernel, dim3((unsigned)n_tiles), dim3(CK_T), 0, v.stream, s->bases.as<uint8_t>() + s->n_bases, s->n_unitigs,
+                     s->d_ulen.as<int64_t>(), s->d_ubase.as<int64_t>(), s->d_utile.as<int64_t>(), s->table.as<uint32_t>(), (int)s->min_cov,
+                     (int)p.per_vote, (int)p.cap, s->d_outoff.as<int64_t>(), s->posmap.as<int64_t>(), s->quals.as<uint8_t>(),
+                     s->hist.as<unsigned long long>());
+  if ((e = hipGetLastError()) != hipSuccess) return hip_fail(v, who, "launch", e);
+  if ((e = hipMemcpyAsync(quals, s->quals.p, (size_t)s->out_bytes, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return hip_fail(v, who, "download", e);
+  if (hist && (e = hipMemcpyAsync(hist, s->hist.p, 8 * QUAL_BINS, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return hip_fail(v, who, "download", e);
+  if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return hip_fail(v, who, "kernel", e);
   return MHAP_OK;
 }
 

@@ -1,5 +1,5 @@
 // correct_kernels.hip — read correction: a pile-up vote over every read from the realigned overlaps' paths and a majority call per
-// position (mhap_correct_begin / _add / _add_views / _finish / _copy / _votes / _free).  The contract — the two views of a record, the 22 counters,
+// position (mhap_correct_begin / _add / _add_views / _finish / _copy / _quality / _votes / _free).  The contract — the two views of a record, the 22 counters,
 // the 65 535-view cap and the call — is the prose of include/mhap_hip.h ("read correction"); tests/consensus_ref.py restates it.
 //
 // The vote table.  24 counters of 16 bits per base, two to a word: 12 words per base, kept as 12 planes per read — word p of position t
@@ -23,6 +23,9 @@
 // call_kernel: one workgroup per read, 256 positions at a time: every thread decides its position (0 to 5 bytes), the workgroup scans
 // the emitted lengths, and in the second of two launches writes the bytes.  The first launch leaves the six counts per read; the reads'
 // output offsets are the prefix sums of their len_out, made on the host, which returns them anyway.
+//
+// qcall_kernel (mhap_correct_quality): the call's scan once more over the table and the offsets of a completed finish, with the base
+// qualities of vote_common.hpp's decide_quality behind every decision and a histogram of them ("base qualities" in include/mhap_hip.h).
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -89,6 +92,55 @@ __global__ __launch_bounds__(CK_T) void call_kernel(const uint8_t* __restrict__ 
   }
 }
 
+// The quality pass of mhap_correct_quality: call_kernel's scan again, over the table and the offsets of a completed finish, with
+// decide_quality() behind every decide().  A kernel of its own, so that call_kernel stays the code it is.  One writer per quality byte;
+// the workgroup's histogram lives in LDS and leaves by one 64-bit atomic per non-empty bin.
+__global__ __launch_bounds__(CK_T) void qcall_kernel(const uint8_t* __restrict__ bases, const int64_t* __restrict__ read_off,
+                                                     const int64_t* __restrict__ read_pos, const int32_t* __restrict__ lengths,
+                                                     const uint32_t* __restrict__ table, int min_cov, int per_vote, int cap,
+                                                     const int64_t* __restrict__ out_offsets, uint8_t* __restrict__ quals,
+                                                     unsigned long long* __restrict__ hist) {
+  __shared__ int wave_sum[CK_T / 64];
+  __shared__ unsigned long long bins[QUAL_BINS];
+  const int64_t r = blockIdx.x;
+  const int64_t len = lengths[r];
+  const uint8_t* own = bases + read_off[r];
+  const uint32_t* w = table + (int64_t)CK_WORDS * read_pos[r];
+  const int64_t o_begin = out_offsets[r], o_end = out_offsets[r + 1];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid < QUAL_BINS) bins[tid] = 0ull;
+  int64_t written = 0;
+  for (int64_t t0 = 0; t0 < len; t0 += CK_T) {
+    const int64_t t = t0 + tid;
+    Decision D{0, {0, 0, 0, 0, 0}, 0, 0, 0, 0};
+    uint8_t q[1 + CK_KI] = {0, 0, 0, 0, 0};
+    if (t < len) {
+      D = decide(w, len, t, own[t], min_cov);
+      decide_quality(w, len, t, own[t], D, per_vote, cap, q);
+    }
+    int incl = D.n;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int u = __shfl_up(incl, d);
+      if (lane >= d) incl += u;
+    }
+    __syncthreads();   // wave_sum of the previous tile has been read (and, the first time, the bins are zero)
+    if (lane == 63) wave_sum[wave] = incl;
+    __syncthreads();
+    int before = 0, tile = 0;
+    for (int u = 0; u < CK_T / 64; u++) { if (u < wave) before += wave_sum[u]; tile += wave_sum[u]; }
+    const int64_t at = o_begin + written + before + (incl - D.n);
+    for (int u = 0; u < D.n; u++)
+      if (at + u < o_end) {   // (the offsets are those of this table and this min_cov: always)
+        quals[at + u] = q[u];
+        atomicAdd(&bins[q[u]], 1ull);
+      }
+    written += tile;
+  }
+  __syncthreads();
+  if (tid < QUAL_BINS && bins[tid]) atomicAdd(hist + tid, bins[tid]);
+}
+
 }  // namespace
 }  // namespace mhap
 
@@ -102,10 +154,12 @@ struct mhap_correct_session {
   std::unordered_map<int64_t, int64_t> by_id;
   std::vector<uint32_t> views;                          // accepted views per target
   int64_t skipped = 0, out_bytes = -1;                  // out_bytes < 0: no finish yet
-  DevBuf bases, table, read_off, read_pos, read_len, items, ops, out_off, out, stats;
+  int32_t min_cov = 0;                                  // of the last completed finish
+  bool voted_since = false;                             // votes were cast after that finish: its offsets are not the table's any more
+  DevBuf bases, table, read_off, read_pos, read_len, items, ops, out_off, out, stats, quals, hist;
   void release() {
     bases.release(); table.release(); read_off.release(); read_pos.release(); read_len.release(); items.release(); ops.release();
-    out_off.release(); out.release(); stats.release();
+    out_off.release(); out.release(); stats.release(); quals.release(); hist.release();
   }
 };
 
@@ -224,6 +278,7 @@ static int correct_add(const char* who, mhap_correct_session* s, const mhap_reco
   }
   s->skipped += skipped;
   if (items.empty()) return MHAP_OK;
+  s->voted_since = true;
   (void)hipSetDevice(v.device);
   hipError_t e;
   // a grid of at most 2^20 views at a time: the items of one launch are 64 MB
@@ -260,7 +315,7 @@ extern "C" int mhap_correct_finish(mhap_correct_session* s, int32_t min_cov, int
   if (skipped_views) *skipped_views = s->skipped;
   s->out_bytes = -1;
   out_offsets[0] = 0;
-  if (s->n_reads == 0) { s->out_bytes = 0; return MHAP_OK; }
+  if (s->n_reads == 0) { s->out_bytes = 0; s->min_cov = min_cov; s->voted_since = false; return MHAP_OK; }
   if (s->n_reads > INT32_MAX) { *v.err = std::string(who) + ": more than 2^31 - 1 reads"; return MHAP_E_INVALID; }
   (void)hipSetDevice(v.device);
   hipError_t e;
@@ -280,7 +335,7 @@ extern "C" int mhap_correct_finish(mhap_correct_session* s, int32_t min_cov, int
                      s->stats.as<int32_t>());
   if ((e = hipGetLastError()) != hipSuccess) return hip_fail(v, who, "launch", e);
   if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return hip_fail(v, who, "kernel", e);
-  s->out_bytes = total;
+  s->out_bytes = total; s->min_cov = min_cov; s->voted_since = false;
   return MHAP_OK;
 }
 
@@ -295,6 +350,38 @@ extern "C" int mhap_correct_copy(mhap_correct_session* s, uint8_t* bytes) {
   hipError_t e;
   if ((e = hipMemcpyAsync(bytes, s->out.p, (size_t)s->out_bytes, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return hip_fail(v, who, "download", e);
   if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return hip_fail(v, who, "download", e);
+  return MHAP_OK;
+}
+
+extern "C" void mhap_quality_default_params(mhap_quality_params* p) {
+  if (!p) return;
+  p->per_vote = 15; p->cap = 60;   // the slope is the measured one (EXPERIMENTS.md, "Base qualities"), the cap a convention
+}
+
+extern "C" int mhap_correct_quality(mhap_correct_session* s, const mhap_quality_params* params, uint8_t* quals, int64_t* hist) {
+  const char* who = "mhap_correct_quality";
+  if (!s) return MHAP_E_INVALID;
+  HandleView v = handle_view(s->h);
+  mhap_quality_params p;
+  mhap_quality_default_params(&p);
+  if (params) p = *params;
+  if (!quality_params_ok(p.per_vote, p.cap, who, *v.err)) return MHAP_E_INVALID;
+  if (s->out_bytes < 0) { *v.err = std::string(who) + ": no mhap_correct_finish has completed"; return MHAP_E_INVALID; }
+  if (s->voted_since) { *v.err = std::string(who) + ": records were added since the last mhap_correct_finish"; return MHAP_E_INVALID; }
+  if (hist) for (int b = 0; b < QUAL_BINS; b++) hist[b] = 0;
+  if (s->out_bytes == 0) return MHAP_OK;
+  if (!quals) { *v.err = std::string(who) + ": null argument"; return MHAP_E_INVALID; }
+  (void)hipSetDevice(v.device);
+  hipError_t e;
+  if ((e = s->quals.ensure((size_t)s->out_bytes)) != hipSuccess || (e = s->hist.ensure(8 * QUAL_BINS)) != hipSuccess) return hip_fail(v, who, "hipMalloc of the quality bytes", e);
+  if ((e = hipMemsetAsync(s->hist.p, 0, 8 * QUAL_BINS, v.stream)) != hipSuccess) return hip_fail(v, who, "memset", e);
+  hipLaunchKernelGGL(qcall_kernel, dim3((unsigned)s->n_reads), dim3(CK_T), 0, v.stream, s->bases.as<uint8_t>(), s->read_off.as<int64_t>(),
+                     s->read_pos.as<int64_t>(), s->read_len.as<int32_t>(), s->table.as<uint32_t>(), (int)s->min_cov, (int)p.per_vote, (int)p.cap,
+                     s->out_off.as<int64_t>(), s->quals.as<uint8_t>(), s->hist.as<unsigned long long>());
+  if ((e = hipGetLastError()) != hipSuccess) return hip_fail(v, who, "launch", e);
+  if ((e = hipMemcpyAsync(quals, s->quals.p, (size_t)s->out_bytes, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return hip_fail(v, who, "download", e);
+  if (hist && (e = hipMemcpyAsync(hist, s->hist.p, 8 * QUAL_BINS, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return hip_fail(v, who, "download", e);
+  if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return hip_fail(v, who, "kernel", e);
   return MHAP_OK;
 }
 

@@ -48,6 +48,8 @@ struct Options {
       if (n.compare(0, 8, "--repeat") == 0 && !b("--repeat-filter")) continue;
       if (n.compare(0, 6, "--best") == 0 && !isset("--best-overlaps")) continue;
       if (n == "--hpc" && !b("--hpc")) continue;
+      if ((n == "--correct-fastq" || n == "--gfa-consensus-fastq") && !isset(n)) continue;   // (and the quality flags only with a FASTQ file to write)
+      if (n.compare(0, 9, "--quality") == 0 && !isset("--correct-fastq") && !isset("--gfa-consensus-fastq")) continue;
       t += n + " = " + m.at(n).value + "\n";
     }
     return t;
@@ -315,6 +317,9 @@ void declare_options(Options& o) {
   o.add("--realign-paf", "With --realign, print one PAF line per overlap instead of the 12 columns: the alignment's interval, its matches and columns, and its path as a cg:Z CIGAR with = X I D.", "false", true);
   o.add("--correct", "With --realign: correct every read of -s from the realigned overlaps and write the corrected reads to this FASTA file. Each overlap votes column by column on both of its reads and every position takes the majority; overlaps that --realign drops cast no vote. Self overlaps only (no -q), one GPU.", "");
   o.add("--correct-min-coverage", "[int] With --correct, the votes a read position needs before it is changed.", "4");
+  o.add("--correct-fastq", "With --correct, also write the corrected reads to this FASTQ file, with one quality per base from the votes that decided it (Phred+33).", "");
+  o.add("--quality-per-vote", "[int] With --correct-fastq or --gfa-consensus-fastq, tenths of a Phred unit per net vote, 1 to 1000.", "15");
+  o.add("--quality-cap", "[int] With --correct-fastq or --gfa-consensus-fastq, the highest quality written, 1 to 93.", "60");
   o.add("--gfa", "With --realign: build the string graph of the realigned overlaps on the GPU (dovetails, contained reads set aside, transitive arcs reduced) and write it to this file as GFA 1: an S line per read that is not contained, an L line per final arc. Self overlaps only (no -q), one GPU.", "");
   o.add("--gfa-unitigs", "With --gfa: compact the final arcs of the string graph into unitigs on the GPU and write them to this second file as GFA 1: an S line with the sequence per unitig, spelled from the reads as stored, an a line per read of it, an L line per arc between unitigs.", "");
   o.add("--gfa-max-hang", "[int] With --gfa, the longest unaligned end an overlap may leave on both reads before it counts as an internal match.", "1000");
@@ -326,6 +331,7 @@ void declare_options(Options& o) {
   o.add("--gfa-clean-rounds", "[int] With --gfa-clean, the most rounds of cleaning.", "16");
   o.add("--gfa-consensus", "With --gfa-unitigs: place every read on a unitig, align it to the unitig and let the reads vote on the GPU; the --gfa-unitigs file then carries the consensus sequences, their lengths, and a-line offsets mapped into them.", "false", true);
   o.add("--gfa-consensus-fasta", "With --gfa-consensus, also write the consensus sequences to this FASTA file.", "");
+  o.add("--gfa-consensus-fastq", "With --gfa-consensus, also write the consensus sequences to this FASTQ file, with one quality per base from the votes that decided it (Phred+33).", "");
   o.add("--gfa-consensus-min-cov", "[int] With --gfa-consensus, the depth below which a position keeps the unitig's own base.", "4");
   o.add("--trim", "With --realign: trim every read of -s on the GPU to the longest stretch that enough realigned overlaps cover, which also splits chimeric reads at their junction. The overlaps printed stay the untrimmed ones; with --gfa the graph, its unitigs and their consensus are built on the trimmed reads and the overlaps rewritten onto them. Self overlaps only (no -q), one GPU.", "false", true);
   o.add("--trim-min-cov", "[int] With --trim, the shrunk overlaps a position needs to be kept.", "3");
@@ -397,6 +403,8 @@ std::vector<int32_t> check_options(Options& o) {
     if (o.s("--correct").empty()) bad("--correct needs the name of the FASTA file to write.");
     if (o.i("--correct-min-coverage") < 1) bad("The correction's minimum coverage must be >=1.");
   }
+  owned(o, {"--correct-fastq"}, o.isset("--correct"), " belongs to --correct: give --correct too.");
+  if (o.isset("--correct-fastq") && o.s("--correct-fastq").empty()) bad("--correct-fastq needs the name of the FASTQ file to write.");
   const char* realigned = "the overlaps realigned on the reads' bases";
   const bool best = o.isset("--best-overlaps") && o.i("--best-overlaps") != 0;
   owned(o, {"--best-min-span", "--best-table"}, best, " belongs to --best-overlaps: give --best-overlaps too.");
@@ -416,6 +424,11 @@ std::vector<int32_t> check_options(Options& o) {
   owned(o, {"--gfa-consensus-fasta", "--gfa-consensus-min-cov"}, o.b("--gfa-consensus"), " belongs to --gfa-consensus: give --gfa-consensus too.");
   if (o.isset("--gfa-consensus-fasta") && o.s("--gfa-consensus-fasta").empty()) bad("--gfa-consensus-fasta needs the name of the FASTA file to write.");
   if (o.i("--gfa-consensus-min-cov") < 1) bad("The value of --gfa-consensus-min-cov must be >=1.");
+  owned(o, {"--gfa-consensus-fastq"}, o.b("--gfa-consensus"), " belongs to --gfa-consensus: give --gfa-consensus too.");
+  if (o.isset("--gfa-consensus-fastq") && o.s("--gfa-consensus-fastq").empty()) bad("--gfa-consensus-fastq needs the name of the FASTQ file to write.");
+  owned(o, {"--quality-per-vote", "--quality-cap"}, o.isset("--correct-fastq") || o.isset("--gfa-consensus-fastq"), " belongs to --correct-fastq or --gfa-consensus-fastq: give one of them too.");
+  if (o.i("--quality-per-vote") < 1 || o.i("--quality-per-vote") > 1000 || o.i("--quality-cap") < 1 || o.i("--quality-cap") > 93)
+    bad("The value of --quality-per-vote must be 1 to 1000 and that of --quality-cap 1 to 93.");
   if (gfa) {
     stage_flag(o, n_devs, "--gfa", "builds the graph from", "lays out", realigned);
     if (o.s("--gfa").empty()) bad("--gfa needs the name of the GFA file to write.");
@@ -511,6 +524,8 @@ void begin_pipeline(const Options& o, mhap_handle* h, Pipeline& p) {
   p.realign.reads = &p.reads; p.realign.band = o.i("--realign-band"); p.realign.min_identity = o.d("--realign-min-identity");
   p.paf = o.b("--realign-paf");
   p.correct.on = o.isset("--correct"); p.correct.fasta = o.s("--correct"); p.correct.min_cov = o.i("--correct-min-coverage");
+  p.correct.quality.fastq = o.s("--correct-fastq"); p.graph.quality.fastq = o.s("--gfa-consensus-fastq");
+  p.correct.quality.p = p.graph.quality.p = mhap_quality_params{o.i("--quality-per-vote"), o.i("--quality-cap")};
   p.select.on = o.isset("--best-overlaps") && o.i("--best-overlaps") != 0; p.select.table = o.s("--best-table");
   mhap_select_default_params(&p.select.p);
   p.select.p.best_n = o.i("--best-overlaps"); p.select.p.min_span = o.i("--best-min-span");

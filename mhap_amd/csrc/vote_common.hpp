@@ -1,9 +1,12 @@
 // vote_common.hpp — what the pile-up votes of read correction (correct_kernels.hip) and of the unitig consensus (consensus_kernels.hip)
-// share: a view's item, the walk over the columns of its path, which casts the votes, and the decision of the call for one position.
+// share: a view's item, the walk over the columns of its path, which casts the votes, the decision of the call for one position and
+// the qualities of the bytes it emits.
 // The contract is the "read correction" section of include/mhap_hip.h; correct_kernels.hip describes the table's planes and the walk.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <string>
 
 #include "device_common.hpp"
 
@@ -151,6 +154,57 @@ __device__ inline Decision decide(const uint32_t* __restrict__ w, int64_t len, i
     }
   }
   return D;
+}
+
+// Base qualities ("base qualities" in include/mhap_hip.h): one byte 0 .. cap per byte of D = decide(w, len, t, own, min_cov), from the
+// same counters, in integers.  Q(m) = min(cap, per_vote * max(m, 0) / 10) of the margin m between the votes for the byte and the rest.
+constexpr int QUAL_BINS = 94;   // Phred 0 .. 93, what FASTQ can print
+
+// the check of both quality entry points: per_vote 1 .. 1000, cap 1 .. 93
+inline bool quality_params_ok(int per_vote, int cap, const char* who, std::string& err) {
+  if (per_vote >= 1 && per_vote <= 1000 && cap >= 1 && cap < QUAL_BINS) return true;
+  err = std::string(who) + ": per_vote must be 1 .. 1000 and cap 1 .. 93 (" + std::to_string(per_vote) + ", " + std::to_string(cap) + ")";
+  return false;
+}
+
+__device__ inline int quality_of(int m, int per_vote, int cap) {
+  if (m <= 0) return 0;
+  const int64_t q = (int64_t)per_vote * m / 10;
+  return q < cap ? (int)q : cap;
+}
+
+__device__ inline void decide_quality(const uint32_t* __restrict__ w, int64_t len, int64_t t, uint32_t own, const Decision& D, int per_vote,
+                                      int cap, uint8_t* __restrict__ q) {
+  if (D.n == 0) return;   // a called deletion without an insertion: no byte, no quality
+  const uint32_t w0 = w[t], w1 = w[len + t], w2 = w[2 * len + t];
+  const int base[4] = {(int)(w0 & 0xFFFFu), (int)(w0 >> 16), (int)(w1 & 0xFFFFu), (int)(w1 >> 16)};
+  const int del = (int)(w2 & 0xFFFFu), span = (int)(w2 >> 16);
+  const int n_base = D.n - D.ins;   // 1 unless the position is called deleted
+  int m_last = 0;
+  bool fixed = false;               // the last byte is not A, C, G or T: its 0 stands
+  if (n_base) {
+    const int e = base_code(D.bytes[0]);
+    if (e < 0) fixed = true;
+    else m_last = 2 * (base[e] + (own == D.bytes[0] ? 1 : 0)) - (base[0] + base[1] + base[2] + base[3] + del + 1);
+    q[0] = (uint8_t)(fixed ? 0 : quality_of(m_last, per_vote, cap));
+  }
+  for (int k = 0; k < D.ins; k++) {
+    const int e = base_code(D.bytes[n_base + k]);   // (decide emits A, C, G or T here)
+    const uint32_t x = w[(3 + 2 * k + (e >> 1)) * len + t];
+    m_last = 2 * (int)((e & 1) ? x >> 16 : x & 0xFFFFu) - (span + 1);
+    fixed = false;
+    q[n_base + k] = (uint8_t)quality_of(m_last, per_vote, cap);
+  }
+  // the last byte also answers for the junction not going on
+  if (t < len - 1 && D.ins < CK_KI && !fixed) {
+    const uint32_t x0 = w[(3 + 2 * D.ins) * len + t], x1 = w[(4 + 2 * D.ins) * len + t];
+    int top = (int)(x0 & 0xFFFFu);
+    if ((int)(x0 >> 16) > top) top = (int)(x0 >> 16);
+    if ((int)(x1 & 0xFFFFu) > top) top = (int)(x1 & 0xFFFFu);
+    if ((int)(x1 >> 16) > top) top = (int)(x1 >> 16);
+    const int m_stop = span + 1 - 2 * top;
+    if (m_stop < m_last) q[D.n - 1] = (uint8_t)quality_of(m_stop, per_vote, cap);
+  }
 }
 
 }  // namespace mhap

@@ -1,6 +1,7 @@
 """The string graph of a file of MHAP overlaps, on the GPU: `python -m mhap_amd.graph overlaps.txt reads.fasta [--band W]
 [--min-identity X] [--max-hang N] [--int-frac F] [--min-overlap N] [--fuzz N] -o out.gfa [--unitigs utg.gfa] [--clean [--tip-reads N]
-[--bubble-bases N] [--clean-rounds N]] [--consensus [--consensus-fasta F] [--consensus-min-cov N]] [--repeat-filter ...]` writes what `mhap-hip --realign
+[--bubble-bases N] [--clean-rounds N]] [--consensus [--consensus-fasta F] [--consensus-fastq F [--quality-per-vote N] [--quality-cap N]]
+[--consensus-min-cov N]] [--repeat-filter ...]` writes what `mhap-hip --realign
 --gfa out.gfa [--gfa-unitigs utg.gfa] [--gfa-clean ...]` writes for the same overlaps.
 
 The overlaps are parsed and realigned as `python -m mhap_amd.realign` does; the records that tool would drop (no alignment, or an
@@ -15,7 +16,8 @@ bubbles whose lesser branch has at most --bubble-bases bases are popped, in at m
 section); the -o file is then the cleaned read graph and the --unitigs file the cleaned unitig graph.
 With --consensus (which needs --unitigs) every read is placed on a unitig, aligned to it and votes, and the --unitigs file carries the
 consensus sequences, their lengths and `a` offsets mapped into them ("unitig consensus" in the same header); --consensus-fasta also
-writes them as FASTA.
+writes them as FASTA, and --consensus-fastq as FASTQ with one quality per base from the votes that decided it ("base qualities" in
+the same header; Phred+33), with one more stderr line that counts them.
 With --trim [--trim-min-cov N] [--trim-end-clip N] [--trim-min-span N] [--trim-penalty N] the reads are trimmed and chimeras split on the GPU first
 ("read trimming" in the same header; `python -m mhap_amd.trim` writes the trimmed reads themselves): every output is then built on
 the surviving reads, their trimmed lengths and the overlaps rewritten onto them.
@@ -28,7 +30,7 @@ and one more with --trim, in front; one more with --clean, one more with --uniti
 import argparse
 import sys
 
-from . import api, repeats
+from . import api, fastq, repeats
 from .realign import kept_rows, read_overlaps
 
 BATCH = 1 << 16   # records realigned and classed per call
@@ -41,19 +43,25 @@ def counts_line(c):
             f"{c['arcs']} arcs, {c['reduced']} reduced, {c['final']} final")
 
 
+def consensus_names(circular):
+    """`utg%06d{l|c}` per unitig, as the GFA names them."""
+    return [f"utg{k + 1:06d}{'c' if c else 'l'}" for k, c in enumerate(circular)]
+
+
 def consensus_fasta(seqs, circular):
     """The FASTA text of consensus sequences: `>utg%06d{l|c}` as the GFA names them, one line per sequence."""
-    return "".join(f">utg{k + 1:06d}{'c' if circular[k] else 'l'}\n{s.decode('latin-1')}\n" for k, s in enumerate(seqs))
+    return "".join(f">{name}\n{s.decode('latin-1')}\n" for name, s in zip(consensus_names(circular), seqs))
 
 
 def graph_overlaps(recs, fasta, band=0, max_shift=0.2, min_identity=0.0, device=0, batch=BATCH, unitigs=False, clean=None, consensus=None,
-                   trim=None, repeat=None, **params):
+                   trim=None, repeat=None, quality=None, **params):
     """Realign `recs` in batches and build the graph: (gfa text, arcs, counts, contained); with unitigs=True two more: the GFA text
     of the unitig graph and the dict of GraphSession.unitigs().  clean: None, or a dict of GraphSession.clean's parameters: the graph
     is cleaned first, both texts and the dict are those of the cleaned graph, and the dict of CLEAN_COUNTS comes last.
     consensus: None, or a dict of ConsensusSession's parameters (min_cov, band), with unitigs=True: the unitig text carries the consensus,
     and the result is a dict instead: gfa, arcs, counts, contained, unitig_gfa, unitigs, clean_counts (or None), consensus_counts,
-    consensus_seqs.
+    consensus_seqs.  quality: None, or with consensus a dict of per_vote and cap: the result dict then has consensus_quals (a uint8
+    array per unitig) and quality_hist of ConsensusSession.quality.
     trim: None, or a dict of TrimSession's parameters (min_cov, end_clip, min_span): the reads are trimmed first ("read trimming" in
     the same header) and everything above is built on the surviving reads, their trimmed lengths and the records rewritten onto
     them; the dict of TRIM_COUNTS then comes last of all (key trim_counts of the dict).
@@ -97,7 +105,8 @@ def graph_overlaps(recs, fasta, band=0, max_shift=0.2, min_identity=0.0, device=
                     for out in kept:
                         cs.add(out)
                     ccounts = cs.run()
-                    return dict(gfa=text, arcs=arcs, counts=counts, contained=gs.contained(), unitig_gfa=cs.gfa(), unitigs=gs.unitigs_table,
+                    quals, qhist = cs.quality(**quality) if quality is not None else (None, None)
+                    return dict(consensus_quals=quals, quality_hist=qhist, gfa=text, arcs=arcs, counts=counts, contained=gs.contained(), unitig_gfa=cs.gfa(), unitigs=gs.unitigs_table,
                                 clean_counts=tail[0] if tail else None, consensus_counts=ccounts, consensus_seqs=cs.sequences(),
                                 trim_counts=tcounts[0] if trim is not None else None, repeat_counts=tcounts[-1] if repeat is not None else None)
             if unitigs:
@@ -133,8 +142,13 @@ def main(argv=None):
     ap.add_argument("--trim-min-span", type=int, default=2000, help="with --trim, the shortest aligned interval that counts")
     ap.add_argument("--trim-penalty", type=int, default=api.TRIM_PENALTY, help="with --trim, the cost of an error column when overlaps are cut to their best stretch; 0: not cut")
     ap.add_argument("--repeat-filter", action="store_true", help="mark repeats from the overlap pile-up first and drop the overlaps that lie in nothing but repeat")
+    ap.add_argument("--consensus-fastq", default=None, help="with --consensus, also write the consensus sequences with base qualities to this FASTQ file")
+    fastq.add_arguments(ap)
     repeats.add_arguments(ap, "repeat-")
     a = ap.parse_args(argv)
+    quality, message = fastq.parameters(a, a.consensus_fastq is not None, "--consensus-fastq")
+    if message:
+        ap.error(message)
     rp, message = repeats.parameters(a, "repeat-")
     if message:
         ap.error(message)
@@ -148,8 +162,8 @@ def main(argv=None):
         ap.error("--trim-min-cov must be >= 1, --trim-end-clip, --trim-min-span and --trim-penalty >= 0")
     if a.consensus and not a.unitigs:
         ap.error("--consensus needs --unitigs")
-    if (a.consensus_fasta or a.consensus_min_cov != 4) and not a.consensus:
-        ap.error("--consensus-fasta and --consensus-min-cov need --consensus")
+    if (a.consensus_fasta or a.consensus_fastq or a.consensus_min_cov != 4) and not a.consensus:
+        ap.error("--consensus-fasta, --consensus-fastq and --consensus-min-cov need --consensus")
     if a.consensus_min_cov < 1:
         ap.error("--consensus-min-cov must be >= 1")
     if a.tip_reads < 0 or a.bubble_bases < 0 or a.clean_rounds < 1:
@@ -165,6 +179,7 @@ def main(argv=None):
                          consensus=dict(min_cov=a.consensus_min_cov) if a.consensus else None,
                          trim=dict(min_cov=a.trim_min_cov, end_clip=a.trim_end_clip, min_span=a.trim_min_span, penalty=a.trim_penalty) if a.trim else None,
                          repeat=dict(rp, penalty=a.trim_penalty) if a.repeat_filter else None,
+                         quality=quality if a.consensus_fastq else None,
                          max_hang=a.max_hang, int_frac_permille=int(round(a.int_frac * 1000)), min_ovlp=a.min_overlap, fuzz=a.fuzz)
     tcounts = rcounts = None
     if a.repeat_filter:
@@ -174,6 +189,7 @@ def main(argv=None):
         tcounts = res["trim_counts"] if a.consensus else res[-1]
         res = res if a.consensus else res[:-1]
     if a.consensus:
+        quals, qhist = res["consensus_quals"], res["quality_hist"]
         res = (res["gfa"], res["arcs"], res["counts"], res["contained"], res["unitig_gfa"], res["unitigs"], res["consensus_counts"],
                res["consensus_seqs"]) + ((res["clean_counts"],) if a.clean else ())
     text, counts = res[0], res[2]
@@ -198,6 +214,10 @@ def main(argv=None):
         if a.consensus_fasta:
             with open(a.consensus_fasta, "w") as fh:
                 fh.write(consensus_fasta(res[7], res[5]["circular"].tolist()))
+        if a.consensus_fastq:
+            with open(a.consensus_fastq, "w") as fh:
+                fh.write(fastq.format_fastq(consensus_names(res[5]["circular"].tolist()), res[7], quals))
+            print(api.quality_counts_line(qhist), file=sys.stderr)
     return 0
 
 

@@ -8,6 +8,8 @@ Each set is genome:reads: reads of 2 500 - 3 500 bases at 10 % error drawn from 
 1 000, fuzz 300 (the scaled flags of the driver tests; the first set is the input of the end-to-end test).  The consensus session
 gets the kept records and runs --repeats times; its four stage times are mhap_consensus_times' (host clocks, each stage ending
 behind a wait for the stream).  The correction session gets the same records with their runs: add is its vote, finish its call.
+After each, the quality pass (ConsensusSession.quality, CorrectSession.quality: the kernel, the download of one byte per output
+byte and of the histogram) is timed on its own, to be read next to `call` and `finish`.
 The first repeat is the warm-up.  A run without a GPU fails: there is no fallback."""
 import argparse
 import os
@@ -44,6 +46,9 @@ def run(G, n, seed, repeats):
                     counts = cs.run()
                     wall = time.time() - t0
                     t = cs.times()
+                    t0 = time.time()
+                    cs.quality()
+                    t_cq = time.time() - t0
             with api.CorrectSession(fa, handle=ms) as cr:
                 t0 = time.time()
                 cr.add(kept, k_off, k_ops)
@@ -51,9 +56,13 @@ def run(G, n, seed, repeats):
                 t0 = time.time()
                 cr.finish()
                 t_fin = time.time() - t0
+                t0 = time.time()
+                cr.quality()
+                t_rq = time.time() - t0
             print(f"{G} bases, {len(fa)} reads ({int(fa.lengths.sum())} bases), {len(kept)} records, {u['counts']['unitigs']} unitigs of {u['counts']['total_bases']} bases, "
                   f"repeat {rep}: consensus run {wall * 1e3:.1f} ms = placement {t['placement'] * 1e3:.1f} + alignment {t['alignment'] * 1e3:.1f} + vote "
-                  f"{t['vote'] * 1e3:.1f} + call {t['call'] * 1e3:.1f}; correction of the same records: add {t_add * 1e3:.1f} ms, finish {t_fin * 1e3:.1f} ms", flush=True)
+                  f"{t['vote'] * 1e3:.1f} + call {t['call'] * 1e3:.1f}; correction of the same records: add {t_add * 1e3:.1f} ms, finish {t_fin * 1e3:.1f} ms; "
+                  f"quality pass: consensus {t_cq * 1e3:.1f} ms, correction {t_rq * 1e3:.1f} ms", flush=True)
         print(api.consensus_counts_line([counts[k] for k in api.CONSENSUS_COUNTS]), flush=True)
 
 
