@@ -174,6 +174,10 @@ int64_t mhap_fasta_scan_reads(const mhap_fasta_scan* s);          /* non-empty r
 int64_t mhap_fasta_scan_bases(const mhap_fasta_scan* s);
 /* ids[n], lengths[n] (either may be NULL); headers: the n NUL-terminated names back to back (mhap_fasta.headers), valid until the scan is freed */
 int mhap_fasta_scan_info(mhap_fasta_scan* s, int64_t* ids, int32_t* lengths, const char** headers, int64_t* headers_bytes);
+/* 1 when the scanned file is FASTQ ("FASTQ input" below); then mhap_fasta_scan_qualities copies one Phred byte per base, in the
+ * reads' order (mhap_fasta_scan_bases bytes).  MHAP_E_INVALID on a FASTA scan. */
+int mhap_fasta_scan_has_qualities(const mhap_fasta_scan* s);
+int mhap_fasta_scan_qualities(const mhap_fasta_scan* s, uint8_t* qualities);
 int mhap_index_add_scan(mhap_handle* h, const mhap_fasta_scan* s);
 /* the reads of the scan as query reads against the index (-q mode, mhap_find_matches_reads), in groups */
 int mhap_find_matches_scan(mhap_handle* h, const mhap_fasta_scan* s, mhap_record_sink sink, void* user);
@@ -444,6 +448,24 @@ typedef struct mhap_fasta {
 } mhap_fasta;
 int mhap_fasta_read(const char* path, int64_t id_offset, mhap_fasta* out, char* err, size_t errcap);
 void mhap_fasta_free(mhap_fasta* f);
+
+/* FASTQ input.  Both readers above (mhap_fasta_read, mhap_fasta_scan_open) take a file whose first byte, after gz / bz2 inflation, is
+ * '@' for FASTQ; the plain-text suffixes "fastq" and "fq" join FastaData's.  A file that begins with '>' is read as before.
+ *   Record grammar.  A header line that opens with '@'; sequence lines up to a line that begins with '+', whose rest is ignored;
+ *   quality lines until as many quality bytes are read as the record has sequence bytes — so a record may span several lines, and a
+ *   quality line may begin with '@' or '+'.  Line ends are the FASTA reader's: \n, \r, \r\n.
+ *   What a record gives is what its FASTA twin (">name" and the sequence) gives: upper-cased bases, ids as the 1-based count of non-empty
+ *   records + id_offset, the name after '@' up to the first white space or comma, lengths, offsets and the pure-ACGT flag.
+ *   Qualities.  Phred = byte - 33, 0 .. 93, one per base in the reads' order; they come through the entry points below and
+ *   mhap_fasta_scan_has_qualities / mhap_fasta_scan_qualities, never through mhap_fasta.  The streamed ingest packs bases as before
+ *   and uploads no qualities: the search does not use them.
+ *   Refused with MHAP_E_INVALID and one line that names the record, counted from 1 with empty records: a record that does not start
+ *   with '@', one without a '+' line, a file that ends before a record's qualities are complete, a quality line that runs past the
+ *   sequence length, a quality byte outside 33 .. 126.
+ * mhap_fasta_read_qualities is mhap_fasta_read that also returns the quality array (total_bases bytes, free with
+ * mhap_qualities_free); *qualities is NULL for a FASTA file. */
+int mhap_fasta_read_qualities(const char* path, int64_t id_offset, mhap_fasta* out, uint8_t** qualities, char* err, size_t errcap);
+void mhap_qualities_free(uint8_t* qualities);
 
 /* Batched local alignment on the GPU: the Smith-Waterman check of EstimateROC's computeDP (J/main/EstimateROC.java:746-800), SSW's
  * scoring as EstimateROC calls it (Aligner.align(s1, s2, MATCH_MATRIX, 2, 1, true), matrix :302-308).  bases: the reads' bytes as
@@ -937,7 +959,8 @@ void mhap_consensus_free(mhap_consensus_session* s);
  * MHAP_E_INVALID with a message otherwise, and for per_vote or cap out of range; params == NULL: the defaults; hist may be NULL.  They
  * may be repeated with other parameters.  The pass is a kernel of its own next to each call kernel (correct_kernels.hip,
  * consensus_kernels.hip) over one shared device function (vote_common.hpp); device memory: 1 byte per output byte from the first call.
- * Left out: reading FASTQ and weighing votes by the reads' own qualities; qualities for called deletions; qualities in the GFA. */
+ * The reads' own qualities weigh the votes on request ("quality-weighted votes" below).
+ * Left out: qualities for called deletions; qualities in the GFA. */
 typedef struct mhap_quality_params { int32_t per_vote, cap; } mhap_quality_params;
 #define MHAP_QUALITY_BINS 94
 void mhap_quality_default_params(mhap_quality_params* p);
@@ -945,6 +968,49 @@ int mhap_correct_quality(mhap_correct_session* s, const mhap_quality_params* par
                          uint8_t* quals /* out_offsets[n_reads] */, int64_t* hist /* MHAP_QUALITY_BINS, or NULL */);
 int mhap_consensus_quality(mhap_consensus_session* s, const mhap_quality_params* params /* NULL: the defaults */,
                            uint8_t* quals /* n_out_bytes */, int64_t* hist /* MHAP_QUALITY_BINS, or NULL */);
+
+/* ---- quality-weighted votes: the pile-up of "read correction" and "unitig consensus" with the reads' own base qualities -------------- */
+
+/* Opt-in.  A session begun with qualities (one Phred byte per base, parallel to `bases`, as "FASTQ input" delivers them) follows the
+ * contract of "read correction" with every "adds 1" replaced by a weight; tests/weighted_vote_ref.py restates it.
+ *
+ * The weight of a base of Phred q, with the parameters 0 <= q_lo <= q_hi <= 93:   q < q_lo: 1;   q_lo <= q < q_hi: 2;   q >= q_hi: 3.
+ * The neutral weight is 2.
+ *
+ * Votes.  M(t, e) adds w(q_e) to base[t][e]; the k-th byte of an Ins group adds w(q_e) to ins[t][k][e]; q_e is the quality of the
+ * evidence byte at its stored position, so a reverse-complemented byte has the quality of the byte it was complemented from.  A byte
+ * that is not A, C, G or T votes nothing, as before.  Del(t) and span[t] add the neutral 2.  A vote stays one integer atomic add, of w
+ * or w << 16; a view adds at most 3 to a counter, so a target accepts 21 845 views (65 535 / 3) before views are skipped and counted in
+ * skipped_views, on the host in arrival order as before, and the unitig consensus refuses a tile that more than 21 845 reads meet.
+ *
+ * The call.  d is the same sum.  d < 2 min_cov: low.  Otherwise own adds w(q_own) in the correction and the neutral 2 in the unitig
+ * consensus (a draft byte has no single quality), total = d + that weight, and 2 del > total calls a deletion; the maximum and its
+ * tie rules are unchanged.  A junction is voted on when span >= 2 min_cov, and an inserted base is emitted when 2 m > span + 2.
+ *
+ * Base qualities, the margins of "base qualities" in weighted units: Q = min(cap, per_vote * max(m, 0) / 20), where the own term of
+ * the base margin is the weight above, n = d + that weight, an inserted byte has m = 2 ins[k][e] - (span + 2), and the stop margin is
+ * (span + 2) - 2 max over b of ins[n_ins][b].
+ *
+ * The oracle inside the rule: with every quality in [q_lo, q_hi) each counter is twice its unweighted value and each comparison the
+ * unweighted one times 2, so the bytes, the six counts and the output qualities are those of the unweighted session.
+ *
+ * mhap_correct_begin_weighted / mhap_consensus_begin_weighted are their siblings with `qualities` (n_bases bytes; NULL: the call is its
+ * sibling, the session unweighted) and the weight parameters (NULL: the defaults; MHAP_E_INVALID unless 0 <= q_lo <= q_hi <= 93).  The
+ * qualities go up once, one byte per base.  Every other entry point keeps its signature and, on a weighted session, follows this rule
+ * through kernels of its own (correct_kernels.hip, consensus_kernels.hip over weighted_vote.hpp); mhap_correct_votes and
+ * mhap_consensus_votes return the weighted counters.  The defaults are the pair that left the fewest wrong bytes on the restatement
+ * (EXPERIMENTS.md, "Quality-weighted votes").
+ * Left out: qualities in the search, trimming, repeat and graph stages; qualities for called deletions; quality-aware alignment;
+ * writing the input's qualities back out. */
+typedef struct mhap_weight_params { int32_t q_lo, q_hi; } mhap_weight_params;
+#define MHAP_WEIGHTED_VIEW_CAP 21845
+void mhap_weight_default_params(mhap_weight_params* p);
+int mhap_correct_begin_weighted(mhap_handle* h, const uint8_t* bases, const uint8_t* qualities /* n_bases, or NULL */, int64_t n_bases,
+                                const int64_t* read_ids, const int64_t* offsets, const int32_t* lengths, int64_t n_reads,
+                                const mhap_weight_params* weights /* NULL: the defaults */, mhap_correct_session** session);
+int mhap_consensus_begin_weighted(mhap_graph_session* g, const uint8_t* bases, const uint8_t* qualities /* n_bases, or NULL */,
+                                  int64_t n_bases, const int64_t* offsets /* n_reads */, const mhap_consensus_params* params,
+                                  const mhap_weight_params* weights /* NULL: the defaults */, mhap_consensus_session** session);
 
 /* ---- read trimming: every read cut to the stretch that other reads support, chimeras split, records rewritten onto the cut reads ---- */
 

@@ -33,6 +33,9 @@ from .api import (  # noqa: F401
     format_paf,
     CorrectSession,
     correct_reads,
+    WeightParams,
+    all_qualities,
+    weight_classes_line,
     GraphSession,
     string_graph,
     format_gfa,

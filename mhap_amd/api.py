@@ -270,6 +270,13 @@ _PROTOTYPES = {
     "mhap_quality_default_params": "v:p",
     "mhap_correct_quality": "i:pppp",
     "mhap_consensus_quality": "i:pppp",
+    "mhap_fasta_read_qualities": "i:pqpppz",
+    "mhap_qualities_free": "v:p",
+    "mhap_fasta_scan_has_qualities": "i:p",
+    "mhap_fasta_scan_qualities": "i:pp",
+    "mhap_weight_default_params": "v:p",
+    "mhap_correct_begin_weighted": "i:pppqpppqpp",
+    "mhap_consensus_begin_weighted": "i:pppqpppp",
 }
 EXPORTED_SYMBOLS = list(_PROTOTYPES)
 MHAP_KMER_HISTOGRAM = 1   # mhap_kmer_count_finish_flags
@@ -347,11 +354,13 @@ class MhapParams:
 class FastaData:
     """Reads (upper-cased, concatenated) + 1-based ids, as J/impl/FastaData.java:125-204 produces them."""
 
-    def __init__(self, bases, offsets, lengths, ids):
+    def __init__(self, bases, offsets, lengths, ids, qualities=None):
         self.bases = np.ascontiguousarray(bases, dtype=np.uint8)
         self.offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         self.lengths = np.ascontiguousarray(lengths, dtype=np.int32)
         self.ids = np.ascontiguousarray(ids, dtype=np.int64)
+        # one Phred value (0 .. 93) per base, parallel to `bases`: what a FASTQ file brought ("FASTQ input" in include/mhap_hip.h); else None
+        self.qualities = None if qualities is None else np.ascontiguousarray(qualities, dtype=np.uint8)
 
     def __len__(self):
         return int(self.lengths.shape[0])
@@ -361,18 +370,23 @@ class FastaData:
         lib = load_library()
         f = _Fasta()
         err = C.create_string_buffer(512)
-        rc = lib.mhap_fasta_read(path.encode(), C.c_int64(id_offset), C.byref(f), err, C.c_size_t(512))
+        qp = C.c_void_p()
+        rc = lib.mhap_fasta_read_qualities(path.encode(), C.c_int64(id_offset), C.byref(f), C.byref(qp), err, C.c_size_t(512))
         if rc != 0:
             raise MhapError(err.value.decode() or f"mhap_fasta_read failed ({rc})")
+        quals = None
         try:
             n, tb = f.n, f.total_bases
+            if qp:
+                quals = np.ctypeslib.as_array(C.cast(qp, C.POINTER(C.c_uint8)), shape=(max(tb, 1),))[:tb].copy()
+                lib.mhap_qualities_free(qp)
             bases = np.ctypeslib.as_array(C.cast(f.bases, C.POINTER(C.c_uint8)), shape=(max(tb, 1),))[:tb].copy()
             offsets = np.ctypeslib.as_array(C.cast(f.offsets, C.POINTER(C.c_int64)), shape=(max(n, 1),))[:n].copy()
             lengths = np.ctypeslib.as_array(C.cast(f.lengths, C.POINTER(C.c_int32)), shape=(max(n, 1),))[:n].copy()
             ids = np.ctypeslib.as_array(C.cast(f.ids, C.POINTER(C.c_int64)), shape=(max(n, 1),))[:n].copy()
         finally:
             lib.mhap_fasta_free(C.byref(f))
-        return cls(bases, offsets, lengths, ids)
+        return cls(bases, offsets, lengths, ids, quals)
 
     @classmethod
     def from_strings(cls, seqs, id_offset=0):
@@ -397,9 +411,12 @@ class FastaData:
         if len(idx):
             offsets[1:] = np.cumsum(lengths[:-1], dtype=np.int64)
         bases = np.empty(int(lengths.sum()), dtype=np.uint8)
+        quals = None if self.qualities is None else np.empty(len(bases), dtype=np.uint8)
         for j, i in enumerate(idx):
             bases[offsets[j]:offsets[j] + lengths[j]] = self.bases[self.offsets[i]:self.offsets[i] + self.lengths[i]]
-        return FastaData(bases, offsets, lengths, self.ids[idx])
+            if quals is not None:
+                quals[offsets[j]:offsets[j] + lengths[j]] = self.qualities[self.offsets[i]:self.offsets[i] + self.lengths[i]]
+        return FastaData(bases, offsets, lengths, self.ids[idx], quals)
 
 
 def synth_reads(n, length, seed=0x4D484150, coverage=30.0, error_rate=0.15, shard=0, nshards=1, repeats=None):
@@ -518,6 +535,50 @@ def _all_reads(fasta, query_fasta):
         return fasta.bases, fasta.ids, fasta.offsets, fasta.lengths
     return (np.concatenate([fasta.bases, query_fasta.bases]), np.concatenate([fasta.ids, query_fasta.ids]),
             np.concatenate([fasta.offsets, query_fasta.offsets + len(fasta.bases)]), np.concatenate([fasta.lengths, query_fasta.lengths]))
+
+
+def all_qualities(fasta, query_fasta=None):
+    """The Phred bytes of the indexed reads followed by those of the -q reads, parallel to _all_reads' bases: what a weighted
+    CorrectSession or ConsensusSession takes.  MhapError when a file brought none (it was FASTA)."""
+    parts = [fasta] if query_fasta is None or len(query_fasta) == 0 else [fasta, query_fasta]
+    if any(getattr(p, "qualities", None) is None for p in parts):
+        raise MhapError("the reads have no base qualities (a FASTQ file brings them)")
+    return parts[0].qualities if len(parts) == 1 else np.concatenate([p.qualities for p in parts])
+
+
+WEIGHTED_VIEW_CAP = 21845   # MHAP_WEIGHTED_VIEW_CAP: accepted views per target of a weighted session (65 535 / 3)
+
+
+class WeightParams(C.Structure):
+    """mhap_weight_params: a base of Phred q votes with weight 1 (q < q_lo), 2 (q_lo <= q < q_hi) or 3 (q >= q_hi); 0 <= q_lo <= q_hi
+    <= 93.  None for either takes the library's default ("quality-weighted votes" in include/mhap_hip.h)."""
+    _fields_ = [("q_lo", C.c_int32), ("q_hi", C.c_int32)]
+
+    def __init__(self, q_lo=None, q_hi=None):
+        d = WeightParams.__new__(WeightParams)
+        load_library().mhap_weight_default_params(C.byref(d))
+        super().__init__(d.q_lo if q_lo is None else int(q_lo), d.q_hi if q_hi is None else int(q_hi))
+
+
+def weight_classes_line(bases, qualities, weights=None):
+    """The one stderr line of a weighted run (the driver prints the same): the A, C, G, T bases of the reads per weight class."""
+    w = weights or WeightParams()
+    b, q = np.asarray(bases, np.uint8), np.asarray(qualities, np.uint8)
+    q = q[(b == 65) | (b == 67) | (b == 71) | (b == 84)]
+    n1, n3 = int((q < w.q_lo).sum()), int((q >= w.q_hi).sum())
+    return (f"Weights: q_lo = {w.q_lo}, q_hi = {w.q_hi}; {n1} bases of weight 1, {len(q) - n1 - n3} of weight 2, {n3} of weight 3")
+
+
+def _weighted_args(bases, qualities, weights):
+    """(the qualities as a checked array, the weight parameters) of a weighted begin; (None, None) without qualities."""
+    if qualities is None:
+        if weights is not None:
+            raise MhapError("weights without qualities")
+        return None, None
+    q = np.ascontiguousarray(qualities, np.uint8)
+    if q.shape != (len(bases),):
+        raise MhapError(f"{len(bases)} bases need {len(bases)} quality bytes, not {q.shape}")
+    return q, weights or WeightParams()
 
 
 def realign_plan(records, fasta, band=0, max_shift=0.2, query_fasta=None):
@@ -772,19 +833,28 @@ class CorrectSession(_Session):
 
     _prefix = "mhap_correct"
 
-    def __init__(self, fasta, query_fasta=None, handle=None, device=0):
+    def __init__(self, fasta, query_fasta=None, handle=None, device=0, qualities=None, weights=None):
+        """qualities: one Phred byte per base of the reads (all_qualities(fasta, query_fasta)) makes the session a weighted one
+        (mhap_correct_begin_weighted; "quality-weighted votes" in include/mhap_hip.h), weights its WeightParams (None: the defaults)."""
         bases, ids, offsets, lengths = _all_reads(fasta, query_fasta)
         self._bases = np.ascontiguousarray(bases, np.uint8)
         self.ids, self._offsets = np.ascontiguousarray(ids, np.int64), np.ascontiguousarray(offsets, np.int64)
         self.lengths = np.ascontiguousarray(lengths, np.int32)
-        super().__init__(handle, device, lambda: self._ms._chk(self._lib.mhap_correct_begin(
-            self._ms._h, _ptr(self._bases), len(self._bases), _ptr(self.ids), _ptr(self._offsets), _ptr(self.lengths), len(self.ids),
-            C.byref(self._s))))
+        self._quals, self.weights = _weighted_args(self._bases, qualities, weights)
+        if self._quals is None:
+            begin = lambda: self._lib.mhap_correct_begin(   # noqa: E731
+                self._ms._h, _ptr(self._bases), len(self._bases), _ptr(self.ids), _ptr(self._offsets), _ptr(self.lengths), len(self.ids),
+                C.byref(self._s))
+        else:   # (an empty array has no bytes to point at, and NULL would mean "unweighted")
+            begin = lambda: self._lib.mhap_correct_begin_weighted(   # noqa: E731
+                self._ms._h, _ptr(self._bases), _ptr(self._quals if len(self._quals) else np.zeros(1, np.uint8)), len(self._bases), _ptr(self.ids),
+                _ptr(self._offsets), _ptr(self.lengths), len(self.ids), C.byref(self.weights), C.byref(self._s))
+        super().__init__(handle, device, lambda: self._ms._chk(begin()))
 
     @classmethod
-    def begin(cls, fasta, query_fasta=None, handle=None, device=0):
+    def begin(cls, fasta, query_fasta=None, handle=None, device=0, qualities=None, weights=None):
         """The constructor under the C entry point's name: the bases go up and the vote table is zeroed."""
-        return cls(fasta, query_fasta=query_fasta, handle=handle, device=device)
+        return cls(fasta, query_fasta=query_fasta, handle=handle, device=device, qualities=qualities, weights=weights)
 
     def add(self, records, op_offsets, ops, views=None):
         """The votes of realigned records and their runs (pair q's are ops[op_offsets[q]:op_offsets[q + 1]]).  views: one byte per
@@ -1239,7 +1309,8 @@ class TrimSession(_ReadsSession):
             raise MhapError(f"TrimSession.trimmed: {len(fasta)} reads for a session of {len(self.ids)}")
         rows, flags = self.table()
         live = np.flatnonzero((flags & TRIM_DELETED) == 0)
-        return FastaData(fasta.bases, fasta.offsets[live] + rows[live, 0], rows[live, 1] - rows[live, 0], self.ids[live])
+        return FastaData(fasta.bases, fasta.offsets[live] + rows[live, 0], rows[live, 1] - rows[live, 0], self.ids[live],
+                         getattr(fasta, "qualities", None))   # (parallel to the same bases: a trimmed read's qualities are the matching slice)
 
 
 REPEAT_COUNTS = ("reads", "reads_with_interval", "whole_reads", "intervals", "repeat_bases", "bases", "eligible_records", "depth",
@@ -1456,16 +1527,24 @@ class ConsensusSession(_Session):
 
     _prefix = "mhap_consensus"
 
-    def __init__(self, graph_session, fasta, band=0, min_cov=4, query_fasta=None):
+    def __init__(self, graph_session, fasta, band=0, min_cov=4, query_fasta=None, qualities=None, weights=None):
+        """qualities, weights: as CorrectSession's (mhap_consensus_begin_weighted)."""
         self._gs = graph_session
         bases, ids, offsets, lengths = _all_reads(fasta, query_fasta)
         if len(ids) != len(graph_session.ids):
             raise MhapError(f"ConsensusSession: {len(ids)} reads for a graph of {len(graph_session.ids)}")
         self._bases = np.ascontiguousarray(bases, np.uint8)
         self._offsets = np.ascontiguousarray(offsets, np.int64)
+        self._quals, self.weights = _weighted_args(self._bases, qualities, weights)
         p = _ConsensusParams(band, min_cov)
-        super().__init__(graph_session._ms, None, lambda: self._ms._chk(self._lib.mhap_consensus_begin(   # (the graph session's handle)
-            graph_session._s, _opt(self._bases), len(self._bases), _opt(self._offsets), C.byref(p), C.byref(self._s))))
+        if self._quals is None:
+            begin = lambda: self._lib.mhap_consensus_begin(   # noqa: E731
+                graph_session._s, _opt(self._bases), len(self._bases), _opt(self._offsets), C.byref(p), C.byref(self._s))
+        else:
+            begin = lambda: self._lib.mhap_consensus_begin_weighted(   # noqa: E731
+                graph_session._s, _opt(self._bases), _ptr(self._quals if len(self._quals) else np.zeros(1, np.uint8)), len(self._bases),
+                _opt(self._offsets), C.byref(p), C.byref(self.weights), C.byref(self._s))
+        super().__init__(graph_session._ms, None, lambda: self._ms._chk(begin()))   # (the graph session's handle)
 
     def add(self, records):
         """The realigned records the graph was given (they stay on the device, 32 bytes each)."""
@@ -1730,6 +1809,16 @@ class FastaScan:
         self._lib.mhap_fasta_scan_bases.restype = C.c_int64
         self.n = self._lib.mhap_fasta_scan_reads(self._s)
         self.total_bases = self._lib.mhap_fasta_scan_bases(self._s)
+        self.has_qualities = bool(self._lib.mhap_fasta_scan_has_qualities(self._s))   # the file is FASTQ
+
+    def qualities(self):
+        """One Phred byte per base, in the reads' order (a FASTQ file only)."""
+        if not self.has_qualities:
+            raise MhapError("FastaScan.qualities: the file is FASTA and brings no base qualities")
+        out = np.zeros(max(self.total_bases, 1), np.uint8)
+        if self._lib.mhap_fasta_scan_qualities(self._s, _ptr(out)) != 0:
+            raise MhapError("mhap_fasta_scan_qualities failed")
+        return out[:self.total_bases]
 
     def __len__(self):
         return int(self.n)

@@ -1,6 +1,6 @@
 """Correct reads on the GPU from a file of MHAP overlaps: `python -m mhap_amd.correct overlaps.txt reads.fasta [queries.fasta] [--band W]
 [--min-identity X] [--min-coverage N] [--best-overlaps N [--best-min-span S]] [-o out.fasta] [--fastq out.fastq [--quality-per-vote N]
-[--quality-cap N]]` writes what `mhap-hip --realign --correct out.fasta` (with the same --best-overlaps flags, and --correct-fastq)
+[--quality-cap N]] [--weigh-qualities [--weight-q-lo Q] [--weight-q-hi Q]]` writes what `mhap-hip --realign --correct out.fasta` (with the same --best-overlaps flags, and --correct-fastq)
 writes for the same overlaps.
 
 The overlaps are parsed and realigned as `python -m mhap_amd.realign` does, with every alignment's path; the records that tool would
@@ -10,6 +10,9 @@ Output is FASTA, one unwrapped line per read: `>ID len=<corrected length> sub=<s
 low=<positions below --min-coverage>`, the ids numeric as the records print them; one line on stderr gives the totals.
 --fastq also writes the corrected reads as FASTQ, the same header fields behind `@`, with one quality per base from the votes that
 decided it ("base qualities" of include/mhap_hip.h; Phred+33), and one more stderr line counts them.
+
+--weigh-qualities, on FASTQ reads, lets every vote weigh the base quality of the read it comes from ("quality-weighted votes" of
+include/mhap_hip.h; `mhap-hip --weigh-qualities`), and one more stderr line counts the reads' bases per weight class.
 
 --best-overlaps N makes two passes ("overlap selection" of include/mhap_hip.h): the first realigns without paths and selects each
 read's N best views over the records that would vote (api.SelectSession), the second realigns only the records that keep a view, with
@@ -74,10 +77,12 @@ def select_pass(recs, fasta, queries, ms, band, min_identity, best_n, best_min_s
 
 
 def correct_overlaps(recs, fasta, queries=None, band=0, max_shift=0.2, min_identity=0.0, min_cov=4, device=0, batch=BATCH, best_n=0,
-                     best_min_span=500, selection=None, quality=None):
+                     best_min_span=500, selection=None, quality=None, weights=None):
     """Realign `recs` with paths in batches and vote: (seqs, stats, skipped_views, records that voted).  best_n > 0: only each read's
     best_n best views vote; `selection` (a dict) then takes the selection's rows, counts and ids.  quality: None, or a dict of per_vote and
-    cap, which then takes `quals` (a uint8 array per read) and `hist` of CorrectSession.quality."""
+    cap, which then takes `quals` (a uint8 array per read) and `hist` of CorrectSession.quality.  weights: None, or (q_lo, q_hi): the votes
+    weigh the reads' own qualities (api.all_qualities: FASTQ reads), "quality-weighted votes" of include/mhap_hip.h."""
+    wkw = {} if weights is None else dict(qualities=api.all_qualities(fasta, queries), weights=api.WeightParams(*weights))
     voted = 0
     with api.MinHashSearch(api.MhapParams(num_hashes=1, ordered_sketch_size=1, max_shift=max_shift, device=device)) as ms:
         views = None
@@ -86,7 +91,7 @@ def correct_overlaps(recs, fasta, queries=None, band=0, max_shift=0.2, min_ident
             recs = recs[which]
             if selection is not None:
                 selection.update(rows=table, counts=counts, ids=sel_ids)
-        with api.CorrectSession(fasta, query_fasta=queries, handle=ms) as cs:
+        with api.CorrectSession(fasta, query_fasta=queries, handle=ms, **wkw) as cs:
             for q0 in range(0, len(recs), batch):
                 out, _, op_offsets, ops = api.realign_records_paths(recs[q0:q0 + batch], fasta, band=band, handle=ms, query_fasta=queries)
                 rows = kept_rows(out, min_identity)
@@ -116,8 +121,12 @@ def main(argv=None):
     ap.add_argument("-o", "--output", default=None, help="the FASTA file to write (default: stdout)")
     ap.add_argument("--fastq", default=None, help="also write the corrected reads with base qualities to this FASTQ file")
     fastq.add_arguments(ap)
+    fastq.add_weight_arguments(ap)
     a = ap.parse_args(argv)
     quality, message = fastq.parameters(a, a.fastq is not None, "--fastq")
+    if message:
+        ap.error(message)
+    weights, message = fastq.weight_parameters(a, True, "a correction")
     if message:
         ap.error(message)
     if a.best_overlaps < 0:
@@ -133,11 +142,18 @@ def main(argv=None):
     recs = read_overlaps(a.overlaps)
     fasta = api.FastaData.from_file(a.reads)
     queries = api.FastaData.from_file(a.queries, len(fasta) if a.query_id_offset is None else a.query_id_offset) if a.queries else None
+    if weights is not None:
+        for path, f in ((a.reads, fasta), (a.queries, queries)):
+            if f is not None and f.qualities is None:
+                print(f"--weigh-qualities needs the base qualities of FASTQ reads: {path} is FASTA.")
+                return 1
+        bases, _, _, _ = api._all_reads(fasta, queries)
+        print(api.weight_classes_line(bases, api.all_qualities(fasta, queries), api.WeightParams(*weights)), file=sys.stderr)
     selection = {}
     ids, seqs, stats, skipped, voted = correct_overlaps(recs, fasta, queries, band=a.band, max_shift=a.max_shift, min_identity=a.min_identity,
                                                         min_cov=a.min_coverage, device=a.device, best_n=a.best_overlaps,
                                                         best_min_span=500 if a.best_min_span is None else a.best_min_span,
-                                                        selection=selection, quality=quality if a.fastq else None)
+                                                        selection=selection, quality=quality if a.fastq else None, weights=weights)
     text = format_fasta(ids, seqs, stats)
     if a.output:
         with open(a.output, "w") as fh:

@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -75,10 +76,33 @@ struct Quality {
 // A one-byte-per-base copy of every read the search has seen (the index's, then each -q file's) and the table of their ids, places and lengths.
 struct Reads {
   std::vector<uint8_t> bases; std::vector<int64_t> ids, offsets; std::vector<int32_t> lengths;
+  std::vector<uint8_t> quals;   // --weigh-qualities: one Phred byte per base, parallel to bases (a trimmed read's are the matching slice); else empty
   int64_t n() const { return (int64_t)ids.size(); }
-  void add(const mhap_fasta& fa) {
+  void add(const mhap_fasta& fa, const uint8_t* q = nullptr) {
     for (int64_t i = 0; i < fa.n; i++) { ids.push_back(fa.ids[i]); offsets.push_back((int64_t)bases.size() + fa.offsets[i]); lengths.push_back(fa.lengths[i]); }
     bases.insert(bases.end(), (const uint8_t*)fa.bases, (const uint8_t*)fa.bases + fa.total_bases);
+    if (q) quals.insert(quals.end(), q, q + fa.total_bases);
+  }
+  // One file of -s into the table.  weigh (--weigh-qualities): with its base qualities, which a FASTA file does not bring.
+  void read_file(const std::string& path, bool weigh, const std::function<void(const mhap_fasta&)>& seen = nullptr) {
+    char err[512] = {0};
+    mhap_fasta fa;
+    uint8_t* q = nullptr;
+    if ((weigh ? mhap_fasta_read_qualities(path.c_str(), n(), &fa, &q, err, sizeof err) : mhap_fasta_read(path.c_str(), n(), &fa, err, sizeof err)) != MHAP_OK) die(err);
+    if (weigh && !q) { printf("--weigh-qualities needs the base qualities of FASTQ reads: %s is FASTA.\n", path.c_str()); exit(1); }
+    if (seen) seen(fa);
+    add(fa, q);
+    mhap_qualities_free(q);
+    mhap_fasta_free(&fa);
+  }
+  // the stderr line of --weigh-qualities: the A, C, G, T bases of the reads per weight class
+  void weight_line(const mhap_weight_params& w) const {
+    long long c[3] = {0, 0, 0};
+    for (size_t i = 0; i < quals.size(); i++) {
+      const uint8_t b = bases[i];
+      if (b == 'A' || b == 'C' || b == 'G' || b == 'T') c[(quals[i] >= w.q_lo ? 1 : 0) + (quals[i] >= w.q_hi ? 1 : 0)]++;
+    }
+    fprintf(stderr, "Weights: q_lo = %d, q_hi = %d; %lld bases of weight 1, %lld of weight 2, %lld of weight 3\n", w.q_lo, w.q_hi, c[0], c[1], c[2]);
   }
   // the table rewritten onto the surviving trimmed reads (the bases stay where they are: a trimmed read begins `begin` bytes later)
   void retrim(const std::vector<int32_t>& rows /* n x 4: begin, end, .. */, const std::vector<uint8_t>& flags) {
@@ -204,7 +228,11 @@ struct HpcStage : Stage {
 // --correct: every kept record votes on both of its reads, or (add_selected) with the views the selection kept
 struct CorrectStage : Stage {
   std::string fasta; int32_t min_cov = 0; mhap_correct_session* s = nullptr; Quality quality;
-  void begin(const Reads& R) { chk(h, mhap_correct_begin(h, R.bases.data(), (int64_t)R.bases.size(), R.ids.data(), R.offsets.data(), R.lengths.data(), R.n(), &s)); }
+  bool weigh = false; mhap_weight_params wp;   // --weigh-qualities: the votes weigh the reads' own base qualities
+  void begin(const Reads& R) {
+    chk(h, mhap_correct_begin_weighted(h, R.bases.data(), weigh ? R.quals.data() : nullptr, (int64_t)R.bases.size(), R.ids.data(), R.offsets.data(),
+                                       R.lengths.data(), R.n(), &wp, &s));
+  }
   int add(const Batch& b) { Tick t{seconds}; return mhap_correct_add(s, b.out.data(), b.k, b.paths); }
   // the records as they came give the alignments of the first pass again (the aligner is deterministic), now with their paths, 65 536 at a time
   void add_selected(const std::vector<mhap_record>& found, const std::vector<uint8_t>& views, Realigner& A) {
@@ -337,6 +365,7 @@ struct RepeatStage : Stage {
 // --gfa: every record it is given is classed for the string graph (queued: nothing waits); finish cleans, compacts into unitigs, spells them or calls their consensus
 struct GraphStage : Stage {
   mhap_graph_params p; std::string gfa, unitigs, consensus_fasta; mhap_graph_session* s = nullptr;
+  bool weigh = false; mhap_weight_params wp;   // --weigh-qualities, for the consensus
   bool clean = false, consensus = false; mhap_clean_params cp; mhap_consensus_params kp; Quality quality; int64_t qhist[MHAP_QUALITY_BINS];
   std::vector<mhap_record> held;              // --gfa-consensus: the consensus takes what the graph took
   int64_t uc[MHAP_UNITIG_COUNTS], kc[MHAP_CONSENSUS_COUNTS];
@@ -362,7 +391,7 @@ struct GraphStage : Stage {
     if (!consensus) chk(h, mhap_graph_spell(s, R.bases.data(), (int64_t)R.bases.size(), R.offsets.data(), seq.data()));
     else {   // the held records, fed now that the unitigs are served; the consensus takes the place of the spelling
       mhap_consensus_session* cs = nullptr;
-      chk(h, mhap_consensus_begin(s, R.bases.data(), (int64_t)R.bases.size(), R.offsets.data(), &kp, &cs));
+      chk(h, mhap_consensus_begin_weighted(s, R.bases.data(), weigh ? R.quals.data() : nullptr, (int64_t)R.bases.size(), R.offsets.data(), &kp, &wp, &cs));
       chk(h, mhap_consensus_add(cs, held.data(), (int64_t)held.size()));
       chk(h, mhap_consensus_run(cs, kc));
       int64_t n_draft = 0, n_out = 0;

@@ -34,6 +34,7 @@
 #include "graph_class.hpp"
 #include "mhap_internal.hpp"
 #include "vote_common.hpp"
+#include "weighted_vote.hpp"
 
 namespace mhap {
 namespace {
@@ -235,6 +236,94 @@ __global__ __launch_bounds__(CK_T) void cqual_kernel(const uint8_t* __restrict__
   if (tid < QUAL_BINS && bins[tid]) atomicAdd(hist + tid, bins[tid]);
 }
 
+// The three kernels of a weighted session ("quality-weighted votes" in include/mhap_hip.h): the schedules of cvote_kernel, ccall_kernel
+// and cqual_kernel over weighted_vote.hpp's walk, decision and qualities.  quals: one Phred byte per base of the reads (the drafts that
+// follow them in `bases` are targets only); a draft byte has no single quality, so own counts with the neutral weight.
+__global__ __launch_bounds__(64) void wcvote_kernel(const uint8_t* __restrict__ bases, const uint8_t* __restrict__ quals, Weights W,
+                                                    const VoteItem* __restrict__ items, const uint32_t* __restrict__ ops,
+                                                    uint32_t* __restrict__ table) {
+  const VoteItem it = items[blockIdx.x];
+  vote_walk_weighted(bases, quals, W, it, ops, table);
+}
+
+__global__ __launch_bounds__(CK_T) void wccall_kernel(const uint8_t* __restrict__ draft, int64_t nu, const int64_t* __restrict__ u_len,
+                                                      const int64_t* __restrict__ ubase, const int64_t* __restrict__ utile,
+                                                      const uint32_t* __restrict__ table, int min_cov, int32_t* __restrict__ tile_len,
+                                                      int32_t* __restrict__ tile_counts, const int64_t* __restrict__ tile_off,
+                                                      const int64_t* __restrict__ out_offsets, uint8_t* __restrict__ out, int64_t* __restrict__ posmap) {
+  __shared__ int wave_sum[CK_T / 64];
+  __shared__ int acc[4];   // n_sub, n_del, n_ins, n_low
+  const int64_t tile = blockIdx.x;
+  const int64_t k = last_at_or_before(utile, nu, tile);
+  const int64_t L = u_len[k], t_begin = (tile - utile[k]) * CT, t_end = min64(L, t_begin + CT);
+  const uint8_t* own = draft + ubase[k];
+  const uint32_t* w = table + (int64_t)CK_WORDS * ubase[k];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid < 4) acc[tid] = 0;
+  int64_t written = 0;
+  int my[4] = {0, 0, 0, 0};
+  for (int64_t t0 = t_begin; t0 < t_end; t0 += CK_T) {
+    const int64_t t = t0 + tid;
+    Decision D{0, {0, 0, 0, 0, 0}, 0, 0, 0, 0};
+    if (t < t_end) D = decide_weighted(w, L, t, own[t], W_NEUTRAL, min_cov);
+    my[0] += D.sub; my[1] += D.del; my[2] += D.ins; my[3] += D.low;
+    int incl = D.n;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int u = __shfl_up(incl, d);
+      if (lane >= d) incl += u;
+    }
+    __syncthreads();
+    if (lane == 63) wave_sum[wave] = incl;
+    __syncthreads();
+    int before = 0, chunk = 0;
+    for (int u = 0; u < CK_T / 64; u++) { if (u < wave) before += wave_sum[u]; chunk += wave_sum[u]; }
+    if (tile_off && t < t_end) {
+      const int64_t at = tile_off[tile] + written + before + (incl - D.n);
+      posmap[ubase[k] + t] = at - out_offsets[k];
+      for (int u = 0; u < D.n; u++) out[at + u] = D.bytes[u];
+    }
+    written += chunk;
+  }
+  __syncthreads();
+  for (int u = 0; u < 4; u++) if (my[u]) atomicAdd(&acc[u], my[u]);
+  __syncthreads();
+  if (tid == 0 && !tile_off) {
+    tile_len[tile] = (int32_t)written;
+    for (int u = 0; u < 4; u++) tile_counts[4 * tile + u] = acc[u];
+  }
+}
+
+__global__ __launch_bounds__(CK_T) void wcqual_kernel(const uint8_t* __restrict__ draft, int64_t nu, const int64_t* __restrict__ u_len,
+                                                      const int64_t* __restrict__ ubase, const int64_t* __restrict__ utile,
+                                                      const uint32_t* __restrict__ table, int min_cov, int per_vote, int cap,
+                                                      const int64_t* __restrict__ out_offsets, const int64_t* __restrict__ posmap,
+                                                      uint8_t* __restrict__ quals, unsigned long long* __restrict__ hist) {
+  __shared__ unsigned long long bins[QUAL_BINS];
+  const int64_t tile = blockIdx.x;
+  const int64_t k = last_at_or_before(utile, nu, tile);
+  const int64_t L = u_len[k], t_begin = (tile - utile[k]) * CT, t_end = min64(L, t_begin + CT);
+  const uint8_t* own = draft + ubase[k];
+  const uint32_t* w = table + (int64_t)CK_WORDS * ubase[k];
+  const int64_t o_end = out_offsets[k + 1];
+  const int tid = threadIdx.x;
+  if (tid < QUAL_BINS) bins[tid] = 0ull;
+  __syncthreads();
+  for (int64_t t = t_begin + tid; t < t_end; t += CK_T) {
+    const Decision D = decide_weighted(w, L, t, own[t], W_NEUTRAL, min_cov);
+    uint8_t q[1 + CK_KI] = {0, 0, 0, 0, 0};
+    decide_quality_weighted(w, L, t, own[t], W_NEUTRAL, D, per_vote, cap, q);
+    const int64_t at = out_offsets[k] + posmap[ubase[k] + t];
+    for (int u = 0; u < D.n; u++)
+      if (at + u < o_end) {   // (the map is that of this table and this min_cov: always)
+        quals[at + u] = q[u];
+        atomicAdd(&bins[q[u]], 1ull);
+      }
+  }
+  __syncthreads();
+  if (tid < QUAL_BINS && bins[tid]) atomicAdd(hist + tid, bins[tid]);
+}
+
 // the cap on reads per tile: 65 535, lowered by MHAP_CONSENSUS_TILE_CAP (tests), read at each run
 uint32_t tile_cap() {
   if (const char* e = getenv("MHAP_CONSENSUS_TILE_CAP")) {
@@ -258,16 +347,18 @@ struct mhap_consensus_session {
   int64_t n_reads = 0, n_bases = 0, n_items = 0;
   std::vector<int64_t> offsets;
   std::vector<uint8_t> host_bases;                        // the reads, then (from a run on) the drafts: what the aligner is given
+  bool weighted = false;                                  // begun with qualities: the w* kernels, WK_CAP reads per tile
+  Weights W{0, 0};
   // the last run; n_unitigs < 0: none has completed
   int64_t n_unitigs = -1, n_draft = 0, out_bytes = 0;
   double seconds[4] = {0, 0, 0, 0};                       // the host's wall time of the last run: placement, alignment, vote, call
   std::vector<int64_t> u_len, ubase, out_offsets, stats, place;
   DevBuf bases, roff, items, rlen, mem_vertex, mem_unitig, mem_off, key1, key2, d_place, d_pairs, d_ustart, d_ulen, d_ucirc, d_ubase,
-      d_utile, m_vertex, m_offset, tile_reads, table, vitems, ops, tile_len, tile_counts, tile_off, d_outoff, out, posmap, quals, hist;
+      d_utile, m_vertex, m_offset, tile_reads, table, vitems, ops, tile_len, tile_counts, tile_off, d_outoff, out, posmap, quals, hist, in_quals;
   void release() {
     for (DevBuf* b : {&bases, &roff, &items, &rlen, &mem_vertex, &mem_unitig, &mem_off, &key1, &key2, &d_place, &d_pairs, &d_ustart, &d_ulen,
                        &d_ucirc, &d_ubase, &d_utile, &m_vertex, &m_offset, &tile_reads, &table, &vitems, &ops, &tile_len, &tile_counts, &tile_off,
-                       &d_outoff, &out, &posmap, &quals, &hist}) b->release();
+                       &d_outoff, &out, &posmap, &quals, &hist, &in_quals}) b->release();
   }
 };
 
@@ -295,9 +386,10 @@ extern "C" void mhap_consensus_default_params(mhap_consensus_params* p) {
   p->band = 0; p->min_cov = 4;
 }
 
-extern "C" int mhap_consensus_begin(mhap_graph_session* g, const uint8_t* bases, int64_t n_bases, const int64_t* offsets,
-                                    const mhap_consensus_params* params, mhap_consensus_session** session) {
-  const char* who = "mhap_consensus_begin";
+// the begin behind mhap_consensus_begin (qualities == nullptr) and mhap_consensus_begin_weighted
+static int consensus_begin(const char* who, mhap_graph_session* g, const uint8_t* bases, const uint8_t* qualities, int64_t n_bases,
+                           const int64_t* offsets, const mhap_consensus_params* params, const mhap_weight_params* weights,
+                           mhap_consensus_session** session) {
   if (session) *session = nullptr;
   if (!g) return MHAP_E_INVALID;
   const GraphView gv = graph_view(g);
@@ -312,8 +404,13 @@ extern "C" int mhap_consensus_begin(mhap_graph_session* g, const uint8_t* bases,
       *v.err = std::string(who) + ": read " + std::to_string(r) + " lies outside the " + std::to_string(n_bases) + " bases";
       return MHAP_E_INVALID;
     }
+  mhap_weight_params wp;
+  mhap_weight_default_params(&wp);
+  if (qualities && weights) wp = *weights;
+  if (qualities && !weight_params_ok(wp.q_lo, wp.q_hi, who, *v.err)) return MHAP_E_INVALID;
   mhap_consensus_session* s = new mhap_consensus_session();
   s->g = g; s->h = gv.h; s->gen = gv.unitig_gen; s->band = p.band; s->min_cov = p.min_cov;
+  s->weighted = qualities != nullptr; s->W = Weights{wp.q_lo, wp.q_hi};
   s->n_reads = gv.n_reads; s->n_bases = n_bases;
   s->offsets.assign(offsets, offsets + gv.n_reads);
   s->host_bases.assign(bases, bases + n_bases);
@@ -321,10 +418,24 @@ extern "C" int mhap_consensus_begin(mhap_graph_session* g, const uint8_t* bases,
   const size_t rb = (size_t)std::max<int64_t>(gv.n_reads, 1);
   hipError_t e = s->roff.ensure(8 * rb);
   if (e == hipSuccess && gv.n_reads > 0) e = hipMemcpyAsync(s->roff.p, s->offsets.data(), 8 * (size_t)gv.n_reads, hipMemcpyHostToDevice, v.stream);
+  if (e == hipSuccess && s->weighted) e = s->in_quals.ensure((size_t)std::max<int64_t>(n_bases, 1));
+  if (e == hipSuccess && s->weighted && n_bases > 0) e = hipMemcpyAsync(s->in_quals.p, qualities, (size_t)n_bases, hipMemcpyHostToDevice, v.stream);
   if (e == hipSuccess) e = hipStreamSynchronize(v.stream);
   if (e != hipSuccess) { s->release(); delete s; return hip_fail(v, who, "the table of reads", e); }
   *session = s;
   return MHAP_OK;
+}
+
+extern "C" int mhap_consensus_begin(mhap_graph_session* g, const uint8_t* bases, int64_t n_bases, const int64_t* offsets,
+                                    const mhap_consensus_params* params, mhap_consensus_session** session) {
+  return consensus_begin("mhap_consensus_begin", g, bases, nullptr, n_bases, offsets, params, nullptr, session);
+}
+
+extern "C" int mhap_consensus_begin_weighted(mhap_graph_session* g, const uint8_t* bases, const uint8_t* qualities, int64_t n_bases,
+                                             const int64_t* offsets, const mhap_consensus_params* params, const mhap_weight_params* weights,
+                                             mhap_consensus_session** session) {
+  return consensus_begin(qualities ? "mhap_consensus_begin_weighted" : "mhap_consensus_begin", g, bases, qualities, n_bases, offsets, params, weights,
+                         session);
 }
 
 extern "C" int mhap_consensus_add(mhap_consensus_session* s, const mhap_record* recs, int64_t n) {
@@ -447,7 +558,7 @@ extern "C" int mhap_consensus_run(mhap_consensus_session* s, int64_t* counts) {
   }
   if (n_tiles > 0 && (e = hipMemcpyAsync(tile_reads.data(), s->tile_reads.p, 4 * (size_t)n_tiles, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return fail("download");
   if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return fail("the placement kernels");
-  const uint32_t cap = tile_cap();
+  const uint32_t cap = s->weighted ? std::min<uint32_t>(tile_cap(), WK_CAP) : tile_cap();   // (a view adds up to 3 to a counter)
   for (int64_t k = 0; k < nu; k++)
     for (int64_t j = utile[(size_t)k]; j < utile[(size_t)k + 1]; j++)
       if (tile_reads[(size_t)j] > cap) {
@@ -485,8 +596,12 @@ extern "C" int mhap_consensus_run(mhap_consensus_session* s, int64_t* counts) {
     up(s->ops, paths->ops.data(), 4 * paths->ops.size());
     up(s->vitems, vitems.data(), sizeof(VoteItem) * vitems.size());
     if (e == hipSuccess) {
-      hipLaunchKernelGGL(cvote_kernel, dim3((unsigned)vitems.size()), dim3(64), 0, v.stream, s->bases.as<uint8_t>(), s->vitems.as<VoteItem>(),
-                         s->ops.as<uint32_t>(), s->table.as<uint32_t>());
+      if (s->weighted)
+        hipLaunchKernelGGL(wcvote_kernel, dim3((unsigned)vitems.size()), dim3(64), 0, v.stream, s->bases.as<uint8_t>(), s->in_quals.as<uint8_t>(),
+                           s->W, s->vitems.as<VoteItem>(), s->ops.as<uint32_t>(), s->table.as<uint32_t>());
+      else
+        hipLaunchKernelGGL(cvote_kernel, dim3((unsigned)vitems.size()), dim3(64), 0, v.stream, s->bases.as<uint8_t>(), s->vitems.as<VoteItem>(),
+                           s->ops.as<uint32_t>(), s->table.as<uint32_t>());
       e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(v.stream);   // (the runs and the items are the host's until here)
@@ -500,7 +615,7 @@ extern "C" int mhap_consensus_run(mhap_consensus_session* s, int64_t* counts) {
   std::vector<int64_t> tile_off((size_t)n_tiles), out_offsets((size_t)nu + 1, 0), stats((size_t)nu * 6, 0);
   const uint8_t* draft = s->bases.as<uint8_t>() + s->n_bases;
   if (n_tiles > 0) {
-    hipLaunchKernelGGL(ccall_kernel, dim3((unsigned)n_tiles), dim3(CK_T), 0, v.stream, draft, nu, s->d_ulen.as<int64_t>(), s->d_ubase.as<int64_t>(),
+    hipLaunchKernelGGL(s->weighted ? wccall_kernel : ccall_kernel, dim3((unsigned)n_tiles), dim3(CK_T), 0, v.stream, draft, nu, s->d_ulen.as<int64_t>(), s->d_ubase.as<int64_t>(),
                        s->d_utile.as<int64_t>(), s->table.as<uint32_t>(), (int)s->min_cov, s->tile_len.as<int32_t>(), s->tile_counts.as<int32_t>(),
                        (const int64_t*)nullptr, (const int64_t*)nullptr, (uint8_t*)nullptr, (int64_t*)nullptr);
     if ((e = hipGetLastError()) != hipSuccess) return fail("launch");
@@ -528,7 +643,7 @@ extern "C" int mhap_consensus_run(mhap_consensus_session* s, int64_t* counts) {
     up(s->tile_off, tile_off.data(), 8 * (size_t)n_tiles);
     up(s->d_outoff, out_offsets.data(), 8 * (size_t)(nu + 1));
     if (e != hipSuccess) return fail("upload");
-    hipLaunchKernelGGL(ccall_kernel, dim3((unsigned)n_tiles), dim3(CK_T), 0, v.stream, draft, nu, s->d_ulen.as<int64_t>(), s->d_ubase.as<int64_t>(),
+    hipLaunchKernelGGL(s->weighted ? wccall_kernel : ccall_kernel, dim3((unsigned)n_tiles), dim3(CK_T), 0, v.stream, draft, nu, s->d_ulen.as<int64_t>(), s->d_ubase.as<int64_t>(),
                        s->d_utile.as<int64_t>(), s->table.as<uint32_t>(), (int)s->min_cov, s->tile_len.as<int32_t>(), s->tile_counts.as<int32_t>(),
                        s->tile_off.as<int64_t>(), s->d_outoff.as<int64_t>(), s->out.as<uint8_t>(), s->posmap.as<int64_t>());
     if ((e = hipGetLastError()) != hipSuccess) return fail("launch");
@@ -613,7 +728,7 @@ extern "C" int mhap_consensus_quality(mhap_consensus_session* s, const mhap_qual
   hipError_t e;
   if ((e = s->quals.ensure((size_t)s->out_bytes)) != hipSuccess || (e = s->hist.ensure(8 * QUAL_BINS)) != hipSuccess) return hip_fail(v, who, "hipMalloc of the quality bytes", e);
   if ((e = hipMemsetAsync(s->hist.p, 0, 8 * QUAL_BINS, v.stream)) != hipSuccess) return hip_fail(v, who, "memset", e);
-  hipLaunchKernelGGL(cqual_kernel, dim3((unsigned)n_tiles), dim3(CK_T), 0, v.stream, s->bases.as<uint8_t>() + s->n_bases, s->n_unitigs,
+  hipLaunchKernelGGL(s->weighted ? wcqual_kernel : cqual_kernel, dim3((unsigned)n_tiles), dim3(CK_T), 0, v.stream, s->bases.as<uint8_t>() + s->n_bases, s->n_unitigs,
                      s->d_ulen.as<int64_t>(), s->d_ubase.as<int64_t>(), s->d_utile.as<int64_t>(), s->table.as<uint32_t>(), (int)s->min_cov,
                      (int)p.per_vote, (int)p.cap, s->d_outoff.as<int64_t>(), s->posmap.as<int64_t>(), s->quals.as<uint8_t>(),
                      s->hist.as<unsigned long long>());

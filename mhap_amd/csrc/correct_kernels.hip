@@ -36,6 +36,7 @@
 #include "mhap_internal.hpp"
 #include "read_table.hpp"
 #include "vote_common.hpp"
+#include "weighted_vote.hpp"
 
 namespace mhap {
 namespace {
@@ -141,6 +142,111 @@ __global__ __launch_bounds__(CK_T) void qcall_kernel(const uint8_t* __restrict__
   if (tid < QUAL_BINS && bins[tid]) atomicAdd(hist + tid, bins[tid]);
 }
 
+// The three kernels of a weighted session ("quality-weighted votes" in include/mhap_hip.h): the schedules of vote_kernel, call_kernel
+// and qcall_kernel over weighted_vote.hpp's walk, decision and qualities.  quals: one Phred byte per base, parallel to bases; the own
+// byte's weight is read next to the own byte.
+__global__ __launch_bounds__(64) void wvote_kernel(const uint8_t* __restrict__ bases, const uint8_t* __restrict__ quals, Weights W,
+                                                   const VoteItem* __restrict__ items, const uint32_t* __restrict__ ops,
+                                                   uint32_t* __restrict__ table) {
+  const VoteItem it = items[blockIdx.x];
+  vote_walk_weighted(bases, quals, W, it, ops, table);
+}
+
+__global__ __launch_bounds__(CK_T) void wcall_kernel(const uint8_t* __restrict__ bases, const uint8_t* __restrict__ quals, Weights W,
+                                                     const int64_t* __restrict__ read_off, const int64_t* __restrict__ read_pos,
+                                                     const int32_t* __restrict__ lengths, const uint32_t* __restrict__ table, int min_cov,
+                                                     const int64_t* __restrict__ out_offsets, uint8_t* __restrict__ out,
+                                                     int32_t* __restrict__ stats) {
+  __shared__ int wave_sum[CK_T / 64];
+  __shared__ int acc[5];   // len_out, n_sub, n_del, n_ins, n_low
+  const int64_t r = blockIdx.x;
+  const int64_t len = lengths[r];
+  const uint8_t* own = bases + read_off[r];
+  const uint8_t* own_q = quals + read_off[r];
+  const uint32_t* w = table + (int64_t)CK_WORDS * read_pos[r];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid < 5) acc[tid] = 0;
+  int64_t written = 0;
+  int my[5] = {0, 0, 0, 0, 0};
+  for (int64_t t0 = 0; t0 < len; t0 += CK_T) {
+    const int64_t t = t0 + tid;
+    Decision D{0, {0, 0, 0, 0, 0}, 0, 0, 0, 0};
+    if (t < len) D = decide_weighted(w, len, t, own[t], weight_of(own_q[t], W), min_cov);
+    my[0] += D.n; my[1] += D.sub; my[2] += D.del; my[3] += D.ins; my[4] += D.low;
+    int incl = D.n;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int u = __shfl_up(incl, d);
+      if (lane >= d) incl += u;
+    }
+    __syncthreads();   // wave_sum of the previous tile has been read
+    if (lane == 63) wave_sum[wave] = incl;
+    __syncthreads();
+    int before = 0, tile = 0;
+    for (int u = 0; u < CK_T / 64; u++) { if (u < wave) before += wave_sum[u]; tile += wave_sum[u]; }
+    if (out_offsets) {
+      uint8_t* o = out + out_offsets[r] + written + before + (incl - D.n);
+      for (int u = 0; u < D.n; u++) o[u] = D.bytes[u];
+    }
+    written += tile;
+  }
+  __syncthreads();
+  for (int u = 0; u < 5; u++) if (my[u]) atomicAdd(&acc[u], my[u]);
+  __syncthreads();
+  if (tid == 0 && !out_offsets) {
+    int32_t* s = stats + 6 * r;
+    s[0] = (int32_t)len; s[1] = acc[0]; s[2] = acc[1]; s[3] = acc[2]; s[4] = acc[3]; s[5] = acc[4];
+  }
+}
+
+__global__ __launch_bounds__(CK_T) void wqcall_kernel(const uint8_t* __restrict__ bases, const uint8_t* __restrict__ in_quals, Weights W,
+                                                      const int64_t* __restrict__ read_off, const int64_t* __restrict__ read_pos,
+                                                      const int32_t* __restrict__ lengths, const uint32_t* __restrict__ table, int min_cov,
+                                                      int per_vote, int cap, const int64_t* __restrict__ out_offsets,
+                                                      uint8_t* __restrict__ quals, unsigned long long* __restrict__ hist) {
+  __shared__ int wave_sum[CK_T / 64];
+  __shared__ unsigned long long bins[QUAL_BINS];
+  const int64_t r = blockIdx.x;
+  const int64_t len = lengths[r];
+  const uint8_t* own = bases + read_off[r];
+  const uint8_t* own_q = in_quals + read_off[r];
+  const uint32_t* w = table + (int64_t)CK_WORDS * read_pos[r];
+  const int64_t o_begin = out_offsets[r], o_end = out_offsets[r + 1];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid < QUAL_BINS) bins[tid] = 0ull;
+  int64_t written = 0;
+  for (int64_t t0 = 0; t0 < len; t0 += CK_T) {
+    const int64_t t = t0 + tid;
+    Decision D{0, {0, 0, 0, 0, 0}, 0, 0, 0, 0};
+    uint8_t q[1 + CK_KI] = {0, 0, 0, 0, 0};
+    if (t < len) {
+      const int own_w = weight_of(own_q[t], W);
+      D = decide_weighted(w, len, t, own[t], own_w, min_cov);
+      decide_quality_weighted(w, len, t, own[t], own_w, D, per_vote, cap, q);
+    }
+    int incl = D.n;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int u = __shfl_up(incl, d);
+      if (lane >= d) incl += u;
+    }
+    __syncthreads();   // wave_sum of the previous tile has been read (and, the first time, the bins are zero)
+    if (lane == 63) wave_sum[wave] = incl;
+    __syncthreads();
+    int before = 0, tile = 0;
+    for (int u = 0; u < CK_T / 64; u++) { if (u < wave) before += wave_sum[u]; tile += wave_sum[u]; }
+    const int64_t at = o_begin + written + before + (incl - D.n);
+    for (int u = 0; u < D.n; u++)
+      if (at + u < o_end) {   // (the offsets are those of this table and this min_cov: always)
+        quals[at + u] = q[u];
+        atomicAdd(&bins[q[u]], 1ull);
+      }
+    written += tile;
+  }
+  __syncthreads();
+  if (tid < QUAL_BINS && bins[tid]) atomicAdd(hist + tid, bins[tid]);
+}
+
 }  // namespace
 }  // namespace mhap
 
@@ -156,16 +262,25 @@ struct mhap_correct_session {
   int64_t skipped = 0, out_bytes = -1;                  // out_bytes < 0: no finish yet
   int32_t min_cov = 0;                                  // of the last completed finish
   bool voted_since = false;                             // votes were cast after that finish: its offsets are not the table's any more
-  DevBuf bases, table, read_off, read_pos, read_len, items, ops, out_off, out, stats, quals, hist;
+  bool weighted = false;                                // begun with qualities: the w* kernels, WK_CAP views per target
+  Weights W{0, 0};
+  DevBuf bases, in_quals, table, read_off, read_pos, read_len, items, ops, out_off, out, stats, quals, hist;
   void release() {
+    in_quals.release();
     bases.release(); table.release(); read_off.release(); read_pos.release(); read_len.release(); items.release(); ops.release();
     out_off.release(); out.release(); stats.release(); quals.release(); hist.release();
   }
 };
 
-extern "C" int mhap_correct_begin(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const int64_t* read_ids, const int64_t* offsets,
-                                  const int32_t* lengths, int64_t n_reads, mhap_correct_session** session) {
-  const char* who = "mhap_correct_begin";
+extern "C" void mhap_weight_default_params(mhap_weight_params* p) {
+  if (!p) return;
+  p->q_lo = 7; p->q_hi = 20;   // the fewest wrong bytes on the restatement (EXPERIMENTS.md, "Quality-weighted votes")
+}
+
+// the begin behind mhap_correct_begin (qualities == nullptr) and mhap_correct_begin_weighted
+static int correct_begin(const char* who, mhap_handle* h, const uint8_t* bases, const uint8_t* qualities, int64_t n_bases,
+                         const int64_t* read_ids, const int64_t* offsets, const int32_t* lengths, int64_t n_reads,
+                         const mhap_weight_params* weights, mhap_correct_session** session) {
   if (session) *session = nullptr;
   if (!h) return MHAP_E_INVALID;
   HandleView v = handle_view(h);
@@ -178,8 +293,13 @@ extern "C" int mhap_correct_begin(mhap_handle* h, const uint8_t* bases, int64_t 
       *v.err = std::string(who) + ": read " + std::to_string(i) + " lies outside the " + std::to_string(n_bases) + " bases";
       return MHAP_E_INVALID;
     }
+  mhap_weight_params wp;
+  mhap_weight_default_params(&wp);
+  if (qualities && weights) wp = *weights;
+  if (qualities && !weight_params_ok(wp.q_lo, wp.q_hi, who, *v.err)) return MHAP_E_INVALID;
   mhap_correct_session* s = new mhap_correct_session();
   s->h = h; s->n_reads = n_reads; s->n_bases = n_bases;
+  s->weighted = qualities != nullptr; s->W = Weights{wp.q_lo, wp.q_hi};
   s->offsets.assign(offsets, offsets + n_reads);
   s->lengths.assign(lengths, lengths + n_reads);
   s->pos.resize((size_t)n_reads);
@@ -198,6 +318,7 @@ extern "C" int mhap_correct_begin(mhap_handle* h, const uint8_t* bases, int64_t 
     if (e == hipSuccess && bytes > 0) e = hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, v.stream);
   };
   up(s->bases, bases, (size_t)n_bases);
+  if (s->weighted) up(s->in_quals, qualities, (size_t)n_bases);
   up(s->read_off, s->offsets.data(), 8 * (size_t)n_reads);
   up(s->read_pos, s->pos.data(), 8 * (size_t)n_reads);
   up(s->read_len, s->lengths.data(), 4 * (size_t)n_reads);
@@ -213,6 +334,18 @@ extern "C" int mhap_correct_begin(mhap_handle* h, const uint8_t* bases, int64_t 
   }
   *session = s;
   return MHAP_OK;
+}
+
+extern "C" int mhap_correct_begin(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const int64_t* read_ids, const int64_t* offsets,
+                                  const int32_t* lengths, int64_t n_reads, mhap_correct_session** session) {
+  return correct_begin("mhap_correct_begin", h, bases, nullptr, n_bases, read_ids, offsets, lengths, n_reads, nullptr, session);
+}
+
+extern "C" int mhap_correct_begin_weighted(mhap_handle* h, const uint8_t* bases, const uint8_t* qualities, int64_t n_bases,
+                                           const int64_t* read_ids, const int64_t* offsets, const int32_t* lengths, int64_t n_reads,
+                                           const mhap_weight_params* weights, mhap_correct_session** session) {
+  return correct_begin(qualities ? "mhap_correct_begin_weighted" : "mhap_correct_begin", h, bases, qualities, n_bases, read_ids, offsets, lengths,
+                       n_reads, weights, session);
 }
 
 // the add behind mhap_correct_add (views == nullptr: both views of every record) and mhap_correct_add_views
@@ -265,7 +398,7 @@ static int correct_add(const char* who, mhap_correct_session* s, const mhap_reco
     for (int view = 0; view < 2; view++) {
       const int64_t target = idx[view];
       if (views && !(views[q] & (1u << view))) continue;   // not selected: no vote, no place under the cap, not a skipped view
-      if (s->views[(size_t)target] >= CK_CAP) { skipped++; continue; }
+      if (s->views[(size_t)target] >= (s->weighted ? WK_CAP : CK_CAP)) { skipped++; continue; }
       s->views[(size_t)target] += 1;
       accepted.emplace_back(target, 1);
       VoteItem it{};
@@ -289,8 +422,12 @@ static int correct_add(const char* who, mhap_correct_session* s, const mhap_reco
   for (size_t g0 = 0; g0 < items.size(); g0 += CHUNK) {
     const size_t c = std::min(CHUNK, items.size() - g0);
     if ((e = hipMemcpyAsync(s->items.p, items.data() + g0, sizeof(VoteItem) * c, hipMemcpyHostToDevice, v.stream)) != hipSuccess) return hip_fail(v, who, "upload", e);
-    hipLaunchKernelGGL(vote_kernel, dim3((unsigned)c), dim3(64), 0, v.stream, s->bases.as<uint8_t>(), s->items.as<VoteItem>(),
-                       s->ops.as<uint32_t>(), s->table.as<uint32_t>());
+    if (s->weighted)
+      hipLaunchKernelGGL(wvote_kernel, dim3((unsigned)c), dim3(64), 0, v.stream, s->bases.as<uint8_t>(), s->in_quals.as<uint8_t>(), s->W,
+                         s->items.as<VoteItem>(), s->ops.as<uint32_t>(), s->table.as<uint32_t>());
+    else
+      hipLaunchKernelGGL(vote_kernel, dim3((unsigned)c), dim3(64), 0, v.stream, s->bases.as<uint8_t>(), s->items.as<VoteItem>(),
+                         s->ops.as<uint32_t>(), s->table.as<uint32_t>());
     if ((e = hipGetLastError()) != hipSuccess) return hip_fail(v, who, "launch", e);
     if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return hip_fail(v, who, "kernel", e);   // (items is reused by the next chunk)
   }
@@ -320,9 +457,17 @@ extern "C" int mhap_correct_finish(mhap_correct_session* s, int32_t min_cov, int
   (void)hipSetDevice(v.device);
   hipError_t e;
   const dim3 grid((unsigned)s->n_reads), block(CK_T);
-  hipLaunchKernelGGL(call_kernel, grid, block, 0, v.stream, s->bases.as<uint8_t>(), s->read_off.as<int64_t>(), s->read_pos.as<int64_t>(),
-                     s->read_len.as<int32_t>(), s->table.as<uint32_t>(), (int)min_cov, (const int64_t*)nullptr, (uint8_t*)nullptr,
-                     s->stats.as<int32_t>());
+  // both launches of the call: the lengths and counts first (out_off == nullptr), then the bytes
+  auto launch_call = [&](const int64_t* out_off, uint8_t* out) {
+    if (s->weighted)
+      hipLaunchKernelGGL(wcall_kernel, grid, block, 0, v.stream, s->bases.as<uint8_t>(), s->in_quals.as<uint8_t>(), s->W, s->read_off.as<int64_t>(),
+                         s->read_pos.as<int64_t>(), s->read_len.as<int32_t>(), s->table.as<uint32_t>(), (int)min_cov, out_off, out,
+                         s->stats.as<int32_t>());
+    else
+      hipLaunchKernelGGL(call_kernel, grid, block, 0, v.stream, s->bases.as<uint8_t>(), s->read_off.as<int64_t>(), s->read_pos.as<int64_t>(),
+                         s->read_len.as<int32_t>(), s->table.as<uint32_t>(), (int)min_cov, out_off, out, s->stats.as<int32_t>());
+  };
+  launch_call(nullptr, nullptr);
   if ((e = hipGetLastError()) != hipSuccess) return hip_fail(v, who, "launch", e);
   if ((e = hipMemcpyAsync(stats, s->stats.p, 24 * (size_t)s->n_reads, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return hip_fail(v, who, "download", e);
   if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return hip_fail(v, who, "kernel", e);
@@ -330,9 +475,7 @@ extern "C" int mhap_correct_finish(mhap_correct_session* s, int32_t min_cov, int
   const int64_t total = out_offsets[s->n_reads];
   if ((e = s->out.ensure((size_t)std::max<int64_t>(total, 1))) != hipSuccess) return hip_fail(v, who, "hipMalloc of the corrected bytes", e);
   if ((e = hipMemcpyAsync(s->out_off.p, out_offsets, 8 * (size_t)(s->n_reads + 1), hipMemcpyHostToDevice, v.stream)) != hipSuccess) return hip_fail(v, who, "upload", e);
-  hipLaunchKernelGGL(call_kernel, grid, block, 0, v.stream, s->bases.as<uint8_t>(), s->read_off.as<int64_t>(), s->read_pos.as<int64_t>(),
-                     s->read_len.as<int32_t>(), s->table.as<uint32_t>(), (int)min_cov, s->out_off.as<int64_t>(), s->out.as<uint8_t>(),
-                     s->stats.as<int32_t>());
+  launch_call(s->out_off.as<int64_t>(), s->out.as<uint8_t>());
   if ((e = hipGetLastError()) != hipSuccess) return hip_fail(v, who, "launch", e);
   if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return hip_fail(v, who, "kernel", e);
   s->out_bytes = total; s->min_cov = min_cov; s->voted_since = false;
@@ -375,9 +518,14 @@ extern "C" int mhap_correct_quality(mhap_correct_session* s, const mhap_quality_
   hipError_t e;
   if ((e = s->quals.ensure((size_t)s->out_bytes)) != hipSuccess || (e = s->hist.ensure(8 * QUAL_BINS)) != hipSuccess) return hip_fail(v, who, "hipMalloc of the quality bytes", e);
   if ((e = hipMemsetAsync(s->hist.p, 0, 8 * QUAL_BINS, v.stream)) != hipSuccess) return hip_fail(v, who, "memset", e);
-  hipLaunchKernelGGL(qcall_kernel, dim3((unsigned)s->n_reads), dim3(CK_T), 0, v.stream, s->bases.as<uint8_t>(), s->read_off.as<int64_t>(),
-                     s->read_pos.as<int64_t>(), s->read_len.as<int32_t>(), s->table.as<uint32_t>(), (int)s->min_cov, (int)p.per_vote, (int)p.cap,
-                     s->out_off.as<int64_t>(), s->quals.as<uint8_t>(), s->hist.as<unsigned long long>());
+  if (s->weighted)
+    hipLaunchKernelGGL(wqcall_kernel, dim3((unsigned)s->n_reads), dim3(CK_T), 0, v.stream, s->bases.as<uint8_t>(), s->in_quals.as<uint8_t>(), s->W,
+                       s->read_off.as<int64_t>(), s->read_pos.as<int64_t>(), s->read_len.as<int32_t>(), s->table.as<uint32_t>(), (int)s->min_cov,
+                       (int)p.per_vote, (int)p.cap, s->out_off.as<int64_t>(), s->quals.as<uint8_t>(), s->hist.as<unsigned long long>());
+  else
+    hipLaunchKernelGGL(qcall_kernel, dim3((unsigned)s->n_reads), dim3(CK_T), 0, v.stream, s->bases.as<uint8_t>(), s->read_off.as<int64_t>(),
+                       s->read_pos.as<int64_t>(), s->read_len.as<int32_t>(), s->table.as<uint32_t>(), (int)s->min_cov, (int)p.per_vote, (int)p.cap,
+                       s->out_off.as<int64_t>(), s->quals.as<uint8_t>(), s->hist.as<unsigned long long>());
   if ((e = hipGetLastError()) != hipSuccess) return hip_fail(v, who, "launch", e);
   if ((e = hipMemcpyAsync(quals, s->quals.p, (size_t)s->out_bytes, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return hip_fail(v, who, "download", e);
   if (hist && (e = hipMemcpyAsync(hist, s->hist.p, 8 * QUAL_BINS, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) return hip_fail(v, who, "download", e);

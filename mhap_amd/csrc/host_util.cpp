@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/mhap_hip.h"
+#include "fastq_host.hpp"
 #include "mhap_internal.hpp"
 
 namespace {
@@ -159,7 +160,10 @@ int mhap_format_paf(const mhap_record* r, const int32_t* d, const uint32_t* ops,
 
 // FastaData.enqueueNextSequenceInFile (J/impl/FastaData.java:125-204).  Deviation (documented in DESIGN.md):
 // an empty record is skipped instead of stopping a worker thread (reference behaviour is thread-count dependent).
-int mhap_fasta_read(const char* path, int64_t id_offset, mhap_fasta* out, char* err, size_t errcap) {
+// A file whose first byte is '@' is FASTQ (fastq_host.hpp): its records give the same arrays as their FASTA twin, and `quals`, when
+// asked for, one Phred byte per base; a FASTA file leaves *quals NULL.
+static int fasta_read(const char* path, int64_t id_offset, mhap_fasta* out, uint8_t** quals, char* err, size_t errcap) {
+  if (quals) *quals = nullptr;
   auto seterr = [&](const std::string& m) { if (err && errcap) snprintf(err, errcap, "%s", m.c_str()); };
   if (!path || !out) { seterr("null argument"); return MHAP_E_INVALID; }
   memset(out, 0, sizeof *out);
@@ -191,7 +195,7 @@ int mhap_fasta_read(const char* path, int64_t id_offset, mhap_fasta* out, char* 
     while ((got = gzread(gf, buf, (unsigned)sizeof buf)) > 0) data.append(buf, (size_t)got);
     gzclose(gf);
   } else {
-    static const char* suffixes[] = {"fna", "contigs", "contig", "final", "fasta", "fa"};   // FastaData.java:50
+    static const char* suffixes[] = {"fna", "contigs", "contig", "final", "fasta", "fa", "fastq", "fq"};   // FastaData.java:50, and FASTQ's
     bool ok = false;
     for (const char* suf : suffixes) ok = ok || ends(suf);
     if (!ok) { seterr(std::string("Unknown file format of file ") + path + "."); return MHAP_E_INVALID; }
@@ -215,9 +219,16 @@ int mhap_fasta_read(const char* path, int64_t id_offset, mhap_fasta* out, char* 
   // lengths and the copy (both parallel over records).
   const size_t N = map_base ? map_len : data.size();
   const char* D = map_base ? (const char*)map_base : data.data();
-  if (N > 0 && D[0] != '>') { seterr("Next sequence does not start with >. Invalid format."); return MHAP_E_INVALID; }   // :150-151
-  std::vector<size_t> hdr;   // offsets of the '>' that open records
-  for (const char* q = D; q && q < D + N;) {
+  const bool fastq = N > 0 && D[0] == '@';
+  if (N > 0 && D[0] != '>' && !fastq) { seterr("Next sequence does not start with >. Invalid format."); return MHAP_E_INVALID; }   // :150-151
+  std::vector<mhap::FastqRec> fq;
+  if (fastq) {
+    std::string e;
+    if (!mhap::fastq_records(D, N, fq, e)) { seterr(e); return MHAP_E_INVALID; }
+  }
+  std::vector<size_t> hdr;   // offsets of the '>' (FASTQ: '@') that open records
+  for (const mhap::FastqRec& r : fq) hdr.push_back((size_t)r.hdr);
+  for (const char* q = D; !fastq && q && q < D + N;) {
     const char* g = (const char*)memchr(q, '>', (size_t)(D + N - q));
     if (!g) break;
     if (g == D || g[-1] == '\n' || g[-1] == '\r') hdr.push_back((size_t)(g - D));
@@ -241,7 +252,7 @@ int mhap_fasta_read(const char* path, int64_t id_offset, mhap_fasta* out, char* 
   };
   par([&](int64_t lo, int64_t hi) {
     for (int64_t r = lo; r < hi; r++) {
-      const size_t end = (r + 1 < nrec) ? hdr[(size_t)r + 1] : N;
+      const size_t end = fastq ? (size_t)fq[(size_t)r].seq_end : (r + 1 < nrec) ? hdr[(size_t)r + 1] : N;
       size_t p = hdr[(size_t)r];
       while (p < end && D[p] != '\n' && D[p] != '\r') p++;   // header line
       body[(size_t)r] = p; bend[(size_t)r] = end;
@@ -291,8 +302,27 @@ int mhap_fasta_read(const char* path, int64_t id_offset, mhap_fasta* out, char* 
     }
   });
   if (!offs.empty()) { memcpy(out->offsets, offs.data(), offs.size() * 8); memcpy(out->lengths, lens.data(), lens.size() * 4); memcpy(out->ids, ids.data(), ids.size() * 8); }
+  if (fastq && quals) {
+    uint8_t* Q = (uint8_t*)malloc(std::max<size_t>((size_t)total, 1));
+    if (!Q) { mhap_fasta_free(out); seterr("out of memory"); return MHAP_E_NOMEM; }
+    par([&](int64_t lo, int64_t hi) {
+      for (int64_t r = lo; r < hi; r++) mhap::fastq_copy_qualities(D, fq[(size_t)r], Q + dst[(size_t)r]);
+    });
+    *quals = Q;
+  }
   return MHAP_OK;
 }
+
+int mhap_fasta_read(const char* path, int64_t id_offset, mhap_fasta* out, char* err, size_t errcap) {
+  return fasta_read(path, id_offset, out, nullptr, err, errcap);
+}
+
+int mhap_fasta_read_qualities(const char* path, int64_t id_offset, mhap_fasta* out, uint8_t** qualities, char* err, size_t errcap) {
+  if (!qualities) { if (err && errcap) snprintf(err, errcap, "null argument"); return MHAP_E_INVALID; }
+  return fasta_read(path, id_offset, out, qualities, err, errcap);
+}
+
+void mhap_qualities_free(uint8_t* qualities) { free(qualities); }
 
 void mhap_fasta_free(mhap_fasta* f) {
   if (!f) return;

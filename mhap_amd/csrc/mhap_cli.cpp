@@ -50,6 +50,7 @@ struct Options {
       if (n == "--hpc" && !b("--hpc")) continue;
       if ((n == "--correct-fastq" || n == "--gfa-consensus-fastq") && !isset(n)) continue;   // (and the quality flags only with a FASTQ file to write)
       if (n.compare(0, 9, "--quality") == 0 && !isset("--correct-fastq") && !isset("--gfa-consensus-fastq")) continue;
+      if (n.compare(0, 7, "--weigh") == 0 && !b("--weigh-qualities")) continue;
       t += n + " = " + m.at(n).value + "\n";
     }
     return t;
@@ -319,6 +320,9 @@ void declare_options(Options& o) {
   o.add("--correct-min-coverage", "[int] With --correct, the votes a read position needs before it is changed.", "4");
   o.add("--correct-fastq", "With --correct, also write the corrected reads to this FASTQ file, with one quality per base from the votes that decided it (Phred+33).", "");
   o.add("--quality-per-vote", "[int] With --correct-fastq or --gfa-consensus-fastq, tenths of a Phred unit per net vote, 1 to 1000.", "15");
+  o.add("--weigh-qualities", "With --correct or --gfa-consensus on FASTQ reads: every vote weighs the base quality of the read it comes from, 1 below --weight-q-lo, 2 up to --weight-q-hi, 3 from there on.", "false", true);
+  o.add("--weight-q-lo", "[int] With --weigh-qualities, the Phred value below which a base votes with weight 1, 0 to 93.", "7");
+  o.add("--weight-q-hi", "[int] With --weigh-qualities, the Phred value from which a base votes with weight 3, --weight-q-lo to 93.", "20");
   o.add("--quality-cap", "[int] With --correct-fastq or --gfa-consensus-fastq, the highest quality written, 1 to 93.", "60");
   o.add("--gfa", "With --realign: build the string graph of the realigned overlaps on the GPU (dovetails, contained reads set aside, transitive arcs reduced) and write it to this file as GFA 1: an S line per read that is not contained, an L line per final arc. Self overlaps only (no -q), one GPU.", "");
   o.add("--gfa-unitigs", "With --gfa: compact the final arcs of the string graph into unitigs on the GPU and write them to this second file as GFA 1: an S line with the sequence per unitig, spelled from the reads as stored, an a line per read of it, an L line per arc between unitigs.", "");
@@ -429,6 +433,10 @@ std::vector<int32_t> check_options(Options& o) {
   owned(o, {"--quality-per-vote", "--quality-cap"}, o.isset("--correct-fastq") || o.isset("--gfa-consensus-fastq"), " belongs to --correct-fastq or --gfa-consensus-fastq: give one of them too.");
   if (o.i("--quality-per-vote") < 1 || o.i("--quality-per-vote") > 1000 || o.i("--quality-cap") < 1 || o.i("--quality-cap") > 93)
     bad("The value of --quality-per-vote must be 1 to 1000 and that of --quality-cap 1 to 93.");
+  owned(o, {"--weigh-qualities"}, o.isset("--correct") || o.b("--gfa-consensus"), " weighs the votes of --correct or --gfa-consensus: give one of them too.");
+  owned(o, {"--weight-q-lo", "--weight-q-hi"}, o.b("--weigh-qualities"), " belongs to --weigh-qualities: give --weigh-qualities too.");
+  if (o.i("--weight-q-lo") < 0 || o.i("--weight-q-lo") > o.i("--weight-q-hi") || o.i("--weight-q-hi") > 93)
+    bad("The values of --weight-q-lo and --weight-q-hi must be 0 <= --weight-q-lo <= --weight-q-hi <= 93.");
   if (gfa) {
     stage_flag(o, n_devs, "--gfa", "builds the graph from", "lays out", realigned);
     if (o.s("--gfa").empty()) bad("--gfa needs the name of the GFA file to write.");
@@ -513,13 +521,11 @@ void precompute_dat(const Engine& E, const Options& o, const mhap_params& P) {
 
 // --realign: the reads of -s (ids as the index assigned them: FastaData's running count), every stage's parameters from its flags, and the sessions that begin before the search
 void begin_pipeline(const Options& o, mhap_handle* h, Pipeline& p) {
-  char err[512] = {0};
-  for (const std::string& sf : p.reads.n() > 0 ? std::vector<std::string>() : list_files(o.s("-s"))) {   // (--hpc has read them already)
-    mhap_fasta fa;
-    if (mhap_fasta_read(sf.c_str(), p.reads.n(), &fa, err, sizeof err) != MHAP_OK) die(err);
-    p.reads.add(fa);
-    mhap_fasta_free(&fa);
-  }
+  const bool weigh = o.b("--weigh-qualities");
+  for (const std::string& sf : p.reads.n() > 0 ? std::vector<std::string>() : list_files(o.s("-s"))) p.reads.read_file(sf, weigh);   // (--hpc has read them already)
+  p.correct.weigh = p.graph.weigh = weigh;
+  p.correct.wp = p.graph.wp = mhap_weight_params{o.i("--weight-q-lo"), o.i("--weight-q-hi")};
+  if (weigh) p.reads.weight_line(p.correct.wp);
   p.realign.h = p.select.h = p.correct.h = p.repeat.h = p.trim.h = p.graph.h = h;
   p.realign.reads = &p.reads; p.realign.band = o.i("--realign-band"); p.realign.min_identity = o.d("--realign-min-identity");
   p.paf = o.b("--realign-paf");
@@ -546,15 +552,9 @@ void begin_pipeline(const Options& o, mhap_handle* h, Pipeline& p) {
 // --hpc: the files of -s read whole into the table of reads (ids as the index assigns them), compressed on the GPU, and the compressed
 // reads sketched and indexed under those ids; the reads the index took, as add_file_to_index counts them
 int64_t add_compressed_to_index(const Engine& E, const Options& o, HpcStage& hpc, int64_t* strands) {
-  char err[512] = {0};
   Reads& R = *hpc.reads;
-  for (const std::string& sf : list_files(o.s("-s"))) {
-    mhap_fasta fa;
-    if (mhap_fasta_read(sf.c_str(), R.n(), &fa, err, sizeof err) != MHAP_OK) die(err);
-    if (g_headers.full) collect_headers(fa);
-    R.add(fa);
-    mhap_fasta_free(&fa);
-  }
+  for (const std::string& sf : list_files(o.s("-s")))
+    R.read_file(sf, o.b("--weigh-qualities"), [](const mhap_fasta& fa) { if (g_headers.full) collect_headers(fa); });
   hpc.compress(0, hpc.index);
   const HpcSide& s = hpc.index;
   if (s.n > 0) chk(E.h, mhap_index_add_reads(E.h, (const char*)s.bases.data(), s.offsets.data(), s.lengths.data(), hpc.ids(s), s.n));

@@ -28,6 +28,7 @@
 #include <thread>
 #include <vector>
 
+#include "fastq_host.hpp"
 #include "kernels.hpp"
 #include "mhap_internal.hpp"
 
@@ -40,6 +41,8 @@ struct FastaScanImpl {
   std::string owned;                          // inflated gz / bz2 input, pipes
   // per non-empty record
   std::vector<uint64_t> hdr, body, end;       // offsets of '>', of the first byte after the header line, of the record's end
+  bool fastq = false;                         // the text is FASTQ: hdr is the '@', end the '+' line, and the qualities lie in [qual, qual_end)
+  std::vector<uint64_t> qual, qual_end;
   std::vector<int32_t> len;                   // bases
   std::vector<uint8_t> raw;                   // 1: has a char other than ACGT/acgt (kept as upper-cased bytes on the device)
   std::vector<uint8_t> oneline;               // 1: the sequence is one line (packed straight from the text)
@@ -279,7 +282,7 @@ int mhap_fasta_scan_open(const char* path, int64_t id_offset, mhap_fasta_scan** 
     if (!inflate_file(name, sc.owned, e)) { seterr(e); delete S; return MHAP_E_INVALID; }
     sc.D = sc.owned.data(); sc.N = sc.owned.size();
   } else {
-    static const char* suffixes[] = {"fna", "contigs", "contig", "final", "fasta", "fa"};   // FastaData.java:50
+    static const char* suffixes[] = {"fna", "contigs", "contig", "final", "fasta", "fa", "fastq", "fq"};   // FastaData.java:50, and FASTQ's
     bool ok = false;
     for (const char* suf : suffixes) ok = ok || ends(suf);
     if (!ok) { seterr(std::string("Unknown file format of file ") + path + "."); delete S; return MHAP_E_INVALID; }
@@ -298,11 +301,19 @@ int mhap_fasta_scan_open(const char* path, int64_t id_offset, mhap_fasta_scan** 
     close(fd);
   }
   const char* D = sc.D; const size_t N = sc.N;
-  if (N > 0 && D[0] != '>') { seterr("Next sequence does not start with >. Invalid format."); delete S; return MHAP_E_INVALID; }   // FastaData.java:150-151
+  // a first byte '@': FASTQ.  Its records come from fastq_host.hpp's sequential pass over the lines (the same on any number of host
+  // threads); pass 2 below then reads a record's sequence lines, which end at its '+' line, as it reads a FASTA record's
+  sc.fastq = N > 0 && D[0] == '@';
+  std::vector<FastqRec> fq;
+  if (sc.fastq) {
+    std::string e;
+    if (!fastq_records(D, N, fq, e)) { seterr(e); delete S; return MHAP_E_INVALID; }
+  }
+  if (N > 0 && D[0] != '>' && !sc.fastq) { seterr("Next sequence does not start with >. Invalid format."); delete S; return MHAP_E_INVALID; }   // FastaData.java:150-151
   // pass 1 (parallel over the text): the '>' that open records (BufferedReader.readLine: a line ends at \n, \r or \r\n)
   const int nthreads = (int)std::max<int64_t>(1, std::min<int64_t>(host_threads(), (int64_t)(N >> 22) + 1));   // >= 4 MB of text per thread
   std::vector<std::vector<uint64_t>> found((size_t)nthreads);
-  parallel_chunks((int64_t)N, nthreads, [&](int64_t lo, int64_t hi, int t) {
+  parallel_chunks(sc.fastq ? 0 : (int64_t)N, nthreads, [&](int64_t lo, int64_t hi, int t) {
     std::vector<uint64_t>& v = found[(size_t)t];
     for (const char* q = D + lo; q < D + hi;) {
       const char* g = (const char*)memchr(q, '>', (size_t)(D + hi - q));
@@ -313,6 +324,7 @@ int mhap_fasta_scan_open(const char* path, int64_t id_offset, mhap_fasta_scan** 
   });
   std::vector<uint64_t> hdr;
   for (auto& v : found) hdr.insert(hdr.end(), v.begin(), v.end());
+  for (const FastqRec& r : fq) hdr.push_back(r.hdr);
   const int64_t nrec = (int64_t)hdr.size();
   // pass 2 (parallel over records): header line, bases, is-it-ACGT, is-it-one-line
   std::vector<uint64_t> body((size_t)nrec), rend((size_t)nrec);
@@ -320,7 +332,7 @@ int mhap_fasta_scan_open(const char* path, int64_t id_offset, mhap_fasta_scan** 
   std::vector<uint8_t> rraw((size_t)nrec), rone((size_t)nrec);
   parallel_chunks(nrec, host_threads(), [&](int64_t lo, int64_t hi, int) {
     for (int64_t r = lo; r < hi; r++) {
-      const size_t e = (r + 1 < nrec) ? (size_t)hdr[(size_t)r + 1] : N;
+      const size_t e = sc.fastq ? (size_t)fq[(size_t)r].seq_end : (r + 1 < nrec) ? (size_t)hdr[(size_t)r + 1] : N;
       size_t p = (size_t)hdr[(size_t)r];
       const char* nl = (const char*)memchr(D + p, '\n', e - p);
       const char* cr = (const char*)memchr(D + p, '\r', nl ? (size_t)(nl - (D + p)) : e - p);
@@ -352,6 +364,7 @@ int mhap_fasta_scan_open(const char* path, int64_t id_offset, mhap_fasta_scan** 
     sc.len.push_back((int32_t)rlen[(size_t)r]); sc.raw.push_back(rraw[(size_t)r]); sc.oneline.push_back(rone[(size_t)r]);
     sc.ids.push_back(count + id_offset);
     sc.total_bases += rlen[(size_t)r];
+    if (sc.fastq) { sc.qual.push_back(fq[(size_t)r].qual); sc.qual_end.push_back(fq[(size_t)r].qual_end); }
   }
   if (prof()) fprintf(stderr, "[ingest] scan of %s: %lld reads, %.1f Mbase, %.3f s on %d threads\n", path, (long long)count, sc.total_bases / 1e6, now_s() - t0, host_threads());
   *out = S;
@@ -361,6 +374,23 @@ int mhap_fasta_scan_open(const char* path, int64_t id_offset, mhap_fasta_scan** 
 void mhap_fasta_scan_free(mhap_fasta_scan* s) { delete s; }
 int64_t mhap_fasta_scan_reads(const mhap_fasta_scan* s) { return s ? (int64_t)s->impl.len.size() : 0; }
 int64_t mhap_fasta_scan_bases(const mhap_fasta_scan* s) { return s ? s->impl.total_bases : 0; }
+
+int mhap_fasta_scan_has_qualities(const mhap_fasta_scan* s) { return s && s->impl.fastq ? 1 : 0; }
+
+int mhap_fasta_scan_qualities(const mhap_fasta_scan* s, uint8_t* qualities) {
+  if (!s || !s->impl.fastq || (!qualities && s->impl.total_bases > 0)) return MHAP_E_INVALID;
+  const FastaScanImpl& sc = s->impl;
+  std::vector<int64_t> at(sc.len.size() + 1, 0);
+  for (size_t r = 0; r < sc.len.size(); r++) at[r + 1] = at[r] + sc.len[r];
+  parallel_chunks((int64_t)sc.len.size(), host_threads(), [&](int64_t lo, int64_t hi, int) {
+    for (int64_t r = lo; r < hi; r++) {
+      FastqRec rec{};
+      rec.qual = sc.qual[(size_t)r]; rec.qual_end = sc.qual_end[(size_t)r]; rec.len = sc.len[(size_t)r];
+      fastq_copy_qualities(sc.D, rec, qualities + at[(size_t)r]);
+    }
+  });
+  return MHAP_OK;
+}
 
 int mhap_fasta_scan_info(mhap_fasta_scan* s, int64_t* ids, int32_t* lengths, const char** headers, int64_t* headers_bytes) {
   if (!s) return MHAP_E_INVALID;

@@ -43,3 +43,26 @@ def parameters(a, owner_given, owner):
     if not 1 <= cap <= PHRED_MAX:
         return None, "--quality-cap must be 1 .. 93"
     return dict(per_vote=per_vote, cap=cap), None
+
+
+def add_weight_arguments(ap):
+    """--weigh-qualities, --weight-q-lo and --weight-q-hi, which both tools take for their votes ("quality-weighted votes" of
+    include/mhap_hip.h)."""
+    ap.add_argument("--weigh-qualities", action="store_true", help="every vote weighs the base quality of the FASTQ read it comes from")
+    ap.add_argument("--weight-q-lo", type=int, default=None, metavar="Q", help="with --weigh-qualities, a base below this Phred value votes with weight 1 (7)")
+    ap.add_argument("--weight-q-hi", type=int, default=None, metavar="Q", help="with --weigh-qualities, a base from this Phred value on votes with weight 3 (20)")
+
+
+def weight_parameters(a, stage_given, stage):
+    """((q_lo, q_hi) or None without --weigh-qualities, None) from the parsed arguments, or (None, the error message).  A threshold
+    that was not given is None: the library's default."""
+    if (a.weight_q_lo is not None or a.weight_q_hi is not None) and not a.weigh_qualities:
+        return None, "--weight-q-lo and --weight-q-hi need --weigh-qualities"
+    if not a.weigh_qualities:
+        return None, None
+    if not stage_given:
+        return None, f"--weigh-qualities needs {stage}"
+    lo, hi = 7 if a.weight_q_lo is None else a.weight_q_lo, 20 if a.weight_q_hi is None else a.weight_q_hi
+    if not 0 <= lo <= hi <= PHRED_MAX:
+        return None, "--weight-q-lo and --weight-q-hi must be 0 <= --weight-q-lo <= --weight-q-hi <= 93"
+    return (lo, hi), None

@@ -17,7 +17,9 @@ section); the -o file is then the cleaned read graph and the --unitigs file the 
 With --consensus (which needs --unitigs) every read is placed on a unitig, aligned to it and votes, and the --unitigs file carries the
 consensus sequences, their lengths and `a` offsets mapped into them ("unitig consensus" in the same header); --consensus-fasta also
 writes them as FASTA, and --consensus-fastq as FASTQ with one quality per base from the votes that decided it ("base qualities" in
-the same header; Phred+33), with one more stderr line that counts them.
+the same header; Phred+33), with one more stderr line that counts them.  With --weigh-qualities [--weight-q-lo Q] [--weight-q-hi Q], on
+FASTQ reads, every vote of the consensus weighs the base quality of the read it comes from ("quality-weighted votes" in the same
+header; with --trim the trimmed reads' qualities are the matching slices), and one more stderr line counts the bases per weight class.
 With --trim [--trim-min-cov N] [--trim-end-clip N] [--trim-min-span N] [--trim-penalty N] the reads are trimmed and chimeras split on the GPU first
 ("read trimming" in the same header; `python -m mhap_amd.trim` writes the trimmed reads themselves): every output is then built on
 the surviving reads, their trimmed lengths and the overlaps rewritten onto them.
@@ -54,7 +56,7 @@ def consensus_fasta(seqs, circular):
 
 
 def graph_overlaps(recs, fasta, band=0, max_shift=0.2, min_identity=0.0, device=0, batch=BATCH, unitigs=False, clean=None, consensus=None,
-                   trim=None, repeat=None, quality=None, **params):
+                   trim=None, repeat=None, quality=None, weights=None, **params):
     """Realign `recs` in batches and build the graph: (gfa text, arcs, counts, contained); with unitigs=True two more: the GFA text
     of the unitig graph and the dict of GraphSession.unitigs().  clean: None, or a dict of GraphSession.clean's parameters: the graph
     is cleaned first, both texts and the dict are those of the cleaned graph, and the dict of CLEAN_COUNTS comes last.
@@ -67,7 +69,9 @@ def graph_overlaps(recs, fasta, band=0, max_shift=0.2, min_identity=0.0, device=
     them; the dict of TRIM_COUNTS then comes last of all (key trim_counts of the dict).
     repeat: None, or a dict of RepeatSession's parameters and `penalty`: every kept record is judged on its refined copy ("repeat
     marking" in the same header) and the void ones reach neither the trimming nor the graph; without trim the graph takes the
-    survivors as realigned.  The dict of REPEAT_COUNTS then comes behind the trimming's (key repeat_counts of the dict)."""
+    survivors as realigned.  The dict of REPEAT_COUNTS then comes behind the trimming's (key repeat_counts of the dict).
+    weights: None, or with consensus (q_lo, q_hi): the consensus votes weigh the reads' own qualities (FASTQ reads; with trim, the
+    trimmed reads' are the matching slices), "quality-weighted votes" in the same header."""
     with api.MinHashSearch(api.MhapParams(num_hashes=1, ordered_sketch_size=1, max_shift=max_shift, device=device)) as ms:
         tcounts = ()
         if repeat is not None:
@@ -101,7 +105,8 @@ def graph_overlaps(recs, fasta, band=0, max_shift=0.2, min_identity=0.0, device=
                     raise api.MhapError("graph_overlaps: consensus needs unitigs=True")
                 if clean is None:
                     gs.unitigs()
-                with api.ConsensusSession(gs, fasta, **consensus) as cs:
+                wkw = {} if weights is None else dict(qualities=api.all_qualities(fasta), weights=api.WeightParams(*weights))
+                with api.ConsensusSession(gs, fasta, **consensus, **wkw) as cs:
                     for out in kept:
                         cs.add(out)
                     ccounts = cs.run()
@@ -144,9 +149,16 @@ def main(argv=None):
     ap.add_argument("--repeat-filter", action="store_true", help="mark repeats from the overlap pile-up first and drop the overlaps that lie in nothing but repeat")
     ap.add_argument("--consensus-fastq", default=None, help="with --consensus, also write the consensus sequences with base qualities to this FASTQ file")
     fastq.add_arguments(ap)
+    fastq.add_weight_arguments(ap)
     repeats.add_arguments(ap, "repeat-")
     a = ap.parse_args(argv)
     quality, message = fastq.parameters(a, a.consensus_fastq is not None, "--consensus-fastq")
+    if message:
+        ap.error(message)
+    if a.weigh_qualities and not a.consensus:
+        print("--weigh-qualities weighs the votes of --consensus: give --consensus too.")
+        return 1
+    weights, message = fastq.weight_parameters(a, True, "--consensus")
     if message:
         ap.error(message)
     rp, message = repeats.parameters(a, "repeat-")
@@ -174,12 +186,17 @@ def main(argv=None):
         ap.error("--max-hang, --min-overlap and --fuzz must be >= 0 and --int-frac in [0, 1]")
     recs = read_overlaps(a.overlaps)
     fasta = api.FastaData.from_file(a.reads)
+    if weights is not None:
+        if fasta.qualities is None:
+            print(f"--weigh-qualities needs the base qualities of FASTQ reads: {a.reads} is FASTA.")
+            return 1
+        print(api.weight_classes_line(fasta.bases, fasta.qualities, api.WeightParams(*weights)), file=sys.stderr)
     res = graph_overlaps(recs, fasta, band=a.band, max_shift=a.max_shift, min_identity=a.min_identity, device=a.device, unitigs=bool(a.unitigs),
                          clean=dict(tip_reads=a.tip_reads, bubble_bases=a.bubble_bases, max_rounds=a.clean_rounds) if a.clean else None,
                          consensus=dict(min_cov=a.consensus_min_cov) if a.consensus else None,
                          trim=dict(min_cov=a.trim_min_cov, end_clip=a.trim_end_clip, min_span=a.trim_min_span, penalty=a.trim_penalty) if a.trim else None,
                          repeat=dict(rp, penalty=a.trim_penalty) if a.repeat_filter else None,
-                         quality=quality if a.consensus_fastq else None,
+                         quality=quality if a.consensus_fastq else None, weights=weights,
                          max_hang=a.max_hang, int_frac_permille=int(round(a.int_frac * 1000)), min_ovlp=a.min_overlap, fuzz=a.fuzz)
     tcounts = rcounts = None
     if a.repeat_filter:

@@ -10,6 +10,8 @@ gets the kept records and runs --repeats times; its four stage times are mhap_co
 behind a wait for the stream).  The correction session gets the same records with their runs: add is its vote, finish its call.
 After each, the quality pass (ConsensusSession.quality, CorrectSession.quality: the kernel, the download of one byte per output
 byte and of the histogram) is timed on its own, to be read next to `call` and `finish`.
+--weigh makes both sessions weighted ones ("quality-weighted votes" in include/mhap_hip.h) over one Phred value drawn per base from
+5, 14 and 30, with the default thresholds: the same records, the weighted vote, call and quality kernels.
 The first repeat is the warm-up.  A run without a GPU fails: there is no fallback."""
 import argparse
 import os
@@ -24,10 +26,11 @@ from mhap_amd import api  # noqa: E402
 from mhap_amd.realign import kept_rows  # noqa: E402
 
 
-def run(G, n, seed, repeats):
+def run(G, n, seed, repeats, weigh=False):
     rng = np.random.default_rng(seed)
     codes = rng.integers(0, 4, G).astype(np.uint8)
     fa = mhap_amd.synth_reads_from_genome(codes, rng.integers(2500, 3501, n).astype(np.int32), seed=9, error_rate=0.10)
+    wkw = dict(qualities=np.random.default_rng(seed + 1).choice([5, 14, 30], len(fa.bases)).astype(np.uint8)) if weigh else {}
     with mhap_amd.MinHashSearch(mhap_amd.MhapParams()) as ms:
         ms.add_data(fa)
         out, _, op_off, ops = api.realign_records_paths(ms.find_matches(), fa, handle=ms)
@@ -40,7 +43,7 @@ def run(G, n, seed, repeats):
                 gs.add(kept)
                 gs.finish()
                 u = gs.unitigs()
-                with api.ConsensusSession(gs, fa) as cs:
+                with api.ConsensusSession(gs, fa, **wkw) as cs:
                     cs.add(kept)
                     t0 = time.time()
                     counts = cs.run()
@@ -49,7 +52,7 @@ def run(G, n, seed, repeats):
                     t0 = time.time()
                     cs.quality()
                     t_cq = time.time() - t0
-            with api.CorrectSession(fa, handle=ms) as cr:
+            with api.CorrectSession(fa, handle=ms, **wkw) as cr:
                 t0 = time.time()
                 cr.add(kept, k_off, k_ops)
                 t_add = time.time() - t0
@@ -59,7 +62,7 @@ def run(G, n, seed, repeats):
                 t0 = time.time()
                 cr.quality()
                 t_rq = time.time() - t0
-            print(f"{G} bases, {len(fa)} reads ({int(fa.lengths.sum())} bases), {len(kept)} records, {u['counts']['unitigs']} unitigs of {u['counts']['total_bases']} bases, "
+            print(f"{'weighted, ' if weigh else ''}{G} bases, {len(fa)} reads ({int(fa.lengths.sum())} bases), {len(kept)} records, {u['counts']['unitigs']} unitigs of {u['counts']['total_bases']} bases, "
                   f"repeat {rep}: consensus run {wall * 1e3:.1f} ms = placement {t['placement'] * 1e3:.1f} + alignment {t['alignment'] * 1e3:.1f} + vote "
                   f"{t['vote'] * 1e3:.1f} + call {t['call'] * 1e3:.1f}; correction of the same records: add {t_add * 1e3:.1f} ms, finish {t_fin * 1e3:.1f} ms; "
                   f"quality pass: consensus {t_cq * 1e3:.1f} ms, correction {t_rq * 1e3:.1f} ms", flush=True)
@@ -70,10 +73,11 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--sets", default="20000:170,400000:3400", help="genome bases:reads, comma-separated")
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--weigh", action="store_true", help="weighted sessions over drawn base qualities")
     a = ap.parse_args()
     for k, item in enumerate(a.sets.split(",")):
         G, n = (int(x) for x in item.split(":"))
-        run(G, n, 41 + 2 * k, a.repeats)
+        run(G, n, 41 + 2 * k, a.repeats, a.weigh)
 
 
 if __name__ == "__main__":
