@@ -88,6 +88,9 @@ VARIANTS = {
     # ordered_kernel records which of its selection paths made every strand's row and launch_ordered prints the codes, one
     # `[ordered paths]` line per launch (tests/test_ordered_paths_gpu.py compares them with tests/ordered_paths_ref.py)
     "ordpaths": (["-DMH_ORD_PATHS"], ["sketch_kernels.hip"]),
+    # the weight-1 MinHash kernel with every seventh slot in depth class 0 (w1_class_of): every later row then runs the exact filter
+    # of class 0 (rare otherwise: a slot without a usable minimum) between steps of the class chain (tests/test_minhash_w1_masks_gpu.py)
+    "w1cls0": (["-DMH_W1_CLS0_TEST"], ["sketch_kernels.hip"]),
 }
 
 

@@ -1259,8 +1259,13 @@ __device__ __forceinline__ void perchain_row(int64_t* best, int32_t* bpos, const
 constexpr int W1_CLS_BASE = 8;            // class c >= 1 filters down to depth W1_CLS_BASE + c - 1; class 0 = the exact masked filter
 constexpr int W1_CLS_MAX = 6;             // depth 13: 2048 x 2^-14 = one false candidate per eight steps at worst
 
-// class of a slot from the high dword of its minimum
-__device__ __forceinline__ int w1_class_of(int32_t bhs) {
+// class of a slot from the high dword of its minimum.  (MH_W1_CLS0_TEST, a variant build for tests: every seventh slot is class 0 whatever its
+// minimum — the exact filter of the slot's depth is a superset of its class's, so the rows stay the same, and every later row then runs the
+// exact filter between steps of the class chain.)
+__device__ __forceinline__ int w1_class_of(int32_t bhs, int slot) {
+#ifdef MH_W1_CLS0_TEST
+  if (slot % 7 == 0) return 0;
+#endif
   const int z = bs_depth(bhs);
   if (z < W1_CLS_BASE) return 0;
   const int c = z - W1_CLS_BASE + 1;
@@ -1579,7 +1584,8 @@ __device__ __forceinline__ uint64_t w1_key_of(uint64_t x, int n, const uint64_t*
 // per-bit loop) plus up to eight scalar-operand v_bitop3 of the second look — on two steps in three.  This version:
 //   * the slot's filter depth selects CODE, not operands: the planes 1..8 are OR-ed unconditionally (four three-VGPR ops; inactive
 //     chains carry key 0 = chain value 0 for ever = never negative, so no mask of active chains is needed), and a scalar switch on the
-//     slot's depth class (one v_readlane per step) adds the planes 9..13 its depth allows with one to three more VGPR-only ops;
+//     slot's depth class (one v_readlane per step; since MH_W1_CLS 4 a bit test of the class block's scalar masks: W1Cls) adds the planes
+//     9..13 its depth allows with one to three more VGPR-only ops;
 //     a slot without a usable minimum (fewer than eight leading zero bits) takes the exact masked filter — rare;
 //   * an append writes ONE 8-byte entry per lane that has candidates — its whole 32-chain candidate mask + (slot, lane) —
 //     at the position the append's own ballot gives it (two v_mbcnt on the scalar fill count); no per-bit loop, no v_ffbl, no
@@ -1691,7 +1697,7 @@ __device__ __forceinline__ bool w1_flush2(int64_t* best, uint2* __restrict__ q, 
 }
 
 #ifndef MH_W1_CLS
-#define MH_W1_CLS 2     // how a step selects its class's filter code: 0 = `switch`, 1 = if-chain in C, 2 = the whole chain in assembly, 3 = classes 3..6 in assembly behind one C branch (fewer scalar instructions than 2 but more TAKEN branches: 1 ms slower)
+#define MH_W1_CLS 4     // how a step selects its class's filter code: 0 = `switch`, 1 = if-chain in C, 2 = the whole chain in assembly, 3 = classes 3..6 in assembly behind one C branch (fewer scalar instructions than 2 but more TAKEN branches: 1 ms slower), 4 = the chain in assembly on the class block's scalar masks, no v_readlane (W1Cls)
 #endif
 // a slot without a usable minimum (fewer than eight leading zero bits, or none at all: every active chain is a candidate): the exact masked
 // filter of its depth.  left = k-mers of the strand from this row's first on (chains j with 64 j + lane < left are active)
@@ -1706,6 +1712,162 @@ __device__ __forceinline__ uint32_t w1_exact_filter(const uint32_t (&P)[64], int
 #pragma unroll
   for (int b = 1; b < W1_CLS_BASE; b++) n = __builtin_amdgcn_bitop3_b32(P[63 - b], bs_sbit(sm, b), n, BS_TT_ANDOR);
   return n;
+}
+
+// The classes of one 64-slot class block.  MH_W1_CLS 4: as wave-uniform 64-bit masks, bit t = slot s0 + t — the thermometer cls >= 2 .. cls >= 6
+// and cls == 0, six v_cmp once per block; a step's class chain tests the slot's bit (s_bitcmp1_b64 takes the slot number itself: it reads the
+// low six bits of its index) where it compared a class fetched with one v_readlane per step, and no per-lane class is alive in the step loop.
+// The other MH_W1_CLS values keep the per-lane classes (vcls) and the v_readlane.  A later-row step of class 6 is then 100 VALU and 9 scalar
+// or branch instructions (two tests and two branches of the chain, the class-0 compare and branch, the loop's add / compare / branch) where
+// MH_W1_CLS 2 has 100 VALU, the v_readlane and 13 (three compares and branches + the trailing s_branch, the class-0 test, the address add of
+// the slot's minimum, the loop's three): 0.7 to 0.9 ms of the kernel's 72 to 74 at C2 on two boxes (profiles/w1_masks_ab.txt; EXPERIMENTS, "Weight-1 MinHash: scalar
+// class masks").  128 VGPRs, four waves per SIMD, no scratch access in either step loop, as before.
+struct W1Cls { int vcls; unsigned long long m0, m2, m3, m4, m5, m6; };
+// the later-row steps of one class block [s0, send)
+__device__ __forceinline__ void w1_class_block(uint32_t (&P)[64], const W1Cls& c, const int32_t* besthi, int s0, int send, int left_row,
+                                               uint2* __restrict__ q, int& qn, int wcap) {
+#if MH_W1_CLS == 4
+  // class 0 (the exact filter) by the NUMBER of the block's next class-0 slot, -1 when there is none: one scalar compare and an untaken
+  // branch per step — a bit test of the class-0 mask is a 64-bit shift, an and and a compare before the branch
+  unsigned long long m0 = c.m0;
+  int z0 = m0 ? s0 + (int)__builtin_ctzll(m0) : -1;
+#endif
+  for (int sb = s0; sb < send; sb += W1_DEFER) {
+    int se = sb + W1_DEFER;
+    if (se > send) se = send;
+    se = __builtin_amdgcn_readfirstlane(se);
+    uint32_t nacc = 0xFFFFFFFFu;   // AND of the sub-block's filter words: a zero bit = the chain passed a slot's filter
+    for (int sl = sb; sl < se; sl++) {
+#if MH_W1_CLS < 4
+      const int cls = __builtin_amdgcn_readlane(c.vcls, sl - s0);
+#endif
+      bs_step(P);
+      uint32_t n = w1_base_filter(P);
+#if MH_W1_CLS == 0
+      switch (cls) {
+        case 1: break;
+        case 2: n |= P[54]; break;
+        case 3: n = __builtin_amdgcn_bitop3_b32(n, P[54], P[53], BS_TT_OR3); break;
+        case 4: n = __builtin_amdgcn_bitop3_b32(n, P[54], P[53], BS_TT_OR3) | P[52]; break;
+        case 5: n = __builtin_amdgcn_bitop3_b32(__builtin_amdgcn_bitop3_b32(n, P[54], P[53], BS_TT_OR3), P[52], P[51], BS_TT_OR3); break;
+        case 6: n = __builtin_amdgcn_bitop3_b32(__builtin_amdgcn_bitop3_b32(n, P[54], P[53], BS_TT_OR3), P[52], P[51], BS_TT_OR3) | P[50]; break;
+        default: n = w1_exact_filter(P, besthi[2 * sl + 1], left_row); break;
+      }
+#elif MH_W1_CLS == 1
+      if (__builtin_expect(cls >= 3, 1)) {
+        n = __builtin_amdgcn_bitop3_b32(n, P[54], P[53], BS_TT_OR3);
+        if (cls >= 5) {
+          n = __builtin_amdgcn_bitop3_b32(n, P[52], P[51], BS_TT_OR3);
+          if (cls >= 6) n |= P[50];
+        } else if (cls == 4) n |= P[52];
+      } else if (cls == 2) n |= P[54];
+      else if (__builtin_expect(cls == 0, 0)) n = w1_exact_filter(P, besthi[2 * sl + 1], left_row);   // no usable minimum yet: the exact filter of the slot's depth
+#elif MH_W1_CLS == 2
+      // The class selects code through a short chain of scalar compares, deepest classes first (the common ones from the third row on),
+      // written out in assembly: the compiler lowers the equivalent `switch` / if-chain through its control-flow structurizer — a compare
+      // tree with "which way did I come" flags in SGPR pairs, 11 to 16 scalar instructions a step (and selects in place of the
+      // innermost branches); this is 6 or 7.  (One asm statement, branches local to it; classes 1..6 add the planes 9..13.)
+      asm volatile(
+          "s_cmp_lt_i32 %[c], 3\n\t"
+          "s_cbranch_scc1 1f\n\t"
+          "v_bitop3_b32 %[n], %[n], %[p54], %[p53] bitop3:0xfe\n\t"
+          "s_cmp_lt_i32 %[c], 5\n\t"
+          "s_cbranch_scc1 2f\n\t"
+          "v_bitop3_b32 %[n], %[n], %[p52], %[p51] bitop3:0xfe\n\t"
+          "s_cmp_lt_i32 %[c], 6\n\t"
+          "s_cbranch_scc1 3f\n\t"
+          "v_or_b32 %[n], %[n], %[p50]\n\t"
+          "s_branch 3f\n"
+          "2:\n\t"
+          "s_cmp_lt_i32 %[c], 4\n\t"
+          "s_cbranch_scc1 3f\n\t"
+          "v_or_b32 %[n], %[n], %[p52]\n\t"
+          "s_branch 3f\n"
+          "1:\n\t"
+          "s_cmp_lt_i32 %[c], 2\n\t"
+          "s_cbranch_scc1 3f\n\t"
+          "v_or_b32 %[n], %[n], %[p54]\n"
+          "3:\n"
+          : [n] "+v"(n)
+          : [c] "s"(cls), [p54] "v"(P[54]), [p53] "v"(P[53]), [p52] "v"(P[52]), [p51] "v"(P[51]), [p50] "v"(P[50])
+          : "scc");
+      if (__builtin_expect(cls == 0, 0)) n = w1_exact_filter(P, besthi[2 * sl + 1], left_row);   // no usable minimum yet: the exact filter of the slot's depth
+#elif MH_W1_CLS == 4
+      // As 2, on the block's masks: every test is s_bitcmp1_b64 mask, slot.  The classes 5 and 6 (the common ones from the third row on)
+      // leave at the first test and end at the common label without a branch behind them: two tests, one taken branch for class 6 where 2 had
+      // three compares and the trailing s_branch; the classes 1..4 follow in line (three tests).  The code each class executes is what it was.
+      asm volatile(
+          "s_bitcmp1_b64 %[m5], %[t]\n\t"
+          "s_cbranch_scc1 5f\n\t"
+          "s_bitcmp1_b64 %[m3], %[t]\n\t"
+          "s_cbranch_scc0 1f\n\t"
+          "v_bitop3_b32 %[n], %[n], %[p54], %[p53] bitop3:0xfe\n\t"
+          "s_bitcmp1_b64 %[m4], %[t]\n\t"
+          "s_cbranch_scc0 3f\n\t"
+          "v_or_b32 %[n], %[n], %[p52]\n\t"
+          "s_branch 3f\n"
+          "1:\n\t"
+          "s_bitcmp1_b64 %[m2], %[t]\n\t"
+          "s_cbranch_scc0 3f\n\t"
+          "v_or_b32 %[n], %[n], %[p54]\n\t"
+          "s_branch 3f\n"
+          "5:\n\t"
+          "v_bitop3_b32 %[n], %[n], %[p54], %[p53] bitop3:0xfe\n\t"
+          "v_bitop3_b32 %[n], %[n], %[p52], %[p51] bitop3:0xfe\n\t"
+          "s_bitcmp1_b64 %[m6], %[t]\n\t"
+          "s_cbranch_scc0 3f\n\t"
+          "v_or_b32 %[n], %[n], %[p50]\n"
+          "3:\n"
+          : [n] "+v"(n)
+          : [t] "s"(sl), [m2] "s"(c.m2), [m3] "s"(c.m3), [m4] "s"(c.m4), [m5] "s"(c.m5), [m6] "s"(c.m6),
+            [p54] "v"(P[54]), [p53] "v"(P[53]), [p52] "v"(P[52]), [p51] "v"(P[51]), [p50] "v"(P[50])
+          : "scc");
+      if (__builtin_expect(sl == z0, 0)) {   // no usable minimum yet: the exact filter of the slot's depth
+        int so;   // (the slot index through an opaque copy: otherwise the address of its minimum is strength-reduced into one more
+                  //  scalar add in EVERY step of the loop, for a path one step in a thousand takes)
+        asm volatile("s_mov_b32 %0, %1" : "=s"(so) : "s"(sl));
+        n = w1_exact_filter(P, besthi[2 * so + 1], left_row);
+        m0 &= m0 - 1ULL;
+        z0 = m0 ? s0 + (int)__builtin_ctzll(m0) : -1;
+      }
+#else
+      // as 2, with the deepest classes (from the third row on the most frequent) on the straightest path: one C branch sends the
+      // classes 0..2 out of line, the assembly takes 3..6 in four scalar instructions
+      if (__builtin_expect(cls < 3, 0)) {
+        if (cls == 2) n |= P[54];
+        else if (cls == 0) {   // no usable minimum yet: the exact filter of the slot's depth
+          int so;   // (the slot index through an opaque copy: otherwise the address of its minimum is strength-reduced into one more
+                    //  scalar add in EVERY step of the loop, for a path one step in a thousand takes)
+          asm volatile("s_mov_b32 %0, %1" : "=s"(so) : "s"(sl));
+          n = w1_exact_filter(P, besthi[2 * so + 1], left_row);
+        }
+      } else {
+        uint32_t o;   // (a result register of its own: tied to n the compiler copies n first, for the other path's sake)
+        asm volatile(
+            "v_bitop3_b32 %[o], %[n], %[p54], %[p53] bitop3:0xfe\n\t"
+            "s_cmp_lt_i32 %[c], 5\n\t"
+            "s_cbranch_scc0 4f\n\t"
+            "s_cmp_lt_i32 %[c], 4\n\t"
+            "s_cbranch_scc1 3f\n\t"
+            "v_or_b32 %[o], %[o], %[p52]\n\t"
+            "s_branch 3f\n"
+            "4:\n\t"
+            "v_bitop3_b32 %[o], %[o], %[p52], %[p51] bitop3:0xfe\n\t"
+            "s_cmp_lt_i32 %[c], 6\n\t"
+            "s_cbranch_scc1 3f\n\t"
+            "v_or_b32 %[o], %[o], %[p50]\n"
+            "3:\n"
+            : [o] "=&v"(o)
+            : [n] "v"(n), [c] "s"(cls), [p54] "v"(P[54]), [p53] "v"(P[53]), [p52] "v"(P[52]), [p51] "v"(P[51]), [p50] "v"(P[50])
+            : "scc");
+        n = o;
+      }
+#endif
+      nacc &= n;   // no ballot, compare or branch per step
+    }
+    const unsigned long long m = __ballot(nacc != 0xFFFFFFFFu);
+    if (__builtin_expect(m != 0ULL, 1)) w1_enqueue(q, qn, wcap, (uint32_t)sb, ~nacc, m);   // (nearly every sub-block has a candidate: the enqueue is the fall-through side)
+  }
 }
 
 template <bool PROF>
@@ -1746,112 +1908,19 @@ __device__ __forceinline__ void w1_row2(int64_t* best, uint2* __restrict__ q, in
   } else {
     const int32_t* besthi = (const int32_t*)best;
     for (int s0 = 0; s0 < H; s0 += 64) {
-      int vcls;
+      W1Cls c;
       {
         uint32_t ln;   // (the lane id where it is used: a value kept across the slot loop is one more register the allocator spills around)
         asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=&v"(ln));
-        vcls = w1_class_of(besthi[2 * (s0 + (int)ln < H ? s0 + (int)ln : H - 1) + 1]);   // classes of 64 slots, one per lane
+        const int sc = s0 + (int)ln < H ? s0 + (int)ln : H - 1;
+        c.vcls = w1_class_of(besthi[2 * sc + 1], sc);   // classes of 64 slots, one per lane
       }
+      c.m0 = __ballot(c.vcls == 0);
+      c.m2 = __ballot(c.vcls >= 2); c.m3 = __ballot(c.vcls >= 3); c.m4 = __ballot(c.vcls >= 4); c.m5 = __ballot(c.vcls >= 5); c.m6 = __ballot(c.vcls >= 6);
       int send = s0 + 64;   // (scalar loop bound: written as a select it became v_med3 and a VALU compare per step)
       if (send > H) send = H;
       send = __builtin_amdgcn_readfirstlane(send);
-      for (int sb = s0; sb < send; sb += W1_DEFER) {
-        int se = sb + W1_DEFER;
-        if (se > send) se = send;
-        se = __builtin_amdgcn_readfirstlane(se);
-        uint32_t nacc = 0xFFFFFFFFu;   // AND of the sub-block's filter words: a zero bit = the chain passed a slot's filter (alive inside the sub-block only)
-        for (int sl = sb; sl < se; sl++) {
-          const int t = sl - s0;
-          const int cls = __builtin_amdgcn_readlane(vcls, t);
-          bs_step(P);
-          uint32_t n = w1_base_filter(P);
-#if MH_W1_CLS == 0
-          switch (cls) {
-            case 1: break;
-            case 2: n |= P[54]; break;
-            case 3: n = __builtin_amdgcn_bitop3_b32(n, P[54], P[53], BS_TT_OR3); break;
-            case 4: n = __builtin_amdgcn_bitop3_b32(n, P[54], P[53], BS_TT_OR3) | P[52]; break;
-            case 5: n = __builtin_amdgcn_bitop3_b32(__builtin_amdgcn_bitop3_b32(n, P[54], P[53], BS_TT_OR3), P[52], P[51], BS_TT_OR3); break;
-            case 6: n = __builtin_amdgcn_bitop3_b32(__builtin_amdgcn_bitop3_b32(n, P[54], P[53], BS_TT_OR3), P[52], P[51], BS_TT_OR3) | P[50]; break;
-            default: n = w1_exact_filter(P, besthi[2 * sl + 1], nk - rb); break;
-          }
-#elif MH_W1_CLS == 1
-          if (__builtin_expect(cls >= 3, 1)) {
-            n = __builtin_amdgcn_bitop3_b32(n, P[54], P[53], BS_TT_OR3);
-            if (cls >= 5) {
-              n = __builtin_amdgcn_bitop3_b32(n, P[52], P[51], BS_TT_OR3);
-              if (cls >= 6) n |= P[50];
-            } else if (cls == 4) n |= P[52];
-          } else if (cls == 2) n |= P[54];
-          else if (__builtin_expect(cls == 0, 0)) n = w1_exact_filter(P, besthi[2 * sl + 1], nk - rb);   // no usable minimum yet: the exact filter of the slot's depth
-#elif MH_W1_CLS == 2
-          // The class selects code through a short chain of scalar compares, deepest classes first (the common ones from the third row on),
-          // written out in assembly: the compiler lowers the equivalent `switch` / if-chain through its control-flow structurizer — a compare
-          // tree with "which way did I come" flags in SGPR pairs, 11 to 16 scalar instructions a step (and selects in place of the
-          // innermost branches); this is 6 or 7.  (One asm statement, branches local to it; classes 1..6 add the planes 9..13.)
-          asm volatile(
-              "s_cmp_lt_i32 %[c], 3\n\t"
-              "s_cbranch_scc1 1f\n\t"
-              "v_bitop3_b32 %[n], %[n], %[p54], %[p53] bitop3:0xfe\n\t"
-              "s_cmp_lt_i32 %[c], 5\n\t"
-              "s_cbranch_scc1 2f\n\t"
-              "v_bitop3_b32 %[n], %[n], %[p52], %[p51] bitop3:0xfe\n\t"
-              "s_cmp_lt_i32 %[c], 6\n\t"
-              "s_cbranch_scc1 3f\n\t"
-              "v_or_b32 %[n], %[n], %[p50]\n\t"
-              "s_branch 3f\n"
-              "2:\n\t"
-              "s_cmp_lt_i32 %[c], 4\n\t"
-              "s_cbranch_scc1 3f\n\t"
-              "v_or_b32 %[n], %[n], %[p52]\n\t"
-              "s_branch 3f\n"
-              "1:\n\t"
-              "s_cmp_lt_i32 %[c], 2\n\t"
-              "s_cbranch_scc1 3f\n\t"
-              "v_or_b32 %[n], %[n], %[p54]\n"
-              "3:\n"
-              : [n] "+v"(n)
-              : [c] "s"(cls), [p54] "v"(P[54]), [p53] "v"(P[53]), [p52] "v"(P[52]), [p51] "v"(P[51]), [p50] "v"(P[50])
-              : "scc");
-          if (__builtin_expect(cls == 0, 0)) n = w1_exact_filter(P, besthi[2 * sl + 1], nk - rb);   // no usable minimum yet: the exact filter of the slot's depth
-#else
-          // as 2, with the deepest classes (from the third row on the most frequent) on the straightest path: one C branch sends the
-          // classes 0..2 out of line, the assembly takes 3..6 in four scalar instructions
-          if (__builtin_expect(cls < 3, 0)) {
-            if (cls == 2) n |= P[54];
-            else if (cls == 0) {   // no usable minimum yet: the exact filter of the slot's depth
-              int so;   // (the slot index through an opaque copy: otherwise the address of its minimum is strength-reduced into one more
-                        //  scalar add in EVERY step of the loop, for a path one step in a thousand takes)
-              asm volatile("s_mov_b32 %0, %1" : "=s"(so) : "s"(sl));
-              n = w1_exact_filter(P, besthi[2 * so + 1], nk - rb);
-            }
-          } else {
-            uint32_t o;   // (a result register of its own: tied to n the compiler copies n first, for the other path's sake)
-            asm volatile(
-                "v_bitop3_b32 %[o], %[n], %[p54], %[p53] bitop3:0xfe\n\t"
-                "s_cmp_lt_i32 %[c], 5\n\t"
-                "s_cbranch_scc0 4f\n\t"
-                "s_cmp_lt_i32 %[c], 4\n\t"
-                "s_cbranch_scc1 3f\n\t"
-                "v_or_b32 %[o], %[o], %[p52]\n\t"
-                "s_branch 3f\n"
-                "4:\n\t"
-                "v_bitop3_b32 %[o], %[o], %[p52], %[p51] bitop3:0xfe\n\t"
-                "s_cmp_lt_i32 %[c], 6\n\t"
-                "s_cbranch_scc1 3f\n\t"
-                "v_or_b32 %[o], %[o], %[p50]\n"
-                "3:\n"
-                : [o] "=&v"(o)
-                : [n] "v"(n), [c] "s"(cls), [p54] "v"(P[54]), [p53] "v"(P[53]), [p52] "v"(P[52]), [p51] "v"(P[51]), [p50] "v"(P[50])
-                : "scc");
-            n = o;
-          }
-#endif
-          nacc &= n;   // no ballot, compare or branch per step
-        }
-        const unsigned long long m = __ballot(nacc != 0xFFFFFFFFu);
-        if (__builtin_expect(m != 0ULL, 1)) w1_enqueue(q, qn, wcap, (uint32_t)sb, ~nacc, m);   // (nearly every sub-block has a candidate: the enqueue is the fall-through side)
-      }
+      w1_class_block(P, c, besthi, s0, send, nk - rb, q, qn, wcap);
     }
   }
   if (qn > wcap) ok = false;
