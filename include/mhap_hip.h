@@ -1188,6 +1188,84 @@ int mhap_repeat_judge_record(const mhap_record* in, const int32_t* intervalsA, i
                              const mhap_repeat_params* params, int32_t* unique /* 2, or NULL */);
 void mhap_repeat_free(mhap_repeat_session* s);
 
+/* ---- variant sites: positions where the pile-up shows two well-supported alleles, overlaps that disagree across them set aside ---- */
+
+/* An opt-in step in front of the repeat marking, the trimming and the string graph (what HiCanu and hifiasm do in front of their
+ * graphs, as integer arithmetic).  Every other stage takes two reads that align well for two views of one sequence; this one asks
+ * whether they agree where the pile-up says there are two alleles, which is what tells the two haplotypes of a diploid sample, or the
+ * two copies of a diverged repeat, apart.  The result is a function of the multiset of accepted views: the same bytes from run to
+ * run and however the records are split over calls or ordered, except for which views the cap below skips.  Nothing is
+ * de-duplicated.  A, C, G, T are the upper-case bytes, with the codes 0, 1, 2, 3; the complement of code b is 3 - b.
+ *
+ * Input.  The reads (bases, read_ids[r], offsets[r], lengths[r], as for mhap_correct_begin), realigned records with their paths as for
+ * mhap_correct_add, and the parameters min_depth (8), min_minor (3), min_pct (25), max_del_pct (25), min_diff (2), diff_pct (50).  The
+ * defaults are provisional (EXPERIMENTS.md, "Variant filter").  min_depth, min_minor and min_diff >= 1 and the three percentages in
+ * 0 .. 100, else MHAP_E_INVALID with a message that gives the six values.
+ *
+ * 1. Votes.  Which records vote, their two views and the columns of a view are those of "read correction" above, word for word.  Six
+ * counters per target position t: base[4] (A, C, G, T), del and span, with the correction's meaning: M(t, e) adds 1 to base[t][e]
+ * when e is A, C, G or T; Del(t) adds 1 to del[t]; two consecutive target-consuming columns t, t' of a view add 1 to span[t].  Ins
+ * columns vote nothing: there are no insertion slots.  Every vote is 1; base qualities play no part.  The counters are 16 bits wide,
+ * two to a word, 12 bytes per base; the cap is the correction's: views are accepted per target in arrival order (record by record,
+ * view A before view B), and a view whose target already has 65 535 accepted views is skipped whole and counted in skipped_views.
+ * The six counters equal the first six of mhap_correct_votes for the same records and paths.
+ *
+ * 2. Sites.  For position t of a read with own byte o: c[b] = base[t][b], plus 1 when o is b; depth = c[A] + c[C] + c[G] + c[T] +
+ * del[t] (so a position nobody voted on has depth 1 when o is A, C, G or T, else 0).  major = the b with the greatest c[b], the
+ * lowest code among those tied; minor = the same over the other three codes.  The position is deep iff depth >= min_depth, and a site
+ * iff all of these hold, in integers:
+ *   o is A, C, G or T;   depth >= min_depth;   c[minor] >= min_minor;   100 c[minor] >= min_pct depth;   100 del[t] <= max_del_pct depth.
+ * Per base one site byte stays on the device: bit 0 site, and for a site bits 1 - 2 major and bits 3 - 4 minor (0 for no site).  Per
+ * read two int32 {n_sites, n_deep}.  The site list has one row of six int32 {pos, major, minor, c[major], c[minor], depth} per site,
+ * in the order of the reads and then of the positions; int64 offsets[n_reads + 1] are the prefix sums of n_sites, so read r's rows
+ * are [offsets[r], offsets[r + 1]).  MHAP_VARIANT_COUNTS int64 counts: reads, reads with a site, sites, deep positions, bases,
+ * accepted views, skipped views.
+ *
+ * 3. Judging a record.  A record that would not vote (no runs, or equal ids) has four zero tallies and keep = 1.  Of any other, every
+ * '=' / 'X' column (i, j) of the path is classed from a = s1[i], b = s2[j] (read B's byte in the aligner's orientation, complemented
+ * through the aligner's table when to_rc), the site byte of A at i, and the site byte of B at its own position (blen - 1 - j when
+ * to_rc, else j) with major and minor replaced by their complements when to_rc.  The column is informative iff either byte is a
+ * site.  Its allele pair is {major, minor} of the one that is; when both are, the two pairs must be equal as sets, else the column
+ * counts as other.  With a and b both in the pair the column counts as agree when a == b and as disagree when not; with either
+ * outside it (any byte that is not A, C, G or T is) as other.  tallies[q] = {informative, agree, disagree, other} as int32, and
+ *   keep[q] = !(disagree >= min_diff && 100 disagree >= diff_pct (agree + disagree)).
+ * The rule is symmetric in the two reads by construction: a column's class reads a and b, and the two site bytes, as unordered
+ * pairs, so a record and the same alignment written from read B's side (rows and columns exchanged, and for to_rc everything
+ * complemented and reversed) get the same four tallies and the same keep.  Records are never rewritten.
+ *
+ * What it does not do.  Votes are not weighed by quality; indels are no variants (a position the pile-up mostly deletes is no site,
+ * that is all); sites are not phased into blocks; the read correction and the consensus stay haplotype-blind; one GPU.
+ *
+ * The session.  mhap_variant_begin uploads the bases once and allocates and zeroes the vote table (params NULL: the defaults); the
+ * handle must outlive the session, whose errors are the handle's.  mhap_variant_add accepts, validates, caps and refuses exactly as
+ * mhap_correct_add does — MHAP_E_INVALID, naming the record, for an id not among read_ids, an alen or blen that disagrees with the
+ * read's length, a paths object of another n, or runs that do not spell the record's intervals (the same two rules) — and a refused
+ * call has cast no vote; one wave per accepted view adds its votes (variant_kernels.hip).  After a completed mhap_variant_finish the
+ * add is refused: the site bytes are those of the votes before it.  mhap_variant_votes: the six counters of every position of read
+ * read_index, position-major, in the order A C G T del span; for tests.  mhap_variant_finish makes the site bytes, the rows, the
+ * offsets and the list on the device (one workgroup per read over tiles of MHAP_VARIANT_TILE positions, longest reads first; a site's
+ * row comes from a prefix sum, never from an atomic) and returns the counts; it may be repeated.  mhap_variant_copy writes the rows,
+ * offsets and the counts[2] rows of the list.  mhap_variant_apply, after a finish (else MHAP_E_INVALID): one wave per record walks the
+ * path again; the records and paths are checked as in the add and a refused call writes nothing; the caller compacts.  Device memory
+ * from begin to free: 14 bytes per base (votes, site byte, the base), 44 per read, 24 per site, 4 per run and 64 per view of the
+ * largest add, 97 per record of the largest apply. */
+typedef struct mhap_variant_params {
+  int32_t min_depth, min_minor, min_pct, max_del_pct, min_diff, diff_pct;
+} mhap_variant_params;
+#define MHAP_VARIANT_COUNTS 7
+#define MHAP_VARIANT_TILE 1024
+typedef struct mhap_variant_session mhap_variant_session;
+void mhap_variant_default_params(mhap_variant_params* p);
+int mhap_variant_begin(mhap_handle* h, const uint8_t* bases, int64_t n_bases, const int64_t* read_ids, const int64_t* offsets,
+                       const int32_t* lengths, int64_t n_reads, const mhap_variant_params* params, mhap_variant_session** session);
+int mhap_variant_add(mhap_variant_session* s, const mhap_record* realigned, int64_t n, const mhap_align_paths* paths);
+int mhap_variant_votes(mhap_variant_session* s, int64_t read_index, uint16_t* counters /* length x 6 */);
+int mhap_variant_finish(mhap_variant_session* s, int64_t* counts /* MHAP_VARIANT_COUNTS */);
+int mhap_variant_copy(mhap_variant_session* s, int32_t* rows /* n_reads x 2 */, int64_t* offsets /* n_reads + 1 */, int32_t* sites /* counts[2] x 6 */);
+int mhap_variant_apply(mhap_variant_session* s, const mhap_record* realigned, int64_t n, const mhap_align_paths* paths, uint8_t* keep /* n */,
+                       int32_t* tallies /* n x 4 */);
+void mhap_variant_free(mhap_variant_session* s);
+
 /* ---- overlap selection: every read keeps its best_n best views as evidence, the others are set aside view by view ---- */
 
 /* An opt-in step in front of the read correction (the overlap selection of Canu's evidence-coverage cap and minimum evidence length

@@ -54,6 +54,8 @@ from .api import (  # noqa: F401
     RepeatSession,
     repeat_counts_line,
     repeat_judge_record,
+    VariantSession,
+    variant_counts_line,
     SelectSession,
     select_overlaps,
     select_counts_line,

@@ -277,6 +277,14 @@ _PROTOTYPES = {
     "mhap_weight_default_params": "v:p",
     "mhap_correct_begin_weighted": "i:pppqpppqpp",
     "mhap_consensus_begin_weighted": "i:pppqpppp",
+    "mhap_variant_default_params": "v:p",
+    "mhap_variant_begin": "i:ppqpppqpp",
+    "mhap_variant_add": "i:ppqp",
+    "mhap_variant_votes": "i:pqp",
+    "mhap_variant_finish": "i:pp",
+    "mhap_variant_copy": "i:pppp",
+    "mhap_variant_apply": "i:ppqppp",
+    "mhap_variant_free": "v:p",
 }
 EXPORTED_SYMBOLS = list(_PROTOTYPES)
 MHAP_KMER_HISTOGRAM = 1   # mhap_kmer_count_finish_flags
@@ -1396,6 +1404,112 @@ class RepeatSession(_ReadsSession):
         keep, unique = np.zeros(len(records), np.uint8), np.zeros((len(records), 2), np.int32)
         self._ms._chk(self._lib.mhap_repeat_apply(self._s, _opt(records), C.c_int64(len(records)), _opt(keep), _opt(unique)))
         return keep, unique
+
+
+VARIANT_COUNTS = ("reads", "reads_with_site", "sites", "deep_positions", "bases", "accepted_views", "skipped_views")   # mhap_variant_finish's counts
+VARIANT_SITE_FIELDS = ("pos", "major", "minor", "n_major", "n_minor", "depth")
+VARIANT_TALLIES = ("informative", "agree", "disagree", "other")
+VARIANT_COUNTERS = 6   # per position: base A C G T, del, span
+VARIANT_TILE = 1024    # MHAP_VARIANT_TILE: the positions the site kernel takes at a time
+VARIANT_DEFAULTS = dict(min_depth=8, min_minor=3, min_pct=25, max_del_pct=25, min_diff=2, diff_pct=50)   # provisional (EXPERIMENTS.md, "Variant filter")
+
+
+class _VariantParams(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("min_depth", "min_minor", "min_pct", "max_del_pct", "min_diff", "diff_pct")]
+
+
+def variant_counts_line(counts, set_aside, judged):
+    """The one stderr line of a variant filter (the driver prints the same); counts: the MHAP_VARIANT_COUNTS values in order."""
+    c = [int(x) for x in counts]
+    return (f"Variant sites: {c[0]} reads, {c[1]} with a site; {c[2]} sites, {c[3]} of {c[4]} positions deep; {c[5]} views, "
+            f"skipped_views = {c[6]}; {int(set_aside)} of {int(judged)} overlaps set aside")
+
+
+class VariantSession(_Session):
+    """Variant sites from the pile-up votes and the overlaps judged across them (mhap_variant_begin / _add / _votes / _finish / _copy /
+    _apply; the contract is the "variant sites" section of include/mhap_hip.h).  The vote table (12 bytes per base) and the site
+    bytes stay on the device from begin to close.
+
+        with VariantSession(fasta, min_depth=8, ...) as vs:
+            vs.add(records, op_offsets, ops)              # what realign_records_paths returned; any number of times
+            counts = vs.finish()                          # a dict of VARIANT_COUNTS
+            rows, offsets, sites = vs.table()             # read r's sites: sites[offsets[r]:offsets[r + 1]], VARIANT_SITE_FIELDS
+            keep, tallies = vs.apply(records, op_offsets, ops)   # records[keep != 0] stay; tallies: int32 (n, 4) of VARIANT_TALLIES
+
+    handle: a MinHashSearch whose device and stream to use (else one is made and closed with the session)."""
+
+    _prefix = "mhap_variant"
+    _table = counts = None
+
+    def __init__(self, fasta, query_fasta=None, handle=None, device=0, **params):
+        unknown = set(params) - set(VARIANT_DEFAULTS)
+        if unknown:
+            raise MhapError(f"VariantSession: no parameter {sorted(unknown)[0]}")
+        bases, ids, offsets, lengths = _all_reads(fasta, query_fasta)
+        self._bases = np.ascontiguousarray(bases, np.uint8)
+        self.ids, self._offsets = np.ascontiguousarray(ids, np.int64), np.ascontiguousarray(offsets, np.int64)
+        self.lengths = np.ascontiguousarray(lengths, np.int32)
+        self.params = dict(VARIANT_DEFAULTS, **params)
+        p = _VariantParams(**{k: int(x) for k, x in self.params.items()})
+        begin = lambda: self._lib.mhap_variant_begin(   # noqa: E731
+            self._ms._h, _ptr(self._bases), len(self._bases), _ptr(self.ids), _ptr(self._offsets), _ptr(self.lengths), len(self.ids),
+            C.byref(p), C.byref(self._s))
+        super().__init__(handle, device, lambda: self._ms._chk(begin()))
+
+    def _with_paths(self, who, records, op_offsets, ops, call):
+        """call(records, n, paths object) with the runs as a paths object, freed afterwards."""
+        records = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
+        op_offsets = np.ascontiguousarray(op_offsets, dtype=np.int64)
+        ops = np.ascontiguousarray(ops, dtype=np.uint32)
+        if len(op_offsets) != len(records) + 1:
+            raise MhapError(f"VariantSession.{who}: {len(records)} records need {len(records) + 1} run offsets, not {len(op_offsets)}")
+        obj = C.c_void_p()
+        if self._lib.mhap_align_paths_from_runs(_ptr(op_offsets), C.c_int64(len(records)), _opt(ops), C.byref(obj)) != 0:
+            raise MhapError(f"VariantSession.{who}: op_offsets is not a list of run offsets over ops")
+        try:
+            return call(records, obj)
+        finally:
+            self._lib.mhap_align_paths_free(obj)
+
+    def add(self, records, op_offsets, ops):
+        """The votes of realigned records and their runs (pair q's are ops[op_offsets[q]:op_offsets[q + 1]])."""
+        self._with_paths("add", records, op_offsets, ops,
+                         lambda recs, obj: self._ms._chk(self._lib.mhap_variant_add(self._s, _opt(recs), C.c_int64(len(recs)), obj)))
+
+    def finish(self):
+        """Make the site bytes, the rows and the site list; returns a dict of VARIANT_COUNTS."""
+        self._table = self.counts = None
+        counts = np.zeros(len(VARIANT_COUNTS), np.int64)
+        self._ms._chk(self._lib.mhap_variant_finish(self._s, _ptr(counts)))
+        self.counts = dict(zip(VARIANT_COUNTS, counts.tolist()))
+        return self.counts
+
+    def table(self):
+        """(rows, offsets, sites) of the last finish: int32 (n, 2) of n_sites and n_deep, int64 (n + 1) and int32 (sites, 6) of
+        VARIANT_SITE_FIELDS."""
+        if self._table is None:
+            n = len(self.ids)
+            rows, offsets = np.zeros((n, 2), np.int32), np.zeros(n + 1, np.int64)
+            sites = np.zeros((self.counts["sites"] if self.counts else 0, 6), np.int32)   # (without a finish the copy refuses)
+            self._ms._chk(self._lib.mhap_variant_copy(self._s, _opt(rows), _ptr(offsets), _opt(sites)))
+            self._table = (rows, offsets, sites)
+        return self._table
+
+    def votes(self, read_index):
+        """The raw counters of one read: a uint16 array (length, VARIANT_COUNTERS)."""
+        if not 0 <= read_index < len(self.ids):
+            raise MhapError(f"VariantSession.votes: read {read_index} is not among the {len(self.ids)} reads")
+        out = np.zeros((int(self.lengths[read_index]), VARIANT_COUNTERS), np.uint16)
+        self._ms._chk(self._lib.mhap_variant_votes(self._s, C.c_int64(read_index), _opt(out)))
+        return out
+
+    def apply(self, records, op_offsets, ops):
+        """(keep, tallies): one byte per record, 0 for one that is set aside, and int32 (n, 4) of VARIANT_TALLIES."""
+        def call(recs, obj):
+            keep, tallies = np.zeros(len(recs), np.uint8), np.zeros((len(recs), 4), np.int32)
+            self._ms._chk(self._lib.mhap_variant_apply(self._s, _opt(recs), C.c_int64(len(recs)), obj, _opt(keep), _opt(tallies)))
+            return keep, tallies
+        return self._with_paths("apply", records, op_offsets, ops, call)
 
 
 SELECT_COUNTS = ("reads", "reads_with_entry", "reads_over", "entries", "kept", "eligible_records")   # mhap_select_finish's counts

@@ -1,5 +1,5 @@
 // cli_pipeline.hpp — what `mhap-hip --realign` does with every batch of found overlaps and after the last one: the reads' table, a
-// realigned batch, one struct per stage (--best-overlaps, --correct, --repeat-filter, --trim, --gfa) and the Pipeline that wires them.  Host only, over the C ABI of
+// realigned batch, one struct per stage (--best-overlaps, --correct, --variant-filter, --repeat-filter, --trim, --gfa) and the Pipeline that wires them.  Host only, over the C ABI of
 // libmhaphip.so.  A call made per batch returns the library's code (the sink reports it); what runs before the first or after the last batch dies on an error.
 #pragma once
 #include <algorithm>
@@ -323,6 +323,65 @@ struct SelectStage : Stage {
   }
 };
 
+// --variant-filter: every kept record votes with its path, batch by batch, and waits as it was found; after the last batch the sites are
+// made, the held records are realigned a second time (the aligner is deterministic: CorrectStage::add_selected), judged against the
+// sites, and each step's survivors go on to the stages behind.  The paths are not kept between the passes: about 12 kB per 10 kb overlap.
+struct VariantStage : Stage {
+  mhap_variant_params p; std::string table; mhap_variant_session* s = nullptr;
+  std::vector<mhap_record> found;             // the kept records as found
+  double second_pass = 0.0;                   // of `seconds`, the realignment of the second pass
+  void begin(const Reads& R) { chk(h, mhap_variant_begin(h, R.bases.data(), (int64_t)R.bases.size(), R.ids.data(), R.offsets.data(), R.lengths.data(), R.n(), &p, &s)); }
+  int add(const Batch& b) {
+    Tick t{seconds};
+    for (int64_t i = 0; i < b.k; i++) found.push_back(b.in[b.row[(size_t)i]]);
+    return mhap_variant_add(s, b.out.data(), b.k, b.paths);
+  }
+  // the sites of every read, the table, and the judgement of the held records in steps of 65 536; feed(b): the stages behind take b's kept records
+  template <class Feed> void finish(const Reads& R, Realigner& A, Batch& b, Feed feed) {
+    double t0 = now();
+    const int64_t nr = R.n(), total = (int64_t)found.size(), step = 1 << 16;
+    int64_t c[MHAP_VARIANT_COUNTS], judged = 0, aside = 0;
+    chk(h, mhap_variant_finish(s, c));
+    if (!table.empty()) {
+      std::vector<int32_t> rows = room<int32_t>(nr, 2), sites = room<int32_t>(c[2], 6);
+      std::vector<int64_t> off((size_t)nr + 1);
+      chk(h, mhap_variant_copy(s, rows.data(), off.data(), sites.data()));
+      Writer w(table);
+      for (int64_t r = 0; r < nr; r++)
+        for (int64_t i = off[(size_t)r]; i < off[(size_t)r + 1]; i++) {
+          const int32_t* x = sites.data() + 6 * i;
+          w.put(std::to_string(R.ids[(size_t)r]) + "\t" + std::to_string(x[0]) + "\t" + "ACGT"[x[1] & 3] + "\t" + "ACGT"[x[2] & 3] + "\t" + std::to_string(x[3]) + "\t" + std::to_string(x[4]) + "\t" +
+                std::to_string(x[5]) + "\n");
+        }
+      w.close();
+    }
+    std::vector<uint8_t> keep; std::vector<int32_t> tallies;
+    for (int64_t q0 = 0; q0 < total; q0 += step) {
+      const double t1 = now();
+      chk(h, A.run(found.data() + q0, std::min(step, total - q0), true, b));   // (the first pass's rule once more: nothing is dropped unless the aligner differs)
+      if (A.gather(b) != MHAP_OK) die("the paths of the overlaps to judge");
+      second_pass += now() - t1;
+      keep = room<uint8_t>(b.k); tallies = room<int32_t>(b.k, 4);
+      chk(h, mhap_variant_apply(s, b.out.data(), b.k, b.paths, keep.data(), tallies.data()));
+      int64_t w = 0;   // the batch compacted to the survivors: the records, their rows and, from those, their paths
+      for (int64_t i = 0; i < b.k; i++)
+        if (keep[(size_t)i]) { b.out[(size_t)w] = b.out[(size_t)i]; b.row[(size_t)w++] = b.row[(size_t)i]; }
+      judged += b.k; aside += b.k - w;
+      b.k = w;
+      if (A.gather(b) != MHAP_OK) die("the paths of the overlaps that stay");
+      seconds += now() - t0;   // (the stages behind count their own)
+      chk(h, feed(b));
+      t0 = now();
+    }
+    mhap_variant_free(s);
+    std::vector<mhap_record>().swap(found);
+    seconds += now() - t0;
+    fprintf(stderr, "Variant sites: %lld reads, %lld with a site; %lld sites, %lld of %lld positions deep; %lld views, skipped_views = %lld; %lld of %lld overlaps set aside\n",
+            ll(c[0]), ll(c[1]), ll(c[2]), ll(c[3]), ll(c[4]), ll(c[5]), ll(c[6]), ll(aside), ll(judged));
+    fprintf(stderr, "Time (s) to mark variant sites and judge: %g (%g to realign a second time)\n", seconds, second_pass);
+  }
+};
+
 // --repeat-filter: the cut copies are piled up (queued: nothing waits); every kept record waits to be judged after the last batch
 struct RepeatStage : Stage {
   mhap_repeat_params p; std::string table; mhap_repeat_session* s = nullptr;
@@ -560,20 +619,29 @@ struct TrimStage : Stage {
 // The stages of one run and which feeds which.  The three functions below are the only place that says so.
 struct Pipeline {
   Reads reads; Realigner realign; bool paf = false;   // paf: --realign-paf, the sink prints the batch's paths
-  SelectStage select; CorrectStage correct; RepeatStage repeat; TrimStage trim; GraphStage graph;
+  SelectStage select; CorrectStage correct; VariantStage variant; RepeatStage repeat; TrimStage trim; GraphStage graph;
   Batch b; bool refine = false, kept_paths = false, all_paths = false;
   void begin() {   // the stages' parameters and `on` are set: the sessions that can begin before the search do
     refine = (trim.on || repeat.on) && trim.penalty > 0;      // the pile-ups take each record cut to the best stretch of its path
-    kept_paths = (correct.on && !select.on) || refine;        // the correction votes batch by batch unless the selection feeds it
+    kept_paths = (correct.on && !select.on) || refine || variant.on;   // the correction votes batch by batch unless the selection feeds it
     all_paths = paf || kept_paths;
     select.hold = correct.on;                                 // the correction's votes: the selection's kept views, else each batch
     repeat.hold_out = graph.on && !trim.on;                   // the graph's records: the trimming's rewritten ones, else the repeat stage's survivors as realigned, else each batch
     trim.hold = graph.on;                                     // the trimming's records: the repeat stage's survivors (cut), else each batch's cut
     if (select.on) select.begin(reads);
     if (correct.on) correct.begin(reads);
+    if (variant.on) variant.begin(reads);
     if (repeat.on) repeat.begin(reads);                       // (the trimming begins once the repeat stage has freed its device arrays)
     else if (trim.on) trim.begin(reads);
     if (graph.on && !trim.on) graph.begin(reads);             // (with the trimming the graph begins after it, on the trimmed reads)
+  }
+  // the kept records of a batch, with their paths, to the pile-ups and the graph: each batch as it is realigned, or with --variant-filter the survivors of each step of its second pass
+  int feed(Batch& x) {
+    int rc = refine ? trim.refine(x) : MHAP_OK;
+    if (rc == MHAP_OK && repeat.on) rc = repeat.add(x);
+    else if (rc == MHAP_OK && trim.on) rc = trim.add(x.cut, x.k);
+    if (rc == MHAP_OK && graph.on && !trim.on && !repeat.on) rc = graph.add(x.out.data(), x.k);
+    return rc;
   }
   // r[0..n) realigned and through every stage that takes its records batch by batch; what is to be printed comes back, or null after an error
   const Batch* batch(const mhap_record* r, int64_t n) {
@@ -581,10 +649,7 @@ struct Pipeline {
     if (rc == MHAP_OK && kept_paths) rc = realign.gather(b);
     if (rc == MHAP_OK && select.on) rc = select.add(b);
     if (rc == MHAP_OK && correct.on && !select.on) rc = correct.add(b);
-    if (rc == MHAP_OK && refine) rc = trim.refine(b);
-    if (rc == MHAP_OK && repeat.on) rc = repeat.add(b);
-    else if (rc == MHAP_OK && trim.on) rc = trim.add(b.cut, b.k);
-    if (rc == MHAP_OK && graph.on && !trim.on && !repeat.on) rc = graph.add(b.out.data(), b.k);
+    if (rc == MHAP_OK) rc = variant.on ? variant.add(b) : feed(b);   // the variant filter holds every batch back: the stages behind it take its survivors after the last one
     if (rc == MHAP_OK) return &b;
     fprintf(stderr, "Exception in mhap-hip: %s (code %d)\n", mhap_last_error(realign.h), rc);
     return nullptr;
@@ -594,6 +659,7 @@ struct Pipeline {
     if (select.on) select.finish(reads);
     if (select.on && correct.on) correct.add_selected(select.found, select.views, realign);
     if (correct.on) correct.finish(reads);
+    if (variant.on) variant.finish(reads, realign, b, [&](Batch& x) { return feed(x); });
     if (repeat.on) {
       repeat.finish(reads);
       if (trim.on) { trim.begin(reads); chk(trim.h, trim.add(repeat.cut.data(), (int64_t)repeat.cut.size(), &repeat.cut)); }

@@ -372,29 +372,10 @@ static int correct_add(const char* who, mhap_correct_session* s, const mhap_reco
     if (o1 == o0 || r.from_id == r.to_id) continue;
     int64_t idx[2];
     if (!find_record_reads(s->by_id, s->lengths.data(), who, q, r, idx, *v.err)) { undo(); return MHAP_E_INVALID; }
-    // the runs are a path from (a1, j0) to (a2, j1), '=' at both ends
     const bool rc = r.to_rc != 0;
-    const int64_t i0 = r.a1, j0 = rc ? (int64_t)r.blen - r.b2 - 1 : r.b1, j1 = rc ? (int64_t)r.blen - r.b1 - 1 : r.b2;
-    int64_t rows = 0, cols = 0;
-    bool ok = o1 - o0 <= INT32_MAX && (paths->ops[(size_t)o0] & 15u) == OP_EQ && (paths->ops[(size_t)o1 - 1] & 15u) == OP_EQ;
-    for (int64_t u = o0; u < o1 && ok; u++) {
-      const uint32_t op = paths->ops[(size_t)u], code = op & 15u;
-      const int64_t len = op >> 4;
-      if (len < 1 || (code != OP_EQ && code != OP_X && code != OP_I && code != OP_D)) ok = false;
-      if (code != OP_D) rows += len;
-      if (code != OP_I) cols += len;
-    }
-    ok = ok && i0 >= 0 && j0 >= 0 && r.a2 < r.alen && j1 < r.blen && rows == (int64_t)r.a2 - i0 + 1 && cols == j1 - j0 + 1;
-    if (!ok) { undo(); return bad(q, "has runs that are not a path between its aligned ends"); }
-    // two adjacent runs of one code are one run split at 2^28 - 1 columns, or no path of the aligner's: the kernel takes the second
-    // for the continuation of the first
-    for (int64_t u = o0 + 1; u < o1; u++) {
-      const uint32_t prev = paths->ops[(size_t)u - 1];
-      if ((prev & 15u) == (paths->ops[(size_t)u] & 15u) && (prev >> 4) != RUN_MAX) {
-        undo();
-        return bad(q, "has runs " + std::to_string(u - 1 - o0) + " and " + std::to_string(u - o0) + " of one code, and the earlier is not a run split at 2^28 - 1 columns");
-      }
-    }
+    int64_t i0, j0;
+    std::string what;
+    if (!path_spells_record(r, paths->ops, o0, o1, i0, j0, what)) { undo(); return bad(q, what); }
     for (int view = 0; view < 2; view++) {
       const int64_t target = idx[view];
       if (views && !(views[q] & (1u << view))) continue;   // not selected: no vote, no place under the cap, not a skipped view

@@ -35,7 +35,7 @@ struct Options {
     return t;
   }
   // (the realignment flags are listed only when --realign is given, the correction flags only when --correct is, the graph's only
-  // when --gfa is, the cleaning's only when --gfa-clean is, the consensus' only when --gfa-consensus is, the trimming's only when --trim is, the repeat stage's only when --repeat-filter is, the selection's only when --best-overlaps is: without them every line the driver writes is what it was before them)
+  // when --gfa is, the cleaning's only when --gfa-clean is, the consensus' only when --gfa-consensus is, the trimming's only when --trim is, the repeat stage's only when --repeat-filter is, the variant stage's only when --variant-filter is, the selection's only when --best-overlaps is: without them every line the driver writes is what it was before them)
   std::string dump() const {
     std::string t;
     for (auto& n : order) {
@@ -46,6 +46,7 @@ struct Options {
       if (n.compare(0, 15, "--gfa-consensus") == 0 && !b("--gfa-consensus")) continue;
       if (n.compare(0, 6, "--trim") == 0 && !b("--trim")) continue;
       if (n.compare(0, 8, "--repeat") == 0 && !b("--repeat-filter")) continue;
+      if (n.compare(0, 9, "--variant") == 0 && !b("--variant-filter")) continue;
       if (n.compare(0, 6, "--best") == 0 && !isset("--best-overlaps")) continue;
       if (n == "--hpc" && !b("--hpc")) continue;
       if ((n == "--correct-fastq" || n == "--gfa-consensus-fastq") && !isset(n)) continue;   // (and the quality flags only with a FASTQ file to write)
@@ -348,6 +349,14 @@ void declare_options(Options& o) {
   o.add("--repeat-min-run", "[int] With --repeat-filter, the shortest stretch of repeat positions that is marked.", "500");
   o.add("--repeat-min-unique", "[int] With --repeat-filter, the aligned bases outside repeats an overlap needs on both reads.", "500");
   o.add("--repeat-table", "With --repeat-filter, write one line per repeat interval to this file: read_id begin end.", "");
+  o.add("--variant-filter", "With --realign: mark the variant sites of every read of -s on the GPU from the pile-up votes of the realigned overlaps (positions where a second allele is well supported), and set aside the overlaps whose two reads disagree across them: the two haplotypes of a diploid sample, or the copies of a diverged repeat. They reach neither --repeat-filter nor --trim nor --gfa; the overlaps are realigned a second time for the judgement. The overlaps printed, --correct and --realign-paf stay on all overlaps. Self overlaps only (no -q), one GPU.", "false", true);
+  o.add("--variant-min-depth", "[int] With --variant-filter, the depth, own base included, a position needs to be a site.", "8");
+  o.add("--variant-min-minor", "[int] With --variant-filter, the votes the second allele of a site needs.", "3");
+  o.add("--variant-min-pct", "[int] With --variant-filter, the share of the depth the second allele of a site needs, in percent.", "25");
+  o.add("--variant-max-del-pct", "[int] With --variant-filter, the greatest share of deletions in the depth of a site, in percent.", "25");
+  o.add("--variant-min-diff", "[int] With --variant-filter, the disagreeing site columns an overlap needs to be set aside.", "2");
+  o.add("--variant-diff-pct", "[int] With --variant-filter, the share of disagreeing among the agreeing and disagreeing site columns an overlap needs to be set aside, in percent.", "50");
+  o.add("--variant-table", "With --variant-filter, write one line per site to this file: read_id pos major minor n_major n_minor depth.", "");
   o.add("--best-overlaps", "[int] With --realign: select each read's N best overlaps on the GPU, by the matches counted on that read, ties at the last place included; with --correct only the selected views of an overlap vote. The overlaps printed, --realign-paf, --gfa and --trim stay on all overlaps. 0) off. Self overlaps only (no -q), one GPU.", "0");
   o.add("--best-min-span", "[int] With --best-overlaps, the shortest aligned interval on a read that counts as evidence for it.", "500");
   o.add("--best-table", "With --best-overlaps, write one line per read to this file: read_id entries kept threshold.", "");
@@ -446,6 +455,15 @@ std::vector<int32_t> check_options(Options& o) {
   owned(o, {"--trim-min-cov", "--trim-end-clip", "--trim-min-span", "--trim-fasta", "--trim-table"}, trim, " belongs to --trim: give --trim too.");
   owned(o, {"--trim-penalty"}, trim || repeat, " belongs to --trim: give --trim too.");
   owned(o, {"--repeat-factor", "--repeat-max-cov", "--repeat-min-run", "--repeat-min-unique", "--repeat-table"}, repeat, " belongs to --repeat-filter: give --repeat-filter too.");
+  owned(o, {"--variant-min-depth", "--variant-min-minor", "--variant-min-pct", "--variant-max-del-pct", "--variant-min-diff", "--variant-diff-pct", "--variant-table"}, o.b("--variant-filter"),
+        " belongs to --variant-filter: give --variant-filter too.");
+  if (o.b("--variant-filter")) {
+    stage_flag(o, n_devs, "--variant-filter", "votes with", "marks", "the reads' bases");
+    const auto pct = [&](const char* n) { return o.i(n) >= 0 && o.i(n) <= 100; };
+    if (o.i("--variant-min-depth") < 1 || o.i("--variant-min-minor") < 1 || o.i("--variant-min-diff") < 1 || !pct("--variant-min-pct") || !pct("--variant-max-del-pct") || !pct("--variant-diff-pct"))
+      bad("The values of --variant-min-depth, --variant-min-minor and --variant-min-diff must be >=1 and those of --variant-min-pct, --variant-max-del-pct and --variant-diff-pct 0 to 100.");
+    if (o.isset("--variant-table") && o.s("--variant-table").empty()) bad("--variant-table needs the name of the file to write.");
+  }
   if (repeat) {
     stage_flag(o, n_devs, "--repeat-filter", "piles up", "marks", realigned);
     if (o.i("--repeat-factor") < 100 || o.i("--repeat-max-cov") < 0 || o.i("--repeat-min-run") < 1 || o.i("--repeat-min-unique") < 0 || o.i("--trim-penalty") < 0)
@@ -526,7 +544,7 @@ void begin_pipeline(const Options& o, mhap_handle* h, Pipeline& p) {
   p.correct.weigh = p.graph.weigh = weigh;
   p.correct.wp = p.graph.wp = mhap_weight_params{o.i("--weight-q-lo"), o.i("--weight-q-hi")};
   if (weigh) p.reads.weight_line(p.correct.wp);
-  p.realign.h = p.select.h = p.correct.h = p.repeat.h = p.trim.h = p.graph.h = h;
+  p.realign.h = p.select.h = p.correct.h = p.variant.h = p.repeat.h = p.trim.h = p.graph.h = h;
   p.realign.reads = &p.reads; p.realign.band = o.i("--realign-band"); p.realign.min_identity = o.d("--realign-min-identity");
   p.paf = o.b("--realign-paf");
   p.correct.on = o.isset("--correct"); p.correct.fasta = o.s("--correct"); p.correct.min_cov = o.i("--correct-min-coverage");
@@ -535,6 +553,8 @@ void begin_pipeline(const Options& o, mhap_handle* h, Pipeline& p) {
   p.select.on = o.isset("--best-overlaps") && o.i("--best-overlaps") != 0; p.select.table = o.s("--best-table");
   mhap_select_default_params(&p.select.p);
   p.select.p.best_n = o.i("--best-overlaps"); p.select.p.min_span = o.i("--best-min-span");
+  p.variant.on = o.b("--variant-filter"); p.variant.table = o.s("--variant-table");
+  p.variant.p = mhap_variant_params{o.i("--variant-min-depth"), o.i("--variant-min-minor"), o.i("--variant-min-pct"), o.i("--variant-max-del-pct"), o.i("--variant-min-diff"), o.i("--variant-diff-pct")};
   p.repeat.on = o.b("--repeat-filter"); p.repeat.table = o.s("--repeat-table");
   mhap_repeat_default_params(&p.repeat.p);
   p.repeat.p.factor_pct = o.i("--repeat-factor"); p.repeat.p.max_cov = o.i("--repeat-max-cov"); p.repeat.p.min_run = o.i("--repeat-min-run"); p.repeat.p.min_unique = o.i("--repeat-min-unique");

@@ -7,7 +7,9 @@
 #include <stdint.h>
 
 #include <string>
+#include <vector>
 
+#include "../../include/mhap_hip.h"
 #include "device_common.hpp"
 
 namespace mhap {
@@ -32,6 +34,35 @@ struct VoteItem {
   int32_t pad;
 };
 
+// The check of every add that takes records with their paths: the runs ops[o0, o1) of record r are a path from (a1, j0) to (a2, j1),
+// '=' at both ends, and no two adjacent runs have one code unless the earlier is a run split at 2^28 - 1 columns (the walk takes the
+// second for the continuation of the first).  i0, j0: the path's first row and column; false with what the refusal says of the record.
+inline bool path_spells_record(const mhap_record& r, const std::vector<uint32_t>& ops, int64_t o0, int64_t o1, int64_t& i0, int64_t& j0,
+                               std::string& what) {
+  const bool rc = r.to_rc != 0;
+  i0 = r.a1; j0 = rc ? (int64_t)r.blen - r.b2 - 1 : r.b1;
+  const int64_t j1 = rc ? (int64_t)r.blen - r.b1 - 1 : r.b2;
+  int64_t rows = 0, cols = 0;
+  bool ok = o1 - o0 <= INT32_MAX && (ops[(size_t)o0] & 15u) == OP_EQ && (ops[(size_t)o1 - 1] & 15u) == OP_EQ;
+  for (int64_t u = o0; u < o1 && ok; u++) {
+    const uint32_t op = ops[(size_t)u], code = op & 15u;
+    const int64_t len = op >> 4;
+    if (len < 1 || (code != OP_EQ && code != OP_X && code != OP_I && code != OP_D)) ok = false;
+    if (code != OP_D) rows += len;
+    if (code != OP_I) cols += len;
+  }
+  ok = ok && i0 >= 0 && j0 >= 0 && r.a2 < r.alen && j1 < r.blen && rows == (int64_t)r.a2 - i0 + 1 && cols == j1 - j0 + 1;
+  if (!ok) { what = "has runs that are not a path between its aligned ends"; return false; }
+  for (int64_t u = o0 + 1; u < o1; u++) {
+    const uint32_t prev = ops[(size_t)u - 1];
+    if ((prev & 15u) == (ops[(size_t)u] & 15u) && (prev >> 4) != RUN_MAX) {
+      what = "has runs " + std::to_string(u - 1 - o0) + " and " + std::to_string(u - o0) + " of one code, and the earlier is not a run split at 2^28 - 1 columns";
+      return false;
+    }
+  }
+  return true;
+}
+
 __device__ inline int base_code(uint32_t c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1; }
 
 __device__ inline void vote(uint32_t* __restrict__ table, int64_t v_words, int tlen, int t, int counter) {
@@ -39,9 +70,16 @@ __device__ inline void vote(uint32_t* __restrict__ table, int64_t v_words, int t
   atomicAdd(table + v_words + (int64_t)(counter >> 1) * tlen + t, (counter & 1) ? 0x10000u : 1u);
 }
 
+struct NoColumn { __device__ void operator()(bool, int, int) const {} };
+
 // The column walk of one view: every column of the path `it` names casts its vote.  One wave; the caller is a kernel of 64 threads.
+// The walk is written once, so its three switches are compile-time: INS false leaves the insertion slots out (a table of three planes,
+// "variant sites"), VOTE false casts no vote at all, and each(diag, i, j) is called for every column by every lane that has one (diag:
+// it is an '=' or 'X' column; lane 0 has a column whenever any lane has), which is what the variant judgement hangs its ballots on.
+// The defaults are the walk as the correction and the consensus use it.
+template <bool VOTE = true, bool INS = true, class Each = NoColumn>
 __device__ inline void vote_walk(const uint8_t* __restrict__ bases, const VoteItem& it, const uint32_t* __restrict__ ops,
-                                 uint32_t* __restrict__ table) {
+                                 uint32_t* __restrict__ table, Each each = Each()) {
   __shared__ int s_col[65], s_i[64], s_j[64];
   __shared__ uint32_t s_op[64];
   const int lane = threadIdx.x;
@@ -81,6 +119,8 @@ __device__ inline void vote_walk(const uint8_t* __restrict__ bases, const VoteIt
       const bool diag = rcode == OP_EQ || rcode == OP_X;
       const int i = s_i[lo] + ((diag || rcode == OP_I) ? c : 0), j = s_j[lo] + ((diag || rcode == OP_D) ? c : 0);
       const bool consumes_target = diag || rcode == (target_b ? OP_D : OP_I);
+      each(diag, i, j);
+      if (!VOTE) continue;
       if (consumes_target) {
         const int t = !target_b ? i : rev ? it.blen - 1 - j : j;
         if (diag) {
@@ -95,7 +135,7 @@ __device__ inline void vote_walk(const uint8_t* __restrict__ bases, const VoteIt
         // the view continues past t unless this is its last column: the path's last, or its first in the reversed view
         const bool view_end = rev ? (ridx == 0 && c == 0) : (ridx == it.n_ops - 1 && c == rlen - 1);
         if (!view_end) vote(table, it.v_words, tlen, t, 5);
-      } else {
+      } else if (INS) {
         // an Ins column: the group is this run (a run split at 2^28 - 1 columns continues a group whose first four slots are taken)
         const int k = rev ? rlen - 1 - c : c;
         if (k < CK_KI) {

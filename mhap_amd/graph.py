@@ -1,7 +1,7 @@
 """The string graph of a file of MHAP overlaps, on the GPU: `python -m mhap_amd.graph overlaps.txt reads.fasta [--band W]
 [--min-identity X] [--max-hang N] [--int-frac F] [--min-overlap N] [--fuzz N] -o out.gfa [--unitigs utg.gfa] [--clean [--tip-reads N]
 [--bubble-bases N] [--clean-rounds N]] [--consensus [--consensus-fasta F] [--consensus-fastq F [--quality-per-vote N] [--quality-cap N]]
-[--consensus-min-cov N]] [--repeat-filter ...]` writes what `mhap-hip --realign
+[--consensus-min-cov N]] [--repeat-filter ...] [--variant-filter ...]` writes what `mhap-hip --realign
 --gfa out.gfa [--gfa-unitigs utg.gfa] [--gfa-clean ...]` writes for the same overlaps.
 
 The overlaps are parsed and realigned as `python -m mhap_amd.realign` does; the records that tool would drop (no alignment, or an
@@ -26,13 +26,17 @@ the surviving reads, their trimmed lengths and the overlaps rewritten onto them.
 With --repeat-filter [--repeat-factor PCT] [--repeat-max-cov N] [--repeat-min-run N] [--repeat-min-unique N] repeats are marked from the
 overlap pile-up first ("repeat marking" in the same header; `python -m mhap_amd.repeats` writes the intervals) and the overlaps that
 lie in nothing but repeat reach neither the trimming nor the graph; a two-copy repeat at ordinary depth is not reliably found.
-Not done: bubbles that are not simple, a second trimming round.  One line on stderr gives the counts (one more with --repeat-filter
-and one more with --trim, in front; one more with --clean, one more with --unitigs, one more with --consensus).
+With --variant-filter [--variant-min-depth N] [--variant-min-minor N] [--variant-min-pct PCT] [--variant-max-del-pct PCT]
+[--variant-min-diff N] [--variant-diff-pct PCT] variant sites are marked from the pile-up votes in front of all of that ("variant sites"
+in the same header; `python -m mhap_amd.variants` writes the sites) and the overlaps whose reads disagree across them reach neither
+the repeat marking nor the trimming nor the graph.
+Not done: bubbles that are not simple, a second trimming round.  One line on stderr gives the counts (one more with --variant-filter,
+one more with --repeat-filter and one more with --trim, in front; one more with --clean, one more with --unitigs, one more with --consensus).
 """
 import argparse
 import sys
 
-from . import api, fastq, repeats
+from . import api, fastq, repeats, variants
 from .realign import kept_rows, read_overlaps
 
 BATCH = 1 << 16   # records realigned and classed per call
@@ -56,7 +60,7 @@ def consensus_fasta(seqs, circular):
 
 
 def graph_overlaps(recs, fasta, band=0, max_shift=0.2, min_identity=0.0, device=0, batch=BATCH, unitigs=False, clean=None, consensus=None,
-                   trim=None, repeat=None, quality=None, weights=None, **params):
+                   trim=None, repeat=None, quality=None, weights=None, variant=None, **params):
     """Realign `recs` in batches and build the graph: (gfa text, arcs, counts, contained); with unitigs=True two more: the GFA text
     of the unitig graph and the dict of GraphSession.unitigs().  clean: None, or a dict of GraphSession.clean's parameters: the graph
     is cleaned first, both texts and the dict are those of the cleaned graph, and the dict of CLEAN_COUNTS comes last.
@@ -70,10 +74,18 @@ def graph_overlaps(recs, fasta, band=0, max_shift=0.2, min_identity=0.0, device=
     repeat: None, or a dict of RepeatSession's parameters and `penalty`: every kept record is judged on its refined copy ("repeat
     marking" in the same header) and the void ones reach neither the trimming nor the graph; without trim the graph takes the
     survivors as realigned.  The dict of REPEAT_COUNTS then comes behind the trimming's (key repeat_counts of the dict).
+    variant: None, or a dict of VariantSession's parameters: the records are judged across the variant sites first ("variant sites"
+    in the same header) and everything above is built from the ones that stay; the dict then carries `counts` (VARIANT_COUNTS),
+    `set_aside` and `judged`, which graph_overlaps fills in.
     weights: None, or with consensus (q_lo, q_hi): the consensus votes weigh the reads' own qualities (FASTQ reads; with trim, the
     trimmed reads' are the matching slices), "quality-weighted votes" in the same header."""
     with api.MinHashSearch(api.MhapParams(num_hashes=1, ordered_sketch_size=1, max_shift=max_shift, device=device)) as ms:
         tcounts = ()
+        if variant is not None:   # the survivors, as they were found: realigned again below, they give the same alignments
+            v = variants.variant_overlaps(recs, fasta, band=band, max_shift=max_shift, min_identity=min_identity, batch=batch, handle=ms,
+                                          **{k: variant[k] for k in api.VARIANT_DEFAULTS if k in variant})
+            recs = recs[v["found_rows"][v["keep"] != 0]]
+            variant.update(counts=v["counts"], set_aside=int((v["keep"] == 0).sum()), judged=len(v["keep"]))
         if repeat is not None:
             repeat = dict(repeat)
             rpenalty = repeat.pop("penalty", api.TRIM_PENALTY)
@@ -151,6 +163,8 @@ def main(argv=None):
     fastq.add_arguments(ap)
     fastq.add_weight_arguments(ap)
     repeats.add_arguments(ap, "repeat-")
+    ap.add_argument("--variant-filter", action="store_true", help="mark variant sites from the pile-up votes first and drop the overlaps whose reads disagree across them")
+    variants.add_arguments(ap, "variant-")
     a = ap.parse_args(argv)
     quality, message = fastq.parameters(a, a.consensus_fastq is not None, "--consensus-fastq")
     if message:
@@ -166,6 +180,12 @@ def main(argv=None):
         ap.error(message)
     if rp != {k: v for k, v in api.REPEAT_DEFAULTS.items() if k in rp} and not a.repeat_filter:
         ap.error("--repeat-factor, --repeat-max-cov, --repeat-min-run and --repeat-min-unique need --repeat-filter")
+    vp, message = variants.parameters(a, "variant-")
+    if message:
+        ap.error(message)
+    if vp != api.VARIANT_DEFAULTS and not a.variant_filter:
+        ap.error("--variant-min-depth, --variant-min-minor, --variant-min-pct, --variant-max-del-pct, --variant-min-diff and --variant-diff-pct need --variant-filter")
+    vp = dict(vp) if a.variant_filter else None
     if (a.trim_min_cov != 3 or a.trim_end_clip != 500 or a.trim_min_span != 2000) and not a.trim:
         ap.error("--trim-min-cov, --trim-end-clip and --trim-min-span need --trim")
     if a.trim_penalty != api.TRIM_PENALTY and not (a.trim or a.repeat_filter):
@@ -196,7 +216,7 @@ def main(argv=None):
                          consensus=dict(min_cov=a.consensus_min_cov) if a.consensus else None,
                          trim=dict(min_cov=a.trim_min_cov, end_clip=a.trim_end_clip, min_span=a.trim_min_span, penalty=a.trim_penalty) if a.trim else None,
                          repeat=dict(rp, penalty=a.trim_penalty) if a.repeat_filter else None,
-                         quality=quality if a.consensus_fastq else None, weights=weights,
+                         quality=quality if a.consensus_fastq else None, weights=weights, variant=vp,
                          max_hang=a.max_hang, int_frac_permille=int(round(a.int_frac * 1000)), min_ovlp=a.min_overlap, fuzz=a.fuzz)
     tcounts = rcounts = None
     if a.repeat_filter:
@@ -215,6 +235,8 @@ def main(argv=None):
             fh.write(text)
     else:
         sys.stdout.write(text)
+    if a.variant_filter:
+        print(api.variant_counts_line([vp["counts"][k] for k in api.VARIANT_COUNTS], vp["set_aside"], vp["judged"]), file=sys.stderr)
     if a.repeat_filter:
         print(api.repeat_counts_line([rcounts[k] for k in api.REPEAT_COUNTS]), file=sys.stderr)
     if a.trim:
