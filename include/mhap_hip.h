@@ -997,7 +997,7 @@ int mhap_consensus_quality(mhap_consensus_session* s, const mhap_quality_params*
  * mhap_correct_begin_weighted / mhap_consensus_begin_weighted are their siblings with `qualities` (n_bases bytes; NULL: the call is its
  * sibling, the session unweighted) and the weight parameters (NULL: the defaults; MHAP_E_INVALID unless 0 <= q_lo <= q_hi <= 93).  The
  * qualities go up once, one byte per base.  Every other entry point keeps its signature and, on a weighted session, follows this rule
- * through kernels of its own (correct_kernels.hip, consensus_kernels.hip over weighted_vote.hpp); mhap_correct_votes and
+ * through the weighted instantiations of the same kernels (vote_common.hpp over weighted_vote.hpp's policies); mhap_correct_votes and
  * mhap_consensus_votes return the weighted counters.  The defaults are the pair that left the fewest wrong bytes on the restatement
  * (EXPERIMENTS.md, "Quality-weighted votes").
  * Left out: qualities in the search, trimming, repeat and graph stages; qualities for called deletions; quality-aware alignment;

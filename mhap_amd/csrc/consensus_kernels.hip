@@ -1,8 +1,8 @@
 // consensus_kernels.hip — the consensus of the served unitigs (mhap_consensus_begin / _add / _run / _copy* / _quality / _votes / _free): every read
 // is placed on a unitig, aligned to the draft in a band round its place, votes as view A of the correction contract, and every draft
 // position takes the majority.  The contract is the "unitig consensus" section of include/mhap_hip.h; tests/unitig_consensus_ref.py
-// restates it.  The class rule is graph_class.hpp's (classify_kernel's), the column walk and the decision vote_common.hpp's
-// (vote_kernel's and call_kernel's), the aligner mhap_align_pairs_banded_paths, unchanged.
+// restates it.  The class rule is graph_class.hpp's (classify_kernel's), the column walk, its vote kernel, the scan of emitted lengths
+// and the decision vote_common.hpp's (the correction's), the aligner mhap_align_pairs_banded_paths, unchanged.
 //
 // add: the host finds every record's reads as mhap_graph_add does and appends the packed records (32 bytes, GItem) to one device array.
 // run, in order, all on the handle's stream:
@@ -17,12 +17,15 @@
 //                    run when a tile is above the cap, before any vote
 //   (the aligner)    the pair rows go down, through mhap_align_pairs_banded_paths over the host copy of reads and drafts, and the runs
 //                    come up again, 4 bytes each, with one VoteItem per aligned pair: view A, target the unitig, i0 = w0 + read_begin
-//   cvote_kernel     one wave per aligned pair: vote_walk, into a table of 12 planes per unitig (48 bytes per draft base)
+//   vote_kernel      vote_common.hpp's, <true, Weigh>: one wave per aligned pair over vote_walk, into a table of 12 planes per unitig
+//                    (48 bytes per draft base)
 //   ccall_kernel     one workgroup per tile, 256 positions at a time: decide() per thread, a workgroup scan of the emitted lengths; the
 //                    first launch leaves every tile's length and four counts, the host prefix-sums the lengths, the second launch writes
 //                    the bytes and the position map.  The junction after t belongs to t's tile; t < L - 1 is the unitig's L.
 // quality, on request after a run:
 //   cqual_kernel     one workgroup per tile: decide() and decide_quality() per position, the bytes' places from the position map
+// A session begun with qualities ("quality-weighted votes") runs the same kernels over weighted_vote.hpp's policies: the reads' bytes
+// vote with QualityWeight, and ccall_kernel and cqual_kernel count a draft byte with NeutralWeight.
 // Integer atomic rates behind the vote layout are not measured here either (correct_kernels.hip).
 #include <hip/hip_runtime.h>
 
@@ -34,6 +37,7 @@
 #include "graph_class.hpp"
 #include "mhap_internal.hpp"
 #include "vote_common.hpp"
+#include "vote_table.hpp"
 #include "weighted_vote.hpp"
 
 namespace mhap {
@@ -44,8 +48,6 @@ constexpr int64_t P_BIAS = (int64_t)1 << 61;   // added to a candidate p before 
 constexpr uint32_t V_TOP = 0x7FFFFFFFu;        // key 1 holds V_TOP - vertex, so that the smallest vertex is the greatest key
 enum { HOW_MEMBER = 0, HOW_RECORD = 1, HOW_UNPLACED = 2 };
 enum { CC_MEMBERS = 0, CC_BY_RECORD, CC_UNPLACED, CC_ALIGNED, CC_NO_ALIGNMENT, CC_BASES_IN, CC_BASES_OUT, CC_SUB, CC_DEL, CC_INS, CC_LOW };
-
-unsigned blocks256(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 __device__ inline int64_t min64(int64_t a, int64_t b) { return a < b ? a : b; }
 __device__ inline int64_t max64(int64_t a, int64_t b) { return a > b ? a : b; }
@@ -147,51 +149,38 @@ __global__ __launch_bounds__(256) void guard_kernel(int64_t nr, const int64_t* _
     if (utile[k] + j < n_tiles) atomicAdd(tile_reads + utile[k] + j, 1u);
 }
 
-__global__ __launch_bounds__(64) void cvote_kernel(const uint8_t* __restrict__ bases, const VoteItem* __restrict__ items,
-                                                   const uint32_t* __restrict__ ops, uint32_t* __restrict__ table) {
-  const VoteItem it = items[blockIdx.x];
-  vote_walk(bases, it, ops, table);
-}
-
-// tile_off == nullptr: count only (tile_len, tile_counts); else write the bytes at tile_off[tile] and the position map
+// tile_off == nullptr: count only (tile_len, tile_counts); else write the bytes at tile_off[tile] and the position map.
+// Weigh: what a draft byte weighs — UnitWeight, or in a weighted session ("quality-weighted votes" in include/mhap_hip.h) the
+// NeutralWeight, because a draft byte has no single quality.
+template <class Weigh>
 __global__ __launch_bounds__(CK_T) void ccall_kernel(const uint8_t* __restrict__ draft, int64_t nu, const int64_t* __restrict__ u_len,
                                                      const int64_t* __restrict__ ubase, const int64_t* __restrict__ utile,
                                                      const uint32_t* __restrict__ table, int min_cov, int32_t* __restrict__ tile_len,
                                                      int32_t* __restrict__ tile_counts, const int64_t* __restrict__ tile_off,
                                                      const int64_t* __restrict__ out_offsets, uint8_t* __restrict__ out, int64_t* __restrict__ posmap) {
-  __shared__ int wave_sum[CK_T / 64];
+  const Weigh own_weight{};
   __shared__ int acc[4];   // n_sub, n_del, n_ins, n_low
   const int64_t tile = blockIdx.x;
   const int64_t k = last_at_or_before(utile, nu, tile);   // (every unitig has at least one tile)
   const int64_t L = u_len[k], t_begin = (tile - utile[k]) * CT, t_end = min64(L, t_begin + CT);
   const uint8_t* own = draft + ubase[k];
   const uint32_t* w = table + (int64_t)CK_WORDS * ubase[k];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   if (tid < 4) acc[tid] = 0;
   int64_t written = 0;
   int my[4] = {0, 0, 0, 0};
   for (int64_t t0 = t_begin; t0 < t_end; t0 += CK_T) {
     const int64_t t = t0 + tid;
     Decision D{0, {0, 0, 0, 0, 0}, 0, 0, 0, 0};
-    if (t < t_end) D = decide(w, L, t, own[t], min_cov);
+    if (t < t_end) D = decide<Weigh::neutral>(w, L, t, own[t], own_weight(ubase[k] + t), min_cov);
     my[0] += D.sub; my[1] += D.del; my[2] += D.ins; my[3] += D.low;
-    int incl = D.n;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int u = __shfl_up(incl, d);
-      if (lane >= d) incl += u;
-    }
-    __syncthreads();
-    if (lane == 63) wave_sum[wave] = incl;
-    __syncthreads();
-    int before = 0, chunk = 0;
-    for (int u = 0; u < CK_T / 64; u++) { if (u < wave) before += wave_sum[u]; chunk += wave_sum[u]; }
+    const EmitScan sc = scan_emitted(D.n);
     if (tile_off && t < t_end) {
-      const int64_t at = tile_off[tile] + written + before + (incl - D.n);
+      const int64_t at = tile_off[tile] + written + sc.before + (sc.incl - D.n);
       posmap[ubase[k] + t] = at - out_offsets[k];
       for (int u = 0; u < D.n; u++) out[at + u] = D.bytes[u];
     }
-    written += chunk;
+    written += sc.tile;
   }
   __syncthreads();
   for (int u = 0; u < 4; u++) if (my[u]) atomicAdd(&acc[u], my[u]);
@@ -203,15 +192,18 @@ __global__ __launch_bounds__(CK_T) void ccall_kernel(const uint8_t* __restrict__
 }
 
 // The quality pass of mhap_consensus_quality, over the table, the offsets and the position map of a completed run: one workgroup per
-// tile as in ccall_kernel, decide() and decide_quality() per position.  A kernel of its own, so that ccall_kernel stays the code it is;
+// tile as in ccall_kernel, decide() and decide_quality() per position.  A kernel of its own, so that ccall_kernel carries no quality;
 // it needs no scan, because the run's position map already says where a position's bytes lie.  One writer per quality byte; the
 // workgroup's histogram lives in LDS and leaves by one 64-bit atomic per non-empty bin.
+template <class Weigh>
 __global__ __launch_bounds__(CK_T) void cqual_kernel(const uint8_t* __restrict__ draft, int64_t nu, const int64_t* __restrict__ u_len,
                                                      const int64_t* __restrict__ ubase, const int64_t* __restrict__ utile,
                                                      const uint32_t* __restrict__ table, int min_cov, int per_vote, int cap,
                                                      const int64_t* __restrict__ out_offsets, const int64_t* __restrict__ posmap,
                                                      uint8_t* __restrict__ quals, unsigned long long* __restrict__ hist) {
   __shared__ unsigned long long bins[QUAL_BINS];
+  constexpr int U = Weigh::neutral;
+  const Weigh own_weight{};
   const int64_t tile = blockIdx.x;
   const int64_t k = last_at_or_before(utile, nu, tile);
   const int64_t L = u_len[k], t_begin = (tile - utile[k]) * CT, t_end = min64(L, t_begin + CT);
@@ -222,97 +214,10 @@ __global__ __launch_bounds__(CK_T) void cqual_kernel(const uint8_t* __restrict__
   if (tid < QUAL_BINS) bins[tid] = 0ull;
   __syncthreads();
   for (int64_t t = t_begin + tid; t < t_end; t += CK_T) {
-    const Decision D = decide(w, L, t, own[t], min_cov);
+    const int own_w = own_weight(ubase[k] + t);
+    const Decision D = decide<U>(w, L, t, own[t], own_w, min_cov);
     uint8_t q[1 + CK_KI] = {0, 0, 0, 0, 0};
-    decide_quality(w, L, t, own[t], D, per_vote, cap, q);
-    const int64_t at = out_offsets[k] + posmap[ubase[k] + t];
-    for (int u = 0; u < D.n; u++)
-      if (at + u < o_end) {   // (the map is that of this table and this min_cov: always)
-        quals[at + u] = q[u];
-        atomicAdd(&bins[q[u]], 1ull);
-      }
-  }
-  __syncthreads();
-  if (tid < QUAL_BINS && bins[tid]) atomicAdd(hist + tid, bins[tid]);
-}
-
-// The three kernels of a weighted session ("quality-weighted votes" in include/mhap_hip.h): the schedules of cvote_kernel, ccall_kernel
-// and cqual_kernel over weighted_vote.hpp's walk, decision and qualities.  quals: one Phred byte per base of the reads (the drafts that
-// follow them in `bases` are targets only); a draft byte has no single quality, so own counts with the neutral weight.
-__global__ __launch_bounds__(64) void wcvote_kernel(const uint8_t* __restrict__ bases, const uint8_t* __restrict__ quals, Weights W,
-                                                    const VoteItem* __restrict__ items, const uint32_t* __restrict__ ops,
-                                                    uint32_t* __restrict__ table) {
-  const VoteItem it = items[blockIdx.x];
-  vote_walk_weighted(bases, quals, W, it, ops, table);
-}
-
-__global__ __launch_bounds__(CK_T) void wccall_kernel(const uint8_t* __restrict__ draft, int64_t nu, const int64_t* __restrict__ u_len,
-                                                      const int64_t* __restrict__ ubase, const int64_t* __restrict__ utile,
-                                                      const uint32_t* __restrict__ table, int min_cov, int32_t* __restrict__ tile_len,
-                                                      int32_t* __restrict__ tile_counts, const int64_t* __restrict__ tile_off,
-                                                      const int64_t* __restrict__ out_offsets, uint8_t* __restrict__ out, int64_t* __restrict__ posmap) {
-  __shared__ int wave_sum[CK_T / 64];
-  __shared__ int acc[4];   // n_sub, n_del, n_ins, n_low
-  const int64_t tile = blockIdx.x;
-  const int64_t k = last_at_or_before(utile, nu, tile);
-  const int64_t L = u_len[k], t_begin = (tile - utile[k]) * CT, t_end = min64(L, t_begin + CT);
-  const uint8_t* own = draft + ubase[k];
-  const uint32_t* w = table + (int64_t)CK_WORDS * ubase[k];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid < 4) acc[tid] = 0;
-  int64_t written = 0;
-  int my[4] = {0, 0, 0, 0};
-  for (int64_t t0 = t_begin; t0 < t_end; t0 += CK_T) {
-    const int64_t t = t0 + tid;
-    Decision D{0, {0, 0, 0, 0, 0}, 0, 0, 0, 0};
-    if (t < t_end) D = decide_weighted(w, L, t, own[t], W_NEUTRAL, min_cov);
-    my[0] += D.sub; my[1] += D.del; my[2] += D.ins; my[3] += D.low;
-    int incl = D.n;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int u = __shfl_up(incl, d);
-      if (lane >= d) incl += u;
-    }
-    __syncthreads();
-    if (lane == 63) wave_sum[wave] = incl;
-    __syncthreads();
-    int before = 0, chunk = 0;
-    for (int u = 0; u < CK_T / 64; u++) { if (u < wave) before += wave_sum[u]; chunk += wave_sum[u]; }
-    if (tile_off && t < t_end) {
-      const int64_t at = tile_off[tile] + written + before + (incl - D.n);
-      posmap[ubase[k] + t] = at - out_offsets[k];
-      for (int u = 0; u < D.n; u++) out[at + u] = D.bytes[u];
-    }
-    written += chunk;
-  }
-  __syncthreads();
-  for (int u = 0; u < 4; u++) if (my[u]) atomicAdd(&acc[u], my[u]);
-  __syncthreads();
-  if (tid == 0 && !tile_off) {
-    tile_len[tile] = (int32_t)written;
-    for (int u = 0; u < 4; u++) tile_counts[4 * tile + u] = acc[u];
-  }
-}
-
-__global__ __launch_bounds__(CK_T) void wcqual_kernel(const uint8_t* __restrict__ draft, int64_t nu, const int64_t* __restrict__ u_len,
-                                                      const int64_t* __restrict__ ubase, const int64_t* __restrict__ utile,
-                                                      const uint32_t* __restrict__ table, int min_cov, int per_vote, int cap,
-                                                      const int64_t* __restrict__ out_offsets, const int64_t* __restrict__ posmap,
-                                                      uint8_t* __restrict__ quals, unsigned long long* __restrict__ hist) {
-  __shared__ unsigned long long bins[QUAL_BINS];
-  const int64_t tile = blockIdx.x;
-  const int64_t k = last_at_or_before(utile, nu, tile);
-  const int64_t L = u_len[k], t_begin = (tile - utile[k]) * CT, t_end = min64(L, t_begin + CT);
-  const uint8_t* own = draft + ubase[k];
-  const uint32_t* w = table + (int64_t)CK_WORDS * ubase[k];
-  const int64_t o_end = out_offsets[k + 1];
-  const int tid = threadIdx.x;
-  if (tid < QUAL_BINS) bins[tid] = 0ull;
-  __syncthreads();
-  for (int64_t t = t_begin + tid; t < t_end; t += CK_T) {
-    const Decision D = decide_weighted(w, L, t, own[t], W_NEUTRAL, min_cov);
-    uint8_t q[1 + CK_KI] = {0, 0, 0, 0, 0};
-    decide_quality_weighted(w, L, t, own[t], W_NEUTRAL, D, per_vote, cap, q);
+    decide_quality<U>(w, L, t, own[t], own_w, D, per_vote, cap, q);
     const int64_t at = out_offsets[k] + posmap[ubase[k] + t];
     for (int u = 0; u < D.n; u++)
       if (at + u < o_end) {   // (the map is that of this table and this min_cov: always)
@@ -596,12 +501,13 @@ extern "C" int mhap_consensus_run(mhap_consensus_session* s, int64_t* counts) {
     up(s->ops, paths->ops.data(), 4 * paths->ops.size());
     up(s->vitems, vitems.data(), sizeof(VoteItem) * vitems.size());
     if (e == hipSuccess) {
+      const dim3 grid((unsigned)vitems.size()), wave(64);
       if (s->weighted)
-        hipLaunchKernelGGL(wcvote_kernel, dim3((unsigned)vitems.size()), dim3(64), 0, v.stream, s->bases.as<uint8_t>(), s->in_quals.as<uint8_t>(),
-                           s->W, s->vitems.as<VoteItem>(), s->ops.as<uint32_t>(), s->table.as<uint32_t>());
+        hipLaunchKernelGGL((vote_kernel<true, QualityWeight>), grid, wave, 0, v.stream, s->bases.as<uint8_t>(), s->vitems.as<VoteItem>(),
+                           s->ops.as<uint32_t>(), s->table.as<uint32_t>(), QualityWeight{s->in_quals.as<uint8_t>(), s->W});
       else
-        hipLaunchKernelGGL(cvote_kernel, dim3((unsigned)vitems.size()), dim3(64), 0, v.stream, s->bases.as<uint8_t>(), s->vitems.as<VoteItem>(),
-                           s->ops.as<uint32_t>(), s->table.as<uint32_t>());
+        hipLaunchKernelGGL((vote_kernel<true, UnitWeight>), grid, wave, 0, v.stream, s->bases.as<uint8_t>(), s->vitems.as<VoteItem>(),
+                           s->ops.as<uint32_t>(), s->table.as<uint32_t>(), UnitWeight());
       e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(v.stream);   // (the runs and the items are the host's until here)
@@ -615,7 +521,7 @@ extern "C" int mhap_consensus_run(mhap_consensus_session* s, int64_t* counts) {
   std::vector<int64_t> tile_off((size_t)n_tiles), out_offsets((size_t)nu + 1, 0), stats((size_t)nu * 6, 0);
   const uint8_t* draft = s->bases.as<uint8_t>() + s->n_bases;
   if (n_tiles > 0) {
-    hipLaunchKernelGGL(s->weighted ? wccall_kernel : ccall_kernel, dim3((unsigned)n_tiles), dim3(CK_T), 0, v.stream, draft, nu, s->d_ulen.as<int64_t>(), s->d_ubase.as<int64_t>(),
+    hipLaunchKernelGGL(s->weighted ? ccall_kernel<NeutralWeight> : ccall_kernel<UnitWeight>, dim3((unsigned)n_tiles), dim3(CK_T), 0, v.stream, draft, nu, s->d_ulen.as<int64_t>(), s->d_ubase.as<int64_t>(),
                        s->d_utile.as<int64_t>(), s->table.as<uint32_t>(), (int)s->min_cov, s->tile_len.as<int32_t>(), s->tile_counts.as<int32_t>(),
                        (const int64_t*)nullptr, (const int64_t*)nullptr, (uint8_t*)nullptr, (int64_t*)nullptr);
     if ((e = hipGetLastError()) != hipSuccess) return fail("launch");
@@ -643,7 +549,7 @@ extern "C" int mhap_consensus_run(mhap_consensus_session* s, int64_t* counts) {
     up(s->tile_off, tile_off.data(), 8 * (size_t)n_tiles);
     up(s->d_outoff, out_offsets.data(), 8 * (size_t)(nu + 1));
     if (e != hipSuccess) return fail("upload");
-    hipLaunchKernelGGL(s->weighted ? wccall_kernel : ccall_kernel, dim3((unsigned)n_tiles), dim3(CK_T), 0, v.stream, draft, nu, s->d_ulen.as<int64_t>(), s->d_ubase.as<int64_t>(),
+    hipLaunchKernelGGL(s->weighted ? ccall_kernel<NeutralWeight> : ccall_kernel<UnitWeight>, dim3((unsigned)n_tiles), dim3(CK_T), 0, v.stream, draft, nu, s->d_ulen.as<int64_t>(), s->d_ubase.as<int64_t>(),
                        s->d_utile.as<int64_t>(), s->table.as<uint32_t>(), (int)s->min_cov, s->tile_len.as<int32_t>(), s->tile_counts.as<int32_t>(),
                        s->tile_off.as<int64_t>(), s->d_outoff.as<int64_t>(), s->out.as<uint8_t>(), s->posmap.as<int64_t>());
     if ((e = hipGetLastError()) != hipSuccess) return fail("launch");
@@ -728,7 +634,7 @@ extern "C" int mhap_consensus_quality(mhap_consensus_session* s, const mhap_qual
   hipError_t e;
   if ((e = s->quals.ensure((size_t)s->out_bytes)) != hipSuccess || (e = s->hist.ensure(8 * QUAL_BINS)) != hipSuccess) return hip_fail(v, who, "hipMalloc of the quality bytes", e);
   if ((e = hipMemsetAsync(s->hist.p, 0, 8 * QUAL_BINS, v.stream)) != hipSuccess) return hip_fail(v, who, "memset", e);
-  hipLaunchKernelGGL(s->weighted ? wcqual_kernel : cqual_kernel, dim3((unsigned)n_tiles), dim3(CK_T), 0, v.stream, s->bases.as<uint8_t>() + s->n_bases, s->n_unitigs,
+  hipLaunchKernelGGL(s->weighted ? cqual_kernel<NeutralWeight> : cqual_kernel<UnitWeight>, dim3((unsigned)n_tiles), dim3(CK_T), 0, v.stream, s->bases.as<uint8_t>() + s->n_bases, s->n_unitigs,
                      s->d_ulen.as<int64_t>(), s->d_ubase.as<int64_t>(), s->d_utile.as<int64_t>(), s->table.as<uint32_t>(), (int)s->min_cov,
                      (int)p.per_vote, (int)p.cap, s->d_outoff.as<int64_t>(), s->posmap.as<int64_t>(), s->quals.as<uint8_t>(),
                      s->hist.as<unsigned long long>());
@@ -760,18 +666,7 @@ extern "C" int mhap_consensus_votes(mhap_consensus_session* s, int64_t unitig, u
   const int64_t len = s->u_len[(size_t)unitig];
   if (len == 0) return MHAP_OK;
   if (!counters) { *v.err = std::string(who) + ": null argument"; return MHAP_E_INVALID; }
-  (void)hipSetDevice(v.device);
-  std::vector<uint32_t> w((size_t)len * CK_WORDS);
-  hipError_t e;
-  if ((e = hipMemcpyAsync(w.data(), s->table.as<uint32_t>() + (int64_t)CK_WORDS * s->ubase[(size_t)unitig], w.size() * 4, hipMemcpyDeviceToHost, v.stream)) != hipSuccess ||
-      (e = hipStreamSynchronize(v.stream)) != hipSuccess) return hip_fail(v, who, "download", e);
-  for (int64_t t = 0; t < len; t++)
-    for (int p = 0; p < CK_WORDS; p++) {
-      const uint32_t x = w[(size_t)(p * len + t)];
-      counters[24 * t + 2 * p] = (uint16_t)(x & 0xFFFFu);
-      counters[24 * t + 2 * p + 1] = (uint16_t)(x >> 16);
-    }
-  return MHAP_OK;
+  return copy_votes(v, who, s->table.as<uint32_t>(), (int64_t)CK_WORDS * s->ubase[(size_t)unitig], len, CK_WORDS, counters);
 }
 
 extern "C" void mhap_consensus_free(mhap_consensus_session* s) {

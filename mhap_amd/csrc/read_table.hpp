@@ -3,7 +3,8 @@
 // 32-byte item the kernels read, the uploads an add has queued, and the begin / apply / free that "read trimming"
 // (trim_kernels.hip), "repeat marking" (repeat_kernels.hip) and "overlap selection" (select_kernels.hip) share.  The string graph's
 // session (graph_kernels.hip) sits on the table too, and the unitig consensus looks its reads up through that session; the read
-// correction (correct_kernels.hip) keeps a table of its own shape and shares the lookup.
+// correction (correct_kernels.hip) and the variant sites (variant_kernels.hip), which keep the bases and a vote table, sit on
+// vote_table.hpp's VoteTable and share the lookup.
 //
 // Two checks of a record, kept apart: find_record_reads (both reads are among the reads, and with the lengths the record gives)
 // is every session's; range_ok (the aligned ends lie inside the reads) is applied by the trimming, the repeat marking and the

@@ -4,8 +4,9 @@
 //
 // The vote table.  The first three planes of the correction's (correct_kernels.hip): word p of position t of a read of length L that
 // starts at table position v is table[3 v + p L + t], word 0 base A | C, word 1 base G | T, word 2 del | span, 16 bits each: 12 bytes
-// per base.  vvote_kernel is one wave per accepted view over vote_common.hpp's vote_walk with the insertion slots compiled out; the
-// adds are the correction's 32-bit atomics on 16-bit halves and the host's cap on accepted views keeps a half from carrying.
+// per base.  The votes are cast by vote_common.hpp's vote_kernel<false, UnitWeight>, one wave per accepted view over vote_walk with
+// the insertion slots compiled out; the adds are the correction's 32-bit atomics on 16-bit halves and the host's cap on accepted
+// views keeps a half from carrying.  The host side of the table is vote_table.hpp's VoteTable, as the correction's.
 //
 // site_kernel: one workgroup of 256 per read, longest first, over tiles of MHAP_VARIANT_TILE positions in the order of
 // pileup_common.hpp's tiles (load j, lane): three coalesced word loads and the own byte per position, one byte stored.
@@ -20,14 +21,13 @@
 
 #include <numeric>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "device_common.hpp"
 #include "mhap_internal.hpp"
 #include "pileup_common.hpp"
-#include "read_table.hpp"
 #include "vote_common.hpp"
+#include "vote_table.hpp"
 
 namespace mhap {
 namespace {
@@ -49,12 +49,6 @@ bool variant_params_ok(const mhap_variant_params& p, const char* who, std::strin
         std::to_string(p.min_depth) + ", " + std::to_string(p.min_minor) + ", " + std::to_string(p.min_pct) + ", " + std::to_string(p.max_del_pct) + ", " +
         std::to_string(p.min_diff) + ", " + std::to_string(p.diff_pct) + ")";
   return false;
-}
-
-__global__ __launch_bounds__(64) void vvote_kernel(const uint8_t* __restrict__ bases, const VoteItem* __restrict__ items,
-                                                   const uint32_t* __restrict__ ops, uint32_t* __restrict__ table) {
-  const VoteItem it = items[blockIdx.x];
-  vote_walk<true, false>(bases, it, ops, table);
 }
 
 // what the rule says of one position
@@ -181,53 +175,20 @@ __global__ __launch_bounds__(64) void judge_kernel(const uint8_t* __restrict__ b
 
 using namespace mhap;
 
-struct mhap_variant_session {
+// the vote table and the reads are VoteTable's; the session's own: the order of the site kernel, the sites and the judge's buffers
+struct mhap_variant_session : VoteTable {
   static constexpr const char* finish_name = "mhap_variant_finish";
   static constexpr int unfinished_rc = MHAP_E_INVALID;
-  mhap_handle* h = nullptr;
-  int64_t n_reads = 0, n_bases = 0, n_pos = 0;          // n_pos: bases of the reads = positions of the table
-  std::vector<int64_t> offsets, pos;                    // read r: its bytes in the bases, its first table position
-  std::vector<int32_t> lengths, order;                  // order: the reads longest first
-  std::unordered_map<int64_t, int64_t> by_id;
-  std::vector<uint32_t> views;                          // accepted views per target
-  int64_t accepted = 0, skipped = 0, n_sites = 0;
+  std::vector<int32_t> order;                           // the reads longest first
+  int64_t accepted = 0, n_sites = 0;
   VParams P{};
   bool finished = false;
-  DevBuf bases, table, read_off, read_pos, read_len, d_order, items, ops, site, cnt, rows, soff, list, jitems, tallies, keep;
+  DevBuf d_order, site, cnt, rows, soff, list, jitems, tallies, keep;
   void release() {
-    for (DevBuf* b : {&bases, &table, &read_off, &read_pos, &read_len, &d_order, &items, &ops, &site, &cnt, &rows, &soff, &list, &jitems, &tallies, &keep}) b->release();
+    release_table();
+    for (DevBuf* b : {&d_order, &site, &cnt, &rows, &soff, &list, &jitems, &tallies, &keep}) b->release();
   }
 };
-
-namespace {
-
-// What add and apply check of record q before they look at its runs: the paths are those of n records, both reads are among the
-// reads with the lengths the record gives, and the runs spell the record.  walk false with MHAP_OK: a record that takes no part.
-int check_record(mhap_variant_session* s, const HandleView& v, const char* who, int64_t q, const mhap_record& r, const mhap_align_paths* paths,
-                 int64_t (&idx)[2], int64_t& i0, int64_t& j0, bool& walk) {
-  const int64_t o0 = paths->offsets[(size_t)q], o1 = paths->offsets[(size_t)q + 1];
-  walk = false;
-  if (o1 == o0 || r.from_id == r.to_id) return MHAP_OK;
-  if (!find_record_reads(s->by_id, s->lengths.data(), who, q, r, idx, *v.err)) return MHAP_E_INVALID;
-  std::string what;
-  if (!path_spells_record(r, paths->ops, o0, o1, i0, j0, what)) {
-    *v.err = std::string(who) + ": record " + std::to_string(q) + " " + what;
-    return MHAP_E_INVALID;
-  }
-  walk = true;
-  return MHAP_OK;
-}
-
-int check_call(const HandleView& v, const char* who, const mhap_record* recs, int64_t n, const mhap_align_paths* paths, bool args_ok) {
-  if (n < 0 || !paths || !args_ok || (n > 0 && !recs)) { *v.err = std::string(who) + ": null or negative argument"; return MHAP_E_INVALID; }
-  if ((int64_t)paths->offsets.size() - 1 != n) {
-    *v.err = std::string(who) + ": the paths are those of " + std::to_string((int64_t)paths->offsets.size() - 1) + " records, not of " + std::to_string(n);
-    return MHAP_E_INVALID;
-  }
-  return MHAP_OK;
-}
-
-}  // namespace
 
 extern "C" void mhap_variant_default_params(mhap_variant_params* p) {
   if (!p) return;
@@ -240,54 +201,26 @@ extern "C" int mhap_variant_begin(mhap_handle* h, const uint8_t* bases, int64_t 
   if (session) *session = nullptr;
   if (!h) return MHAP_E_INVALID;
   HandleView v = handle_view(h);
-  if (!session || n_bases < 0 || n_reads < 0 || (n_bases > 0 && !bases) || (n_reads > 0 && (!read_ids || !offsets || !lengths))) {
-    *v.err = std::string(who) + ": null or negative argument";
-    return MHAP_E_INVALID;
-  }
+  if (!VoteTable::args_ok(v, who, session, bases, n_bases, read_ids, offsets, lengths, n_reads)) return MHAP_E_INVALID;
   if (n_reads > INT32_MAX) { *v.err = std::string(who) + ": more than 2^31 - 1 reads"; return MHAP_E_INVALID; }
-  for (int64_t i = 0; i < n_reads; i++)
-    if (offsets[i] < 0 || lengths[i] < 0 || offsets[i] > n_bases - lengths[i]) {
-      *v.err = std::string(who) + ": read " + std::to_string(i) + " lies outside the " + std::to_string(n_bases) + " bases";
-      return MHAP_E_INVALID;
-    }
+  if (!VoteTable::reads_inside(v, who, n_bases, offsets, lengths, n_reads)) return MHAP_E_INVALID;
   mhap_variant_params p;
   mhap_variant_default_params(&p);
   if (params) p = *params;
   if (!variant_params_ok(p, who, *v.err)) return MHAP_E_INVALID;
   mhap_variant_session* s = new mhap_variant_session();
-  s->h = h; s->n_reads = n_reads; s->n_bases = n_bases;
   s->P = VParams{p.min_depth, p.min_minor, p.min_pct, p.max_del_pct, p.min_diff, p.diff_pct};
-  s->offsets.assign(offsets, offsets + n_reads);
-  s->lengths.assign(lengths, lengths + n_reads);
-  s->pos.resize((size_t)n_reads);
-  s->views.assign((size_t)n_reads, 0u);
-  s->by_id.reserve((size_t)n_reads * 2);
-  for (int64_t i = 0; i < n_reads; i++) {
-    s->by_id.emplace(read_ids[i], i);   // (the first read of an id wins, as in mhap_realign_plan)
-    s->pos[(size_t)i] = s->n_pos;
-    s->n_pos += lengths[i];
-  }
   s->order.resize((size_t)n_reads);   // the long workgroups start early
   std::iota(s->order.begin(), s->order.end(), 0);
   std::stable_sort(s->order.begin(), s->order.end(), [&](int32_t a, int32_t b) { return lengths[a] > lengths[b]; });
   (void)hipSetDevice(v.device);
-  hipError_t e = hipSuccess;
-  const size_t np = (size_t)std::max<int64_t>(s->n_pos, 1), table_bytes = np * VK_WORDS * 4, nr = (size_t)std::max<int64_t>(n_reads, 1);
-  auto up = [&](DevBuf& b, const void* src, size_t bytes) {
-    if (e == hipSuccess) e = b.ensure(std::max<size_t>(bytes, 1));
-    if (e == hipSuccess && bytes > 0) e = hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, v.stream);
-  };
-  up(s->bases, bases, (size_t)n_bases);
-  up(s->read_off, s->offsets.data(), 8 * (size_t)n_reads);
-  up(s->read_pos, s->pos.data(), 8 * (size_t)n_reads);
-  up(s->read_len, s->lengths.data(), 4 * (size_t)n_reads);
-  up(s->d_order, s->order.data(), 4 * (size_t)n_reads);
+  hipError_t e = s->begin_table(v, h, VK_WORDS, bases, n_bases, read_ids, offsets, lengths, n_reads);
+  const size_t np = (size_t)std::max<int64_t>(s->n_pos, 1), nr = (size_t)std::max<int64_t>(n_reads, 1);
+  VoteTable::upload(v, e, s->d_order, s->order.data(), 4 * (size_t)n_reads);
   if (e == hipSuccess) e = s->site.ensure(np);
   if (e == hipSuccess) e = s->cnt.ensure(4 * nr);
   if (e == hipSuccess) e = s->rows.ensure(8 * nr);
   if (e == hipSuccess) e = s->soff.ensure(8 * (nr + 1));
-  if (e == hipSuccess) e = s->table.ensure(table_bytes);
-  if (e == hipSuccess) e = hipMemsetAsync(s->table.p, 0, table_bytes, v.stream);
   if (e == hipSuccess) e = hipStreamSynchronize(v.stream);
   if (e != hipSuccess) {
     s->release();
@@ -306,72 +239,18 @@ extern "C" int mhap_variant_add(mhap_variant_session* s, const mhap_record* recs
   if (rc != MHAP_OK) return rc;
   if (s->finished) { *v.err = std::string(who) + ": mhap_variant_finish has completed, and its sites are those of the votes before it"; return MHAP_E_INVALID; }
   std::vector<VoteItem> items;
-  std::vector<int64_t> accepted;   // the targets of the accepted views, to take back when a later record is refused
-  int64_t skipped = 0;
-  for (int64_t q = 0; q < n; q++) {
-    const mhap_record& r = recs[q];
-    int64_t idx[2], i0, j0;
-    bool walk;
-    if ((rc = check_record(s, v, who, q, r, paths, idx, i0, j0, walk)) != MHAP_OK) {
-      for (int64_t t : accepted) s->views[(size_t)t] -= 1;
-      return rc;
-    }
-    if (!walk) continue;
-    const int64_t o0 = paths->offsets[(size_t)q], o1 = paths->offsets[(size_t)q + 1];
-    for (int view = 0; view < 2; view++) {
-      const int64_t target = idx[view];
-      if (s->views[(size_t)target] >= CK_CAP) { skipped++; continue; }
-      s->views[(size_t)target] += 1;
-      accepted.push_back(target);
-      VoteItem it{};
-      it.a_off = s->offsets[(size_t)idx[0]]; it.b_off = s->offsets[(size_t)idx[1]];
-      it.v_words = (int64_t)VK_WORDS * s->pos[(size_t)target];
-      it.ops_off = o0; it.alen = r.alen; it.blen = r.blen; it.i0 = (int32_t)i0; it.j0 = (int32_t)j0;
-      it.n_ops = (int32_t)(o1 - o0); it.view = view; it.rc = r.to_rc != 0 ? 1 : 0;
-      items.push_back(it);
-    }
-  }
-  s->skipped += skipped;
+  if ((rc = s->build_items(v, who, recs, n, paths, nullptr, CK_CAP, items)) != MHAP_OK) return rc;
   s->accepted += (int64_t)items.size();
   if (items.empty()) return MHAP_OK;
-  (void)hipSetDevice(v.device);
-  hipError_t e;
-  constexpr size_t CHUNK = (size_t)1 << 20;   // a grid of at most 2^20 views at a time, as the correction's
-  if ((e = s->ops.ensure(4 * paths->ops.size())) != hipSuccess) return hip_fail(v, who, "hipMalloc of the runs", e);
-  if ((e = s->items.ensure(sizeof(VoteItem) * std::min(items.size(), CHUNK))) != hipSuccess) return hip_fail(v, who, "hipMalloc", e);
-  if ((e = hipMemcpyAsync(s->ops.p, paths->ops.data(), 4 * paths->ops.size(), hipMemcpyHostToDevice, v.stream)) != hipSuccess) return hip_fail(v, who, "upload", e);
-  for (size_t g0 = 0; g0 < items.size(); g0 += CHUNK) {
-    const size_t c = std::min(CHUNK, items.size() - g0);
-    if ((e = hipMemcpyAsync(s->items.p, items.data() + g0, sizeof(VoteItem) * c, hipMemcpyHostToDevice, v.stream)) != hipSuccess) return hip_fail(v, who, "upload", e);
-    hipLaunchKernelGGL(vvote_kernel, dim3((unsigned)c), dim3(64), 0, v.stream, s->bases.as<uint8_t>(), s->items.as<VoteItem>(), s->ops.as<uint32_t>(),
-                       s->table.as<uint32_t>());
-    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(v, who, "launch", e);
-    if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return hip_fail(v, who, "kernel", e);   // (items is reused by the next chunk)
-  }
-  return MHAP_OK;
+  return s->cast_votes(v, who, paths, items, [&](unsigned c) {
+    hipLaunchKernelGGL((vote_kernel<false, UnitWeight>), dim3(c), dim3(64), 0, v.stream, s->bases.as<uint8_t>(), s->items.as<VoteItem>(),
+                       s->ops.as<uint32_t>(), s->table.as<uint32_t>(), UnitWeight());
+  });
 }
 
 extern "C" int mhap_variant_votes(mhap_variant_session* s, int64_t read_index, uint16_t* counters) {
-  const char* who = "mhap_variant_votes";
   if (!s) return MHAP_E_INVALID;
-  HandleView v = handle_view(s->h);
-  if (read_index < 0 || read_index >= s->n_reads) { *v.err = std::string(who) + ": read " + std::to_string(read_index) + " is not among the " + std::to_string(s->n_reads) + " reads"; return MHAP_E_INVALID; }
-  const int64_t len = s->lengths[(size_t)read_index];
-  if (len == 0) return MHAP_OK;
-  if (!counters) { *v.err = std::string(who) + ": null argument"; return MHAP_E_INVALID; }
-  (void)hipSetDevice(v.device);
-  std::vector<uint32_t> w((size_t)len * VK_WORDS);
-  hipError_t e;
-  if ((e = hipMemcpyAsync(w.data(), s->table.as<uint32_t>() + (int64_t)VK_WORDS * s->pos[(size_t)read_index], w.size() * 4, hipMemcpyDeviceToHost,
-                          v.stream)) != hipSuccess) return hip_fail(v, who, "download", e);
-  if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return hip_fail(v, who, "download", e);
-  for (int64_t t = 0; t < len; t++)
-    for (int p = 0; p < VK_WORDS; p++) {
-      const uint32_t x = w[(size_t)(p * len + t)];
-      counters[6 * t + 2 * p] = (uint16_t)(x & 0xFFFFu);
-      counters[6 * t + 2 * p + 1] = (uint16_t)(x >> 16);
-    }
-  return MHAP_OK;
+  return s->read_votes("mhap_variant_votes", read_index, counters);
 }
 
 extern "C" int mhap_variant_finish(mhap_variant_session* s, int64_t* counts) {
@@ -449,13 +328,10 @@ extern "C" int mhap_variant_apply(mhap_variant_session* s, const mhap_record* re
     const mhap_record& r = recs[q];
     int64_t idx[2], i0, j0;
     bool walk;
-    if ((rc = check_record(s, v, who, q, r, paths, idx, i0, j0, walk)) != MHAP_OK) return rc;
+    if ((rc = s->check_record(v, who, q, r, paths, idx, i0, j0, walk)) != MHAP_OK) return rc;
     JudgeItem J{};   // (a record that takes no part: no runs, no column, four zeros and keep = 1)
     if (walk) {
-      const int64_t o0 = paths->offsets[(size_t)q], o1 = paths->offsets[(size_t)q + 1];
-      J.it.a_off = s->offsets[(size_t)idx[0]]; J.it.b_off = s->offsets[(size_t)idx[1]];
-      J.it.ops_off = o0; J.it.alen = r.alen; J.it.blen = r.blen; J.it.i0 = (int32_t)i0; J.it.j0 = (int32_t)j0;
-      J.it.n_ops = (int32_t)(o1 - o0); J.it.rc = r.to_rc != 0 ? 1 : 0;
+      J.it = s->item_of(r, paths, q, idx, i0, j0);
       J.site_a = s->pos[(size_t)idx[0]]; J.site_b = s->pos[(size_t)idx[1]];
     }
     items[(size_t)q] = J;

@@ -1,6 +1,8 @@
-// vote_common.hpp — what the pile-up votes of read correction (correct_kernels.hip) and of the unitig consensus (consensus_kernels.hip)
-// share: a view's item, the walk over the columns of its path, which casts the votes, the decision of the call for one position and
-// the qualities of the bytes it emits.
+// vote_common.hpp — the device side of the pile-up votes, written once for read correction (correct_kernels.hip), the unitig consensus
+// (consensus_kernels.hip) and the variant sites (variant_kernels.hip): a view's item, the walk over the columns of its path, which casts
+// the votes, and the vote kernel over it; the workgroup scan of the lengths a call emits; the decision of the call for one position and
+// the qualities of the bytes it emits.  What a vote weighs is a compile-time policy (UnitWeight here, the weighted two in
+// weighted_vote.hpp); the host side of a table is vote_table.hpp.
 // The contract is the "read correction" section of include/mhap_hip.h; correct_kernels.hip describes the table's planes and the walk.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -65,21 +67,31 @@ inline bool path_spells_record(const mhap_record& r, const std::vector<uint32_t>
 
 __device__ inline int base_code(uint32_t c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1; }
 
-__device__ inline void vote(uint32_t* __restrict__ table, int64_t v_words, int tlen, int t, int counter) {
+// What a vote weighs, as a compile-time policy of the walk, the decision and the kernels: weigh(at) is the weight of the byte stored
+// at index `at` of the bases, `neutral` the weight of a vote that has no byte (Del, span) and with it the unit U every comparison of
+// the call is written in.  The unit policy is the unweighted contract: every vote 1, nothing loaded.  weighted_vote.hpp has the two of
+// the "quality-weighted votes".
+struct UnitWeight {
+  static constexpr int neutral = 1;
+  __device__ int operator()(int64_t) const { return 1; }
+};
+
+__device__ inline void vote(uint32_t* __restrict__ table, int64_t v_words, int tlen, int t, int counter, uint32_t w) {
   if ((unsigned)t >= (unsigned)tlen) return;   // (add validated the path: never taken)
-  atomicAdd(table + v_words + (int64_t)(counter >> 1) * tlen + t, (counter & 1) ? 0x10000u : 1u);
+  atomicAdd(table + v_words + (int64_t)(counter >> 1) * tlen + t, (counter & 1) ? w << 16 : w);
 }
 
 struct NoColumn { __device__ void operator()(bool, int, int) const {} };
 
 // The column walk of one view: every column of the path `it` names casts its vote.  One wave; the caller is a kernel of 64 threads.
-// The walk is written once, so its three switches are compile-time: INS false leaves the insertion slots out (a table of three planes,
-// "variant sites"), VOTE false casts no vote at all, and each(diag, i, j) is called for every column by every lane that has one (diag:
-// it is an '=' or 'X' column; lane 0 has a column whenever any lane has), which is what the variant judgement hangs its ballots on.
-// The defaults are the walk as the correction and the consensus use it.
-template <bool VOTE = true, bool INS = true, class Each = NoColumn>
+// The walk is written once, so its switches are compile-time: INS false leaves the insertion slots out (a table of three planes,
+// "variant sites"), VOTE false casts no vote at all, each(diag, i, j) is called for every column by every lane that has one (diag:
+// it is an '=' or 'X' column; lane 0 has a column whenever any lane has), which is what the variant judgement hangs its ballots on,
+// and weigh is the weight policy: an evidence byte votes with weigh(the index it is stored at), Del and span with Weigh::neutral.
+// The defaults are the walk as the unweighted correction and consensus use it.
+template <bool VOTE = true, bool INS = true, class Each = NoColumn, class Weigh = UnitWeight>
 __device__ inline void vote_walk(const uint8_t* __restrict__ bases, const VoteItem& it, const uint32_t* __restrict__ ops,
-                                 uint32_t* __restrict__ table, Each each = Each()) {
+                                 uint32_t* __restrict__ table, Each each = Each(), Weigh weigh = Weigh()) {
   __shared__ int s_col[65], s_i[64], s_j[64];
   __shared__ uint32_t s_op[64];
   const int lane = threadIdx.x;
@@ -121,20 +133,23 @@ __device__ inline void vote_walk(const uint8_t* __restrict__ bases, const VoteIt
       const bool consumes_target = diag || rcode == (target_b ? OP_D : OP_I);
       each(diag, i, j);
       if (!VOTE) continue;
+      // The stored index of the column's evidence byte; its quality, where there is one, lies at the same index.  The byte is
+      // complemented whenever the record is to_rc: view A reads s2 = rc(B), and view B is turned round.
+      const int64_t at = target_b ? it.a_off + i : it.b_off + (it.rc ? it.blen - 1 - j : j);
       if (consumes_target) {
         const int t = !target_b ? i : rev ? it.blen - 1 - j : j;
         if (diag) {
-          uint32_t e = target_b ? (uint32_t)bases[it.a_off + i]
-                                : (it.rc ? rc_char(bases[it.b_off + (it.blen - 1 - j)]) : (uint32_t)bases[it.b_off + j]);
-          if (rev) e = rc_char(e);
+          uint32_t e = bases[at];
+          const uint32_t wt = (uint32_t)weigh(at);
+          if (it.rc) e = rc_char(e);
           const int b = base_code(e);
-          if (b >= 0) vote(table, it.v_words, tlen, t, b);
+          if (b >= 0) vote(table, it.v_words, tlen, t, b, wt);
         } else {
-          vote(table, it.v_words, tlen, t, 4);
+          vote(table, it.v_words, tlen, t, 4, Weigh::neutral);
         }
         // the view continues past t unless this is its last column: the path's last, or its first in the reversed view
         const bool view_end = rev ? (ridx == 0 && c == 0) : (ridx == it.n_ops - 1 && c == rlen - 1);
-        if (!view_end) vote(table, it.v_words, tlen, t, 5);
+        if (!view_end) vote(table, it.v_words, tlen, t, 5, Weigh::neutral);
       } else if (INS) {
         // an Ins column: the group is this run (a run split at 2^28 - 1 columns continues a group whose first four slots are taken)
         const int k = rev ? rlen - 1 - c : c;
@@ -144,11 +159,11 @@ __device__ inline void vote_walk(const uint8_t* __restrict__ bases, const VoteIt
           if (!split) {
             // the target position before the group in the view's order: the row / column consumed last, or next in the reversed view
             const int t = !target_b ? s_i[lo] - 1 : rev ? it.blen - 1 - s_j[lo] : s_j[lo] - 1;
-            uint32_t e = target_b ? (uint32_t)bases[it.a_off + i]
-                                  : (it.rc ? rc_char(bases[it.b_off + (it.blen - 1 - j)]) : (uint32_t)bases[it.b_off + j]);
-            if (rev) e = rc_char(e);
+            uint32_t e = bases[at];
+            const uint32_t wt = (uint32_t)weigh(at);
+            if (it.rc) e = rc_char(e);
             const int b = base_code(e);
-            if (b >= 0) vote(table, it.v_words, tlen, t, 6 + 4 * k + b);
+            if (b >= 0) vote(table, it.v_words, tlen, t, 6 + 4 * k + b, wt);
           }
         }
       }
@@ -156,21 +171,56 @@ __device__ inline void vote_walk(const uint8_t* __restrict__ bases, const VoteIt
   }
 }
 
+namespace {
+
+// The vote kernel of the correction, the consensus and the variant sites: one wave per accepted view.
+template <bool INS, class Weigh>
+__global__ __launch_bounds__(64) void vote_kernel(const uint8_t* __restrict__ bases, const VoteItem* __restrict__ items,
+                                                  const uint32_t* __restrict__ ops, uint32_t* __restrict__ table, Weigh weigh) {
+  const VoteItem it = items[blockIdx.x];
+  vote_walk<true, INS>(bases, it, ops, table, NoColumn(), weigh);
+}
+
+}  // namespace
+
+// What every thread of a call kernel knows of the lengths the workgroup's CK_T threads emit: incl, the inclusive scan up to the
+// thread within its wave; before, the sum of the waves in front of it; tile, the sum of all.  The thread's first byte lies at
+// before + incl - n of the tile.  Two barriers; the first also says that every thread is done with the previous scan.
+struct EmitScan { int incl, before, tile; };
+
+__device__ inline EmitScan scan_emitted(int n) {
+  __shared__ int wave_sum[CK_T / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  EmitScan s{n, 0, 0};
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int u = __shfl_up(s.incl, d);
+    if (lane >= d) s.incl += u;
+  }
+  __syncthreads();   // wave_sum of the previous tile has been read
+  if (lane == 63) wave_sum[wave] = s.incl;
+  __syncthreads();
+  for (int u = 0; u < CK_T / 64; u++) { if (u < wave) s.before += wave_sum[u]; s.tile += wave_sum[u]; }
+  return s;
+}
+
 // the decision for one position: the bytes it emits (at most 1 + CK_KI) and what it counts
 struct Decision { int n; uint8_t bytes[1 + CK_KI]; int sub, del, ins, low; };
 
-__device__ inline Decision decide(const uint32_t* __restrict__ w, int64_t len, int64_t t, uint32_t own, int min_cov) {
+// U: the unit the counters are in, 1 or the weighted contract's neutral 2; own_w: the weight of the own byte.  min_cov is in votes.
+template <int U>
+__device__ inline Decision decide(const uint32_t* __restrict__ w, int64_t len, int64_t t, uint32_t own, int own_w, int min_cov) {
   Decision D{0, {0, 0, 0, 0, 0}, 0, 0, 0, 0};
   const uint32_t w0 = w[t], w1 = w[len + t], w2 = w[2 * len + t];
   int base[4] = {(int)(w0 & 0xFFFFu), (int)(w0 >> 16), (int)(w1 & 0xFFFFu), (int)(w1 >> 16)};
   const int del = (int)(w2 & 0xFFFFu), span = (int)(w2 >> 16);
   const int d = base[0] + base[1] + base[2] + base[3] + del;
-  if (d < min_cov) {
+  if (d < U * min_cov) {
     D.bytes[D.n++] = (uint8_t)own; D.low = 1;
   } else {
     const int ob = base_code(own);
-    if (ob >= 0) base[ob] += 1;
-    const int total = d + 1;
+    if (ob >= 0) base[ob] += own_w;
+    const int total = d + own_w;
     if (2 * del > total) D.del = 1;
     else {
       int best = 0;
@@ -182,13 +232,13 @@ __device__ inline Decision decide(const uint32_t* __restrict__ w, int64_t len, i
       D.sub = out != own;
     }
   }
-  if (t < len - 1 && span >= min_cov) {
+  if (t < len - 1 && span >= U * min_cov) {
     for (int k = 0; k < CK_KI; k++) {
       const uint32_t x0 = w[(3 + 2 * k) * len + t], x1 = w[(4 + 2 * k) * len + t];
       const int v[4] = {(int)(x0 & 0xFFFFu), (int)(x0 >> 16), (int)(x1 & 0xFFFFu), (int)(x1 >> 16)};
       int best = 0;
       for (int b = 1; b < 4; b++) if (v[b] > v[best]) best = b;
-      if (2 * v[best] <= span + 1) break;
+      if (2 * v[best] <= span + U) break;
       D.bytes[D.n++] = (uint8_t)((0x54474341u >> (8 * best)) & 0xFFu);
       D.ins += 1;
     }
@@ -196,8 +246,9 @@ __device__ inline Decision decide(const uint32_t* __restrict__ w, int64_t len, i
   return D;
 }
 
-// Base qualities ("base qualities" in include/mhap_hip.h): one byte 0 .. cap per byte of D = decide(w, len, t, own, min_cov), from the
-// same counters, in integers.  Q(m) = min(cap, per_vote * max(m, 0) / 10) of the margin m between the votes for the byte and the rest.
+// Base qualities ("base qualities" in include/mhap_hip.h): one byte 0 .. cap per byte of D = decide<U>(w, len, t, own, own_w, min_cov),
+// from the same counters, in integers.  Q(m) = min(cap, per_vote * max(m, 0) / (10 U)) of the margin m, in units of U, between the
+// votes for the byte and the rest.
 constexpr int QUAL_BINS = 94;   // Phred 0 .. 93, what FASTQ can print
 
 // the check of both quality entry points: per_vote 1 .. 1000, cap 1 .. 93
@@ -207,14 +258,16 @@ inline bool quality_params_ok(int per_vote, int cap, const char* who, std::strin
   return false;
 }
 
+template <int U>
 __device__ inline int quality_of(int m, int per_vote, int cap) {
   if (m <= 0) return 0;
-  const int64_t q = (int64_t)per_vote * m / 10;
+  const int64_t q = (int64_t)per_vote * m / (10 * U);
   return q < cap ? (int)q : cap;
 }
 
-__device__ inline void decide_quality(const uint32_t* __restrict__ w, int64_t len, int64_t t, uint32_t own, const Decision& D, int per_vote,
-                                      int cap, uint8_t* __restrict__ q) {
+template <int U>
+__device__ inline void decide_quality(const uint32_t* __restrict__ w, int64_t len, int64_t t, uint32_t own, int own_w, const Decision& D,
+                                      int per_vote, int cap, uint8_t* __restrict__ q) {
   if (D.n == 0) return;   // a called deletion without an insertion: no byte, no quality
   const uint32_t w0 = w[t], w1 = w[len + t], w2 = w[2 * len + t];
   const int base[4] = {(int)(w0 & 0xFFFFu), (int)(w0 >> 16), (int)(w1 & 0xFFFFu), (int)(w1 >> 16)};
@@ -225,15 +278,15 @@ __device__ inline void decide_quality(const uint32_t* __restrict__ w, int64_t le
   if (n_base) {
     const int e = base_code(D.bytes[0]);
     if (e < 0) fixed = true;
-    else m_last = 2 * (base[e] + (own == D.bytes[0] ? 1 : 0)) - (base[0] + base[1] + base[2] + base[3] + del + 1);
-    q[0] = (uint8_t)(fixed ? 0 : quality_of(m_last, per_vote, cap));
+    else m_last = 2 * (base[e] + (own == D.bytes[0] ? own_w : 0)) - (base[0] + base[1] + base[2] + base[3] + del + own_w);
+    q[0] = (uint8_t)(fixed ? 0 : quality_of<U>(m_last, per_vote, cap));
   }
   for (int k = 0; k < D.ins; k++) {
     const int e = base_code(D.bytes[n_base + k]);   // (decide emits A, C, G or T here)
     const uint32_t x = w[(3 + 2 * k + (e >> 1)) * len + t];
-    m_last = 2 * (int)((e & 1) ? x >> 16 : x & 0xFFFFu) - (span + 1);
+    m_last = 2 * (int)((e & 1) ? x >> 16 : x & 0xFFFFu) - (span + U);
     fixed = false;
-    q[n_base + k] = (uint8_t)quality_of(m_last, per_vote, cap);
+    q[n_base + k] = (uint8_t)quality_of<U>(m_last, per_vote, cap);
   }
   // the last byte also answers for the junction not going on
   if (t < len - 1 && D.ins < CK_KI && !fixed) {
@@ -242,8 +295,8 @@ __device__ inline void decide_quality(const uint32_t* __restrict__ w, int64_t le
     if ((int)(x0 >> 16) > top) top = (int)(x0 >> 16);
     if ((int)(x1 & 0xFFFFu) > top) top = (int)(x1 & 0xFFFFu);
     if ((int)(x1 >> 16) > top) top = (int)(x1 >> 16);
-    const int m_stop = span + 1 - 2 * top;
-    if (m_stop < m_last) q[D.n - 1] = (uint8_t)quality_of(m_stop, per_vote, cap);
+    const int m_stop = span + U - 2 * top;
+    if (m_stop < m_last) q[D.n - 1] = (uint8_t)quality_of<U>(m_stop, per_vote, cap);
   }
 }
 
