@@ -416,7 +416,10 @@ int mhap_group_add_scan(mhap_group* g, const mhap_fasta_scan* s);
 int mhap_group_find_matches_self(mhap_group* g, mhap_record_sink sink, void* user);
 int mhap_group_find_matches_reads(mhap_group* g, const char* bases, const int64_t* offsets, const int32_t* lengths, const int64_t* ids,
                                   int64_t n, mhap_record_sink sink, void* user);
-int mhap_group_get_stats(mhap_group* g, mhap_stats* sum);           /* counters summed over the ranks */
+/* counters summed over the ranks, except queries_searched: that sum divided by N.  The division is exact: every rank probes every
+ * gathered row that carries a sketch, and no rank counts a padding row or an unsketched read.  candidates_compared and table_elements
+ * add up to what one index of all the reads counts (a stored strand and its postings are on exactly one rank). */
+int mhap_group_get_stats(mhap_group* g, mhap_stats* sum);
 
 int mhap_get_stats(mhap_handle* h, mhap_stats* out);
 int mhap_get_kernel_times(mhap_handle* h, mhap_kernel_times* out);

@@ -941,10 +941,10 @@ int mhap_group_add_scan(mhap_group* g, const mhap_fasta_scan* s) {
   const int64_t first = g->reads_added;
   const int rc = on_ranks(g, [&](int r) {
     const int64_t i0 = ((r - first) % N + N) % N;          // rank r takes the records whose ordinal in the data set is congruent to r
-    if (i0 >= n) {
-      if (dist_eager_wanted(g->h[(size_t)r])) { const int rx = dist_eager_begin(g->h[(size_t)r], 0, nullptr, false); return rx < 0 ? rx : (int)MHAP_OK; }
-      return (int)MHAP_OK;
-    }
+    // (no record for this rank: with the eager exchange on it still makes the rendezvous its peers make.  Theirs is the ingest plan's
+    //  (dist_ingest_scope inside ingest_add_subset), not the add's as in mhap_group_add_reads: the empty subset announces 0 groups there,
+    //  which suspends the eager exchange on every rank for this ingest, and no add makes a rendezvous)
+    if (i0 >= n) return ingest_add_subset(g->h[(size_t)r], scan_impl(s), i0, N);
     int64_t entries = 0;
     (void)mhap_index_size(g->h[(size_t)r], &entries);
     if (entries == 0) { const int rr = mhap_index_reserve(g->h[(size_t)r], (n - i0 + N - 1) / N); if (rr != MHAP_OK) return rr; }
