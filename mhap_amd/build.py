@@ -16,8 +16,8 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libmhaphip.so")
 CLI = os.path.join(LIBDIR, "mhap-hip")
 KMERS_CLI = os.path.join(LIBDIR, "mhap-hip-kmers")   # the -f filter file from the reads (mhap_kmers_cli.cpp)
-SOURCES = ["sketch_kernels.hip", "search_kernels.hip", "join_kernels.hip", "mhap_capi.hip", "mhap_dist.hip", "mhap_ingest.hip", "kmer_kernels.hip", "align_kernels.hip", "realign_kernels.hip", "correct_kernels.hip", "graph_kernels.hip", "consensus_kernels.hip", "trim_kernels.hip", "repeat_kernels.hip", "variant_kernels.hip", "select_kernels.hip", "ksim_kernels.hip", "hpc_kernels.hip", "hpc_host.cpp", "fastq_host.cpp", "host_util.cpp"]
-HEADERS = ["align_common.hpp", "device_common.hpp", "graph_class.hpp", "trim_common.hpp", "read_table.hpp", "pileup_common.hpp", "select_common.hpp", "vote_common.hpp", "vote_table.hpp", "weighted_vote.hpp", "hpc_common.hpp", "fastq_host.hpp", "kernels.hpp", "capi_switches.hpp", "sketch_plan.hpp", "mhap_internal.hpp", "overlap_lane.hpp", os.path.join("..", "..", "include", "mhap_hip.h")]
+SOURCES = ["sketch_kernels.hip", "search_kernels.hip", "join_kernels.hip", "mhap_capi.hip", "mhap_dist.hip", "mhap_ingest.hip", "kmer_kernels.hip", "align_kernels.hip", "realign_kernels.hip", "correct_kernels.hip", "graph_kernels.hip", "unitig_kernels.hip", "consensus_kernels.hip", "trim_kernels.hip", "repeat_kernels.hip", "variant_kernels.hip", "select_kernels.hip", "ksim_kernels.hip", "hpc_kernels.hip", "hpc_host.cpp", "fastq_host.cpp", "host_util.cpp"]
+HEADERS = ["align_common.hpp", "device_common.hpp", "graph_class.hpp", "graph_session.hpp", "trim_common.hpp", "read_table.hpp", "pileup_common.hpp", "select_common.hpp", "vote_common.hpp", "vote_table.hpp", "weighted_vote.hpp", "hpc_common.hpp", "fastq_host.hpp", "kernels.hpp", "capi_switches.hpp", "sketch_plan.hpp", "mhap_internal.hpp", "overlap_lane.hpp", os.path.join("..", "..", "include", "mhap_hip.h")]
 ARCH = "gfx950"
 
 

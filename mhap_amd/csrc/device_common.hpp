@@ -226,7 +226,7 @@ __device__ inline uint32_t strand_char(const uint8_t* __restrict__ store, const 
   return (0x54474341u >> (8 * code)) & 0xFFu;  // "ACGT"
 }
 
-// (graph_kernels.hip and repeat_kernels.hip)  start[0 .. n] = the exclusive prefix sums of deg[0 .. n): one workgroup, 1024 values at a time with a carry
+// (graph_kernels.hip, unitig_kernels.hip and repeat_kernels.hip)  start[0 .. n] = the exclusive prefix sums of deg[0 .. n): one workgroup, 1024 values at a time with a carry
 template <class T>
 __global__ __launch_bounds__(1024) void scan_kernel(const T* __restrict__ deg, int64_t n, int64_t* __restrict__ start) {
   __shared__ int64_t wave_sum[16];

@@ -76,6 +76,14 @@ struct DevBuf {
   template <class T> T* as() const { return (T*)p; }
 };
 
+// A DevBuf of T: the element type is said once, where the buffer is declared, and sizes are counted in elements.
+template <class T>
+struct Dev {
+  DevBuf b;
+  T* get() const { return (T*)b.p; }
+  hipError_t ensure(size_t n) { return b.ensure(n * sizeof(T)); }
+  void release() { b.release(); }
+};
 
 // The parts of a handle the multi-GPU exchange reads: the rank's own tables (entry 2j / 2j+1 = forward / reverse strand of its
 // j-th read) and the host mirrors of ids and strands.  `dist` is an opaque slot owned by mhap_dist.hip (freed by mhap_destroy

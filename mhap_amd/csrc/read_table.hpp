@@ -2,7 +2,8 @@
 // table (ids, lengths, the lengths on the device), a record's two reads looked up and checked against it, the record packed as the
 // 32-byte item the kernels read, the uploads an add has queued, and the begin / apply / free that "read trimming"
 // (trim_kernels.hip), "repeat marking" (repeat_kernels.hip) and "overlap selection" (select_kernels.hip) share.  The string graph's
-// session (graph_kernels.hip) sits on the table too, and the unitig consensus looks its reads up through that session; the read
+// session (graph_session.hpp; its calls are in graph_kernels.hip and unitig_kernels.hip) begins, frees and queues its steps through
+// the same skeleton, and the unitig consensus looks its reads up through that session; the read
 // correction (correct_kernels.hip) and the variant sites (variant_kernels.hip), which keep the bases and a vote table, sit on
 // vote_table.hpp's VoteTable and share the lookup.
 //
@@ -75,6 +76,7 @@ struct ReadTable {
   struct Pending { std::vector<GItem> host; hipEvent_t ev = nullptr; };   // packed records an upload may still be reading
   std::deque<Pending> pending;
   DevBuf d_lengths, items;
+  static constexpr bool any_length = false;   // a session that sets it takes every length >= 0 (the graph: nothing indexes a base)
 
   void reap(bool all) {
     while (!pending.empty() && (all || hipEventQuery(pending.front().ev) == hipSuccess)) {
@@ -88,12 +90,13 @@ struct ReadTable {
   }
 
   // the arguments every begin refuses; false with the handle's message set
-  static bool table_ok(const HandleView& v, const char* who, const void* session, const int64_t* read_ids, const int32_t* lens, int64_t n) {
+  static bool table_ok(const HandleView& v, const char* who, const void* session, const int64_t* read_ids, const int32_t* lens, int64_t n,
+                       bool any_len = false) {
     if (!session || n < 0 || (n > 0 && (!read_ids || !lens))) { *v.err = std::string(who) + ": null or negative argument"; return false; }
     if (n >= ((int64_t)1 << 30)) { *v.err = std::string(who) + ": 2^30 reads or more"; return false; }
     for (int64_t i = 0; i < n; i++)
-      if (lens[i] < 0 || lens[i] > INT32_MAX - 8) {
-        *v.err = std::string(who) + ": read " + std::to_string(i) + " has a negative length or one above 2^31 - 9";
+      if (lens[i] < 0 || (!any_len && lens[i] > INT32_MAX - 8)) {
+        *v.err = std::string(who) + ": read " + std::to_string(i) + (any_len ? " has a negative length" : " has a negative length or one above 2^31 - 9");
         return false;
       }
     return true;
@@ -115,12 +118,13 @@ struct ReadTable {
     return find_record_reads(by_id, lengths.data(), who, q, r, idx, err);
   }
   // the records of a call as items for the sessions whose kernels index a read by a record's aligned ends: record by record, the
-  // lookup and then range_ok; a refused record leaves its message in err
-  bool pack_records(const char* who, const mhap_record* recs, int64_t n, std::vector<GItem>& out, std::string& err) const {
+  // lookup and then range_ok (`ranges` false: the lookup alone, for the graph and the consensus, where a record's aligned ends
+  // index nothing); a refused record leaves its message in err
+  bool pack_records(const char* who, const mhap_record* recs, int64_t n, std::vector<GItem>& out, std::string& err, bool ranges = true) const {
     out.resize((size_t)n);
     for (int64_t q = 0; q < n; q++) {
       int32_t idx[2];
-      if (!find_reads(who, q, recs[q], idx, err) || !range_ok(who, q, recs[q], err)) return false;
+      if (!find_reads(who, q, recs[q], idx, err) || (ranges && !range_ok(who, q, recs[q], err))) return false;
       out[(size_t)q] = pack_item(idx, recs[q]);
     }
     return true;
@@ -191,15 +195,33 @@ struct ReadTable {
 // S sits on ReadTable and has: `finished` (a finish has completed), `finish_name` and `unfinished_rc` (the entry point a call before
 // it is told of, and the code it gets), and release().
 
-// One step of a begin's queue: nothing runs once a step has failed.
+struct Copy { void* dst; const void* src; size_t bytes; };   // one download
+
+// The steps a call queues: nothing runs once a step has failed, and `what` keeps the kind of step that did, as hip_fail names it.
+// The caller looks at ok() before it launches kernels, which are no steps; launched() looks at them afterwards.
 struct Steps {
   hipError_t e;
   hipStream_t stream;
-  void ensure(DevBuf& b, size_t bytes) { if (e == hipSuccess) e = b.ensure(bytes); }
-  void zero(DevBuf& b, size_t bytes) { if (e == hipSuccess) e = hipMemsetAsync(b.p, 0, bytes, stream); }
+  const char* what = "";
+  bool ok() const { return e == hipSuccess; }
+  int fail(const HandleView& v, const char* who) const { return hip_fail(v, who, what, e); }
+  void step(const char* w, hipError_t r) { e = r; if (r != hipSuccess) what = w; }   // (behind an ok())
+  void ensure(DevBuf& b, size_t bytes, const char* w = "hipMalloc") { if (ok()) step(w, b.ensure(bytes)); }
+  template <class T> void ensure(Dev<T>& b, size_t n, const char* w = "hipMalloc") { ensure(b.b, n * sizeof(T), w); }
+  template <class... B> void ensure_all(const char* w, size_t n, B&... b) { (ensure(b, n, w), ...); }   // n elements each
+  void fill(void* p, int byte, size_t bytes) { if (ok()) step("memset", hipMemsetAsync(p, byte, bytes, stream)); }
+  void zero(DevBuf& b, size_t bytes) { fill(b.p, 0, bytes); }
+  template <class T> void zero(Dev<T>& b, size_t n) { fill(b.b.p, 0, n * sizeof(T)); }
+  void upload(void* dst, const void* src, size_t bytes) { if (ok()) step("upload", hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream)); }
+  void launched() { if (ok()) step("launch", hipGetLastError()); }
+  // these few values, and the one wait for them
+  void fetch(std::initializer_list<Copy> cs) {
+    for (const Copy& c : cs) if (ok()) step("download", hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, stream));
+    if (ok()) step("kernel", hipStreamSynchronize(stream));
+  }
 };
 
-// begin: the arguments and the parameters checked (`rule`: what a refused set of parameters is told), the session made, `setup`
+// begin: the arguments (the lengths by S::any_length) and the parameters checked (`rule`: what a refused set of parameters is told), the session made, `setup`
 // fills its fields from the parameters and queues the table and the session's own buffers (hipError_t setup(S&, const Params&,
 // const HandleView&)), and the one wait.
 template <class S, class Params, class Setup>
@@ -208,7 +230,7 @@ int session_begin(const char* who, mhap_handle* h, const int64_t* read_ids, cons
   if (session) *session = nullptr;
   if (!h) return MHAP_E_INVALID;
   HandleView v = handle_view(h);
-  if (!ReadTable::table_ok(v, who, session, read_ids, lengths, n_reads)) return MHAP_E_INVALID;
+  if (!ReadTable::table_ok(v, who, session, read_ids, lengths, n_reads, S::any_length)) return MHAP_E_INVALID;
   Params p;
   defaults(&p);
   if (params) p = *params;
@@ -253,13 +275,10 @@ int apply_begin(S* s, const HandleView& v, const char* who, const mhap_record* i
   return MHAP_OK;
 }
 inline int apply_end(const HandleView& v, const char* who, void* dst, const DevBuf& out, size_t bytes) {
-  hipError_t e;
-  if ((e = hipGetLastError()) != hipSuccess) { (void)hipStreamSynchronize(v.stream); return hip_fail(v, who, "launch", e); }
-  if ((e = hipMemcpyAsync(dst, out.p, bytes, hipMemcpyDeviceToHost, v.stream)) != hipSuccess) {
-    (void)hipStreamSynchronize(v.stream);
-    return hip_fail(v, who, "download", e);
-  }
-  if ((e = hipStreamSynchronize(v.stream)) != hipSuccess) return hip_fail(v, who, "kernel", e);
+  Steps q{hipSuccess, v.stream};
+  q.launched();
+  q.fetch({{dst, out.p, bytes}});
+  if (!q.ok()) { (void)hipStreamSynchronize(v.stream); return q.fail(v, who); }
   return MHAP_OK;
 }
 

@@ -1,4 +1,4 @@
-"""Graph cleaning on the GPU (mhap_graph_clean / _copy_dropped / _copy_removed, graph_kernels.hip) against its CPU restatement
+"""Graph cleaning on the GPU (mhap_graph_clean / _copy_dropped / _copy_removed, unitig_kernels.hip) against its CPU restatement
 (tests/graph_clean_ref.py over unitig_ref.py and string_graph_ref.py), exactly: the dropped and removed bytes, the counts, every table
 of the cleaned unitigs, their spelled sequences and both GFA texts; then `mhap-hip --realign --gfa --gfa-unitigs --gfa-clean` against
 `python -m mhap_amd.graph --clean` and against the genome its reads were drawn from.  The shapes are those of test_graph_clean_cpu.py,

@@ -1,7 +1,9 @@
 """The string graph on the GPU (mhap_graph_*, graph_kernels.hip) against its CPU restatement (tests/string_graph_ref.py): the class of
 every record, the contained flag of every read, the whole arc table except the q labels, the counts and the GFA text, exactly; then
 `mhap-hip --realign --gfa` against `python -m mhap_amd.graph` end to end.  The records are fabricated from reads placed on a line:
-no bases and no alignment are needed."""
+no bases and no alignment are needed.  Two tests take one session through every call of the stage (the unitigs, their spelling and
+the cleaning are unitig_kernels.hip's, over the session of graph_session.hpp): twice over with more records in between, and on
+tables of no, one and two reads."""
 import os
 import subprocess
 import sys
@@ -14,7 +16,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import mhap_amd  # noqa: E402
+import graph_clean_ref as cr  # noqa: E402
 import string_graph_ref as sg  # noqa: E402
+import unitig_ref as ur  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -332,6 +336,151 @@ def test_read_counts_at_the_edge_of_a_scan_tile(n_reads):
         b = _compare(gs, ref, recs)
     assert a[0].tolist() == b[0].tolist() and a[1] == b[1] and a[3] == b[3]
     assert a[1]["arcs"] == 6 and int(a[0][:, 0].max()) == 2 * n_reads - 1
+
+
+# ---- the whole session: every group of buffers made, grown, reset and released ---------------------------------------------------------
+
+UNITIG_TABLES = ("unitig_start", "unitig_len", "circular", "vertex", "offset", "span", "links")
+
+
+def _same_unitigs(got, exp):
+    for k in UNITIG_TABLES:
+        assert got[k].dtype == exp[k].dtype and got[k].shape == exp[k].shape, (k, got[k].shape, exp[k].shape)
+        assert np.array_equal(got[k], exp[k]), k
+    assert got["counts"] == exp["counts"]
+
+
+def _spelled(gs, u, bases, offsets):
+    out = np.full(u["counts"]["total_bases"], 1, np.uint8)      # (1: a byte no read holds)
+    return gs.spell_into(bases, offsets, out).tobytes()
+
+
+def _life(gs, ref, recs_in_order, bases, offsets):
+    """finish, unitigs, spell, clean and spell on the session and on the restatement alike, every table and count vector compared
+    (string_graph_ref, unitig_ref, graph_clean_ref); returns all of it as a list."""
+    gs.finish()
+    ref.finish()
+    arcs, counts, contained, _ = _compare(gs, ref, recs_in_order)
+    want_u = ur.of_graph(ref)
+    u = gs.unitigs()
+    _same_unitigs(u, want_u.tables())
+    seq = _spelled(gs, u, bases, offsets)
+    assert seq == b"".join(want_u.sequences(bases, offsets, ref.lengths))
+    want = cr.Cleaned(ref)
+    ccounts = gs.clean()
+    assert ccounts == want.counts
+    dropped, removed = gs.dropped(), gs.removed()
+    assert dropped.tolist() == want.dropped and removed.tolist() == want.removed
+    c = gs.cleaned_unitigs()
+    _same_unitigs(c, want.unitigs.tables())
+    assert gs.unitigs_info() == (len(c["unitig_len"]), len(c["vertex"]), len(c["links"]), c["counts"]["total_bases"])
+    cseq = _spelled(gs, c, bases, offsets)
+    assert cseq == b"".join(want.unitigs.sequences(bases, offsets, ref.lengths))
+    return [arcs, counts, gs.classes(), contained, u, seq, ccounts, dropped, removed, c, cseq]
+
+
+def _same_life(a, b):
+    for x, y in zip(a, b):
+        if isinstance(x, dict) and "vertex" in x:
+            _same_unitigs(x, y)
+        elif isinstance(x, np.ndarray):
+            assert x.shape == y.shape and (sg.strip_q(x) == sg.strip_q(y) if x.ndim == 2 else np.array_equal(x, y))
+        else:
+            assert x == y
+
+
+def _placed_anew(ids, lengths, seed, genome, share=2500):
+    """The same reads placed on another line, and of that placement's records (sg.placed, at least `share` positions shared) the
+    dovetails only: arcs that contradict the first layout, so forks, links and unitigs, and no new contained read."""
+    rng = np.random.default_rng(seed)
+    reads = []
+    for ln in lengths:
+        s = int(rng.integers(0, genome - ln + 1))
+        reads.append((s, s + ln, int(rng.integers(0, 2))))
+    recs = np.concatenate([sg.placed(ids[i], ids[j], reads[i], reads[j]) for i in range(len(ids)) for j in range(i + 1, len(ids))
+                           if min(reads[i][1], reads[j][1]) - max(reads[i][0], reads[j][0]) >= share])
+    g = sg.Graph(ids, lengths)
+    g.add(recs)
+    return recs[np.array(g.classes) == sg.DOVETAIL]
+
+
+def test_one_session_two_lives():
+    """finish -> unitigs -> clean -> spell, more records, the refusals that must hold until the next finish, and the sequence again:
+    the second life's tables are those of a fresh session given both batches at once, and of the restatement.  40 reads; the first
+    batch is their layout and a few contradicting dovetails (259 records: 122 arcs; served after the clean 10 unitigs, 17 members, 26
+    links, six reads dropped), the second 86 more dovetails (198 arcs; 20 unitigs, 22 members, 72 links, one other read dropped), so
+    the arc list, the link table, the removed bytes and the spelled bases outgrow the first life's buffers and the dropped bytes
+    must start from zero again.  (The uncleaned member count cannot rise over one read table: every read that is not contained is
+    a member of one unitig and an add only contains more reads.  It is the served, cleaned count that rises, 17 to 22.)"""
+    ids, lengths, reads, recs = sg.layout(5, n_reads=40, genome=40000, jitter=300)
+    _, bases, offsets = ur.plant(reads, 5, 40000)
+    first = np.concatenate([recs, _placed_anew(ids, lengths, 202, 160000)])
+    second = _placed_anew(ids, lengths, 300, 60000)
+    both = np.concatenate([first, second])
+    ref = sg.Graph(ids, lengths)
+    with mhap_amd.GraphSession(ids, lengths) as gs:
+        gs.add(first)
+        ref.add(first)
+        one = _life(gs, ref, first, bases, offsets)
+        assert 200 < len(first) < 400 and one[7].any()
+        gs.add(second)
+        ref.add(second)
+        for call in (gs.unitigs, gs.clean):
+            with pytest.raises(mhap_amd.MhapError, match="records were added after the last mhap_graph_finish"):
+                call()
+        gs.finish()
+        assert gs.unitigs_info()[0] == -1
+        with pytest.raises(mhap_amd.MhapError, match="mhap_graph_copy_unitigs: no mhap_graph_unitigs has completed since the last mhap_graph_finish"):
+            gs._ms._chk(gs._lib.mhap_graph_copy_unitigs(gs._s, None, None, None))
+        with pytest.raises(mhap_amd.MhapError, match="mhap_graph_copy_layout: no mhap_graph_unitigs has completed"):
+            gs._ms._chk(gs._lib.mhap_graph_copy_layout(gs._s, None, None, None))
+        with pytest.raises(mhap_amd.MhapError, match="mhap_graph_copy_links: no mhap_graph_unitigs has completed"):
+            gs._ms._chk(gs._lib.mhap_graph_copy_links(gs._s, None))
+        with pytest.raises(mhap_amd.MhapError, match="mhap_graph_spell: no mhap_graph_unitigs has completed"):
+            gs.spell_into(bases, offsets, np.zeros(10, np.uint8))
+        with pytest.raises(mhap_amd.MhapError, match="mhap_graph_copy_dropped: no mhap_graph_clean has completed since the last mhap_graph_finish"):
+            gs.dropped()
+        gs.unitigs()
+        with pytest.raises(mhap_amd.MhapError, match="mhap_graph_copy_dropped: no mhap_graph_clean has completed"):
+            gs.dropped()
+        two = _life(gs, ref, both, bases, offsets)
+    for k, name in ((0, None), (4, "unitig_len"), (4, "links"), (9, "unitig_len"), (9, "vertex"), (9, "links"), (8, None)):
+        a, b = (one[k], two[k]) if name is None else (one[k][name], two[k][name])
+        assert len(b) > len(a), (k, name, len(a), len(b))                           # every one of them had to grow
+    assert len(two[10]) > len(one[10]) and two[7].tolist() != one[7].tolist()
+    fresh_ref = sg.Graph(ids, lengths)
+    with mhap_amd.GraphSession(ids, lengths) as gs:
+        gs.add(both)
+        fresh_ref.add(both)
+        _same_life(two, _life(gs, fresh_ref, both, bases, offsets))
+
+
+@pytest.mark.parametrize("n_reads", [0, 1, 2])
+def test_empty_and_degenerate_sessions(n_reads):
+    """No read; one read and no record; two reads whose only record is a containment: no arc, the contained read on no unitig, the
+    other a unitig of one read without links.  Every call of the session, twice closed."""
+    ids, lengths = list(range(1, n_reads + 1)), [10000, 4000][:n_reads]
+    recs = sg.placed(1, 2, (0, 10000, 0), (3000, 7000, 1)) if n_reads == 2 else np.zeros(0, sg.RECORD_DTYPE)
+    bases, offsets = ur.random_bases(lengths, 9)
+    ref = sg.Graph(ids, lengths)
+    gs = mhap_amd.GraphSession(ids, lengths)
+    gs.add(recs)
+    ref.add(recs)
+    life = _life(gs, ref, recs, bases, offsets)
+    arcs, counts, classes, contained, u, seq, ccounts, dropped, removed, c, cseq = life
+    assert len(arcs) == 0 and counts["arcs"] == 0 and classes.tolist() == [sg.B_CONTAINED][:len(recs)] and contained.tolist() == [0, 1][:n_reads]
+    assert gs.info() == (n_reads, len(recs), 0)
+    assert u["unitig_start"].tolist() == [0, 1][:min(n_reads, 1) + 1] and u["unitig_len"].tolist() == [10000][:n_reads] and len(u["links"]) == 0
+    assert u["vertex"].tolist() == [0][:n_reads] and seq == bytes(bases[:10000 * min(n_reads, 1)])
+    _same_unitigs(c, u)
+    assert cseq == seq and ccounts["rounds"] == 1 and not dropped.any() and len(removed) == 0
+    assert gs.gfa() == ref.gfa() and gs.gfa(cleaned=True) == ref.gfa()
+    gs._ms._chk(gs._lib.mhap_graph_copy_arcs(gs._s, None))                          # nothing to copy: no pointer is looked at
+    gs._ms._chk(gs._lib.mhap_graph_copy_links(gs._s, None))
+    gs._ms._chk(gs._lib.mhap_graph_copy_removed(gs._s, None))
+    _same_life(life, _life(gs, ref, recs, bases, offsets))                          # and the whole sequence again
+    gs.close()
+    gs.close()
 
 
 # ---- end to end ----------------------------------------------------------------------------------------------------------------------

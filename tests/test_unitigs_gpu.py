@@ -1,4 +1,4 @@
-"""The unitigs on the GPU (mhap_graph_unitigs / _copy_* / _spell, graph_kernels.hip) against their CPU restatement
+"""The unitigs on the GPU (mhap_graph_unitigs / _copy_* / _spell, unitig_kernels.hip) against their CPU restatement
 (tests/unitig_ref.py over tests/string_graph_ref.py): every array, the counts, the link rows, the sequences and the GFA text, exactly;
 then `mhap-hip --realign --gfa --gfa-unitigs` against the genome its reads were drawn from and against `python -m mhap_amd.graph
 --unitigs`.  The graphs are fabricated from reads placed on a line and from hand-made dovetails."""
